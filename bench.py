@@ -21,7 +21,14 @@ holds the whole alignment and computes its row panels (fold pairing), RCCL all-g
 the values allow), P and E(K) re-derived from the gathered d on every rank.  Strong scaling either way: the problem is fixed,
 `value` = total pairs / time (max over ranks, barrier + synchronize on both sides).
 
-Prints ONE JSON line (rank 0):
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: set-up, one untimed first call, --warmup steps,
+--steps timed steps, the line -- metric, value (pairs/s over the timed steps), unit, higher_is_better, dtype, ms_per_step (one timed
+step), n_gpus, steps, warmup and a short config.  --dump-outputs DIR writes, after the timed steps, the last step's d, compared sites,
+P(direct) and E(K) at a fixed, seeded sample of the pairs (dump_sample; every pair where there are fewer) as DIR/<name>.npy in float64:
+pair_i, pair_j, d, nn, p_direct, expected_k.  The inputs depend on the arguments only, so two builds can be compared output for output.
+--full adds everything else, each measured by runs of its own after the timed steps:
+  single_pass       one call on a freshly packed alignment, cold (the untimed first call) and warm (a second handle)
+  value_steady_state  --steps more passes over the alignment as it stands, nothing rebuilt
   roofline          the dominant kernel of the timed region from HIP events on the launch stream (recorded by the library around
                     each part of a dense call).  With site classes in use (the default on this workload, csrc/site_classes.hip) a call
                     is: the four-operand pair kernel over the dense sites (matrix cores), the minority lists' kernel, the one-operand
@@ -36,8 +43,9 @@ Prints ONE JSON line (rank 0):
                     "counts->posterior->code fused front-end"), timed separately (N = 1 only)
   cpu_baseline      the oracle (CPU port of the reference algorithm) on the host cores on a bounded sample of the same
                     workload, pair loop and trans_dist legs reported separately, the trans_dist leg also through the reference's
-                    own source compiled in place (oracle/_ref) (rank 0, every N); its sample block doubles as the ALWAYS-ON
-                    result check: the GPU's d / nn of those pairs -- at N > 1: rows rank 0 owns after the exchange -- must be bit-equal
+                    own source compiled in place (oracle/_ref) (rank 0, every N); its sample block doubles as the result check of
+                    every --full run (--no-cpu-baseline: the check alone): the GPU's d / nn of those pairs -- at N > 1: rows rank 0
+                    owns after the exchange -- must be bit-equal
 """
 import argparse
 import json
@@ -67,6 +75,8 @@ COUNT_FLOP_PER_SITE = 2.0    # the counting pass over invariant sites (site clas
 MU = 1e-4                    # per-sample substitution probability
 P_N = 0.01
 P_PARTIAL_C4 = 0.005         # SURVEY.md 8d, config 4 mix: partial-ambiguity IUPAC codes
+DUMP_PAIRS = 1 << 20         # --dump-outputs: cells (i < j) sampled; six float64 arrays of this length = 48 MB at most
+DUMP_SEED = 20241022
 
 
 def parse():
@@ -84,8 +94,14 @@ def parse():
                     help="N > 1: `sites` -- every rank holds a slice of the SITES and counts all pairs over it, the sums arrive as row panels "
                          "(reduce-scatter): every stage of a call shrinks with N; `pairs` -- every rank holds the whole alignment and computes "
                          "its row panels (all-gather): what is built once per pack is repeated on every rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline_general and dm_frontend")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: single_pass, the steady-state pass, roofline, sensitivity, filter, roofline_general, "
+                         "dm_frontend, cpu_baseline with its oracle check (off: set up, warm up, time --steps calls, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write d, nn, P(direct) and E(K) of the last step at a fixed, seeded sample of the pairs "
+                         "(at most %d) as DIR/<name>.npy, float64" % DUMP_PAIRS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: only the oracle check of cpu_baseline, no timed CPU legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip sensitivity, filter, roofline_general and dm_frontend")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="minimum wall time of each CPU baseline leg")
     ap.add_argument("--lamb", type=float, default=1e-3 * 29903)     # tracs distance defaults (distance.py:76-90)
     ap.add_argument("--beta", type=float, default=73.0)
@@ -159,6 +175,29 @@ def synth_kw(p_partial=0.0, workload="sparse"):
     if p_partial or "p_partial" not in kw:
         kw["p_partial"] = p_partial
     return kw
+
+
+def dump_sample(n):
+    """--dump-outputs: the cells (i, j > i) that are written -- a fixed, seeded sample in row-major pair order, every pair where there
+    are at most DUMP_PAIRS -- as int64 arrays (i, j).  Depends on n only."""
+    import numpy as np
+    pairs = n * (n - 1) // 2
+    if pairs <= DUMP_PAIRS:
+        k = np.arange(pairs, dtype=np.int64)
+    else:
+        k = np.sort(np.random.default_rng(DUMP_SEED).choice(pairs, size=DUMP_PAIRS, replace=False)).astype(np.int64)
+    r = np.arange(n, dtype=np.int64)
+    first = r * (2 * n - r - 1) // 2                      # pair index of (i, i + 1): the pairs of the rows above row i
+    i = np.searchsorted(first, k, side="right") - 1
+    return i, k - first[i] + i + 1
+
+
+def dump_outputs(path, cells, vals):
+    """Write the sampled cells and their d, nn, P(direct), E(K) (vals: 4 x cells, any float64-convertible) as path/<name>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in zip(("pair_i", "pair_j", "d", "nn", "p_direct", "expected_k"), list(cells) + list(vals)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def pair_split_ms(lib, calls=1):
@@ -324,6 +363,8 @@ def main():
     _WORKLOAD_OF_PROFILES = args.workload if args.partial == 0 else "partial"
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if not in_launcher():
         if args.gpus > 1:
             raise SystemExit(launch_ranks(args))              # N ranks as a child process; nothing here has touched a GPU
@@ -508,18 +549,19 @@ def main():
             return (time.perf_counter() - t) * 1e3
         cold_ms = one_pass(aln)
         cold_stages = dev.pack_stages()
-        aln2 = dev.Alignment(n, L)
-        synth.pack_synthetic_device(aln2, seed=seed, **synth_kw(args.partial, args.workload))
-        warm_ms = one_pass(aln2)
-        warm_stages = dev.pack_stages()
-        aln2.close()
-        del aln2
-        single = {"cold_ms": cold_ms, "warm_ms": warm_ms, "value_single_pass": n * (n - 1) // 2 / (warm_ms / 1e3), "unit": "pairs/s",
-                  "per_pack_ms": sum(ms for _, ms in warm_stages),
-                  "stages_ms": {k: round(v, 3) for k, v in warm_stages}, "cold_stages_ms": {k: round(v, 3) for k, v in cold_stages},
-                  "note": "packed planes resident -> d, nn, P, E(K) for ONE pass over a freshly packed alignment, with everything the library "
-                          "decides and builds once per pack (stages: HIP events on the launch stream); cold = first pass of the process, warm = "
-                          "a second handle packed afterwards (wall clock around one call, host synchronisation included); `value` times K such calls back to back"}
+        if args.full:
+            aln2 = dev.Alignment(n, L)
+            synth.pack_synthetic_device(aln2, seed=seed, **synth_kw(args.partial, args.workload))
+            warm_ms = one_pass(aln2)
+            warm_stages = dev.pack_stages()
+            aln2.close()
+            del aln2
+            single = {"cold_ms": cold_ms, "warm_ms": warm_ms, "value_single_pass": n * (n - 1) // 2 / (warm_ms / 1e3), "unit": "pairs/s",
+                      "per_pack_ms": sum(ms for _, ms in warm_stages),
+                      "stages_ms": {k: round(v, 3) for k, v in warm_stages}, "cold_stages_ms": {k: round(v, 3) for k, v in cold_stages},
+                      "note": "packed planes resident -> d, nn, P, E(K) for ONE pass over a freshly packed alignment, with everything the library "
+                              "decides and builds once per pack (stages: HIP events on the launch stream); cold = first pass of the process, warm = "
+                              "a second handle packed afterwards (wall clock around one call, host synchronisation included); `value` times K such calls back to back"}
         t_first = cold_ms / 1e3
     else:
         # first pass over this rank's panels (untimed): the once-per-pack work, and what the exchange needs to know -- do the
@@ -559,16 +601,21 @@ def main():
     torch.cuda.synchronize()
     del tc_ev[:]
     elapsed = timed_run(args.warmup, args.steps, True)
+    if args.dump_outputs and rank == 0:                           # the last timed step's results (whole matrices on every rank)
+        cells = dump_sample(n)
+        ii, jj = torch.from_numpy(cells[0]).to(device), torch.from_numpy(cells[1]).to(device)
+        dk, nk = sets[(args.warmup + args.steps - 1) % nsets]
+        dump_outputs(args.dump_outputs, cells, [m[ii, jj].to(torch.float64).cpu().numpy() for m in (dk, nk, pmat, emat)])
     split_calls = args.steps if len(ranges) == 1 else 1
     split = pair_split_ms(lib, split_calls)                       # the timed calls' dense kernels (mean; two ranges per step: the last call)
     call_stages = dev.pack_stages_bytes()                         # the once-per-pack stages of the last timed call
     timed = range(args.warmup, args.warmup + args.steps)
     kern_ms = [ev0[i].elapsed_time(ev1[i]) for i in timed]
     tc_ms = [a.elapsed_time(b) for a, b in tc_ev] or [0.0]
-    # ---- steady state: the same K steps over the alignment as it stands (nothing rebuilt) -- round 1-3's `value` --------------------
+    # ---- steady state (--full): the same K steps over the alignment as it stands (nothing rebuilt) -- round 1-3's `value` -------------
     steady_first = args.warmup + args.steps
-    elapsed_steady = timed_run(steady_first, args.steps, False)
-    steady_kern_ms = [ev0[i].elapsed_time(ev1[i]) for i in range(steady_first, steady_first + args.steps)]
+    if args.full:
+        elapsed_steady = timed_run(steady_first, args.steps, False)
 
     pairs_total = n * (n - 1) // 2
     my_pairs = sum(partition.pairs_in_rows(n, r0, r1) for r0, r1 in ranges)
@@ -576,7 +623,7 @@ def main():
     my_pairs_per_launch = my_pairs / len(ranges)
     classes = aln.site_classes                                    # (variable, invariant) sites, or None: whole alignment read
 
-    dmat, nmat = sets[(args.warmup + 2 * args.steps - 1) % nsets]    # the last step's results
+    dmat, nmat = sets[(args.warmup + (2 if args.full else 1) * args.steps - 1) % nsets]    # the last step's results
     checksum = int(dmat[:n].sum().item()) if rank == 0 else 0
     if os.environ.get("TRACS_BENCH_VERIFY") and rank == 0:
         # the gathered matrices must equal a single-pass recomputation on this rank
@@ -597,8 +644,6 @@ def main():
         ms_per_step = elapsed / args.steps * 1e3
         value = pairs_total * args.steps / elapsed
         enc = aln.encoding or "general"
-        roof = dense_call_roofline(aln, split, n, L, world, partition.pairs_in_rows(n, *ranges[-1]), ranges[-1][1] - ranges[-1][0],
-                                   my_pairs_per_launch, kern_s, split_calls, overlap)
         enc_name = "consensus (ACGTN) alignment" if enc == "consensus" else "general IUPAC alignment (%.2g partial codes)" % args.partial
         W = WORKLOADS[args.workload]
         out = {"metric": "sample-pairs/sec for 10kx5Mbp SNP+transcluster distance", "value": value,
@@ -607,11 +652,9 @@ def main():
                "dtype": "u32", "data": "synthetic",
                "step": "ONE CALL per step: packed planes resident in HBM -> d, compared sites, P(direct), E(K) of all pairs, with everything "
                        "the library decides and builds per alignment (encoding, site classes, lists) redone in every step -- the reference's "
-                       "unit of work, one pairsnp call per alignment (src/pairsnp.hpp:320-457).  value_steady_state: repeated passes over "
-                       "one packed alignment, nothing rebuilt (what rounds 1-3 reported as `value`)",
-               "value_steady_state": pairs_total * args.steps / elapsed_steady,
-               "ms_per_step_steady_state": elapsed_steady / args.steps * 1e3,
-               "roofline_per_pack": per_pack_roofline(call_stages),
+                       "unit of work, one pairsnp call per alignment (src/pairsnp.hpp:320-457)." +
+                       ("  value_steady_state: repeated passes over one packed alignment, nothing rebuilt (what rounds 1-3 reported as "
+                        "`value`)" if args.full else ""),
                "config": {"workload": "%d samples x %d sites, %s, mu = %g per sample + %g N (%s): pairsnp (d + compared "
                                       "sites) + transcluster (P, E(K)), all %d pairs"
                                       % (n, L, enc_name, W["mu_sample"], W["p_n"], "SURVEY 8d" if args.workload == "sparse" else
@@ -628,35 +671,52 @@ def main():
                           "workload_name": args.workload, "exchange": exchange,
                           "streams": ("2: transcluster on a second stream beside the rest of the dense call, from the moment the distances "
                                       "are final (tracs_pairsnp_notify_distances)") if overlap else "1",
-                          "setup_seconds": round(setup_s, 1), "first_call_ms": round(t_first * 1e3, 1), "checksum_d": checksum},
-               "roofline": roof}
-        if single is not None:
-            out["single_pass"] = single
-        if world == 1 and not args.no_extras and args.partial == 0 and args.workload == "sparse":
-            out["sensitivity"] = sensitivity(args, n, L, seed, days, dev, synth, torch, device, lib, value)
-            out["value_worst_workload"] = min([value] + [w["pairs_per_s"] for w in out["sensitivity"]["workloads"].values()])   # per call, like `value`
-        filter_block = None
-        if world == 1 and not args.no_extras:
-            # `tracs distance --filter`: the recombination filter over every emitted pair of the timed alignment (not part of `value`)
-            out["filter"] = filter_leg(n, L, seed, synth_kw(args.partial, args.workload), aln, dmat, nmat, dev, synth, torch, device)
-            filter_block = out["filter"].pop("_block", None)
-        if world == 1 and not args.no_extras and args.partial == 0:
-            out["roofline_general"] = general_pass(args, n, L, seed, dev, synth, torch, device)
-            out["dm_frontend"] = dm_frontend(args, L, dev, torch, device)
+                          "setup_seconds": round(setup_s, 1), "first_call_ms": round(t_first * 1e3, 1), "checksum_d": checksum}}
         if world > 1:
             out["config"]["communicator"], out["config"]["ranks_seen"] = comm_info, comm_info["ranks_seen"]
-            if not args.no_cpu_baseline:                       # (the gathered matrix is whole on every rank)
-                keys[0] = distinct_keys(torch, dmat, n, days, [(0, n)])
-                out["config"]["distinct_keys"] = keys[0]
-        # ALWAYS: the first 128 samples' block against the oracle (full length, bit-equal), with or without the timed CPU legs
-        out["cpu_baseline"] = cpu_baseline(n, L, seed, days_np, args, dmat, nmat, keys[0], check_only=args.no_cpu_baseline,
-                                           filter_block=filter_block)
-        if filter_block is not None and "filter" in out:
-            out["filter"]["oracle_check"] = out["cpu_baseline"].get("filter")
-        print(json.dumps(out), flush=True)
+        if not args.full:
+            print(json.dumps(out), flush=True)
+        else:
+            full_line(out, args, n, L, seed, world, days, days_np, dev, synth, torch, device, lib, aln, dmat, nmat, keys,
+                      value, elapsed_steady, call_stages, single,
+                      dense_call_roofline(aln, split, n, L, world, partition.pairs_in_rows(n, *ranges[-1]), ranges[-1][1] - ranges[-1][0],
+                                          my_pairs_per_launch, kern_s, split_calls, overlap))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_line(out, args, n, L, seed, world, days, days_np, dev, synth, torch, device, lib, aln, dmat, nmat, keys,
+              value, elapsed_steady, call_stages, single, roof):
+    """--full (rank 0 of main()): the steady-state pass, the rooflines, single_pass and the legs with runs of their own, beside the
+    headline; then the line."""
+    pairs_total = n * (n - 1) // 2
+    out["value_steady_state"] = pairs_total * args.steps / elapsed_steady
+    out["ms_per_step_steady_state"] = elapsed_steady / args.steps * 1e3
+    out["roofline_per_pack"] = per_pack_roofline(call_stages)
+    out["roofline"] = roof
+    if single is not None:
+        out["single_pass"] = single
+    if world == 1 and not args.no_extras and args.partial == 0 and args.workload == "sparse":
+        out["sensitivity"] = sensitivity(args, n, L, seed, days, dev, synth, torch, device, lib, value)
+        out["value_worst_workload"] = min([value] + [w["pairs_per_s"] for w in out["sensitivity"]["workloads"].values()])   # per call, like `value`
+    filter_block = None
+    if world == 1 and not args.no_extras:
+        # `tracs distance --filter`: the recombination filter over every emitted pair of the timed alignment (not part of `value`)
+        out["filter"] = filter_leg(n, L, seed, synth_kw(args.partial, args.workload), aln, dmat, nmat, dev, synth, torch, device)
+        filter_block = out["filter"].pop("_block", None)
+    if world == 1 and not args.no_extras and args.partial == 0:
+        out["roofline_general"] = general_pass(args, n, L, seed, dev, synth, torch, device)
+        out["dm_frontend"] = dm_frontend(args, L, dev, torch, device)
+    if world > 1 and not args.no_cpu_baseline:                 # (the gathered matrix is whole on every rank)
+        keys[0] = distinct_keys(torch, dmat, n, days, [(0, n)])
+        out["config"]["distinct_keys"] = keys[0]
+    # with --full ALWAYS: the first 128 samples' block against the oracle (full length, bit-equal), with or without the timed CPU legs
+    out["cpu_baseline"] = cpu_baseline(n, L, seed, days_np, args, dmat, nmat, keys[0], check_only=args.no_cpu_baseline,
+                                       filter_block=filter_block)
+    if filter_block is not None and "filter" in out:
+        out["filter"]["oracle_check"] = out["cpu_baseline"].get("filter")
+    print(json.dumps(out), flush=True)
 
 
 def distinct_keys(torch, dmat, n, days, ranges, dist=None, world=1):
@@ -765,10 +825,23 @@ def site_sharded(args, n, L, seed, world, rank, device, dist, exchange, comm_inf
     for _ in range(args.warmup):
         step()
     elapsed, marks = timed_run(args.steps, True)
+    if args.dump_outputs:
+        # the last timed step's results: every rank contributes the sampled cells of the rows it owns, rank 0 writes the sums
+        cells = dump_sample(n)
+        ii, jj = torch.from_numpy(cells[0]).to(device), torch.from_numpy(cells[1]).to(device)
+        owned = torch.zeros(rows_pad, dtype=torch.bool, device=device)
+        for q0, q1 in own:
+            owned[q0:q1] = True
+        vals = torch.stack([m[ii, jj].to(torch.float64) for m in (dmat, nmat, pmat, emat)])
+        vals = torch.where(owned[ii][None, :], vals, torch.zeros_like(vals)).contiguous()
+        dist.all_reduce(vals)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, cells, vals.cpu().numpy())
     stages = dev.pack_stages_bytes()
     split = pair_split_ms(lib, args.steps)
     kern_ms = sum(m[0].elapsed_time(m[1]) for m in marks) / len(marks)
-    elapsed_steady, _ = timed_run(args.steps, False)
+    if args.full:                                              # the steady-state pass: nothing rebuilt
+        elapsed_steady, _ = timed_run(args.steps, False)
     if not ex.check():
         raise SystemExit("the exchange overflowed its 16-bit cells in a later call (rank %d)" % rank)
     pairs_total = n * (n - 1) // 2
@@ -780,7 +853,7 @@ def site_sharded(args, n, L, seed, world, rank, device, dist, exchange, comm_inf
     cks = torch.tensor([int(dmat[mine].sum().item())], dtype=torch.int64, device=device)
     dist.all_reduce(cks)
     checksum = int(cks.item())
-    n_keys = distinct_keys(torch, dmat, n, days, own, dist, world) if not args.no_cpu_baseline else 0
+    n_keys = distinct_keys(torch, dmat, n, days, own, dist, world) if args.full and not args.no_cpu_baseline else 0
     if os.environ.get("TRACS_BENCH_VERIFY"):
         # this rank's rows must equal the same rows of a single call over the whole alignment
         full = dev.Alignment(n, L)
@@ -802,19 +875,12 @@ def site_sharded(args, n, L, seed, world, rank, device, dist, exchange, comm_inf
         def mean_ms(a, b):
             return sum(m[a].elapsed_time(m[b]) for m in marks) / len(marks)
         W = WORKLOADS[args.workload]
-        # rank 0's dense call over its slice: all pairs, all rows, L = the slice's sites
-        roof = dense_call_roofline(aln, split, n, l1 - l0, world, pairs_total, n, pairs_total, kern_ms / 1e3, args.steps)
-        roof["scope"] = ("rank 0's dense call over its slice of the sites (%d of %d): every rank runs the same kernels on 1 / %d of the "
-                         "sites for all pairs; the step is shared between the slice's call, the exchange and transcluster (config.rank0_ms)"
-                         % (l1 - l0, L, world))
         out = {"metric": "sample-pairs/sec for 10kx5Mbp SNP+transcluster distance", "value": pairs_total * args.steps / elapsed,
                "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
                "dtype": "u32", "data": "synthetic",
                "step": "ONE CALL per step (as at N = 1): every rank's slice counts as freshly packed, the once-per-pack work is redone in every "
-                       "step; value_steady_state: repeated passes, nothing rebuilt",
-               "value_steady_state": pairs_total * args.steps / elapsed_steady,
-               "ms_per_step_steady_state": elapsed_steady / args.steps * 1e3,
+                       "step" + ("; value_steady_state: repeated passes, nothing rebuilt" if args.full else ""),
                "config": {"workload": "%d samples x %d sites, mu = %g per sample + %g N (%s): pairsnp (d + compared sites) + transcluster (P, E(K)), "
                                       "all %d pairs" % (n, L, W["mu_sample"], W["p_n"], "SURVEY 8d" if args.workload == "sparse" else
                                                          "workload '%s'" % args.workload, pairs_total),
@@ -839,14 +905,22 @@ def site_sharded(args, n, L, seed, world, rank, device, dist, exchange, comm_inf
                           "kernels_ms": None if not split else dict(zip(("pair", "lists", "count", "nn_lists"), split)),
                           "mean_d": checksum / float(pairs_total), "checksum_d": checksum, "distinct_keys": n_keys or None,
                           "clock_rate": args.lamb, "trans_rate": args.beta, "precision": args.precision,
-                          "setup_seconds": round(setup_s, 1), "first_call_ms": round(t_first * 1e3, 1)},
-               "roofline_per_pack": per_pack_roofline(stages),
-               "roofline": roof}
-        # ALWAYS: the first samples' block of the rows rank 0 owns against the oracle (full length, bit-equal), with or without the
-        # timed CPU legs
-        m = min(128, own[0][1] - own[0][0]) if own and own[0][0] == 0 else 0
-        if m >= 2:
-            out["cpu_baseline"] = cpu_baseline(n, L, seed, days_np, args, dmat, nmat, n_keys, m_max=m, check_only=args.no_cpu_baseline)
+                          "setup_seconds": round(setup_s, 1), "first_call_ms": round(t_first * 1e3, 1)}}
+        if args.full:
+            out["value_steady_state"] = pairs_total * args.steps / elapsed_steady
+            out["ms_per_step_steady_state"] = elapsed_steady / args.steps * 1e3
+            out["roofline_per_pack"] = per_pack_roofline(stages)
+            # rank 0's dense call over its slice: all pairs, all rows, L = the slice's sites
+            roof = dense_call_roofline(aln, split, n, l1 - l0, world, pairs_total, n, pairs_total, kern_ms / 1e3, args.steps)
+            roof["scope"] = ("rank 0's dense call over its slice of the sites (%d of %d): every rank runs the same kernels on 1 / %d of the "
+                             "sites for all pairs; the step is shared between the slice's call, the exchange and transcluster (config.rank0_ms)"
+                             % (l1 - l0, L, world))
+            out["roofline"] = roof
+            # with --full ALWAYS: the first samples' block of the rows rank 0 owns against the oracle (full length, bit-equal), with or
+            # without the timed CPU legs
+            m = min(128, own[0][1] - own[0][0]) if own and own[0][0] == 0 else 0
+            if m >= 2:
+                out["cpu_baseline"] = cpu_baseline(n, L, seed, days_np, args, dmat, nmat, n_keys, m_max=m, check_only=args.no_cpu_baseline)
         print(json.dumps(out), flush=True)
     dist.barrier()
     dist.destroy_process_group()

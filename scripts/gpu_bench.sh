@@ -5,8 +5,8 @@ cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout 1500 python bench.py --steps 3 --warmup 1 2>&1 | tail -1 | tee $OUT/bench_c3.json
-timeout 600 python bench.py --samples 1000 --sites 1000000 --steps 10 --warmup 2 2>&1 | tail -1 | tee $OUT/bench_c2.json
+timeout 1500 python bench.py --full --steps 3 --warmup 1 2>&1 | tail -1 | tee $OUT/bench_c3.json
+timeout 600 python bench.py --full --samples 1000 --sites 1000000 --steps 10 --warmup 2 2>&1 | tail -1 | tee $OUT/bench_c2.json
 cd /tmp
 T="python3 $GRAFT_REPO_ROOT/scripts/prof_target.py 10000 5000000 1"
 for c in FETCH_SIZE WRITE_SIZE; do

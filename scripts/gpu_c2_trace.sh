@@ -1,5 +1,6 @@
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp; export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/c2 -o t -- python3 $GRAFT_REPO_ROOT/bench.py --samples 1000 --sites 1000000 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > /tmp/c2.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/c2 -o t -- python3 $ROOT/bench.py --full --samples 1000 --sites 1000000 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > /tmp/c2.log 2>&1
 python3 - <<PY
 import csv,glob
 f=glob.glob('/tmp/c2/**/*kernel_stats.csv',recursive=True)[0]

@@ -5,5 +5,5 @@ for rep in 1 2; do for T in 128 64; do
 done; done
 for T in 128 64; do
   echo "== config 2, TRACS_CLASSIFY_THREADS=$T"
-  TRACS_CLASSIFY_THREADS=$T python bench.py --samples 1000 --sites 1000000 --steps 20 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "import sys,json; j=json.loads(sys.stdin.read()); print(j['ms_per_step'], [(s['stage'], s['ms']) for s in j['roofline_per_pack']['stages']])"
+  TRACS_CLASSIFY_THREADS=$T python bench.py --full --samples 1000 --sites 1000000 --steps 20 --warmup 5 --no-extras --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "import sys,json; j=json.loads(sys.stdin.read()); print(j['ms_per_step'], [(s['stage'], s['ms']) for s in j['roofline_per_pack']['stages']])"
 done

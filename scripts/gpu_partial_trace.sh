@@ -1,5 +1,6 @@
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp; export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -o t -- python3 $GRAFT_REPO_ROOT/bench.py --partial 0.005 --steps 3 --warmup 1 --no-extras --no-cpu-baseline > /tmp/pp.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pp -o t -- python3 $ROOT/bench.py --full --partial 0.005 --steps 3 --warmup 1 --no-extras --no-cpu-baseline > /tmp/pp.log 2>&1
 python3 - <<PY
 import csv,glob
 f=glob.glob('/tmp/pp/**/*kernel_stats.csv',recursive=True)[0]

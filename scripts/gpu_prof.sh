@@ -1,12 +1,13 @@
 #!/bin/bash
 # usage: bash scripts/gpu_prof.sh <tag> [samples] [sites]  -- rocprofv3 kernel trace + PMC passes of bench.py
 TAG=${1:-p01}; NS=${2:-10000}; NL=${3:-5000000}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python3 $GRAFT_REPO_ROOT/bench.py --samples $NS --sites $NL --steps 2 --warmup 1 --no-cpu-baseline"
+BENCH="python3 $ROOT/bench.py --full --samples $NS --sites $NL --steps 2 --warmup 1 --no-cpu-baseline"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $BENCH > $OUT/trace.log 2>&1
 tail -2 $OUT/trace.log
 timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- $BENCH > $OUT/pmc_fetch.log 2>&1

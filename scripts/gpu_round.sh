@@ -10,5 +10,5 @@ nproc > $OUT/host.txt; lscpu | grep -E "Model name|^CPU\(s\)|Thread|Socket" >> $
 timeout 1200 python -m pytest tests -m gpu -x -q 2>&1 | tail -25 | tee $OUT/pytest_gpu.txt
 timeout 300 python __graft_entry__.py smoke 2>&1 | tail -3 | tee $OUT/smoke.txt
 # config 2 (1000 x 1 Mbp) quick line, then the headline config
-timeout 600 python bench.py --samples 1000 --sites 1000000 --steps 5 --warmup 2 --cpu-seconds 5 2>&1 | tail -3 | tee $OUT/bench_c2.json
-timeout 1500 python bench.py --steps 3 --warmup 1 2>&1 | tail -3 | tee $OUT/bench_c3.json
+timeout 600 python bench.py --full --samples 1000 --sites 1000000 --steps 5 --warmup 2 --cpu-seconds 5 2>&1 | tail -3 | tee $OUT/bench_c2.json
+timeout 1500 python bench.py --full --steps 3 --warmup 1 2>&1 | tail -3 | tee $OUT/bench_c3.json

@@ -188,6 +188,25 @@ def kseq():
     jdump("kseq_golden.json", out)
 
 
+def oracle_vs_ref():
+    """The inputs of tests/test_oracle_vs_ref.py and oracle/_ref's outputs for them, so that the test also runs where oracle/_ref
+    cannot be built: trans_dist on 400 keys for each of three (lamb, beta), calculate_posteriors on 2 000 count rows."""
+    rng = np.random.default_rng(5)
+    out = {}
+    for t, (lamb, beta) in enumerate(((5.3, 6.0), (29.903, 73.0), (3.0, 52.0))):
+        N = rng.integers(0, 90, 400); days = rng.integers(0, 300, 400); days[:20] = 0
+        delta = days * 86400.0 / 31556952.0
+        rp0, rek = R.ref_trans_dist(N.tolist(), delta.tolist(), lamb, beta, 0.01)
+        out.update({"lamb_beta_%d" % t: np.array([lamb, beta]), "N_%d" % t: N.astype(np.int64), "days_%d" % t: days.astype(np.int64),
+                    "p0_%d" % t: np.asarray(rp0, np.float64), "ek_%d" % t: np.asarray(rek, np.float64)})
+    counts = rng.poisson(6, (2000, 4)).astype(float); counts[:30] = 0; counts[30:60] = 4
+    out["counts"] = counts
+    for keep in (False, True):
+        out["posteriors_keep_%d" % keep] = np.asarray(R.ref_calculate_posteriors(counts, [3.0, 0.2, 9.0, 0.7], keep, 0.04), np.float64)
+    np.savez_compressed(os.path.join(HERE, "oracle_vs_ref_golden.npz"), **out)
+    print("wrote oracle_vs_ref_golden.npz")
+
+
 def pairsnp_unpinned():
     cases = {}
     specs = {"iupac_small": dict(n=7, L=61, seed=3, mu_lineage=0.05, mu_sample=0.03, p_n=0.05, p_partial=0.1, p_lower=0.2, p_other=0.05),
@@ -294,6 +313,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:] == ["large-n"]:              # only the fixture added in round 2
         transcluster_large_n()
+        sys.exit(0)
+    if sys.argv[1:] == ["oracle-vs-ref"]:        # only the fixture of tests/test_oracle_vs_ref.py
+        oracle_vs_ref()
         sys.exit(0)
     transcluster()
     transcluster_large_n()

@@ -101,7 +101,7 @@ def test_bench_gpus_2_launches_its_own_ranks(part):
     for the dominant kernel of rank 0's call, a cpu_baseline whose block check (rows rank 0 owns, against the oracle) has passed;
     TRACS_BENCH_VERIFY: every rank's d / nn / P / E(K) equal a single call over the whole alignment."""
     out, lines = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--samples", "1501", "--sites", "100000", "--partition", part,
-                         "--cpu-seconds", "0.5"], {"TRACS_BENCH_BACKEND": "gloo", "TRACS_BENCH_VERIFY": "1"})
+                         "--cpu-seconds", "0.5", "--full"], {"TRACS_BENCH_BACKEND": "gloo", "TRACS_BENCH_VERIFY": "1"})
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     assert len(lines) == 1
     j = json.loads(lines[0])

@@ -141,7 +141,7 @@ def test_multirank_driver_path_on_one_gpu(part):
     env = dict(os.environ, TRACS_BENCH_BACKEND="gloo", TRACS_BENCH_VERIFY="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                           "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3",
-                          "--warmup", "1", "--samples", "1501", "--sites", "100000", "--partition", part], capture_output=True, text=True, env=env,
+                          "--warmup", "1", "--samples", "1501", "--sites", "100000", "--partition", part, "--full"], capture_output=True, text=True, env=env,
                          timeout=600, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert '"n_gpus": 2' in out.stdout and '"scaling": "strong"' in out.stdout
@@ -390,7 +390,7 @@ def test_config5_edge_clustering_two_ranks_equals_one():
 
 
 def test_bench_line_contract_small():
-    """bench.py on one GPU at a small size: one JSON line with the fields the driver reads -- metric / value / unit / n_gpus /
+    """bench.py --full on one GPU at a small size: one JSON line with the fields the driver reads -- metric / value / unit / n_gpus /
     steps / ms_per_step / scaling / dtype / config.workload, a `roofline` object (bound, achieved, peak, unit, frac, traffic) for
     the dominant kernel with the site-class report beside it, `roofline_general`, `dm_frontend`, and a `cpu_baseline` (kind,
     cores, sample, the two legs) whose block check -- GPU d / nn bit-equal to the oracle on the timed alignment -- has passed."""
@@ -398,7 +398,7 @@ def test_bench_line_contract_small():
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--samples", "700", "--sites",
-                          "200000", "--cpu-seconds", "0.5"], capture_output=True, text=True, timeout=900, cwd=root)
+                          "200000", "--cpu-seconds", "0.5", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
