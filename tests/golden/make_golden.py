@@ -29,7 +29,7 @@ from oracle import oracle as O  # noqa: E402
 from tracs_amd import synth  # noqa: E402
 
 R = O.ref_module()
-assert R is not None, "oracle/_ref is not built (make -C oracle)"
+assert R is not None or sys.argv[1:] == ["hp-transcluster"], "oracle/_ref is not built (make -C oracle)"
 
 
 def jdump(name, obj):
@@ -307,7 +307,58 @@ def python_reference():
     jdump("python_reference_golden.json", out)
 
 
+# ---------------------------------------------------------------------------------------
+# transcluster's p0 and E(K) from the series' definition at 40 digits (tests/hp_transcluster.py): neither the reference nor the
+# oracle is used.  Keys: the CLI defaults' full cross of N x delta, and for every other (lamb, beta, thr) set two deltas per N,
+# drawn with a fixed seed (every N boundary stays in).
+HP_SETS = ((1e-3 * 29903, 73.0, 0.01),      # the CLI defaults
+           (1e-3 * 29903, 73.0, 1e-6),      # the reference's own default threshold
+           (5.3, 6.0, 0.01), (3.0, 52.0, 0.01),
+           (20.0, 2.0, 0.05),               # short series
+           (200.0, 150.0, 0.01),            # x = delta (lamb + beta) = 600 at 626 days; `upper` overflows near 3.5 years
+           (0.5, 73.0, 0.01))               # k* = beta (N + 1) / lamb beyond the loop's 10 000 terms at small N
+HP_N = (0, 1, 2, 7, 30, 127, 128, 129, 191, 192, 193, 1000, 1600, 3000, 4100, 6000, 8000, 9998, 9999, 10000, 10001, 15000,
+        22766, 22767, 22768, 22769, 32766, 32767, 32768, 50000, 100000)
+HP_GAPS = (0, 1, 2, 30, 365, 730, 1000, 2400, 9000)          # whole days: every route
+HP_YEARS = (1e-9, 0.37, 3.3)                                  # deltas that are no whole number of days: the array routes only
+HP_FIELDS = ("set", "N", "gap", "delta", "p0", "ln_eK", "k_stop", "cls", "k_lo", "k_hi", "ln_e_lo", "ln_e_hi", "ln_upper")
+
+
+def _hp_one(args):
+    import hp_transcluster as H
+    s, N, gap, delta = args
+    lamb, beta, thr = HP_SETS[s]
+    r = H.evaluate(N, delta, lamb, beta, thr)
+    return [s, N, gap, delta] + [r[f] for f in HP_FIELDS[4:]]
+
+
+def hp_transcluster():
+    import multiprocessing
+    sys.path.insert(0, os.path.dirname(HERE))
+    import hp_transcluster as H
+    deltas = [(g, H.day_delta(g)) for g in HP_GAPS] + [(None, y) for y in HP_YEARS]
+    rng = np.random.default_rng(20261016)
+    work = []
+    for s in range(len(HP_SETS)):
+        for N in HP_N:
+            pick = range(len(deltas)) if s == 0 else sorted(rng.choice(len(deltas), 2, replace=False).tolist())
+            work += [(s, N) + deltas[i] for i in pick]
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool:
+        rows = pool.map(_hp_one, sorted(work, key=lambda w: -w[1]), chunksize=1)
+    rows.sort(key=lambda r: (r[0], r[1], r[3]))
+    out = {"about": "transcluster log P(direct) and E(K) from the series' definition at %d digits (tests/hp_transcluster.py); "
+                    "delta = gap * 86400 / 31556952 in double for whole-day gaps" % H.DPS,
+           "sets": [list(x) for x in HP_SETS], "fields": list(HP_FIELDS), "keys": rows}
+    with open(os.path.join(HERE, "transcluster_hp_golden.json"), "w") as fh:
+        fh.write(json.dumps({k: v for k, v in out.items() if k != "keys"})[:-1] + ', "keys": [\n')
+        fh.write(",\n".join(json.dumps(r) for r in rows) + "\n]}\n")
+    print("wrote transcluster_hp_golden.json", len(rows), "keys")
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["hp-transcluster"]:     # only the high-precision transcluster fixture (no reference, no oracle needed)
+        hp_transcluster()
+        sys.exit(0)
     if sys.argv[1:] == ["outbreak"]:             # only the fixture added in round 3
         transcluster_outbreak()
         sys.exit(0)

@@ -297,6 +297,8 @@ def load():
     L.tracs_debug_tile_variant.restype = C.c_char_p
     L.tracs_debug_mfma_shape.restype = C.c_char_p
     L.tracs_debug_last_trans_dist_keys.restype = C.c_uint64
+    L.tracs_debug_trans_routes.restype = C.c_int
+    L.tracs_debug_trans_routes.argtypes = [C.POINTER(C.c_double)]
     L.tracs_debug_iupac_mask.restype = C.c_int
     L.tracs_debug_iupac_mask.argtypes = [C.c_int]
     _lib = L

@@ -17,7 +17,9 @@
 #include "common.h"
 
 #include <cmath>
+#include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 namespace tracs {
@@ -173,6 +175,10 @@ struct TcTables {
                                     // in LINEAR space (x <= TC_LINEAR_X_MAX over the call's gaps: F >= exp(-x) stays far from underflow)
 };
 constexpr double TC_LINEAR_X_MAX = 600.0;
+// ln of the largest double.  Where the bound `upper` overflows (few SNPs over a gap of years: delta lamb - pois > 709.78) the
+// reference's diff = upper - exp(elprob) (:232) is +inf until exp(elprob) overflows too, and NaN -- the loop ends -- from there on:
+// its loop stops at the first k whose stopping sum exceeds the largest double.  The scaled loops below test exactly that.
+constexpr double TC_LN_DBL_MAX = 709.782712893383973;
 constexpr unsigned long long TC_TABLE_ELEMS = 48ull << 20;      // doubles in the lnS table (384 MB)
 
 // A key handed over without any term summed (state[0] is NaN: tc_keys_kernel does that for N >= TC_WAVE_PREFIX_MIN)
@@ -255,7 +261,10 @@ __device__ __forceinline__ void tc_eval_wave(int N, double delta, const TcParams
     }
     if (pos) upper = exp(P.ln_beta + delta * P.lamb + log(n1) - (P.ln_lamb + pois));
     else upper = exp(P.ln_beta + log(n1) - P.ln_lamb);
-    double lim = Me == -INFINITY ? INFINITY : (upper - P.thr) * exp(-Me);
+    // the stopping test in units of exp(Me): (upper - thr) exp(-Me), or, with upper = inf, the largest double in those units
+    auto stop_lim = [&](double mx) { return upper < INFINITY ? (upper - P.thr) * exp(-mx) : exp(TC_LN_DBL_MAX - mx); };
+    const double ln_lim = upper < INFINITY ? log(upper - P.thr) : TC_LN_DBL_MAX;
+    double lim = Me == -INFINITY ? INFINITY : stop_lim(Me);
     // TPL consecutive k per lane and step (lane-major: the terms of a step stay in k order): the TPL x 2 exponentials of a lane are
     // independent, and the two wave scans and two wave maxima of a step are paid once per 64 x TPL terms
     constexpr int TPL = TRACS_TC_TPL;
@@ -283,7 +292,7 @@ __device__ __forceinline__ void tc_eval_wave(int N, double delta, const TcParams
                 const int j = 63 - __clzll((long long)low);
                 const int k_lo = __shfl(kj, j, 64);
                 const double t_lo = __shfl(tj, j, 64);
-                if (log((double)k_lo) + t_lo < log(upper - P.thr)) k_start = k_lo;
+                if (log((double)k_lo) + t_lo < ln_lim) k_start = k_lo;
             }
         }
     }
@@ -354,7 +363,7 @@ __device__ __forceinline__ void tc_eval_wave(int N, double delta, const TcParams
         }
         accumulate_n(t1, Lps, Mp, moved, lp);
         accumulate_n(t2, Els, Me, moved, el);
-        if (moved) lim = (upper - P.thr) * exp(-Me);
+        if (moved) lim = stop_lim(Me);
         // the while condition (upper - elprob > thr) fails after the first k whose prefix reaches lim (the prefixes grow with k)
         bool stop = false;
         double val = lp[TPL - 1];
@@ -420,7 +429,7 @@ __device__ __forceinline__ bool tc_eval_ratio(int N, double delta, long long gap
             const int j = 63 - __clzll((long long)low);
             const int k_lo = __shfl(kj, j, 64);
             const double t_lo = __shfl(tj, j, 64);
-            if (log((double)k_lo) + t_lo < log(upper - P.thr)) k_start = k_lo;
+            if (log((double)k_lo) + t_lo < (upper < INFINITY ? log(upper - P.thr) : TC_LN_DBL_MAX)) k_start = k_lo;
         }
     }
     auto wave_prefix = [&](double e) {                                // inclusive prefix sums across the wave
@@ -432,7 +441,7 @@ __device__ __forceinline__ bool tc_eval_ratio(int N, double delta, long long gap
         return e;
     };
     const double ref = bounded ? t_peak : t2_at(1);                   // (a loop that stops at its first term: that term is 1)
-    const double flim = (upper - P.thr) * exp(-ref);
+    const double flim = upper < INFINITY ? (upper - P.thr) * exp(-ref) : exp(TC_LN_DBL_MAX - ref);     // (see TC_LN_DBL_MAX)
     const double qb = P.beta / (P.lamb + P.beta);
     double S1 = 0.0, S2 = 0.0;                                        // sums of the steps before this one (wave-uniform)
     for (int k0 = k_start; k0 < 10000; k0 += 64 * FT) {
@@ -1211,6 +1220,14 @@ struct TcWorkspaceIds { enum { SLOTS = 0, ESLOT, SLOT_ID, NKEYS, KEY_ELEM, KEY_P
 constexpr unsigned long long TC_POIS_ELEMS = 16ull << 20;        // doubles in the pois table (128 MB)
 
 static unsigned long long g_last_keys = 0;        // distinct (N, delta) keys of the last entry-point call (bench.py reports it)
+// Where the last key evaluation left its counters (tracs_debug_trans_routes reads them back after the call; tests only)
+struct TcRoutes {
+    const unsigned *n_keys = nullptr, *long_ids = nullptr, *rest_ids = nullptr;
+    const TcTables *tab = nullptr;
+    unsigned nk = 0;
+    bool grid = false;
+};
+static TcRoutes g_routes;
 constexpr size_t TD_MAX_ELEMS = 1ull << 31;       // elements per pass: element indices and slots are 32-bit
 
 // The distinct keys are known (key_elem[0 .. nk): elements of `src` that carry them; n_keys[0] = nk on the device, n_keys[1] = 0):
@@ -1268,6 +1285,8 @@ static int tc_evaluate_keys(const Src &src, const unsigned *key_elem, unsigned n
     hipLaunchKernelGGL((tc_long_keys_kernel<Src>), dim3(std::min<unsigned>(nk, 256u * 32u)), dim3(64), 0, stream, src, key_elem,
                        rest_ids, n_keys + 9, P, lg, key_p0, key_eK, key_state, kt, tab);
     *key_p0_out = key_p0; *key_eK_out = key_eK;
+    g_routes.n_keys = n_keys; g_routes.long_ids = long_ids; g_routes.rest_ids = rest_ids; g_routes.tab = tab; g_routes.nk = nk;
+    g_routes.grid = std::is_same<Src, GridSource>::value;
     return TRACS_OK;
 }
 
@@ -1517,6 +1536,38 @@ using namespace tracs;
 extern "C" {
 
 unsigned long long tracs_debug_last_trans_dist_keys(void) { return g_last_keys; }
+
+// The routes of the last key evaluation (tests only; read after the call, nothing in the kernels' work changes):
+// out[0] distinct keys, out[1] finished by the serial kernel, [2] by the term-ratio loop, [3] by the same-day ratio loop,
+// [4] by the log-space wave loop, [5] (gap, M) tables built, [6] ... in linear form, [7] 1 = grid route, 0 = hash route.
+// -> 8, or 0 before any evaluation.
+int tracs_debug_trans_routes(double *out)
+{
+    const TcRoutes r = g_routes;
+    if (!r.n_keys || !out) return 0;
+    TRACS_HIP_CHECK(hipDeviceSynchronize());
+    unsigned h[16];
+    TcTables t;
+    TRACS_HIP_CHECK(hipMemcpy(h, r.n_keys, sizeof h, hipMemcpyDeviceToHost));
+    TRACS_HIP_CHECK(hipMemcpy(&t, r.tab, sizeof t, hipMemcpyDeviceToHost));
+    const unsigned n_long = h[1], n_zero = h[8], n_rest = h[9];     // (tc_evaluate_keys: [1] long keys, [8] same-day long keys, [9] left to the wave)
+    // same-day long keys sit at the end of long_ids; those the ratio loop did not take are among rest_ids
+    std::vector<unsigned> zero(n_zero), rest(n_rest);
+    if (n_zero) TRACS_HIP_CHECK(hipMemcpy(zero.data(), r.long_ids + (r.nk - n_zero), n_zero * 4ull, hipMemcpyDeviceToHost));
+    if (n_rest) TRACS_HIP_CHECK(hipMemcpy(rest.data(), r.rest_ids, n_rest * 4ull, hipMemcpyDeviceToHost));
+    std::sort(zero.begin(), zero.end());
+    unsigned zero_rest = 0;
+    for (unsigned id : rest) zero_rest += std::binary_search(zero.begin(), zero.end(), id) ? 1u : 0u;
+    out[0] = r.nk;
+    out[1] = (double)r.nk - n_long - n_zero;
+    out[2] = (double)n_long - (n_rest - zero_rest);
+    out[3] = (double)n_zero - zero_rest;
+    out[4] = n_rest;
+    out[5] = t.ok ? 1.0 : 0.0;
+    out[6] = t.ok && t.linear ? 1.0 : 0.0;
+    out[7] = r.grid ? 1.0 : 0.0;
+    return 8;
+}
 
 size_t tracs_trans_keys_words(void) { return (size_t)KS_WORDS + KS_TRAILER; }
 

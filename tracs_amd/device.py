@@ -306,6 +306,16 @@ def trans_dist_device(snpdiff, datediff, lamb, beta, threshold_Ek, exp_p0=False)
     return p0, eK
 
 
+def trans_routes():
+    """How the last transcluster call evaluated its distinct keys (csrc/transcluster.hip tracs_debug_trans_routes; tests only)."""
+    out = (C.c_double * 8)()
+    if _lib.require_gpu().tracs_debug_trans_routes(out) != 8:
+        return None
+    v = [int(x) for x in out]
+    return {"keys": v[0], "serial": v[1], "ratio": v[2], "ratio_zero": v[3], "wave": v[4], "tables": bool(v[5]),
+            "linear": bool(v[6]), "route": "grid" if v[7] else "hash"}
+
+
 def trans_dist_dense(dist, n, days, lamb, beta, threshold_Ek, p0, eK, exp_p0=True, dist_threshold=2147483647,
                      row_begin=0, row_end=None, col_begin=0, base_row=0):
     L = _lib.require_gpu()
