@@ -69,6 +69,16 @@ const uint64_t *tracs_pairsnp_ncompared(const tracs_pairsnp_result *r);
 const char *tracs_pairsnp_name(const tracs_pairsnp_result *r, size_t i);
 void tracs_pairsnp_free(tracs_pairsnp_result *r);
 
+/* Per-sample k nearest neighbours (not in the reference).  The candidates of sample s are ranked by the key
+ * (d, j): SNP distance first, then the candidate's sample index, a total order.  One file: every j != s (the same pair can come
+ * back under each of its samples).  Two files: only the samples of file 0 get lists, their candidates are the samples of file 1.
+ * Only pairs with d <= dist are eligible; each sample keeps min(k, eligible) neighbours, 1 <= k <= 1024 (else TRACS_E_ARG).
+ * The result is read through the tracs_pairsnp_* accessors: rows = s ascending, then the key ascending; cols = j, d, nn exact;
+ * filter != 0: the filtered distances of the emitted pairs (selection always uses the raw d), else zeros.  n_threads is accepted
+ * for signature parity with tracs_pairsnp and unused: every stage runs on the GPU.                                           */
+int tracs_nearest(const char *const *fasta, int n_fasta, int n_threads, int k, int dist, int filter,
+                  tracs_pairsnp_result **out);
+
 /* trans_dist(snpdiff, datediff, lamb, beta, threshold_Ek) -> (p0_log[n], eK[n])
  *   replaces: src/python_bindings.cpp:19-21 -> src/transcluster.hpp:240-287.               */
 int tracs_trans_dist(const int32_t *snpdiff, const double *datediff, size_t n, double lamb, double beta,
@@ -187,6 +197,26 @@ int tracs_edges_count_f64(const double *val, const uint32_t *dist, size_t ld, si
 int tracs_edges_fill_f64(const double *val, const uint32_t *dist, size_t ld, size_t n, size_t row_begin, size_t row_end,
                          size_t col_begin, int32_t dist_threshold, double threshold, const int64_t *offsets, uint32_t *rows,
                          uint32_t *cols, double *vals, void *stream);
+
+/* k-nearest-neighbour selection over dense panels (csrc/nearest.hip; what tracs_nearest runs).  The state is a device buffer of
+ * tracs_knn_state_bytes(n_lists, k) bytes holding one running list per sample of [0, n_lists): the k smallest keys (d, j) offered
+ * so far with their compared-site counts.
+ *   tracs_knn_init    every list empty
+ *   tracs_knn_update  merge the panel rows [row_begin, row_end) of dist / ncomp (tracs_pairsnp_dense[_thr]'s cells: columns
+ *                     j >= max(col_begin, i + 1), indexed by ABSOLUTE row, leading dimension ld) into the lists: row i offers
+ *                     (d(i, j), j) to list i; with symmetric != 0 (one-file mode) column c also offers (d(i, c), i) to list c.  A
+ *                     cell is eligible iff it is, read as unsigned, <= dist_threshold.  The state must hold lists for row_end
+ *                     samples (n with symmetric).  Every cell is offered at most once over the updates of one state: panels do not
+ *                     overlap.  Two stream-ordered launches; nn is read for the kept cells while the panel is resident.
+ *   tracs_knn_emit    lists [list_begin, list_end) -> offsets (device int64[list_end - list_begin + 1], exclusive: list s's
+ *                     neighbours are entries offsets[s - list_begin] ..) and, unless all four are NULL, rows / cols / d / nn
+ *                     (device uint32, room for (list_end - list_begin) * k entries) in list order, each list by key.          */
+size_t tracs_knn_state_bytes(size_t n_lists, int k);
+int tracs_knn_init(void *state, size_t n_lists, int k, void *stream);
+int tracs_knn_update(const uint32_t *dist, const uint32_t *ncomp, size_t ld, size_t n, size_t row_begin, size_t row_end,
+                     size_t col_begin, int32_t dist_threshold, int k, int symmetric, void *state, void *stream);
+int tracs_knn_emit(void *state, size_t list_begin, size_t list_end, int k, int64_t *offsets, uint32_t *rows, uint32_t *cols,
+                   uint32_t *d, uint32_t *nn, void *stream);
 
 /* Recombination filter (src/pairsnp.hpp:251-318) on emitted pairs.  rows/cols: device uint32[n_pairs];
  * pos_off: device int64[n_pairs+1] = exclusive scan of the pairs' SNP distances; positions: device uint32

@@ -37,6 +37,7 @@ SYMBOLS = [
     "tracs_alltoall", "tracs_tri_pack", "tracs_tri_sum", "tracs_rccl_version",
     "tracs_coo_fill_f64", "tracs_distance_open", "tracs_distance_nseq", "tracs_distance_name", "tracs_distance_run", "tracs_distance_free",
     "tracs_warm_up",
+    "tracs_nearest", "tracs_knn_state_bytes", "tracs_knn_init", "tracs_knn_update", "tracs_knn_emit",
 ]
 
 
@@ -141,6 +142,16 @@ def load():
     L.tracs_distance_name.argtypes = [vp, sz]
     L.tracs_distance_run.restype = C.c_int
     L.tracs_distance_run.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dbl, dbl, dbl, dbl, C.c_char_p, C.c_char_p, C.c_int, u64p, u64p]
+    L.tracs_nearest.restype = C.c_int
+    L.tracs_nearest.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.tracs_knn_state_bytes.restype = sz
+    L.tracs_knn_state_bytes.argtypes = [sz, C.c_int]
+    L.tracs_knn_init.restype = C.c_int
+    L.tracs_knn_init.argtypes = [vp, sz, C.c_int, vp]
+    L.tracs_knn_update.restype = C.c_int
+    L.tracs_knn_update.argtypes = [vp, vp, sz, sz, sz, sz, sz, i32, C.c_int, C.c_int, vp, vp]
+    L.tracs_knn_emit.restype = C.c_int
+    L.tracs_knn_emit.argtypes = [vp, sz, sz, C.c_int, vp, vp, vp, vp, vp, vp]
     L.tracs_warm_up.restype = None
     L.tracs_warm_up.argtypes = []
     L.tracs_distance_free.restype = None

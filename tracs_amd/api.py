@@ -31,6 +31,33 @@ def pairsnp_arrays(fasta, n_threads=1, dist=2147483647, filter=False):
     arr = (C.c_char_p * len(paths))(*paths)
     h = C.c_void_p()
     _lib.check(L.tracs_pairsnp(arr, len(paths), int(n_threads), int(dist), int(bool(filter)), C.byref(h)))
+    return _result_arrays(L, h)
+
+
+def nearest_arrays(fasta, k, n_threads=1, dist=2147483647, filter=False):
+    """The k nearest neighbours of each sample (tracs_nearest, include/tracs_hip.h): the six arrays of pairsnp_arrays, rows = the
+    sample (ascending), cols = its neighbours ranked by (SNP distance, sample index), at most k per sample.  One file: candidates
+    are all other samples; two files: the samples of file 0 get lists, their candidates are the samples of file 1.  Only pairs
+    with d <= dist are eligible.  filter: the filtered distances of the emitted pairs (the ranking uses the raw distance).
+    n_threads is accepted for parity with pairsnp_arrays and unused: every stage runs on the GPU."""
+    paths = _paths(fasta)
+    if len(paths) < 1 or len(paths) > 2:
+        raise RuntimeError("Invalid number of fasta files!")
+    k = int(k)
+    if k < 1 or k > 1024:
+        raise ValueError("nearest_arrays(): k must be in [1, 1024], got %d" % k)
+    for p in paths:
+        if not os.path.exists(p):
+            raise FileNotFoundError(os.fsdecode(p))
+    L = _lib.require_gpu()
+    arr = (C.c_char_p * len(paths))(*paths)
+    h = C.c_void_p()
+    _lib.check(L.tracs_nearest(arr, len(paths), int(n_threads), k, int(dist), int(bool(filter)), C.byref(h)))
+    return _result_arrays(L, h)
+
+
+def _result_arrays(L, h):
+    """(rows, cols, distances, names, filt_distances, n_compared) of a tracs_pairsnp_result, which they then own."""
     owner = _ResultOwner(L, h)
     n = L.tracs_pairsnp_len(h)
     nseq = L.tracs_pairsnp_nseq(h)

@@ -363,6 +363,109 @@ int tracs_pairsnp(const char *const *fasta, int n_fasta, int n_threads, int dist
     return TRACS_OK;
 }
 
+// (min, max) of each emitted pair: the recombination filter's pairs are (i, j > i), as tracs_pairsnp emits them
+__global__ __launch_bounds__(256) void knn_pair_order_kernel(const unsigned *__restrict__ rows, const unsigned *__restrict__ cols, size_t n,
+                                                             unsigned *__restrict__ lo, unsigned *__restrict__ hi)
+{
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (size_t)gridDim.x * 256) {
+        const unsigned r = rows[t], c = cols[t];
+        lo[t] = r < c ? r : c;
+        hi[t] = r < c ? c : r;
+    }
+}
+
+// k nearest neighbours per sample (include/tracs_hip.h): FASTA -> planes -> row panels of tracs_pairsnp_dense_thr ->
+// tracs_knn_update -> tracs_knn_emit -> (filter) tracs_filter_recomb_pairs on the emitted pairs -> one device-to-host copy.
+int tracs_nearest(const char *const *fasta, int n_fasta, int n_threads, int k, int dist, int filter, tracs_pairsnp_result **out)
+{
+    (void)n_threads;
+    if (!out) { set_error("tracs_nearest: out is NULL"); return TRACS_E_ARG; }
+    *out = nullptr;
+    if (n_fasta < 1 || n_fasta > 2 || !fasta) { set_error("Invalid number of fasta files!"); return TRACS_E_ARG; }
+    if (k < 1 || k > 1024) { set_error("tracs_nearest: k must be in [1, 1024]"); return TRACS_E_ARG; }
+    SigintScope sigint;
+    tracs_alignment *a = nullptr;
+    char *names = nullptr;
+    size_t names_bytes = 0, n0 = 0;
+    int rc = tracs_alignment_from_fasta(fasta, n_fasta, &a, &names, &names_bytes, &n0);
+    if (rc) return rc;
+    auto *res = new tracs_pairsnp_result();
+    res->nseq = a->n; res->L = a->L;
+    { size_t o = 0; for (size_t i = 0; i < a->n; i++) { res->names.emplace_back(names + o); o += res->names.back().size() + 1; } }
+    tracs_free(names);
+    const size_t n = a->n;
+    const size_t i_end = n_fasta == 1 ? n : n0;                     // pair ranges (src/pairsnp.hpp:348-360)
+    const size_t j_start = n_fasta == 1 ? 0 : n0;
+    const size_t n_lists = n_fasta == 1 ? n : n0;                   // two files: lists for the samples of file 0 only
+    unsigned *d_dist = nullptr, *d_nn = nullptr, *d_out = nullptr;
+    void *d_state = nullptr;
+    long long *d_off = nullptr;
+    auto cleanup = [&]() {
+        void *p[] = {d_dist, d_nn, d_out, d_state, d_off};
+        for (void *q : p) if (q) (void)hipFree(q);
+        tracs_alignment_free(a);
+    };
+#define NN_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); delete res; set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
+#define NN_RC(x) do { int r__ = (x); if (r__) { cleanup(); delete res; return r__; } } while (0)
+#define NN_INTERRUPT() do { if (g_sigint) { cleanup(); delete res; set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; } } while (0)
+    StageClock clock;
+    size_t total = 0;
+    if (n >= 2 && i_end > 0 && j_start < n) {
+        NN_CHECK(hipMalloc(&d_state, tracs_knn_state_bytes(n_lists, k)));
+        NN_RC(tracs_knn_init(d_state, n_lists, k, nullptr));
+        // row panels bounded to ~1 GiB per dense matrix, as tracs_pairsnp / tracs_distance_run
+        const size_t panel = std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
+        NN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dist), panel * n * 4));
+        NN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_nn), panel * n * 4));
+        for (size_t r0 = 0; r0 < i_end; r0 += panel) {
+            NN_INTERRUPT();
+            const size_t r1 = std::min(i_end, r0 + panel);
+            unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
+            NN_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
+            NN_RC(tracs_knn_update(bd, bn, n, n, r0, r1, j_start, dist, k, n_fasta == 1 ? 1 : 0, d_state, nullptr));
+        }
+        clock.mark("dense panels + selection");
+        // rows, cols, d, nn, filt (and the filter's ordered pairs) in one block: one copy back
+        const size_t cap = n_lists * (size_t)k;
+        NN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_off), (n_lists + 1) * 8));
+        NN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_out), cap * 4 * (filter ? 7 : 4)));
+        unsigned *c_rows = d_out, *c_cols = d_out + cap, *c_d = d_out + 2 * cap, *c_n = d_out + 3 * cap;
+        NN_RC(tracs_knn_emit(d_state, 0, n_lists, k, reinterpret_cast<int64_t *>(d_off), c_rows, c_cols, c_d, c_n, nullptr));
+        long long tot = 0;
+        NN_CHECK(hipMemcpy(&tot, d_off + n_lists, 8, hipMemcpyDeviceToHost));
+        total = (size_t)tot;
+        clock.mark("emit");
+        if (filter && total) {
+            NN_INTERRUPT();
+            unsigned *c_f = d_out + 4 * cap, *c_lo = d_out + 5 * cap, *c_hi = d_out + 6 * cap;
+            hipLaunchKernelGGL(knn_pair_order_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0, nullptr,
+                               c_rows, c_cols, total, c_lo, c_hi);
+            NN_CHECK(hipGetLastError());
+            NN_RC(tracs_filter_recomb_pairs(a, c_lo, c_hi, c_d, total, c_f, nullptr));
+            clock.mark("recombination filter");
+        }
+        if (total) {
+            const size_t ncol = filter ? 5 : 4;
+            std::vector<unsigned> h32(ncol * total);
+            NN_CHECK(hipMemcpy2D(h32.data(), total * 4, d_out, cap * 4, total * 4, ncol, hipMemcpyDeviceToHost));
+            widen_append(res->rows, h32.data(), total);
+            widen_append(res->cols, h32.data() + total, total);
+            widen_append(res->dist, h32.data() + 2 * total, total);
+            widen_append(res->ncomp, h32.data() + 3 * total, total);
+            if (filter) widen_append(res->filt, h32.data() + 4 * total, total);
+            clock.mark("D2H + widening");
+        }
+    }
+#undef NN_CHECK
+#undef NN_RC
+    if (g_sigint) { cleanup(); delete res; set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+#undef NN_INTERRUPT
+    if (!filter) res->filt.assign(res->rows.size(), 0);
+    cleanup();
+    *out = res;
+    return TRACS_OK;
+}
+
 // ---- `tracs distance` for one alignment, results on the device until the CSV rows (tracs/distance.py:159-258) --------------------------
 // open: read + pack the FASTA(s) (the names are what the caller needs to look the sampling dates up); run: row panel by row panel --
 // dense call (d, compared sites; early out beyond the threshold), transcluster on the panel (P(direct), E(K): src/transcluster.hpp:

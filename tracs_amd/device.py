@@ -235,6 +235,41 @@ def coo_from_dense(dist, ncomp, n, dist_threshold=2147483647, row_begin=0, row_e
     return out
 
 
+def knn_init(n_lists, k, device=None):
+    """An empty k-nearest-neighbour state for samples [0, n_lists) (tracs_knn_init): a torch.uint8 device buffer."""
+    L = _lib.require_gpu()
+    nbytes = L.tracs_knn_state_bytes(int(n_lists), int(k))
+    if nbytes == 0 and n_lists:
+        raise ValueError("knn_init(): k must be in [1, 1024], got %d" % int(k))
+    state = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device if device is not None else "cuda")
+    _lib.check(L.tracs_knn_init(_ptr(state), int(n_lists), int(k), _stream()))
+    return state
+
+
+def knn_update(state, dist, ncomp, n, k, row_begin=0, row_end=None, col_begin=0, dist_threshold=2147483647, symmetric=True,
+               base_row=0):
+    """Merge the panel rows [row_begin, row_end) of dist / ncomp (as tracs_pairsnp_dense writes them; the panels hold rows
+    base_row..) into the lists (tracs_knn_update).  symmetric: one-file mode, column c offers its cells to list c as well."""
+    L = _lib.require_gpu()
+    row_end = n if row_end is None else row_end
+    ld = dist.stride(0)
+    assert ncomp.stride(0) == ld
+    _lib.check(L.tracs_knn_update(_panel_ptr(dist, base_row), _panel_ptr(ncomp, base_row), ld, n, row_begin, row_end, col_begin,
+                                  int(dist_threshold), int(k), int(bool(symmetric)), _ptr(state), _stream()))
+
+
+def knn_emit(state, k, list_begin, list_end):
+    """Lists [list_begin, list_end) -> rows, cols, d, nn (torch.int32 on device), by list, each list by (d, j) (tracs_knn_emit)."""
+    L = _lib.require_gpu()
+    nl = max(0, int(list_end) - int(list_begin))
+    off = torch.zeros(nl + 1, dtype=torch.int64, device=state.device)
+    out = [torch.empty(max(nl * int(k), 1), dtype=torch.int32, device=state.device) for _ in range(4)]
+    _lib.check(L.tracs_knn_emit(_ptr(state), int(list_begin), int(list_end), int(k), _ptr(off), _ptr(out[0]), _ptr(out[1]),
+                                _ptr(out[2]), _ptr(out[3]), _stream()))
+    total = int(off[nl].item())
+    return [o[:total] for o in out]
+
+
 def edges_from_dense_f64(val, dist, n, threshold, dist_threshold=2147483647, row_begin=0, row_end=None, col_begin=0, base_row=0,
                          with_values=False):
     """Cells (i, j > i) with dist <= dist_threshold and val <= threshold, row-major -> rows, cols (torch.int32)[, values f64]:

@@ -12,12 +12,18 @@ import sys
 from datetime import date
 
 from . import _lib
-from .utils import check_positive_float, check_positive_int
+from .utils import check_nearest_k, check_positive_float, check_positive_int
 
 
 def pairsnp_arrays(*args, **kwargs):
     """tracs_amd.api.pairsnp_arrays, imported with numpy on first use (the array route only: --gpus N, incomplete metadata, TRACS_DISTANCE_ARRAYS)"""
     from .api import pairsnp_arrays as f
+    return f(*args, **kwargs)
+
+
+def nearest_arrays(*args, **kwargs):
+    """tracs_amd.api.nearest_arrays, imported with numpy on first use (--nearest K)"""
+    from .api import nearest_arrays as f
     return f(*args, **kwargs)
 
 
@@ -48,6 +54,9 @@ def distance_parser(parser):
                      help="Only output those transmission pairs with a SNP distance <= D")
     snp.add_argument("--filter", dest="recomb_filter", action="store_true", default=False,
                      help="Filter out regions with unusually high SNP distances often caused by HGT")
+    snp.add_argument("--nearest", dest="nearest", type=check_nearest_k, default=None, metavar="K",
+                     help="Only output each sample's K nearest samples (by SNP distance, then input order; 1 <= K <= 1024). "
+                          "With --msa-db: the K nearest database samples of each query sample.  Not in the reference.")
     tr = parser.add_argument_group("Transmission distance options")
     tr.add_argument("--clock_rate", dest="clock_rate", type=check_positive_float, default=1e-3 * 29903,
                     help="clock rate as defined in the transcluster paper (SNPs/genome/year) default=1e-3 * 29903")
@@ -197,6 +206,9 @@ def _pairs_multi_gpu(msas, args, ctx):
 
 
 def distance(args):
+    nearest = getattr(args, "nearest", None)
+    if nearest is not None and getattr(args, "gpus", 1) > 1:
+        raise SystemExit("tracs distance: --nearest runs on one GPU; use --gpus 1")
     from . import multigpu
     if getattr(args, "gpus", 1) > 1 and not multigpu.in_worker():
         rc = multigpu.spawn("tracs_amd", _cli_of(args), args.gpus)     # before anything here has touched the GPU
@@ -241,7 +253,7 @@ def distance(args):
         msas = [msa, args.msa_db] if args.msa_db is not None else [msa]
         t_stage[0] = time.perf_counter()
         ref = os.path.basename(msa).split(".")[0].replace("_combined", "")      # (:208-209)
-        if ctx is None and os.environ.get("TRACS_DISTANCE_ARRAYS") is None:
+        if ctx is None and nearest is None and os.environ.get("TRACS_DISTANCE_ARRAYS") is None:
             # one GPU: the results stay on the device until the CSV rows (with --filter: the filtered distances and the transmission
             # model they drive too)
             for p in msas:
@@ -250,7 +262,10 @@ def distance(args):
             if _rows_on_device(msas, args, dates, ref, stage):
                 logging.info("Saving distances for %s", msa)
                 continue
-        if ctx is None:
+        if nearest is not None:
+            # each sample's K nearest (tracs_nearest), then the array route below: -K drops rows after the selection
+            res = nearest_arrays(fasta=msas, k=nearest, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter)
+        elif ctx is None:
             res = pairsnp_arrays(fasta=msas, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter)
         else:
             res = _pairs_multi_gpu(msas, args, ctx)

@@ -14,3 +14,11 @@ def check_positive_float(value):
     if fvalue <= 0:
         raise argparse.ArgumentTypeError("%s is an invalid positive float value" % value)
     return fvalue
+
+
+def check_nearest_k(value):
+    """--nearest K: 1 <= K <= 1024 (tracs_nearest's bound)."""
+    ivalue = int(value)
+    if ivalue < 1 or ivalue > 1024:
+        raise argparse.ArgumentTypeError("%s is an invalid --nearest value: K must be in [1, 1024]" % value)
+    return ivalue
