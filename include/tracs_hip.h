@@ -218,6 +218,28 @@ int tracs_knn_update(const uint32_t *dist, const uint32_t *ncomp, size_t ld, siz
 int tracs_knn_emit(void *state, size_t list_begin, size_t list_end, int k, int64_t *offsets, uint32_t *rows, uint32_t *cols,
                    uint32_t *d, uint32_t *nn, void *stream);
 
+/* Minimum spanning forest of the offered pairs (csrc/forest.hip; what tracs_distance_forest runs).  Pairs are ordered
+ * by (weight, i, j), i < j their sample indices: uint32 weights as numbers; f64 weights as numbers with -0.0 == +0.0 and every NaN
+ * above +inf.  A total order, so the forest is unique and independent of how the pairs are split into updates.  The state is a device
+ * buffer of tracs_msf_state_bytes(n) bytes for the vertices [0, n): the running forest (< n edges, each with the values its row is
+ * written with: d, nn, filtered d, P, E(K)) and per-vertex scratch.
+ *   tracs_msf_init        the empty forest
+ *   tracs_msf_update_coo  F <- MSF(F u batch): m pairs (rows[t], cols[t]) (device uint32, either order, an endpoint >= n or a loop
+ *                         is skipped) with weight[t] (device; weight_kind 0: uint32, 1: double); e_mask != NULL: only pairs with
+ *                         e_max >= e_mask[t] are eligible (a NaN fails); d / nn / filt / p / e (device, any may be NULL: stored as
+ *                         0) are the values kept with a pair.  Every pair is offered at most once over the updates of one state.
+ *                         n_taken (host, optional): the batch's eligible pairs.  Boruvka rounds on the device, one word read per
+ *                         round; synchronises the stream.
+ *   tracs_msf_emit        *n_edges <- the forest's size; unless NULL, rows < cols, d, nn, filt (device uint32) and p, e (device
+ *                         double), room for n - 1 entries, receive the forest in (i, j) order.  Synchronises the stream.        */
+size_t tracs_msf_state_bytes(size_t n);
+int tracs_msf_init(void *state, size_t n, void *stream);
+int tracs_msf_update_coo(void *state, size_t n, size_t m, const uint32_t *rows, const uint32_t *cols, const void *weight, int weight_kind,
+                         const double *e_mask, double e_max, const uint32_t *d, const uint32_t *nn, const uint32_t *filt,
+                         const double *p, const double *e, uint64_t *n_taken, void *stream);
+int tracs_msf_emit(void *state, size_t n, size_t *n_edges, uint32_t *rows, uint32_t *cols, uint32_t *d, uint32_t *nn, uint32_t *filt,
+                   double *p, double *e, void *stream);
+
 /* Recombination filter (src/pairsnp.hpp:251-318) on emitted pairs.  rows/cols: device uint32[n_pairs];
  * pos_off: device int64[n_pairs+1] = exclusive scan of the pairs' SNP distances; positions: device uint32
  * workspace of pos_off[n_pairs] entries (receives each pair's sorted SNP sites); found[t] = SNP bits seen
@@ -387,6 +409,12 @@ size_t tracs_distance_nseq(const tracs_distance *h);
 const char *tracs_distance_name(const tracs_distance *h, size_t i);
 int tracs_distance_run(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
                        const char *path, const char *ref, int filter, uint64_t *rows_written, uint64_t *n_pairs);
+/*   tracs_distance_forest `--mst WEIGHT` (not in the reference): the pairs tracs_distance_run would write (d <= dist;
+ *                         k_max >= 0 with days: k_max >= E(K)) are eligible; only their minimum spanning forest (tracs_msf_*) under
+ *                         weight 0: d, 1: the filtered d (filter != 0), 2: P(direct), 3: E(K) (2, 3: days != NULL) is appended to
+ *                         `path`, in (i, j) order, each row byte-identical to tracs_distance_run's.  n_eligible: the eligible pairs. */
+int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
+                          int filter, int weight, const char *path, const char *ref, uint64_t *rows_written, uint64_t *n_eligible);
 void tracs_distance_free(tracs_distance *h);
 
 /* Rows of `tracs distance`'s CSV appended to path (tracs/distance.py:206-258; the caller writes the header, :157):

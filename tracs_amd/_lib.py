@@ -38,6 +38,7 @@ SYMBOLS = [
     "tracs_coo_fill_f64", "tracs_distance_open", "tracs_distance_nseq", "tracs_distance_name", "tracs_distance_run", "tracs_distance_free",
     "tracs_warm_up",
     "tracs_nearest", "tracs_knn_state_bytes", "tracs_knn_init", "tracs_knn_update", "tracs_knn_emit",
+    "tracs_distance_forest", "tracs_msf_state_bytes", "tracs_msf_init", "tracs_msf_update_coo", "tracs_msf_emit",
 ]
 
 
@@ -152,6 +153,17 @@ def load():
     L.tracs_knn_update.argtypes = [vp, vp, sz, sz, sz, sz, sz, i32, C.c_int, C.c_int, vp, vp]
     L.tracs_knn_emit.restype = C.c_int
     L.tracs_knn_emit.argtypes = [vp, sz, sz, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.tracs_distance_forest.restype = C.c_int
+    L.tracs_distance_forest.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dbl, dbl, dbl, dbl, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                        u64p, u64p]
+    L.tracs_msf_state_bytes.restype = sz
+    L.tracs_msf_state_bytes.argtypes = [sz]
+    L.tracs_msf_init.restype = C.c_int
+    L.tracs_msf_init.argtypes = [vp, sz, vp]
+    L.tracs_msf_update_coo.restype = C.c_int
+    L.tracs_msf_update_coo.argtypes = [vp, sz, sz, vp, vp, vp, C.c_int, vp, dbl, vp, vp, vp, vp, vp, u64p, vp]
+    L.tracs_msf_emit.restype = C.c_int
+    L.tracs_msf_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp]
     L.tracs_warm_up.restype = None
     L.tracs_warm_up.argtypes = []
     L.tracs_distance_free.restype = None

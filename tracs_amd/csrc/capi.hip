@@ -675,6 +675,133 @@ int tracs_distance_run(tracs_distance *h, int dist, const int32_t *days, double 
     return rc;
 }
 
+// `tracs distance --mst WEIGHT` for one alignment (include/tracs_hip.h): the panel loop of tracs_distance_run up to
+// the COO of the panel's pairs within the threshold (with P and E(K), --filter's filtered distances and their P and E(K)), then
+// tracs_msf_update_coo instead of the rows; after the last panel the forest is emitted and written through the same row writer.
+int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
+                          int filter, int weight, const char *path, const char *ref, uint64_t *rows_written, uint64_t *n_eligible)
+{
+    if (rows_written) *rows_written = 0;
+    if (n_eligible) *n_eligible = 0;
+    if (!h || !h->a || !path || !ref) { set_error("tracs_distance_forest: NULL argument"); return TRACS_E_ARG; }
+    if (weight < 0 || weight > 3) { set_error("tracs_distance_forest: weight must be 0 (snp), 1 (filter), 2 (direct) or 3 (expectedK)"); return TRACS_E_ARG; }
+    if (weight == 1 && !filter) { set_error("tracs_distance_forest: the filter weight needs filter != 0"); return TRACS_E_ARG; }
+    if (weight >= 2 && !days) { set_error("tracs_distance_forest: the direct and expectedK weights need sampling dates"); return TRACS_E_ARG; }
+    SigintScope sigint;
+    tracs_alignment *a = h->a;
+    const size_t n = a->n;
+    const size_t i_end = h->n_fasta == 1 ? n : h->n0;               // pair ranges (:348-360)
+    const size_t j_start = h->n_fasta == 1 ? 0 : h->n0;
+    const bool with_dates = days != nullptr;
+    const bool dense_tc = with_dates && !filter;
+    // rows per panel (TRACS_FOREST_PANEL_ROWS: diagnostics -- small panels in tests, so that the forest crosses panel boundaries)
+    static const size_t PANEL_ROWS = [] { const char *e = std::getenv("TRACS_FOREST_PANEL_ROWS"); const long long v = e ? std::atoll(e) : 0; return v >= 1 ? (size_t)v : (size_t)0; }();
+    unsigned *d_dist = nullptr, *d_nn = nullptr, *d_coo = nullptr;
+    double *d_p = nullptr, *d_e = nullptr, *d_cp = nullptr;
+    int *d_days = nullptr;
+    long long *d_off = nullptr;
+    void *d_state = nullptr;
+    tracs::DistanceRowWriter writer;
+    auto cleanup = [&]() {
+        void *q[] = {d_dist, d_nn, d_coo, d_p, d_e, d_cp, d_days, d_off, d_state};
+        for (void *x : q) if (x) (void)hipFree(x);
+    };
+#define MF_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
+#define MF_RC(x) do { int r__ = (x); if (r__) { cleanup(); return r__; } } while (0)
+    MF_RC(writer.open(path, h->name_ptr.data(), h->name_ptr.size(), ref));
+    StageClock clock;
+    uint64_t eligible = 0;
+    const double e_max = (with_dates && k_max >= 0.0) ? k_max : -1.0;
+    if (n >= 2 && i_end > 0 && j_start < n) {
+        const size_t panel = PANEL_ROWS ? std::min(PANEL_ROWS, i_end)
+                                        : std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
+        MF_CHECK(hipMalloc(&d_state, tracs_msf_state_bytes(n)));
+        MF_RC(tracs_msf_init(d_state, n, nullptr));
+        MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dist), panel * n * 4));
+        MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_nn), panel * n * 4));
+        MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_off), (panel + 1) * 8));
+        if (dense_tc) {
+            MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_p), panel * n * 8));
+            MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_e), panel * n * 8));
+        }
+        if (with_dates) {
+            MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_days), n * 4));
+            MF_CHECK(hipMemcpy(d_days, days, n * 4, hipMemcpyHostToDevice));
+        }
+        const size_t n32 = filter ? 5 : 4;
+        size_t cap = 0;
+        for (size_t r0 = 0; r0 < i_end; r0 += panel) {
+            if (g_sigint) { cleanup(); set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+            const size_t r1 = std::min(i_end, r0 + panel);
+            unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
+            double *bp = dense_tc ? d_p - r0 * n : nullptr, *be = dense_tc ? d_e - r0 * n : nullptr;
+            MF_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
+            if (dense_tc)
+                MF_RC(tracs_trans_dist_dense(bd, n, n, r0, r1, j_start, dist, d_days, lamb, beta, precision, 1, bp, be, nullptr));
+            MF_RC(tracs_coo_count(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), nullptr));
+            long long total = 0;
+            MF_CHECK(hipMemcpy(&total, d_off + (r1 - r0), 8, hipMemcpyDeviceToHost));
+            if (total <= 0) continue;
+            if ((size_t)total > cap) {
+                if (d_coo) MF_CHECK(hipFree(d_coo));
+                if (d_cp) MF_CHECK(hipFree(d_cp));
+                d_coo = nullptr; d_cp = nullptr;
+                cap = (size_t)total;
+                MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_coo), cap * 4 * n32));
+                if (with_dates) MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cp), cap * (filter ? 24 : 16)));
+            }
+            unsigned *c_rows = d_coo, *c_cols = d_coo + cap, *c_d = d_coo + 2 * cap, *c_n = d_coo + 3 * cap, *c_f = filter ? d_coo + 4 * cap : nullptr;
+            double *c_p = d_cp, *c_e = with_dates ? d_cp + cap : nullptr, *c_delta = (with_dates && filter) ? d_cp + 2 * cap : nullptr;
+            MF_RC(tracs_coo_fill(bd, bn, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), c_rows, c_cols, c_d, c_n, nullptr));
+            if (dense_tc)
+                MF_RC(tracs_coo_fill_f64(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), bp, be, c_p, c_e, nullptr));
+            if (filter) {
+                MF_RC(tracs_filter_recomb_pairs(a, c_rows, c_cols, c_d, (size_t)total, c_f, nullptr));
+                if (with_dates) {
+                    hipLaunchKernelGGL(coo_delta_kernel, dim3((unsigned)std::min<size_t>(((size_t)total + 255) / 256, 65535)), dim3(256), 0, nullptr, c_rows, c_cols,
+                                       d_days, (size_t)total, c_delta);
+                    MF_RC(tracs_trans_dist_device(reinterpret_cast<const int32_t *>(c_f), c_delta, (size_t)total, lamb, beta, precision, 1, c_p, c_e, nullptr));
+                }
+            }
+            // the weight the cluster step reads: column 3 (d), 6 (filtered d), 4 (P), 5 (E(K)); -K drops pairs with E(K) above it or NaN
+            const void *wv = weight == 0 ? (const void *)c_d : weight == 1 ? (const void *)c_f : weight == 2 ? (const void *)c_p : (const void *)c_e;
+            uint64_t taken = 0;
+            MF_RC(tracs_msf_update_coo(d_state, n, (size_t)total, c_rows, c_cols, wv, weight >= 2 ? 1 : 0, e_max >= 0.0 ? c_e : nullptr, e_max,
+                                       c_d, c_n, c_f, c_p, c_e, &taken, nullptr));
+            eligible += taken;
+        }
+        clock.mark("dense panels + transcluster + forest updates");
+        size_t nf = 0;
+        MF_RC(tracs_msf_emit(d_state, n, &nf, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        if (nf) {
+            // the forest's rows: rows, cols, d, nn, filt (uint32), P, E(K) (f64) -- < n of them
+            if (d_coo) MF_CHECK(hipFree(d_coo));
+            if (d_cp) MF_CHECK(hipFree(d_cp));
+            d_coo = nullptr; d_cp = nullptr;
+            MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_coo), nf * 4 * 5));
+            MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cp), nf * 16));
+            MF_RC(tracs_msf_emit(d_state, n, &nf, d_coo, d_coo + nf, d_coo + 2 * nf, d_coo + 3 * nf, d_coo + 4 * nf, d_cp, d_cp + nf, nullptr));
+            std::vector<uint32_t> h32(nf * 5);
+            std::vector<double> h64(nf * 2);
+            MF_CHECK(hipMemcpy(h32.data(), d_coo, nf * 20, hipMemcpyDeviceToHost));
+            MF_CHECK(hipMemcpy(h64.data(), d_cp, nf * 16, hipMemcpyDeviceToHost));
+            const uint32_t *hr = h32.data(), *hc = hr + nf, *hd = hr + 2 * nf, *hn = hr + 3 * nf, *hf = hr + 4 * nf;
+            // the filtered column as the full run writes it: --filter: the filtered distances; else metadata on: "NA", off: zeros (:240-258)
+            MF_RC(writer.append_u32(hr, hc, hd, filter ? hf : (with_dates ? nullptr : hf), hn, days, with_dates ? h64.data() : nullptr,
+                                    with_dates ? h64.data() + nf : nullptr, nf, with_dates ? 1 : 0, -1.0));
+        }
+        clock.mark("forest rows: emit, device -> host, format, write");
+    }
+#undef MF_CHECK
+#undef MF_RC
+    cleanup();
+    const int rc = writer.close();
+    if (rows_written) *rows_written = writer.written();
+    if (n_eligible) *n_eligible = eligible;
+    if (g_sigint) { set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+    return rc;
+}
+
 size_t tracs_pairsnp_len(const tracs_pairsnp_result *r) { return r ? r->rows.size() : 0; }
 size_t tracs_pairsnp_nseq(const tracs_pairsnp_result *r) { return r ? r->nseq : 0; }
 size_t tracs_pairsnp_seqlen(const tracs_pairsnp_result *r) { return r ? r->L : 0; }

@@ -270,6 +270,50 @@ def knn_emit(state, k, list_begin, list_end):
     return [o[:total] for o in out]
 
 
+def msf_init(n, device=None):
+    """An empty minimum-spanning-forest state for the vertices [0, n) (tracs_msf_init): a torch.uint8 device buffer."""
+    L = _lib.require_gpu()
+    state = torch.empty(max(L.tracs_msf_state_bytes(int(n)), 1), dtype=torch.uint8, device=device if device is not None else "cuda")
+    _lib.check(L.tracs_msf_init(_ptr(state), int(n), _stream()))
+    return state
+
+
+def msf_update(state, n, rows, cols, weight, e_mask=None, e_max=-1.0, d=None, nn=None, filt=None, p=None, e=None):
+    """F <- MSF(F u batch) (tracs_msf_update_coo): rows / cols int32 or uint32 device tensors, weight uint32-valued (int32 / uint32
+    tensor, read as unsigned) or float64; e_mask (float64): only pairs with e_max >= e_mask are eligible.  d, nn, filt (32-bit) and
+    p, e (float64) are the values kept with a pair.  -> the batch's eligible pairs."""
+    L = _lib.require_gpu()
+    m = int(rows.numel())
+    assert cols.numel() == m and weight.numel() == m
+    for t in (rows, cols, weight, e_mask, d, nn, filt, p, e):
+        assert t is None or (t.is_contiguous() and t.numel() == m)
+    for t in (rows, cols, d, nn, filt):
+        assert t is None or t.element_size() == 4
+    for t in (e_mask, p, e):
+        assert t is None or t.dtype == torch.float64
+    if weight.dtype == torch.float64:
+        kind = 1
+    else:
+        assert weight.element_size() == 4 and not weight.is_floating_point()
+        kind = 0
+    taken = C.c_uint64(0)
+    _lib.check(L.tracs_msf_update_coo(_ptr(state), int(n), m, _ptr(rows), _ptr(cols), _ptr(weight), kind, _ptr(e_mask), float(e_max),
+                                      _ptr(d), _ptr(nn), _ptr(filt), _ptr(p), _ptr(e), C.byref(taken), _stream()))
+    return taken.value
+
+
+def msf_emit(state, n):
+    """The forest in (i, j) order (tracs_msf_emit): rows < cols, d, nn, filt (torch.int32) and p, e (torch.float64) on the device."""
+    L = _lib.require_gpu()
+    cnt = C.c_size_t(0)
+    _lib.check(L.tracs_msf_emit(_ptr(state), int(n), C.byref(cnt), *([C.c_void_p(0)] * 7), _stream()))
+    k = cnt.value
+    u = [torch.empty(max(k, 1), dtype=torch.int32, device=state.device) for _ in range(5)]
+    f = [torch.empty(max(k, 1), dtype=torch.float64, device=state.device) for _ in range(2)]
+    _lib.check(L.tracs_msf_emit(_ptr(state), int(n), C.byref(cnt), *[_ptr(t) for t in u + f], _stream()))
+    return [t[:k] for t in u + f]
+
+
 def edges_from_dense_f64(val, dist, n, threshold, dist_threshold=2147483647, row_begin=0, row_end=None, col_begin=0, base_row=0,
                          with_values=False):
     """Cells (i, j > i) with dist <= dist_threshold and val <= threshold, row-major -> rows, cols (torch.int32)[, values f64]:

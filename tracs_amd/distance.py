@@ -31,6 +31,9 @@ def calculate_trans_prob(*args, **kwargs):
     from .transcluster import calculate_trans_prob as f
     return f(*args, **kwargs)
 
+# --mst WEIGHT -> tracs_distance_forest's weight (the columns `cluster -D` reads: snp 3, filter 6, direct 4, expectedK 5)
+MST_WEIGHTS = {"snp": 0, "filter": 1, "direct": 2, "expectedK": 3}
+
 HEADER = ("sampleA,sampleB,date difference,SNP distance,transmission distance,expected K,"
           "filtered SNP distance,sites considered,MSA file\n")
 
@@ -57,6 +60,12 @@ def distance_parser(parser):
     snp.add_argument("--nearest", dest="nearest", type=check_nearest_k, default=None, metavar="K",
                      help="Only output each sample's K nearest samples (by SNP distance, then input order; 1 <= K <= 1024). "
                           "With --msa-db: the K nearest database samples of each query sample.  Not in the reference.")
+    snp.add_argument("--mst", dest="mst", choices=list(MST_WEIGHTS), default=None, metavar="WEIGHT",
+                     help="Only output the minimum spanning forest of the pairs the run would write, under the column that "
+                          "`cluster -D WEIGHT` reads (snp | filter | direct | expectedK; filter needs --filter, direct and expectedK "
+                          "need --meta): at most n - 1 rows, each identical to its row in the full output.  For every threshold T, "
+                          "`cluster -c T -D WEIGHT` on this file puts the same samples into the same clusters as on the full file "
+                          "(cluster numbers may be permuted).  With --meta every sample needs a date.  Not in the reference.")
     tr = parser.add_argument_group("Transmission distance options")
     tr.add_argument("--clock_rate", dest="clock_rate", type=check_positive_float, default=1e-3 * 29903,
                     help="clock rate as defined in the transcluster paper (SNPs/genome/year) default=1e-3 * 29903")
@@ -150,6 +159,55 @@ def _rows_on_device(msas, args, dates, ref, stage):
         L.tracs_distance_free(h)
 
 
+def _forest_on_device(msas, args, dates, ref, stage):
+    """--mst WEIGHT for one alignment (tracs_distance_open / _forest: include/tracs_hip.h): the panel loop of _rows_on_device up to the
+    pairs within the threshold with their P and E(K), then the minimum spanning forest of the eligible pairs on the device; only its
+    rows are formatted and appended.  With metadata every sample needs a date (the full run's array route has KeyError rules of its
+    own instead)."""
+    L = _lib.require_gpu()
+    arr = (C.c_char_p * len(msas))(*[os.fsencode(p) for p in msas])
+    h = C.c_void_p()
+    _lib.check(L.tracs_distance_open(arr, len(msas), C.byref(h)))
+    try:
+        stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
+        days = None
+        if dates is not None:
+            n = L.tracs_distance_nseq(h)
+            epoch = date(1970, 1, 1)
+            got = []
+            for i in range(n):
+                name = L.tracs_distance_name(h, i).decode("utf-8", "replace")
+                if name not in dates:
+                    raise SystemExit("tracs distance --mst: sample '%s' has no sampling date in %s" % (name, args.metadata))
+                got.append((dates[name][1] - epoch).days)
+            days = (C.c_int32 * max(n, 1))(*got)
+            logging.info("Inferring transmission probabilities for %s", msas[0])
+        written, eligible = C.c_uint64(0), C.c_uint64(0)
+        kmax = -1.0 if (args.trans_threshold is None or dates is None) else float(args.trans_threshold)
+        _lib.check(L.tracs_distance_forest(h, int(args.snp_threshold), days, float(args.clock_rate), float(args.trans_rate),
+                                           float(args.precision), kmax, int(bool(args.recomb_filter)), MST_WEIGHTS[args.mst],
+                                           os.fsencode(args.output_file), ref.encode(), C.byref(written), C.byref(eligible)))
+        stage("[sum] tracs_distance_forest (dense panels, transcluster, forest: %d eligible pairs, %d rows written)"
+              % (eligible.value, written.value))
+    finally:
+        L.tracs_distance_free(h)
+
+
+def check_mst_args(args):
+    """--mst's argument checks, before anything touches the GPU (SystemExit with the message)."""
+    mst = getattr(args, "mst", None)
+    if mst is None:
+        return
+    if getattr(args, "nearest", None) is not None:
+        raise SystemExit("tracs distance: --mst and --nearest cannot be combined")
+    if getattr(args, "gpus", 1) > 1:
+        raise SystemExit("tracs distance: --mst runs on one GPU; use --gpus 1")
+    if mst == "filter" and not args.recomb_filter:
+        raise SystemExit("tracs distance: --mst filter needs --filter (the filtered SNP distance column)")
+    if mst in ("direct", "expectedK") and args.metadata is None:
+        raise SystemExit("tracs distance: --mst %s needs --meta (the sampling dates that transmission distances come from)" % mst)
+
+
 def _cli_of(args):
     """The command line that reproduces `args` (the multi-GPU path re-launches itself, one process per GPU)."""
     argv = ["distance", "--msa"] + list(args.msa_files) + ["-o", args.output_file, "-D", str(args.snp_threshold),
@@ -206,6 +264,8 @@ def _pairs_multi_gpu(msas, args, ctx):
 
 
 def distance(args):
+    check_mst_args(args)
+    mst = getattr(args, "mst", None)
     nearest = getattr(args, "nearest", None)
     if nearest is not None and getattr(args, "gpus", 1) > 1:
         raise SystemExit("tracs distance: --nearest runs on one GPU; use --gpus 1")
@@ -253,6 +313,14 @@ def distance(args):
         msas = [msa, args.msa_db] if args.msa_db is not None else [msa]
         t_stage[0] = time.perf_counter()
         ref = os.path.basename(msa).split(".")[0].replace("_combined", "")      # (:208-209)
+        if mst is not None:
+            # the minimum spanning forest of the pairs the full run would write (one GPU, on the device until its rows)
+            for p in msas:
+                if not os.path.exists(p):
+                    raise FileNotFoundError(p)
+            _forest_on_device(msas, args, dates, ref, stage)
+            logging.info("Saving the minimum spanning forest for %s", msa)
+            continue
         if ctx is None and nearest is None and os.environ.get("TRACS_DISTANCE_ARRAYS") is None:
             # one GPU: the results stay on the device until the CSV rows (with --filter: the filtered distances and the transmission
             # model they drive too)
