@@ -240,6 +240,28 @@ int tracs_msf_update_coo(void *state, size_t n, size_t m, const uint32_t *rows, 
 int tracs_msf_emit(void *state, size_t n, size_t *n_edges, uint32_t *rows, uint32_t *cols, uint32_t *d, uint32_t *nn, uint32_t *filt,
                    double *p, double *e, void *stream);
 
+/* Histogram of pair values over dense panels (csrc/histogram.hip; what tracs_distance_histogram runs).  The state is
+ * a device buffer of tracs_hist_state_bytes(n_bins) bytes: per value v in [0, n_bins) three 64-bit counts -- pairs `within` a group
+ * (both samples grouped, equal labels), `between` groups (both grouped, labels differ) and `ungrouped` (a sample with label < 0, or
+ * group == NULL) -- plus a count of offered values >= n_bins.  group: device int32[n], or NULL.  Counts are exact; the state is a
+ * sum, so it does not depend on how the pairs are split into updates.  1 <= n_bins <= 2^31 (else TRACS_E_ARG; _state_bytes: 0).
+ *   tracs_hist_init        every count 0
+ *   tracs_hist_update      count the cells of tracs_pairsnp_dense[_thr] in the panel rows [row_begin, row_end): columns
+ *                          j >= max(col_begin, i + 1), indexed by ABSOLUTE row, leading dimension ld, n < 2^30.  A cell is counted
+ *                          iff it is, read as unsigned, <= dist_threshold (tracs_coo_count's rule).  One launch, the panel read once.
+ *   tracs_hist_update_coo  count m listed pairs (rows[t], cols[t]) (device uint32; only read with group != NULL) with value val[t]
+ *   tracs_hist_emit        *n_rows <- the non-empty bins; unless all four are NULL, value (device uint32) and within / between /
+ *                          ungrouped (device uint64), room for *n_rows entries each (ask with NULLs first), receive them ascending
+ *                          by value.  Fails with a message when a value >= n_bins was offered.  Synchronises the stream.          */
+size_t tracs_hist_state_bytes(size_t n_bins);
+int tracs_hist_init(void *state, size_t n_bins, void *stream);
+int tracs_hist_update(const uint32_t *dist, size_t ld, size_t n, size_t row_begin, size_t row_end, size_t col_begin,
+                      int32_t dist_threshold, const int32_t *group, void *state, size_t n_bins, void *stream);
+int tracs_hist_update_coo(const uint32_t *rows, const uint32_t *cols, const uint32_t *val, size_t m, const int32_t *group,
+                          void *state, size_t n_bins, void *stream);
+int tracs_hist_emit(void *state, size_t n_bins, size_t *n_rows, uint32_t *value, uint64_t *within, uint64_t *between,
+                    uint64_t *ungrouped, void *stream);
+
 /* Recombination filter (src/pairsnp.hpp:251-318) on emitted pairs.  rows/cols: device uint32[n_pairs];
  * pos_off: device int64[n_pairs+1] = exclusive scan of the pairs' SNP distances; positions: device uint32
  * workspace of pos_off[n_pairs] entries (receives each pair's sorted SNP sites); found[t] = SNP bits seen
@@ -415,6 +437,14 @@ int tracs_distance_run(tracs_distance *h, int dist, const int32_t *days, double 
  *                         `path`, in (i, j) order, each row byte-identical to tracs_distance_run's.  n_eligible: the eligible pairs. */
 int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
                           int filter, int weight, const char *path, const char *ref, uint64_t *rows_written, uint64_t *n_eligible);
+/*   tracs_distance_histogram `--histogram` (not in the reference): tracs_distance_run's panel loop without rows.  The
+ *                         pairs it would write (d <= dist) are counted by SNP distance and class (tracs_hist_*; group: HOST int32[n]
+ *                         in the order of tracs_distance_name, label < 0: ungrouped; NULL: every pair ungrouped) in min(L, dist) + 1
+ *                         bins; filter != 0: a second histogram takes their filtered distances (tracs_filter_recomb_pairs).  Appends
+ *                         "snp,<d>,<within>,<between>,<ungrouped>,<ref>" per non-empty bin, ascending, then the same with "filter".
+ *                         n_eligible: the pairs counted (the rows tracs_distance_run would write without metadata).              */
+int tracs_distance_histogram(tracs_distance *h, int dist, int filter, const int32_t *group, const char *path, const char *ref,
+                             uint64_t *n_eligible, uint64_t *rows_written);
 void tracs_distance_free(tracs_distance *h);
 
 /* Rows of `tracs distance`'s CSV appended to path (tracs/distance.py:206-258; the caller writes the header, :157):

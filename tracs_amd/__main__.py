@@ -1,15 +1,16 @@
 """`tracs <command>` for the commands on the GPU distance path (reference: tracs/__main__.py:15-57).
 
 `distance` and `cluster` are the hot path; `combine` and `align-post` are the data formats either side of it (SURVEY.md 8f
-row 4: `align-post` is the part of `tracs align` after the pileup, tracs/align.py:444-647, with that command's option names).
-Read mapping (`align` proper), threshold/build-db/pipe/plot are outside the scope of this repository and are reported as such.
+row 4: `align-post` is the part of `tracs align` after the pileup, tracs/align.py:444-647, with that command's option names);
+`threshold` fits the SNP cut-off between them, from two distance files or from the histogram `distance --histogram` counts.
+Read mapping (`align` proper), build-db/pipe/plot are outside the scope of this repository and are reported as such.
 """
 import argparse
 import sys
 
 from . import __version__
 
-OUT_OF_SCOPE = ["align", "threshold", "build-db", "pipe", "plot"]
+OUT_OF_SCOPE = ["align", "build-db", "pipe", "plot"]
 
 
 def align_post_parser(parser):
@@ -48,7 +49,7 @@ def main():
     sub = parser.add_subparsers(title="subcommands", dest="command")
     # (a command's module is imported when that command -- or the help -- is asked for: `tracs distance` on ten isolates is 0.4 s, of
     # which the interpreter and the imports are most; the cluster command's numpy is not its business)
-    want = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ("distance", "cluster", "combine", "align-post") else None
+    want = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ("distance", "cluster", "combine", "align-post", "threshold") else None
 
     def register(name, get):
         if want is None or want == name:
@@ -65,10 +66,14 @@ def main():
     def _combine():
         from .combine import combine_parser
         return combine_parser
+    def _threshold():
+        from .threshold import threshold_parser
+        return threshold_parser
     register("distance", _distance)
     register("cluster", _cluster)
     register("combine", _combine)
     register("align-post", lambda: align_post_parser)
+    register("threshold", _threshold)
     if len(sys.argv) > 1 and sys.argv[1] in OUT_OF_SCOPE:
         parser.error("'%s' is not part of the MI355X distance path; use the reference TRACS for it" % sys.argv[1])
     args = parser.parse_args()

@@ -39,6 +39,7 @@ SYMBOLS = [
     "tracs_warm_up",
     "tracs_nearest", "tracs_knn_state_bytes", "tracs_knn_init", "tracs_knn_update", "tracs_knn_emit",
     "tracs_distance_forest", "tracs_msf_state_bytes", "tracs_msf_init", "tracs_msf_update_coo", "tracs_msf_emit",
+    "tracs_distance_histogram", "tracs_hist_state_bytes", "tracs_hist_init", "tracs_hist_update", "tracs_hist_update_coo", "tracs_hist_emit",
 ]
 
 
@@ -164,6 +165,20 @@ def load():
     L.tracs_msf_update_coo.argtypes = [vp, sz, sz, vp, vp, vp, C.c_int, vp, dbl, vp, vp, vp, vp, vp, u64p, vp]
     L.tracs_msf_emit.restype = C.c_int
     L.tracs_msf_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tracs_distance_histogram.restype = C.c_int
+    L.tracs_distance_histogram.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_char_p, C.c_char_p, u64p, u64p]
+    L.tracs_hist_state_bytes.restype = sz
+    L.tracs_hist_state_bytes.argtypes = [sz]
+    L.tracs_hist_init.restype = C.c_int
+    L.tracs_hist_init.argtypes = [vp, sz, vp]
+    L.tracs_hist_update.restype = C.c_int
+    L.tracs_hist_update.argtypes = [vp, sz, sz, sz, sz, sz, i32, vp, vp, sz, vp]
+    L.tracs_hist_update_coo.restype = C.c_int
+    L.tracs_hist_update_coo.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
+    L.tracs_hist_emit.restype = C.c_int
+    L.tracs_hist_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp]
+    L.tracs_debug_hist_routes.restype = C.c_int
+    L.tracs_debug_hist_routes.argtypes = [vp, C.POINTER(C.c_double)]
     L.tracs_warm_up.restype = None
     L.tracs_warm_up.argtypes = []
     L.tracs_distance_free.restype = None

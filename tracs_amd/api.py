@@ -56,6 +56,81 @@ def nearest_arrays(fasta, k, n_threads=1, dist=2147483647, filter=False):
     return _result_arrays(L, h)
 
 
+def group_labels(names, groups):
+    """int32 label per sample name for tracs_distance_histogram: groups maps name -> label (any hashable; missing or None:
+    ungrouped = -1); labels are numbered in order of first appearance.  None -> None."""
+    if groups is None:
+        return None
+    number = {}
+    out = np.full(len(names), -1, np.int32)
+    for i, name in enumerate(names):
+        lab = groups.get(name)
+        if lab is not None:
+            out[i] = number.setdefault(lab, len(number))
+    return out
+
+
+def read_histogram_rows(path):
+    """The rows of a `distance --histogram` file (header skipped) -> {column: {ref: (value, within, between, ungrouped)}}, numpy
+    arrays (uint32; uint64) in file order."""
+    got = {}
+    with open(path, "r") as fh:
+        next(fh, None)
+        for ln, line in enumerate(fh, 2):
+            f = line.rstrip("\n").split(",", 5)
+            if len(f) != 6:
+                raise ValueError("%s line %d: expected 6 fields (column,distance,within,between,ungrouped,MSA file)" % (path, ln))
+            got.setdefault(f[0], {}).setdefault(f[5], []).append((int(f[1]), int(f[2]), int(f[3]), int(f[4])))
+    out = {}
+    for col, refs in got.items():
+        for ref, rows in refs.items():
+            a = np.array(rows, dtype=np.uint64).reshape(-1, 4)
+            out.setdefault(col, {})[ref] = (a[:, 0].astype(np.uint32), a[:, 1].copy(), a[:, 2].copy(), a[:, 3].copy())
+    return out
+
+
+def distance_histogram(fasta, dist=2147483647, filter=False, groups=None):
+    """How many pairs have each SNP distance (tracs_distance_histogram, include/tracs_hip.h): the pairs pairsnp_arrays(fasta, dist=dist)
+    returns, counted on the GPU without being emitted.  -> (names, {"snp": h[, "filter": h]}) with h = {"value": uint32[], "within":
+    uint64[], "between": uint64[], "ungrouped": uint64[]}, the non-empty bins ascending.  groups: mapping sample name -> label (any
+    hashable; missing or None: ungrouped); without it every pair is `ungrouped`.  filter: also the histogram of the filtered
+    distances of the same pairs."""
+    import tempfile
+    paths = _paths(fasta)
+    if len(paths) < 1 or len(paths) > 2:
+        raise RuntimeError("Invalid number of fasta files!")
+    for p in paths:
+        if not os.path.exists(p):
+            raise FileNotFoundError(os.fsdecode(p))
+    L = _lib.require_gpu()
+    arr = (C.c_char_p * len(paths))(*paths)
+    h = C.c_void_p()
+    _lib.check(L.tracs_distance_open(arr, len(paths), C.byref(h)))
+    try:
+        names = [L.tracs_distance_name(h, i).decode("utf-8", "replace") for i in range(L.tracs_distance_nseq(h))]
+        labels = group_labels(names, groups)
+        gp = labels.ctypes.data_as(C.POINTER(C.c_int32)) if labels is not None and len(labels) else None
+        fd, tmp = tempfile.mkstemp(suffix=".csv")
+        os.close(fd)
+        try:
+            with open(tmp, "w") as fh:
+                fh.write("header\n")
+            eligible, written = C.c_uint64(0), C.c_uint64(0)
+            _lib.check(L.tracs_distance_histogram(h, int(dist), int(bool(filter)), gp, os.fsencode(tmp), b"x", C.byref(eligible),
+                                                  C.byref(written)))
+            rows = read_histogram_rows(tmp)
+        finally:
+            os.unlink(tmp)
+    finally:
+        L.tracs_distance_free(h)
+    empty = (np.zeros(0, np.uint32),) + tuple(np.zeros(0, np.uint64) for _ in range(3))
+    out = {}
+    for col in ("snp", "filter") if filter else ("snp",):
+        v, w, b, u = rows.get(col, {}).get("x", empty)
+        out[col] = {"value": v, "within": w, "between": b, "ungrouped": u}
+    return names, out
+
+
 def _result_arrays(L, h):
     """(rows, cols, distances, names, filt_distances, n_compared) of a tracs_pairsnp_result, which they then own."""
     owner = _ResultOwner(L, h)

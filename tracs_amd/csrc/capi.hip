@@ -802,6 +802,125 @@ int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, doub
     return rc;
 }
 
+// `tracs distance --histogram` for one alignment (include/tracs_hip.h): the panel loop of tracs_distance_run with
+// tracs_hist_update on each dense panel instead of the rows; with --filter the panel's pairs within the threshold are extracted and
+// filtered as tracs_distance_run does, and a second state counts their filtered distances.  What crosses to the host is the
+// non-empty bins.
+int tracs_distance_histogram(tracs_distance *h, int dist, int filter, const int32_t *group, const char *path, const char *ref,
+                             uint64_t *n_eligible, uint64_t *rows_written)
+{
+    if (rows_written) *rows_written = 0;
+    if (n_eligible) *n_eligible = 0;
+    if (!h || !h->a || !path || !ref) { set_error("tracs_distance_histogram: NULL argument"); return TRACS_E_ARG; }
+    if (dist < 0) { set_error("tracs_distance_histogram: dist must not be negative"); return TRACS_E_ARG; }
+    SigintScope sigint;
+    tracs_alignment *a = h->a;
+    const size_t n = a->n;
+    const size_t i_end = h->n_fasta == 1 ? n : h->n0;               // pair ranges (:348-360)
+    const size_t j_start = h->n_fasta == 1 ? 0 : h->n0;
+    const size_t n_bins = std::min<size_t>(a->L, (size_t)dist) + 1;  // d <= L and d <= dist: no eligible value falls outside
+    // rows per panel (TRACS_FOREST_PANEL_ROWS: diagnostics -- small panels in tests, as tracs_distance_forest)
+    static const size_t PANEL_ROWS = [] { const char *e = std::getenv("TRACS_FOREST_PANEL_ROWS"); const long long v = e ? std::atoll(e) : 0; return v >= 1 ? (size_t)v : (size_t)0; }();
+    unsigned *d_dist = nullptr, *d_nn = nullptr, *d_coo = nullptr, *d_val = nullptr;
+    int *d_group = nullptr;
+    long long *d_off = nullptr;
+    void *d_state[2] = {nullptr, nullptr};
+    uint64_t *d_cnt = nullptr;
+    auto cleanup = [&]() {
+        void *q[] = {d_dist, d_nn, d_coo, d_val, d_group, d_off, d_state[0], d_state[1], d_cnt};
+        for (void *x : q) if (x) (void)hipFree(x);
+    };
+#define HG_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
+#define HG_RC(x) do { int r__ = (x); if (r__) { cleanup(); return r__; } } while (0)
+    FILE *fp = std::fopen(path, "ab");
+    if (!fp) { set_error(std::string("cannot open ") + path + " for appending"); return TRACS_E_OPEN; }
+    struct Closer { FILE *&f; ~Closer() { if (f) std::fclose(f); } } closer{fp};
+    StageClock clock;
+    uint64_t eligible = 0, written = 0;
+    if (n >= 2 && i_end > 0 && j_start < n) {
+        const size_t panel = PANEL_ROWS ? std::min(PANEL_ROWS, i_end)
+                                        : std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
+        const int n_states = filter ? 2 : 1;
+        for (int s = 0; s < n_states; s++) {
+            HG_CHECK(hipMalloc(&d_state[s], tracs_hist_state_bytes(n_bins)));
+            HG_RC(tracs_hist_init(d_state[s], n_bins, nullptr));
+        }
+        HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dist), panel * n * 4));
+        HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_nn), panel * n * 4));
+        if (group) {
+            HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_group), n * 4));
+            HG_CHECK(hipMemcpy(d_group, group, n * 4, hipMemcpyHostToDevice));
+        }
+        if (filter) HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_off), (panel + 1) * 8));
+        size_t cap = 0;
+        for (size_t r0 = 0; r0 < i_end; r0 += panel) {
+            if (g_sigint) { cleanup(); set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+            const size_t r1 = std::min(i_end, r0 + panel);
+            unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
+            HG_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
+            HG_RC(tracs_hist_update(bd, n, n, r0, r1, j_start, dist, d_group, d_state[0], n_bins, nullptr));
+            if (!filter) continue;
+            // the filtered distances of the panel's eligible pairs (src/pairsnp.hpp:405-413), as tracs_distance_run takes them
+            HG_RC(tracs_coo_count(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), nullptr));
+            long long total = 0;
+            HG_CHECK(hipMemcpy(&total, d_off + (r1 - r0), 8, hipMemcpyDeviceToHost));
+            if (total <= 0) continue;
+            if ((size_t)total > cap) {
+                if (d_coo) { void *old = d_coo; d_coo = nullptr; HG_CHECK(hipFree(old)); }
+                cap = (size_t)total;
+                HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_coo), cap * 4 * 5));
+            }
+            unsigned *c_rows = d_coo, *c_cols = d_coo + cap, *c_d = d_coo + 2 * cap, *c_n = d_coo + 3 * cap, *c_f = d_coo + 4 * cap;
+            HG_RC(tracs_coo_fill(bd, bn, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), c_rows, c_cols, c_d, c_n, nullptr));
+            HG_RC(tracs_filter_recomb_pairs(a, c_rows, c_cols, c_d, (size_t)total, c_f, nullptr));
+            HG_RC(tracs_hist_update_coo(c_rows, c_cols, c_f, (size_t)total, d_group, d_state[1], n_bins, nullptr));
+        }
+        clock.mark("dense panels + histogram updates");
+        static const char *const column[2] = {"snp", "filter"};
+        std::string text;
+        for (int s = 0; s < n_states; s++) {
+            size_t nr = 0;
+            HG_RC(tracs_hist_emit(d_state[s], n_bins, &nr, nullptr, nullptr, nullptr, nullptr, nullptr));
+            if (!nr) continue;
+            if (d_val) { void *old = d_val; d_val = nullptr; HG_CHECK(hipFree(old)); }
+            if (d_cnt) { void *old = d_cnt; d_cnt = nullptr; HG_CHECK(hipFree(old)); }
+            HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_val), nr * 4));
+            HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cnt), nr * 8 * 3));
+            HG_RC(tracs_hist_emit(d_state[s], n_bins, &nr, d_val, d_cnt, d_cnt + nr, d_cnt + 2 * nr, nullptr));
+            std::vector<uint32_t> hv(nr);
+            std::vector<uint64_t> hc(nr * 3);
+            HG_CHECK(hipMemcpy(hv.data(), d_val, nr * 4, hipMemcpyDeviceToHost));
+            HG_CHECK(hipMemcpy(hc.data(), d_cnt, nr * 24, hipMemcpyDeviceToHost));
+            char line[160];
+            for (size_t t = 0; t < nr; t++) {
+                const int k = std::snprintf(line, sizeof line, "%s,%u,%llu,%llu,%llu,", column[s], hv[t], (unsigned long long)hc[t],
+                                            (unsigned long long)hc[nr + t], (unsigned long long)hc[2 * nr + t]);
+                text.append(line, (size_t)k);
+                text.append(ref);
+                text.push_back('\n');
+                if (s == 0) eligible += hc[t] + hc[nr + t] + hc[2 * nr + t];
+            }
+            written += nr;
+        }
+        if (!text.empty() && std::fwrite(text.data(), 1, text.size(), fp) != text.size()) {
+            cleanup();
+            set_error(std::string("write to ") + path + " failed");
+            return TRACS_E_OPEN;
+        }
+        clock.mark("histogram rows: emit, device -> host, format, write");
+    }
+#undef HG_CHECK
+#undef HG_RC
+    cleanup();
+    const int rc_close = std::fclose(fp);
+    fp = nullptr;
+    if (rc_close != 0) { set_error(std::string("write to ") + path + " failed"); return TRACS_E_OPEN; }
+    if (rows_written) *rows_written = written;
+    if (n_eligible) *n_eligible = eligible;
+    if (g_sigint) { set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+    return TRACS_OK;
+}
+
 size_t tracs_pairsnp_len(const tracs_pairsnp_result *r) { return r ? r->rows.size() : 0; }
 size_t tracs_pairsnp_nseq(const tracs_pairsnp_result *r) { return r ? r->nseq : 0; }
 size_t tracs_pairsnp_seqlen(const tracs_pairsnp_result *r) { return r ? r->L : 0; }

@@ -314,6 +314,61 @@ def msf_emit(state, n):
     return [t[:k] for t in u + f]
 
 
+def hist_init(n_bins, device=None):
+    """An all-zero histogram state for the values [0, n_bins) (tracs_hist_init): a torch.uint8 device buffer."""
+    L = _lib.require_gpu()
+    nbytes = L.tracs_hist_state_bytes(int(n_bins))
+    if nbytes == 0:
+        raise ValueError("hist_init(): n_bins must be in [1, 2^31], got %d" % int(n_bins))
+    state = torch.empty(nbytes, dtype=torch.uint8, device=device if device is not None else "cuda")
+    _lib.check(L.tracs_hist_init(_ptr(state), int(n_bins), _stream()))
+    return state
+
+
+def hist_update(state, n_bins, dist, n, row_begin=0, row_end=None, col_begin=0, dist_threshold=2147483647, group=None, base_row=0):
+    """Count the cells of the panel rows [row_begin, row_end) of dist (as tracs_pairsnp_dense writes them; the panel holds rows
+    base_row..) that are, read as unsigned, <= dist_threshold (tracs_hist_update).  group: torch.int32 device labels of the n
+    samples (< 0: ungrouped) or None (every pair ungrouped)."""
+    L = _lib.require_gpu()
+    row_end = n if row_end is None else row_end
+    assert dist.element_size() == 4 and dist.stride(1) == 1
+    assert group is None or (group.dtype == torch.int32 and group.is_contiguous() and group.numel() == n)
+    _lib.check(L.tracs_hist_update(_panel_ptr(dist, base_row), dist.stride(0), int(n), int(row_begin), int(row_end), int(col_begin),
+                                   int(dist_threshold), _ptr(group), _ptr(state), int(n_bins), _stream()))
+
+
+def hist_update_coo(state, n_bins, rows, cols, val, group=None):
+    """Count the listed pairs (rows, cols) with their values val: 32-bit device vectors of equal length (tracs_hist_update_coo)."""
+    L = _lib.require_gpu()
+    m = int(val.numel())
+    for t in (rows, cols, val):
+        assert t.is_contiguous() and t.numel() == m and t.element_size() == 4 and not t.is_floating_point()
+    assert group is None or (group.dtype == torch.int32 and group.is_contiguous())
+    _lib.check(L.tracs_hist_update_coo(_ptr(rows), _ptr(cols), _ptr(val), m, _ptr(group), _ptr(state), int(n_bins), _stream()))
+
+
+def hist_emit(state, n_bins):
+    """The non-empty bins, ascending (tracs_hist_emit): value (torch.int32, bit pattern uint32), within, between, ungrouped
+    (torch.int64, bit pattern uint64) on the device.  RuntimeError when a value >= n_bins was offered."""
+    L = _lib.require_gpu()
+    cnt = C.c_size_t(0)
+    _lib.check(L.tracs_hist_emit(_ptr(state), int(n_bins), C.byref(cnt), *([C.c_void_p(0)] * 4), _stream()))
+    k = cnt.value
+    value = torch.empty(max(k, 1), dtype=torch.int32, device=state.device)
+    counts = [torch.empty(max(k, 1), dtype=torch.int64, device=state.device) for _ in range(3)]
+    if k:
+        _lib.check(L.tracs_hist_emit(_ptr(state), int(n_bins), C.byref(cnt), _ptr(value), *[_ptr(t) for t in counts], _stream()))
+    return [value[:k]] + [t[:k] for t in counts]
+
+
+def hist_routes(state):
+    """The cells the updates of `state` counted by each route of csrc/histogram.hip, and its LDS slots per class (tests only)."""
+    out = (C.c_double * 4)()
+    if _lib.require_gpu().tracs_debug_hist_routes(_ptr(state), out) != 4:
+        return None
+    return {"combined": int(out[0]), "lds": int(out[1]), "global": int(out[2]), "window": int(out[3])}
+
+
 def edges_from_dense_f64(val, dist, n, threshold, dist_threshold=2147483647, row_begin=0, row_end=None, col_begin=0, base_row=0,
                          with_values=False):
     """Cells (i, j > i) with dist <= dist_threshold and val <= threshold, row-major -> rows, cols (torch.int32)[, values f64]:

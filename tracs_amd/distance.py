@@ -34,6 +34,8 @@ def calculate_trans_prob(*args, **kwargs):
 # --mst WEIGHT -> tracs_distance_forest's weight (the columns `cluster -D` reads: snp 3, filter 6, direct 4, expectedK 5)
 MST_WEIGHTS = {"snp": 0, "filter": 1, "direct": 2, "expectedK": 3}
 
+HISTOGRAM_HEADER = "column,distance,within,between,ungrouped,MSA file\n"
+
 HEADER = ("sampleA,sampleB,date difference,SNP distance,transmission distance,expected K,"
           "filtered SNP distance,sites considered,MSA file\n")
 
@@ -66,6 +68,15 @@ def distance_parser(parser):
                           "need --meta): at most n - 1 rows, each identical to its row in the full output.  For every threshold T, "
                           "`cluster -c T -D WEIGHT` on this file puts the same samples into the same clusters as on the full file "
                           "(cluster numbers may be permuted).  With --meta every sample needs a date.  Not in the reference.")
+    snp.add_argument("--histogram", dest="histogram", action="store_true", default=False,
+                     help="Instead of the pairs, output how many of them have each SNP distance (and, with --filter, each filtered "
+                          "SNP distance): rows column,distance,within,between,ungrouped,MSA file, one per non-empty bin.  The pairs "
+                          "are the ones the run would write (-D, --msa-db); they are counted on the GPU and never emitted.  "
+                          "`tracs threshold --histogram` reads this file.  Not in the reference.")
+    snp.add_argument("--groups", dest="groups", default=None, type=os.path.abspath, metavar="GROUPS.csv",
+                     help="With --histogram: csv (header line skipped) of sample name, group label.  A pair counts as `within` when "
+                          "both samples have the same label, `between` when they have different labels, `ungrouped` when either has "
+                          "none (empty label, or not listed).  Without --groups every pair is `ungrouped`.")
     tr = parser.add_argument_group("Transmission distance options")
     tr.add_argument("--clock_rate", dest="clock_rate", type=check_positive_float, default=1e-3 * 29903,
                     help="clock rate as defined in the transcluster paper (SNPs/genome/year) default=1e-3 * 29903")
@@ -208,6 +219,69 @@ def check_mst_args(args):
         raise SystemExit("tracs distance: --mst %s needs --meta (the sampling dates that transmission distances come from)" % mst)
 
 
+def check_histogram_args(args):
+    """--histogram's and --groups' argument checks, before anything touches the GPU (SystemExit with the message)."""
+    if not getattr(args, "histogram", False):
+        if getattr(args, "groups", None) is not None:
+            raise SystemExit("tracs distance: --groups needs --histogram (the labels only split the histogram's counts)")
+        return
+    if getattr(args, "nearest", None) is not None:
+        raise SystemExit("tracs distance: --histogram and --nearest cannot be combined")
+    if getattr(args, "mst", None) is not None:
+        raise SystemExit("tracs distance: --histogram and --mst cannot be combined")
+    if getattr(args, "gpus", 1) > 1:
+        raise SystemExit("tracs distance: --histogram runs on one GPU; use --gpus 1")
+    if args.metadata is not None:
+        raise SystemExit("tracs distance: --histogram counts SNP distances and takes no --meta (no histogram of transmission distances)")
+    if args.trans_threshold is not None:
+        raise SystemExit("tracs distance: --histogram counts SNP distances and takes no -K (no histogram of E(K))")
+
+
+def read_groups(path):
+    """--groups: csv, header line skipped (as --meta, :148), first column the sample name, second the group label.  -> {name: label};
+    an empty label (or a line without a second column) leaves the sample ungrouped; one name with two different labels is an error."""
+    groups = {}
+    with open(path, "r") as fh:
+        next(fh, None)
+        for line in fh:
+            f = line.rstrip("\r\n").split(",")
+            name = f[0].strip()
+            if not name:
+                continue
+            label = f[1].strip() if len(f) > 1 else ""
+            label = label if label else None
+            if name in groups and groups[name] != label:
+                raise SystemExit("tracs distance: --groups %s lists sample '%s' with two different labels ('%s' and '%s')"
+                                 % (path, name, "" if groups[name] is None else groups[name], "" if label is None else label))
+            groups[name] = label
+    return groups
+
+
+def _histogram_on_device(msas, args, groups, ref, stage):
+    """--histogram for one alignment (tracs_distance_open / _histogram: include/tracs_hip.h): the panel loop of _rows_on_device with
+    a histogram update per panel instead of the rows; only the non-empty bins are formatted and appended."""
+    from .api import group_labels
+    L = _lib.require_gpu()
+    arr = (C.c_char_p * len(msas))(*[os.fsencode(p) for p in msas])
+    h = C.c_void_p()
+    _lib.check(L.tracs_distance_open(arr, len(msas), C.byref(h)))
+    try:
+        stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
+        labels = None
+        if groups is not None:
+            n = L.tracs_distance_nseq(h)
+            lab = group_labels([L.tracs_distance_name(h, i).decode("utf-8", "replace") for i in range(n)], groups)
+            labels = (C.c_int32 * max(n, 1))(*[int(x) for x in lab])
+            logging.info("%d of %d samples of %s have a group label (%d groups)", int((lab >= 0).sum()), n, msas[0],
+                         int(lab.max()) + 1 if n else 0)
+        eligible, written = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(L.tracs_distance_histogram(h, int(args.snp_threshold), int(bool(args.recomb_filter)), labels,
+                                              os.fsencode(args.output_file), ref.encode(), C.byref(eligible), C.byref(written)))
+        stage("[sum] tracs_distance_histogram (dense panels, histogram: %d pairs counted, %d rows written)" % (eligible.value, written.value))
+    finally:
+        L.tracs_distance_free(h)
+
+
 def _cli_of(args):
     """The command line that reproduces `args` (the multi-GPU path re-launches itself, one process per GPU)."""
     argv = ["distance", "--msa"] + list(args.msa_files) + ["-o", args.output_file, "-D", str(args.snp_threshold),
@@ -265,6 +339,9 @@ def _pairs_multi_gpu(msas, args, ctx):
 
 def distance(args):
     check_mst_args(args)
+    check_histogram_args(args)
+    histogram = getattr(args, "histogram", False)
+    groups = read_groups(args.groups) if histogram and args.groups is not None else None
     mst = getattr(args, "mst", None)
     nearest = getattr(args, "nearest", None)
     if nearest is not None and getattr(args, "gpus", 1) > 1:
@@ -291,7 +368,7 @@ def distance(args):
     logging.info("Estimating transmission distances...")
     if lead:
         with open(args.output_file, "w") as out:
-            out.write(HEADER)
+            out.write(HISTOGRAM_HEADER if histogram else HEADER)
     import time
     trace = os.environ.get("TRACS_STAGE_TRACE") is not None      # "[stage] name seconds" lines on stderr (scripts/bench_e2e.py)
     t_stage = [time.perf_counter()]
@@ -313,6 +390,14 @@ def distance(args):
         msas = [msa, args.msa_db] if args.msa_db is not None else [msa]
         t_stage[0] = time.perf_counter()
         ref = os.path.basename(msa).split(".")[0].replace("_combined", "")      # (:208-209)
+        if histogram:
+            # how many of the pairs the full run would write have each SNP distance (one GPU, counted on the device)
+            for p in msas:
+                if not os.path.exists(p):
+                    raise FileNotFoundError(p)
+            _histogram_on_device(msas, args, groups, ref, stage)
+            logging.info("Saving the distance histogram for %s", msa)
+            continue
         if mst is not None:
             # the minimum spanning forest of the pairs the full run would write (one GPU, on the device until its rows)
             for p in msas:
