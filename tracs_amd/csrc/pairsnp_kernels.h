@@ -86,6 +86,10 @@ void site_classes_free(tracs_alignment *a);
 // stage clock of the once-per-pack work (HIP events on the launch stream; tracs_debug_pack_stages, TRACS_CLASSES_TRACE)
 void pack_stage_begin(hipStream_t stream);
 void pack_stage_mark(const char *name, hipStream_t stream, double bytes_read = 0.0, double bytes_written = 0.0);
+// the last marked stage's bytes written are *count x bytes_each, a count the device reports once the build has run (a host address that
+// stays valid until pack_stage_count_gone(count))
+void pack_stage_written_later(const unsigned long long *count, double bytes_each);
+void pack_stage_count_gone(const unsigned long long *count);
 void pack_stage_end();
 
 // ---- sparse side structures of the general matrix-core path (general_sparse.hip) -------------------------------

@@ -590,6 +590,8 @@ static constexpr int kMaxStages = 12;
 static hipEvent_t g_stage_ev[kMaxStages + 1];
 static const char *g_stage_name[kMaxStages];
 static double g_stage_rd[kMaxStages], g_stage_wr[kMaxStages];     // bytes the stage reads / writes (its arrays, once per pass over them)
+static const unsigned long long *g_stage_cnt[kMaxStages];          // bytes written = a count the device reports later (pack_stage_written_later)
+static double g_stage_cnt_bytes[kMaxStages];
 static int g_stage_n = 0;
 static bool g_stage_on = false, g_stage_valid = false;
 
@@ -605,13 +607,23 @@ static void stage_begin(hipStream_t stream)
 static void stage_mark(const char *name, hipStream_t stream, double rd = 0.0, double wr = 0.0)
 {
     if (!g_stage_on || g_stage_n >= kMaxStages) return;
-    g_stage_rd[g_stage_n] = rd; g_stage_wr[g_stage_n] = wr;
+    g_stage_rd[g_stage_n] = rd; g_stage_wr[g_stage_n] = wr; g_stage_cnt[g_stage_n] = nullptr;
     g_stage_name[g_stage_n++] = name;
     (void)hipEventRecord(g_stage_ev[g_stage_n], stream);
     g_stage_valid = true;
 }
 void pack_stage_mark(const char *name, hipStream_t stream, double rd, double wr) { stage_mark(name, stream, rd, wr); }
 void pack_stage_begin(hipStream_t stream) { stage_begin(stream); }
+void pack_stage_written_later(const unsigned long long *count, double bytes_each)
+{
+    if (!g_stage_on || g_stage_n == 0 || !g_stage_valid) return;
+    g_stage_cnt[g_stage_n - 1] = count; g_stage_cnt_bytes[g_stage_n - 1] = bytes_each;
+}
+void pack_stage_count_gone(const unsigned long long *count)
+{
+    for (int k = 0; k < g_stage_n; k++)
+        if (g_stage_cnt[k] == count) { g_stage_wr[k] = (double)*count * g_stage_cnt_bytes[k]; g_stage_cnt[k] = nullptr; }
+}
 void pack_stage_end()
 {
     static const bool trace = std::getenv("TRACS_CLASSES_TRACE") != nullptr;
@@ -934,7 +946,7 @@ int tracs_debug_pack_stage_bytes(double *rd, double *wr, int max_stages)
     using namespace tracs;
     if (!g_stage_valid) return 0;
     int k = 0;
-    for (; k < g_stage_n && k < max_stages; k++) { if (rd) rd[k] = g_stage_rd[k]; if (wr) wr[k] = g_stage_wr[k]; }
+    for (; k < g_stage_n && k < max_stages; k++) { if (rd) rd[k] = g_stage_rd[k]; if (wr) wr[k] = g_stage_cnt[k] ? (double)*g_stage_cnt[k] * g_stage_cnt_bytes[k] : g_stage_wr[k]; }
     return k;
 }
 

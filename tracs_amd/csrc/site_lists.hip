@@ -10,10 +10,11 @@
 //   per sample   its LISTED entries with w = 1 (rank << 5 | w << 4 | mask: its mask lacks the site's reference base -- the entries that
 //                walk lists) -- few: a sample differs from the others at a few hundred sites;
 //                its N BITMAP over the NNL sites, sample-major (T: 16 bytes per 128-site group, the transposed N plane): what
-//                nn_rows_kernel reads instead of a stream of list addresses.
+//                nn_rows_kernel reads instead of a stream of list addresses -- or, where those sites are few, its ROW SLOTS: per batch of
+//                64 groups a count and the sites' ranks as 16-bit entries (row_slots_kernel below).
 //
 // Built from the N plane alone (+ the five planes of the flagged samples, ~1 %): site_lists_kernel reads it once, group by group
-// (bits transposed through LDS, encoded by the site's own thread), n_bitmap_kernel once more, sample by sample (+ each sample's N count).
+// (bits transposed through LDS, encoded by the site's own thread), n_bitmap_kernel / row_slots_kernel once more, sample by sample (+ each sample's N count).
 //
 // The walks.  nn_rows_kernel: row i of the pair matrix in LDS; every N site of sample i (a set bit of its bitmap) is a work item --
 // the site's line(s), scanned by four lanes and decoded piece by piece: NN(i, j) += 1 for every listed j > i.  minor_fixup_kernel:
@@ -26,6 +27,7 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <cstddef>
 #include <cstdlib>
 
 namespace tracs {
@@ -49,11 +51,19 @@ struct SiteLists {
     unsigned *c_p = nullptr;                   // per sample: sum of w over its listed entries
     uint4 *T = nullptr;                        // N bitmaps of the rows over the NNL sites: T[s * tgroups + g]
     size_t tgroups = 0;
+    unsigned short *slots = nullptr;           // ... or, where the rows' N sites are few, ROW SLOTS instead of T: 512 bytes per (row, batch of 64 groups),
+                                               //   slots[(s * batches + b) * 256]: entry 0 the count c (SLOT_OVERFLOW: more than SLOT_CAP -- the walk reads
+                                               //   that batch of the row from the stored N plane), entries 1 .. c the sites' ranks - off_lst[64 b], any order;
+                                               //   only the first ceil(2 (c + 1) / 128) lines of a slot are ever written
+    size_t batches = 0;
+    uint4 *nnl_mask = nullptr;                 // per group: the NNL sites (a copy, kept with the slots: what an overflowed slot's plane words are cut to)
     uint4 *lst_mask = nullptr;                 // per group: sites with lists (copies: the classification's own live in shared scratch)
     unsigned *off_lst = nullptr;               // per group: rank of its first site with lists
     size_t sites = 0, groups = 0;
     unsigned long long tot_p = 0, tot_nnl = 0;
     unsigned max_row = 0;                      // the most N sites (outside the dense class) any sample has: row splits of nn_rows_kernel
+    unsigned max_row_pad = 0;                  //   (the build's two results come back in one copy: max_row, slot_lines)
+    unsigned long long slot_lines = 0;         // 128-byte lines of the slots that the build wrote
     unsigned rows[4] = {0, 0, 0, 0};           // T holds the rows of these ranges only (n_rows of them; 0: all)
     int n_rows = 0;
     // nw_rows (the second form of the classes without its U pass): the N plane site-major and the site of every rank
@@ -678,6 +688,170 @@ __global__ __launch_bounds__(256) void n_bitmap_kernel(const MinorBuild mb, size
     if (live && (lane % NB_GW) == 0u && cnt) atomicAdd(&c_counted[s], cnt);
 }
 
+// ---- per sample: ROW SLOTS -- its N sites among the NNL sites as 16-bit entries, where they are few ----------------------------------
+// At 1 % N a row's bitmap holds 1.3 set bits per 16-byte word: a batch of 64 groups -- what a wave of nn_rows_kernel takes at a time --
+// is 1 024 bytes of bitmap for ~82 sites.  A SLOT (SiteLists::slots) holds the batch's sites as 16-bit entries behind their count: the
+// rank of the site's line less off_lst of the batch's first group (a batch has at most 8 192 sites with lists), i.e. what the walk puts
+// into its ring, ready made.  Same grid, same whole-line reads of the N plane and the same N counts as n_bitmap_kernel; a wave takes
+// 8 samples x 64 groups at a time -- lane = (sample lane / 8, group lane % 8 of each of the batch's eight octets), in two halves of four
+// octets: four 16-byte loads in flight per lane (all eight at once: 180 VGPRs, two waves per SIMD) --, drops the entries into LDS (512 bytes per sample, at offsets from a prefix over the sample's eight lanes) and
+// stores the slots' lines in use as whole lines, 16 bytes per lane.  A sample with more than SLOT_CAP sites in the batch gets the
+// overflow mark alone.
+constexpr unsigned SLOT_BYTES = 512, SLOT_CAP = SLOT_BYTES / 2 - 1, SLOT_OVERFLOW = 0xFFFFu, SLOT_GROUPS = 64;
+constexpr double SLOT_MEAN_MAX = 160.0;        // slots instead of bitmaps up to this many entries per slot on average (a Poisson count of that
+                                               // mean exceeds SLOT_CAP with probability 2e-12, and the slot is still under half of the bitmap's bytes)
+#ifndef TRACS_SLOTS_WAVES
+#define TRACS_SLOTS_WAVES 4
+#endif
+#if TRACS_SLOTS_WAVES > 0
+#define TRACS_SLOTS_ATTR __attribute__((amdgpu_waves_per_eu(TRACS_SLOTS_WAVES, TRACS_SLOTS_WAVES)))
+#else
+#define TRACS_SLOTS_ATTR
+#endif
+__device__ __forceinline__ void wave_sync_lds()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ uint4 and4(const uint4 &a, const uint4 &b) { return make_uint4(a.x & b.x, a.y & b.y, a.z & b.z, a.w & b.w); }
+
+__global__ __launch_bounds__(256) TRACS_SLOTS_ATTR void row_slots_kernel(const MinorBuild mb, size_t n_pad, unsigned n, size_t groups, size_t batches,
+                                                        size_t bat_per_chunk, unsigned short *__restrict__ slots, unsigned *__restrict__ c_counted,
+                                                        unsigned long long *__restrict__ lines_written)
+{
+    __shared__ uint4 stage[4][8 * SLOT_BYTES / 16];
+    __shared__ unsigned wave_lines[4];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, ls = lane >> 3, gl = lane & 7u;
+    const size_t s = ((size_t)blockIdx.x * 4 + wave) * 8 + ls;
+    const size_t b0 = (size_t)blockIdx.y * bat_per_chunk, b1 = min(batches, b0 + bat_per_chunk);
+    const bool live = s < n;
+    const bool row = live && slots != nullptr && row_wanted(mb, s);
+    const bool any_row = __ballot(row) != 0ull;
+    const uint4 *np = mb.planes + 4 * n_pad + min(s, n_pad - 1);
+    unsigned short *mine = reinterpret_cast<unsigned short *>(&stage[wave][ls * (SLOT_BYTES / 16)]);
+    uint4 *out = reinterpret_cast<uint4 *>(slots) + (row ? s * batches : (size_t)0) * (SLOT_BYTES / 16);
+    unsigned cnt = 0, nlines = 0;
+    const unsigned glast = (unsigned)groups - 1u;
+    // the batch in two halves of four octets (the registers of four waves per SIMD); the next half's loads are in flight while this
+    // one's entries are made (behind the last group they read the last group again: nobody looks at them)
+    uint4 vn[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) vn[k] = np[(size_t)min((unsigned)b0 * SLOT_GROUPS + gl + k * 8u, glast) * NPLANES * n_pad];
+    for (size_t b = b0; b < b1; b++) {
+        unsigned total = 0;                                  // the sample's entries so far (the same in its eight lanes)
+        bool over = false;
+#pragma unroll 1
+        for (unsigned h = 0; h < 2; h++) {
+            const unsigned gb = (unsigned)b * SLOT_GROUPS + h * 32u + gl;      // (32-bit group numbers: one offset from the masks' wave-uniform addresses)
+            uint4 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = vn[k];
+            unsigned c = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const unsigned g = gb + k * 8u, gm = min(g, glast);
+                const uint4 um = mb.un_mask[gm], nm = mb.nnl_mask[gm];
+                if (g > glast || !live) v[k] = make_uint4(0u, 0u, 0u, 0u);
+                cnt += __popc(v[k].x & um.x) + __popc(v[k].y & um.y) + __popc(v[k].z & um.z) + __popc(v[k].w & um.w);
+                v[k] = and4(v[k], nm);
+                c += __popc(v[k].x) + __popc(v[k].y) + __popc(v[k].z) + __popc(v[k].w);
+            }
+            // the groups' list masks and ranks first, the next half's plane words behind them: loads come back in order, so waiting for
+            // the masks leaves the plane words in flight while the entries are made
+            uint4 lm4[4];
+            unsigned og4[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) { const unsigned gm = min(gb + k * 8u, glast); lm4[k] = mb.lst_mask[gm]; og4[k] = mb.off_lst[gm]; }
+            const unsigned o0 = mb.off_lst[min((unsigned)b * SLOT_GROUPS, glast)];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < 4; k++) vn[k] = np[(size_t)min(gb + 32u + k * 8u, glast) * NPLANES * n_pad];
+            __builtin_amdgcn_sched_barrier(0);
+            if (!any_row) continue;
+            unsigned x = c;                                  // inclusive prefix over the sample's eight lanes
+#pragma unroll
+            for (unsigned d = 1; d < 8; d <<= 1) { const unsigned t = __shfl_up(x, d, 8); if (gl >= d) x += t; }
+            unsigned pos = 1u + total + x - c;
+            total += __shfl(x, 7, 8);
+            over = over || total > SLOT_CAP;
+            if (row && !over && c) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    unsigned r0 = v[k].x, r1 = v[k].y, r2 = v[k].z, r3 = v[k].w;
+                    if ((r0 | r1 | r2 | r3) == 0u) continue;
+                    const uint4 lm = lm4[k];
+                    const unsigned og = og4[k] - o0;
+                    const unsigned pre1 = og + __popc(lm.x), pre2 = pre1 + __popc(lm.y), pre3 = pre2 + __popc(lm.z);
+                    while (r0) { const unsigned bit = __ffs(r0) - 1; r0 &= r0 - 1; mine[pos++] = (unsigned short)(og + __popc(lm.x & ((1u << bit) - 1u))); }
+                    while (r1) { const unsigned bit = __ffs(r1) - 1; r1 &= r1 - 1; mine[pos++] = (unsigned short)(pre1 + __popc(lm.y & ((1u << bit) - 1u))); }
+                    while (r2) { const unsigned bit = __ffs(r2) - 1; r2 &= r2 - 1; mine[pos++] = (unsigned short)(pre2 + __popc(lm.z & ((1u << bit) - 1u))); }
+                    while (r3) { const unsigned bit = __ffs(r3) - 1; r3 &= r3 - 1; mine[pos++] = (unsigned short)(pre3 + __popc(lm.w & ((1u << bit) - 1u))); }
+                }
+            }
+        }
+        if (!any_row) continue;
+        if (gl == 0u) mine[0] = (unsigned short)(over ? SLOT_OVERFLOW : total);
+        // the slot's lines in use (the count alone: one), line j by the sample's eight lanes: whole 128-byte lines
+        const unsigned nl = !row ? 0u : over ? 1u : (2u * (total + 1u) + 127u) / 128u;
+        wave_sync_lds();
+#pragma unroll
+        for (unsigned j = 0; j < SLOT_BYTES / 128; j++)
+            if (nl > j) out[b * (SLOT_BYTES / 16) + j * 8 + gl] = stage[wave][ls * (SLOT_BYTES / 16) + j * 8 + gl];
+        wave_sync_lds();                                     // (the next batch's entries go where these were read)
+        if (gl == 0u) nlines += nl;
+    }
+#pragma unroll
+    for (unsigned off = 1; off < 8; off <<= 1) cnt += __shfl_xor(cnt, off, 64);
+    if (live && gl == 0u && cnt) atomicAdd(&c_counted[s], cnt);
+#pragma unroll
+    for (unsigned off = 1; off < 64; off <<= 1) nlines += __shfl_xor(nlines, off, 64);
+    if (lane == 0u) wave_lines[wave] = nlines;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        const unsigned t = wave_lines[0] + wave_lines[1] + wave_lines[2] + wave_lines[3];
+        if (t) atomicAdd(lines_written, (unsigned long long)t);
+    }
+}
+
+// the bitmap of the rows that hold slots (tracs_debug_lists alone: the diagnostics' view of the rows is the bitmap, whatever the walk reads):
+// one thread per (row, group) -- the entries of its batch's slot that fall into the group's run of ranks, or, behind the overflow
+// mark, the stored N plane's word
+__global__ __launch_bounds__(64) void slots_to_bitmap_kernel(const unsigned short *__restrict__ slots, size_t batches, const uint4 *__restrict__ nplane,
+                                                             size_t n_pad, const uint4 *__restrict__ nnl_mask, const uint4 *__restrict__ lst_mask,
+                                                             const unsigned *__restrict__ off_lst, size_t groups, size_t tgroups, int wanted,
+                                                             uint4 *__restrict__ T)
+{
+    const size_t s = blockIdx.y, b = blockIdx.x, g = b * SLOT_GROUPS + threadIdx.x;
+    if (g >= tgroups) return;
+    unsigned w[4] = {0u, 0u, 0u, 0u};
+    if (g < groups && wanted) {
+        const unsigned short *slot = slots + (s * batches + b) * (SLOT_BYTES / 2);
+        const unsigned c = slot[0];
+        const uint4 lm4 = lst_mask[g];
+        const unsigned lm[4] = {lm4.x, lm4.y, lm4.z, lm4.w};
+        if (c == SLOT_OVERFLOW) {
+            const uint4 t = and4(nplane[g * NPLANES * n_pad + s], nnl_mask[g]);
+            w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
+        } else {
+            const unsigned first = off_lst[g] - off_lst[b * SLOT_GROUPS], count = __popc(lm[0]) + __popc(lm[1]) + __popc(lm[2]) + __popc(lm[3]);
+            for (unsigned e = 1; e <= min(c, SLOT_CAP); e++) {
+                unsigned k = (unsigned)slot[e] - first;      // the k-th site with a list of this group
+                if (k >= count) continue;
+                for (int q = 0; q < 4; q++) {
+                    const unsigned pc = __popc(lm[q]);
+                    if (k >= pc) { k -= pc; continue; }
+                    unsigned m = lm[q];
+                    while (k--) m &= m - 1;
+                    w[q] |= m & (0u - m);
+                    break;
+                }
+            }
+        }
+    }
+    T[s * tgroups + g] = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 __global__ void max_count_kernel(const unsigned *__restrict__ c, size_t n, unsigned *__restrict__ out)
 {
     const size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -823,8 +997,76 @@ constexpr unsigned NN_MAX_SPLITS = 32;
 #ifndef TRACS_NN_THREADS
 #define TRACS_NN_THREADS 1024
 #endif
+// the set bits of one bitmap word per lane (group g of the row: its N sites among the NNL sites) go into the wave's ring as lines
 template <bool CLAMP>
-__global__ __launch_bounds__(TRACS_NN_THREADS) void nn_rows_kernel(const uint4 *__restrict__ T, size_t tgroups, const uint4 *__restrict__ lst_mask,
+__device__ __forceinline__ void push_row_bits(Walk<CLAMP> &W, const uint4 &tw, size_t g, size_t groups, const uint4 *__restrict__ lst_mask,
+                                              const unsigned *__restrict__ off_lst)
+{
+    unsigned r0 = tw.x, r1 = tw.y, r2 = tw.z, r3 = tw.w;
+    // this lane's set bits, and where its items go in the ring: an inclusive wave scan of the counts (DPP)
+    const unsigned cnt = __popc(r0) + __popc(r1) + __popc(r2) + __popc(r3);
+    unsigned x = cnt;
+    x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);      // row_shr:1 .. 8: scan inside the rows of 16
+    x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, true);
+    x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, true);
+    x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, true);
+    x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);     // row_bcast:15 -> rows 1, 3
+    x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);     // row_bcast:31 -> rows 2, 3
+    const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)x, 63);
+    if (total == 0u) return;
+    const size_t gm = min(g, groups - 1);
+    const uint4 lm = lst_mask[gm];
+    const unsigned og = off_lst[gm];
+    const unsigned pre1 = og + __popc(lm.x), pre2 = pre1 + __popc(lm.y), pre3 = pre2 + __popc(lm.z);
+    W.drain_lines_to(31);
+    if (total <= LINE_RING - 32u) {
+        // (the usual case: all of the batch's sites fit the ring at once -- every lane drops its own, word by word)
+        unsigned pos = W.lhead + W.lcount + x - cnt;
+        while (r0) { const unsigned bit = __ffs(r0) - 1; r0 &= r0 - 1; W.lring[pos++ & (LINE_RING - 1u)] = make_uint2(og + __popc(lm.x & ((1u << bit) - 1u)), 0xFFFFFFFFu); }
+        while (r1) { const unsigned bit = __ffs(r1) - 1; r1 &= r1 - 1; W.lring[pos++ & (LINE_RING - 1u)] = make_uint2(pre1 + __popc(lm.y & ((1u << bit) - 1u)), 0xFFFFFFFFu); }
+        while (r2) { const unsigned bit = __ffs(r2) - 1; r2 &= r2 - 1; W.lring[pos++ & (LINE_RING - 1u)] = make_uint2(pre2 + __popc(lm.z & ((1u << bit) - 1u)), 0xFFFFFFFFu); }
+        while (r3) { const unsigned bit = __ffs(r3) - 1; r3 &= r3 - 1; W.lring[pos++ & (LINE_RING - 1u)] = make_uint2(pre3 + __popc(lm.w & ((1u << bit) - 1u)), 0xFFFFFFFFu); }
+        W.lcount += total;
+        return;
+    }
+    for (;;) {                                            // a sample that is N nearly everywhere: one bit per lane and step
+        W.drain_lines_to(31);                            // room for 64 more
+        const bool has = (r0 | r1 | r2 | r3) != 0u;
+        if (!__ballot(has)) break;
+        unsigned rank = 0;
+        if (r0) { const unsigned bit = __ffs(r0) - 1; r0 &= r0 - 1; rank = og + __popc(lm.x & ((1u << bit) - 1u)); }
+        else if (r1) { const unsigned bit = __ffs(r1) - 1; r1 &= r1 - 1; rank = pre1 + __popc(lm.y & ((1u << bit) - 1u)); }
+        else if (r2) { const unsigned bit = __ffs(r2) - 1; r2 &= r2 - 1; rank = pre2 + __popc(lm.z & ((1u << bit) - 1u)); }
+        else if (r3) { const unsigned bit = __ffs(r3) - 1; r3 &= r3 - 1; rank = pre3 + __popc(lm.w & ((1u << bit) - 1u)); }
+        W.push_line(has, rank);
+    }
+}
+
+// 128 entries of a slot, two per lane (entries e0 + 2 lane and the one behind it; entry 0 is the count): those among 1 .. c go into the
+// ring at the place their index gives them -- no scan --, at most LINE_RING - 32 at a time (the room drain_lines_to(31) makes)
+template <bool CLAMP>
+__device__ __forceinline__ void push_slot_entries(Walk<CLAMP> &W, unsigned word, unsigned e0, unsigned c, unsigned base)
+{
+    const unsigned ea = e0 + 2u * W.lane, eb = ea + 1u;
+    const unsigned last = min(c, e0 + 127u);
+    for (unsigned first = max(e0, 1u); first <= last; first += LINE_RING - 32u) {
+        const unsigned upto = min(last, first + (LINE_RING - 32u) - 1u);
+        W.drain_lines_to(31);
+        const unsigned pos = W.lhead + W.lcount - first;
+        if (ea >= first && ea <= upto) W.lring[(pos + ea) & (LINE_RING - 1u)] = make_uint2(base + (word & 0xFFFFu), 0xFFFFFFFFu);
+        if (eb >= first && eb <= upto) W.lring[(pos + eb) & (LINE_RING - 1u)] = make_uint2(base + (word >> 16), 0xFFFFFFFFu);
+        W.lcount += upto - first + 1u;
+    }
+}
+__device__ __forceinline__ unsigned load_stream(const unsigned *p) { return __builtin_nontemporal_load(p); }
+
+// SLOTS: the row's N sites come from its slots (row_slots_kernel) instead of its bitmap T -- per batch one 4-byte load per lane (entries
+// 0 .. 127: the count comes from lane 0), a second one only behind 127 entries; a batch whose slot overflowed is read from the stored N
+// plane itself, one 128-byte line per 16 bytes: slow, always right, and rare.
+template <bool CLAMP, bool SLOTS>
+__global__ __launch_bounds__(TRACS_NN_THREADS) void nn_rows_kernel(const uint4 *__restrict__ T, size_t tgroups, const unsigned *__restrict__ slots,
+                                                                   const uint4 *__restrict__ nplane, size_t n_pad, const uint4 *__restrict__ nnl_mask,
+                                                                   const uint4 *__restrict__ lst_mask,
                                                                    const unsigned *__restrict__ off_lst, size_t groups, const uint4 *__restrict__ lines,
                                                                    const unsigned *__restrict__ c_u, unsigned n, unsigned row_begin, unsigned col_begin,
                                                                    unsigned chunk, unsigned target, unsigned segments, unsigned *__restrict__ ncomp,
@@ -850,52 +1092,37 @@ __global__ __launch_bounds__(TRACS_NN_THREADS) void nn_rows_kernel(const uint4 *
     const size_t batches = (tgroups + 63) / 64;
     const size_t per = (batches + nz - 1) / nz;
     const size_t b_first = (size_t)blockIdx.z * per, b_last = min(batches, b_first + per);
-    const uint4 *Trow = T + (size_t)i * tgroups;
     const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
     size_t b = b_first + wave;
-    uint4 tw_next = (b < b_last && b * 64 + lane < tgroups) ? load_stream(Trow + b * 64 + lane) : zero4;
-    for (; b < b_last; b += nwaves) {
-        const size_t g = b * 64 + lane;
-        const uint4 tw = tw_next;
-        const size_t bn = b + nwaves;
-        tw_next = (bn < b_last && bn * 64 + lane < tgroups) ? load_stream(Trow + bn * 64 + lane) : zero4;     // the next batch's bitmap: in flight during this one
-        unsigned r0 = tw.x, r1 = tw.y, r2 = tw.z, r3 = tw.w;
-        // this lane's set bits, and where its items go in the ring: an inclusive wave scan of the counts (DPP)
-        const unsigned cnt = __popc(r0) + __popc(r1) + __popc(r2) + __popc(r3);
-        unsigned x = cnt;
-        x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);      // row_shr:1 .. 8: scan inside the rows of 16
-        x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, true);
-        x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, true);
-        x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, true);
-        x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);     // row_bcast:15 -> rows 1, 3
-        x += (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);     // row_bcast:31 -> rows 2, 3
-        const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)x, 63);
-        if (total == 0u) continue;
-        const size_t gm = min(g, groups - 1);
-        const uint4 lm = lst_mask[gm];
-        const unsigned og = off_lst[gm];
-        const unsigned pre1 = og + __popc(lm.x), pre2 = pre1 + __popc(lm.y), pre3 = pre2 + __popc(lm.z);
-        W.drain_lines_to(31);
-        if (total <= LINE_RING - 32u) {
-            // (the usual case: all of the batch's sites fit the ring at once -- every lane drops its own, word by word)
-            unsigned pos = W.lhead + W.lcount + x - cnt;
-            while (r0) { const unsigned bit = __ffs(r0) - 1; r0 &= r0 - 1; W.lring[pos++ & (LINE_RING - 1u)] = make_uint2(og + __popc(lm.x & ((1u << bit) - 1u)), 0xFFFFFFFFu); }
-            while (r1) { const unsigned bit = __ffs(r1) - 1; r1 &= r1 - 1; W.lring[pos++ & (LINE_RING - 1u)] = make_uint2(pre1 + __popc(lm.y & ((1u << bit) - 1u)), 0xFFFFFFFFu); }
-            while (r2) { const unsigned bit = __ffs(r2) - 1; r2 &= r2 - 1; W.lring[pos++ & (LINE_RING - 1u)] = make_uint2(pre2 + __popc(lm.z & ((1u << bit) - 1u)), 0xFFFFFFFFu); }
-            while (r3) { const unsigned bit = __ffs(r3) - 1; r3 &= r3 - 1; W.lring[pos++ & (LINE_RING - 1u)] = make_uint2(pre3 + __popc(lm.w & ((1u << bit) - 1u)), 0xFFFFFFFFu); }
-            W.lcount += total;
-            continue;
+    if constexpr (SLOTS) {
+        // (a row's slots are less than 2^32 bytes: dword offsets of 32 bits from the row's -- wave-uniform -- address)
+        const unsigned *Srow = slots + (size_t)i * batches * (SLOT_BYTES / 4);
+        unsigned sw_next = b < b_last ? load_stream(Srow + ((unsigned)b * (SLOT_BYTES / 4) + lane)) : 0u;
+        for (; b < b_last; b += nwaves) {
+            const unsigned sw = sw_next;
+            const size_t bn = b + nwaves;
+            sw_next = bn < b_last ? load_stream(Srow + ((unsigned)bn * (SLOT_BYTES / 4) + lane)) : 0u;      // the next batch's slot: in flight during this one
+            const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)sw, 0) & 0xFFFFu;
+            if (c == 0u) continue;
+            if (c == SLOT_OVERFLOW) {
+                const size_t g = b * 64 + lane;
+                const uint4 tw = g < groups ? and4(nplane[g * NPLANES * n_pad + i], nnl_mask[g]) : zero4;
+                push_row_bits(W, tw, g, groups, lst_mask, off_lst);
+                continue;
+            }
+            const unsigned base = off_lst[min(b * 64, groups - 1)];
+            push_slot_entries(W, sw, 0u, c, base);
+            if (c > 127u) push_slot_entries(W, load_stream(Srow + ((unsigned)b * (SLOT_BYTES / 4) + 64u + lane)), 128u, c, base);
         }
-        for (;;) {                                            // a sample that is N nearly everywhere: one bit per lane and step
-            W.drain_lines_to(31);                            // room for 64 more
-            const bool has = (r0 | r1 | r2 | r3) != 0u;
-            if (!__ballot(has)) break;
-            unsigned rank = 0;
-            if (r0) { const unsigned bit = __ffs(r0) - 1; r0 &= r0 - 1; rank = og + __popc(lm.x & ((1u << bit) - 1u)); }
-            else if (r1) { const unsigned bit = __ffs(r1) - 1; r1 &= r1 - 1; rank = pre1 + __popc(lm.y & ((1u << bit) - 1u)); }
-            else if (r2) { const unsigned bit = __ffs(r2) - 1; r2 &= r2 - 1; rank = pre2 + __popc(lm.z & ((1u << bit) - 1u)); }
-            else if (r3) { const unsigned bit = __ffs(r3) - 1; r3 &= r3 - 1; rank = pre3 + __popc(lm.w & ((1u << bit) - 1u)); }
-            W.push_line(has, rank);
+    } else {
+        const uint4 *Trow = T + (size_t)i * tgroups;
+        uint4 tw_next = (b < b_last && b * 64 + lane < tgroups) ? load_stream(Trow + b * 64 + lane) : zero4;
+        for (; b < b_last; b += nwaves) {
+            const size_t g = b * 64 + lane;
+            const uint4 tw = tw_next;
+            const size_t bn = b + nwaves;
+            tw_next = (bn < b_last && bn * 64 + lane < tgroups) ? load_stream(Trow + bn * 64 + lane) : zero4;     // the next batch's bitmap: in flight during this one
+            push_row_bits(W, tw, g, groups, lst_mask, off_lst);
         }
     }
     W.finish();
@@ -1155,6 +1382,7 @@ __global__ __launch_bounds__(256) void site_of_rank_kernel(const uint4 *__restri
 void minority_lists_free(tracs_alignment *a)
 {
     if (!a) return;
+    if (a->lists) pack_stage_count_gone(&a->lists->slot_lines);
     delete a->lists;                               // (the arrays live in the alignment's pack arena: released with it)
     a->lists = nullptr;
 }
@@ -1167,7 +1395,7 @@ int minority_lists_build(tracs_alignment *a, const MinorBuild &mb_, hipStream_t 
     const size_t n = a->n, L = mb.sites, groups = a->groups;
     if (L == 0 || L >= (1ull << 26) || n >= (1ull << 27)) return TRACS_OK;           // entries hold rank << 5 (+ a flag bit) / sample << 5
     auto *g = new SiteLists();
-    auto fail_soft = [&]() { (void)hipGetLastError(); delete g; return TRACS_OK; };
+    auto fail_soft = [&]() { (void)hipGetLastError(); pack_stage_count_gone(&g->slot_lines); delete g; return TRACS_OK; };
 #define SL_TRY(x) do { if ((x) != hipSuccess) return fail_soft(); } while (0)
     g->sites = L; g->groups = groups; g->tot_p = mb.tot_p; g->tot_nnl = mb.tot_nnl;
     g->n_rows = mb.n_rows;
@@ -1186,7 +1414,14 @@ int minority_lists_build(tracs_alignment *a, const MinorBuild &mb_, hipStream_t 
     SL_TRY(pack_alloc(a, groups * sizeof(uint4), reinterpret_cast<void **>(&g->lst_mask)));
     SL_TRY(pack_alloc(a, groups * sizeof(unsigned), reinterpret_cast<void **>(&g->off_lst)));
     const bool bitmaps = mb.tot_nnl > 0;
-    if (bitmaps) SL_TRY(pack_alloc(a, n * g->tgroups * sizeof(uint4), reinterpret_cast<void **>(&g->T)));
+    // the rows' N sites: slots where a slot holds few entries on average, else bitmaps (TRACS_ROW_LISTS=0|1 forces the choice: A/B runs, tests)
+    static const int env_slots = [] { const char *e = getenv("TRACS_ROW_LISTS"); return e ? atoi(e) : -1; }();
+    g->batches = (g->tgroups + SLOT_GROUPS - 1) / SLOT_GROUPS;
+    const bool row_slots = bitmaps && (env_slots >= 0 ? env_slots != 0 : (double)mb.tot_nnl <= SLOT_MEAN_MAX * (double)n * (double)g->batches);
+    if (row_slots) {
+        SL_TRY(pack_alloc(a, n * g->batches * SLOT_BYTES, reinterpret_cast<void **>(&g->slots)));
+        SL_TRY(pack_alloc(a, groups * sizeof(uint4), reinterpret_cast<void **>(&g->nnl_mask)));
+    } else if (bitmaps) SL_TRY(pack_alloc(a, n * g->tgroups * sizeof(uint4), reinterpret_cast<void **>(&g->T)));
     unsigned *cnt = nullptr, *e_cnt = nullptr;
     uint2 *E = nullptr, *tmp = nullptr;
     int rc;
@@ -1206,6 +1441,7 @@ int minority_lists_build(tracs_alignment *a, const MinorBuild &mb_, hipStream_t 
     SL_TRY(hipMemsetAsync(g->c_p, 0, std::max<size_t>(n, 1) * 4, stream));
     SL_TRY(hipMemcpyAsync(g->lst_mask, mb.lst_mask, groups * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
     SL_TRY(hipMemcpyAsync(g->off_lst, mb.off_lst, groups * sizeof(unsigned), hipMemcpyDeviceToDevice, stream));
+    if (row_slots) SL_TRY(hipMemcpyAsync(g->nnl_mask, mb.nnl_mask, groups * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
     const double plane_b = (double)groups * (double)a->n_pad * sizeof(uint4);      // the N plane
 #ifndef TRACS_SITE_PIECE
 #define TRACS_SITE_PIECE 512
@@ -1235,7 +1471,20 @@ int minority_lists_build(tracs_alignment *a, const MinorBuild &mb_, hipStream_t 
     }
     pack_stage_mark("listed entries per sample", stream, (double)std::min<unsigned long long>(mb.tot_p, 2 * L) * (two_pass ? 16.0 : 8.0) + (double)n * 4.0,
                     (double)std::min<unsigned long long>(mb.tot_p, 2 * L) * (two_pass ? 12.0 : 4.0) + (double)n * 12.0);
-    if (bitmaps) {
+    if (row_slots) {
+        // (a->c_counted was zeroed by the caller: this kernel is what fills it when the rows' slots are built)
+        unsigned long long *d_lines = reinterpret_cast<unsigned long long *>(d_max + 2);
+        const unsigned chunks = (unsigned)std::min<size_t>(64, std::max<size_t>(1, g->batches / 2));
+        const size_t bpc = (g->batches + chunks - 1) / chunks;
+        const dim3 grid((unsigned)((n + 31) / 32), (unsigned)((g->batches + bpc - 1) / bpc));
+        hipLaunchKernelGGL(row_slots_kernel, grid, dim3(256), 0, stream, mb, a->n_pad, (unsigned)n, groups, g->batches, bpc, g->slots, a->c_counted, d_lines);
+        hipLaunchKernelGGL(max_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a->c_counted, n, d_max);
+        // written: the slots' lines in use (~2 per slot at 1 % N), as the kernel counted them
+        pack_stage_mark("N slots of the rows", stream, plane_b, 0.0);
+        pack_stage_written_later(&g->slot_lines, 128.0);
+        static_assert(offsetof(SiteLists, slot_lines) == offsetof(SiteLists, max_row) + 8, "max_row and slot_lines come back in one copy");
+        SL_TRY(hipMemcpyAsync(&g->max_row, d_max, 16, hipMemcpyDeviceToHost, stream));       // (read after the caller's synchronisation)
+    } else if (bitmaps) {
         // (a->c_counted was zeroed by the caller: this kernel is what fills it when the rows' bitmaps are built)
         const size_t octs = g->tgroups / NB_GW;
         const unsigned chunks = (unsigned)std::min<size_t>(64, std::max<size_t>(1, octs / 16));
@@ -1273,7 +1522,7 @@ int nn_rows_add(tracs_alignment *a, size_t row_begin, size_t row_end, size_t col
                 unsigned lu, hipStream_t stream)
 {
     const SiteLists *g = a->lists;
-    if (!g || !g->T) { set_error("nn_rows_add: lists not built"); return TRACS_E_ARG; }
+    if (!g || (!g->T && !g->slots)) { set_error("nn_rows_add: lists not built"); return TRACS_E_ARG; }
     const size_t n = a->n;
     const unsigned chunk = row_chunk(n);
     const size_t lds = (size_t)chunk * 4 + 256 + kWalkLds;
@@ -1281,8 +1530,9 @@ int nn_rows_add(tracs_alignment *a, size_t row_begin, size_t row_end, size_t col
     (void)hipGetDevice(&dev);
     static bool attr_set[64] = {false};
     if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        TRACS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nn_rows_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROW_CHUNK_MAX * 4 + 256 + (int)kWalkLds));
-        TRACS_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(nn_rows_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROW_CHUNK_MAX * 4 + 256 + (int)kWalkLds));
+        const void *fns[4] = {reinterpret_cast<const void *>(nn_rows_kernel<true, false>), reinterpret_cast<const void *>(nn_rows_kernel<false, false>),
+                              reinterpret_cast<const void *>(nn_rows_kernel<true, true>), reinterpret_cast<const void *>(nn_rows_kernel<false, true>)};
+        for (const void *fn : fns) TRACS_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ROW_CHUNK_MAX * 4 + 256 + (int)kWalkLds));
         attr_set[dev] = true;
     }
     // ~2048 workgroups' worth of walks each, never less than 8192 (a workgroup's fixed cost: its row in LDS)
@@ -1299,12 +1549,16 @@ int nn_rows_add(tracs_alignment *a, size_t row_begin, size_t row_end, size_t col
     const unsigned segments = seg_bytes ? (unsigned)std::min<unsigned long long>(NN_MAX_SPLITS, std::max<unsigned long long>(1, (g->n_lines * 128ull + seg_bytes - 1) / seg_bytes)) : 1u;
     const unsigned splits = (unsigned)std::min<unsigned long long>(NN_MAX_SPLITS, std::max<unsigned long long>(segments, ((unsigned long long)g->max_row + target - 1) / target));
     const dim3 grid((unsigned)(row_end - row_begin), (unsigned)((n + chunk - 1) / chunk), splits);
-    if (grid.y == 1)                                       // one column chunk: every decoded position is a counter of the row
-        hipLaunchKernelGGL(nn_rows_kernel<false>, grid, dim3(TRACS_NN_THREADS), lds, stream, g->T, g->tgroups, g->lst_mask, g->off_lst, g->groups, g->lines,
-                           a->c_counted, (unsigned)n, (unsigned)row_begin, (unsigned)col_begin, chunk, target, segments, ncomp, ld, add_terms, lu);
-    else
-        hipLaunchKernelGGL(nn_rows_kernel<true>, grid, dim3(TRACS_NN_THREADS), lds, stream, g->T, g->tgroups, g->lst_mask, g->off_lst, g->groups, g->lines,
-                           a->c_counted, (unsigned)n, (unsigned)row_begin, (unsigned)col_begin, chunk, target, segments, ncomp, ld, add_terms, lu);
+    const uint4 *nplane = a->planes + 4 * a->n_pad;          // the stored N plane: what a row reads where its slot overflowed
+#define TRACS_NN_LAUNCH(CL, SL) hipLaunchKernelGGL((nn_rows_kernel<CL, SL>), grid, dim3(TRACS_NN_THREADS), lds, stream, g->T, g->tgroups, \
+        reinterpret_cast<const unsigned *>(g->slots), nplane, a->n_pad, g->nnl_mask, g->lst_mask, g->off_lst, g->groups, g->lines, \
+        a->c_counted, (unsigned)n, (unsigned)row_begin, (unsigned)col_begin, chunk, target, segments, ncomp, ld, add_terms, lu)
+    if (grid.y == 1) {                                     // one column chunk: every decoded position is a counter of the row
+        if (g->slots) TRACS_NN_LAUNCH(false, true); else TRACS_NN_LAUNCH(false, false);
+    } else {
+        if (g->slots) TRACS_NN_LAUNCH(true, true); else TRACS_NN_LAUNCH(true, false);
+    }
+#undef TRACS_NN_LAUNCH
     TRACS_HIP_CHECK(hipGetLastError());
     return TRACS_OK;
 }
@@ -1369,8 +1623,9 @@ extern "C" {
 //   what 0  sizes: out64[0..7] = sites with lists, lines, p entries, tgroups, groups, bitmap present, n, the most N sites of a sample
 //   what 1  lines (n_lines x 128 bytes)     what 2  lst_mask (groups x 16 bytes)     what 3  off_lst (groups x 4 bytes)
 //   what 4  p_off ((sites + 1) x 8)          what 5  p_ent (tot_p x 4: short lists)   what 6  s_off ((n + 1) x 8)
-//   what 7  s_ent (tot_p x 4)                what 8  T (n x tgroups x 16)             what 9  c_p (n x 4)
+//   what 7  s_ent (tot_p x 4)                what 8  T (n x tgroups x 16; rows held as slots: expanded)      what 9  c_p (n x 4)
 //   what 10 q lines (n_qlines x 4 qw bytes: the p lists)     what 11 out64[0] = n_qlines     what 12 out64[0] = qw (dwords per q line)
+//   what 13 out64[0] = 1 when the rows are held as slots, out64[1] = the 128-byte lines of them that the build wrote
 // Returns the bytes copied (what >= 1), 0 when the lists do not exist or `cap` is too small.
 size_t tracs_debug_lists(const tracs_alignment *a, int what, void *out, size_t cap)
 {
@@ -1383,7 +1638,7 @@ size_t tracs_debug_lists(const tracs_alignment *a, int what, void *out, size_t c
     case 0: {
         if (cap < 64) return 0;
         uint64_t *o = static_cast<uint64_t *>(out);
-        o[0] = g->sites; o[1] = g->n_lines; o[2] = g->tot_p; o[3] = g->tgroups; o[4] = g->groups; o[5] = g->T ? 1 : 0; o[6] = a->n; o[7] = g->max_row;
+        o[0] = g->sites; o[1] = g->n_lines; o[2] = g->tot_p; o[3] = g->tgroups; o[4] = g->groups; o[5] = (g->T || g->slots) ? 1 : 0; o[6] = a->n; o[7] = g->max_row;
         return 64;
     }
     case 1: src = g->lines; bytes = g->n_lines * 128; break;
@@ -1393,11 +1648,34 @@ size_t tracs_debug_lists(const tracs_alignment *a, int what, void *out, size_t c
     case 5: src = g->p_ent; bytes = g->tot_p * 4; break;
     case 6: src = g->s_off; bytes = (a->n + 1) * 8; break;
     case 7: src = g->s_ent; bytes = g->tot_p * 4; break;
-    case 8: src = g->T; bytes = g->T ? a->n * g->tgroups * 16 : 0; break;
+    case 8: {
+        if (!g->slots) { src = g->T; bytes = g->T ? a->n * g->tgroups * 16 : 0; break; }
+        // rows in slots: expanded to the bitmap they stand for (rows outside the handle's ranges: zero)
+        bytes = a->n * g->tgroups * 16;
+        if (bytes == 0 || bytes > cap) return 0;
+        uint4 *tmp = nullptr;
+        if (hipDeviceSynchronize() != hipSuccess || hipMalloc(reinterpret_cast<void **>(&tmp), bytes) != hipSuccess) { (void)hipGetLastError(); return 0; }
+        bool ok = true;
+        for (size_t s0 = 0; s0 < a->n && ok; ) {
+            // (runs of rows that are all wanted or all not: at most five)
+            auto wanted = [&](size_t s) { if (g->n_rows == 0) return true; for (int k = 0; k < g->n_rows; k++) if (s >= g->rows[2 * k] && s < g->rows[2 * k + 1]) return true; return false; };
+            const bool w = wanted(s0);
+            size_t s1 = s0 + 1;
+            while (s1 < a->n && s1 - s0 < 65535 && wanted(s1) == w) s1++;
+            hipLaunchKernelGGL(slots_to_bitmap_kernel, dim3((unsigned)g->batches, (unsigned)(s1 - s0)), dim3(64), 0, 0, g->slots + s0 * g->batches * (SLOT_BYTES / 2), g->batches,
+                               a->planes + 4 * a->n_pad + s0, a->n_pad, g->nnl_mask, g->lst_mask, g->off_lst, g->groups, g->tgroups, w ? 1 : 0, tmp + s0 * g->tgroups);
+            ok = hipGetLastError() == hipSuccess;
+            s0 = s1;
+        }
+        ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, tmp, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+        (void)hipFree(tmp);
+        return ok ? bytes : 0;
+    }
     case 9: src = g->c_p; bytes = a->n * 4; break;
     case 10: src = g->qlines; bytes = g->n_qlines * g->qw * 4; break;
     case 11: if (cap < 8) return 0; *static_cast<uint64_t *>(out) = g->n_qlines; return 8;
     case 12: if (cap < 8) return 0; *static_cast<uint64_t *>(out) = g->qw; return 8;
+    case 13: if (cap < 16) return 0; static_cast<uint64_t *>(out)[0] = g->slots ? 1 : 0; static_cast<uint64_t *>(out)[1] = g->slot_lines; return 16;
     default: return 0;
     }
     if (!src || bytes == 0 || bytes > cap) return 0;

@@ -133,7 +133,7 @@ class Alignment:
 
     @property
     def list_stats(self):
-        """{nn_visits, nn_walks, n_lines, p_entries, n_entry_bytes[, max_row_n, bitmaps, row_splits]}: list entries one pass of the N
+        """{nn_visits, nn_walks, n_lines, p_entries, n_entry_bytes[, max_row_n, bitmaps, row_splits, row_lists, row_list_lines]}: list entries one pass of the N
         co-occurrence walk decodes (sum of cN^2 over the sites whose co-occurrences come from lists) in how many list walks (sum of
         cN), 128-byte lines reserved for the per-site N lists, entries of the listed-sample lists, bytes per N list entry; the most N
         sites any sample has and the workgroups its row is cut over; None without classes."""
@@ -147,6 +147,10 @@ class Alignment:
             # (nn_rows_kernel cuts a row over up to 32 workgroups by its N sites: csrc/site_lists.hip)
             target = max(8192, st["nn_walks"] // 2048)
             st.update(max_row_n=int(sizes[7]), bitmaps=bool(sizes[5]), row_splits=min(32, max(1, -(-int(sizes[7]) // target))))
+            # (the rows' N sites as slots of 16-bit entries instead of bitmaps, and the 128-byte lines of them that the build wrote)
+            rl = (C.c_uint64 * 2)()
+            has = self._L.tracs_debug_lists(self._h, 13, rl, 16) == 16
+            st.update(row_lists=bool(has and rl[0]), row_list_lines=int(rl[1]) if has else 0)
         return st
 
     @property
