@@ -51,7 +51,7 @@ int tracs_device_count(void);
  *   fasta: 1 path (all i<j) or 2 paths (file0 x file1 only, pairsnp.hpp:352-360); plain or gzip.
  *   n_threads: accepted for signature parity; the pair loop runs on the GPU.
  *   dist: emit pairs with d <= dist (signed int compare, pairsnp.hpp:405).
- *   filter: recombination filter (pairsnp.hpp:251-318; parity unpinned); 0 => filt_distances are `len` zeros
+ *   filter: recombination filter (pairsnp.hpp:251-318; pinned to its definition); 0 => filt_distances are `len` zeros
  *           (pairsnp.hpp:452 with combine_vectors :31).
  * The result is an opaque handle read through the accessors below; rows/cols/... are
  * row-major (i, then j) like the reference (pairsnp.hpp:451-455).                         */

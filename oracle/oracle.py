@@ -178,7 +178,8 @@ def filter_recomb_positions(pos, L):
 
 
 def filter_recomb_pairs(seqs, rows, cols, n_threads=1):
-    """Filtered SNP distance (src/pairsnp.hpp:251-318) of the listed pairs.  PARITY UNPINNED (Boost)."""
+    """Filtered SNP distance (src/pairsnp.hpp:251-318) of the listed pairs.  No comparison with Boost; pinned to the
+    definition at 50 digits on crafted boundary cases (tests/test_filter_hp.py)."""
     seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
     n, L = seqs.shape
     planes = pack(seqs)

@@ -529,8 +529,9 @@ int orc_num_threads(void)
 /* ------------------------------------------------------------------------- */
 /* Recombination filter.  src/pairsnp.hpp:223-318 (filter_recomb, range_count) with
  * cached_binomial_cdf (:41-58) = boost::math::cdf(binomial_distribution(n, p), k).
- * PARITY UNPINNED: Boost is absent and the reference's golden input (long_filt.aln,
- * tests/test_pairsnp.py:14-21) is not in the tree.  Boost documents
+ * No comparison with Boost: it is absent and the reference's golden input (long_filt.aln,
+ * tests/test_pairsnp.py:14-21) is not in the tree; the decision is pinned to the definition at 50
+ * digits on crafted boundary cases instead (tests/test_filter_hp.py).  Boost documents
  *   cdf(binomial(n, p), k) = ibetac(k + 1, n - k, p)  for k < n,  1 for k = n;
  * here ibetac comes from the Lentz continued fraction for the regularised incomplete
  * beta function (checked against scipy.stats.binom.cdf in tests/test_filter_recomb.py). */
@@ -585,13 +586,16 @@ uint64_t orc_filter_recomb_positions(const int64_t *pos, int64_t d_count, int64_
     if (window_size_half > 5000) window_size_half = 5000;                   /* :270 */
     if (window_size_half < 50) window_size_half = 50;                       /* :271 */
     uint64_t filtered_d = 0;
+    int64_t u0 = 0;
     for (int64_t t = 0; t < d_count; t++) {                                 /* :281 */
         int i = (int)pos[t];
         int64_t left = i - window_size_half; if (left < 0) left = 0;        /* :284 */
         int64_t right = (int64_t)i + window_size_half + 1; if (right > aln_length) right = aln_length;   /* :285 */
-        /* range_count :223-248: scan from the first set bit; count those in [left, right), span first..last */
+        /* range_count :223-248: scan from the first set bit; count those in [left, right), span first..last
+         * (the sites are sorted and `left` never goes back, so the scan resumes at the first site >= the last `left`) */
         int64_t count = 0, first = 0, length = 0;
-        for (int64_t u = 0; u < d_count && pos[u] < right; u++)
+        while (u0 < d_count && pos[u0] < left) u0++;
+        for (int64_t u = u0; u < d_count && pos[u] < right; u++)
             if (pos[u] >= left) {
                 if (count == 0) first = pos[u];
                 count++;

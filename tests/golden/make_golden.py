@@ -29,7 +29,7 @@ from oracle import oracle as O  # noqa: E402
 from tracs_amd import synth  # noqa: E402
 
 R = O.ref_module()
-assert R is not None or sys.argv[1:] == ["hp-transcluster"], "oracle/_ref is not built (make -C oracle)"
+assert R is not None or sys.argv[1:] in (["hp-transcluster"], ["hp-filter"]), "oracle/_ref is not built (make -C oracle)"
 
 
 def jdump(name, obj):
@@ -355,7 +355,74 @@ def hp_transcluster():
     print("wrote transcluster_hp_golden.json", len(rows), "keys")
 
 
+# ---------------------------------------------------------------------------------------
+# The recombination filter's keep / drop boundary from its definition at 50 digits (tests/hp_filter.py).  One alignment per L; its
+# sample s differs from sample 0 at the crafted sites of d_s.  What the d reach:
+#   9 000:     the smallest d; L / (2 d) = 50 exactly (90: wh 51 against the clamp at 50, 91); dense p, where the binomial sum runs
+#              on the lower side of the mean
+#   120 000:   wh at 5 000 exactly (12); L / (2 d) = 1 500 exactly (40: the double rounding of 1.0 / p / 2.0 + 1); wh 51 against
+#              50 (1 200, 1 201); spans clipped by 2 wh + 1
+#   600 000:   wh clamped at 5 000 (45, 60) and the first d below the clamp (61); the bench workload's p = 980 / 5 M (118)
+#   1 000 000: the bench workload's p again (196); the last table row and the first per-SNP one (65 536, 65 537); d far beyond
+# A d whose sites held an ill cell would be replaced by d + 1 and said so here: none did.
+FILTER_HP_CASES = ((9000, (2, 3, 90, 91, 600, 1500)),
+                   (120000, (2, 7, 12, 37, 40, 300, 1200, 1201, 9000)),
+                   (600000, (45, 60, 61, 118)),
+                   (1000000, (196, 4200, 65536, 65537, 70000, 150000)))
+
+
+def _hp_filter_one(args):
+    import hp_filter as H
+    L, d = args
+    _, thr, wh = H.window(L, d)
+    row = H.row(L, d)
+    pos, covered = H.plan(L, d, row)
+    kept, cells, ill, margin = H.filter_positions(pos, L)
+    assert ill == 0, ("ill cell", L, d)
+    hit = H.must_hit(L, d, row)
+    assert all(c in cells for c in hit), ("the sites miss a boundary cell", L, d)
+    # every k that has a boundary within reach of a window (n* <= 2 wh + 1; k = 2: <= wh + 1), up to 8 of them where d >= 600 and 2
+    # where d >= 20: a sparse pair has no more than five or six such k (120 000 / 1 200: k = 2 .. 6), whatever the sites
+    attainable = sum(n is not None and n <= (wh + 1 if k == 0 else 2 * wh + 1) for k, n in enumerate(row))
+    assert len(covered) >= min(8 if d >= 600 else 2 if d >= 20 else 0, attainable), (L, d, covered)
+    p = d / L
+    ratio = 0.0
+    with H.mp.workdps(H.DPS):
+        for k, n in ((k + 2, n - e) for k, n in enumerate(row) if n is not None for e in (0, 1)):
+            margin = min(margin, H.rel_margin(n, k, L, d))
+            err = abs(H.mpf(1.0 - O.binomial_cdf(n, p, k)) - H.tail(n, k, p)) / H.mpf(thr)
+            ratio = max(ratio, float(err))
+    assert O.filter_recomb_positions(pos, L) == kept, ("oracle != definition", L, d)
+    shape, at_wh, beyond = H.choose_probe(L, d)
+    return {"L": L, "d": d, "wh": wh, "row": row, "min_margin": margin, "covered": len(covered), "attainable": attainable, "cells": len(cells),
+            "expected": kept, "probe": [shape, at_wh, beyond]}, ratio
+
+
+def hp_filter():
+    import multiprocessing
+    sys.path.insert(0, os.path.dirname(HERE))
+    import hp_filter as H
+    work = [(L, d) for L, ds in FILTER_HP_CASES for d in ds]
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool:
+        res = pool.map(_hp_filter_one, work, chunksize=1)
+    cases = [r[0] for r in res]
+    head = {"about": "the recombination filter's smallest surviving span n*(k), k = 2 .. 63, and the filtered distance of crafted pairs "
+                     "(hp_filter.boundary_positions(L, d, row)) from the definition at %d digits (tests/hp_filter.py)" % H.DPS,
+            "margin": H.MARGIN, "digits": H.DPS,
+            "measured": {"min_relative_margin": min(c["min_margin"] for c in cases),
+                         "oracle_max_error_over_threshold": float("%.2g" % max(r[1] for r in res)),
+                         "ill_cells": 0,
+                         "covered_per_case": {"%d/%d" % (c["L"], c["d"]): c["covered"] for c in cases}}}
+    with open(os.path.join(HERE, "filter_hp_golden.json"), "w") as fh:
+        fh.write(json.dumps(head)[:-1] + ', "cases": [\n')
+        fh.write(",\n".join(json.dumps(c) for c in cases) + "\n]}\n")
+    print("wrote filter_hp_golden.json", len(cases), "cases;", json.dumps(head["measured"]))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["hp-filter"]:            # only the high-precision filter fixture (no reference needed)
+        hp_filter()
+        sys.exit(0)
     if sys.argv[1:] == ["hp-transcluster"]:     # only the high-precision transcluster fixture (no reference, no oracle needed)
         hp_transcluster()
         sys.exit(0)

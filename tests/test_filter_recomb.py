@@ -1,6 +1,8 @@
-"""Recombination filter (src/pairsnp.hpp:223-318).  PARITY UNPINNED: the reference needs Boost's binomial CDF
-and its golden input long_filt.aln is not in the tree, so the oracle is checked against first principles
-(scipy's binomial CDF, an independent Python restatement) and the GPU against the oracle."""
+"""Recombination filter (src/pairsnp.hpp:223-318).  No comparison with Boost: the reference needs its binomial CDF
+and its golden input long_filt.aln is not in the tree.  Here the oracle is checked against first principles
+(scipy's binomial CDF, an independent Python restatement) and the GPU against the oracle on random alignments with planted blocks;
+the keep / drop boundary itself -- oracle and every GPU route against the definition at 50 digits -- is tests/test_filter_hp.py and
+tests/test_gpu_filter_hp.py."""
 import os
 
 import numpy as np

@@ -11,7 +11,8 @@
 //                          HBM-bound; sample-minor layout => 16 B segments) and writes the sorted site list;
 //   filter_test_kernel     lanes stride over the SNPs: two binary searches give count and span, the
 //                          binomial tail is summed directly (integer a, b: I_p(k+1, n-k) is a finite sum).
-// PARITY UNPINNED: Boost's ibetac is replaced by the exact finite sum.
+// No comparison with Boost (absent): its ibetac is replaced by the exact finite sum, and the keep / drop decision is pinned to the
+// definition at 50 digits on crafted boundary pairs (tests/test_gpu_filter_hp.py).
 #include "common.h"
 #include "filter_math.h"
 
@@ -259,7 +260,9 @@ int filter_scan_route(const tracs_alignment *a, const unsigned *rows, const unsi
     long long *off;
     unsigned long long *sums;
     int rc;
-    if ((rc = workspace_get(ScanWs::POS, (std::min<size_t>(per * std::max<size_t>(max_d, 1), kMaxPos) + 64) * 4, reinterpret_cast<void **>(&pos))) ||
+    // (a batch is never less than one pair: a pair with more SNP sites than kMaxPos still needs room for all of them)
+    const size_t pos_cap = std::max<size_t>(std::min<size_t>(per * std::max<size_t>(max_d, 1), kMaxPos), max_d);
+    if ((rc = workspace_get(ScanWs::POS, (pos_cap + 64) * 4, reinterpret_cast<void **>(&pos))) ||
         (rc = workspace_get(ScanWs::FOUND, per * 4, reinterpret_cast<void **>(&found))) ||
         (rc = workspace_get(ScanWs::OFF, (per + 1) * 8, reinterpret_cast<void **>(&off))) ||
         (rc = workspace_get(ScanWs::SUMS, ((per + 1023) / 1024 + 1) * 8, reinterpret_cast<void **>(&sums)))) return rc;

@@ -19,7 +19,8 @@
 // one compare.  Pairs whose lists do not fit a wave's LDS (partial IUPAC codes: tens of thousands of entries per sample) take the
 // same merge over global memory (flt_pairs_long_kernel); alignments whose lists cannot be built (more than a tenth of all cells
 // listed, no memory) the scan of the planes (filter.hip: the reference's own way, which also returns the positions).
-// PARITY UNPINNED: Boost's ibetac is replaced by the exact finite sum.
+// No comparison with Boost (absent): its ibetac is replaced by the exact finite sum, and the keep / drop decision is pinned to the
+// definition at 50 digits on crafted boundary pairs (tests/test_gpu_filter_hp.py).
 #include "common.h"
 #include "filter_math.h"
 #include "pairsnp_kernels.h"

@@ -1,7 +1,8 @@
 // filter_math.h -- arithmetic shared by the two routes of the recombination filter (filter.hip: positions from a scan of the
 // planes; filter_lists.hip: positions from the samples' departure lists).  Reference behaviour restated (never copied):
 // /root/reference/src/pairsnp.hpp filter_recomb :251-318, range_count :223-248, cached_binomial_cdf :41-58.
-// PARITY UNPINNED: Boost's ibetac is replaced by the exact finite sum.
+// No comparison with Boost (absent): its ibetac is replaced by the exact finite sum, and the keep / drop decision is pinned to the
+// definition at 50 digits on crafted boundary pairs (tests/test_gpu_filter_hp.py).
 #pragma once
 #include "common.h"
 
