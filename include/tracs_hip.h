@@ -79,6 +79,15 @@ void tracs_pairsnp_free(tracs_pairsnp_result *r);
 int tracs_nearest(const char *const *fasta, int n_fasta, int n_threads, int k, int dist, int filter,
                   tracs_pairsnp_result **out);
 
+/* tracs_pairsnp / tracs_nearest under a site rule (tracs_alignment_select_sites: keep over the columns of the files, NULL = all;
+ * max_n_samples counted over every loaded sample, both files of a two-file run; UINT32_MAX = no rule): the result is that of the
+ * files with the dropped columns deleted, tracs_pairsnp_seqlen the number of kept columns.  Without any rule: the plain entry
+ * points, call for call.                                                                                                     */
+int tracs_pairsnp_sites(const char *const *fasta, int n_fasta, int n_threads, int dist, int filter, const uint64_t *keep,
+                        size_t keep_len, uint32_t max_n_samples, tracs_pairsnp_result **out);
+int tracs_nearest_sites(const char *const *fasta, int n_fasta, int n_threads, int k, int dist, int filter, const uint64_t *keep,
+                        size_t keep_len, uint32_t max_n_samples, tracs_pairsnp_result **out);
+
 /* trans_dist(snpdiff, datediff, lamb, beta, threshold_Ek) -> (p0_log[n], eK[n])
  *   replaces: src/python_bindings.cpp:19-21 -> src/transcluster.hpp:240-287.               */
 int tracs_trans_dist(const int32_t *snpdiff, const double *datediff, size_t n, double lamb, double beta,
@@ -140,6 +149,21 @@ int tracs_alignment_pack(tracs_alignment *a, const uint8_t *ascii, size_t first,
 int tracs_alignment_from_fasta(const char *const *fasta, int n_fasta, tracs_alignment **out,
                                char **names_out, size_t *names_bytes, size_t *n_first_file);
 void tracs_free(void *p);
+
+/* Site rules (not in the reference).  A run with a site rule is, by definition, the run on the alignment with the
+ * dropped columns deleted from every record: the kept columns are packed into a new handle that is byte for byte what packing the
+ * column-deleted text gives, and every other entry point runs on that handle unchanged.
+ *   tracs_alignment_site_n_counts  per site, the samples that are N there (bit set in the stored N plane: 'N', '-' and every byte
+ *                                  that is not an IUPAC letter; partial codes are not N) -> counts, device uint32[L]
+ *   tracs_alignment_select_sites   keep: host bitmap, bit s of keep[s / 64] = site s may stay; NULL = all.  keep_len must equal the
+ *                                  handle's length.  max_n_samples: a site stays only if at most that many samples are N there;
+ *                                  UINT32_MAX = no rule.  *out: a NEW handle over the kept columns (src is left as it was and stays
+ *                                  usable).  kept (host, ceil(L / 64) words, may be NULL) receives the final bitmap, *n_kept its
+ *                                  population.  A rule that leaves no site is refused (TRACS_E_ARG, "no site left after the site
+ *                                  rules").  Synchronises the stream.                                                        */
+int tracs_alignment_site_n_counts(const tracs_alignment *a, uint32_t *counts, void *stream);
+int tracs_alignment_select_sites(const tracs_alignment *src, const uint64_t *keep, size_t keep_len, uint32_t max_n_samples,
+                                 tracs_alignment **out, uint64_t *kept, size_t *n_kept, void *stream);
 
 /* Dense pair block: for rows i in [row_begin,row_end) and columns j in [max(col_begin,i+1), n)
  *   dist[i*ld + j]  = d(i,j)  = L - popcount(match)           (pairsnp.hpp:398-403)
@@ -427,6 +451,14 @@ void tracs_warm_up(void);
  *                         evaluated per emitted pair (tracs_trans_dist_device) instead of on the panel.                          */
 typedef struct tracs_distance tracs_distance;
 int tracs_distance_open(const char *const *fasta, int n_fasta, tracs_distance **out);
+/*   tracs_distance_open_sites  tracs_distance_open under a site rule (tracs_alignment_select_sites' keep / keep_len / max_n_samples):
+ *                         every later call on the handle sees the kept columns only.  _source_len: columns read; _len: columns kept;
+ *                         _kept_sites: the final bitmap over the columns read, ceil(source_len / 64) host words.                  */
+int tracs_distance_open_sites(const char *const *fasta, int n_fasta, const uint64_t *keep, size_t keep_len, uint32_t max_n_samples,
+                              tracs_distance **out);
+size_t tracs_distance_source_len(const tracs_distance *h);
+size_t tracs_distance_len(const tracs_distance *h);
+int tracs_distance_kept_sites(const tracs_distance *h, uint64_t *kept);
 size_t tracs_distance_nseq(const tracs_distance *h);
 const char *tracs_distance_name(const tracs_distance *h, size_t i);
 int tracs_distance_run(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,

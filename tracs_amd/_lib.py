@@ -39,6 +39,8 @@ SYMBOLS = [
     "tracs_warm_up",
     "tracs_nearest", "tracs_knn_state_bytes", "tracs_knn_init", "tracs_knn_update", "tracs_knn_emit",
     "tracs_distance_forest", "tracs_msf_state_bytes", "tracs_msf_init", "tracs_msf_update_coo", "tracs_msf_emit",
+    "tracs_alignment_site_n_counts", "tracs_alignment_select_sites", "tracs_pairsnp_sites", "tracs_nearest_sites",
+    "tracs_distance_open_sites", "tracs_distance_source_len", "tracs_distance_len", "tracs_distance_kept_sites",
     "tracs_distance_histogram", "tracs_hist_state_bytes", "tracs_hist_init", "tracs_hist_update", "tracs_hist_update_coo", "tracs_hist_emit",
 ]
 
@@ -177,6 +179,24 @@ def load():
     L.tracs_hist_update_coo.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
     L.tracs_hist_emit.restype = C.c_int
     L.tracs_hist_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp]
+    L.tracs_alignment_site_n_counts.restype = C.c_int
+    L.tracs_alignment_site_n_counts.argtypes = [vp, vp, vp]
+    L.tracs_alignment_select_sites.restype = C.c_int
+    L.tracs_alignment_select_sites.argtypes = [vp, u64p, sz, C.c_uint32, C.POINTER(vp), u64p, C.POINTER(sz), vp]
+    L.tracs_pairsnp_sites.restype = C.c_int
+    L.tracs_pairsnp_sites.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, u64p, sz, C.c_uint32, C.POINTER(vp)]
+    L.tracs_nearest_sites.restype = C.c_int
+    L.tracs_nearest_sites.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u64p, sz, C.c_uint32, C.POINTER(vp)]
+    L.tracs_distance_open_sites.restype = C.c_int
+    L.tracs_distance_open_sites.argtypes = [C.POINTER(C.c_char_p), C.c_int, u64p, sz, C.c_uint32, C.POINTER(vp)]
+    L.tracs_distance_source_len.restype = sz
+    L.tracs_distance_source_len.argtypes = [vp]
+    L.tracs_distance_len.restype = sz
+    L.tracs_distance_len.argtypes = [vp]
+    L.tracs_distance_kept_sites.restype = C.c_int
+    L.tracs_distance_kept_sites.argtypes = [vp, u64p]
+    L.tracs_debug_site_select_timing.restype = C.c_int
+    L.tracs_debug_site_select_timing.argtypes = [vp, u64p, sz, C.c_uint32, C.c_int, C.POINTER(C.c_float), C.POINTER(sz), C.POINTER(C.c_int)]
     L.tracs_debug_hist_routes.restype = C.c_int
     L.tracs_debug_hist_routes.argtypes = [vp, C.POINTER(C.c_double)]
     L.tracs_warm_up.restype = None

@@ -18,8 +18,18 @@ def _paths(fasta):
     return [os.fsencode(p) for p in fasta]
 
 
-def pairsnp_arrays(fasta, n_threads=1, dist=2147483647, filter=False):
-    """Like pairsnp() but returns numpy arrays: (rows, cols, distances, names, filt_distances, n_compared)."""
+def _site_args(sites):
+    """sites (tracs_amd.sites.Sites or None) -> (array kept alive, keep pointer, keep_len, max_n_samples) of the _sites entry points"""
+    if sites is None:
+        return None, None, 0, 0xFFFFFFFF
+    words, keep_len, max_n = sites.c_args()
+    return words, (words.ctypes.data_as(C.POINTER(C.c_uint64)) if words is not None else None), keep_len, max_n
+
+
+def pairsnp_arrays(fasta, n_threads=1, dist=2147483647, filter=False, sites=None, info=None):
+    """Like pairsnp() but returns numpy arrays: (rows, cols, distances, names, filt_distances, n_compared).
+    sites (tracs_amd.sites.Sites): the run on the files with the dropped columns deleted.  info: a dict that
+    receives "seqlen", the alignment length the result stands for (the kept columns)."""
     paths = _paths(fasta)
     if len(paths) < 1 or len(paths) > 2:
         raise RuntimeError("Invalid number of fasta files!")      # src/pairsnp.hpp:340-343
@@ -30,16 +40,22 @@ def pairsnp_arrays(fasta, n_threads=1, dist=2147483647, filter=False):
     L = _lib.require_gpu()
     arr = (C.c_char_p * len(paths))(*paths)
     h = C.c_void_p()
-    _lib.check(L.tracs_pairsnp(arr, len(paths), int(n_threads), int(dist), int(bool(filter)), C.byref(h)))
+    if sites is None:
+        _lib.check(L.tracs_pairsnp(arr, len(paths), int(n_threads), int(dist), int(bool(filter)), C.byref(h)))
+    else:
+        alive, kp, keep_len, max_n = _site_args(sites)
+        _lib.check(L.tracs_pairsnp_sites(arr, len(paths), int(n_threads), int(dist), int(bool(filter)), kp, keep_len, max_n, C.byref(h)))
+    if info is not None:
+        info["seqlen"] = int(L.tracs_pairsnp_seqlen(h))
     return _result_arrays(L, h)
 
 
-def nearest_arrays(fasta, k, n_threads=1, dist=2147483647, filter=False):
+def nearest_arrays(fasta, k, n_threads=1, dist=2147483647, filter=False, sites=None, info=None):
     """The k nearest neighbours of each sample (tracs_nearest, include/tracs_hip.h): the six arrays of pairsnp_arrays, rows = the
     sample (ascending), cols = its neighbours ranked by (SNP distance, sample index), at most k per sample.  One file: candidates
     are all other samples; two files: the samples of file 0 get lists, their candidates are the samples of file 1.  Only pairs
     with d <= dist are eligible.  filter: the filtered distances of the emitted pairs (the ranking uses the raw distance).
-    n_threads is accepted for parity with pairsnp_arrays and unused: every stage runs on the GPU."""
+    n_threads is accepted for parity with pairsnp_arrays and unused: every stage runs on the GPU.  sites: as pairsnp_arrays."""
     paths = _paths(fasta)
     if len(paths) < 1 or len(paths) > 2:
         raise RuntimeError("Invalid number of fasta files!")
@@ -52,7 +68,13 @@ def nearest_arrays(fasta, k, n_threads=1, dist=2147483647, filter=False):
     L = _lib.require_gpu()
     arr = (C.c_char_p * len(paths))(*paths)
     h = C.c_void_p()
-    _lib.check(L.tracs_nearest(arr, len(paths), int(n_threads), k, int(dist), int(bool(filter)), C.byref(h)))
+    if sites is None:
+        _lib.check(L.tracs_nearest(arr, len(paths), int(n_threads), k, int(dist), int(bool(filter)), C.byref(h)))
+    else:
+        alive, kp, keep_len, max_n = _site_args(sites)
+        _lib.check(L.tracs_nearest_sites(arr, len(paths), int(n_threads), k, int(dist), int(bool(filter)), kp, keep_len, max_n, C.byref(h)))
+    if info is not None:
+        info["seqlen"] = int(L.tracs_pairsnp_seqlen(h))
     return _result_arrays(L, h)
 
 
@@ -89,12 +111,12 @@ def read_histogram_rows(path):
     return out
 
 
-def distance_histogram(fasta, dist=2147483647, filter=False, groups=None):
+def distance_histogram(fasta, dist=2147483647, filter=False, groups=None, sites=None):
     """How many pairs have each SNP distance (tracs_distance_histogram, include/tracs_hip.h): the pairs pairsnp_arrays(fasta, dist=dist)
     returns, counted on the GPU without being emitted.  -> (names, {"snp": h[, "filter": h]}) with h = {"value": uint32[], "within":
     uint64[], "between": uint64[], "ungrouped": uint64[]}, the non-empty bins ascending.  groups: mapping sample name -> label (any
     hashable; missing or None: ungrouped); without it every pair is `ungrouped`.  filter: also the histogram of the filtered
-    distances of the same pairs."""
+    distances of the same pairs.  sites: as pairsnp_arrays."""
     import tempfile
     paths = _paths(fasta)
     if len(paths) < 1 or len(paths) > 2:
@@ -105,7 +127,11 @@ def distance_histogram(fasta, dist=2147483647, filter=False, groups=None):
     L = _lib.require_gpu()
     arr = (C.c_char_p * len(paths))(*paths)
     h = C.c_void_p()
-    _lib.check(L.tracs_distance_open(arr, len(paths), C.byref(h)))
+    if sites is None:
+        _lib.check(L.tracs_distance_open(arr, len(paths), C.byref(h)))
+    else:
+        alive, kp, keep_len, max_n = _site_args(sites)
+        _lib.check(L.tracs_distance_open_sites(arr, len(paths), kp, keep_len, max_n, C.byref(h)))
     try:
         names = [L.tracs_distance_name(h, i).decode("utf-8", "replace") for i in range(L.tracs_distance_nseq(h))]
         labels = group_labels(names, groups)

@@ -190,8 +190,29 @@ extern "C" void tracs_warm_up(void)
     std::call_once(once, [] { std::thread(warm_up_body).detach(); });
 }
 
+// A site rule of the FASTA entry points: which columns stay.  No rule at all is a NULL pointer, and then nothing
+// below differs from what the entry points did before there were rules.
+struct SiteRule {
+    const uint64_t *keep = nullptr;      // host bitmap over the columns read, NULL: every column may stay
+    size_t keep_len = 0;
+    uint32_t max_n = UINT32_MAX;         // a column stays only if at most that many samples are N there
+    std::vector<uint64_t> kept;          // out: the final bitmap over the columns read
+    size_t source_len = 0;               // out: columns read
+    bool active() const { return keep != nullptr || max_n != UINT32_MAX; }
+};
+
+static int alignment_from_fasta_sites(const char *const *fasta, int n_fasta, tracs_alignment **out, char **names_out,
+                                      size_t *names_bytes, size_t *n_first_file, SiteRule *rule);
+
 int tracs_alignment_from_fasta(const char *const *fasta, int n_fasta, tracs_alignment **out, char **names_out,
                                size_t *names_bytes, size_t *n_first_file)
+{
+    return alignment_from_fasta_sites(fasta, n_fasta, out, names_out, names_bytes, n_first_file, nullptr);
+}
+
+// read + pack, then -- only with a rule -- select the kept columns into a new handle and free the one that was packed
+static int alignment_from_fasta_sites(const char *const *fasta, int n_fasta, tracs_alignment **out, char **names_out,
+                                      size_t *names_bytes, size_t *n_first_file, SiteRule *rule)
 {
     if (out) *out = nullptr;
     if (names_out) *names_out = nullptr;
@@ -234,6 +255,19 @@ int tracs_alignment_from_fasta(const char *const *fasta, int n_fasta, tracs_alig
         if (rc) { tracs_alignment_free(a); return rc; }
     }
     clock.mark("H2D + pack", (double)fd.n * (double)fd.L);
+    if (rule) {
+        rule->source_len = a->L;
+        if (rule->active()) {
+            // (the N rule counts over every loaded sample: both files of a two-file run)
+            tracs_alignment *sel = nullptr;
+            rule->kept.assign((a->L + 63) / 64, 0);
+            rc = select_sites(a, rule->keep, rule->keep_len, rule->max_n, &sel, rule->kept.data(), nullptr, nullptr, true);
+            tracs_alignment_free(a);
+            if (rc) return rc;
+            a = sel;
+            clock.mark("site rules (N counts, list, selection)");
+        }
+    }
     if (names_out) {
         size_t bytes = 0;
         for (auto &nm : fd.names) bytes += nm.size() + 1;
@@ -248,9 +282,35 @@ int tracs_alignment_from_fasta(const char *const *fasta, int n_fasta, tracs_alig
     return TRACS_OK;
 }
 
+static int pairsnp_run(const char *const *fasta, int n_fasta, int dist, int filter, SiteRule *rule, tracs_pairsnp_result **out);
+static int nearest_run(const char *const *fasta, int n_fasta, int k, int dist, int filter, SiteRule *rule, tracs_pairsnp_result **out);
+
 int tracs_pairsnp(const char *const *fasta, int n_fasta, int n_threads, int dist, int filter, tracs_pairsnp_result **out)
 {
     (void)n_threads;
+    return pairsnp_run(fasta, n_fasta, dist, filter, nullptr, out);
+}
+
+int tracs_pairsnp_sites(const char *const *fasta, int n_fasta, int n_threads, int dist, int filter, const uint64_t *keep, size_t keep_len,
+                        uint32_t max_n_samples, tracs_pairsnp_result **out)
+{
+    (void)n_threads;
+    SiteRule rule;
+    rule.keep = keep; rule.keep_len = keep_len; rule.max_n = max_n_samples;
+    return pairsnp_run(fasta, n_fasta, dist, filter, rule.active() ? &rule : nullptr, out);
+}
+
+int tracs_nearest_sites(const char *const *fasta, int n_fasta, int n_threads, int k, int dist, int filter, const uint64_t *keep,
+                        size_t keep_len, uint32_t max_n_samples, tracs_pairsnp_result **out)
+{
+    (void)n_threads;
+    SiteRule rule;
+    rule.keep = keep; rule.keep_len = keep_len; rule.max_n = max_n_samples;
+    return nearest_run(fasta, n_fasta, k, dist, filter, rule.active() ? &rule : nullptr, out);
+}
+
+static int pairsnp_run(const char *const *fasta, int n_fasta, int dist, int filter, SiteRule *rule, tracs_pairsnp_result **out)
+{
     if (!out) { set_error("tracs_pairsnp: out is NULL"); return TRACS_E_ARG; }
     *out = nullptr;
     if (n_fasta < 1 || n_fasta > 2 || !fasta) { set_error("Invalid number of fasta files!"); return TRACS_E_ARG; }   // :340-343
@@ -258,7 +318,7 @@ int tracs_pairsnp(const char *const *fasta, int n_fasta, int n_threads, int dist
     tracs_alignment *a = nullptr;
     char *names = nullptr;
     size_t names_bytes = 0, n0 = 0;
-    int rc = tracs_alignment_from_fasta(fasta, n_fasta, &a, &names, &names_bytes, &n0);
+    int rc = alignment_from_fasta_sites(fasta, n_fasta, &a, &names, &names_bytes, &n0, rule);
     if (rc) return rc;
     auto *res = new tracs_pairsnp_result();
     res->nseq = a->n; res->L = a->L;
@@ -379,6 +439,11 @@ __global__ __launch_bounds__(256) void knn_pair_order_kernel(const unsigned *__r
 int tracs_nearest(const char *const *fasta, int n_fasta, int n_threads, int k, int dist, int filter, tracs_pairsnp_result **out)
 {
     (void)n_threads;
+    return nearest_run(fasta, n_fasta, k, dist, filter, nullptr, out);
+}
+
+static int nearest_run(const char *const *fasta, int n_fasta, int k, int dist, int filter, SiteRule *rule, tracs_pairsnp_result **out)
+{
     if (!out) { set_error("tracs_nearest: out is NULL"); return TRACS_E_ARG; }
     *out = nullptr;
     if (n_fasta < 1 || n_fasta > 2 || !fasta) { set_error("Invalid number of fasta files!"); return TRACS_E_ARG; }
@@ -387,7 +452,7 @@ int tracs_nearest(const char *const *fasta, int n_fasta, int n_threads, int k, i
     tracs_alignment *a = nullptr;
     char *names = nullptr;
     size_t names_bytes = 0, n0 = 0;
-    int rc = tracs_alignment_from_fasta(fasta, n_fasta, &a, &names, &names_bytes, &n0);
+    int rc = alignment_from_fasta_sites(fasta, n_fasta, &a, &names, &names_bytes, &n0, rule);
     if (rc) return rc;
     auto *res = new tracs_pairsnp_result();
     res->nseq = a->n; res->L = a->L;
@@ -478,9 +543,11 @@ struct tracs_distance {
     std::vector<const char *> name_ptr;
     size_t n0 = 0;
     int n_fasta = 0;
+    size_t source_len = 0;               // columns read (site rules: h->a holds the kept ones)
+    std::vector<uint64_t> kept;          // the kept columns; empty: every column
 };
 
-int tracs_distance_open(const char *const *fasta, int n_fasta, tracs_distance **out)
+static int distance_open(const char *const *fasta, int n_fasta, SiteRule *rule, tracs_distance **out)
 {
     if (!out) { set_error("tracs_distance_open: out is NULL"); return TRACS_E_ARG; }
     *out = nullptr;
@@ -488,13 +555,37 @@ int tracs_distance_open(const char *const *fasta, int n_fasta, tracs_distance **
     auto *h = new tracs_distance();
     char *names = nullptr;
     size_t names_bytes = 0;
-    const int rc = tracs_alignment_from_fasta(fasta, n_fasta, &h->a, &names, &names_bytes, &h->n0);
+    const int rc = alignment_from_fasta_sites(fasta, n_fasta, &h->a, &names, &names_bytes, &h->n0, rule);
     if (rc) { delete h; return rc; }
+    h->source_len = rule ? rule->source_len : h->a->L;
+    if (rule) h->kept = std::move(rule->kept);
     h->n_fasta = n_fasta;
     { size_t o = 0; for (size_t i = 0; i < h->a->n; i++) { h->names.emplace_back(names + o); o += h->names.back().size() + 1; } }
     tracs_free(names);
     for (auto &s : h->names) h->name_ptr.push_back(s.c_str());
     *out = h;
+    return TRACS_OK;
+}
+
+int tracs_distance_open(const char *const *fasta, int n_fasta, tracs_distance **out) { return distance_open(fasta, n_fasta, nullptr, out); }
+
+int tracs_distance_open_sites(const char *const *fasta, int n_fasta, const uint64_t *keep, size_t keep_len, uint32_t max_n_samples,
+                              tracs_distance **out)
+{
+    SiteRule rule;
+    rule.keep = keep; rule.keep_len = keep_len; rule.max_n = max_n_samples;
+    return distance_open(fasta, n_fasta, rule.active() ? &rule : nullptr, out);
+}
+
+size_t tracs_distance_source_len(const tracs_distance *h) { return h ? h->source_len : 0; }
+size_t tracs_distance_len(const tracs_distance *h) { return (h && h->a) ? h->a->L : 0; }
+int tracs_distance_kept_sites(const tracs_distance *h, uint64_t *kept)
+{
+    if (!h || !kept) { set_error("tracs_distance_kept_sites: NULL argument"); return TRACS_E_ARG; }
+    const size_t words = (h->source_len + 63) / 64;
+    if (!h->kept.empty()) { std::memcpy(kept, h->kept.data(), words * 8); return TRACS_OK; }
+    for (size_t w = 0; w < words; w++) kept[w] = ~0ull;
+    if (h->source_len & 63) kept[words - 1] = (1ull << (h->source_len & 63)) - 1;
     return TRACS_OK;
 }
 

@@ -115,6 +115,11 @@ static inline size_t pair_groups(const tracs_alignment *a) { return a->classes_s
 
 void filter_index_free(tracs_alignment *a);        // filter_lists.hip
 
+// site_select.hip: the kept sites of `src` packed into a new handle (tracs_alignment_select_sites); release_src_arena: `src` is about
+// to be freed, its unused arena goes before the new handle is allocated
+int select_sites(tracs_alignment *src, const uint64_t *keep, size_t keep_len, uint32_t max_n_samples, tracs_alignment **out,
+                 uint64_t *kept, size_t *n_kept, hipStream_t stream, bool release_src_arena);
+
 // device memory that lives until the alignment is packed again (site_classes_free releases all of it at once)
 hipError_t pack_alloc(tracs_alignment *a, size_t bytes, void **out);
 void pack_release(tracs_alignment *a);

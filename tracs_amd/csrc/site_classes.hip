@@ -904,6 +904,14 @@ int site_classes_decide(tracs_alignment *a, hipStream_t stream, int *partial)
     return decide(a, true, true, stream, partial);
 }
 
+// compact_sites_kernel<0> on any list (site_select.hip's timing entry measures select_sites_kernel against it); n_pad / 64 <= 65535
+void launch_compact_general(const uint4 *src, const unsigned *list, unsigned count, uint4 *dst, size_t n_pad, unsigned n, unsigned groups_dst,
+                            hipStream_t stream)
+{
+    const dim3 grid((groups_dst + 3) / 4, (unsigned)(n_pad / 64));
+    hipLaunchKernelGGL((compact_sites_kernel<0>), grid, dim3(256), 0, stream, src, list, count, dst, n_pad, n, groups_dst);
+}
+
 }  // namespace tracs
 
 extern "C" {

@@ -153,6 +153,32 @@ class Alignment:
             st.update(row_lists=bool(has and rl[0]), row_list_lines=int(rl[1]) if has else 0)
         return st
 
+    def site_n_counts(self):
+        """torch.int32 [L] on the device: per site, the samples that are N there (the stored N plane: 'N', '-' and every byte that
+        is not an IUPAC letter; partial codes are not N).  tracs_alignment_site_n_counts."""
+        out = torch.empty(self.L, dtype=torch.int32, device="cuda")
+        _lib.check(self._L.tracs_alignment_site_n_counts(self._h, _ptr(out), _stream()))
+        return out
+
+    def select_sites(self, keep=None, max_n_samples=None):
+        """-> (Alignment over the kept columns, kept bool ndarray [L]): a column stays when keep (bool per column; None: all) allows
+        it and at most max_n_samples samples are N there (None: no rule).  The new handle is byte for byte what packing the
+        column-deleted sequences gives; this one is left as it was.  tracs_alignment_select_sites."""
+        from .sites import Sites, bitmap_to_bool
+        words, keep_len, max_n = Sites(keep, max_n_samples).c_args()
+        kept = np.zeros((self.L + 63) // 64, np.uint64)
+        h, n_kept = C.c_void_p(), C.c_size_t(0)
+        u64p = C.POINTER(C.c_uint64)
+        _lib.check(self._L.tracs_alignment_select_sites(self._h, words.ctypes.data_as(u64p) if words is not None else None, keep_len, max_n,
+                                                        C.byref(h), kept.ctypes.data_as(u64p), C.byref(n_kept), _stream()))
+        new = Alignment.__new__(Alignment)
+        new._L, new._h = self._L, h
+        new.n, new.L = self.n, int(n_kept.value)
+        for attr in ("names", "n_first"):
+            if hasattr(self, attr):
+                setattr(new, attr, getattr(self, attr))
+        return new, bitmap_to_bool(kept, self.L)
+
     @property
     def nbytes(self):
         return self._L.tracs_alignment_bytes(self._h)

@@ -77,6 +77,21 @@ def distance_parser(parser):
                      help="With --histogram: csv (header line skipped) of sample name, group label.  A pair counts as `within` when "
                           "both samples have the same label, `between` when they have different labels, `ungrouped` when either has "
                           "none (empty label, or not listed).  Without --groups every pair is `ungrouped`.")
+    st = parser.add_argument_group("Site selection",
+                                   "A run with a site rule is the run on the alignment with the dropped columns deleted from every "
+                                   "record (applied to the packed alignment on the GPU; not in the reference).")
+    st.add_argument("--mask", dest="mask_bed", default=None, type=os.path.abspath, metavar="BED",
+                    help="Columns to drop (BED: 0-based, half-open; alignment columns, or contig coordinates with --mask-reference)")
+    st.add_argument("--keep", dest="keep_bed", default=None, type=os.path.abspath, metavar="BED",
+                    help="Only these columns may stay.  Together with --mask: keep minus mask.")
+    st.add_argument("--mask-reference", dest="mask_reference", default=None, type=os.path.abspath, metavar="REF.fa",
+                    help="The reference genome the alignments were made against: contig names and offsets for --mask and --keep "
+                         "(columns are its contigs concatenated in file order)")
+    st.add_argument("--max-n-share", dest="max_n_share", default=None, type=float, metavar="F",
+                    help="Drop a column when more than floor(F n) of the n samples are N there (0 <= F < 1; with --msa-db: the "
+                         "samples of both files)")
+    st.add_argument("--sites-out", dest="sites_out", default=None, type=str, metavar="FILE",
+                    help="Write the kept columns as a BED (readable back through --keep; contig coordinates with --mask-reference)")
     tr = parser.add_argument_group("Transmission distance options")
     tr.add_argument("--clock_rate", dest="clock_rate", type=check_positive_float, default=1e-3 * 29903,
                     help="clock rate as defined in the transcluster paper (SNPs/genome/year) default=1e-3 * 29903")
@@ -136,7 +151,7 @@ def _append_rows(path, names, rows, cols, snpd, filt, ncomp, ddiff, tdist, ek, k
     return written.value
 
 
-def _rows_on_device(msas, args, dates, ref, stage):
+def _rows_on_device(msas, args, dates, ref, stage, rule=None):
     """One alignment through libtracs_hip.so's device-resident path (tracs_distance_open / _run: include/tracs_hip.h): FASTA -> packed
     planes -> dense panels -> transcluster on the panels -> the pairs within the threshold with their P and E(K) -> ONE device-to-host
     pass, in batches -> the CSV rows, formatted and appended by the library's host threads.  Nothing comes back to Python but the
@@ -144,9 +159,7 @@ def _rows_on_device(msas, args, dates, ref, stage):
     only if that sample's index is at most the largest index among the emitted pairs, tracs/transcluster.py:23-32: left to the
     array path below, which reproduces that)."""
     L = _lib.require_gpu()
-    arr = (C.c_char_p * len(msas))(*[os.fsencode(p) for p in msas])
-    h = C.c_void_p()
-    _lib.check(L.tracs_distance_open(arr, len(msas), C.byref(h)))
+    h = _open(L, msas, rule, args)
     try:
         stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
         days = None
@@ -170,15 +183,13 @@ def _rows_on_device(msas, args, dates, ref, stage):
         L.tracs_distance_free(h)
 
 
-def _forest_on_device(msas, args, dates, ref, stage):
+def _forest_on_device(msas, args, dates, ref, stage, rule=None):
     """--mst WEIGHT for one alignment (tracs_distance_open / _forest: include/tracs_hip.h): the panel loop of _rows_on_device up to the
     pairs within the threshold with their P and E(K), then the minimum spanning forest of the eligible pairs on the device; only its
     rows are formatted and appended.  With metadata every sample needs a date (the full run's array route has KeyError rules of its
     own instead)."""
     L = _lib.require_gpu()
-    arr = (C.c_char_p * len(msas))(*[os.fsencode(p) for p in msas])
-    h = C.c_void_p()
-    _lib.check(L.tracs_distance_open(arr, len(msas), C.byref(h)))
+    h = _open(L, msas, rule, args)
     try:
         stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
         days = None
@@ -219,6 +230,122 @@ def check_mst_args(args):
         raise SystemExit("tracs distance: --mst %s needs --meta (the sampling dates that transmission distances come from)" % mst)
 
 
+def check_site_args(args):
+    """The site rules' argument checks, before anything touches the GPU (SystemExit with the message)."""
+    mask, keep = getattr(args, "mask_bed", None), getattr(args, "keep_bed", None)
+    share, ref, out = getattr(args, "max_n_share", None), getattr(args, "mask_reference", None), getattr(args, "sites_out", None)
+    if share is not None and not (0.0 <= share < 1.0):            # (a NaN fails too)
+        raise SystemExit("tracs distance: --max-n-share must be in [0, 1), got %r" % share)
+    if ref is not None and mask is None and keep is None:
+        raise SystemExit("tracs distance: --mask-reference needs --mask or --keep (it only gives their contigs an offset)")
+    rule = mask is not None or keep is not None or share is not None
+    if out is not None and not rule:
+        raise SystemExit("tracs distance: --sites-out needs a site rule (--mask, --keep or --max-n-share)")
+    if not rule:
+        return
+    if getattr(args, "gpus", 1) > 1:
+        raise SystemExit("tracs distance: site rules (--mask, --keep, --max-n-share) run on one GPU; use --gpus 1")
+    if out is not None and len(getattr(args, "msa_files", None) or []) > 1:
+        raise SystemExit("tracs distance: --sites-out describes one alignment; give one --msa file")
+    if out is not None and share is not None and getattr(args, "nearest", None) is not None:
+        raise SystemExit("tracs distance: --sites-out with --nearest takes file rules only (--mask, --keep), not --max-n-share")
+
+
+class _SiteRule:
+    """The site rule of one alignment: the keep bitmap over its columns (None: files give none) and the N threshold (None: no rule)"""
+
+    def __init__(self, L, keep, max_n, contigs):
+        from .sites import Sites
+        self.L, self.keep, self.max_n, self.contigs = L, keep, max_n, contigs
+        self.sites = Sites(keep, max_n)
+        self.reported = False
+
+    def report(self, args, msa, kept_words=None, n_kept=None):
+        """the INFO line of the alignment and --sites-out, once"""
+        from . import sites as S
+        if self.reported:
+            return
+        self.reported = True
+        by_files = self.L - int(self.keep.sum()) if self.keep is not None else 0
+        if n_kept is None:
+            n_kept = int(S.bitmap_to_bool(kept_words, self.L).sum())
+        logging.info("Site rules for %s: kept %d of %d columns (%d dropped by --mask / --keep, %d by --max-n-share)",
+                     msa, n_kept, self.L, by_files, self.L - by_files - n_kept)
+        if getattr(args, "sites_out", None) is not None:
+            S.write_kept_bed(args.sites_out, kept_words if kept_words is not None else self.keep, self.L, self.contigs)
+
+
+def read_site_files(args):
+    """--mask / --keep / --mask-reference, read once: (keep intervals or None, mask intervals or None, contigs or None); ValueError ->
+    SystemExit with the message"""
+    from . import sites as S
+    contigs = None
+    try:
+        if getattr(args, "mask_reference", None) is not None:
+            from .align_post import read_contigs
+            contigs = read_contigs(args.mask_reference)
+        keep = S.read_bed(args.keep_bed, contigs) if getattr(args, "keep_bed", None) is not None else None
+        mask = S.read_bed(args.mask_bed, contigs) if getattr(args, "mask_bed", None) is not None else None
+    except ValueError as e:
+        raise SystemExit("tracs distance: %s" % e)
+    return keep, mask, contigs
+
+
+def site_rule_for(msas, args, files):
+    """The rule of one alignment (None without any site option).  The bitmap needs the alignment's length and the share the number of
+    loaded samples before the library opens the files: the length comes from the first record; the sample count, only with
+    --max-n-share, from a host-side read of the files (the library's own FASTA reader)."""
+    from . import sites as S
+    keep_iv, mask_iv, contigs = files
+    share = getattr(args, "max_n_share", None)
+    if keep_iv is None and mask_iv is None and share is None:
+        return None
+    for p in msas:
+        if not os.path.exists(p):
+            raise FileNotFoundError(p)
+    L = S.first_record_length(msas[0])
+    keep = None
+    if keep_iv is not None or mask_iv is not None:
+        try:
+            keep = S.keep_bool(L, keep_iv, mask_iv)
+        except ValueError as e:
+            raise SystemExit("tracs distance: %s: %s" % (msas[0], e))
+    max_n = None
+    if share is not None:
+        lib = _lib.load()
+        n = 0
+        for p in msas:
+            cnt, length = C.c_size_t(0), C.c_size_t(0)
+            _lib.check(lib.tracs_debug_read_fasta(os.fsencode(p), C.byref(cnt), C.byref(length), None))
+            n += cnt.value
+        max_n = S.max_n_samples(share, n)
+    return _SiteRule(L, keep, max_n, contigs)
+
+
+def _open(L, msas, rule, args):
+    """tracs_distance_open, or -- with a site rule -- tracs_distance_open_sites, its INFO line and --sites-out -> the handle"""
+    arr = (C.c_char_p * len(msas))(*[os.fsencode(p) for p in msas])
+    h = C.c_void_p()
+    if rule is None:
+        _lib.check(L.tracs_distance_open(arr, len(msas), C.byref(h)))
+        return h
+    import numpy as np
+    words, keep_len, max_n = rule.sites.c_args()
+    u64p = C.POINTER(C.c_uint64)
+    _lib.check(L.tracs_distance_open_sites(arr, len(msas), words.ctypes.data_as(u64p) if words is not None else None, keep_len, max_n,
+                                           C.byref(h)))
+    try:
+        src_len = L.tracs_distance_source_len(h)
+        kept = np.zeros((src_len + 63) // 64, np.uint64)
+        _lib.check(L.tracs_distance_kept_sites(h, kept.ctypes.data_as(u64p)))
+        rule.L = src_len
+        rule.report(args, msas[0], kept_words=kept, n_kept=L.tracs_distance_len(h))
+    except BaseException:
+        L.tracs_distance_free(h)
+        raise
+    return h
+
+
 def check_histogram_args(args):
     """--histogram's and --groups' argument checks, before anything touches the GPU (SystemExit with the message)."""
     if not getattr(args, "histogram", False):
@@ -257,14 +384,12 @@ def read_groups(path):
     return groups
 
 
-def _histogram_on_device(msas, args, groups, ref, stage):
+def _histogram_on_device(msas, args, groups, ref, stage, rule=None):
     """--histogram for one alignment (tracs_distance_open / _histogram: include/tracs_hip.h): the panel loop of _rows_on_device with
     a histogram update per panel instead of the rows; only the non-empty bins are formatted and appended."""
     from .api import group_labels
     L = _lib.require_gpu()
-    arr = (C.c_char_p * len(msas))(*[os.fsencode(p) for p in msas])
-    h = C.c_void_p()
-    _lib.check(L.tracs_distance_open(arr, len(msas), C.byref(h)))
+    h = _open(L, msas, rule, args)
     try:
         stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
         labels = None
@@ -340,6 +465,8 @@ def _pairs_multi_gpu(msas, args, ctx):
 def distance(args):
     check_mst_args(args)
     check_histogram_args(args)
+    check_site_args(args)
+    site_files = read_site_files(args)
     histogram = getattr(args, "histogram", False)
     groups = read_groups(args.groups) if histogram and args.groups is not None else None
     mst = getattr(args, "mst", None)
@@ -390,12 +517,14 @@ def distance(args):
         msas = [msa, args.msa_db] if args.msa_db is not None else [msa]
         t_stage[0] = time.perf_counter()
         ref = os.path.basename(msa).split(".")[0].replace("_combined", "")      # (:208-209)
+        rule = site_rule_for(msas, args, site_files)
+        ruled = dict(rule=rule) if rule is not None else {}                 # (no rule: every route is called as it always was)
         if histogram:
             # how many of the pairs the full run would write have each SNP distance (one GPU, counted on the device)
             for p in msas:
                 if not os.path.exists(p):
                     raise FileNotFoundError(p)
-            _histogram_on_device(msas, args, groups, ref, stage)
+            _histogram_on_device(msas, args, groups, ref, stage, **ruled)
             logging.info("Saving the distance histogram for %s", msa)
             continue
         if mst is not None:
@@ -403,7 +532,7 @@ def distance(args):
             for p in msas:
                 if not os.path.exists(p):
                     raise FileNotFoundError(p)
-            _forest_on_device(msas, args, dates, ref, stage)
+            _forest_on_device(msas, args, dates, ref, stage, **ruled)
             logging.info("Saving the minimum spanning forest for %s", msa)
             continue
         if ctx is None and nearest is None and os.environ.get("TRACS_DISTANCE_ARRAYS") is None:
@@ -412,14 +541,22 @@ def distance(args):
             for p in msas:
                 if not os.path.exists(p):
                     raise FileNotFoundError(p)               # (api.pairsnp_arrays's diagnosis; the reference passes a NULL gzFile on)
-            if _rows_on_device(msas, args, dates, ref, stage):
+            if _rows_on_device(msas, args, dates, ref, stage, **ruled):
                 logging.info("Saving distances for %s", msa)
                 continue
         if nearest is not None:
             # each sample's K nearest (tracs_nearest), then the array route below: -K drops rows after the selection
-            res = nearest_arrays(fasta=msas, k=nearest, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter)
+            info = {}
+            ruled = dict(sites=rule.sites, info=info) if rule is not None else {}      # (no rule: the call as it always was)
+            res = nearest_arrays(fasta=msas, k=nearest, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter, **ruled)
+            if rule is not None:
+                rule.report(args, msa, n_kept=info["seqlen"])
         elif ctx is None:
-            res = pairsnp_arrays(fasta=msas, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter)
+            info = {}
+            ruled = dict(sites=rule.sites, info=info) if rule is not None else {}
+            res = pairsnp_arrays(fasta=msas, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter, **ruled)
+            if rule is not None:
+                rule.report(args, msa, n_kept=info["seqlen"])
         else:
             res = _pairs_multi_gpu(msas, args, ctx)
         stage("pairsnp (total, incl. the copy of the result into numpy arrays)")
