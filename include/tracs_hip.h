@@ -165,6 +165,60 @@ int tracs_alignment_site_n_counts(const tracs_alignment *a, uint32_t *counts, vo
 int tracs_alignment_select_sites(const tracs_alignment *src, const uint64_t *keep, size_t keep_len, uint32_t max_n_samples,
                                  tracs_alignment **out, uint64_t *kept, size_t *n_kept, void *stream);
 
+/* Sample rule and pair rule (not in the reference).  A run with the sample rule is, by definition, the run on the FASTA
+ * file(s) with the dropped records deleted: the kept samples are gathered into a new handle that is byte for byte what packing the
+ * record-deleted text gives (pad samples, tail bits, pad groups and slack zero; n_pad may shrink), and every other entry point runs
+ * on that handle unchanged.  The pair rule is one pass over a dense panel before anything reads it.
+ *   tracs_alignment_sample_n_counts  per sample, the sites at which it is N (the stored N plane, as tracs_alignment_site_n_counts)
+ *                                    among the columns `keep` leaves (host bitmap as tracs_alignment_select_sites takes it, keep_len
+ *                                    = the handle's length; NULL: every column) -> counts, device uint32[n].  Exact (integer sums).
+ *                                    With a bitmap the call synchronises the stream.
+ *   tracs_alignment_select_samples   keep_sample: host uint8[n], non-zero = the sample stays.  *out: a NEW handle over the kept
+ *                                    samples in their order (src is left as it was and stays usable).  A mask that keeps nothing is
+ *                                    refused (TRACS_E_ARG, "no sample left after the sample rule").  Synchronises the stream.
+ *   tracs_pairs_min_sites            the cells of one dense call -- rows [row_begin, row_end), columns [max(col_begin, i + 1), n) of
+ *                                    dist / ncomp (device uint32, indexed by ABSOLUTE row, leading dimension ld >= n): a cell whose
+ *                                    distance, read unsigned, is <= dist_threshold and whose ncomp is < min_sites gets the distance
+ *                                    0xFFFFFFFF, which tracs_coo_count / _fill, tracs_knn_update, tracs_hist_update and the
+ *                                    transcluster entry points read as "beyond the threshold".  Every other cell, ncomp and every
+ *                                    byte outside the cell set stay as they were.  min_sites = 0: nothing is launched.             */
+int tracs_alignment_sample_n_counts(const tracs_alignment *a, const uint64_t *keep, size_t keep_len, uint32_t *counts, void *stream);
+int tracs_alignment_select_samples(const tracs_alignment *src, const uint8_t *keep_sample, tracs_alignment **out, void *stream);
+int tracs_pairs_min_sites(uint32_t *dist, const uint32_t *ncomp, size_t ld, size_t n, size_t row_begin, size_t row_end, size_t col_begin,
+                          int32_t dist_threshold, uint32_t min_sites, void *stream);
+
+/* The rules of the FASTA entry points in one place.  Applied in this order:
+ *   1. keep / keep_len       the file rules' bitmap over the columns read (NULL: every column); L' = the columns it leaves
+ *   2. max_sample_n_share G  a record is left out when more than floor(G L') of those columns are N in it; with two files the rule
+ *                            applies to both and the first file's count shrinks; a file left without a record is refused
+ *                            (TRACS_E_ARG, "no sample left after the sample rule").  G = 1 drops nothing.  < 0: no rule
+ *   3. max_n_share F         a column is dropped when more than floor(F n') of the n' SURVIVING samples are N there (computed in the
+ *                            library as floor(F * (double)n'), once n' is known).  < 0: no rule.  max_n_samples: the same rule
+ *                            with the threshold given (UINT32_MAX: no rule); giving both is refused
+ *   4. min_sites M           a pair is eligible only if its compared-sites count over the kept columns is >= M (tracs_pairs_min_sites
+ *                            on every dense panel).  0: no rule
+ * A struct without any rule (or NULL) is call for call the plain entry point.                                                    */
+typedef struct tracs_rules {
+    const uint64_t *keep;
+    size_t keep_len;
+    double max_n_share;
+    double max_sample_n_share;
+    uint32_t min_sites;
+    uint32_t max_n_samples;
+} tracs_rules;
+int tracs_pairsnp_rules(const char *const *fasta, int n_fasta, int n_threads, int dist, int filter, const tracs_rules *rules,
+                        tracs_pairsnp_result **out);
+int tracs_nearest_rules(const char *const *fasta, int n_fasta, int n_threads, int k, int dist, int filter, const tracs_rules *rules,
+                        tracs_pairsnp_result **out);
+/* What the sample rule saw, on a result: the records read in input order (both files), each one's N sites among the L' file-kept
+ * columns (tracs_pairsnp_rule_sites), and whether it stayed.  tracs_pairsnp_nseq / _name are the SURVIVING samples, the ones rows and
+ * cols index.  Without a sample rule: the loaded samples, all kept, counts 0.                                                     */
+size_t tracs_pairsnp_source_nseq(const tracs_pairsnp_result *r);
+const char *tracs_pairsnp_source_name(const tracs_pairsnp_result *r, size_t i);
+uint32_t tracs_pairsnp_source_n_count(const tracs_pairsnp_result *r, size_t i);
+int tracs_pairsnp_source_kept(const tracs_pairsnp_result *r, size_t i);
+size_t tracs_pairsnp_rule_sites(const tracs_pairsnp_result *r);
+
 /* Dense pair block: for rows i in [row_begin,row_end) and columns j in [max(col_begin,i+1), n)
  *   dist[i*ld + j]  = d(i,j)  = L - popcount(match)           (pairsnp.hpp:398-403)
  *   ncomp[i*ld + j] = nn(i,j) = L - popcount(N_i | N_j)       (pairsnp.hpp:417-420)
@@ -456,6 +510,16 @@ int tracs_distance_open(const char *const *fasta, int n_fasta, tracs_distance **
  *                         _kept_sites: the final bitmap over the columns read, ceil(source_len / 64) host words.                  */
 int tracs_distance_open_sites(const char *const *fasta, int n_fasta, const uint64_t *keep, size_t keep_len, uint32_t max_n_samples,
                               tracs_distance **out);
+/*   tracs_distance_open_rules  tracs_distance_open under a tracs_rules: every later call on the handle sees the surviving samples
+ *                         (tracs_distance_nseq / _name) and the kept columns only, and _run, _forest and _histogram apply the handle's
+ *                         min_sites to every dense panel before anything reads it.  _source_nseq / _source_name / _source_n_count /
+ *                         _source_kept / _rule_sites: as the tracs_pairsnp_source_* accessors.                                      */
+int tracs_distance_open_rules(const char *const *fasta, int n_fasta, const tracs_rules *rules, tracs_distance **out);
+size_t tracs_distance_source_nseq(const tracs_distance *h);
+const char *tracs_distance_source_name(const tracs_distance *h, size_t i);
+uint32_t tracs_distance_source_n_count(const tracs_distance *h, size_t i);
+int tracs_distance_source_kept(const tracs_distance *h, size_t i);
+size_t tracs_distance_rule_sites(const tracs_distance *h);
 size_t tracs_distance_source_len(const tracs_distance *h);
 size_t tracs_distance_len(const tracs_distance *h);
 int tracs_distance_kept_sites(const tracs_distance *h, uint64_t *kept);

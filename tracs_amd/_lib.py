@@ -41,8 +41,18 @@ SYMBOLS = [
     "tracs_distance_forest", "tracs_msf_state_bytes", "tracs_msf_init", "tracs_msf_update_coo", "tracs_msf_emit",
     "tracs_alignment_site_n_counts", "tracs_alignment_select_sites", "tracs_pairsnp_sites", "tracs_nearest_sites",
     "tracs_distance_open_sites", "tracs_distance_source_len", "tracs_distance_len", "tracs_distance_kept_sites",
+    "tracs_alignment_sample_n_counts", "tracs_alignment_select_samples", "tracs_pairs_min_sites", "tracs_pairsnp_rules",
+    "tracs_nearest_rules", "tracs_distance_open_rules", "tracs_pairsnp_source_nseq", "tracs_pairsnp_source_name",
+    "tracs_pairsnp_source_n_count", "tracs_pairsnp_source_kept", "tracs_pairsnp_rule_sites", "tracs_distance_source_nseq",
+    "tracs_distance_source_name", "tracs_distance_source_n_count", "tracs_distance_source_kept", "tracs_distance_rule_sites",
     "tracs_distance_histogram", "tracs_hist_state_bytes", "tracs_hist_init", "tracs_hist_update", "tracs_hist_update_coo", "tracs_hist_emit",
 ]
+
+
+class Rules(C.Structure):
+    """tracs_rules (include/tracs_hip.h): shares < 0, min_sites = 0 and max_n_samples = 2^32 - 1 mean no rule"""
+    _fields_ = [("keep", C.POINTER(C.c_uint64)), ("keep_len", C.c_size_t), ("max_n_share", C.c_double),
+                ("max_sample_n_share", C.c_double), ("min_sites", C.c_uint32), ("max_n_samples", C.c_uint32)]
 
 
 class TracsError(RuntimeError):
@@ -195,6 +205,27 @@ def load():
     L.tracs_distance_len.argtypes = [vp]
     L.tracs_distance_kept_sites.restype = C.c_int
     L.tracs_distance_kept_sites.argtypes = [vp, u64p]
+    L.tracs_alignment_sample_n_counts.restype = C.c_int
+    L.tracs_alignment_sample_n_counts.argtypes = [vp, u64p, sz, vp, vp]
+    L.tracs_alignment_select_samples.restype = C.c_int
+    L.tracs_alignment_select_samples.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(vp), vp]
+    L.tracs_pairs_min_sites.restype = C.c_int
+    L.tracs_pairs_min_sites.argtypes = [vp, vp, sz, sz, sz, sz, sz, i32, C.c_uint32, vp]
+    rp = C.POINTER(Rules)
+    L.tracs_pairsnp_rules.restype = C.c_int
+    L.tracs_pairsnp_rules.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, rp, C.POINTER(vp)]
+    L.tracs_nearest_rules.restype = C.c_int
+    L.tracs_nearest_rules.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, rp, C.POINTER(vp)]
+    L.tracs_distance_open_rules.restype = C.c_int
+    L.tracs_distance_open_rules.argtypes = [C.POINTER(C.c_char_p), C.c_int, rp, C.POINTER(vp)]
+    for kind in ("pairsnp", "distance"):
+        for name, res, args in (("source_nseq", sz, [vp]), ("source_name", C.c_char_p, [vp, sz]), ("source_n_count", C.c_uint32, [vp, sz]),
+                                ("source_kept", C.c_int, [vp, sz]), ("rule_sites", sz, [vp])):
+            f = getattr(L, "tracs_%s_%s" % (kind, name))
+            f.restype = res
+            f.argtypes = args
+    L.tracs_debug_sample_select_timing.restype = C.c_int
+    L.tracs_debug_sample_select_timing.argtypes = [vp, u64p, sz, C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_float), C.POINTER(sz)]
     L.tracs_debug_site_select_timing.restype = C.c_int
     L.tracs_debug_site_select_timing.argtypes = [vp, u64p, sz, C.c_uint32, C.c_int, C.POINTER(C.c_float), C.POINTER(sz), C.POINTER(C.c_int)]
     L.tracs_debug_hist_routes.restype = C.c_int

@@ -26,10 +26,51 @@ def _site_args(sites):
     return words, (words.ctypes.data_as(C.POINTER(C.c_uint64)) if words is not None else None), keep_len, max_n
 
 
-def pairsnp_arrays(fasta, n_threads=1, dist=2147483647, filter=False, sites=None, info=None):
+def _rules(sites, max_sample_n_share, max_n_share, min_sites):
+    """The sample / pair rules and the N share of the FASTA entry points -> (_lib.Rules, array kept alive), or
+    (None, None) when none of the three is given (the call then goes the way it always went)."""
+    if max_sample_n_share is None and max_n_share is None and min_sites is None:
+        return None, None
+    for name, share in (("max_sample_n_share", max_sample_n_share), ("max_n_share", max_n_share)):
+        if share is not None and not (0.0 <= float(share) <= 1.0):
+            raise ValueError("%s must be in [0, 1], got %r" % (name, share))
+    if min_sites is not None and not (1 <= int(min_sites) <= 0xFFFFFFFF):
+        raise ValueError("min_sites must be in [1, 2^32 - 1], got %r" % (min_sites,))
+    if sites is not None and sites.max_n_samples is not None:
+        if max_sample_n_share is not None:
+            raise ValueError("Sites(max_n_samples=...) cannot be combined with max_sample_n_share: the N rule counts over the samples "
+                             "that survive the sample rule, whose number is only known on the device; give max_n_share")
+        if max_n_share is not None:
+            raise ValueError("Sites(max_n_samples=...) and max_n_share are two forms of one rule; give one")
+    words, keep_len, max_n = (None, 0, 0xFFFFFFFF) if sites is None else sites.c_args()
+    r = _lib.Rules(words.ctypes.data_as(C.POINTER(C.c_uint64)) if words is not None else None, keep_len,
+                   -1.0 if max_n_share is None else float(max_n_share), -1.0 if max_sample_n_share is None else float(max_sample_n_share),
+                   0 if min_sites is None else int(min_sites), max_n)
+    return r, words
+
+
+def _source_info(L, h, kind, info):
+    """info <- what the sample rule saw (tracs_<kind>_source_*): the names of the records read, their N counts among the
+    "rule_sites" file-kept columns, and which stayed"""
+    if info is None:
+        return
+    get = lambda name: getattr(L, "tracs_%s_%s" % (kind, name))                     # noqa: E731
+    n = get("source_nseq")(h)
+    info["source_names"] = [get("source_name")(h, i).decode("utf-8", "replace") for i in range(n)]
+    info["n_counts"] = np.array([get("source_n_count")(h, i) for i in range(n)], np.uint32)
+    info["kept"] = np.array([get("source_kept")(h, i) != 0 for i in range(n)], bool)
+    info["rule_sites"] = int(get("rule_sites")(h))
+
+
+def pairsnp_arrays(fasta, n_threads=1, dist=2147483647, filter=False, sites=None, info=None, max_sample_n_share=None, max_n_share=None,
+                   min_sites=None):
     """Like pairsnp() but returns numpy arrays: (rows, cols, distances, names, filt_distances, n_compared).
     sites (tracs_amd.sites.Sites): the run on the files with the dropped columns deleted.  info: a dict that
-    receives "seqlen", the alignment length the result stands for (the kept columns)."""
+    receives "seqlen", the alignment length the result stands for (the kept columns).
+    max_sample_n_share G: the run on the files without the records that are N at more than floor(G L') of the L' columns
+    sites.keep leaves; max_n_share F: columns dropped where more than floor(F n') of the n' surviving samples are N; min_sites M:
+    only pairs compared over at least M kept sites.  names, rows and cols are the surviving samples; info then
+    also receives "source_names", "n_counts", "kept" (per record read) and "rule_sites" (L')."""
     paths = _paths(fasta)
     if len(paths) < 1 or len(paths) > 2:
         raise RuntimeError("Invalid number of fasta files!")      # src/pairsnp.hpp:340-343
@@ -40,7 +81,11 @@ def pairsnp_arrays(fasta, n_threads=1, dist=2147483647, filter=False, sites=None
     L = _lib.require_gpu()
     arr = (C.c_char_p * len(paths))(*paths)
     h = C.c_void_p()
-    if sites is None:
+    rules, alive = _rules(sites, max_sample_n_share, max_n_share, min_sites)
+    if rules is not None:
+        _lib.check(L.tracs_pairsnp_rules(arr, len(paths), int(n_threads), int(dist), int(bool(filter)), C.byref(rules), C.byref(h)))
+        _source_info(L, h, "pairsnp", info)
+    elif sites is None:
         _lib.check(L.tracs_pairsnp(arr, len(paths), int(n_threads), int(dist), int(bool(filter)), C.byref(h)))
     else:
         alive, kp, keep_len, max_n = _site_args(sites)
@@ -50,12 +95,14 @@ def pairsnp_arrays(fasta, n_threads=1, dist=2147483647, filter=False, sites=None
     return _result_arrays(L, h)
 
 
-def nearest_arrays(fasta, k, n_threads=1, dist=2147483647, filter=False, sites=None, info=None):
+def nearest_arrays(fasta, k, n_threads=1, dist=2147483647, filter=False, sites=None, info=None, max_sample_n_share=None, max_n_share=None,
+                   min_sites=None):
     """The k nearest neighbours of each sample (tracs_nearest, include/tracs_hip.h): the six arrays of pairsnp_arrays, rows = the
     sample (ascending), cols = its neighbours ranked by (SNP distance, sample index), at most k per sample.  One file: candidates
     are all other samples; two files: the samples of file 0 get lists, their candidates are the samples of file 1.  Only pairs
     with d <= dist are eligible.  filter: the filtered distances of the emitted pairs (the ranking uses the raw distance).
-    n_threads is accepted for parity with pairsnp_arrays and unused: every stage runs on the GPU.  sites: as pairsnp_arrays."""
+    n_threads is accepted for parity with pairsnp_arrays and unused: every stage runs on the GPU.  sites, max_sample_n_share,
+    max_n_share, min_sites, info: as pairsnp_arrays (the k nearest among the eligible pairs of the surviving samples)."""
     paths = _paths(fasta)
     if len(paths) < 1 or len(paths) > 2:
         raise RuntimeError("Invalid number of fasta files!")
@@ -68,7 +115,11 @@ def nearest_arrays(fasta, k, n_threads=1, dist=2147483647, filter=False, sites=N
     L = _lib.require_gpu()
     arr = (C.c_char_p * len(paths))(*paths)
     h = C.c_void_p()
-    if sites is None:
+    rules, alive = _rules(sites, max_sample_n_share, max_n_share, min_sites)
+    if rules is not None:
+        _lib.check(L.tracs_nearest_rules(arr, len(paths), int(n_threads), k, int(dist), int(bool(filter)), C.byref(rules), C.byref(h)))
+        _source_info(L, h, "pairsnp", info)
+    elif sites is None:
         _lib.check(L.tracs_nearest(arr, len(paths), int(n_threads), k, int(dist), int(bool(filter)), C.byref(h)))
     else:
         alive, kp, keep_len, max_n = _site_args(sites)
@@ -111,12 +162,14 @@ def read_histogram_rows(path):
     return out
 
 
-def distance_histogram(fasta, dist=2147483647, filter=False, groups=None, sites=None):
+def distance_histogram(fasta, dist=2147483647, filter=False, groups=None, sites=None, max_sample_n_share=None, max_n_share=None,
+                       min_sites=None, info=None):
     """How many pairs have each SNP distance (tracs_distance_histogram, include/tracs_hip.h): the pairs pairsnp_arrays(fasta, dist=dist)
     returns, counted on the GPU without being emitted.  -> (names, {"snp": h[, "filter": h]}) with h = {"value": uint32[], "within":
     uint64[], "between": uint64[], "ungrouped": uint64[]}, the non-empty bins ascending.  groups: mapping sample name -> label (any
     hashable; missing or None: ungrouped); without it every pair is `ungrouped`.  filter: also the histogram of the filtered
-    distances of the same pairs.  sites: as pairsnp_arrays."""
+    distances of the same pairs.  sites, max_sample_n_share, max_n_share, min_sites, info: as pairsnp_arrays (names are the
+    surviving samples, only eligible pairs are counted)."""
     import tempfile
     paths = _paths(fasta)
     if len(paths) < 1 or len(paths) > 2:
@@ -127,12 +180,19 @@ def distance_histogram(fasta, dist=2147483647, filter=False, groups=None, sites=
     L = _lib.require_gpu()
     arr = (C.c_char_p * len(paths))(*paths)
     h = C.c_void_p()
-    if sites is None:
+    rules, alive = _rules(sites, max_sample_n_share, max_n_share, min_sites)
+    if rules is not None:
+        _lib.check(L.tracs_distance_open_rules(arr, len(paths), C.byref(rules), C.byref(h)))
+    elif sites is None:
         _lib.check(L.tracs_distance_open(arr, len(paths), C.byref(h)))
     else:
         alive, kp, keep_len, max_n = _site_args(sites)
         _lib.check(L.tracs_distance_open_sites(arr, len(paths), kp, keep_len, max_n, C.byref(h)))
     try:
+        if rules is not None:
+            _source_info(L, h, "distance", info)
+        if info is not None:
+            info["seqlen"] = int(L.tracs_distance_len(h))
         names = [L.tracs_distance_name(h, i).decode("utf-8", "replace") for i in range(L.tracs_distance_nseq(h))]
         labels = group_labels(names, groups)
         gp = labels.ctypes.data_as(C.POINTER(C.c_int32)) if labels is not None and len(labels) else None

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <csignal>
 #include <cstdio>
 #include <cstdlib>
@@ -129,10 +130,20 @@ struct SigintScope {
     ~SigintScope() { if (installed) (void)sigaction(SIGINT, &old, nullptr); }
 };
 
+// What a sample rule saw: every record read, its N sites among the columns the file rules leave, whether it stayed.
+// Without a sample rule `names` is empty and the accessors answer from the loaded samples: all kept, counts 0.
+struct SourceSamples {
+    std::vector<std::string> names;
+    std::vector<uint32_t> n_count;
+    std::vector<uint8_t> kept;
+    size_t rule_sites = 0;               // L': the columns the file rules leave (every column without file rules)
+};
+
 struct tracs_pairsnp_result {
     size_t nseq = 0, L = 0;
     std::vector<uint64_t> rows, cols, dist, filt, ncomp;
     std::vector<std::string> names;
+    SourceSamples source;
 };
 
 extern "C" {
@@ -198,8 +209,16 @@ struct SiteRule {
     uint32_t max_n = UINT32_MAX;         // a column stays only if at most that many samples are N there
     std::vector<uint64_t> kept;          // out: the final bitmap over the columns read
     size_t source_len = 0;               // out: columns read
+    // the _rules entry points; shares < 0 and min_sites = 0: no rule
+    double max_n_share = -1.0;           // max_n = floor(share x the samples that SURVIVE the sample rule), taken once they are known
+    double max_sample_share = -1.0;      // a record goes when more than floor(share x L') of the file-kept columns are N in it
+    uint32_t min_sites = 0;              // a pair is eligible only if it was compared over at least that many kept sites
+    SourceSamples source;                // out: rule_sites always, the rest with the sample rule
     bool active() const { return keep != nullptr || max_n != UINT32_MAX; }
+    bool sample_rule() const { return max_sample_share >= 0.0; }
 };
+
+static int apply_sample_rule(tracs_alignment **pa, FastaData &fd, size_t *n0, int n_fasta, SiteRule *rule);
 
 static int alignment_from_fasta_sites(const char *const *fasta, int n_fasta, tracs_alignment **out, char **names_out,
                                       size_t *names_bytes, size_t *n_first_file, SiteRule *rule);
@@ -257,6 +276,22 @@ static int alignment_from_fasta_sites(const char *const *fasta, int n_fasta, tra
     clock.mark("H2D + pack", (double)fd.n * (double)fd.L);
     if (rule) {
         rule->source_len = a->L;
+        rule->source.rule_sites = a->L;
+        if (rule->keep && rule->keep_len == a->L) {
+            size_t lp = 0;
+            for (size_t w = 0; w < (a->L + 63) / 64; w++) {
+                const uint64_t m = (w == a->L / 64) ? ((1ull << (a->L & 63)) - 1) : ~0ull;
+                lp += (size_t)__builtin_popcountll(rule->keep[w] & m);
+            }
+            rule->source.rule_sites = lp;
+        }
+        if (rule->sample_rule()) {
+            // file rules first (the counts are taken under their bitmap), then the records, then -- below -- the N share over the survivors
+            rc = apply_sample_rule(&a, fd, &n0, n_fasta, rule);
+            if (rc) { tracs_alignment_free(a); return rc; }
+            clock.mark("sample rule (N counts, gather)");
+        }
+        if (rule->max_n_share >= 0.0) rule->max_n = (uint32_t)std::floor(rule->max_n_share * (double)a->n);
         if (rule->active()) {
             // (the N rule counts over every loaded sample: both files of a two-file run)
             tracs_alignment *sel = nullptr;
@@ -279,6 +314,57 @@ static int alignment_from_fasta_sites(const char *const *fasta, int n_fasta, tra
     }
     if (n_first_file) *n_first_file = n0;
     *out = a;
+    return TRACS_OK;
+}
+
+// The sample rule on a freshly packed handle: counts under the file rules' bitmap, the kept flags, and -- unless every record stays --
+// the survivors gathered into a new handle that replaces *pa (the packed one is freed); fd.names and *n0 shrink with it.
+static int apply_sample_rule(tracs_alignment **pa, FastaData &fd, size_t *n0, int n_fasta, SiteRule *rule)
+{
+    tracs_alignment *a = *pa;
+    const size_t n = a->n;
+    SourceSamples &src = rule->source;
+    src.names = fd.names;
+    src.n_count.assign(n, 0);
+    src.kept.assign(n, 1);
+    if (rule->keep && rule->keep_len != a->L) {
+        set_error("site rules: the keep bitmap covers " + std::to_string(rule->keep_len) + " sites, the alignment has " + std::to_string(a->L));
+        return TRACS_E_ARG;
+    }
+    if (!n) { set_error("no sample left after the sample rule"); return TRACS_E_ARG; }
+    if (a->L) {
+        unsigned *d_counts = nullptr;
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_counts), n * 4);
+        if (e != hipSuccess) { (void)hipGetLastError(); set_error(std::string("hipMalloc(sample counts): ") + hipGetErrorString(e)); return TRACS_E_NOMEM; }
+        int rc = sample_n_counts(a, rule->keep, rule->keep_len, d_counts, nullptr);
+        if (!rc && (e = hipMemcpy(src.n_count.data(), d_counts, n * 4, hipMemcpyDeviceToHost)) != hipSuccess) {
+            set_error(std::string("hipMemcpy(sample counts): ") + hipGetErrorString(e));
+            rc = TRACS_E_HIP;
+        }
+        (void)hipFree(d_counts);
+        if (rc) return rc;
+    }
+    const double limit = std::floor(rule->max_sample_share * (double)src.rule_sites);
+    size_t kept0 = 0, kept1 = 0;
+    for (size_t s = 0; s < n; s++) {
+        src.kept[s] = (double)src.n_count[s] <= limit;
+        if (src.kept[s]) (s < *n0 ? kept0 : kept1)++;
+    }
+    if (kept0 + kept1 == 0 || (n_fasta == 2 && (kept0 == 0 || kept1 == 0))) { set_error("no sample left after the sample rule"); return TRACS_E_ARG; }
+    if (kept0 + kept1 == n) return TRACS_OK;
+    tracs_alignment *sel = nullptr;
+    const int rc = select_samples(a, src.kept.data(), &sel, nullptr, true);
+    if (rc) return rc;
+    tracs_alignment_free(a);
+    *pa = sel;
+    std::vector<std::string> names;
+    names.reserve(kept0 + kept1);
+    for (size_t s = 0; s < n; s++)
+        if (src.kept[s]) names.push_back(std::move(fd.names[s]));
+    fd.names = std::move(names);
+    fd.n = kept0 + kept1;
+    if (n_fasta == 2) *n0 = kept0;
+    else *n0 = fd.n;
     return TRACS_OK;
 }
 
@@ -309,6 +395,50 @@ int tracs_nearest_sites(const char *const *fasta, int n_fasta, int n_threads, in
     return nearest_run(fasta, n_fasta, k, dist, filter, rule.active() ? &rule : nullptr, out);
 }
 
+// a tracs_rules of the _rules entry points -> the rule the runs take; a share outside [0, 1] (a NaN too) and both forms of the N rule
+// at once are refused.  No field set at all: no rule, call for call the plain entry points.
+static int rules_from_struct(const tracs_rules *in, SiteRule &rule, bool *any)
+{
+    *any = false;
+    if (!in) return TRACS_OK;
+    for (double share : {in->max_n_share, in->max_sample_n_share})
+        if (!(share < 0.0) && !(share <= 1.0)) { set_error("tracs_rules: a share must be in [0, 1], or negative for no rule"); return TRACS_E_ARG; }
+    if (!(in->max_n_share < 0.0) && in->max_n_samples != UINT32_MAX) {
+        set_error("tracs_rules: max_n_share and max_n_samples are two forms of one rule; give one");
+        return TRACS_E_ARG;
+    }
+    rule.keep = in->keep; rule.keep_len = in->keep_len; rule.max_n = in->max_n_samples;
+    if (!(in->max_n_share < 0.0)) rule.max_n_share = in->max_n_share;
+    if (!(in->max_sample_n_share < 0.0)) rule.max_sample_share = in->max_sample_n_share;
+    rule.min_sites = in->min_sites;
+    *any = rule.active() || rule.max_n_share >= 0.0 || rule.sample_rule() || rule.min_sites != 0;
+    return TRACS_OK;
+}
+
+int tracs_pairsnp_rules(const char *const *fasta, int n_fasta, int n_threads, int dist, int filter, const tracs_rules *rules,
+                        tracs_pairsnp_result **out)
+{
+    (void)n_threads;
+    SiteRule rule;
+    bool any = false;
+    if (out) *out = nullptr;
+    const int rc = rules_from_struct(rules, rule, &any);
+    if (rc) return rc;
+    return pairsnp_run(fasta, n_fasta, dist, filter, any ? &rule : nullptr, out);
+}
+
+int tracs_nearest_rules(const char *const *fasta, int n_fasta, int n_threads, int k, int dist, int filter, const tracs_rules *rules,
+                        tracs_pairsnp_result **out)
+{
+    (void)n_threads;
+    SiteRule rule;
+    bool any = false;
+    if (out) *out = nullptr;
+    const int rc = rules_from_struct(rules, rule, &any);
+    if (rc) return rc;
+    return nearest_run(fasta, n_fasta, k, dist, filter, any ? &rule : nullptr, out);
+}
+
 static int pairsnp_run(const char *const *fasta, int n_fasta, int dist, int filter, SiteRule *rule, tracs_pairsnp_result **out)
 {
     if (!out) { set_error("tracs_pairsnp: out is NULL"); return TRACS_E_ARG; }
@@ -322,6 +452,9 @@ static int pairsnp_run(const char *const *fasta, int n_fasta, int dist, int filt
     if (rc) return rc;
     auto *res = new tracs_pairsnp_result();
     res->nseq = a->n; res->L = a->L;
+    if (rule) res->source = std::move(rule->source);
+    else res->source.rule_sites = a->L;
+    const uint32_t min_sites = rule ? rule->min_sites : 0;
     { size_t o = 0; for (size_t i = 0; i < a->n; i++) { res->names.emplace_back(names + o); o += res->names.back().size() + 1; } }
     tracs_free(names);
     // pair ranges (:348-360)
@@ -364,6 +497,7 @@ static int pairsnp_run(const char *const *fasta, int n_fasta, int dist, int filt
             unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;
             lap(t_pull);
             PS_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));   // early out beyond `dist`
+            if (min_sites) PS_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, min_sites, nullptr));
             lap(t_dense);
             PS_RC(tracs_coo_count(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), nullptr));
             long long total = 0;
@@ -456,6 +590,9 @@ static int nearest_run(const char *const *fasta, int n_fasta, int k, int dist, i
     if (rc) return rc;
     auto *res = new tracs_pairsnp_result();
     res->nseq = a->n; res->L = a->L;
+    if (rule) res->source = std::move(rule->source);
+    else res->source.rule_sites = a->L;
+    const uint32_t min_sites = rule ? rule->min_sites : 0;
     { size_t o = 0; for (size_t i = 0; i < a->n; i++) { res->names.emplace_back(names + o); o += res->names.back().size() + 1; } }
     tracs_free(names);
     const size_t n = a->n;
@@ -487,6 +624,7 @@ static int nearest_run(const char *const *fasta, int n_fasta, int k, int dist, i
             const size_t r1 = std::min(i_end, r0 + panel);
             unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
             NN_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
+            if (min_sites) NN_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, min_sites, nullptr));
             NN_RC(tracs_knn_update(bd, bn, n, n, r0, r1, j_start, dist, k, n_fasta == 1 ? 1 : 0, d_state, nullptr));
         }
         clock.mark("dense panels + selection");
@@ -545,6 +683,8 @@ struct tracs_distance {
     int n_fasta = 0;
     size_t source_len = 0;               // columns read (site rules: h->a holds the kept ones)
     std::vector<uint64_t> kept;          // the kept columns; empty: every column
+    uint32_t min_sites = 0;              // the pair rule of _run, _forest and _histogram (0: none)
+    SourceSamples source;                // the records read (sample rule: h->a and names hold the survivors)
 };
 
 static int distance_open(const char *const *fasta, int n_fasta, SiteRule *rule, tracs_distance **out)
@@ -558,7 +698,8 @@ static int distance_open(const char *const *fasta, int n_fasta, SiteRule *rule, 
     const int rc = alignment_from_fasta_sites(fasta, n_fasta, &h->a, &names, &names_bytes, &h->n0, rule);
     if (rc) { delete h; return rc; }
     h->source_len = rule ? rule->source_len : h->a->L;
-    if (rule) h->kept = std::move(rule->kept);
+    if (rule) { h->kept = std::move(rule->kept); h->min_sites = rule->min_sites; h->source = std::move(rule->source); }
+    else h->source.rule_sites = h->a->L;
     h->n_fasta = n_fasta;
     { size_t o = 0; for (size_t i = 0; i < h->a->n; i++) { h->names.emplace_back(names + o); o += h->names.back().size() + 1; } }
     tracs_free(names);
@@ -576,6 +717,40 @@ int tracs_distance_open_sites(const char *const *fasta, int n_fasta, const uint6
     rule.keep = keep; rule.keep_len = keep_len; rule.max_n = max_n_samples;
     return distance_open(fasta, n_fasta, rule.active() ? &rule : nullptr, out);
 }
+
+int tracs_distance_open_rules(const char *const *fasta, int n_fasta, const tracs_rules *rules, tracs_distance **out)
+{
+    SiteRule rule;
+    bool any = false;
+    if (out) *out = nullptr;
+    const int rc = rules_from_struct(rules, rule, &any);
+    if (rc) return rc;
+    return distance_open(fasta, n_fasta, any ? &rule : nullptr, out);
+}
+
+// the records read, before the sample rule (without one: the loaded samples, all kept, counts 0)
+static size_t source_nseq(const SourceSamples &s, const std::vector<std::string> &names) { return s.names.empty() ? names.size() : s.names.size(); }
+static const char *source_name(const SourceSamples &s, const std::vector<std::string> &names, size_t i)
+{
+    const std::vector<std::string> &v = s.names.empty() ? names : s.names;
+    return i < v.size() ? v[i].c_str() : nullptr;
+}
+static uint32_t source_n_count(const SourceSamples &s, size_t i) { return i < s.n_count.size() ? s.n_count[i] : 0; }
+static int source_kept(const SourceSamples &s, const std::vector<std::string> &names, size_t i)
+{
+    return s.names.empty() ? (i < names.size() ? 1 : 0) : (i < s.kept.size() ? (int)s.kept[i] : 0);
+}
+
+size_t tracs_distance_source_nseq(const tracs_distance *h) { return h ? source_nseq(h->source, h->names) : 0; }
+const char *tracs_distance_source_name(const tracs_distance *h, size_t i) { return h ? source_name(h->source, h->names, i) : nullptr; }
+uint32_t tracs_distance_source_n_count(const tracs_distance *h, size_t i) { return h ? source_n_count(h->source, i) : 0; }
+int tracs_distance_source_kept(const tracs_distance *h, size_t i) { return h ? source_kept(h->source, h->names, i) : 0; }
+size_t tracs_distance_rule_sites(const tracs_distance *h) { return h ? h->source.rule_sites : 0; }
+size_t tracs_pairsnp_source_nseq(const tracs_pairsnp_result *r) { return r ? source_nseq(r->source, r->names) : 0; }
+const char *tracs_pairsnp_source_name(const tracs_pairsnp_result *r, size_t i) { return r ? source_name(r->source, r->names, i) : nullptr; }
+uint32_t tracs_pairsnp_source_n_count(const tracs_pairsnp_result *r, size_t i) { return r ? source_n_count(r->source, i) : 0; }
+int tracs_pairsnp_source_kept(const tracs_pairsnp_result *r, size_t i) { return r ? source_kept(r->source, r->names, i) : 0; }
+size_t tracs_pairsnp_rule_sites(const tracs_pairsnp_result *r) { return r ? r->source.rule_sites : 0; }
 
 size_t tracs_distance_source_len(const tracs_distance *h) { return h ? h->source_len : 0; }
 size_t tracs_distance_len(const tracs_distance *h) { return (h && h->a) ? h->a->L : 0; }
@@ -681,6 +856,7 @@ int tracs_distance_run(tracs_distance *h, int dist, const int32_t *days, double 
             unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
             double *bp = dense_tc ? d_p - r0 * n : nullptr, *be = dense_tc ? d_e - r0 * n : nullptr;
             DR_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
+            if (h->min_sites) DR_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, h->min_sites, nullptr));
             lap(t_dense);
             if (dense_tc)
                 DR_RC(tracs_trans_dist_dense(bd, n, n, r0, r1, j_start, dist, d_days, lamb, beta, precision, 1, bp, be, nullptr));
@@ -827,6 +1003,7 @@ int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, doub
             unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
             double *bp = dense_tc ? d_p - r0 * n : nullptr, *be = dense_tc ? d_e - r0 * n : nullptr;
             MF_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
+            if (h->min_sites) MF_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, h->min_sites, nullptr));
             if (dense_tc)
                 MF_RC(tracs_trans_dist_dense(bd, n, n, r0, r1, j_start, dist, d_days, lamb, beta, precision, 1, bp, be, nullptr));
             MF_RC(tracs_coo_count(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), nullptr));
@@ -949,6 +1126,7 @@ int tracs_distance_histogram(tracs_distance *h, int dist, int filter, const int3
             const size_t r1 = std::min(i_end, r0 + panel);
             unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
             HG_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
+            if (h->min_sites) HG_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, h->min_sites, nullptr));
             HG_RC(tracs_hist_update(bd, n, n, r0, r1, j_start, dist, d_group, d_state[0], n_bins, nullptr));
             if (!filter) continue;
             // the filtered distances of the panel's eligible pairs (src/pairsnp.hpp:405-413), as tracs_distance_run takes them

@@ -120,6 +120,13 @@ void filter_index_free(tracs_alignment *a);        // filter_lists.hip
 int select_sites(tracs_alignment *src, const uint64_t *keep, size_t keep_len, uint32_t max_n_samples, tracs_alignment **out,
                  uint64_t *kept, size_t *n_kept, hipStream_t stream, bool release_src_arena);
 
+// sample_select.hip: the sample rule's counts and gather (tracs_alignment_sample_n_counts / _select_samples; release_src_arena as
+// above) and the pair rule's veto pass over the cells of one dense call (tracs_pairs_min_sites; min_sites = 0: nothing is launched)
+int sample_n_counts(const tracs_alignment *a, const uint64_t *keep, size_t keep_len, uint32_t *counts, hipStream_t stream);
+int select_samples(tracs_alignment *src, const uint8_t *keep_sample, tracs_alignment **out, hipStream_t stream, bool release_src_arena);
+int pairs_min_sites(uint32_t *dist, const uint32_t *ncomp, size_t ld, size_t n, size_t row_begin, size_t row_end, size_t col_begin,
+                    int32_t dist_threshold, uint32_t min_sites, hipStream_t stream);
+
 // device memory that lives until the alignment is packed again (site_classes_free releases all of it at once)
 hipError_t pack_alloc(tracs_alignment *a, size_t bytes, void **out);
 void pack_release(tracs_alignment *a);

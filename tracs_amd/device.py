@@ -179,6 +179,33 @@ class Alignment:
                 setattr(new, attr, getattr(self, attr))
         return new, bitmap_to_bool(kept, self.L)
 
+    def sample_n_counts(self, keep=None):
+        """torch.int32 [n] on the device: per sample, the sites at which it is N (the stored N plane, as site_n_counts) among the
+        columns keep (bool per column; None: all) leaves.  tracs_alignment_sample_n_counts."""
+        from .sites import Sites
+        words, keep_len, _ = Sites(keep).c_args()
+        out = torch.empty(self.n, dtype=torch.int32, device="cuda")
+        _lib.check(self._L.tracs_alignment_sample_n_counts(self._h, words.ctypes.data_as(C.POINTER(C.c_uint64)) if words is not None else None,
+                                                           keep_len, _ptr(out), _stream()))
+        return out
+
+    def select_samples(self, mask):
+        """-> Alignment over the samples mask (one bool per sample) keeps, in their order: byte for byte what packing the kept
+        sequences gives; this one is left as it was.  tracs_alignment_select_samples."""
+        m = np.ascontiguousarray(np.asarray(mask, dtype=bool).astype(np.uint8))
+        if m.ndim != 1 or m.shape[0] != self.n:
+            raise ValueError("select_samples: the mask covers %s samples, the alignment has %d" % (m.shape[0] if m.ndim == 1 else m.shape, self.n))
+        h = C.c_void_p()
+        _lib.check(self._L.tracs_alignment_select_samples(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(h), _stream()))
+        new = Alignment.__new__(Alignment)
+        new._L, new._h = self._L, h
+        new.n, new.L = int(m.sum()), self.L
+        if hasattr(self, "names"):
+            new.names = [x for x, k in zip(self.names, m) if k]
+        if hasattr(self, "n_first"):
+            new.n_first = int(m[:self.n_first].sum())
+        return new
+
     @property
     def nbytes(self):
         return self._L.tracs_alignment_bytes(self._h)
@@ -247,6 +274,18 @@ def pairsnp_dense(aln, dist, ncomp=None, row_begin=0, row_end=None, col_begin=0,
     else:
         _lib.check(aln._L.tracs_pairsnp_dense_thr(aln._h, int(row_begin), int(row_end), int(col_begin), _panel_ptr(dist, base_row),
                                                   _panel_ptr(ncomp, base_row), int(ld), int(dist_threshold), _stream()))
+
+
+def pairs_min_sites(dist, ncomp, n, min_sites, row_begin=0, row_end=None, col_begin=0, dist_threshold=2147483647, base_row=0):
+    """The pair rule on a dense panel (dist / ncomp as pairsnp_dense wrote them), in place: every cell of rows [row_begin, row_end) x
+    cols [max(col_begin, i + 1), n) that is within dist_threshold (read unsigned) and was compared over fewer than min_sites sites
+    gets the distance 0xFFFFFFFF (-1), which every consumer reads as beyond the threshold.  tracs_pairs_min_sites."""
+    L = _lib.require_gpu()
+    row_end = n if row_end is None else row_end
+    ld = dist.stride(0)
+    assert ncomp.stride(0) == ld and base_row <= row_begin and row_end - base_row <= dist.shape[0]
+    _lib.check(L.tracs_pairs_min_sites(_panel_ptr(dist, base_row), _panel_ptr(ncomp, base_row), int(ld), int(n), int(row_begin), int(row_end),
+                                       int(col_begin), int(dist_threshold), int(min_sites), _stream()))
 
 
 def coo_from_dense(dist, ncomp, n, dist_threshold=2147483647, row_begin=0, row_end=None, col_begin=0, base_row=0):

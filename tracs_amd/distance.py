@@ -7,6 +7,7 @@ CSV rows :206-258 (header :157).  The pair loop and the transcluster integral ru
 import argparse
 import ctypes as C
 import logging
+import math
 import os
 import sys
 from datetime import date
@@ -92,6 +93,18 @@ def distance_parser(parser):
                          "samples of both files)")
     st.add_argument("--sites-out", dest="sites_out", default=None, type=str, metavar="FILE",
                     help="Write the kept columns as a BED (readable back through --keep; contig coordinates with --mask-reference)")
+    sm = parser.add_argument_group("Sample and pair selection",
+                                   "A run with the sample rule is the run on the FASTA file(s) with the dropped records deleted; the pair "
+                                   "rule removes pairs from what the run would write (both applied on the GPU; not in the reference).")
+    sm.add_argument("--max-sample-n-share", dest="max_sample_n_share", default=None, type=float, metavar="G",
+                    help="Leave out a sample when more than floor(G L') of the L' columns that --mask / --keep leave are N in it "
+                         "(0 <= G <= 1; 1 drops nothing and only reports; with --msa-db: applied to both files).  --max-n-share then "
+                         "counts over the remaining samples.  A left-out sample needs no date in --meta.")
+    sm.add_argument("--min-sites", dest="min_sites", default=None, type=int, metavar="M",
+                    help="Only pairs compared over at least M sites (the `sites considered` column, after the site rules) are eligible: "
+                         "for the full output, --nearest, --mst and --histogram alike")
+    sm.add_argument("--samples-out", dest="samples_out", default=None, type=str, metavar="FILE",
+                    help="With --max-sample-n-share: write sample,MSA file,N sites,sites,kept for every record read, in input order")
     tr = parser.add_argument_group("Transmission distance options")
     tr.add_argument("--clock_rate", dest="clock_rate", type=check_positive_float, default=1e-3 * 29903,
                     help="clock rate as defined in the transcluster paper (SNPs/genome/year) default=1e-3 * 29903")
@@ -251,21 +264,71 @@ def check_site_args(args):
         raise SystemExit("tracs distance: --sites-out with --nearest takes file rules only (--mask, --keep), not --max-n-share")
 
 
-class _SiteRule:
-    """The site rule of one alignment: the keep bitmap over its columns (None: files give none) and the N threshold (None: no rule)"""
+SAMPLES_HEADER = "sample,MSA file,N sites,sites,kept\n"
 
-    def __init__(self, L, keep, max_n, contigs):
+
+def check_sample_args(args):
+    """The sample and pair rules' argument checks, before anything touches the GPU (SystemExit with the message)."""
+    share, m, out = getattr(args, "max_sample_n_share", None), getattr(args, "min_sites", None), getattr(args, "samples_out", None)
+    if share is not None and not (0.0 <= share <= 1.0):            # (a NaN fails too)
+        raise SystemExit("tracs distance: --max-sample-n-share must be in [0, 1], got %r" % share)
+    if m is not None and not (1 <= m <= 0xFFFFFFFF):
+        raise SystemExit("tracs distance: --min-sites must be in [1, 2^32 - 1], got %r" % m)
+    if out is not None and share is None:
+        raise SystemExit("tracs distance: --samples-out needs --max-sample-n-share (it lists what the sample rule decided)")
+    if out is not None and len(getattr(args, "msa_files", None) or []) > 1:
+        raise SystemExit("tracs distance: --samples-out describes one alignment; give one --msa file")
+    if (share is not None or m is not None) and getattr(args, "gpus", 1) > 1:
+        raise SystemExit("tracs distance: the sample and pair rules (--max-sample-n-share, --min-sites) run on one GPU; use --gpus 1")
+
+
+def write_samples_out(path, names, ref, n_counts, sites, kept):
+    """--samples-out: one row per record read, in input order: sample,MSA file,N sites,sites,kept (kept: 1 or 0)"""
+    with open(path, "w") as fh:
+        fh.write(SAMPLES_HEADER)
+        for name, cnt, k in zip(names, n_counts, kept):
+            fh.write("%s,%s,%d,%d,%d\n" % (name, ref, int(cnt), int(sites), 1 if k else 0))
+
+
+class _SiteRule:
+    """The rules of one alignment.  Site rules: the keep bitmap over its columns (None: files give none) and the N threshold (None: no
+    rule).  With the sample rule (sample_share) or the pair rule (min_sites) the N rule travels as its share instead (share), because
+    it counts over the samples that survive, and the route is the library's _rules entry points."""
+
+    def __init__(self, L, keep, max_n, contigs, share=None, sample_share=None, min_sites=None):
         from .sites import Sites
         self.L, self.keep, self.max_n, self.contigs = L, keep, max_n, contigs
+        self.share, self.sample_share, self.min_sites = share, sample_share, min_sites
         self.sites = Sites(keep, max_n)
         self.reported = False
 
-    def report(self, args, msa, kept_words=None, n_kept=None):
-        """the INFO line of the alignment and --sites-out, once"""
+    def uses_rules(self):
+        return self.sample_share is not None or self.min_sites is not None
+
+    def has_site_rule(self):
+        return self.keep is not None or self.max_n is not None or self.share is not None
+
+    def api_kwargs(self, info):
+        """what pairsnp_arrays / nearest_arrays take for this rule"""
+        if not self.uses_rules():
+            return dict(sites=self.sites, info=info)
+        return dict(sites=self.sites, info=info, max_sample_n_share=self.sample_share, max_n_share=self.share, min_sites=self.min_sites)
+
+    def report(self, args, msa, kept_words=None, n_kept=None, source=None):
+        """the INFO lines of the alignment, --sites-out and --samples-out, once.  source: (names, N counts, kept flags, L') of the
+        records read, with the sample rule"""
         from . import sites as S
         if self.reported:
             return
         self.reported = True
+        if self.sample_share is not None and source is not None:
+            names, n_counts, kept, rule_sites = source
+            logging.info("Sample rule for %s: kept %d of %d samples (dropped: N at more than %d of %d columns)", msa, int(sum(bool(k) for k in kept)),
+                         len(names), math.floor(self.sample_share * rule_sites), rule_sites)
+            if getattr(args, "samples_out", None) is not None:
+                write_samples_out(args.samples_out, names, os.path.basename(msa).split(".")[0].replace("_combined", ""), n_counts, rule_sites, kept)
+        if not self.has_site_rule():
+            return
         by_files = self.L - int(self.keep.sum()) if self.keep is not None else 0
         if n_kept is None:
             n_kept = int(S.bitmap_to_bool(kept_words, self.L).sum())
@@ -298,12 +361,13 @@ def site_rule_for(msas, args, files):
     from . import sites as S
     keep_iv, mask_iv, contigs = files
     share = getattr(args, "max_n_share", None)
-    if keep_iv is None and mask_iv is None and share is None:
+    sample_share, min_sites = getattr(args, "max_sample_n_share", None), getattr(args, "min_sites", None)
+    if keep_iv is None and mask_iv is None and share is None and sample_share is None and min_sites is None:
         return None
     for p in msas:
         if not os.path.exists(p):
             raise FileNotFoundError(p)
-    L = S.first_record_length(msas[0])
+    L = S.first_record_length(msas[0]) if (keep_iv is not None or mask_iv is not None or share is not None) else 0      # (0: no site rule)
     keep = None
     if keep_iv is not None or mask_iv is not None:
         try:
@@ -311,6 +375,9 @@ def site_rule_for(msas, args, files):
         except ValueError as e:
             raise SystemExit("tracs distance: %s: %s" % (msas[0], e))
     max_n = None
+    if sample_share is not None or min_sites is not None:
+        # the library takes F itself and computes floor(F n') over the samples that survive the sample rule: no host read for n
+        return _SiteRule(L, keep, None, contigs, share=share, sample_share=sample_share, min_sites=min_sites)
     if share is not None:
         lib = _lib.load()
         n = 0
@@ -332,18 +399,37 @@ def _open(L, msas, rule, args):
     import numpy as np
     words, keep_len, max_n = rule.sites.c_args()
     u64p = C.POINTER(C.c_uint64)
-    _lib.check(L.tracs_distance_open_sites(arr, len(msas), words.ctypes.data_as(u64p) if words is not None else None, keep_len, max_n,
-                                           C.byref(h)))
+    kp = words.ctypes.data_as(u64p) if words is not None else None
+    if rule.uses_rules():
+        rules = _lib.Rules(kp, keep_len, -1.0 if rule.share is None else float(rule.share),
+                           -1.0 if rule.sample_share is None else float(rule.sample_share), int(rule.min_sites or 0), 0xFFFFFFFF)
+        _lib.check(L.tracs_distance_open_rules(arr, len(msas), C.byref(rules), C.byref(h)))
+    else:
+        _lib.check(L.tracs_distance_open_sites(arr, len(msas), kp, keep_len, max_n, C.byref(h)))
     try:
         src_len = L.tracs_distance_source_len(h)
         kept = np.zeros((src_len + 63) // 64, np.uint64)
         _lib.check(L.tracs_distance_kept_sites(h, kept.ctypes.data_as(u64p)))
         rule.L = src_len
-        rule.report(args, msas[0], kept_words=kept, n_kept=L.tracs_distance_len(h))
+        source = None
+        if rule.sample_share is not None:
+            ns = L.tracs_distance_source_nseq(h)
+            source = ([L.tracs_distance_source_name(h, i).decode("utf-8", "replace") for i in range(ns)],
+                      [L.tracs_distance_source_n_count(h, i) for i in range(ns)], [L.tracs_distance_source_kept(h, i) for i in range(ns)],
+                      L.tracs_distance_rule_sites(h))
+        rule.report(args, msas[0], kept_words=kept, n_kept=L.tracs_distance_len(h), source=source)
     except BaseException:
         L.tracs_distance_free(h)
         raise
     return h
+
+
+def _report_arrays(rule, args, msa, info):
+    """rule.report for the array routes: what pairsnp_arrays / nearest_arrays left in `info`"""
+    source = None
+    if "source_names" in info:
+        source = (info["source_names"], info["n_counts"], info["kept"], info["rule_sites"])
+    rule.report(args, msa, n_kept=info["seqlen"], source=source)
 
 
 def check_histogram_args(args):
@@ -466,6 +552,7 @@ def distance(args):
     check_mst_args(args)
     check_histogram_args(args)
     check_site_args(args)
+    check_sample_args(args)
     site_files = read_site_files(args)
     histogram = getattr(args, "histogram", False)
     groups = read_groups(args.groups) if histogram and args.groups is not None else None
@@ -547,16 +634,16 @@ def distance(args):
         if nearest is not None:
             # each sample's K nearest (tracs_nearest), then the array route below: -K drops rows after the selection
             info = {}
-            ruled = dict(sites=rule.sites, info=info) if rule is not None else {}      # (no rule: the call as it always was)
+            ruled = rule.api_kwargs(info) if rule is not None else {}      # (no rule: the call as it always was)
             res = nearest_arrays(fasta=msas, k=nearest, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter, **ruled)
             if rule is not None:
-                rule.report(args, msa, n_kept=info["seqlen"])
+                _report_arrays(rule, args, msa, info)
         elif ctx is None:
             info = {}
-            ruled = dict(sites=rule.sites, info=info) if rule is not None else {}
+            ruled = rule.api_kwargs(info) if rule is not None else {}
             res = pairsnp_arrays(fasta=msas, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter, **ruled)
             if rule is not None:
-                rule.report(args, msa, n_kept=info["seqlen"])
+                _report_arrays(rule, args, msa, info)
         else:
             res = _pairs_multi_gpu(msas, args, ctx)
         stage("pairsnp (total, incl. the copy of the result into numpy arrays)")
