@@ -427,6 +427,8 @@ int tracs_posterior_codes_device(const uint16_t *counts, size_t L, const double 
 int tracs_find_dirichlet_priors_device(const double *counts, size_t L, size_t K, int max_iter, double tol, int method,
                                        double error_filt_threshold, double *alphas_out_host, int *iters_out,
                                        void *stream);
+/* Tests only: the digamma the fit sums (csrc/dirichlet.hip digamma_pos), evaluated on the device for n host doubles > 0.  */
+int tracs_debug_digamma(const double *x, size_t n, double *out);
 
 /* The same with the align stage's coverage rules (tracs/align.py:599-613): sites with total count < min_cov, or with
  * cov_lo <= total <= cov_hi (outlier band; pass cov_lo > cov_hi to disable), become fully ambiguous (mask 15).        */

@@ -307,9 +307,10 @@ def calculate_posteriors(counts, alphas, keep, threshold):
     return out
 
 
-def find_dirichlet_priors(counts, max_iter=1000, tol=1e-5, method="FPI", error_filt_threshold=None):
+def find_dirichlet_priors(counts, max_iter=1000, tol=1e-5, method="FPI", error_filt_threshold=None, return_iters=False):
     """numpy/scipy restatement of tracs/dirichlet_multinomial.py:9-73 (own structure; pinned by
-    tests/golden/python_reference_golden.json, which holds the reference's outputs incl. the R MGLM known answer)."""
+    tests/golden/python_reference_golden.json, which holds the reference's outputs incl. the R MGLM known answer, and to the
+    definition at 50 digits by tests/golden/dirichlet_hp_golden.json).  return_iters: -> (alphas, iterations done)."""
     from scipy.special import psi
     x = np.array(counts, dtype=np.float64)
     K = x.shape[1]
@@ -321,11 +322,13 @@ def find_dirichlet_priors(counts, max_iter=1000, tol=1e-5, method="FPI", error_f
     if poly.sum() <= 5:
         out = np.zeros(K)
         out[-1] = 1.0
-        return out
+        return (out, 0) if return_iters else out
     x = np.sort(x[poly], axis=1)                               # :36
     tot = x.sum(1)
     alpha = x.mean(0) + 0.5                                    # :40
+    iters = 0
     for _ in range(max_iter):
+        iters += 1
         a0 = alpha.sum()
         if method == "LOO":                                    # :43-54
             new = alpha * (x / (x - 1 + alpha)).sum(0) / (tot / (tot - 1 + a0)).sum()
@@ -337,7 +340,8 @@ def find_dirichlet_priors(counts, max_iter=1000, tol=1e-5, method="FPI", error_f
             alpha = new if done else np.maximum(new, 1e-16)
         if done:
             break
-    return np.sort(alpha)[::-1]                                # :70
+    alpha = np.sort(alpha)[::-1]                               # :70
+    return (alpha, iters) if return_iters else alpha
 
 
 def connected_components(n, I, J):

@@ -29,7 +29,7 @@ from oracle import oracle as O  # noqa: E402
 from tracs_amd import synth  # noqa: E402
 
 R = O.ref_module()
-assert R is not None or sys.argv[1:] in (["hp-transcluster"], ["hp-filter"]), "oracle/_ref is not built (make -C oracle)"
+assert R is not None or sys.argv[1:] in (["hp-transcluster"], ["hp-filter"], ["hp-dirichlet"]), "oracle/_ref is not built (make -C oracle)"
 
 
 def jdump(name, obj):
@@ -419,7 +419,120 @@ def hp_filter():
     print("wrote filter_hp_golden.json", len(cases), "cases;", json.dumps(head["measured"]))
 
 
+# ---------------------------------------------------------------------------------------
+# The Dirichlet-multinomial prior fit from its definition at 50 digits, and the true values of digamma on a grid
+# (tests/hp_dirichlet.py).  A case is a table of distinct rows with multiplicities (not a generator seed) plus the call's
+# parameters; several cases share a table.  Tables whose name starts with "raw" hold rows as a caller would pass them (unsorted,
+# unfiltered); the others hold kept rows, sorted ascending -- filtering them again changes nothing, so their cases may still pass a
+# filter threshold.
+def _dir_tables(H):
+    t = {}
+
+    def kept(c, filt=0.01):
+        return H.distinct(np.sort(H.select_rows(np.asarray(c, np.float64), filt), axis=1))
+    t["d8"] = kept(synth.allele_counts(3000, seed=21, depth=8, p_two=0.06))
+    t["d25"] = kept(synth.allele_counts(3000, seed=9, depth=25, p_two=0.06))
+    t["d200"] = kept(synth.allele_counts(1000, seed=23, depth=200, p_two=0.06))
+    for name, seed, scale in (("c60k", 24, 500), ("c3e8", 25, 2500000)):      # per-allele counts near 60 000 and near 3e8
+        rng = np.random.default_rng(seed)
+        c = synth.allele_counts(300, seed=seed, depth=120, p_two=0.1).astype(np.int64)
+        t[name] = kept(c * scale + (c > 0) * rng.integers(0, scale, c.shape))
+    for K in (2, 3, 5, 8):                                                     # K alleles at depth 25, probabilities ~ 0.7 ** k
+        rng = np.random.default_rng(30 + K)
+        p = 0.7 ** np.arange(K)
+        c = np.array([rng.multinomial(n, p / p.sum()) for n in rng.poisson(25, {2: 2000, 3: 600, 5: 300, 8: 300}[K])])
+        t["k%d" % K] = kept(c, None)
+    rng = np.random.default_rng(40)                                            # K = 4, two alleles only
+    dep = rng.poisson(25, 2000)
+    b = rng.binomial(dep, rng.beta(0.6, 1.4, 2000))                            # overdispersed: the fit converges within max_iter
+    t["two"] = kept(np.stack([b, dep - b, 0 * b, 0 * b], 1), None)
+    d25 = t["d25"]
+    t["cut5"] = [r[:-1] + [1] for r in d25[:5]]
+    t["cut6"] = [r[:-1] + [1] for r in d25[:6]]
+    # the filter at equality: 1 / 20 == 0.05 is not < 0.05 (kept); 1 / 40 is (the cell becomes 0: one allele left, dropped);
+    # a row without counts divides 0 / 0 and stays as it is (dropped)
+    base = [r for r in d25[:120]]
+    t["raw_base"] = base              # the variants add one row each (the cases' extra_rows)
+    return t
+
+
+def _dir_cases():
+    c = []
+    for tab in ("d8", "d25", "d200"):
+        for method in ("FPI", "LOO"):
+            for tol in (1e-5, 1e-11):
+                c.append(dict(name="%s_%s_%g" % (tab, method, tol), table=tab, method=method, tol=tol, max_iter=1000,
+                              error_filt_threshold=0.01 if method == "FPI" else None))
+    for tab in ("c60k", "c3e8"):
+        c.append(dict(name=tab, table=tab, method="FPI", tol=1e-5, max_iter=1000, error_filt_threshold=0.01))
+    for K in (2, 3, 5, 8):
+        c.append(dict(name="k%d" % K, table="k%d" % K, method="FPI", tol=1e-5, max_iter=1000, error_filt_threshold=None))
+    c.append(dict(name="two_converged", table="two", method="FPI", tol=1e-5, max_iter=1000, error_filt_threshold=None))
+    c.append(dict(name="two_max_iter", table="two", method="FPI", tol=1e-5, max_iter=40, error_filt_threshold=None))
+    for mi in (0, 1, 31, 32, 33, 64, 65):
+        c.append(dict(name="d25_max_iter_%d" % mi, table="d25", method="FPI", tol=1e-5, max_iter=mi, error_filt_threshold=0.01))
+    for tab in ("cut5", "cut6"):
+        c.append(dict(name=tab, table=tab, method="FPI", tol=1e-5, max_iter=1000, error_filt_threshold=None))
+    for name, extra in (("base", []), ("keep19", [[19, 1, 0, 0, 400]]), ("drop39", [[39, 1, 0, 0, 400]]), ("zero", [[0, 0, 0, 0, 400]])):
+        c.append(dict(name=name + "_filter_0.05", table="raw_base", extra_rows=extra, method="FPI", tol=1e-5, max_iter=1000,
+                      error_filt_threshold=0.05))
+    return c
+
+
+def _hp_dirichlet_one(args):
+    import hp_dirichlet as H
+    case, table = args
+    rows = H.expand(table + case.get("extra_rows", []))
+    K = rows.shape[1]
+    keptrows = H.select_rows(rows, case["error_filt_threshold"])
+    out = dict(case, K=K, kept_rows=int(len(keptrows)))
+    if len(keptrows) <= 5:
+        alphas, iters, margin = [0] * (K - 1) + [1], 0, None
+        out.update(alphas=[[float(a), 0.0] for a in alphas], iters=0, margin=None)
+    else:
+        d = np.array(H.distinct(np.sort(keptrows, axis=1)), np.float64)
+        alphas, iters, margin = H.hp_fit(d[:, :-1], case["max_iter"], case["tol"], case["method"], mult=d[:, -1])
+        assert margin is None or margin >= H.ILL, ("ill case", case["name"], margin)
+        out.update(alphas=[H.split(a) for a in alphas], iters=iters, margin=margin)
+    got, oit = O.find_dirichlet_priors(rows, max_iter=case["max_iter"], tol=case["tol"], method=case["method"],
+                                       error_filt_threshold=case["error_filt_threshold"], return_iters=True)
+    assert oit == out["iters"], ("the oracle stops elsewhere", case["name"], oit, out["iters"])
+    hi, lo = np.array(out["alphas"]).T
+    out["oracle_rel_err"] = float(H.rel_errors(got, hi, lo).max())
+    return out
+
+
+def hp_dirichlet():
+    import multiprocessing
+    from scipy.special import psi
+    sys.path.insert(0, os.path.dirname(HERE))
+    import hp_dirichlet as H
+    tables = _dir_tables(H)
+    cases = _dir_cases()
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool:
+        res = pool.map(_hp_dirichlet_one, [(c, tables[c["table"]]) for c in cases], chunksize=1)
+    xs = H.digamma_grid()
+    hi, lo = H.digamma_true(xs)
+    scipy_worst = float(np.abs(H.ulp_errors(psi(xs), hi, H.digamma_lo(hi, lo))).max())
+    head = {"about": "find_dirichlet_priors (alphas, iterations) and digamma from their definitions at %d digits (tests/hp_dirichlet.py); "
+                     "a value is [nearest double, double of the remainder]; digamma_lo_ulp: the remainder in units of ulp(digamma_hi)" % H.DPS,
+            "digits": H.DPS, "ill": H.ILL,
+            "digamma": {"points": len(xs), "x_first_last": [float(xs[0]), float(xs[-1])], "x_sum": float(np.sum(xs)),
+                        "scipy_worst_ulp": float("%.3g" % scipy_worst)}}
+    with open(os.path.join(HERE, "dirichlet_hp_golden.json"), "w") as fh:
+        fh.write(json.dumps(head)[:-1] + ',\n"digamma_hi": ' + json.dumps(hi) + ',\n"digamma_lo_ulp": ' + json.dumps(lo) + ',\n"tables": {\n')
+        fh.write(",\n".join('"%s": %s' % (k, json.dumps(v, separators=(",", ":"))) for k, v in tables.items()) + '\n},\n"cases": [\n')
+        fh.write(",\n".join(json.dumps(c) for c in res) + "\n]}\n")
+    print("wrote dirichlet_hp_golden.json", len(res), "cases; scipy's psi worst %.3g ulp" % scipy_worst)
+    for c in res:
+        print("  %-22s kept %5d  iters %4d  margin %-10s oracle_rel_err %.3g" % (c["name"], c["kept_rows"], c["iters"],
+                                                                                 "%.3g" % c["margin"] if c["margin"] is not None else "-", c["oracle_rel_err"]))
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["hp-dirichlet"]:         # only the high-precision fit / digamma fixture (no reference needed)
+        hp_dirichlet()
+        sys.exit(0)
     if sys.argv[1:] == ["hp-filter"]:            # only the high-precision filter fixture (no reference needed)
         hp_filter()
         sys.exit(0)
