@@ -187,6 +187,21 @@ int tracs_alignment_select_samples(const tracs_alignment *src, const uint8_t *ke
 int tracs_pairs_min_sites(uint32_t *dist, const uint32_t *ncomp, size_t ld, size_t n, size_t row_begin, size_t row_end, size_t col_begin,
                           int32_t dist_threshold, uint32_t min_sites, void *stream);
 
+/* The alignment a run compared, back as text, and what is in its columns (not in the reference).  Masks are the
+ * pack's: bit 0 = A, 1 = C, 2 = G, 3 = T.  The canonical letter of a mask m is "XACMGRSVTWYHKDBN"[m] (15 -> 'N'): lower case, '-' and
+ * non-letters come out as their upper-case letter or 'N', and packing the canonical text of a handle gives the handle's bytes back.
+ *   tracs_alignment_site_census  per site, over the handle's n samples (pad samples never count): counts (device uint32, category-
+ *                                major counts[c * L + s], c = A, C, G, T, N, other: the samples whose mask is exactly that letter,
+ *                                all four bits, or a partial code; the six sum to n; may be NULL) and whether the site DIFFERS:
+ *                                two samples have disjoint masks there (m_i & m_j == 0) -- exactly the sites that add 1 to some
+ *                                d(i, j).  differs (host bitmap, ceil(L / 64) words, bit s of differs[s / 64]; may be NULL),
+ *                                *n_differs its population (may be NULL).  Synchronises the stream when either is asked for.
+ *   tracs_alignment_unpack       samples [first, first + count) -> canonical text, device uint8, row k at ascii + k * stride.  Writes
+ *                                the L bytes of each row and nothing else (no byte at or beyond column L, no other row).  Refused
+ *                                with TRACS_E_ARG, nothing launched: first + count > n, stride < L, a NULL pointer.               */
+int tracs_alignment_site_census(const tracs_alignment *a, uint32_t *counts, uint64_t *differs, size_t *n_differs, void *stream);
+int tracs_alignment_unpack(const tracs_alignment *a, size_t first, size_t count, uint8_t *ascii, size_t stride, void *stream);
+
 /* The rules of the FASTA entry points in one place.  Applied in this order:
  *   1. keep / keep_len       the file rules' bitmap over the columns read (NULL: every column); L' = the columns it leaves
  *   2. max_sample_n_share G  a record is left out when more than floor(G L') of those columns are N in it; with two files the rule
@@ -543,6 +558,19 @@ int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, doub
  *                         n_eligible: the pairs counted (the rows tracs_distance_run would write without metadata).              */
 int tracs_distance_histogram(tracs_distance *h, int dist, int filter, const int32_t *group, const char *path, const char *ref,
                              uint64_t *n_eligible, uint64_t *rows_written);
+/*   tracs_distance_site_census    tracs_alignment_site_census of what the handle compares (the surviving samples, the kept columns),
+ *                         everything on the host: counts_host uint32[6 * tracs_distance_len] (may be NULL), differs_host
+ *                         ceil(tracs_distance_len / 64) words (may be NULL), *n_differs (may be NULL).
+ *   tracs_distance_write_alignment  that alignment as FASTA (tracs_write_fasta_rows: ".gz" by suffix), samples [sample_begin,
+ *                         sample_end) under their names, unpacked in batches of samples -- device buffer, pinned host buffer,
+ *                         writer --, so memory does not grow with n: two buffers of at most 256 MiB (one row when a row is
+ *                         longer) plus the writer's members.  differing_only != 0: only the columns that differ among ALL the
+ *                         handle's samples (census, then tracs_alignment_select_sites under the differs bitmap into a temporary
+ *                         handle that is freed again; no such column: refused).  *sites_written: columns per record.  The handle
+ *                         is left as it was.                                                                                   */
+int tracs_distance_site_census(tracs_distance *h, uint32_t *counts_host, uint64_t *differs_host, size_t *n_differs);
+int tracs_distance_write_alignment(tracs_distance *h, const char *path, size_t sample_begin, size_t sample_end, int differing_only,
+                                   int n_threads, int gzip_level, size_t *sites_written);
 void tracs_distance_free(tracs_distance *h);
 
 /* Rows of `tracs distance`'s CSV appended to path (tracs/distance.py:206-258; the caller writes the header, :157):
@@ -575,6 +603,13 @@ void tracs_edges_free(tracs_edge_list *e);
  * a file with more than one record is an error ("... contains more than one sequence").                         */
 int tracs_combine_fasta(const char *out_path, const char *const *sample_names, const char *const *fasta_paths,
                         size_t n, int n_threads, int gzip_level, double *frac_n, uint64_t *lengths);
+
+/* Rows of text as FASTA: ">" names[k] "\n" the L bytes at ascii_host + k * stride "\n", k < count, one line per record.  Plain
+ * text unless path ends in ".gz": then one gzip member per record, compressed in parallel (n_threads <= 0: all cores; gzip_level
+ * < 0: 6) and written in order, as tracs_combine_fasta does.  append != 0 extends the file (a multi-member gzip stays one stream),
+ * else it is truncated; count = 0 leaves an empty (or unchanged) file.  Host only.                                            */
+int tracs_write_fasta_rows(const char *path, const char *const *names, const uint8_t *ascii_host, size_t stride, size_t count,
+                           size_t L, int append, int n_threads, int gzip_level);
 
 /* ===================================================================================== */
 /* (4) MULTI-GPU EXCHANGE -- RCCL over xGMI, one communicator rank per process             */

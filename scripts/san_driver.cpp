@@ -99,6 +99,28 @@ int main(int argc, char **argv)
         put(paths[2], ">x\nAC\n>y\nAC\n", false);
         if (tracs_combine_fasta(out.c_str(), names, pp, 5, 3, 6, fr, ln) == 0) { printf("combine: two records accepted\n"); fails++; }
     }
+    for (int gz = 0; gz < 2; gz++) {   // rows of text -> FASTA: stride > L, count = 0, append, an unwritable path
+        const size_t L = 1003, stride = 1024, count = 9;
+        std::vector<uint8_t> rows(count * stride - (stride - L), 'A');       // the last row ends at its L-th byte: nothing beyond may be read
+        std::vector<std::string> nm;
+        std::vector<const char *> np;
+        for (size_t k = 0; k < count; k++) { nm.push_back("row" + std::to_string(k)); for (size_t i = 0; i < L; i++) rows[k * stride + i] = "ACGTN"[(k + i) % 5]; }
+        for (auto &s : nm) np.push_back(s.c_str());
+        const std::string p = dir + (gz ? "/san_rows.fa.gz" : "/san_rows.fa");
+        int bad = 0;
+        bad += tracs_write_fasta_rows(p.c_str(), np.data(), rows.data(), stride, 4, L, 0, 3, 6) != 0;
+        bad += tracs_write_fasta_rows(p.c_str(), nullptr, nullptr, stride, 0, L, 1, 3, 6) != 0;                 // count = 0: nothing added
+        bad += tracs_write_fasta_rows(p.c_str(), np.data() + 4, rows.data() + 4 * stride, stride, count - 4, L, 1, 3, 6) != 0;
+        tracs::FastaData fd;
+        std::string err;
+        if (bad || tracs::read_fasta(p, fd, err) != 0 || fd.n != count || fd.L != L || fd.names[8] != "row8" ||
+            std::memcmp(fd.seq.data() + 8 * L, rows.data() + 8 * stride, L) != 0) { printf("fasta rows (gz %d): %s\n", gz, err.c_str()); fails++; }
+        FILE *f = nullptr;
+        if (tracs_write_fasta_rows(p.c_str(), nullptr, nullptr, stride, 0, L, 0, 1, 6) != 0 || !(f = fopen(p.c_str(), "rb")) || fgetc(f) != EOF) { printf("fasta rows: count = 0 must leave an empty file\n"); fails++; }
+        if (f) fclose(f);
+        const std::string nowhere = dir + "/no_such_folder/rows.fa" + (gz ? ".gz" : "");
+        if (tracs_write_fasta_rows(nowhere.c_str(), np.data(), rows.data(), stride, 4, L, 0, 3, 6) != TRACS_E_OPEN) { printf("fasta rows: unwritable path accepted\n"); fails++; }
+    }
     {
         const double v[] = {0.0, -0.0, 1e300, 5e-324, 123456.789, 1e16, 1e-5};
         char buf[512];

@@ -45,6 +45,8 @@ SYMBOLS = [
     "tracs_nearest_rules", "tracs_distance_open_rules", "tracs_pairsnp_source_nseq", "tracs_pairsnp_source_name",
     "tracs_pairsnp_source_n_count", "tracs_pairsnp_source_kept", "tracs_pairsnp_rule_sites", "tracs_distance_source_nseq",
     "tracs_distance_source_name", "tracs_distance_source_n_count", "tracs_distance_source_kept", "tracs_distance_rule_sites",
+    "tracs_alignment_site_census", "tracs_alignment_unpack", "tracs_write_fasta_rows", "tracs_distance_site_census",
+    "tracs_distance_write_alignment",
     "tracs_distance_histogram", "tracs_hist_state_bytes", "tracs_hist_init", "tracs_hist_update", "tracs_hist_update_coo", "tracs_hist_emit",
 ]
 
@@ -392,6 +394,18 @@ def load():
     L.tracs_debug_trans_routes.argtypes = [C.POINTER(C.c_double)]
     L.tracs_debug_iupac_mask.restype = C.c_int
     L.tracs_debug_iupac_mask.argtypes = [C.c_int]
+    L.tracs_alignment_site_census.restype = C.c_int
+    L.tracs_alignment_site_census.argtypes = [vp, vp, u64p, C.POINTER(sz), vp]
+    L.tracs_alignment_unpack.restype = C.c_int
+    L.tracs_alignment_unpack.argtypes = [vp, sz, sz, vp, sz, vp]
+    L.tracs_write_fasta_rows.restype = C.c_int
+    L.tracs_write_fasta_rows.argtypes = [C.c_char_p, cpp, vp, sz, sz, sz, C.c_int, C.c_int, C.c_int]
+    L.tracs_distance_site_census.restype = C.c_int
+    L.tracs_distance_site_census.argtypes = [vp, vp, u64p, C.POINTER(sz)]
+    L.tracs_distance_write_alignment.restype = C.c_int
+    L.tracs_distance_write_alignment.argtypes = [vp, C.c_char_p, sz, sz, C.c_int, C.c_int, C.c_int, C.POINTER(sz)]
+    L.tracs_debug_differs_table.restype = C.c_int
+    L.tracs_debug_differs_table.argtypes = [vp, sz]
     _lib = L
     return L
 

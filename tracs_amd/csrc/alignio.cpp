@@ -663,6 +663,36 @@ const int32_t *tracs_edges_i(const tracs_edge_list *e) { return e ? e->I.data() 
 const int32_t *tracs_edges_j(const tracs_edge_list *e) { return e ? e->J.data() : nullptr; }
 void tracs_edges_free(tracs_edge_list *e) { delete e; }
 
+// One gzip member holding `text` (-> NULL, or what failed).  gzip FEXTRA subfield "TR": the member's total size in bytes (patched in
+// after the deflate), so a reader can hop from member to member and inflate them in parallel (fasta.cpp); every other gzip reader
+// ignores extra fields.
+static const char *gzip_member(const char *text, size_t len, int level, std::vector<unsigned char> &o)
+{
+    z_stream zs;
+    std::memset(&zs, 0, sizeof zs);
+    if (deflateInit2(&zs, level, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) return "deflateInit2 failed";
+    unsigned char extra[12] = {'T', 'R', 8, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    gz_header gh;
+    std::memset(&gh, 0, sizeof gh);
+    gh.os = 3;
+    gh.extra = extra;
+    gh.extra_len = sizeof extra;
+    deflateSetHeader(&zs, &gh);
+    o.resize(deflateBound(&zs, (uLong)len) + 128);
+    zs.next_in = reinterpret_cast<Bytef *>(const_cast<char *>(text));
+    zs.avail_in = (uInt)len;
+    zs.next_out = o.data();
+    zs.avail_out = (uInt)o.size();
+    const int zr = deflate(&zs, Z_FINISH);
+    o.resize(zr == Z_STREAM_END ? zs.total_out : 0);
+    deflateEnd(&zs);
+    if (o.size() > 24 && o[3] == 4 && o[12] == 'T' && o[13] == 'R') {   // FLG = FEXTRA only: payload at byte 16
+        const uint64_t sz = o.size();
+        for (int b = 0; b < 8; b++) o[16 + b] = (unsigned char)(sz >> (8 * b));
+    }
+    return zr == Z_STREAM_END ? nullptr : "deflate failed";
+}
+
 // One gzip member per sample (a multi-member gzip file is what gzopen/zcat/kseq read as one stream), compressed in
 // parallel and written in input order:  ">" sample "\n" sequence "\n"  (tracs/combine.py:227-231).
 int tracs_combine_fasta(const char *out_path, const char *const *sample_names, const char *const *fasta_paths, size_t n,
@@ -711,38 +741,10 @@ int tracs_combine_fasta(const char *out_path, const char *const *sample_names, c
                 for (size_t k = 0; k < fd.L; k++) nN += fd.seq[k] == 'N';
                 if (frac_n) frac_n[s] = fd.L ? (double)nN / (double)fd.L : 0.0;  // seq.count("N") / len(seq)  (:238)
                 if (lengths) lengths[s] = fd.L;
-                z_stream zs;
-                std::memset(&zs, 0, sizeof zs);
-                if (deflateInit2(&zs, level, Z_DEFLATED, 15 + 16, 8, Z_DEFAULT_STRATEGY) != Z_OK) {
+                const char *zerr = gzip_member(text.data(), text.size(), level, member[t]);
+                if (zerr) {
                     std::lock_guard<std::mutex> lock(mu);
-                    if (rc == TRACS_OK) { rc = TRACS_E_NOMEM; first_error = "deflateInit2 failed"; }
-                    return;
-                }
-                // gzip FEXTRA subfield "TR": the member's total size in bytes (patched in below), so a reader can hop from
-                // member to member and inflate them in parallel (fasta.cpp); every other gzip reader ignores extra fields
-                unsigned char extra[12] = {'T', 'R', 8, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-                gz_header gh;
-                std::memset(&gh, 0, sizeof gh);
-                gh.os = 3;
-                gh.extra = extra;
-                gh.extra_len = sizeof extra;
-                deflateSetHeader(&zs, &gh);
-                std::vector<unsigned char> &o = member[t];
-                o.resize(deflateBound(&zs, (uLong)text.size()) + 128);
-                zs.next_in = reinterpret_cast<Bytef *>(const_cast<char *>(text.data()));
-                zs.avail_in = (uInt)text.size();
-                zs.next_out = o.data();
-                zs.avail_out = (uInt)o.size();
-                const int zr = deflate(&zs, Z_FINISH);
-                o.resize(zr == Z_STREAM_END ? zs.total_out : 0);
-                deflateEnd(&zs);
-                if (o.size() > 24 && o[3] == 4 && o[12] == 'T' && o[13] == 'R') {   // FLG = FEXTRA only: payload at byte 16
-                    const uint64_t sz = o.size();
-                    for (int b = 0; b < 8; b++) o[16 + b] = (unsigned char)(sz >> (8 * b));
-                }
-                if (zr != Z_STREAM_END) {
-                    std::lock_guard<std::mutex> lock(mu);
-                    if (rc == TRACS_OK) { rc = TRACS_E_NOMEM; first_error = "deflate failed"; }
+                    if (rc == TRACS_OK) { rc = TRACS_E_NOMEM; first_error = zerr; }
                 }
             });
         for (auto &x : th) x.join();
@@ -755,6 +757,64 @@ int tracs_combine_fasta(const char *out_path, const char *const *sample_names, c
             }
     }
     if (std::fclose(fo) != 0 && rc == TRACS_OK) { rc = TRACS_E_OPEN; first_error = std::string("error closing '") + out_path + "'"; }
+    if (rc != TRACS_OK) set_error(first_error);
+    return rc;
+}
+
+// Rows of canonical text -> FASTA, one line per record:  ">" name "\n" sequence "\n".  Row k is the L bytes at ascii + k * stride.
+// Plain text unless `path` ends in ".gz"; then one gzip member per record, compressed in parallel and written in order, as
+// tracs_combine_fasta does.  append: the file is extended (a multi-member gzip stays one stream), else truncated.
+int tracs_write_fasta_rows(const char *path, const char *const *names, const uint8_t *ascii, size_t stride, size_t count, size_t L,
+                           int append, int n_threads, int gzip_level)
+{
+    if (!path || (count && (!names || (!ascii && L)))) { set_error("tracs_write_fasta_rows: NULL argument"); return TRACS_E_ARG; }
+    if (count > 1 && stride < L) { set_error("tracs_write_fasta_rows: stride shorter than one row"); return TRACS_E_ARG; }
+    const size_t plen = std::strlen(path);
+    const bool gz = plen >= 3 && std::strcmp(path + plen - 3, ".gz") == 0;
+    FILE *fo = std::fopen(path, append ? "ab" : "wb");
+    if (!fo) { set_error(std::string("cannot open '") + path + "' for writing"); return TRACS_E_OPEN; }
+    int rc = TRACS_OK;
+    std::string first_error;
+    auto put = [&](const void *p, size_t k) {
+        if (k && std::fwrite(p, 1, k, fo) != k && rc == TRACS_OK) { rc = TRACS_E_OPEN; first_error = std::string("error writing '") + path + "'"; }
+    };
+    if (!gz) {
+        for (size_t k = 0; k < count && rc == TRACS_OK; k++) {
+            put(">", 1);
+            put(names[k], std::strlen(names[k]));
+            put("\n", 1);
+            put(ascii + k * stride, L);
+            put("\n", 1);
+        }
+    } else {
+        const unsigned T = (unsigned)std::max(1, std::min(n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency(), 64));
+        const int level = gzip_level < 0 ? 6 : std::min(9, gzip_level);
+        std::mutex mu;
+        for (size_t base = 0; base < count && rc == TRACS_OK; base += T) {
+            const size_t cnt = std::min<size_t>(T, count - base);
+            std::vector<std::vector<unsigned char>> member(cnt);
+            std::vector<std::thread> th;
+            for (size_t t = 0; t < cnt; t++)
+                th.emplace_back([&, t]() {
+                    const size_t k = base + t;
+                    std::string text;
+                    text.reserve(L + std::strlen(names[k]) + 4);
+                    text.push_back('>');
+                    text += names[k];
+                    text.push_back('\n');
+                    if (L) text.append(reinterpret_cast<const char *>(ascii + k * stride), L);
+                    text.push_back('\n');
+                    const char *zerr = gzip_member(text.data(), text.size(), level, member[t]);
+                    if (zerr) {
+                        std::lock_guard<std::mutex> lock(mu);
+                        if (rc == TRACS_OK) { rc = TRACS_E_NOMEM; first_error = zerr; }
+                    }
+                });
+            for (auto &x : th) x.join();
+            for (size_t t = 0; t < cnt && rc == TRACS_OK; t++) put(member[t].data(), member[t].size());
+        }
+    }
+    if (std::fclose(fo) != 0 && rc == TRACS_OK) { rc = TRACS_E_OPEN; first_error = std::string("error closing '") + path + "'"; }
     if (rc != TRACS_OK) set_error(first_error);
     return rc;
 }

@@ -768,6 +768,75 @@ size_t tracs_distance_nseq(const tracs_distance *h) { return h ? h->names.size()
 const char *tracs_distance_name(const tracs_distance *h, size_t i) { return (h && i < h->names.size()) ? h->names[i].c_str() : nullptr; }
 void tracs_distance_free(tracs_distance *h) { if (h) { if (h->a) tracs_alignment_free(h->a); delete h; } }
 
+// ---- what the handle compares, looked at and written out (csrc/msa_out.hip) -----------------------------------------
+int tracs_distance_site_census(tracs_distance *h, uint32_t *counts_host, uint64_t *differs_host, size_t *n_differs)
+{
+    if (n_differs) *n_differs = 0;
+    if (!h || !h->a) { set_error("tracs_distance_site_census: NULL argument"); return TRACS_E_ARG; }
+    const tracs_alignment *a = h->a;
+    if (!a->L) return TRACS_OK;
+    uint32_t *d_counts = nullptr;
+    if (counts_host) {
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_counts), a->L * 6 * 4);
+        if (e != hipSuccess) { (void)hipGetLastError(); set_error(std::string("hipMalloc(site census): ") + hipGetErrorString(e)); return TRACS_E_NOMEM; }
+    }
+    int rc = site_census(a, d_counts, differs_host, n_differs, nullptr);
+    if (!rc && counts_host) {
+        const hipError_t e = hipMemcpy(counts_host, d_counts, a->L * 6 * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { set_error(std::string("hipMemcpy(site census): ") + hipGetErrorString(e)); rc = TRACS_E_HIP; }
+    }
+    if (d_counts) (void)hipFree(d_counts);
+    return rc;
+}
+
+// Batches of samples: device buffer -> pinned host buffer -> writer.  The two buffers hold `batch` rows of `stride` bytes (the row
+// length rounded up to 16, so every row takes the kernel's 16-byte stores): at most 256 MiB each, or one row when a row is longer --
+// whatever n is.  The writer adds one compressed member per thread.
+int tracs_distance_write_alignment(tracs_distance *h, const char *path, size_t sample_begin, size_t sample_end, int differing_only,
+                                   int n_threads, int gzip_level, size_t *sites_written)
+{
+    if (sites_written) *sites_written = 0;
+    if (!h || !h->a || !path) { set_error("tracs_distance_write_alignment: NULL argument"); return TRACS_E_ARG; }
+    if (sample_begin > sample_end || sample_end > h->a->n) { set_error("tracs_distance_write_alignment: sample range outside the alignment"); return TRACS_E_ARG; }
+    const tracs_alignment *a = h->a;
+    tracs_alignment *cut = nullptr;
+    int rc = TRACS_OK;
+    if (differing_only) {
+        std::vector<uint64_t> differs((a->L + 63) / 64, 0);
+        size_t nd = 0;
+        if ((rc = site_census(a, nullptr, differs.data(), &nd, nullptr))) return rc;
+        if (!nd) { set_error("no column differs among the samples"); return TRACS_E_ARG; }
+        if ((rc = select_sites(const_cast<tracs_alignment *>(a), differs.data(), a->L, UINT32_MAX, &cut, nullptr, nullptr, nullptr, false))) return rc;
+        a = cut;
+    }
+    const size_t L = a->L, stride = (L + 15) / 16 * 16, count = sample_end - sample_begin;
+    const size_t batch = std::max<size_t>(1, std::min<size_t>(count, stride ? (256ull << 20) / stride : count));
+    uint8_t *d_buf = nullptr, *h_buf = nullptr;
+    auto done = [&](int r) {
+        if (d_buf) (void)hipFree(d_buf);
+        if (h_buf) (void)hipHostFree(h_buf);
+        if (cut) tracs_alignment_free(cut);
+        return r;
+    };
+#define WA_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { (void)hipGetLastError(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return done(TRACS_E_HIP); } } while (0)
+    if (count && L) {
+        WA_CHECK(hipMalloc(reinterpret_cast<void **>(&d_buf), batch * stride));
+        WA_CHECK(hipHostMalloc(reinterpret_cast<void **>(&h_buf), batch * stride, hipHostMallocDefault));
+    }
+    if ((rc = tracs_write_fasta_rows(path, nullptr, nullptr, stride, 0, L, 0, n_threads, gzip_level))) return done(rc);     // truncate
+    for (size_t s = sample_begin; s < sample_end; s += batch) {
+        const size_t cnt = std::min(batch, sample_end - s);
+        if (L) {
+            if ((rc = unpack_rows(a, s, cnt, d_buf, stride, nullptr))) return done(rc);
+            WA_CHECK(hipMemcpy(h_buf, d_buf, cnt * stride, hipMemcpyDeviceToHost));
+        }
+        if ((rc = tracs_write_fasta_rows(path, h->name_ptr.data() + s, h_buf, stride, cnt, L, 1, n_threads, gzip_level))) return done(rc);
+    }
+#undef WA_CHECK
+    if (sites_written) *sites_written = L;
+    return done(TRACS_OK);
+}
+
 // the date difference of every emitted pair, as tracs/transcluster.py:26-33 takes it: |t_i - t_j| / 31556952.0 with t = whole days in seconds
 __global__ __launch_bounds__(256) void coo_delta_kernel(const unsigned *__restrict__ rows, const unsigned *__restrict__ cols, const int *__restrict__ days,
                                                         size_t n, double *__restrict__ out)

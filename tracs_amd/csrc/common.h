@@ -127,6 +127,10 @@ int select_samples(tracs_alignment *src, const uint8_t *keep_sample, tracs_align
 int pairs_min_sites(uint32_t *dist, const uint32_t *ncomp, size_t ld, size_t n, size_t row_begin, size_t row_end, size_t col_begin,
                     int32_t dist_threshold, uint32_t min_sites, hipStream_t stream);
 
+// msa_out.hip: the per-site census (counts device / differs host) and rows of canonical text (tracs_alignment_site_census / _unpack)
+int site_census(const tracs_alignment *a, uint32_t *counts, uint64_t *differs, size_t *n_differs, hipStream_t stream);
+int unpack_rows(const tracs_alignment *a, size_t first, size_t count, uint8_t *ascii, size_t stride, hipStream_t stream);
+
 // device memory that lives until the alignment is packed again (site_classes_free releases all of it at once)
 hipError_t pack_alloc(tracs_alignment *a, size_t bytes, void **out);
 void pack_release(tracs_alignment *a);

@@ -206,6 +206,28 @@ class Alignment:
             new.n_first = int(m[:self.n_first].sum())
         return new
 
+    def site_census(self):
+        """-> (torch.int32 [6, L] on the device, bool ndarray [L]): per site, the samples whose allele mask is exactly A, C, G, T, all
+        four (N), or a partial code -- the six rows sum to n --, and whether the site differs: two samples with disjoint masks, the
+        sites that add 1 to some SNP distance.  Pad samples never count.  tracs_alignment_site_census."""
+        from .sites import bitmap_to_bool
+        counts = torch.empty((6, self.L), dtype=torch.int32, device="cuda")
+        words = np.zeros((self.L + 63) // 64, np.uint64)
+        _lib.check(self._L.tracs_alignment_site_census(self._h, _ptr(counts), words.ctypes.data_as(C.POINTER(C.c_uint64)), None, _stream()))
+        return counts, bitmap_to_bool(words, self.L)
+
+    def unpack(self, first=0, count=None, stride=None, out=None):
+        """-> torch.uint8 [count, stride] on the device: samples [first, first + count) as canonical text ("XACMGRSVTWYHKDBN"[mask];
+        packing it gives this handle's bytes back).  Only the first L bytes of each row are written (stride: default L).  out: a
+        contiguous uint8 device tensor [count, stride] to write into.  tracs_alignment_unpack."""
+        count = self.n - int(first) if count is None else int(count)
+        stride = self.L if stride is None else int(stride)
+        if out is None:
+            out = torch.empty((max(count, 0), stride), dtype=torch.uint8, device="cuda")
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.numel() >= max(count, 0) * stride
+        _lib.check(self._L.tracs_alignment_unpack(self._h, int(first), count, _ptr(out), stride, _stream()))
+        return out
+
     @property
     def nbytes(self):
         return self._L.tracs_alignment_bytes(self._h)

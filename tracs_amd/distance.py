@@ -105,6 +105,22 @@ def distance_parser(parser):
                          "for the full output, --nearest, --mst and --histogram alike")
     sm.add_argument("--samples-out", dest="samples_out", default=None, type=str, metavar="FILE",
                     help="With --max-sample-n-share: write sample,MSA file,N sites,sites,kept for every record read, in input order")
+    mo = parser.add_argument_group("The compared alignment",
+                                   "What the run compared, after every rule: the surviving samples and the kept columns (unpacked and "
+                                   "counted on the GPU; not in the reference).  One --msa file, no --msa-db, one GPU.  For the files "
+                                   "alone, add --histogram: no pair rows are written.")
+    mo.add_argument("--msa-out", dest="msa_out", default=None, type=str, metavar="FILE",
+                    help="Write the alignment the run compared as FASTA (gzip when FILE ends in .gz): the surviving samples in order "
+                         "under their names, the kept columns, in canonical text -- upper-case IUPAC letters, N for '-' and for every "
+                         "byte that is no IUPAC letter.  `distance --msa FILE` without any rule gives the same result.")
+    mo.add_argument("--msa-out-sites", dest="msa_out_sites", default=None, choices=["kept", "differing"],
+                    help="kept (default): every kept column.  differing: only the columns at which two surviving samples have "
+                         "disjoint allele sets -- the columns that add to some SNP distance; every SNP distance stays the same, "
+                         "`sites considered` and the filter's alignment length shrink")
+    mo.add_argument("--site-table", dest="site_table", default=None, type=str, metavar="FILE",
+                    help="Write contig,position,A,C,G,T,N,other,differs per kept column, in order: the surviving samples that are "
+                         "exactly that letter, N, or a partial code there, and whether the column differs (positions 0-based, in the "
+                         "coordinates of --sites-out)")
     tr = parser.add_argument_group("Transmission distance options")
     tr.add_argument("--clock_rate", dest="clock_rate", type=check_positive_float, default=1e-3 * 29903,
                     help="clock rate as defined in the transcluster paper (SNPs/genome/year) default=1e-3 * 29903")
@@ -164,7 +180,7 @@ def _append_rows(path, names, rows, cols, snpd, filt, ncomp, ddiff, tdist, ek, k
     return written.value
 
 
-def _rows_on_device(msas, args, dates, ref, stage, rule=None):
+def _rows_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
     """One alignment through libtracs_hip.so's device-resident path (tracs_distance_open / _run: include/tracs_hip.h): FASTA -> packed
     planes -> dense panels -> transcluster on the panels -> the pairs within the threshold with their P and E(K) -> ONE device-to-host
     pass, in batches -> the CSV rows, formatted and appended by the library's host threads.  Nothing comes back to Python but the
@@ -191,12 +207,13 @@ def _rows_on_device(msas, args, dates, ref, stage, rule=None):
                                         kmax, os.fsencode(args.output_file), ref.encode(), int(bool(args.recomb_filter)), C.byref(written),
                                         C.byref(pairs)))
         stage("[sum] tracs_distance_run (dense panels, transcluster, rows: %d pairs, %d rows written)" % (pairs.value, written.value))
+        write_msa_outputs(L, h, args, msas[0], contigs)
         return True
     finally:
         L.tracs_distance_free(h)
 
 
-def _forest_on_device(msas, args, dates, ref, stage, rule=None):
+def _forest_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
     """--mst WEIGHT for one alignment (tracs_distance_open / _forest: include/tracs_hip.h): the panel loop of _rows_on_device up to the
     pairs within the threshold with their P and E(K), then the minimum spanning forest of the eligible pairs on the device; only its
     rows are formatted and appended.  With metadata every sample needs a date (the full run's array route has KeyError rules of its
@@ -224,6 +241,7 @@ def _forest_on_device(msas, args, dates, ref, stage, rule=None):
                                            os.fsencode(args.output_file), ref.encode(), C.byref(written), C.byref(eligible)))
         stage("[sum] tracs_distance_forest (dense panels, transcluster, forest: %d eligible pairs, %d rows written)"
               % (eligible.value, written.value))
+        write_msa_outputs(L, h, args, msas[0], contigs)
     finally:
         L.tracs_distance_free(h)
 
@@ -262,6 +280,71 @@ def check_site_args(args):
         raise SystemExit("tracs distance: --sites-out describes one alignment; give one --msa file")
     if out is not None and share is not None and getattr(args, "nearest", None) is not None:
         raise SystemExit("tracs distance: --sites-out with --nearest takes file rules only (--mask, --keep), not --max-n-share")
+
+
+def check_msa_out_args(args):
+    """--msa-out / --msa-out-sites / --site-table: argument checks, before anything touches the GPU (SystemExit with the message)."""
+    out, which, table = getattr(args, "msa_out", None), getattr(args, "msa_out_sites", None), getattr(args, "site_table", None)
+    if which is not None and out is None:
+        raise SystemExit("tracs distance: --msa-out-sites needs --msa-out (it chooses the columns of that file)")
+    if out is None and table is None:
+        return
+    if getattr(args, "msa_db", None) is not None:
+        raise SystemExit("tracs distance: --msa-out and --site-table describe one alignment and take no --msa-db")
+    if len(getattr(args, "msa_files", None) or []) > 1:
+        raise SystemExit("tracs distance: --msa-out and --site-table describe one alignment; give one --msa file")
+    if getattr(args, "gpus", 1) > 1:
+        raise SystemExit("tracs distance: --msa-out and --site-table run on one GPU; use --gpus 1")
+    inputs = list(getattr(args, "msa_files", None) or [])
+    inputs += [getattr(args, k, None) for k in ("metadata", "mask_bed", "keep_bed", "mask_reference", "groups")]
+    inputs = {os.path.realpath(p) for p in inputs if p is not None}
+    for opt, path in (("--msa-out", out), ("--site-table", table)):
+        if path is not None and os.path.realpath(path) in inputs:
+            raise SystemExit("tracs distance: %s %s is one of the run's input files" % (opt, path))
+    outs = [os.path.realpath(p) for p in (out, table, getattr(args, "output_file", None), getattr(args, "sites_out", None),
+                                          getattr(args, "samples_out", None)) if p is not None]
+    if len(set(outs)) != len(outs):
+        raise SystemExit("tracs distance: two outputs of the run name the same file")
+
+
+def write_msa_outputs(L, h, args, msa, contigs):
+    """--msa-out and --site-table for what the handle compares (the surviving samples, the kept columns): the census and the unpack
+    run on the GPU (tracs_distance_site_census / _write_alignment), one INFO line per file.  The handle is left as it was."""
+    out, table = getattr(args, "msa_out", None), getattr(args, "site_table", None)
+    if out is None and table is None:
+        return
+    import numpy as np
+    from . import sites as S
+    n, length = L.tracs_distance_nseq(h), L.tracs_distance_len(h)
+    u64p = C.POINTER(C.c_uint64)
+    counts = np.zeros((6, length), np.uint32) if table is not None else None
+    differs = np.zeros((length + 63) // 64, np.uint64)
+    n_differs = C.c_size_t(0)
+    _lib.check(L.tracs_distance_site_census(h, counts.ctypes.data if counts is not None else None, differs.ctypes.data_as(u64p),
+                                            C.byref(n_differs)))
+    if table is not None:
+        src_len = L.tracs_distance_source_len(h)
+        kept = np.zeros((src_len + 63) // 64, np.uint64)
+        _lib.check(L.tracs_distance_kept_sites(h, kept.ctypes.data_as(u64p)))
+        S.write_site_table(table, np.flatnonzero(S.bitmap_to_bool(kept, src_len)), counts, S.bitmap_to_bool(differs, length), contigs)
+        logging.info("Site table for %s: %s (%d samples, %d columns, %d differing)", msa, table, n, length, n_differs.value)
+    if out is not None:
+        written = C.c_size_t(0)
+        _lib.check(L.tracs_distance_write_alignment(h, os.fsencode(out), 0, n, int(getattr(args, "msa_out_sites", None) == "differing"),
+                                                    int(args.n_cpu), -1, C.byref(written)))
+        logging.info("Compared alignment of %s: %s (%d records, %d columns, %d differing)", msa, out, n, written.value, n_differs.value)
+
+
+def _msa_outputs_fresh(msas, args, rule, contigs):
+    """write_msa_outputs for the routes without a distance handle: one is opened with the same rules for the write"""
+    if getattr(args, "msa_out", None) is None and getattr(args, "site_table", None) is None:
+        return
+    L = _lib.require_gpu()
+    h = _open(L, msas, rule, args)
+    try:
+        write_msa_outputs(L, h, args, msas[0], contigs)
+    finally:
+        L.tracs_distance_free(h)
 
 
 SAMPLES_HEADER = "sample,MSA file,N sites,sites,kept\n"
@@ -470,7 +553,7 @@ def read_groups(path):
     return groups
 
 
-def _histogram_on_device(msas, args, groups, ref, stage, rule=None):
+def _histogram_on_device(msas, args, groups, ref, stage, rule=None, contigs=None):
     """--histogram for one alignment (tracs_distance_open / _histogram: include/tracs_hip.h): the panel loop of _rows_on_device with
     a histogram update per panel instead of the rows; only the non-empty bins are formatted and appended."""
     from .api import group_labels
@@ -489,6 +572,7 @@ def _histogram_on_device(msas, args, groups, ref, stage, rule=None):
         _lib.check(L.tracs_distance_histogram(h, int(args.snp_threshold), int(bool(args.recomb_filter)), labels,
                                               os.fsencode(args.output_file), ref.encode(), C.byref(eligible), C.byref(written)))
         stage("[sum] tracs_distance_histogram (dense panels, histogram: %d pairs counted, %d rows written)" % (eligible.value, written.value))
+        write_msa_outputs(L, h, args, msas[0], contigs)
     finally:
         L.tracs_distance_free(h)
 
@@ -553,6 +637,7 @@ def distance(args):
     check_histogram_args(args)
     check_site_args(args)
     check_sample_args(args)
+    check_msa_out_args(args)
     site_files = read_site_files(args)
     histogram = getattr(args, "histogram", False)
     groups = read_groups(args.groups) if histogram and args.groups is not None else None
@@ -606,6 +691,9 @@ def distance(args):
         ref = os.path.basename(msa).split(".")[0].replace("_combined", "")      # (:208-209)
         rule = site_rule_for(msas, args, site_files)
         ruled = dict(rule=rule) if rule is not None else {}                 # (no rule: every route is called as it always was)
+        msa_outputs = getattr(args, "msa_out", None) is not None or getattr(args, "site_table", None) is not None
+        if msa_outputs:
+            ruled["contigs"] = site_files[2]
         if histogram:
             # how many of the pairs the full run would write have each SNP distance (one GPU, counted on the device)
             for p in msas:
@@ -638,12 +726,14 @@ def distance(args):
             res = nearest_arrays(fasta=msas, k=nearest, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter, **ruled)
             if rule is not None:
                 _report_arrays(rule, args, msa, info)
+            _msa_outputs_fresh(msas, args, rule, site_files[2])
         elif ctx is None:
             info = {}
             ruled = rule.api_kwargs(info) if rule is not None else {}
             res = pairsnp_arrays(fasta=msas, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter, **ruled)
             if rule is not None:
                 _report_arrays(rule, args, msa, info)
+            _msa_outputs_fresh(msas, args, rule, site_files[2])
         else:
             res = _pairs_multi_gpu(msas, args, ctx)
         stage("pairsnp (total, incl. the copy of the result into numpy arrays)")

@@ -190,3 +190,36 @@ def first_record_length(path):
             elif seen:
                 n += len(line.strip())
     return n
+
+
+SITE_TABLE_HEADER = "contig,position,A,C,G,T,N,other,differs\n"
+
+
+def write_site_table(path, positions, counts, differs, contigs=None):
+    """--site-table: one row per kept column, in order -- contig,position,A,C,G,T,N,other,differs.  positions: the kept columns in
+    the coordinates of the files read (int array); counts: [6, K] (device.Alignment.site_census's rows); differs: bool[K].
+    contigs ([(name, length)]): contig coordinates as write_kept_bed gives them; without: contig 'alignment', alignment columns."""
+    positions = np.asarray(positions, dtype=np.int64)
+    counts = np.asarray(counts)
+    differs = np.asarray(differs, dtype=bool)
+    if counts.shape != (6, len(positions)) or differs.shape != (len(positions),):
+        raise ValueError("write_site_table: %d positions, counts %s, differs %s" % (len(positions), counts.shape, differs.shape))
+    if contigs is None:
+        pieces = [(ALIGNMENT_CONTIG, 0, len(positions), 0)]
+    else:
+        pieces, off = [], 0
+        for name, length in contigs:
+            lo, hi = np.searchsorted(positions, [off, off + int(length)])
+            if hi > lo:
+                pieces.append((name, int(lo), int(hi), off))
+            off += int(length)
+        if len(positions) and positions[-1] >= off:
+            raise ValueError("the alignment reaches column %d, past the reference's contigs (%d)" % (int(positions[-1]), off))
+    with open(path, "w") as fh:
+        fh.write(SITE_TABLE_HEADER)
+        step = 1 << 16
+        for name, lo, hi, off in pieces:
+            for b in range(lo, hi, step):
+                e = min(hi, b + step)
+                cols = [positions[b:e] - off] + [counts[c, b:e] for c in range(6)] + [differs[b:e].astype(np.int64)]
+                fh.write("".join("%s,%d,%d,%d,%d,%d,%d,%d,%d\n" % ((name,) + row) for row in zip(*[c.tolist() for c in cols])))
