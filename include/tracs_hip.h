@@ -372,6 +372,26 @@ int tracs_filter_recomb_device(const tracs_alignment *a, const uint32_t *rows, c
  * (d, count).  Synchronises the stream (an internal consistency check: every pair's SNP count must equal d[t]).            */
 int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const uint32_t *cols, const uint32_t *d, size_t n_pairs,
                               uint32_t *filt, void *stream);
+
+/* The SNP sites of listed pairs (csrc/pair_sites.hip): what tracs_pairsnp_dense counts and the filter sums, kept
+ * per site.  rows / cols: device uint32[n_pairs], sample indices in either order; a pair may repeat.  No distance is supplied.
+ *   tracs_pair_sites_count  d[t] (device uint32[n_pairs]) = the sites at which the two samples' allele sets are disjoint
+ *                           (src/pairsnp.hpp:398-403); off (device int64[n_pairs + 1]) = the exclusive scan of d; *total (host) =
+ *                           off[n_pairs].  An index >= n is refused (TRACS_E_ARG).  Synchronises the stream.
+ *   tracs_pair_sites_fill   the entries of pair t at site / info [off[t] - entry_base, off[t + 1] - entry_base) (device uint32, room
+ *                           entries each; nothing is stored outside [0, room)), ascending by site: site = the index into the packed
+ *                           alignment (the kept columns), info = the rows[t] sample's allele mask in bits 0-3 and the cols[t]
+ *                           sample's in bits 4-7 (A = 1, C = 2, G = 4, T = 8; neither is 15).  filter != 0: bit 8 is set on the SNPs
+ *                           filter_recomb drops (src/pairsnp.hpp:251-318: with d <= 1 none; else those whose window holds more than
+ *                           one SNP and has 1 - CDF < 0.05 / d), so the entries without it number tracs_filter_recomb_pairs' filt[t].
+ *                           A subrange of the pairs is filled by passing rows + t0, cols + t0, off + t0 and entry_base = off[t0].
+ * TRACS_PAIR_SITES_LANES_MIN (diagnostic): the number of pairs from which count and fill take a pair per lane instead of a wave per
+ * pair (default 16 384, as TRACS_FILTER_LANES_MIN).                                                                              */
+int tracs_pair_sites_count(const tracs_alignment *a, const uint32_t *rows, const uint32_t *cols, size_t n_pairs, uint32_t *d, int64_t *off,
+                           uint64_t *total, void *stream);
+int tracs_pair_sites_fill(const tracs_alignment *a, const uint32_t *rows, const uint32_t *cols, size_t n_pairs, const int64_t *off,
+                          int64_t entry_base, uint32_t *site, uint32_t *info, size_t room, int filter, void *stream);
+
 /* transcluster on device arrays (same math as tracs_trans_dist).  workspace is managed
  * internally (hipMallocAsync on the stream).  exp_p0 != 0 writes exp(p0) (what
  * tracs/transcluster.py:38-39 returns with log=False).                                     */
@@ -571,6 +591,23 @@ int tracs_distance_histogram(tracs_distance *h, int dist, int filter, const int3
 int tracs_distance_site_census(tracs_distance *h, uint32_t *counts_host, uint64_t *differs_host, size_t *n_differs);
 int tracs_distance_write_alignment(tracs_distance *h, const char *path, size_t sample_begin, size_t sample_end, int differing_only,
                                    int n_threads, int gzip_level, size_t *sites_written);
+/*   tracs_distance_alignment   the packed alignment the handle compares (the surviving samples, the kept columns); owned by the handle.
+ *   tracs_distance_pair_sites  `tracs pair-sites` (not in the reference): `path` is created and receives the header
+ *                         sampleA,sampleB,contig,position,alleleA,alleleB,dropped and one row per SNP site of every listed pair
+ *                         (rows / cols: HOST uint32[n_pairs], indices into tracs_distance_name), pairs in list order, sites
+ *                         ascending.  contig / position: the column in the coordinates of the files read (through the kept-columns
+ *                         bitmap), relative to its contig (names and lengths in file order; n_contigs = 0: contig "alignment");
+ *                         alleles: "XACMGRSVTWYHKDBN"[mask] of rows[t] and cols[t]; dropped: NA, or with filter != 0 the verdict of
+ *                         tracs_pair_sites_fill (1: dropped).  All pairs are counted first; a total above max_entries is refused
+ *                         with a message that states it, before the file is touched.  The entries then come in batches of pairs:
+ *                         two buffers (device, pinned host) of at most 256 MiB, or of one pair's entries when a pair has more
+ *                         (TRACS_PAIR_SITES_BATCH: entries per batch, diagnostic); fill, copy and formatting of a batch run one
+ *                         after another (nothing overlaps); rows are formatted on n_threads host threads
+ *                         (<= 0: up to 16).  *rows_written: the rows.                                                          */
+tracs_alignment *tracs_distance_alignment(tracs_distance *h);
+int tracs_distance_pair_sites(tracs_distance *h, const uint32_t *rows, const uint32_t *cols, size_t n_pairs, int filter, uint64_t max_entries,
+                              const char *path, const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs,
+                              int n_threads, uint64_t *rows_written);
 void tracs_distance_free(tracs_distance *h);
 
 /* Rows of `tracs distance`'s CSV appended to path (tracs/distance.py:206-258; the caller writes the header, :157):

@@ -2,7 +2,8 @@
 
 `distance` and `cluster` are the hot path; `combine` and `align-post` are the data formats either side of it (SURVEY.md 8f
 row 4: `align-post` is the part of `tracs align` after the pileup, tracs/align.py:444-647, with that command's option names);
-`threshold` fits the SNP cut-off between them, from two distance files or from the histogram `distance --histogram` counts.
+`threshold` fits the SNP cut-off between them, from two distance files or from the histogram `distance --histogram` counts;
+`pair-sites` lists the SNP sites, alleles and filter verdicts behind the pairs of a distance file.
 Read mapping (`align` proper), build-db/pipe/plot are outside the scope of this repository and are reported as such.
 """
 import argparse
@@ -49,7 +50,7 @@ def main():
     sub = parser.add_subparsers(title="subcommands", dest="command")
     # (a command's module is imported when that command -- or the help -- is asked for: `tracs distance` on ten isolates is 0.4 s, of
     # which the interpreter and the imports are most; the cluster command's numpy is not its business)
-    want = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ("distance", "cluster", "combine", "align-post", "threshold") else None
+    want = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] in ("distance", "cluster", "combine", "align-post", "threshold", "pair-sites") else None
 
     def register(name, get):
         if want is None or want == name:
@@ -69,7 +70,11 @@ def main():
     def _threshold():
         from .threshold import threshold_parser
         return threshold_parser
+    def _pair_sites():
+        from .pair_sites import pair_sites_parser
+        return pair_sites_parser
     register("distance", _distance)
+    register("pair-sites", _pair_sites)
     register("cluster", _cluster)
     register("combine", _combine)
     register("align-post", lambda: align_post_parser)

@@ -47,6 +47,7 @@ SYMBOLS = [
     "tracs_distance_source_name", "tracs_distance_source_n_count", "tracs_distance_source_kept", "tracs_distance_rule_sites",
     "tracs_alignment_site_census", "tracs_alignment_unpack", "tracs_write_fasta_rows", "tracs_distance_site_census",
     "tracs_distance_write_alignment",
+    "tracs_pair_sites_count", "tracs_pair_sites_fill", "tracs_distance_alignment", "tracs_distance_pair_sites",
     "tracs_distance_histogram", "tracs_hist_state_bytes", "tracs_hist_init", "tracs_hist_update", "tracs_hist_update_coo", "tracs_hist_emit",
 ]
 
@@ -404,6 +405,15 @@ def load():
     L.tracs_distance_site_census.argtypes = [vp, vp, u64p, C.POINTER(sz)]
     L.tracs_distance_write_alignment.restype = C.c_int
     L.tracs_distance_write_alignment.argtypes = [vp, C.c_char_p, sz, sz, C.c_int, C.c_int, C.c_int, C.POINTER(sz)]
+    L.tracs_pair_sites_count.restype = C.c_int
+    L.tracs_pair_sites_count.argtypes = [vp, vp, vp, sz, vp, vp, u64p, vp]
+    L.tracs_pair_sites_fill.restype = C.c_int
+    L.tracs_pair_sites_fill.argtypes = [vp, vp, vp, sz, vp, i64, vp, vp, sz, C.c_int, vp]
+    L.tracs_distance_alignment.restype = vp
+    L.tracs_distance_alignment.argtypes = [vp]
+    L.tracs_distance_pair_sites.restype = C.c_int
+    L.tracs_distance_pair_sites.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, C.c_int, C.c_uint64, C.c_char_p, cpp, u64p, sz,
+                                            C.c_int, u64p]
     L.tracs_debug_differs_table.restype = C.c_int
     L.tracs_debug_differs_table.argtypes = [vp, sz]
     _lib = L

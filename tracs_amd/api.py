@@ -217,6 +217,67 @@ def distance_histogram(fasta, dist=2147483647, filter=False, groups=None, sites=
     return names, out
 
 
+def pair_sites(fasta, pairs, filter=False, sites=None, info=None, max_sample_n_share=None, max_n_share=None):
+    """The SNP sites behind listed pairs -> (offsets int64[m + 1], site uint32[], info uint32[], names): pair t's
+    entries are [offsets[t], offsets[t + 1]), ascending by site; site indexes the compared alignment (the kept columns; info receives
+    "positions", their columns in the files read); info bits 0-3 / 4-7: the allele masks (A = 1, C = 2, G = 4, T = 8) of the pair's
+    first / second sample, bit 8 (filter only): the recombination filter drops the SNP.  pairs: [(a, b), ..], each a sample name or
+    an index into names (the surviving samples).  sites, max_sample_n_share, max_n_share, info: as pairsnp_arrays."""
+    import torch
+    from . import device as dev
+    from .sites import bitmap_to_bool
+    paths = _paths(fasta)
+    if len(paths) < 1 or len(paths) > 2:
+        raise RuntimeError("Invalid number of fasta files!")
+    for p in paths:
+        if not os.path.exists(p):
+            raise FileNotFoundError(os.fsdecode(p))
+    L = _lib.require_gpu()
+    arr = (C.c_char_p * len(paths))(*paths)
+    h = C.c_void_p()
+    rules, alive = _rules(sites, max_sample_n_share, max_n_share, None)
+    if rules is not None:
+        _lib.check(L.tracs_distance_open_rules(arr, len(paths), C.byref(rules), C.byref(h)))
+    elif sites is None:
+        _lib.check(L.tracs_distance_open(arr, len(paths), C.byref(h)))
+    else:
+        alive, kp, keep_len, max_n = _site_args(sites)
+        _lib.check(L.tracs_distance_open_sites(arr, len(paths), kp, keep_len, max_n, C.byref(h)))
+    try:
+        if rules is not None:
+            _source_info(L, h, "distance", info)
+        names = [L.tracs_distance_name(h, i).decode("utf-8", "replace") for i in range(L.tracs_distance_nseq(h))]
+        if info is not None:
+            info["seqlen"] = int(L.tracs_distance_len(h))
+            src_len = L.tracs_distance_source_len(h)
+            kept = np.zeros((src_len + 63) // 64, np.uint64)
+            _lib.check(L.tracs_distance_kept_sites(h, kept.ctypes.data_as(C.POINTER(C.c_uint64))))
+            info["positions"] = np.flatnonzero(bitmap_to_bool(kept, src_len))
+        index = {}
+        for i, name in enumerate(names):
+            index[name] = -1 if name in index else i
+
+        def resolve(x):
+            if isinstance(x, str):
+                if index.get(x, None) is None:
+                    raise ValueError("pair_sites(): sample '%s' is not among the samples of the run" % x)
+                if index[x] < 0:
+                    raise ValueError("pair_sites(): the name '%s' is carried by two samples" % x)
+                return index[x]
+            if not (0 <= int(x) < len(names)):
+                raise ValueError("pair_sites(): sample index %d is outside [0, %d)" % (int(x), len(names)))
+            return int(x)
+        idx = np.array([(resolve(a), resolve(b)) for a, b in pairs], np.int32).reshape(-1, 2)
+        aln = dev.Alignment.borrowed(L, L.tracs_distance_alignment(h))      # the handle's alignment: freed with the handle below
+        got = dev.pair_sites(aln, torch.from_numpy(np.ascontiguousarray(idx[:, 0])).cuda(),
+                             torch.from_numpy(np.ascontiguousarray(idx[:, 1])).cuda(), filter=filter)
+        off, site, bits = (t.cpu().numpy() for t in got)
+        aln.close()
+    finally:
+        L.tracs_distance_free(h)
+    return off, site.view(np.uint32), bits.view(np.uint32), names
+
+
 def _result_arrays(L, h):
     """(rows, cols, distances, names, filt_distances, n_compared) of a tracs_pairsnp_result, which they then own."""
     owner = _ResultOwner(L, h)

@@ -837,6 +837,19 @@ int tracs_distance_write_alignment(tracs_distance *h, const char *path, size_t s
     return done(TRACS_OK);
 }
 
+// ---- the sites behind listed pairs (csrc/pair_sites.hip) --------------------------------------------------------------
+tracs_alignment *tracs_distance_alignment(tracs_distance *h) { return h ? h->a : nullptr; }
+
+int tracs_distance_pair_sites(tracs_distance *h, const uint32_t *rows, const uint32_t *cols, size_t n_pairs, int filter, uint64_t max_entries,
+                              const char *path, const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs,
+                              int n_threads, uint64_t *rows_written)
+{
+    if (rows_written) *rows_written = 0;
+    if (!h || !h->a) { set_error("tracs_distance_pair_sites: NULL argument"); return TRACS_E_ARG; }
+    return pair_sites_write(h->a, h->name_ptr.data(), h->kept.empty() ? nullptr : h->kept.data(), h->source_len, rows, cols, n_pairs, filter,
+                            max_entries, path, contig_names, contig_lengths, n_contigs, n_threads, rows_written);
+}
+
 // the date difference of every emitted pair, as tracs/transcluster.py:26-33 takes it: |t_i - t_j| / 31556952.0 with t = whole days in seconds
 __global__ __launch_bounds__(256) void coo_delta_kernel(const unsigned *__restrict__ rows, const unsigned *__restrict__ cols, const int *__restrict__ days,
                                                         size_t n, double *__restrict__ out)

@@ -131,6 +131,12 @@ int pairs_min_sites(uint32_t *dist, const uint32_t *ncomp, size_t ld, size_t n, 
 int site_census(const tracs_alignment *a, uint32_t *counts, uint64_t *differs, size_t *n_differs, hipStream_t stream);
 int unpack_rows(const tracs_alignment *a, size_t first, size_t count, uint8_t *ascii, size_t stride, hipStream_t stream);
 
+// pair_sites.hip: the SNP sites of listed pairs (tracs_pair_sites_count / _fill) and the rows of `tracs pair-sites`
+// (tracs_distance_pair_sites: names of the handle's samples, its kept-columns bitmap or NULL, the columns read)
+int pair_sites_write(const tracs_alignment *a, const char *const *names, const uint64_t *kept, size_t source_len, const uint32_t *rows,
+                     const uint32_t *cols, size_t n_pairs, int filter, uint64_t max_entries, const char *path, const char *const *contig_names,
+                     const uint64_t *contig_lengths, size_t n_contigs, int n_threads, uint64_t *rows_written);
+
 // device memory that lives until the alignment is packed again (site_classes_free releases all of it at once)
 hipError_t pack_alloc(tracs_alignment *a, size_t bytes, void **out);
 void pack_release(tracs_alignment *a);

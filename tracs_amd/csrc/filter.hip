@@ -15,6 +15,7 @@
 // definition at 50 digits on crafted boundary pairs (tests/test_gpu_filter_hp.py).
 #include "common.h"
 #include "filter_math.h"
+#include "scan_kernels.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -189,53 +190,6 @@ static int filter_scan_launch(const tracs_alignment *a, const unsigned *rows, co
     return TRACS_OK;
 }
 
-// pos_off of a batch on the device: exclusive scan of d[0 .. n) in three launches (tiles of 1 024)
-__global__ __launch_bounds__(256) void filter_tile_sums_kernel(const unsigned *__restrict__ d, size_t n, unsigned long long *__restrict__ sums)
-{
-    __shared__ unsigned long long part[4];
-    const size_t base = (size_t)blockIdx.x * 1024;
-    unsigned long long s = 0;
-    for (int k = 0; k < 4; k++) { const size_t t = base + (size_t)k * 256 + threadIdx.x; if (t < n) s += d[t]; }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
-}
-__global__ __launch_bounds__(1024) void filter_scan_sums_kernel(unsigned long long *__restrict__ sums, size_t tiles)
-{
-    __shared__ unsigned long long part[1024];
-    const size_t per = (tiles + 1023) / 1024, b = std::min(tiles, (size_t)threadIdx.x * per), e = std::min(tiles, b + per);
-    unsigned long long s = 0;
-    for (size_t k = b; k < e; k++) s += sums[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (unsigned st = 1; st < 1024; st <<= 1) {
-        const unsigned long long v = threadIdx.x >= st ? part[threadIdx.x - st] : 0ull;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    unsigned long long run = part[threadIdx.x] - s;
-    for (size_t k = b; k < e; k++) { const unsigned long long v = sums[k]; sums[k] = run; run += v; }
-}
-__global__ __launch_bounds__(256) void filter_offsets_kernel(const unsigned *__restrict__ d, size_t n, const unsigned long long *__restrict__ sums,
-                                                             long long *__restrict__ off)
-{
-    __shared__ unsigned long long wsum[4];
-    const size_t base = (size_t)blockIdx.x * 1024 + (size_t)threadIdx.x * 4;
-    unsigned v[4];
-    unsigned long long s = 0;
-    for (int k = 0; k < 4; k++) { v[k] = base + k < n ? d[base + k] : 0u; s += v[k]; }
-    unsigned long long incl = s;
-    const int lane = threadIdx.x & 63;
-    for (int o = 1; o < 64; o <<= 1) { const unsigned long long x = __shfl_up(incl, o, 64); if (lane >= o) incl += x; }
-    if (lane == 63) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    unsigned long long run = sums[blockIdx.x] + incl - s;
-    for (unsigned w = 0; w < (threadIdx.x >> 6); w++) run += wsum[w];
-    // (n + 1 offsets: index n takes the total)
-    for (int k = 0; k < 4; k++) { if (base + k <= n) off[base + k] = (long long)run; run += v[k]; }
-}
 __global__ __launch_bounds__(256) void filter_found_check_kernel(const unsigned *__restrict__ found, const unsigned *__restrict__ d, size_t n,
                                                                  unsigned *__restrict__ bad)
 {
@@ -265,15 +219,10 @@ int filter_scan_route(const tracs_alignment *a, const unsigned *rows, const unsi
     if ((rc = workspace_get(ScanWs::POS, (pos_cap + 64) * 4, reinterpret_cast<void **>(&pos))) ||
         (rc = workspace_get(ScanWs::FOUND, per * 4, reinterpret_cast<void **>(&found))) ||
         (rc = workspace_get(ScanWs::OFF, (per + 1) * 8, reinterpret_cast<void **>(&off))) ||
-        (rc = workspace_get(ScanWs::SUMS, ((per + 1023) / 1024 + 1) * 8, reinterpret_cast<void **>(&sums)))) return rc;
+        (rc = workspace_get(ScanWs::SUMS, offsets_scan_sums(per) * 8, reinterpret_cast<void **>(&sums)))) return rc;
     for (size_t t0 = 0; t0 < n_pairs; t0 += per) {
-        const size_t np = std::min(per, n_pairs - t0), tiles = (np + 1023) / 1024;
-        // (np + 1 offsets: the tile that holds index np writes off[np]; when np is a multiple of 1 024 that is one tile more)
-        const size_t otiles = np / 1024 + 1;
-        TRACS_HIP_CHECK(hipMemsetAsync(sums, 0, (otiles + 1) * 8, stream));
-        hipLaunchKernelGGL(filter_tile_sums_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, d + t0, np, sums);
-        hipLaunchKernelGGL(filter_scan_sums_kernel, dim3(1), dim3(1024), 0, stream, sums, otiles);
-        hipLaunchKernelGGL(filter_offsets_kernel, dim3((unsigned)otiles), dim3(256), 0, stream, d + t0, np, sums, off);
+        const size_t np = std::min(per, n_pairs - t0);
+        if ((rc = offsets_scan_launch(d + t0, np, sums, off, stream))) return rc;
         if ((rc = filter_scan_launch(a, rows + t0, cols + t0, np, off, pos, found, filt + t0, tbl, tbl_state, lg, stream))) return rc;
         hipLaunchKernelGGL(filter_found_check_kernel, dim3((unsigned)std::min<size_t>((np + 255) / 256, 4096)), dim3(256), 0, stream, found,
                            d + t0, np, bad);

@@ -53,6 +53,14 @@ class Alignment:
         self.n_first = n0.value
         return self
 
+    @classmethod
+    def borrowed(cls, lib, handle):
+        """A view of a tracs_alignment that another handle owns (tracs_distance_alignment): close() and __del__ leave it alone."""
+        self = cls.__new__(cls)
+        self._L, self._h, self._borrowed = lib, C.c_void_p(handle), True
+        self.n, self.L = lib.tracs_alignment_n(self._h), lib.tracs_alignment_len(self._h)
+        return self
+
     def pack(self, ascii_u8, first=0):
         """ascii_u8: torch.uint8 [count, L] on the GPU, or a numpy uint8 array on the host."""
         if isinstance(ascii_u8, torch.Tensor):
@@ -237,7 +245,8 @@ class Alignment:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.tracs_alignment_free(self._h)
+            if not getattr(self, "_borrowed", False):
+                self._L.tracs_alignment_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -507,6 +516,30 @@ def filter_recomb_pairs(aln, rows, cols, d):
     if n:
         _lib.check(L.tracs_filter_recomb_pairs(aln._h, _ptr(rows), _ptr(cols), _ptr(d), n, _ptr(filt), _stream()))
     return filt[:n]
+
+
+def pair_sites(aln, rows, cols, filter=False):
+    """The SNP sites of the listed pairs (rows, cols: 32-bit device vectors of sample indices, either order, repeats allowed) ->
+    (offsets torch.int64 [m + 1], site, info torch.int32) on the device: pair t's entries are [offsets[t], offsets[t + 1]), ascending
+    by site -- the sites at which the two samples' allele sets are disjoint, so their number is the pair's SNP distance.  info: bits
+    0-3 the rows[t] sample's allele mask, bits 4-7 the cols[t] sample's (A = 1, C = 2, G = 4, T = 8); with filter, bit 8 is set on
+    the SNPs the recombination filter drops.  tracs_pair_sites_count / _fill (csrc/pair_sites.hip)."""
+    L = _lib.require_gpu()
+    m = int(rows.numel())
+    assert cols.numel() == m
+    for t in (rows, cols):
+        assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and not t.is_floating_point()
+    d = torch.empty(max(m, 1), dtype=torch.int32, device=rows.device)
+    off = torch.empty(m + 1, dtype=torch.int64, device=rows.device)
+    total = C.c_uint64(0)
+    _lib.check(L.tracs_pair_sites_count(aln._h, _ptr(rows), _ptr(cols), m, _ptr(d), _ptr(off), C.byref(total), _stream()))
+    k = int(total.value)
+    site = torch.empty(max(k, 1), dtype=torch.int32, device=rows.device)
+    info = torch.empty(max(k, 1), dtype=torch.int32, device=rows.device)
+    if k:
+        _lib.check(L.tracs_pair_sites_fill(aln._h, _ptr(rows), _ptr(cols), m, _ptr(off), 0, _ptr(site), _ptr(info), k, int(bool(filter)),
+                                           _stream()))
+    return off, site[:k], info[:k]
 
 
 def filter_index_info(aln):

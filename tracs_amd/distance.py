@@ -41,6 +41,28 @@ HEADER = ("sampleA,sampleB,date difference,SNP distance,transmission distance,ex
           "filtered SNP distance,sites considered,MSA file\n")
 
 
+def add_site_rule_options(st):
+    """--mask, --keep, --mask-reference and --max-n-share: the site rules that `distance` and `pair-sites` share"""
+    st.add_argument("--mask", dest="mask_bed", default=None, type=os.path.abspath, metavar="BED",
+                    help="Columns to drop (BED: 0-based, half-open; alignment columns, or contig coordinates with --mask-reference)")
+    st.add_argument("--keep", dest="keep_bed", default=None, type=os.path.abspath, metavar="BED",
+                    help="Only these columns may stay.  Together with --mask: keep minus mask.")
+    st.add_argument("--mask-reference", dest="mask_reference", default=None, type=os.path.abspath, metavar="REF.fa",
+                    help="The reference genome the alignments were made against: contig names and offsets for --mask and --keep "
+                         "(columns are its contigs concatenated in file order)")
+    st.add_argument("--max-n-share", dest="max_n_share", default=None, type=float, metavar="F",
+                    help="Drop a column when more than floor(F n) of the n samples are N there (0 <= F < 1; with --msa-db: the "
+                         "samples of both files)")
+
+
+def add_sample_rule_options(sm):
+    """--max-sample-n-share: the sample rule that `distance` and `pair-sites` share"""
+    sm.add_argument("--max-sample-n-share", dest="max_sample_n_share", default=None, type=float, metavar="G",
+                    help="Leave out a sample when more than floor(G L') of the L' columns that --mask / --keep leave are N in it "
+                         "(0 <= G <= 1; 1 drops nothing and only reports; with --msa-db: applied to both files).  --max-n-share then "
+                         "counts over the remaining samples.  A left-out sample needs no date in --meta.")
+
+
 def distance_parser(parser):
     parser.description = ("Estimates pairwise SNP and transmission distances between each pair of samples "
                           "aligned to the same reference genome.")
@@ -81,25 +103,13 @@ def distance_parser(parser):
     st = parser.add_argument_group("Site selection",
                                    "A run with a site rule is the run on the alignment with the dropped columns deleted from every "
                                    "record (applied to the packed alignment on the GPU; not in the reference).")
-    st.add_argument("--mask", dest="mask_bed", default=None, type=os.path.abspath, metavar="BED",
-                    help="Columns to drop (BED: 0-based, half-open; alignment columns, or contig coordinates with --mask-reference)")
-    st.add_argument("--keep", dest="keep_bed", default=None, type=os.path.abspath, metavar="BED",
-                    help="Only these columns may stay.  Together with --mask: keep minus mask.")
-    st.add_argument("--mask-reference", dest="mask_reference", default=None, type=os.path.abspath, metavar="REF.fa",
-                    help="The reference genome the alignments were made against: contig names and offsets for --mask and --keep "
-                         "(columns are its contigs concatenated in file order)")
-    st.add_argument("--max-n-share", dest="max_n_share", default=None, type=float, metavar="F",
-                    help="Drop a column when more than floor(F n) of the n samples are N there (0 <= F < 1; with --msa-db: the "
-                         "samples of both files)")
+    add_site_rule_options(st)
     st.add_argument("--sites-out", dest="sites_out", default=None, type=str, metavar="FILE",
                     help="Write the kept columns as a BED (readable back through --keep; contig coordinates with --mask-reference)")
     sm = parser.add_argument_group("Sample and pair selection",
                                    "A run with the sample rule is the run on the FASTA file(s) with the dropped records deleted; the pair "
                                    "rule removes pairs from what the run would write (both applied on the GPU; not in the reference).")
-    sm.add_argument("--max-sample-n-share", dest="max_sample_n_share", default=None, type=float, metavar="G",
-                    help="Leave out a sample when more than floor(G L') of the L' columns that --mask / --keep leave are N in it "
-                         "(0 <= G <= 1; 1 drops nothing and only reports; with --msa-db: applied to both files).  --max-n-share then "
-                         "counts over the remaining samples.  A left-out sample needs no date in --meta.")
+    add_sample_rule_options(sm)
     sm.add_argument("--min-sites", dest="min_sites", default=None, type=int, metavar="M",
                     help="Only pairs compared over at least M sites (the `sites considered` column, after the site rules) are eligible: "
                          "for the full output, --nearest, --mst and --histogram alike")
