@@ -333,6 +333,33 @@ int tracs_msf_update_coo(void *state, size_t n, size_t m, const uint32_t *rows, 
 int tracs_msf_emit(void *state, size_t n, size_t *n_edges, uint32_t *rows, uint32_t *cols, uint32_t *d, uint32_t *nn, uint32_t *filt,
                    double *p, double *e, void *stream);
 
+/* Each vertex's most likely earlier source among the offered pairs (csrc/ancestors.hip; what tracs_distance_ancestors runs; DESIGN.md
+ * 3.16).  Vertex s has the day days[s]; vertex a is a candidate source of s when {a, s} is an offered, eligible pair and
+ * days[a] < days[s], strictly.  The chosen source is the smallest candidate under (value key, days[s] - days[a], a): a total order, so
+ * the result is independent of how the pairs are split into updates.  A vertex without a candidate is a root.  The state is a device
+ * buffer of tracs_anc_state_bytes(n) bytes for the vertices [0, n): the days, per vertex the running best keys and the winning pair
+ * with the values its row is written with (d, nn, filtered d, P, E(K)), and scratch for emit.
+ *   tracs_anc_init        no pair offered yet; days_device: device int32[n] (days since 1970-01-01, negative ones too), copied
+ *   tracs_anc_update_coo  offer m pairs (rows[t], cols[t]) (device uint32, either order; an endpoint >= n, a loop or a pair with equal
+ *                         days is skipped) with value[t] (device; value_kind 0: uint32 ascending; 1: double ascending, -0.0 == +0.0,
+ *                         every NaN above +inf; 2: double DESCENDING, -0.0 == +0.0, every NaN after -inf); e_mask != NULL: only pairs
+ *                         with e_max >= e_mask[t] are eligible (a NaN fails); d / nn / filt / p / e (device, any may be NULL: stored
+ *                         as 0) are the values kept with a pair.  Every pair is offered at most once over the updates of one state.
+ *                         n_taken (host, optional): the candidates offered -- the batch's eligible pairs with unequal days; reading
+ *                         it synchronises the stream.  Five stream-ordered launches, one atomic target per pair.
+ *   tracs_anc_emit        *n_links <- the number of vertices with a source; unless NULL, rows < cols, d, nn, filt (device uint32) and
+ *                         p, e (device double), room for n - 1 entries, receive the links in (i, j) order; unless NULL, parent, root
+ *                         and generation (device uint32[n]) receive per vertex its source (0xFFFFFFFF for a root), the vertex reached
+ *                         by following sources, and the number of links to it (pointer doubling, ceil(log2 n) rounds).  Synchronises
+ *                         the stream.                                                                                            */
+size_t tracs_anc_state_bytes(size_t n);
+int tracs_anc_init(void *state, size_t n, const int32_t *days_device, void *stream);
+int tracs_anc_update_coo(void *state, size_t n, size_t m, const uint32_t *rows, const uint32_t *cols, const void *value, int value_kind,
+                         const double *e_mask, double e_max, const uint32_t *d, const uint32_t *nn, const uint32_t *filt,
+                         const double *p, const double *e, uint64_t *n_taken, void *stream);
+int tracs_anc_emit(void *state, size_t n, size_t *n_links, uint32_t *rows, uint32_t *cols, uint32_t *d, uint32_t *nn, uint32_t *filt,
+                   double *p, double *e, uint32_t *parent, uint32_t *root, uint32_t *generation, void *stream);
+
 /* Histogram of pair values over dense panels (csrc/histogram.hip; what tracs_distance_histogram runs).  The state is
  * a device buffer of tracs_hist_state_bytes(n_bins) bytes: per value v in [0, n_bins) three 64-bit counts -- pairs `within` a group
  * (both samples grouped, equal labels), `between` groups (both grouped, labels differ) and `ungrouped` (a sample with label < 0, or
@@ -570,6 +597,18 @@ int tracs_distance_run(tracs_distance *h, int dist, const int32_t *days, double 
  *                         `path`, in (i, j) order, each row byte-identical to tracs_distance_run's.  n_eligible: the eligible pairs. */
 int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
                           int filter, int weight, const char *path, const char *ref, uint64_t *rows_written, uint64_t *n_eligible);
+/*   tracs_distance_ancestors `--ancestors WEIGHT` (not in the reference): tracs_distance_forest's panel loop with
+ *                         tracs_anc_update_coo in place of the forest update.  days (HOST int32[n], required) order the samples; each
+ *                         sample's source is chosen among the pairs tracs_distance_run would write, under weight 0: d, 1: the
+ *                         filtered d (filter != 0), 3: E(K), all ascending, or 2: P(direct) DESCENDING (the likeliest source first;
+ *                         tracs_distance_forest's weight 2 is ascending).  The chosen pairs' rows are appended to `path` in (i, j)
+ *                         order, each byte-identical to tracs_distance_run's.  tree_path != NULL: one line per sample is appended to
+ *                         it, in order: sample,date,ancestor,ancestor date,root,generation,ref -- meta_dates[s] (n strings, required
+ *                         then) is sample s's date as text; a root has empty ancestor fields, itself as root and generation 0.
+ *                         n_eligible: the candidates offered (eligible pairs with unequal days).                                */
+int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
+                             int filter, int weight, const char *path, const char *ref, const char *tree_path,
+                             const char *const *meta_dates, uint64_t *rows_written, uint64_t *n_eligible);
 /*   tracs_distance_histogram `--histogram` (not in the reference): tracs_distance_run's panel loop without rows.  The
  *                         pairs it would write (d <= dist) are counted by SNP distance and class (tracs_hist_*; group: HOST int32[n]
  *                         in the order of tracs_distance_name, label < 0: ungrouped; NULL: every pair ungrouped) in min(L, dist) + 1

@@ -49,6 +49,7 @@ SYMBOLS = [
     "tracs_distance_write_alignment",
     "tracs_pair_sites_count", "tracs_pair_sites_fill", "tracs_distance_alignment", "tracs_distance_pair_sites",
     "tracs_distance_histogram", "tracs_hist_state_bytes", "tracs_hist_init", "tracs_hist_update", "tracs_hist_update_coo", "tracs_hist_emit",
+    "tracs_distance_ancestors", "tracs_anc_state_bytes", "tracs_anc_init", "tracs_anc_update_coo", "tracs_anc_emit",
 ]
 
 
@@ -182,6 +183,17 @@ def load():
     L.tracs_msf_update_coo.argtypes = [vp, sz, sz, vp, vp, vp, C.c_int, vp, dbl, vp, vp, vp, vp, vp, u64p, vp]
     L.tracs_msf_emit.restype = C.c_int
     L.tracs_msf_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tracs_distance_ancestors.restype = C.c_int
+    L.tracs_distance_ancestors.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dbl, dbl, dbl, dbl, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
+                                           C.c_char_p, C.POINTER(C.c_char_p), u64p, u64p]
+    L.tracs_anc_state_bytes.restype = sz
+    L.tracs_anc_state_bytes.argtypes = [sz]
+    L.tracs_anc_init.restype = C.c_int
+    L.tracs_anc_init.argtypes = [vp, sz, vp, vp]
+    L.tracs_anc_update_coo.restype = C.c_int
+    L.tracs_anc_update_coo.argtypes = [vp, sz, sz, vp, vp, vp, C.c_int, vp, dbl, vp, vp, vp, vp, vp, u64p, vp]
+    L.tracs_anc_emit.restype = C.c_int
+    L.tracs_anc_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tracs_distance_histogram.restype = C.c_int
     L.tracs_distance_histogram.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_char_p, C.c_char_p, u64p, u64p]
     L.tracs_hist_state_bytes.restype = sz

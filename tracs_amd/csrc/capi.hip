@@ -1152,6 +1152,147 @@ int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, doub
     return rc;
 }
 
+// `tracs distance --ancestors WEIGHT` for one alignment (include/tracs_hip.h): the panel loop of tracs_distance_forest
+// with tracs_anc_update_coo instead of the forest update; after the last panel the links are emitted and written through the same row
+// writer, and the tree file is written from parent / root / generation.
+int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
+                             int filter, int weight, const char *path, const char *ref, const char *tree_path,
+                             const char *const *meta_dates, uint64_t *rows_written, uint64_t *n_eligible)
+{
+    if (rows_written) *rows_written = 0;
+    if (n_eligible) *n_eligible = 0;
+    if (!h || !h->a || !path || !ref) { set_error("tracs_distance_ancestors: NULL argument"); return TRACS_E_ARG; }
+    if (weight < 0 || weight > 3) { set_error("tracs_distance_ancestors: weight must be 0 (snp), 1 (filter), 2 (direct) or 3 (expectedK)"); return TRACS_E_ARG; }
+    if (weight == 1 && !filter) { set_error("tracs_distance_ancestors: the filter weight needs filter != 0"); return TRACS_E_ARG; }
+    if (!days) { set_error("tracs_distance_ancestors: sampling dates are required (they order the samples)"); return TRACS_E_ARG; }
+    if (tree_path && !meta_dates) { set_error("tracs_distance_ancestors: the tree file needs the samples' dates as text"); return TRACS_E_ARG; }
+    SigintScope sigint;
+    tracs_alignment *a = h->a;
+    const size_t n = a->n;
+    const size_t i_end = h->n_fasta == 1 ? n : h->n0;               // pair ranges (:348-360)
+    const size_t j_start = h->n_fasta == 1 ? 0 : h->n0;
+    const bool dense_tc = !filter;
+    // rows per panel (TRACS_FOREST_PANEL_ROWS: diagnostics -- small panels in tests, as tracs_distance_forest)
+    static const size_t PANEL_ROWS = [] { const char *e = std::getenv("TRACS_FOREST_PANEL_ROWS"); const long long v = e ? std::atoll(e) : 0; return v >= 1 ? (size_t)v : (size_t)0; }();
+    unsigned *d_dist = nullptr, *d_nn = nullptr, *d_coo = nullptr, *d_tree = nullptr;
+    double *d_p = nullptr, *d_e = nullptr, *d_cp = nullptr;
+    int *d_days = nullptr;
+    long long *d_off = nullptr;
+    void *d_state = nullptr;
+    tracs::DistanceRowWriter writer;
+    auto cleanup = [&]() {
+        void *q[] = {d_dist, d_nn, d_coo, d_tree, d_p, d_e, d_cp, d_days, d_off, d_state};
+        for (void *x : q) if (x) (void)hipFree(x);
+    };
+#define AN_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
+#define AN_RC(x) do { int r__ = (x); if (r__) { cleanup(); return r__; } } while (0)
+    AN_RC(writer.open(path, h->name_ptr.data(), h->name_ptr.size(), ref));
+    StageClock clock;
+    uint64_t eligible = 0;
+    const double e_max = k_max >= 0.0 ? k_max : -1.0;
+    std::vector<uint32_t> tree(n * 3);                              // parent, root, generation
+    for (size_t s = 0; s < n; s++) { tree[s] = 0xFFFFFFFFu; tree[n + s] = (uint32_t)s; tree[2 * n + s] = 0; }      // (no pair at all: every sample a root)
+    if (n >= 2 && i_end > 0 && j_start < n) {
+        const size_t panel = PANEL_ROWS ? std::min(PANEL_ROWS, i_end)
+                                        : std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
+        AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_days), n * 4));
+        AN_CHECK(hipMemcpy(d_days, days, n * 4, hipMemcpyHostToDevice));
+        AN_CHECK(hipMalloc(&d_state, tracs_anc_state_bytes(n)));
+        AN_RC(tracs_anc_init(d_state, n, d_days, nullptr));
+        AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dist), panel * n * 4));
+        AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_nn), panel * n * 4));
+        AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_off), (panel + 1) * 8));
+        if (dense_tc) {
+            AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_p), panel * n * 8));
+            AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_e), panel * n * 8));
+        }
+        const size_t n32 = filter ? 5 : 4;
+        size_t cap = 0;
+        for (size_t r0 = 0; r0 < i_end; r0 += panel) {
+            if (g_sigint) { cleanup(); set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+            const size_t r1 = std::min(i_end, r0 + panel);
+            unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
+            double *bp = dense_tc ? d_p - r0 * n : nullptr, *be = dense_tc ? d_e - r0 * n : nullptr;
+            AN_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
+            if (h->min_sites) AN_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, h->min_sites, nullptr));
+            if (dense_tc)
+                AN_RC(tracs_trans_dist_dense(bd, n, n, r0, r1, j_start, dist, d_days, lamb, beta, precision, 1, bp, be, nullptr));
+            AN_RC(tracs_coo_count(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), nullptr));
+            long long total = 0;
+            AN_CHECK(hipMemcpy(&total, d_off + (r1 - r0), 8, hipMemcpyDeviceToHost));
+            if (total <= 0) continue;
+            if ((size_t)total > cap) {
+                if (d_coo) AN_CHECK(hipFree(d_coo));
+                if (d_cp) AN_CHECK(hipFree(d_cp));
+                d_coo = nullptr; d_cp = nullptr;
+                cap = (size_t)total;
+                AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_coo), cap * 4 * n32));
+                AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cp), cap * (filter ? 24 : 16)));
+            }
+            unsigned *c_rows = d_coo, *c_cols = d_coo + cap, *c_d = d_coo + 2 * cap, *c_n = d_coo + 3 * cap, *c_f = filter ? d_coo + 4 * cap : nullptr;
+            double *c_p = d_cp, *c_e = d_cp + cap, *c_delta = filter ? d_cp + 2 * cap : nullptr;
+            AN_RC(tracs_coo_fill(bd, bn, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), c_rows, c_cols, c_d, c_n, nullptr));
+            if (dense_tc)
+                AN_RC(tracs_coo_fill_f64(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), bp, be, c_p, c_e, nullptr));
+            if (filter) {
+                AN_RC(tracs_filter_recomb_pairs(a, c_rows, c_cols, c_d, (size_t)total, c_f, nullptr));
+                hipLaunchKernelGGL(coo_delta_kernel, dim3((unsigned)std::min<size_t>(((size_t)total + 255) / 256, 65535)), dim3(256), 0, nullptr, c_rows, c_cols,
+                                   d_days, (size_t)total, c_delta);
+                AN_RC(tracs_trans_dist_device(reinterpret_cast<const int32_t *>(c_f), c_delta, (size_t)total, lamb, beta, precision, 1, c_p, c_e, nullptr));
+            }
+            // the value a source is chosen by: d, filtered d and E(K) ascending, P(direct) descending; -K drops pairs with E(K) above it or NaN
+            const void *wv = weight == 0 ? (const void *)c_d : weight == 1 ? (const void *)c_f : weight == 2 ? (const void *)c_p : (const void *)c_e;
+            uint64_t taken = 0;
+            AN_RC(tracs_anc_update_coo(d_state, n, (size_t)total, c_rows, c_cols, wv, weight == 2 ? 2 : weight == 3 ? 1 : 0,
+                                       e_max >= 0.0 ? c_e : nullptr, e_max, c_d, c_n, c_f, c_p, c_e, &taken, nullptr));
+            eligible += taken;
+        }
+        clock.mark("dense panels + transcluster + ancestor updates");
+        size_t nl = 0;
+        AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_tree), n * 12));
+        AN_RC(tracs_anc_emit(d_state, n, &nl, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_tree, d_tree + n, d_tree + 2 * n, nullptr));
+        AN_CHECK(hipMemcpy(tree.data(), d_tree, n * 12, hipMemcpyDeviceToHost));
+        if (nl) {
+            // the links' rows: rows, cols, d, nn, filt (uint32), P, E(K) (f64) -- < n of them
+            if (d_coo) AN_CHECK(hipFree(d_coo));
+            if (d_cp) AN_CHECK(hipFree(d_cp));
+            d_coo = nullptr; d_cp = nullptr;
+            AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_coo), nl * 4 * 5));
+            AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cp), nl * 16));
+            AN_RC(tracs_anc_emit(d_state, n, &nl, d_coo, d_coo + nl, d_coo + 2 * nl, d_coo + 3 * nl, d_coo + 4 * nl, d_cp, d_cp + nl, nullptr, nullptr,
+                                 nullptr, nullptr));
+            std::vector<uint32_t> h32(nl * 5);
+            std::vector<double> h64(nl * 2);
+            AN_CHECK(hipMemcpy(h32.data(), d_coo, nl * 20, hipMemcpyDeviceToHost));
+            AN_CHECK(hipMemcpy(h64.data(), d_cp, nl * 16, hipMemcpyDeviceToHost));
+            const uint32_t *hr = h32.data(), *hc = hr + nl, *hd = hr + 2 * nl, *hn = hr + 3 * nl, *hf = hr + 4 * nl;
+            // the filtered column as the full run writes it with metadata: --filter: the filtered distances; else "NA" (:204)
+            AN_RC(writer.append_u32(hr, hc, hd, filter ? hf : nullptr, hn, days, h64.data(), h64.data() + nl, nl, 1, -1.0));
+        }
+        clock.mark("ancestor rows: emit, device -> host, format, write");
+    }
+#undef AN_CHECK
+#undef AN_RC
+    cleanup();
+    int rc = writer.close();
+    if (rows_written) *rows_written = writer.written();
+    if (n_eligible) *n_eligible = eligible;
+    if (g_sigint) { set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+    if (rc == TRACS_OK && tree_path) {
+        // one line per sample, in order, from parent / root / generation
+        std::FILE *fh = std::fopen(tree_path, "ab");
+        if (!fh) { set_error(std::string("tracs_distance_ancestors: cannot open ") + tree_path); return TRACS_E_OPEN; }
+        for (size_t s = 0; s < n; s++) {
+            const uint32_t pa = tree[s], ro = tree[n + s];
+            const bool link = pa != 0xFFFFFFFFu && pa < n;
+            std::fprintf(fh, "%s,%s,%s,%s,%s,%u,%s\n", h->name_ptr[s], meta_dates[s] ? meta_dates[s] : "", link ? h->name_ptr[pa] : "",
+                         link && meta_dates[pa] ? meta_dates[pa] : "", h->name_ptr[ro < n ? ro : s], (unsigned)tree[2 * n + s], ref);
+        }
+        if (std::fclose(fh) != 0) { set_error(std::string("tracs_distance_ancestors: write failed: ") + tree_path); return TRACS_E_OPEN; }
+    }
+    return rc;
+}
+
 // `tracs distance --histogram` for one alignment (include/tracs_hip.h): the panel loop of tracs_distance_run with
 // tracs_hist_update on each dense panel instead of the rows; with --filter the panel's pairs within the threshold are extracted and
 // filtered as tracs_distance_run does, and a second state counts their filtered distances.  What crosses to the host is the

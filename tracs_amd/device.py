@@ -414,6 +414,55 @@ def msf_emit(state, n):
     return [t[:k] for t in u + f]
 
 
+def anc_init(n, days, device=None):
+    """A state without any offered pair for the vertices [0, n) (tracs_anc_init): a torch.uint8 device buffer.  days: torch.int32
+    device tensor of n sampling days (days since 1970-01-01; copied into the state)."""
+    L = _lib.require_gpu()
+    assert days.dtype == torch.int32 and days.is_contiguous() and days.numel() == int(n)
+    state = torch.empty(max(L.tracs_anc_state_bytes(int(n)), 1), dtype=torch.uint8, device=device if device is not None else days.device)
+    _lib.check(L.tracs_anc_init(_ptr(state), int(n), _ptr(days), _stream()))
+    return state
+
+
+def anc_update(state, n, rows, cols, value, descending=False, e_mask=None, e_max=-1.0, d=None, nn=None, filt=None, p=None, e=None):
+    """Offer a batch of pairs to every later-dated endpoint (tracs_anc_update_coo): rows / cols int32 or uint32 device tensors, value
+    uint32-valued (int32 / uint32 tensor, read as unsigned, ascending) or float64 (ascending, or descending=True); e_mask (float64):
+    only pairs with e_max >= e_mask are eligible.  d, nn, filt (32-bit) and p, e (float64) are the values kept with a pair.  -> the
+    candidates offered (the batch's eligible pairs with unequal days)."""
+    L = _lib.require_gpu()
+    m = int(rows.numel())
+    assert cols.numel() == m and value.numel() == m
+    for t in (rows, cols, value, e_mask, d, nn, filt, p, e):
+        assert t is None or (t.is_contiguous() and t.numel() == m)
+    for t in (rows, cols, d, nn, filt):
+        assert t is None or t.element_size() == 4
+    for t in (e_mask, p, e):
+        assert t is None or t.dtype == torch.float64
+    if value.dtype == torch.float64:
+        kind = 2 if descending else 1
+    else:
+        assert value.element_size() == 4 and not value.is_floating_point() and not descending
+        kind = 0
+    taken = C.c_uint64(0)
+    _lib.check(L.tracs_anc_update_coo(_ptr(state), int(n), m, _ptr(rows), _ptr(cols), _ptr(value), kind, _ptr(e_mask), float(e_max),
+                                      _ptr(d), _ptr(nn), _ptr(filt), _ptr(p), _ptr(e), C.byref(taken), _stream()))
+    return taken.value
+
+
+def anc_emit(state, n):
+    """The links in (i, j) order and the trees (tracs_anc_emit): rows < cols, d, nn, filt (torch.int32), p, e (torch.float64), then
+    parent (-1 for a root), root and generation (torch.int32[n]), all on the device."""
+    L = _lib.require_gpu()
+    cnt = C.c_size_t(0)
+    _lib.check(L.tracs_anc_emit(_ptr(state), int(n), C.byref(cnt), *([C.c_void_p(0)] * 10), _stream()))
+    k = cnt.value
+    u = [torch.empty(max(k, 1), dtype=torch.int32, device=state.device) for _ in range(5)]
+    f = [torch.empty(max(k, 1), dtype=torch.float64, device=state.device) for _ in range(2)]
+    t = [torch.empty(max(int(n), 1), dtype=torch.int32, device=state.device) for _ in range(3)]
+    _lib.check(L.tracs_anc_emit(_ptr(state), int(n), C.byref(cnt), *[_ptr(x) for x in u + f + t], _stream()))
+    return [x[:k] for x in u + f] + [x[:int(n)] for x in t]
+
+
 def hist_init(n_bins, device=None):
     """An all-zero histogram state for the values [0, n_bins) (tracs_hist_init): a torch.uint8 device buffer."""
     L = _lib.require_gpu()

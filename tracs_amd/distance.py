@@ -35,6 +35,11 @@ def calculate_trans_prob(*args, **kwargs):
 # --mst WEIGHT -> tracs_distance_forest's weight (the columns `cluster -D` reads: snp 3, filter 6, direct 4, expectedK 5)
 MST_WEIGHTS = {"snp": 0, "filter": 1, "direct": 2, "expectedK": 3}
 
+# --ancestors WEIGHT -> tracs_distance_ancestors's weight: the same columns; direct (a probability) is read DESCENDING there
+ANCESTOR_WEIGHTS = {"snp": 0, "filter": 1, "direct": 2, "expectedK": 3}
+
+ANCESTORS_HEADER = "sample,date,ancestor,ancestor date,root,generation,MSA file\n"
+
 HISTOGRAM_HEADER = "column,distance,within,between,ungrouped,MSA file\n"
 
 HEADER = ("sampleA,sampleB,date difference,SNP distance,transmission distance,expected K,"
@@ -91,6 +96,21 @@ def distance_parser(parser):
                           "need --meta): at most n - 1 rows, each identical to its row in the full output.  For every threshold T, "
                           "`cluster -c T -D WEIGHT` on this file puts the same samples into the same clusters as on the full file "
                           "(cluster numbers may be permuted).  With --meta every sample needs a date.  Not in the reference.")
+    snp.add_argument("--ancestors", dest="ancestors", choices=list(ANCESTOR_WEIGHTS), default=None, metavar="WEIGHT",
+                     help="Only output, for each sample, the pair that links it to its most likely earlier source (SeqTrack-style; "
+                          "needs --meta): among the pairs the run would write, the candidates of a sample are its partners with a "
+                          "strictly earlier sampling date, and the source is the best of them under (WEIGHT, date gap, input order).  "
+                          "WEIGHT: snp | filter | expectedK, smallest first (filter needs --filter), or direct, LARGEST first -- the "
+                          "transmission distance column is a probability, so the likeliest source has the largest value (--mst direct "
+                          "and `cluster -D direct` read the same column as 'at most a threshold').  At most n - 1 rows, each identical "
+                          "to its row in the full output, in pair order.  The file stays a valid `cluster -d` input, but its connected "
+                          "components are the transmission trees (the root column of --ancestors-out), not single-linkage clusters.  "
+                          "Same-day samples are never linked; a sample without a candidate is a root.  Every compared sample needs a "
+                          "date.  One GPU, no --msa-db; not with --mst, --nearest or --histogram.  Not in the reference.")
+    snp.add_argument("--ancestors-out", dest="ancestors_out", default=None, type=str, metavar="FILE",
+                     help="With --ancestors: write sample,date,ancestor,ancestor date,root,generation,MSA file for every compared "
+                          "sample, in input order (dates as --meta gives them; a root has no ancestor, itself as root and generation 0; "
+                          "else root is the sample reached by following sources and generation the number of links to it)")
     snp.add_argument("--histogram", dest="histogram", action="store_true", default=False,
                      help="Instead of the pairs, output how many of them have each SNP distance (and, with --filter, each filtered "
                           "SNP distance): rows column,distance,within,between,ungrouped,MSA file, one per non-empty bin.  The pairs "
@@ -254,6 +274,72 @@ def _forest_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
         write_msa_outputs(L, h, args, msas[0], contigs)
     finally:
         L.tracs_distance_free(h)
+
+
+def _ancestors_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
+    """--ancestors WEIGHT for one alignment (tracs_distance_open / _ancestors: include/tracs_hip.h): the panel loop of
+    _forest_on_device with, instead of the forest, each later-dated sample's best earlier partner kept on the device; only the chosen
+    pairs' rows are formatted and appended, and --ancestors-out gets one line per compared sample.  Every compared sample needs a
+    date (checked on the opened handle: samples the sample rule left out need none)."""
+    L = _lib.require_gpu()
+    h = _open(L, msas, rule, args)
+    try:
+        stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
+        n = L.tracs_distance_nseq(h)
+        epoch = date(1970, 1, 1)
+        got, text = [], []
+        for i in range(n):
+            name = L.tracs_distance_name(h, i).decode("utf-8", "replace")
+            if name not in dates:
+                raise SystemExit("tracs distance --ancestors: sample '%s' has no sampling date in %s" % (name, args.metadata))
+            got.append((dates[name][1] - epoch).days)
+            text.append(dates[name][0].encode())
+        days = (C.c_int32 * max(n, 1))(*got)
+        tree = getattr(args, "ancestors_out", None)
+        meta_dates = (C.c_char_p * max(n, 1))(*text) if tree is not None else None
+        logging.info("Inferring transmission probabilities for %s", msas[0])
+        written, eligible = C.c_uint64(0), C.c_uint64(0)
+        kmax = -1.0 if args.trans_threshold is None else float(args.trans_threshold)
+        _lib.check(L.tracs_distance_ancestors(h, int(args.snp_threshold), days, float(args.clock_rate), float(args.trans_rate),
+                                              float(args.precision), kmax, int(bool(args.recomb_filter)), ANCESTOR_WEIGHTS[args.ancestors],
+                                              os.fsencode(args.output_file), ref.encode(), os.fsencode(tree) if tree is not None else None,
+                                              meta_dates, C.byref(written), C.byref(eligible)))
+        stage("[sum] tracs_distance_ancestors (dense panels, transcluster, ancestors: %d candidates, %d rows written)"
+              % (eligible.value, written.value))
+        write_msa_outputs(L, h, args, msas[0], contigs)
+    finally:
+        L.tracs_distance_free(h)
+
+
+def check_ancestors_args(args):
+    """--ancestors' and --ancestors-out's argument checks, before anything touches the GPU (SystemExit with the message)."""
+    anc, out = getattr(args, "ancestors", None), getattr(args, "ancestors_out", None)
+    if anc is None:
+        if out is not None:
+            raise SystemExit("tracs distance: --ancestors-out needs --ancestors (it lists the trees that --ancestors builds)")
+        return
+    if getattr(args, "mst", None) is not None:
+        raise SystemExit("tracs distance: --ancestors and --mst cannot be combined")
+    if getattr(args, "nearest", None) is not None:
+        raise SystemExit("tracs distance: --ancestors and --nearest cannot be combined")
+    if getattr(args, "histogram", False):
+        raise SystemExit("tracs distance: --ancestors and --histogram cannot be combined")
+    if getattr(args, "msa_db", None) is not None:
+        raise SystemExit("tracs distance: --ancestors links the samples of one alignment and takes no --msa-db")
+    if getattr(args, "gpus", 1) > 1:
+        raise SystemExit("tracs distance: --ancestors runs on one GPU; use --gpus 1")
+    if args.metadata is None:
+        raise SystemExit("tracs distance: --ancestors %s needs --meta (the sampling dates that order the samples)" % anc)
+    if anc == "filter" and not args.recomb_filter:
+        raise SystemExit("tracs distance: --ancestors filter needs --filter (the filtered SNP distance column)")
+    if out is not None:
+        inputs = list(getattr(args, "msa_files", None) or [])
+        inputs += [getattr(args, k, None) for k in ("metadata", "mask_bed", "keep_bed", "mask_reference")]
+        if os.path.realpath(out) in {os.path.realpath(p) for p in inputs if p is not None}:
+            raise SystemExit("tracs distance: --ancestors-out %s is one of the run's input files" % out)
+        others = [getattr(args, k, None) for k in ("output_file", "sites_out", "samples_out", "msa_out", "site_table")]
+        if os.path.realpath(out) in {os.path.realpath(p) for p in others if p is not None}:
+            raise SystemExit("tracs distance: --ancestors-out %s is also another output of the run" % out)
 
 
 def check_mst_args(args):
@@ -531,6 +617,8 @@ def check_histogram_args(args):
         if getattr(args, "groups", None) is not None:
             raise SystemExit("tracs distance: --groups needs --histogram (the labels only split the histogram's counts)")
         return
+    if getattr(args, "ancestors", None) is not None:
+        raise SystemExit("tracs distance: --ancestors and --histogram cannot be combined")
     if getattr(args, "nearest", None) is not None:
         raise SystemExit("tracs distance: --histogram and --nearest cannot be combined")
     if getattr(args, "mst", None) is not None:
@@ -643,6 +731,7 @@ def _pairs_multi_gpu(msas, args, ctx):
 
 
 def distance(args):
+    check_ancestors_args(args)
     check_mst_args(args)
     check_histogram_args(args)
     check_site_args(args)
@@ -652,7 +741,10 @@ def distance(args):
     histogram = getattr(args, "histogram", False)
     groups = read_groups(args.groups) if histogram and args.groups is not None else None
     mst = getattr(args, "mst", None)
+    ancestors = getattr(args, "ancestors", None)
     nearest = getattr(args, "nearest", None)
+    if nearest is not None and ancestors is not None:
+        raise SystemExit("tracs distance: --ancestors and --nearest cannot be combined")
     if nearest is not None and getattr(args, "gpus", 1) > 1:
         raise SystemExit("tracs distance: --nearest runs on one GPU; use --gpus 1")
     from . import multigpu
@@ -678,6 +770,9 @@ def distance(args):
     if lead:
         with open(args.output_file, "w") as out:
             out.write(HISTOGRAM_HEADER if histogram else HEADER)
+        if ancestors is not None and getattr(args, "ancestors_out", None) is not None:
+            with open(args.ancestors_out, "w") as out:
+                out.write(ANCESTORS_HEADER)
     import time
     trace = os.environ.get("TRACS_STAGE_TRACE") is not None      # "[stage] name seconds" lines on stderr (scripts/bench_e2e.py)
     t_stage = [time.perf_counter()]
@@ -719,6 +814,14 @@ def distance(args):
                     raise FileNotFoundError(p)
             _forest_on_device(msas, args, dates, ref, stage, **ruled)
             logging.info("Saving the minimum spanning forest for %s", msa)
+            continue
+        if ancestors is not None:
+            # each sample's most likely earlier source among the pairs the full run would write (one GPU, on the device until its rows)
+            for p in msas:
+                if not os.path.exists(p):
+                    raise FileNotFoundError(p)
+            _ancestors_on_device(msas, args, dates, ref, stage, **ruled)
+            logging.info("Saving the ancestor links for %s", msa)
             continue
         if ctx is None and nearest is None and os.environ.get("TRACS_DISTANCE_ARRAYS") is None:
             # one GPU: the results stay on the device until the CSV rows (with --filter: the filtered distances and the transmission
