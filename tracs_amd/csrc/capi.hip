@@ -14,6 +14,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -90,6 +92,15 @@ struct StageClock {
         t = std::chrono::steady_clock::now();
     }
 };
+// the time since the clock's last mark or lap goes into `acc` (the entry points that print sums over their panels)
+static void lap(StageClock &clock, double &acc)
+{
+    if (!clock.on) return;
+    (void)hipDeviceSynchronize();
+    const auto now = std::chrono::steady_clock::now();
+    acc += std::chrono::duration<double>(now - clock.t).count();
+    clock.t = now;
+}
 
 // dst[base + t] = src[t] (uint32 -> uint64) on several host threads: at 5 x 10^7 pairs the five result columns are 2 GB
 static void widen_append(std::vector<uint64_t> &dst, const unsigned *src, size_t count)
@@ -145,6 +156,217 @@ struct tracs_pairsnp_result {
     std::vector<std::string> names;
     SourceSamples source;
 };
+
+// the date difference of every emitted pair, as tracs/transcluster.py:26-33 takes it: |t_i - t_j| / 31556952.0 with t = whole days in seconds
+extern "C" __global__ __launch_bounds__(256) void coo_delta_kernel(const unsigned *__restrict__ rows, const unsigned *__restrict__ cols,
+                                                                   const int *__restrict__ days, size_t n, double *__restrict__ out)
+{
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (size_t)gridDim.x * 256) {
+        const long long dd = (long long)days[rows[t]] - (long long)days[cols[t]];
+        out[t] = (double)((dd < 0 ? -dd : dd) * 86400ll) / 31556952.0;
+    }
+}
+
+// ---- what the host entry points below share: owners, the row-panel walk, the pair-extraction stage ------------------------------------
+namespace {
+
+// Owners: what an entry point allocates is freed when it returns, on every path.  The device and the pinned buffer are move-only;
+// alloc() replaces what is held, grow() only when it is too small (an exact fit: the pair buffers never hold slack).
+template <bool kPinned> struct OwnedBuffer {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    OwnedBuffer() = default;
+    OwnedBuffer(OwnedBuffer &&o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+    OwnedBuffer &operator=(OwnedBuffer &&o) noexcept
+    {
+        if (this != &o) { release(); ptr = o.ptr; bytes = o.bytes; o.ptr = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~OwnedBuffer() { release(); }
+    void release()
+    {
+        if (ptr) (void)(kPinned ? hipHostFree(ptr) : hipFree(ptr));
+        ptr = nullptr; bytes = 0;
+    }
+    int alloc(size_t want)
+    {
+        release();
+        const hipError_t e = kPinned ? hipHostMalloc(&ptr, want, hipHostMallocDefault) : hipMalloc(&ptr, want);
+        if (e != hipSuccess) { ptr = nullptr; set_error(std::string(kPinned ? "hipHostMalloc: " : "hipMalloc: ") + hipGetErrorString(e)); return TRACS_E_HIP; }
+        bytes = want;
+        return TRACS_OK;
+    }
+    int grow(size_t want) { return want > bytes ? alloc(want) : TRACS_OK; }
+    int upload(const void *host, size_t count)
+    {
+        const int rc = alloc(count);
+        if (rc) return rc;
+        TRACS_HIP_CHECK(hipMemcpy(ptr, host, count, hipMemcpyHostToDevice));
+        return TRACS_OK;
+    }
+    template <class T> T *as() const { return static_cast<T *>(ptr); }
+};
+using DeviceBuffer = OwnedBuffer<false>;
+using PinnedBuffer = OwnedBuffer<true>;
+
+// the copy stream of tracs_distance_run and its events; declared AFTER the pinned buffers it copies into, so that it is drained and
+// destroyed before they are freed
+struct CopyLane {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr}, ready = nullptr;
+    CopyLane() = default;
+    CopyLane(const CopyLane &) = delete;
+    CopyLane &operator=(const CopyLane &) = delete;
+    int create()
+    {
+        TRACS_HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        for (auto &e : ev) TRACS_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        TRACS_HIP_CHECK(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+        return TRACS_OK;
+    }
+    ~CopyLane()
+    {
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (ready) (void)hipEventDestroy(ready);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+struct AlignmentFree { void operator()(tracs_alignment *a) const { tracs_alignment_free(a); } };
+using AlignmentOwner = std::unique_ptr<tracs_alignment, AlignmentFree>;
+struct ResultFree { void operator()(tracs_pairsnp_result *r) const { delete r; } };
+using ResultOwner = std::unique_ptr<tracs_pairsnp_result, ResultFree>;
+
+static int interrupted() { set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+
+// a diagnostics switch that counts rows, read on every call (0: not set, or below `least`)
+static size_t env_rows(const char *name, long long least)
+{
+    const char *e = std::getenv(name);
+    const long long v = e ? std::atoll(e) : 0;
+    return v >= least ? (size_t)v : (size_t)0;
+}
+
+// where a stage-trace lap goes: the entry point that owns the timers says which of its sums takes it
+enum Lap { LAP_DENSE, LAP_TC, LAP_COO, LAP_FILTER };
+using LapFn = std::function<void(Lap)>;
+
+// The row-panel walk of every host entry point: the pair range (src/pairsnp.hpp:348-360), the panel height (~1 GiB per dense uint32
+// matrix; TRACS_FOREST_PANEL_ROWS: diagnostics -- small panels in tests, so that every route crosses panel boundaries), the dense
+// buffers, and per panel the SIGINT look, the dense call (early out beyond `dist`) and -- directly after it, before anything reads
+// the panel -- the pair rule.
+struct Panel {
+    size_t r0 = 0, r1 = 0;
+    unsigned *bd = nullptr, *bn = nullptr;       // addressed as base[i * n + j] with i absolute: the bases are shifted by r0 rows
+    double *bp = nullptr, *be = nullptr;         // the f64 panels, when the walk holds them
+};
+
+struct PanelWalk {
+    tracs_alignment *a;
+    size_t n, i_end, j_start;
+    int dist;
+    uint32_t min_sites;
+    LapFn lap;
+    size_t height = 0, at = 0;
+    DeviceBuffer d_dist, d_nn, d_off, d_p, d_e;
+
+    PanelWalk(tracs_alignment *a_, int n_fasta, size_t n0, int dist_, uint32_t min_sites_, LapFn lap_ = nullptr)
+        : a(a_), n(a_->n), i_end(n_fasta == 1 ? a_->n : n0), j_start(n_fasta == 1 ? 0 : n0), dist(dist_), min_sites(min_sites_), lap(std::move(lap_)) {}
+    bool any() const { return n >= 2 && i_end > 0 && j_start < n; }       // else: no pair exists
+    int64_t *off() const { return d_off.as<int64_t>(); }
+    // with_off: row offsets for a PairStage; with_f64: the P(direct) and E(K) panels of the dense transcluster route
+    int begin(bool with_off, bool with_f64)
+    {
+        const size_t rows = env_rows("TRACS_FOREST_PANEL_ROWS", 1);
+        height = rows ? std::min(rows, i_end) : std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
+        int rc;
+        if ((rc = d_dist.alloc(height * n * 4)) || (rc = d_nn.alloc(height * n * 4))) return rc;
+        if (with_off && (rc = d_off.alloc((height + 1) * 8))) return rc;
+        if (with_f64 && ((rc = d_p.alloc(height * n * 8)) || (rc = d_e.alloc(height * n * 8)))) return rc;
+        return TRACS_OK;
+    }
+    bool more() const { return at < i_end; }
+    int next(Panel &p)
+    {
+        if (g_sigint) return interrupted();
+        p.r0 = at;
+        p.r1 = at = std::min(i_end, at + height);
+        p.bd = d_dist.as<unsigned>() - p.r0 * n;
+        p.bn = d_nn.as<unsigned>() - p.r0 * n;
+        p.bp = d_p.ptr ? d_p.as<double>() - p.r0 * n : nullptr;
+        p.be = d_e.ptr ? d_e.as<double>() - p.r0 * n : nullptr;
+        int rc = tracs_pairsnp_dense_thr(a, p.r0, p.r1, j_start, p.bd, p.bn, n, dist, nullptr);
+        if (!rc && min_sites) rc = pairs_min_sites(p.bd, p.bn, n, n, p.r0, p.r1, j_start, dist, min_sites, nullptr);
+        if (!rc && lap) lap(LAP_DENSE);
+        return rc;
+    }
+};
+
+// The pairs of one panel within the threshold, in row-major order (src/pairsnp.hpp:451-455), as columns on the device.
+// With dates (set_days) the columns carry P(direct) and E(K): without --filter from transcluster on the dense panel (the walk holds
+// the f64 panels: begin(true, dense_tc())), with --filter from the FILTERED distance, pair by pair (tracs/distance.py:183-193 ->
+// tracs/transcluster.py:8-41).  total = 0 is a result like any other: the panel holds no pair, the columns are not valid.
+struct PairColumns {
+    size_t total = 0;
+    unsigned *rows = nullptr, *cols = nullptr, *d = nullptr, *nn = nullptr, *filt = nullptr;
+    double *p = nullptr, *e = nullptr;
+};
+
+struct PairStage {
+    const PanelWalk &w;
+    bool filter;
+    double lamb, beta, precision;
+    DeviceBuffer d_days, coo, cp;
+
+    PairStage(const PanelWalk &walk, int filter_, double lamb_ = 0.0, double beta_ = 0.0, double precision_ = 0.0)
+        : w(walk), filter(filter_ != 0), lamb(lamb_), beta(beta_), precision(precision_) {}
+    int set_days(const int32_t *days) { return d_days.upload(days, w.n * 4); }
+    bool with_dates() const { return d_days.ptr != nullptr; }
+    bool dense_tc() const { return with_dates() && !filter; }
+    const int *days() const { return d_days.as<int>(); }
+    void release() { coo.release(); cp.release(); }
+    int extract(const Panel &pn, PairColumns &c)
+    {
+        c = PairColumns();
+        const size_t n = w.n;
+        int rc;
+        if (dense_tc()) {
+            if ((rc = tracs_trans_dist_dense(pn.bd, n, n, pn.r0, pn.r1, w.j_start, w.dist, days(), lamb, beta, precision, 1, pn.bp, pn.be, nullptr))) return rc;
+            if (w.lap) w.lap(LAP_TC);
+        }
+        if ((rc = tracs_coo_count(pn.bd, n, n, pn.r0, pn.r1, w.j_start, w.dist, w.off(), nullptr))) return rc;
+        long long total = 0;
+        TRACS_HIP_CHECK(hipMemcpy(&total, w.off() + (pn.r1 - pn.r0), 8, hipMemcpyDeviceToHost));
+        if (total <= 0) return TRACS_OK;
+        const size_t t = (size_t)total;
+        if ((rc = coo.grow(t * 4 * (filter ? 5 : 4)))) return rc;
+        if (with_dates() && (rc = cp.grow(t * (filter ? 24 : 16)))) return rc;
+        c.rows = coo.as<unsigned>(); c.cols = c.rows + t; c.d = c.rows + 2 * t; c.nn = c.rows + 3 * t;
+        c.filt = filter ? c.rows + 4 * t : nullptr;
+        c.p = with_dates() ? cp.as<double>() : nullptr;
+        c.e = with_dates() ? c.p + t : nullptr;
+        if ((rc = tracs_coo_fill(pn.bd, pn.bn, n, n, pn.r0, pn.r1, w.j_start, w.dist, w.off(), c.rows, c.cols, c.d, c.nn, nullptr))) return rc;
+        if (dense_tc() && (rc = tracs_coo_fill_f64(pn.bd, n, n, pn.r0, pn.r1, w.j_start, w.dist, w.off(), pn.bp, pn.be, c.p, c.e, nullptr))) return rc;
+        if (w.lap) w.lap(LAP_COO);
+        if (filter) {
+            // the recombination filter on the emitted pairs (src/pairsnp.hpp:405-413): SNP sites from the samples' departure lists
+            if (g_sigint) return interrupted();
+            if ((rc = tracs_filter_recomb_pairs(w.a, c.rows, c.cols, c.d, t, c.filt, nullptr))) return rc;
+            if (with_dates()) {
+                double *delta = c.p + 2 * t;
+                hipLaunchKernelGGL(coo_delta_kernel, dim3((unsigned)std::min<size_t>((t + 255) / 256, 65535)), dim3(256), 0, nullptr, c.rows, c.cols,
+                                   days(), t, delta);
+                if ((rc = tracs_trans_dist_device(reinterpret_cast<const int32_t *>(c.filt), delta, t, lamb, beta, precision, 1, c.p, c.e, nullptr))) return rc;
+            }
+            if (w.lap) w.lap(LAP_FILTER);
+        }
+        c.total = t;
+        return TRACS_OK;
+    }
+};
+
+}  // namespace
 
 extern "C" {
 
@@ -439,121 +661,68 @@ int tracs_nearest_rules(const char *const *fasta, int n_fasta, int n_threads, in
     return nearest_run(fasta, n_fasta, k, dist, filter, any ? &rule : nullptr, out);
 }
 
+// read + pack for the array entry points: the alignment and the result that will carry its pairs, both owned
+static int result_from_fasta(const char *const *fasta, int n_fasta, SiteRule *rule, AlignmentOwner &a, ResultOwner &res,
+                             size_t *n0)
+{
+    tracs_alignment *packed = nullptr;
+    char *names = nullptr;
+    size_t names_bytes = 0;
+    const int rc = alignment_from_fasta_sites(fasta, n_fasta, &packed, &names, &names_bytes, n0, rule);
+    if (rc) return rc;
+    a.reset(packed);
+    res.reset(new tracs_pairsnp_result());
+    res->nseq = a->n; res->L = a->L;
+    if (rule) res->source = std::move(rule->source);
+    else res->source.rule_sites = a->L;
+    { size_t o = 0; for (size_t i = 0; i < a->n; i++) { res->names.emplace_back(names + o); o += res->names.back().size() + 1; } }
+    tracs_free(names);
+    return TRACS_OK;
+}
+
 static int pairsnp_run(const char *const *fasta, int n_fasta, int dist, int filter, SiteRule *rule, tracs_pairsnp_result **out)
 {
     if (!out) { set_error("tracs_pairsnp: out is NULL"); return TRACS_E_ARG; }
     *out = nullptr;
     if (n_fasta < 1 || n_fasta > 2 || !fasta) { set_error("Invalid number of fasta files!"); return TRACS_E_ARG; }   // :340-343
     SigintScope sigint;
-    tracs_alignment *a = nullptr;
-    char *names = nullptr;
-    size_t names_bytes = 0, n0 = 0;
-    int rc = alignment_from_fasta_sites(fasta, n_fasta, &a, &names, &names_bytes, &n0, rule);
+    AlignmentOwner a;
+    ResultOwner res;
+    size_t n0 = 0;
+    int rc = result_from_fasta(fasta, n_fasta, rule, a, res, &n0);
     if (rc) return rc;
-    auto *res = new tracs_pairsnp_result();
-    res->nseq = a->n; res->L = a->L;
-    if (rule) res->source = std::move(rule->source);
-    else res->source.rule_sites = a->L;
-    const uint32_t min_sites = rule ? rule->min_sites : 0;
-    { size_t o = 0; for (size_t i = 0; i < a->n; i++) { res->names.emplace_back(names + o); o += res->names.back().size() + 1; } }
-    tracs_free(names);
-    // pair ranges (:348-360)
-    const size_t n = a->n;
-    const size_t i_end = n_fasta == 1 ? n : n0;
-    const size_t j_start = n_fasta == 1 ? 0 : n0;
-
-    unsigned *d_dist = nullptr, *d_nn = nullptr, *d_rows = nullptr, *d_cols = nullptr, *d_d = nullptr, *d_n = nullptr;
-    unsigned *d_filt = nullptr;
-    long long *d_off = nullptr;
-    size_t pair_cap = 0;
-    auto cleanup = [&]() {
-        void *p[] = {d_dist, d_nn, d_rows, d_cols, d_d, d_n, d_off, d_filt};
-        for (void *q : p) if (q) (void)hipFree(q);
-        tracs_alignment_free(a);
-    };
-#define PS_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); delete res; set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
-#define PS_RC(x) do { int r__ = (x); if (r__) { cleanup(); delete res; return r__; } } while (0)
     StageClock clock;
     double t_dense = 0.0, t_coo = 0.0, t_pull = 0.0, t_filter = 0.0;
-    auto lap = [&](double &acc) {
-        if (!clock.on) return;
-        (void)hipDeviceSynchronize();
-        const auto now = std::chrono::steady_clock::now();
-        acc += std::chrono::duration<double>(now - clock.t).count();
-        clock.t = now;
-    };
-    if (n >= 2 && i_end > 0) {
-        // row panels bounded to ~1 GiB per dense matrix
-        const size_t panel = std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
-        PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dist), panel * n * 4));
-        PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_nn), panel * n * 4));
-        PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_off), (panel + 1) * 8));
-        size_t cap = 0;
+    PanelWalk walk(a.get(), n_fasta, n0, dist, rule ? rule->min_sites : 0,
+                   [&](Lap l) { lap(clock, l == LAP_DENSE ? t_dense : l == LAP_COO ? t_coo : t_filter); });
+    PairStage stage(walk, filter);
+    if (walk.any()) {
+        if ((rc = walk.begin(true, false))) return rc;
         std::vector<unsigned> h32;
-        for (size_t r0 = 0; r0 < i_end; r0 += panel) {
-            if (g_sigint) { cleanup(); delete res; set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
-            const size_t r1 = std::min(i_end, r0 + panel);
-            // the dense block is addressed as base[(i) * ld + j] with i absolute: shift the base
-            unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;
-            lap(t_pull);
-            PS_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));   // early out beyond `dist`
-            if (min_sites) PS_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, min_sites, nullptr));
-            lap(t_dense);
-            PS_RC(tracs_coo_count(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), nullptr));
-            long long total = 0;
-            PS_CHECK(hipMemcpy(&total, d_off + (r1 - r0), 8, hipMemcpyDeviceToHost));
-            if (total <= 0) continue;
-            if ((size_t)total > cap) {
-                void *p[] = {d_rows, d_cols, d_d, d_n};
-                for (void *q : p) if (q) PS_CHECK(hipFree(q));
-                d_rows = d_cols = d_d = d_n = nullptr;
-                cap = (size_t)total;
-                PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_rows), cap * 4));
-                PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cols), cap * 4));
-                PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_d), cap * 4));
-                PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_n), cap * 4));
-            }
-            PS_RC(tracs_coo_fill(bd, bn, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), d_rows, d_cols, d_d, d_n, nullptr));
-            lap(t_coo);
-            h32.resize((size_t)total);
-            auto pull = [&](unsigned *src, std::vector<uint64_t> &dst) -> hipError_t {
-                hipError_t e = hipMemcpy(h32.data(), src, (size_t)total * 4, hipMemcpyDeviceToHost);
-                if (e != hipSuccess) return e;
-                widen_append(dst, h32.data(), (size_t)total);
-                return hipSuccess;
+        PairColumns c;
+        for (Panel pn; walk.more();) {
+            lap(clock, t_pull);
+            if ((rc = walk.next(pn)) || (rc = stage.extract(pn, c))) return rc;
+            if (!c.total) continue;
+            h32.resize(c.total);
+            auto pull = [&](const unsigned *src, std::vector<uint64_t> &dst) -> int {
+                TRACS_HIP_CHECK(hipMemcpy(h32.data(), src, c.total * 4, hipMemcpyDeviceToHost));
+                widen_append(dst, h32.data(), c.total);
+                return TRACS_OK;
             };
-            PS_CHECK(pull(d_rows, res->rows));
-            PS_CHECK(pull(d_cols, res->cols));
-            PS_CHECK(pull(d_d, res->dist));
-            PS_CHECK(pull(d_n, res->ncomp));
-            lap(t_pull);
-            if (filter) {
-                // recombination filter on the pairs just emitted (:405-413): SNP sites from the samples' departure lists
-                if (g_sigint) { cleanup(); delete res; set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
-                if ((size_t)total > pair_cap) {
-                    if (d_filt) PS_CHECK(hipFree(d_filt));
-                    d_filt = nullptr;
-                    pair_cap = (size_t)total + (size_t)total / 4 + 16;
-                    PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_filt), pair_cap * 4));
-                }
-                PS_RC(tracs_filter_recomb_pairs(a, d_rows, d_cols, d_d, (size_t)total, d_filt, nullptr));
-                PS_CHECK(hipMemcpy(h32.data(), d_filt, (size_t)total * 4, hipMemcpyDeviceToHost));
-                widen_append(res->filt, h32.data(), (size_t)total);
-                lap(t_filter);
-            }
+            if ((rc = pull(c.rows, res->rows)) || (rc = pull(c.cols, res->cols)) || (rc = pull(c.d, res->dist)) || (rc = pull(c.nn, res->ncomp))) return rc;
+            if (filter && (rc = pull(c.filt, res->filt))) return rc;
+            lap(clock, t_pull);
         }
     }
     if (clock.on)
         std::fprintf(stderr, "[stage] dense panels (once-per-pack work + pair kernels) %.4f s\n[stage] COO extraction (device) %.4f s\n"
                              "[stage] COO D2H + widening to uint64 (%zu pairs) %.4f s\n[stage] recombination filter %.4f s\n",
                      t_dense, t_coo, res->rows.size(), t_pull, t_filter);
-#undef PS_CHECK
-#undef PS_RC
     // a Ctrl-C that arrived during the last panel / filter batch is not swallowed (the reference looks at its flag on every row)
-    if (g_sigint) { cleanup(); delete res; set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+    if (g_sigint) return interrupted();
     if (!filter) res->filt.assign(res->rows.size(), 0);      // filter off: `len` zeros (:452 via combine_vectors :31)
-    cleanup();
-    *out = res;
+    *out = res.release();
     return TRACS_OK;
 }
 
@@ -583,74 +752,46 @@ static int nearest_run(const char *const *fasta, int n_fasta, int k, int dist, i
     if (n_fasta < 1 || n_fasta > 2 || !fasta) { set_error("Invalid number of fasta files!"); return TRACS_E_ARG; }
     if (k < 1 || k > 1024) { set_error("tracs_nearest: k must be in [1, 1024]"); return TRACS_E_ARG; }
     SigintScope sigint;
-    tracs_alignment *a = nullptr;
-    char *names = nullptr;
-    size_t names_bytes = 0, n0 = 0;
-    int rc = alignment_from_fasta_sites(fasta, n_fasta, &a, &names, &names_bytes, &n0, rule);
+    AlignmentOwner a;
+    ResultOwner res;
+    size_t n0 = 0;
+    int rc = result_from_fasta(fasta, n_fasta, rule, a, res, &n0);
     if (rc) return rc;
-    auto *res = new tracs_pairsnp_result();
-    res->nseq = a->n; res->L = a->L;
-    if (rule) res->source = std::move(rule->source);
-    else res->source.rule_sites = a->L;
-    const uint32_t min_sites = rule ? rule->min_sites : 0;
-    { size_t o = 0; for (size_t i = 0; i < a->n; i++) { res->names.emplace_back(names + o); o += res->names.back().size() + 1; } }
-    tracs_free(names);
     const size_t n = a->n;
-    const size_t i_end = n_fasta == 1 ? n : n0;                     // pair ranges (src/pairsnp.hpp:348-360)
-    const size_t j_start = n_fasta == 1 ? 0 : n0;
     const size_t n_lists = n_fasta == 1 ? n : n0;                   // two files: lists for the samples of file 0 only
-    unsigned *d_dist = nullptr, *d_nn = nullptr, *d_out = nullptr;
-    void *d_state = nullptr;
-    long long *d_off = nullptr;
-    auto cleanup = [&]() {
-        void *p[] = {d_dist, d_nn, d_out, d_state, d_off};
-        for (void *q : p) if (q) (void)hipFree(q);
-        tracs_alignment_free(a);
-    };
-#define NN_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); delete res; set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
-#define NN_RC(x) do { int r__ = (x); if (r__) { cleanup(); delete res; return r__; } } while (0)
-#define NN_INTERRUPT() do { if (g_sigint) { cleanup(); delete res; set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; } } while (0)
+    PanelWalk walk(a.get(), n_fasta, n0, dist, rule ? rule->min_sites : 0);
+    DeviceBuffer d_state, d_off, d_out;
     StageClock clock;
-    size_t total = 0;
-    if (n >= 2 && i_end > 0 && j_start < n) {
-        NN_CHECK(hipMalloc(&d_state, tracs_knn_state_bytes(n_lists, k)));
-        NN_RC(tracs_knn_init(d_state, n_lists, k, nullptr));
-        // row panels bounded to ~1 GiB per dense matrix, as tracs_pairsnp / tracs_distance_run
-        const size_t panel = std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
-        NN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dist), panel * n * 4));
-        NN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_nn), panel * n * 4));
-        for (size_t r0 = 0; r0 < i_end; r0 += panel) {
-            NN_INTERRUPT();
-            const size_t r1 = std::min(i_end, r0 + panel);
-            unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
-            NN_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
-            if (min_sites) NN_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, min_sites, nullptr));
-            NN_RC(tracs_knn_update(bd, bn, n, n, r0, r1, j_start, dist, k, n_fasta == 1 ? 1 : 0, d_state, nullptr));
+    if (walk.any()) {
+        if ((rc = d_state.alloc(tracs_knn_state_bytes(n_lists, k))) || (rc = tracs_knn_init(d_state.ptr, n_lists, k, nullptr))) return rc;
+        if ((rc = walk.begin(false, false))) return rc;
+        for (Panel pn; walk.more();) {
+            if ((rc = walk.next(pn))) return rc;
+            if ((rc = tracs_knn_update(pn.bd, pn.bn, n, n, pn.r0, pn.r1, walk.j_start, dist, k, n_fasta == 1 ? 1 : 0, d_state.ptr, nullptr))) return rc;
         }
         clock.mark("dense panels + selection");
         // rows, cols, d, nn, filt (and the filter's ordered pairs) in one block: one copy back
         const size_t cap = n_lists * (size_t)k;
-        NN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_off), (n_lists + 1) * 8));
-        NN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_out), cap * 4 * (filter ? 7 : 4)));
-        unsigned *c_rows = d_out, *c_cols = d_out + cap, *c_d = d_out + 2 * cap, *c_n = d_out + 3 * cap;
-        NN_RC(tracs_knn_emit(d_state, 0, n_lists, k, reinterpret_cast<int64_t *>(d_off), c_rows, c_cols, c_d, c_n, nullptr));
+        if ((rc = d_off.alloc((n_lists + 1) * 8)) || (rc = d_out.alloc(cap * 4 * (filter ? 7 : 4)))) return rc;
+        unsigned *c_rows = d_out.as<unsigned>(), *c_cols = c_rows + cap, *c_d = c_rows + 2 * cap, *c_n = c_rows + 3 * cap;
+        if ((rc = tracs_knn_emit(d_state.ptr, 0, n_lists, k, d_off.as<int64_t>(), c_rows, c_cols, c_d, c_n, nullptr))) return rc;
         long long tot = 0;
-        NN_CHECK(hipMemcpy(&tot, d_off + n_lists, 8, hipMemcpyDeviceToHost));
-        total = (size_t)tot;
+        TRACS_HIP_CHECK(hipMemcpy(&tot, d_off.as<int64_t>() + n_lists, 8, hipMemcpyDeviceToHost));
+        const size_t total = (size_t)tot;
         clock.mark("emit");
         if (filter && total) {
-            NN_INTERRUPT();
-            unsigned *c_f = d_out + 4 * cap, *c_lo = d_out + 5 * cap, *c_hi = d_out + 6 * cap;
+            if (g_sigint) return interrupted();
+            unsigned *c_f = c_rows + 4 * cap, *c_lo = c_rows + 5 * cap, *c_hi = c_rows + 6 * cap;
             hipLaunchKernelGGL(knn_pair_order_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535)), dim3(256), 0, nullptr,
                                c_rows, c_cols, total, c_lo, c_hi);
-            NN_CHECK(hipGetLastError());
-            NN_RC(tracs_filter_recomb_pairs(a, c_lo, c_hi, c_d, total, c_f, nullptr));
+            TRACS_HIP_CHECK(hipGetLastError());
+            if ((rc = tracs_filter_recomb_pairs(a.get(), c_lo, c_hi, c_d, total, c_f, nullptr))) return rc;
             clock.mark("recombination filter");
         }
         if (total) {
             const size_t ncol = filter ? 5 : 4;
             std::vector<unsigned> h32(ncol * total);
-            NN_CHECK(hipMemcpy2D(h32.data(), total * 4, d_out, cap * 4, total * 4, ncol, hipMemcpyDeviceToHost));
+            TRACS_HIP_CHECK(hipMemcpy2D(h32.data(), total * 4, c_rows, cap * 4, total * 4, ncol, hipMemcpyDeviceToHost));
             widen_append(res->rows, h32.data(), total);
             widen_append(res->cols, h32.data() + total, total);
             widen_append(res->dist, h32.data() + 2 * total, total);
@@ -659,13 +800,9 @@ static int nearest_run(const char *const *fasta, int n_fasta, int k, int dist, i
             clock.mark("D2H + widening");
         }
     }
-#undef NN_CHECK
-#undef NN_RC
-    if (g_sigint) { cleanup(); delete res; set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
-#undef NN_INTERRUPT
+    if (g_sigint) return interrupted();
     if (!filter) res->filt.assign(res->rows.size(), 0);
-    cleanup();
-    *out = res;
+    *out = res.release();
     return TRACS_OK;
 }
 
@@ -799,42 +936,34 @@ int tracs_distance_write_alignment(tracs_distance *h, const char *path, size_t s
     if (!h || !h->a || !path) { set_error("tracs_distance_write_alignment: NULL argument"); return TRACS_E_ARG; }
     if (sample_begin > sample_end || sample_end > h->a->n) { set_error("tracs_distance_write_alignment: sample range outside the alignment"); return TRACS_E_ARG; }
     const tracs_alignment *a = h->a;
-    tracs_alignment *cut = nullptr;
+    AlignmentOwner cut;
     int rc = TRACS_OK;
     if (differing_only) {
         std::vector<uint64_t> differs((a->L + 63) / 64, 0);
         size_t nd = 0;
+        tracs_alignment *sel = nullptr;
         if ((rc = site_census(a, nullptr, differs.data(), &nd, nullptr))) return rc;
         if (!nd) { set_error("no column differs among the samples"); return TRACS_E_ARG; }
-        if ((rc = select_sites(const_cast<tracs_alignment *>(a), differs.data(), a->L, UINT32_MAX, &cut, nullptr, nullptr, nullptr, false))) return rc;
-        a = cut;
+        if ((rc = select_sites(const_cast<tracs_alignment *>(a), differs.data(), a->L, UINT32_MAX, &sel, nullptr, nullptr, nullptr, false))) return rc;
+        cut.reset(sel);
+        a = sel;
     }
     const size_t L = a->L, stride = (L + 15) / 16 * 16, count = sample_end - sample_begin;
     const size_t batch = std::max<size_t>(1, std::min<size_t>(count, stride ? (256ull << 20) / stride : count));
-    uint8_t *d_buf = nullptr, *h_buf = nullptr;
-    auto done = [&](int r) {
-        if (d_buf) (void)hipFree(d_buf);
-        if (h_buf) (void)hipHostFree(h_buf);
-        if (cut) tracs_alignment_free(cut);
-        return r;
-    };
-#define WA_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { (void)hipGetLastError(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return done(TRACS_E_HIP); } } while (0)
-    if (count && L) {
-        WA_CHECK(hipMalloc(reinterpret_cast<void **>(&d_buf), batch * stride));
-        WA_CHECK(hipHostMalloc(reinterpret_cast<void **>(&h_buf), batch * stride, hipHostMallocDefault));
-    }
-    if ((rc = tracs_write_fasta_rows(path, nullptr, nullptr, stride, 0, L, 0, n_threads, gzip_level))) return done(rc);     // truncate
+    DeviceBuffer d_buf;
+    PinnedBuffer h_buf;
+    if (count && L && ((rc = d_buf.alloc(batch * stride)) || (rc = h_buf.alloc(batch * stride)))) return rc;
+    if ((rc = tracs_write_fasta_rows(path, nullptr, nullptr, stride, 0, L, 0, n_threads, gzip_level))) return rc;     // truncate
     for (size_t s = sample_begin; s < sample_end; s += batch) {
         const size_t cnt = std::min(batch, sample_end - s);
         if (L) {
-            if ((rc = unpack_rows(a, s, cnt, d_buf, stride, nullptr))) return done(rc);
-            WA_CHECK(hipMemcpy(h_buf, d_buf, cnt * stride, hipMemcpyDeviceToHost));
+            if ((rc = unpack_rows(a, s, cnt, d_buf.as<uint8_t>(), stride, nullptr))) return rc;
+            TRACS_HIP_CHECK(hipMemcpy(h_buf.ptr, d_buf.ptr, cnt * stride, hipMemcpyDeviceToHost));
         }
-        if ((rc = tracs_write_fasta_rows(path, h->name_ptr.data() + s, h_buf, stride, cnt, L, 1, n_threads, gzip_level))) return done(rc);
+        if ((rc = tracs_write_fasta_rows(path, h->name_ptr.data() + s, h_buf.as<uint8_t>(), stride, cnt, L, 1, n_threads, gzip_level))) return rc;
     }
-#undef WA_CHECK
     if (sites_written) *sites_written = L;
-    return done(TRACS_OK);
+    return TRACS_OK;
 }
 
 // ---- the sites behind listed pairs (csrc/pair_sites.hip) --------------------------------------------------------------
@@ -850,16 +979,6 @@ int tracs_distance_pair_sites(tracs_distance *h, const uint32_t *rows, const uin
                             max_entries, path, contig_names, contig_lengths, n_contigs, n_threads, rows_written);
 }
 
-// the date difference of every emitted pair, as tracs/transcluster.py:26-33 takes it: |t_i - t_j| / 31556952.0 with t = whole days in seconds
-__global__ __launch_bounds__(256) void coo_delta_kernel(const unsigned *__restrict__ rows, const unsigned *__restrict__ cols, const int *__restrict__ days,
-                                                        size_t n, double *__restrict__ out)
-{
-    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (size_t)gridDim.x * 256) {
-        const long long dd = (long long)days[rows[t]] - (long long)days[cols[t]];
-        out[t] = (double)((dd < 0 ? -dd : dd) * 86400ll) / 31556952.0;
-    }
-}
-
 int tracs_distance_run(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
                        const char *path, const char *ref, int filter, uint64_t *rows_written, uint64_t *n_pairs)
 {
@@ -867,166 +986,118 @@ int tracs_distance_run(tracs_distance *h, int dist, const int32_t *days, double 
     if (n_pairs) *n_pairs = 0;
     if (!h || !h->a || !path || !ref) { set_error("tracs_distance_run: NULL argument"); return TRACS_E_ARG; }
     SigintScope sigint;
-    tracs_alignment *a = h->a;
-    const size_t n = a->n;
-    const size_t i_end = h->n_fasta == 1 ? n : h->n0;               // pair ranges (:348-360)
-    const size_t j_start = h->n_fasta == 1 ? 0 : h->n0;
     const bool with_dates = days != nullptr;
     // rows per device-to-host batch (TRACS_DISTANCE_BATCH_ROWS: diagnostics -- small batches in tests)
-    static const size_t CH_MAX = [] { const char *e = std::getenv("TRACS_DISTANCE_BATCH_ROWS"); const long long v = e ? std::atoll(e) : 0; return v >= 16 ? (size_t)v : (size_t)1 << 22; }();
+    const size_t batch_rows = env_rows("TRACS_DISTANCE_BATCH_ROWS", 16);
     // (never more than the pairs there can be: ten isolates do not pin a quarter of a gigabyte of host memory)
-    const size_t CH = std::max<size_t>(64, std::min<size_t>(CH_MAX, (h->n_fasta == 1 ? h->a->n : h->n0) * h->a->n));
-    unsigned *d_dist = nullptr, *d_nn = nullptr, *d_coo = nullptr;
-    double *d_p = nullptr, *d_e = nullptr, *d_cp = nullptr;
-    const bool dense_tc = with_dates && !filter;                   // --filter: the transmission model is driven by the FILTERED distance
-                                                                    // (tracs/distance.py:183-193): per emitted pair, after the filter
-    int *d_days = nullptr;
-    long long *d_off = nullptr;
-    char *pin[2] = {nullptr, nullptr};
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr}, ready = nullptr;
+    const size_t CH = std::max<size_t>(64, std::min<size_t>(batch_rows ? batch_rows : (size_t)1 << 22, (h->n_fasta == 1 ? h->a->n : h->n0) * h->a->n));
     tracs::DistanceRowWriter writer;
-    auto cleanup = [&]() {
-        void *p[] = {d_dist, d_nn, d_coo, d_p, d_e, d_cp, d_days, d_off};
-        for (void *q : p) if (q) (void)hipFree(q);
-        for (char *q : pin) if (q) (void)hipHostFree(q);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (ready) (void)hipEventDestroy(ready);
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
-    };
-#define DR_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
-#define DR_RC(x) do { int r__ = (x); if (r__) { cleanup(); return r__; } } while (0)
-    DR_RC(writer.open(path, h->name_ptr.data(), h->name_ptr.size(), ref));
+    int rc = writer.open(path, h->name_ptr.data(), h->name_ptr.size(), ref);
+    if (rc) return rc;
     StageClock clock;
     double t_dense = 0.0, t_tc = 0.0, t_coo = 0.0, t_rows = 0.0;
-    auto lap = [&](double &acc) {
-        if (!clock.on) return;
-        (void)hipDeviceSynchronize();
-        const auto now = std::chrono::steady_clock::now();
-        acc += std::chrono::duration<double>(now - clock.t).count();
-        clock.t = now;
-    };
+    // (the extraction's own lap stays with the sum that follows it, as the table of DESIGN.md 5 has it)
+    PanelWalk walk(h->a, h->n_fasta, h->n0, dist, h->min_sites, [&](Lap l) { if (l != LAP_COO) lap(clock, l == LAP_DENSE ? t_dense : t_tc); });
+    // --filter: the transmission model is driven by the FILTERED distance (tracs/distance.py:183-193): per emitted pair, after the filter
+    PairStage stage(walk, filter, lamb, beta, precision);
+    PinnedBuffer pin[2];
+    CopyLane lane;                                                  // (after `pin`: drained and destroyed before they are freed)
     uint64_t pairs = 0;
-    if (n >= 2 && i_end > 0) {
-        // row panels bounded to ~1 GiB per uint32 matrix (2 GiB per f64 one)
-        const size_t panel = std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
-        DR_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dist), panel * n * 4));
-        DR_CHECK(hipMalloc(reinterpret_cast<void **>(&d_nn), panel * n * 4));
-        DR_CHECK(hipMalloc(reinterpret_cast<void **>(&d_off), (panel + 1) * 8));
-        if (dense_tc) {
-            DR_CHECK(hipMalloc(reinterpret_cast<void **>(&d_p), panel * n * 8));
-            DR_CHECK(hipMalloc(reinterpret_cast<void **>(&d_e), panel * n * 8));
-        }
-        if (with_dates) {
-            DR_CHECK(hipMalloc(reinterpret_cast<void **>(&d_days), n * 4));
-            DR_CHECK(hipMemcpy(d_days, days, n * 4, hipMemcpyHostToDevice));
-        }
+    if (walk.any()) {
+        if (with_dates && (rc = stage.set_days(days))) return rc;
+        if ((rc = walk.begin(true, stage.dense_tc()))) return rc;
         // a batch on the host: four uint32 columns (five with --filter), then two f64 ones; two of them, so that one is formatted while the
         // next arrives
         const size_t n32 = filter ? 5 : 4;
         const size_t batch_bytes = CH * (n32 * 4 + (with_dates ? 16 : 0) + 4);
-        for (auto &q : pin) DR_CHECK(hipHostMalloc(reinterpret_cast<void **>(&q), batch_bytes, hipHostMallocDefault));
-        DR_CHECK(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
-        for (auto &e : ev) DR_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        DR_CHECK(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+        const size_t f64_at = (CH * n32 * 4 + 7) / 8 * 8;
+        for (auto &q : pin) if ((rc = q.alloc(batch_bytes))) return rc;
+        if ((rc = lane.create())) return rc;
         std::vector<uint32_t> zeros;                                  // the filtered column without metadata: `len` zeros (:240-258)
         if (!with_dates) zeros.assign(CH, 0u);
-        size_t cap = 0;
-        for (size_t r0 = 0; r0 < i_end; r0 += panel) {
-            if (g_sigint) { cleanup(); set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
-            const size_t r1 = std::min(i_end, r0 + panel);
-            unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
-            double *bp = dense_tc ? d_p - r0 * n : nullptr, *be = dense_tc ? d_e - r0 * n : nullptr;
-            DR_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
-            if (h->min_sites) DR_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, h->min_sites, nullptr));
-            lap(t_dense);
-            if (dense_tc)
-                DR_RC(tracs_trans_dist_dense(bd, n, n, r0, r1, j_start, dist, d_days, lamb, beta, precision, 1, bp, be, nullptr));
-            lap(t_tc);
-            DR_RC(tracs_coo_count(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), nullptr));
-            long long total = 0;
-            DR_CHECK(hipMemcpy(&total, d_off + (r1 - r0), 8, hipMemcpyDeviceToHost));
-            if (total <= 0) continue;
-            if ((size_t)total > cap) {
-                if (d_coo) DR_CHECK(hipFree(d_coo));
-                if (d_cp) DR_CHECK(hipFree(d_cp));
-                d_coo = nullptr; d_cp = nullptr;
-                cap = (size_t)total;
-                DR_CHECK(hipMalloc(reinterpret_cast<void **>(&d_coo), cap * 4 * n32));
-                if (with_dates) DR_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cp), cap * (filter ? 24 : 16)));
-            }
-            unsigned *c_rows = d_coo, *c_cols = d_coo + cap, *c_d = d_coo + 2 * cap, *c_n = d_coo + 3 * cap, *c_f = filter ? d_coo + 4 * cap : nullptr;
-            double *c_p = d_cp, *c_e = with_dates ? d_cp + cap : nullptr, *c_delta = (with_dates && filter) ? d_cp + 2 * cap : nullptr;
-            DR_RC(tracs_coo_fill(bd, bn, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), c_rows, c_cols, c_d, c_n, nullptr));
-            if (dense_tc)
-                DR_RC(tracs_coo_fill_f64(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), bp, be, c_p, c_e, nullptr));
-            if (filter) {
-                // the recombination filter on the emitted pairs (src/pairsnp.hpp:405-413), then -- with dates -- P(direct) and E(K) of the
-                // filtered distances, pair by pair (tracs/distance.py:183-193 -> tracs/transcluster.py:8-41 -> trans_dist)
-                DR_RC(tracs_filter_recomb_pairs(a, c_rows, c_cols, c_d, (size_t)total, c_f, nullptr));
-                if (with_dates) {
-                    hipLaunchKernelGGL(coo_delta_kernel, dim3((unsigned)std::min<size_t>(((size_t)total + 255) / 256, 65535)), dim3(256), 0, nullptr, c_rows, c_cols,
-                                       d_days, (size_t)total, c_delta);
-                    DR_RC(tracs_trans_dist_device(reinterpret_cast<const int32_t *>(c_f), c_delta, (size_t)total, lamb, beta, precision, 1, c_p, c_e, nullptr));
-                }
-                lap(t_tc);
-            }
-            DR_CHECK(hipEventRecord(ready, nullptr));
-            DR_CHECK(hipStreamWaitEvent(copy_stream, ready, 0));
-            lap(t_coo);
-            const size_t nb = ((size_t)total + CH - 1) / CH;
+        PairColumns c;
+        for (Panel pn; walk.more();) {
+            if ((rc = walk.next(pn)) || (rc = stage.extract(pn, c))) return rc;
+            if (!c.total) continue;
+            TRACS_HIP_CHECK(hipEventRecord(lane.ready, nullptr));
+            TRACS_HIP_CHECK(hipStreamWaitEvent(lane.stream, lane.ready, 0));
+            lap(clock, t_coo);
+            const size_t nb = (c.total + CH - 1) / CH;
             auto post = [&](size_t k) -> hipError_t {                 // batch k -> pinned set k % 2
-                const size_t o = k * CH, cnt = std::min(CH, (size_t)total - o);
-                char *dst = pin[k & 1];
-                const unsigned *src32[5] = {c_rows, c_cols, c_d, c_n, c_f};
+                const size_t o = k * CH, cnt = std::min(CH, c.total - o);
+                char *dst = pin[k & 1].as<char>();
+                const unsigned *src32[5] = {c.rows, c.cols, c.d, c.nn, c.filt};
                 for (size_t q = 0; q < n32; q++) {
-                    const hipError_t e = hipMemcpyAsync(dst + (size_t)q * CH * 4, src32[q] + o, cnt * 4, hipMemcpyDeviceToHost, copy_stream);
+                    const hipError_t e = hipMemcpyAsync(dst + (size_t)q * CH * 4, src32[q] + o, cnt * 4, hipMemcpyDeviceToHost, lane.stream);
                     if (e != hipSuccess) return e;
                 }
                 if (with_dates) {
-                    const size_t f64_at = (CH * n32 * 4 + 7) / 8 * 8;
-                    hipError_t e = hipMemcpyAsync(dst + f64_at, c_p + o, cnt * 8, hipMemcpyDeviceToHost, copy_stream);
-                    if (e == hipSuccess) e = hipMemcpyAsync(dst + f64_at + CH * 8, c_e + o, cnt * 8, hipMemcpyDeviceToHost, copy_stream);
+                    hipError_t e = hipMemcpyAsync(dst + f64_at, c.p + o, cnt * 8, hipMemcpyDeviceToHost, lane.stream);
+                    if (e == hipSuccess) e = hipMemcpyAsync(dst + f64_at + CH * 8, c.e + o, cnt * 8, hipMemcpyDeviceToHost, lane.stream);
                     if (e != hipSuccess) return e;
                 }
-                return hipEventRecord(ev[k & 1], copy_stream);
+                return hipEventRecord(lane.ev[k & 1], lane.stream);
             };
-            DR_CHECK(post(0));
+            TRACS_HIP_CHECK(post(0));
             for (size_t k = 0; k < nb; k++) {
-                if (g_sigint) { (void)hipStreamSynchronize(copy_stream); cleanup(); set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
-                DR_CHECK(hipEventSynchronize(ev[k & 1]));
-                if (k + 1 < nb) DR_CHECK(post(k + 1));
-                const size_t cnt = std::min(CH, (size_t)total - k * CH);
-                const char *src = pin[k & 1];
+                if (g_sigint) { (void)hipStreamSynchronize(lane.stream); return interrupted(); }
+                TRACS_HIP_CHECK(hipEventSynchronize(lane.ev[k & 1]));
+                if (k + 1 < nb) TRACS_HIP_CHECK(post(k + 1));
+                const size_t cnt = std::min(CH, c.total - k * CH);
+                const char *src = pin[k & 1].as<char>();
                 const uint32_t *hr = reinterpret_cast<const uint32_t *>(src), *hc = hr + CH, *hd = hr + 2 * CH, *hn = hr + 3 * CH;
-                const size_t f64_at = (CH * n32 * 4 + 7) / 8 * 8;
                 const double *hp = reinterpret_cast<const double *>(src + f64_at), *he = hp + CH;
                 // the filtered column: --filter: the filtered distances; else metadata on: a column of "NA" (:204), metadata off: zeros (:240-258)
                 const uint32_t *hf = filter ? hr + 4 * CH : (with_dates ? nullptr : zeros.data());
-                DR_RC(writer.append_u32(hr, hc, hd, hf, hn, days, with_dates ? hp : nullptr, with_dates ? he : nullptr,
-                                        cnt, with_dates ? 1 : 0, with_dates ? k_max : -1.0));
+                if ((rc = writer.append_u32(hr, hc, hd, hf, hn, days, with_dates ? hp : nullptr, with_dates ? he : nullptr,
+                                            cnt, with_dates ? 1 : 0, with_dates ? k_max : -1.0))) return rc;
             }
-            pairs += (uint64_t)total;
-            lap(t_rows);
+            pairs += (uint64_t)c.total;
+            lap(clock, t_rows);
         }
     }
     if (clock.on)
         std::fprintf(stderr, "[stage] dense panels (once-per-pack work + pair kernels) %.4f s\n[stage] transcluster on the panels (device) %.4f s\n"
                              "[stage] COO extraction (device) %.4f s\n[stage] rows: device -> host, format, write (%llu pairs) %.4f s\n",
                      t_dense, t_tc, t_coo, (unsigned long long)pairs, t_rows);
-#undef DR_CHECK
-#undef DR_RC
-    cleanup();
-    const int rc = writer.close();
+    rc = writer.close();
     if (rows_written) *rows_written = writer.written();
     if (n_pairs) *n_pairs = pairs;
-    if (g_sigint) { set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+    if (g_sigint) return interrupted();
     return rc;
 }
 
-// `tracs distance --mst WEIGHT` for one alignment (include/tracs_hip.h): the panel loop of tracs_distance_run up to
-// the COO of the panel's pairs within the threshold (with P and E(K), --filter's filtered distances and their P and E(K)), then
-// tracs_msf_update_coo instead of the rows; after the last panel the forest is emitted and written through the same row writer.
+// The rows that --mst and --ancestors keep, `count` < n of them: rows, cols, d, nn, filt (uint32), P, E(K) (f64) emitted into fresh
+// columns, copied to the host and written through the row writer.  The filtered column as the full run writes it: --filter: the
+// filtered distances; else metadata on: "NA" (:204), metadata off: the emitted column (zeros, :240-258).
+using EmitFn = std::function<int(unsigned *, unsigned *, unsigned *, unsigned *, unsigned *, double *, double *)>;
+static int write_emitted_rows(size_t count, const EmitFn &emit, tracs::DistanceRowWriter &writer, const int32_t *days, int filter)
+{
+    DeviceBuffer coo, cp;
+    int rc;
+    if ((rc = coo.alloc(count * 4 * 5)) || (rc = cp.alloc(count * 16))) return rc;
+    unsigned *c = coo.as<unsigned>();
+    double *f = cp.as<double>();
+    if ((rc = emit(c, c + count, c + 2 * count, c + 3 * count, c + 4 * count, f, f + count))) return rc;
+    std::vector<uint32_t> h32(count * 5);
+    std::vector<double> h64(count * 2);
+    TRACS_HIP_CHECK(hipMemcpy(h32.data(), c, count * 20, hipMemcpyDeviceToHost));
+    TRACS_HIP_CHECK(hipMemcpy(h64.data(), f, count * 16, hipMemcpyDeviceToHost));
+    const uint32_t *hr = h32.data(), *hc = hr + count, *hd = hr + 2 * count, *hn = hr + 3 * count, *hf = hr + 4 * count;
+    const bool with_dates = days != nullptr;
+    return writer.append_u32(hr, hc, hd, (filter || !with_dates) ? hf : nullptr, hn, days, with_dates ? h64.data() : nullptr,
+                             with_dates ? h64.data() + count : nullptr, count, with_dates ? 1 : 0, -1.0);
+}
+
+// the column a pair is weighed by: 0 d, 1 filtered d, 2 P(direct), 3 E(K) (the columns `cluster -D` reads: 3, 6, 4, 5)
+static const void *weight_column(const PairColumns &c, int weight)
+{
+    return weight == 0 ? (const void *)c.d : weight == 1 ? (const void *)c.filt : weight == 2 ? (const void *)c.p : (const void *)c.e;
+}
+
+// `tracs distance --mst WEIGHT` for one alignment (include/tracs_hip.h): the panel walk and the pair stage of
+// tracs_distance_run (the panel's pairs within the threshold with P and E(K), --filter's filtered distances and their P and E(K)),
+// then tracs_msf_update_coo instead of the rows; after the last panel the forest is emitted and written through the same row writer.
 int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
                           int filter, int weight, const char *path, const char *ref, uint64_t *rows_written, uint64_t *n_eligible)
 {
@@ -1037,123 +1108,47 @@ int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, doub
     if (weight == 1 && !filter) { set_error("tracs_distance_forest: the filter weight needs filter != 0"); return TRACS_E_ARG; }
     if (weight >= 2 && !days) { set_error("tracs_distance_forest: the direct and expectedK weights need sampling dates"); return TRACS_E_ARG; }
     SigintScope sigint;
-    tracs_alignment *a = h->a;
-    const size_t n = a->n;
-    const size_t i_end = h->n_fasta == 1 ? n : h->n0;               // pair ranges (:348-360)
-    const size_t j_start = h->n_fasta == 1 ? 0 : h->n0;
-    const bool with_dates = days != nullptr;
-    const bool dense_tc = with_dates && !filter;
-    // rows per panel (TRACS_FOREST_PANEL_ROWS: diagnostics -- small panels in tests, so that the forest crosses panel boundaries)
-    static const size_t PANEL_ROWS = [] { const char *e = std::getenv("TRACS_FOREST_PANEL_ROWS"); const long long v = e ? std::atoll(e) : 0; return v >= 1 ? (size_t)v : (size_t)0; }();
-    unsigned *d_dist = nullptr, *d_nn = nullptr, *d_coo = nullptr;
-    double *d_p = nullptr, *d_e = nullptr, *d_cp = nullptr;
-    int *d_days = nullptr;
-    long long *d_off = nullptr;
-    void *d_state = nullptr;
+    const size_t n = h->a->n;
     tracs::DistanceRowWriter writer;
-    auto cleanup = [&]() {
-        void *q[] = {d_dist, d_nn, d_coo, d_p, d_e, d_cp, d_days, d_off, d_state};
-        for (void *x : q) if (x) (void)hipFree(x);
-    };
-#define MF_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
-#define MF_RC(x) do { int r__ = (x); if (r__) { cleanup(); return r__; } } while (0)
-    MF_RC(writer.open(path, h->name_ptr.data(), h->name_ptr.size(), ref));
+    int rc = writer.open(path, h->name_ptr.data(), h->name_ptr.size(), ref);
+    if (rc) return rc;
     StageClock clock;
     uint64_t eligible = 0;
-    const double e_max = (with_dates && k_max >= 0.0) ? k_max : -1.0;
-    if (n >= 2 && i_end > 0 && j_start < n) {
-        const size_t panel = PANEL_ROWS ? std::min(PANEL_ROWS, i_end)
-                                        : std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
-        MF_CHECK(hipMalloc(&d_state, tracs_msf_state_bytes(n)));
-        MF_RC(tracs_msf_init(d_state, n, nullptr));
-        MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dist), panel * n * 4));
-        MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_nn), panel * n * 4));
-        MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_off), (panel + 1) * 8));
-        if (dense_tc) {
-            MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_p), panel * n * 8));
-            MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_e), panel * n * 8));
-        }
-        if (with_dates) {
-            MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_days), n * 4));
-            MF_CHECK(hipMemcpy(d_days, days, n * 4, hipMemcpyHostToDevice));
-        }
-        const size_t n32 = filter ? 5 : 4;
-        size_t cap = 0;
-        for (size_t r0 = 0; r0 < i_end; r0 += panel) {
-            if (g_sigint) { cleanup(); set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
-            const size_t r1 = std::min(i_end, r0 + panel);
-            unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
-            double *bp = dense_tc ? d_p - r0 * n : nullptr, *be = dense_tc ? d_e - r0 * n : nullptr;
-            MF_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
-            if (h->min_sites) MF_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, h->min_sites, nullptr));
-            if (dense_tc)
-                MF_RC(tracs_trans_dist_dense(bd, n, n, r0, r1, j_start, dist, d_days, lamb, beta, precision, 1, bp, be, nullptr));
-            MF_RC(tracs_coo_count(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), nullptr));
-            long long total = 0;
-            MF_CHECK(hipMemcpy(&total, d_off + (r1 - r0), 8, hipMemcpyDeviceToHost));
-            if (total <= 0) continue;
-            if ((size_t)total > cap) {
-                if (d_coo) MF_CHECK(hipFree(d_coo));
-                if (d_cp) MF_CHECK(hipFree(d_cp));
-                d_coo = nullptr; d_cp = nullptr;
-                cap = (size_t)total;
-                MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_coo), cap * 4 * n32));
-                if (with_dates) MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cp), cap * (filter ? 24 : 16)));
-            }
-            unsigned *c_rows = d_coo, *c_cols = d_coo + cap, *c_d = d_coo + 2 * cap, *c_n = d_coo + 3 * cap, *c_f = filter ? d_coo + 4 * cap : nullptr;
-            double *c_p = d_cp, *c_e = with_dates ? d_cp + cap : nullptr, *c_delta = (with_dates && filter) ? d_cp + 2 * cap : nullptr;
-            MF_RC(tracs_coo_fill(bd, bn, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), c_rows, c_cols, c_d, c_n, nullptr));
-            if (dense_tc)
-                MF_RC(tracs_coo_fill_f64(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), bp, be, c_p, c_e, nullptr));
-            if (filter) {
-                MF_RC(tracs_filter_recomb_pairs(a, c_rows, c_cols, c_d, (size_t)total, c_f, nullptr));
-                if (with_dates) {
-                    hipLaunchKernelGGL(coo_delta_kernel, dim3((unsigned)std::min<size_t>(((size_t)total + 255) / 256, 65535)), dim3(256), 0, nullptr, c_rows, c_cols,
-                                       d_days, (size_t)total, c_delta);
-                    MF_RC(tracs_trans_dist_device(reinterpret_cast<const int32_t *>(c_f), c_delta, (size_t)total, lamb, beta, precision, 1, c_p, c_e, nullptr));
-                }
-            }
-            // the weight the cluster step reads: column 3 (d), 6 (filtered d), 4 (P), 5 (E(K)); -K drops pairs with E(K) above it or NaN
-            const void *wv = weight == 0 ? (const void *)c_d : weight == 1 ? (const void *)c_f : weight == 2 ? (const void *)c_p : (const void *)c_e;
+    const double e_max = (days && k_max >= 0.0) ? k_max : -1.0;
+    PanelWalk walk(h->a, h->n_fasta, h->n0, dist, h->min_sites);
+    PairStage stage(walk, filter, lamb, beta, precision);
+    DeviceBuffer d_state;
+    if (walk.any()) {
+        if ((rc = d_state.alloc(tracs_msf_state_bytes(n))) || (rc = tracs_msf_init(d_state.ptr, n, nullptr))) return rc;
+        if (days && (rc = stage.set_days(days))) return rc;
+        if ((rc = walk.begin(true, stage.dense_tc()))) return rc;
+        PairColumns c;
+        for (Panel pn; walk.more();) {
+            if ((rc = walk.next(pn)) || (rc = stage.extract(pn, c))) return rc;
+            if (!c.total) continue;
+            // -K drops pairs with E(K) above it or NaN
             uint64_t taken = 0;
-            MF_RC(tracs_msf_update_coo(d_state, n, (size_t)total, c_rows, c_cols, wv, weight >= 2 ? 1 : 0, e_max >= 0.0 ? c_e : nullptr, e_max,
-                                       c_d, c_n, c_f, c_p, c_e, &taken, nullptr));
+            if ((rc = tracs_msf_update_coo(d_state.ptr, n, c.total, c.rows, c.cols, weight_column(c, weight), weight >= 2 ? 1 : 0,
+                                           e_max >= 0.0 ? c.e : nullptr, e_max, c.d, c.nn, c.filt, c.p, c.e, &taken, nullptr))) return rc;
             eligible += taken;
         }
         clock.mark("dense panels + transcluster + forest updates");
         size_t nf = 0;
-        MF_RC(tracs_msf_emit(d_state, n, &nf, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
-        if (nf) {
-            // the forest's rows: rows, cols, d, nn, filt (uint32), P, E(K) (f64) -- < n of them
-            if (d_coo) MF_CHECK(hipFree(d_coo));
-            if (d_cp) MF_CHECK(hipFree(d_cp));
-            d_coo = nullptr; d_cp = nullptr;
-            MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_coo), nf * 4 * 5));
-            MF_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cp), nf * 16));
-            MF_RC(tracs_msf_emit(d_state, n, &nf, d_coo, d_coo + nf, d_coo + 2 * nf, d_coo + 3 * nf, d_coo + 4 * nf, d_cp, d_cp + nf, nullptr));
-            std::vector<uint32_t> h32(nf * 5);
-            std::vector<double> h64(nf * 2);
-            MF_CHECK(hipMemcpy(h32.data(), d_coo, nf * 20, hipMemcpyDeviceToHost));
-            MF_CHECK(hipMemcpy(h64.data(), d_cp, nf * 16, hipMemcpyDeviceToHost));
-            const uint32_t *hr = h32.data(), *hc = hr + nf, *hd = hr + 2 * nf, *hn = hr + 3 * nf, *hf = hr + 4 * nf;
-            // the filtered column as the full run writes it: --filter: the filtered distances; else metadata on: "NA", off: zeros (:240-258)
-            MF_RC(writer.append_u32(hr, hc, hd, filter ? hf : (with_dates ? nullptr : hf), hn, days, with_dates ? h64.data() : nullptr,
-                                    with_dates ? h64.data() + nf : nullptr, nf, with_dates ? 1 : 0, -1.0));
-        }
+        if ((rc = tracs_msf_emit(d_state.ptr, n, &nf, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
+        stage.release();
+        if (nf && (rc = write_emitted_rows(nf, [&](unsigned *r, unsigned *cc, unsigned *d, unsigned *nn, unsigned *f, double *p, double *e) {
+                       return tracs_msf_emit(d_state.ptr, n, &nf, r, cc, d, nn, f, p, e, nullptr); }, writer, days, filter))) return rc;
         clock.mark("forest rows: emit, device -> host, format, write");
     }
-#undef MF_CHECK
-#undef MF_RC
-    cleanup();
-    const int rc = writer.close();
+    rc = writer.close();
     if (rows_written) *rows_written = writer.written();
     if (n_eligible) *n_eligible = eligible;
-    if (g_sigint) { set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+    if (g_sigint) return interrupted();
     return rc;
 }
 
-// `tracs distance --ancestors WEIGHT` for one alignment (include/tracs_hip.h): the panel loop of tracs_distance_forest
-// with tracs_anc_update_coo instead of the forest update; after the last panel the links are emitted and written through the same row
+// `tracs distance --ancestors WEIGHT` for one alignment (include/tracs_hip.h): as tracs_distance_forest, with
+// tracs_anc_update_coo instead of the forest update; after the last panel the links are emitted and written through the same row
 // writer, and the tree file is written from parent / root / generation.
 int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
                              int filter, int weight, const char *path, const char *ref, const char *tree_path,
@@ -1167,117 +1162,48 @@ int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, d
     if (!days) { set_error("tracs_distance_ancestors: sampling dates are required (they order the samples)"); return TRACS_E_ARG; }
     if (tree_path && !meta_dates) { set_error("tracs_distance_ancestors: the tree file needs the samples' dates as text"); return TRACS_E_ARG; }
     SigintScope sigint;
-    tracs_alignment *a = h->a;
-    const size_t n = a->n;
-    const size_t i_end = h->n_fasta == 1 ? n : h->n0;               // pair ranges (:348-360)
-    const size_t j_start = h->n_fasta == 1 ? 0 : h->n0;
-    const bool dense_tc = !filter;
-    // rows per panel (TRACS_FOREST_PANEL_ROWS: diagnostics -- small panels in tests, as tracs_distance_forest)
-    static const size_t PANEL_ROWS = [] { const char *e = std::getenv("TRACS_FOREST_PANEL_ROWS"); const long long v = e ? std::atoll(e) : 0; return v >= 1 ? (size_t)v : (size_t)0; }();
-    unsigned *d_dist = nullptr, *d_nn = nullptr, *d_coo = nullptr, *d_tree = nullptr;
-    double *d_p = nullptr, *d_e = nullptr, *d_cp = nullptr;
-    int *d_days = nullptr;
-    long long *d_off = nullptr;
-    void *d_state = nullptr;
+    const size_t n = h->a->n;
     tracs::DistanceRowWriter writer;
-    auto cleanup = [&]() {
-        void *q[] = {d_dist, d_nn, d_coo, d_tree, d_p, d_e, d_cp, d_days, d_off, d_state};
-        for (void *x : q) if (x) (void)hipFree(x);
-    };
-#define AN_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
-#define AN_RC(x) do { int r__ = (x); if (r__) { cleanup(); return r__; } } while (0)
-    AN_RC(writer.open(path, h->name_ptr.data(), h->name_ptr.size(), ref));
+    int rc = writer.open(path, h->name_ptr.data(), h->name_ptr.size(), ref);
+    if (rc) return rc;
     StageClock clock;
     uint64_t eligible = 0;
     const double e_max = k_max >= 0.0 ? k_max : -1.0;
     std::vector<uint32_t> tree(n * 3);                              // parent, root, generation
     for (size_t s = 0; s < n; s++) { tree[s] = 0xFFFFFFFFu; tree[n + s] = (uint32_t)s; tree[2 * n + s] = 0; }      // (no pair at all: every sample a root)
-    if (n >= 2 && i_end > 0 && j_start < n) {
-        const size_t panel = PANEL_ROWS ? std::min(PANEL_ROWS, i_end)
-                                        : std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
-        AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_days), n * 4));
-        AN_CHECK(hipMemcpy(d_days, days, n * 4, hipMemcpyHostToDevice));
-        AN_CHECK(hipMalloc(&d_state, tracs_anc_state_bytes(n)));
-        AN_RC(tracs_anc_init(d_state, n, d_days, nullptr));
-        AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dist), panel * n * 4));
-        AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_nn), panel * n * 4));
-        AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_off), (panel + 1) * 8));
-        if (dense_tc) {
-            AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_p), panel * n * 8));
-            AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_e), panel * n * 8));
-        }
-        const size_t n32 = filter ? 5 : 4;
-        size_t cap = 0;
-        for (size_t r0 = 0; r0 < i_end; r0 += panel) {
-            if (g_sigint) { cleanup(); set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
-            const size_t r1 = std::min(i_end, r0 + panel);
-            unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
-            double *bp = dense_tc ? d_p - r0 * n : nullptr, *be = dense_tc ? d_e - r0 * n : nullptr;
-            AN_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
-            if (h->min_sites) AN_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, h->min_sites, nullptr));
-            if (dense_tc)
-                AN_RC(tracs_trans_dist_dense(bd, n, n, r0, r1, j_start, dist, d_days, lamb, beta, precision, 1, bp, be, nullptr));
-            AN_RC(tracs_coo_count(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), nullptr));
-            long long total = 0;
-            AN_CHECK(hipMemcpy(&total, d_off + (r1 - r0), 8, hipMemcpyDeviceToHost));
-            if (total <= 0) continue;
-            if ((size_t)total > cap) {
-                if (d_coo) AN_CHECK(hipFree(d_coo));
-                if (d_cp) AN_CHECK(hipFree(d_cp));
-                d_coo = nullptr; d_cp = nullptr;
-                cap = (size_t)total;
-                AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_coo), cap * 4 * n32));
-                AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cp), cap * (filter ? 24 : 16)));
-            }
-            unsigned *c_rows = d_coo, *c_cols = d_coo + cap, *c_d = d_coo + 2 * cap, *c_n = d_coo + 3 * cap, *c_f = filter ? d_coo + 4 * cap : nullptr;
-            double *c_p = d_cp, *c_e = d_cp + cap, *c_delta = filter ? d_cp + 2 * cap : nullptr;
-            AN_RC(tracs_coo_fill(bd, bn, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), c_rows, c_cols, c_d, c_n, nullptr));
-            if (dense_tc)
-                AN_RC(tracs_coo_fill_f64(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), bp, be, c_p, c_e, nullptr));
-            if (filter) {
-                AN_RC(tracs_filter_recomb_pairs(a, c_rows, c_cols, c_d, (size_t)total, c_f, nullptr));
-                hipLaunchKernelGGL(coo_delta_kernel, dim3((unsigned)std::min<size_t>(((size_t)total + 255) / 256, 65535)), dim3(256), 0, nullptr, c_rows, c_cols,
-                                   d_days, (size_t)total, c_delta);
-                AN_RC(tracs_trans_dist_device(reinterpret_cast<const int32_t *>(c_f), c_delta, (size_t)total, lamb, beta, precision, 1, c_p, c_e, nullptr));
-            }
-            // the value a source is chosen by: d, filtered d and E(K) ascending, P(direct) descending; -K drops pairs with E(K) above it or NaN
-            const void *wv = weight == 0 ? (const void *)c_d : weight == 1 ? (const void *)c_f : weight == 2 ? (const void *)c_p : (const void *)c_e;
+    PanelWalk walk(h->a, h->n_fasta, h->n0, dist, h->min_sites);
+    PairStage stage(walk, filter, lamb, beta, precision);
+    DeviceBuffer d_state, d_tree;
+    if (walk.any()) {
+        // the day numbers on the device first: they order the samples of the state
+        if ((rc = stage.set_days(days))) return rc;
+        if ((rc = d_state.alloc(tracs_anc_state_bytes(n))) || (rc = tracs_anc_init(d_state.ptr, n, stage.days(), nullptr))) return rc;
+        if ((rc = walk.begin(true, stage.dense_tc()))) return rc;
+        PairColumns c;
+        for (Panel pn; walk.more();) {
+            if ((rc = walk.next(pn)) || (rc = stage.extract(pn, c))) return rc;
+            if (!c.total) continue;
+            // a source is chosen by d, filtered d and E(K) ascending, P(direct) descending; -K drops pairs with E(K) above it or NaN
             uint64_t taken = 0;
-            AN_RC(tracs_anc_update_coo(d_state, n, (size_t)total, c_rows, c_cols, wv, weight == 2 ? 2 : weight == 3 ? 1 : 0,
-                                       e_max >= 0.0 ? c_e : nullptr, e_max, c_d, c_n, c_f, c_p, c_e, &taken, nullptr));
+            if ((rc = tracs_anc_update_coo(d_state.ptr, n, c.total, c.rows, c.cols, weight_column(c, weight), weight == 2 ? 2 : weight == 3 ? 1 : 0,
+                                           e_max >= 0.0 ? c.e : nullptr, e_max, c.d, c.nn, c.filt, c.p, c.e, &taken, nullptr))) return rc;
             eligible += taken;
         }
         clock.mark("dense panels + transcluster + ancestor updates");
         size_t nl = 0;
-        AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_tree), n * 12));
-        AN_RC(tracs_anc_emit(d_state, n, &nl, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_tree, d_tree + n, d_tree + 2 * n, nullptr));
-        AN_CHECK(hipMemcpy(tree.data(), d_tree, n * 12, hipMemcpyDeviceToHost));
-        if (nl) {
-            // the links' rows: rows, cols, d, nn, filt (uint32), P, E(K) (f64) -- < n of them
-            if (d_coo) AN_CHECK(hipFree(d_coo));
-            if (d_cp) AN_CHECK(hipFree(d_cp));
-            d_coo = nullptr; d_cp = nullptr;
-            AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_coo), nl * 4 * 5));
-            AN_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cp), nl * 16));
-            AN_RC(tracs_anc_emit(d_state, n, &nl, d_coo, d_coo + nl, d_coo + 2 * nl, d_coo + 3 * nl, d_coo + 4 * nl, d_cp, d_cp + nl, nullptr, nullptr,
-                                 nullptr, nullptr));
-            std::vector<uint32_t> h32(nl * 5);
-            std::vector<double> h64(nl * 2);
-            AN_CHECK(hipMemcpy(h32.data(), d_coo, nl * 20, hipMemcpyDeviceToHost));
-            AN_CHECK(hipMemcpy(h64.data(), d_cp, nl * 16, hipMemcpyDeviceToHost));
-            const uint32_t *hr = h32.data(), *hc = hr + nl, *hd = hr + 2 * nl, *hn = hr + 3 * nl, *hf = hr + 4 * nl;
-            // the filtered column as the full run writes it with metadata: --filter: the filtered distances; else "NA" (:204)
-            AN_RC(writer.append_u32(hr, hc, hd, filter ? hf : nullptr, hn, days, h64.data(), h64.data() + nl, nl, 1, -1.0));
-        }
+        if ((rc = d_tree.alloc(n * 12))) return rc;
+        unsigned *t = d_tree.as<unsigned>();
+        if ((rc = tracs_anc_emit(d_state.ptr, n, &nl, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, t, t + n, t + 2 * n, nullptr))) return rc;
+        TRACS_HIP_CHECK(hipMemcpy(tree.data(), t, n * 12, hipMemcpyDeviceToHost));
+        stage.release();
+        if (nl && (rc = write_emitted_rows(nl, [&](unsigned *r, unsigned *cc, unsigned *d, unsigned *nn, unsigned *f, double *p, double *e) {
+                       return tracs_anc_emit(d_state.ptr, n, &nl, r, cc, d, nn, f, p, e, nullptr, nullptr, nullptr, nullptr); }, writer, days, filter))) return rc;
         clock.mark("ancestor rows: emit, device -> host, format, write");
     }
-#undef AN_CHECK
-#undef AN_RC
-    cleanup();
-    int rc = writer.close();
+    rc = writer.close();
     if (rows_written) *rows_written = writer.written();
     if (n_eligible) *n_eligible = eligible;
-    if (g_sigint) { set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+    if (g_sigint) return interrupted();
     if (rc == TRACS_OK && tree_path) {
         // one line per sample, in order, from parent / root / generation
         std::FILE *fh = std::fopen(tree_path, "ab");
@@ -1293,9 +1219,9 @@ int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, d
     return rc;
 }
 
-// `tracs distance --histogram` for one alignment (include/tracs_hip.h): the panel loop of tracs_distance_run with
+// `tracs distance --histogram` for one alignment (include/tracs_hip.h): the panel walk of tracs_distance_run with
 // tracs_hist_update on each dense panel instead of the rows; with --filter the panel's pairs within the threshold are extracted and
-// filtered as tracs_distance_run does, and a second state counts their filtered distances.  What crosses to the host is the
+// filtered by the same pair stage, and a second state counts their filtered distances.  What crosses to the host is the
 // non-empty bins.
 int tracs_distance_histogram(tracs_distance *h, int dist, int filter, const int32_t *group, const char *path, const char *ref,
                              uint64_t *n_eligible, uint64_t *rows_written)
@@ -1305,84 +1231,46 @@ int tracs_distance_histogram(tracs_distance *h, int dist, int filter, const int3
     if (!h || !h->a || !path || !ref) { set_error("tracs_distance_histogram: NULL argument"); return TRACS_E_ARG; }
     if (dist < 0) { set_error("tracs_distance_histogram: dist must not be negative"); return TRACS_E_ARG; }
     SigintScope sigint;
-    tracs_alignment *a = h->a;
-    const size_t n = a->n;
-    const size_t i_end = h->n_fasta == 1 ? n : h->n0;               // pair ranges (:348-360)
-    const size_t j_start = h->n_fasta == 1 ? 0 : h->n0;
-    const size_t n_bins = std::min<size_t>(a->L, (size_t)dist) + 1;  // d <= L and d <= dist: no eligible value falls outside
-    // rows per panel (TRACS_FOREST_PANEL_ROWS: diagnostics -- small panels in tests, as tracs_distance_forest)
-    static const size_t PANEL_ROWS = [] { const char *e = std::getenv("TRACS_FOREST_PANEL_ROWS"); const long long v = e ? std::atoll(e) : 0; return v >= 1 ? (size_t)v : (size_t)0; }();
-    unsigned *d_dist = nullptr, *d_nn = nullptr, *d_coo = nullptr, *d_val = nullptr;
-    int *d_group = nullptr;
-    long long *d_off = nullptr;
-    void *d_state[2] = {nullptr, nullptr};
-    uint64_t *d_cnt = nullptr;
-    auto cleanup = [&]() {
-        void *q[] = {d_dist, d_nn, d_coo, d_val, d_group, d_off, d_state[0], d_state[1], d_cnt};
-        for (void *x : q) if (x) (void)hipFree(x);
-    };
-#define HG_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
-#define HG_RC(x) do { int r__ = (x); if (r__) { cleanup(); return r__; } } while (0)
+    const size_t n = h->a->n;
+    const size_t n_bins = std::min<size_t>(h->a->L, (size_t)dist) + 1;  // d <= L and d <= dist: no eligible value falls outside
     FILE *fp = std::fopen(path, "ab");
     if (!fp) { set_error(std::string("cannot open ") + path + " for appending"); return TRACS_E_OPEN; }
     struct Closer { FILE *&f; ~Closer() { if (f) std::fclose(f); } } closer{fp};
     StageClock clock;
     uint64_t eligible = 0, written = 0;
-    if (n >= 2 && i_end > 0 && j_start < n) {
-        const size_t panel = PANEL_ROWS ? std::min(PANEL_ROWS, i_end)
-                                        : std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
+    PanelWalk walk(h->a, h->n_fasta, h->n0, dist, h->min_sites);
+    PairStage stage(walk, filter);                                   // (used only under --filter: five uint32 columns, no dates)
+    DeviceBuffer d_state[2], d_group, d_val, d_cnt;
+    if (walk.any()) {
+        int rc;
         const int n_states = filter ? 2 : 1;
-        for (int s = 0; s < n_states; s++) {
-            HG_CHECK(hipMalloc(&d_state[s], tracs_hist_state_bytes(n_bins)));
-            HG_RC(tracs_hist_init(d_state[s], n_bins, nullptr));
-        }
-        HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_dist), panel * n * 4));
-        HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_nn), panel * n * 4));
-        if (group) {
-            HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_group), n * 4));
-            HG_CHECK(hipMemcpy(d_group, group, n * 4, hipMemcpyHostToDevice));
-        }
-        if (filter) HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_off), (panel + 1) * 8));
-        size_t cap = 0;
-        for (size_t r0 = 0; r0 < i_end; r0 += panel) {
-            if (g_sigint) { cleanup(); set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
-            const size_t r1 = std::min(i_end, r0 + panel);
-            unsigned *bd = d_dist - r0 * n, *bn = d_nn - r0 * n;     // addressed as base[i * ld + j] with i absolute
-            HG_RC(tracs_pairsnp_dense_thr(a, r0, r1, j_start, bd, bn, n, dist, nullptr));
-            if (h->min_sites) HG_RC(pairs_min_sites(bd, bn, n, n, r0, r1, j_start, dist, h->min_sites, nullptr));
-            HG_RC(tracs_hist_update(bd, n, n, r0, r1, j_start, dist, d_group, d_state[0], n_bins, nullptr));
+        for (int s = 0; s < n_states; s++)
+            if ((rc = d_state[s].alloc(tracs_hist_state_bytes(n_bins))) || (rc = tracs_hist_init(d_state[s].ptr, n_bins, nullptr))) return rc;
+        if ((rc = walk.begin(filter != 0, false))) return rc;
+        if (group && (rc = d_group.upload(group, n * 4))) return rc;
+        PairColumns c;
+        for (Panel pn; walk.more();) {
+            if ((rc = walk.next(pn))) return rc;
+            if ((rc = tracs_hist_update(pn.bd, n, n, pn.r0, pn.r1, walk.j_start, dist, d_group.as<int>(), d_state[0].ptr, n_bins, nullptr))) return rc;
             if (!filter) continue;
             // the filtered distances of the panel's eligible pairs (src/pairsnp.hpp:405-413), as tracs_distance_run takes them
-            HG_RC(tracs_coo_count(bd, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), nullptr));
-            long long total = 0;
-            HG_CHECK(hipMemcpy(&total, d_off + (r1 - r0), 8, hipMemcpyDeviceToHost));
-            if (total <= 0) continue;
-            if ((size_t)total > cap) {
-                if (d_coo) { void *old = d_coo; d_coo = nullptr; HG_CHECK(hipFree(old)); }
-                cap = (size_t)total;
-                HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_coo), cap * 4 * 5));
-            }
-            unsigned *c_rows = d_coo, *c_cols = d_coo + cap, *c_d = d_coo + 2 * cap, *c_n = d_coo + 3 * cap, *c_f = d_coo + 4 * cap;
-            HG_RC(tracs_coo_fill(bd, bn, n, n, r0, r1, j_start, dist, reinterpret_cast<int64_t *>(d_off), c_rows, c_cols, c_d, c_n, nullptr));
-            HG_RC(tracs_filter_recomb_pairs(a, c_rows, c_cols, c_d, (size_t)total, c_f, nullptr));
-            HG_RC(tracs_hist_update_coo(c_rows, c_cols, c_f, (size_t)total, d_group, d_state[1], n_bins, nullptr));
+            if ((rc = stage.extract(pn, c))) return rc;
+            if (c.total && (rc = tracs_hist_update_coo(c.rows, c.cols, c.filt, c.total, d_group.as<int>(), d_state[1].ptr, n_bins, nullptr))) return rc;
         }
         clock.mark("dense panels + histogram updates");
         static const char *const column[2] = {"snp", "filter"};
         std::string text;
         for (int s = 0; s < n_states; s++) {
             size_t nr = 0;
-            HG_RC(tracs_hist_emit(d_state[s], n_bins, &nr, nullptr, nullptr, nullptr, nullptr, nullptr));
+            if ((rc = tracs_hist_emit(d_state[s].ptr, n_bins, &nr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
             if (!nr) continue;
-            if (d_val) { void *old = d_val; d_val = nullptr; HG_CHECK(hipFree(old)); }
-            if (d_cnt) { void *old = d_cnt; d_cnt = nullptr; HG_CHECK(hipFree(old)); }
-            HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_val), nr * 4));
-            HG_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cnt), nr * 8 * 3));
-            HG_RC(tracs_hist_emit(d_state[s], n_bins, &nr, d_val, d_cnt, d_cnt + nr, d_cnt + 2 * nr, nullptr));
+            if ((rc = d_val.alloc(nr * 4)) || (rc = d_cnt.alloc(nr * 8 * 3))) return rc;
+            uint64_t *cnt = d_cnt.as<uint64_t>();
+            if ((rc = tracs_hist_emit(d_state[s].ptr, n_bins, &nr, d_val.as<unsigned>(), cnt, cnt + nr, cnt + 2 * nr, nullptr))) return rc;
             std::vector<uint32_t> hv(nr);
             std::vector<uint64_t> hc(nr * 3);
-            HG_CHECK(hipMemcpy(hv.data(), d_val, nr * 4, hipMemcpyDeviceToHost));
-            HG_CHECK(hipMemcpy(hc.data(), d_cnt, nr * 24, hipMemcpyDeviceToHost));
+            TRACS_HIP_CHECK(hipMemcpy(hv.data(), d_val.ptr, nr * 4, hipMemcpyDeviceToHost));
+            TRACS_HIP_CHECK(hipMemcpy(hc.data(), cnt, nr * 24, hipMemcpyDeviceToHost));
             char line[160];
             for (size_t t = 0; t < nr; t++) {
                 const int k = std::snprintf(line, sizeof line, "%s,%u,%llu,%llu,%llu,", column[s], hv[t], (unsigned long long)hc[t],
@@ -1395,21 +1283,17 @@ int tracs_distance_histogram(tracs_distance *h, int dist, int filter, const int3
             written += nr;
         }
         if (!text.empty() && std::fwrite(text.data(), 1, text.size(), fp) != text.size()) {
-            cleanup();
             set_error(std::string("write to ") + path + " failed");
             return TRACS_E_OPEN;
         }
         clock.mark("histogram rows: emit, device -> host, format, write");
     }
-#undef HG_CHECK
-#undef HG_RC
-    cleanup();
     const int rc_close = std::fclose(fp);
     fp = nullptr;
     if (rc_close != 0) { set_error(std::string("write to ") + path + " failed"); return TRACS_E_OPEN; }
     if (rows_written) *rows_written = written;
     if (n_eligible) *n_eligible = eligible;
-    if (g_sigint) { set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
+    if (g_sigint) return interrupted();
     return TRACS_OK;
 }
 

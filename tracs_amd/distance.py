@@ -5,6 +5,7 @@ flags :15-131, dates CSV :145-151, per-MSA pairsnp :159-176, transmission block 
 CSV rows :206-258 (header :157).  The pair loop and the transcluster integral run on the MI355X.
 """
 import argparse
+import contextlib
 import ctypes as C
 import logging
 import math
@@ -210,6 +211,43 @@ def _append_rows(path, names, rows, cols, snpd, filt, ncomp, ddiff, tdist, ek, k
     return written.value
 
 
+class _MissingDate(KeyError):
+    """a compared sample that --meta does not list (the full-output route then leaves the alignment to the array route)"""
+
+
+def _names_of(L, h):
+    return [L.tracs_distance_name(h, i).decode("utf-8", "replace") for i in range(L.tracs_distance_nseq(h))]
+
+
+def _days_of(L, h, dates, option, metadata=None):
+    """The day numbers of the handle's samples, in order, as the c_int32 array the library takes.  A sample without a date:
+    SystemExit naming `option` and the metadata file, or -- option None, the full-output route -- _MissingDate."""
+    epoch = date(1970, 1, 1)
+    got = []
+    for name in _names_of(L, h):
+        if name not in dates:
+            if option is None:
+                raise _MissingDate(name)
+            raise SystemExit("tracs distance %s: sample '%s' has no sampling date in %s" % (option, name, metadata))
+        got.append((dates[name][1] - epoch).days)
+    return (C.c_int32 * max(len(got), 1))(*got)
+
+
+@contextlib.contextmanager
+def _opened(msas, args, stage, rule=None, contigs=None):
+    """One alignment's handle for the body of a device-resident route: opened with the rule (tracs_distance_open*), its [sum] stage
+    line, -> (library, handle); after the body --msa-out / --site-table from the same handle; freed whatever happens (a body that
+    raises skips those outputs)."""
+    L = _lib.require_gpu()
+    h = _open(L, msas, rule, args)
+    try:
+        stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
+        yield L, h
+        write_msa_outputs(L, h, args, msas[0], contigs)
+    finally:
+        L.tracs_distance_free(h)
+
+
 def _rows_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
     """One alignment through libtracs_hip.so's device-resident path (tracs_distance_open / _run: include/tracs_hip.h): FASTA -> packed
     planes -> dense panels -> transcluster on the panels -> the pairs within the threshold with their P and E(K) -> ONE device-to-host
@@ -217,52 +255,31 @@ def _rows_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
     sample names (to look the dates up).  -> False when the path does not apply: a sample without a date (the reference raises KeyError
     only if that sample's index is at most the largest index among the emitted pairs, tracs/transcluster.py:23-32: left to the
     array path below, which reproduces that)."""
-    L = _lib.require_gpu()
-    h = _open(L, msas, rule, args)
     try:
-        stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
-        days = None
-        if dates is not None:
-            n = L.tracs_distance_nseq(h)
-            epoch = date(1970, 1, 1)
-            try:
-                days = (C.c_int32 * max(n, 1))(*[(dates[L.tracs_distance_name(h, i).decode("utf-8", "replace")][1] - epoch).days for i in range(n)])
-            except KeyError:
-                return False
-        written, pairs = C.c_uint64(0), C.c_uint64(0)
-        if dates is not None:
-            logging.info("Inferring transmission probabilities for %s", msas[0])
-        kmax = -1.0 if (args.trans_threshold is None or dates is None) else float(args.trans_threshold)
-        _lib.check(L.tracs_distance_run(h, int(args.snp_threshold), days, float(args.clock_rate), float(args.trans_rate), float(args.precision),
-                                        kmax, os.fsencode(args.output_file), ref.encode(), int(bool(args.recomb_filter)), C.byref(written),
-                                        C.byref(pairs)))
-        stage("[sum] tracs_distance_run (dense panels, transcluster, rows: %d pairs, %d rows written)" % (pairs.value, written.value))
-        write_msa_outputs(L, h, args, msas[0], contigs)
-        return True
-    finally:
-        L.tracs_distance_free(h)
+        with _opened(msas, args, stage, rule, contigs) as (L, h):
+            days = _days_of(L, h, dates, None) if dates is not None else None
+            written, pairs = C.c_uint64(0), C.c_uint64(0)
+            if dates is not None:
+                logging.info("Inferring transmission probabilities for %s", msas[0])
+            kmax = -1.0 if (args.trans_threshold is None or dates is None) else float(args.trans_threshold)
+            _lib.check(L.tracs_distance_run(h, int(args.snp_threshold), days, float(args.clock_rate), float(args.trans_rate), float(args.precision),
+                                            kmax, os.fsencode(args.output_file), ref.encode(), int(bool(args.recomb_filter)), C.byref(written),
+                                            C.byref(pairs)))
+            stage("[sum] tracs_distance_run (dense panels, transcluster, rows: %d pairs, %d rows written)" % (pairs.value, written.value))
+    except _MissingDate:
+        return False
+    return True
 
 
 def _forest_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
-    """--mst WEIGHT for one alignment (tracs_distance_open / _forest: include/tracs_hip.h): the panel loop of _rows_on_device up to the
+    """--mst WEIGHT for one alignment (tracs_distance_open / _forest: include/tracs_hip.h): the panel walk of _rows_on_device up to the
     pairs within the threshold with their P and E(K), then the minimum spanning forest of the eligible pairs on the device; only its
     rows are formatted and appended.  With metadata every sample needs a date (the full run's array route has KeyError rules of its
     own instead)."""
-    L = _lib.require_gpu()
-    h = _open(L, msas, rule, args)
-    try:
-        stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
+    with _opened(msas, args, stage, rule, contigs) as (L, h):
         days = None
         if dates is not None:
-            n = L.tracs_distance_nseq(h)
-            epoch = date(1970, 1, 1)
-            got = []
-            for i in range(n):
-                name = L.tracs_distance_name(h, i).decode("utf-8", "replace")
-                if name not in dates:
-                    raise SystemExit("tracs distance --mst: sample '%s' has no sampling date in %s" % (name, args.metadata))
-                got.append((dates[name][1] - epoch).days)
-            days = (C.c_int32 * max(n, 1))(*got)
+            days = _days_of(L, h, dates, "--mst", args.metadata)
             logging.info("Inferring transmission probabilities for %s", msas[0])
         written, eligible = C.c_uint64(0), C.c_uint64(0)
         kmax = -1.0 if (args.trans_threshold is None or dates is None) else float(args.trans_threshold)
@@ -271,32 +288,20 @@ def _forest_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
                                            os.fsencode(args.output_file), ref.encode(), C.byref(written), C.byref(eligible)))
         stage("[sum] tracs_distance_forest (dense panels, transcluster, forest: %d eligible pairs, %d rows written)"
               % (eligible.value, written.value))
-        write_msa_outputs(L, h, args, msas[0], contigs)
-    finally:
-        L.tracs_distance_free(h)
 
 
 def _ancestors_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
-    """--ancestors WEIGHT for one alignment (tracs_distance_open / _ancestors: include/tracs_hip.h): the panel loop of
+    """--ancestors WEIGHT for one alignment (tracs_distance_open / _ancestors: include/tracs_hip.h): the panel walk of
     _forest_on_device with, instead of the forest, each later-dated sample's best earlier partner kept on the device; only the chosen
     pairs' rows are formatted and appended, and --ancestors-out gets one line per compared sample.  Every compared sample needs a
     date (checked on the opened handle: samples the sample rule left out need none)."""
-    L = _lib.require_gpu()
-    h = _open(L, msas, rule, args)
-    try:
-        stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
-        n = L.tracs_distance_nseq(h)
-        epoch = date(1970, 1, 1)
-        got, text = [], []
-        for i in range(n):
-            name = L.tracs_distance_name(h, i).decode("utf-8", "replace")
-            if name not in dates:
-                raise SystemExit("tracs distance --ancestors: sample '%s' has no sampling date in %s" % (name, args.metadata))
-            got.append((dates[name][1] - epoch).days)
-            text.append(dates[name][0].encode())
-        days = (C.c_int32 * max(n, 1))(*got)
+    with _opened(msas, args, stage, rule, contigs) as (L, h):
+        days = _days_of(L, h, dates, "--ancestors", args.metadata)
         tree = getattr(args, "ancestors_out", None)
-        meta_dates = (C.c_char_p * max(n, 1))(*text) if tree is not None else None
+        meta_dates = None
+        if tree is not None:
+            text = [dates[name][0].encode() for name in _names_of(L, h)]
+            meta_dates = (C.c_char_p * max(len(text), 1))(*text)
         logging.info("Inferring transmission probabilities for %s", msas[0])
         written, eligible = C.c_uint64(0), C.c_uint64(0)
         kmax = -1.0 if args.trans_threshold is None else float(args.trans_threshold)
@@ -306,9 +311,6 @@ def _ancestors_on_device(msas, args, dates, ref, stage, rule=None, contigs=None)
                                               meta_dates, C.byref(written), C.byref(eligible)))
         stage("[sum] tracs_distance_ancestors (dense panels, transcluster, ancestors: %d candidates, %d rows written)"
               % (eligible.value, written.value))
-        write_msa_outputs(L, h, args, msas[0], contigs)
-    finally:
-        L.tracs_distance_free(h)
 
 
 def check_ancestors_args(args):
@@ -543,9 +545,7 @@ def site_rule_for(msas, args, files):
     sample_share, min_sites = getattr(args, "max_sample_n_share", None), getattr(args, "min_sites", None)
     if keep_iv is None and mask_iv is None and share is None and sample_share is None and min_sites is None:
         return None
-    for p in msas:
-        if not os.path.exists(p):
-            raise FileNotFoundError(p)
+    _require_files(msas)
     L = S.first_record_length(msas[0]) if (keep_iv is not None or mask_iv is not None or share is not None) else 0      # (0: no site rule)
     keep = None
     if keep_iv is not None or mask_iv is not None:
@@ -652,17 +652,15 @@ def read_groups(path):
 
 
 def _histogram_on_device(msas, args, groups, ref, stage, rule=None, contigs=None):
-    """--histogram for one alignment (tracs_distance_open / _histogram: include/tracs_hip.h): the panel loop of _rows_on_device with
+    """--histogram for one alignment (tracs_distance_open / _histogram: include/tracs_hip.h): the panel walk of _rows_on_device with
     a histogram update per panel instead of the rows; only the non-empty bins are formatted and appended."""
     from .api import group_labels
-    L = _lib.require_gpu()
-    h = _open(L, msas, rule, args)
-    try:
-        stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
+    with _opened(msas, args, stage, rule, contigs) as (L, h):
         labels = None
         if groups is not None:
-            n = L.tracs_distance_nseq(h)
-            lab = group_labels([L.tracs_distance_name(h, i).decode("utf-8", "replace") for i in range(n)], groups)
+            names = _names_of(L, h)
+            n = len(names)
+            lab = group_labels(names, groups)
             labels = (C.c_int32 * max(n, 1))(*[int(x) for x in lab])
             logging.info("%d of %d samples of %s have a group label (%d groups)", int((lab >= 0).sum()), n, msas[0],
                          int(lab.max()) + 1 if n else 0)
@@ -670,9 +668,6 @@ def _histogram_on_device(msas, args, groups, ref, stage, rule=None, contigs=None
         _lib.check(L.tracs_distance_histogram(h, int(args.snp_threshold), int(bool(args.recomb_filter)), labels,
                                               os.fsencode(args.output_file), ref.encode(), C.byref(eligible), C.byref(written)))
         stage("[sum] tracs_distance_histogram (dense panels, histogram: %d pairs counted, %d rows written)" % (eligible.value, written.value))
-        write_msa_outputs(L, h, args, msas[0], contigs)
-    finally:
-        L.tracs_distance_free(h)
 
 
 def _cli_of(args):
@@ -730,6 +725,12 @@ def _pairs_multi_gpu(msas, args, ctx):
     return host[0], host[1], host[2], names, filt, host[3]
 
 
+def _require_files(msas):
+    for p in msas:
+        if not os.path.exists(p):
+            raise FileNotFoundError(p)
+
+
 def distance(args):
     check_ancestors_args(args)
     check_mst_args(args)
@@ -743,8 +744,6 @@ def distance(args):
     mst = getattr(args, "mst", None)
     ancestors = getattr(args, "ancestors", None)
     nearest = getattr(args, "nearest", None)
-    if nearest is not None and ancestors is not None:
-        raise SystemExit("tracs distance: --ancestors and --nearest cannot be combined")
     if nearest is not None and getattr(args, "gpus", 1) > 1:
         raise SystemExit("tracs distance: --nearest runs on one GPU; use --gpus 1")
     from . import multigpu
@@ -801,34 +800,26 @@ def distance(args):
             ruled["contigs"] = site_files[2]
         if histogram:
             # how many of the pairs the full run would write have each SNP distance (one GPU, counted on the device)
-            for p in msas:
-                if not os.path.exists(p):
-                    raise FileNotFoundError(p)
+            _require_files(msas)
             _histogram_on_device(msas, args, groups, ref, stage, **ruled)
             logging.info("Saving the distance histogram for %s", msa)
             continue
         if mst is not None:
             # the minimum spanning forest of the pairs the full run would write (one GPU, on the device until its rows)
-            for p in msas:
-                if not os.path.exists(p):
-                    raise FileNotFoundError(p)
+            _require_files(msas)
             _forest_on_device(msas, args, dates, ref, stage, **ruled)
             logging.info("Saving the minimum spanning forest for %s", msa)
             continue
         if ancestors is not None:
             # each sample's most likely earlier source among the pairs the full run would write (one GPU, on the device until its rows)
-            for p in msas:
-                if not os.path.exists(p):
-                    raise FileNotFoundError(p)
+            _require_files(msas)
             _ancestors_on_device(msas, args, dates, ref, stage, **ruled)
             logging.info("Saving the ancestor links for %s", msa)
             continue
         if ctx is None and nearest is None and os.environ.get("TRACS_DISTANCE_ARRAYS") is None:
             # one GPU: the results stay on the device until the CSV rows (with --filter: the filtered distances and the transmission
             # model they drive too)
-            for p in msas:
-                if not os.path.exists(p):
-                    raise FileNotFoundError(p)               # (api.pairsnp_arrays's diagnosis; the reference passes a NULL gzFile on)
+            _require_files(msas)                             # (api.pairsnp_arrays's diagnosis; the reference passes a NULL gzFile on)
             if _rows_on_device(msas, args, dates, ref, stage, **ruled):
                 logging.info("Saving distances for %s", msa)
                 continue
