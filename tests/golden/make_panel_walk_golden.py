@@ -1,6 +1,8 @@
 """Writes tests/golden/panel_walk_golden.json: sha256 and row count of every CSV that tests/test_gpu_panel_walk.py compares, as a
 given build of libtracs_hip.so writes them at its default panel height.  The file in the repository comes from a build of the commit
 BEFORE the host entry points shared one panel walk, so the test pins the refactored code to the bytes of the code it replaced.
+The mst_* and ancestors_* entries come from a build of commit 27c4601 (before forest.hip and ancestors.hip shared csrc/pair_select.h);
+that build wrote the eight older entries as they stood, so one run of this script at that commit gives the whole file.
 Needs a GPU.  Inputs, routes and options are the test's own (imported from it); nothing here is an expected value.
 
 usage: python tests/golden/make_panel_walk_golden.py DIRECTORY_WITH_libtracs_hip.so [OUT.json]"""

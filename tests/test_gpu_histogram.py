@@ -237,6 +237,29 @@ def test_hist_update_panel_splits(hiplib, oracle):
     aln.close()
 
 
+@pytest.mark.parametrize("n_bins", [1023 * 1024, 1024 * 1024, 1024 * 1024 + 1, 2048 * 1024 + 1])
+def test_hist_emit_at_scan_seams(hiplib, n_bins):
+    """tracs_hist_emit scans the per-chunk counts of non-empty bins (chunks of 1 024 bins) in one workgroup that steps by 1 024 and
+    writes the total at index `chunks`: 1 023, 1 024, 1 025 and 2 049 chunks.  One ungrouped batch: a seeded draw of bins plus the
+    first and last bin of the range and of the chunks around the step, some of them repeated; expected from np.unique."""
+    import torch
+
+    from tracs_amd import device as dev
+    rng = np.random.default_rng(1024)
+    edges = [0, n_bins - 1] + [b for c in (1022, 1023, 1024, 1025) for b in (c * 1024, c * 1024 + 1023)]
+    edges = [b for b in edges if b < n_bins]
+    values = np.concatenate([rng.integers(0, n_bins, 3000), edges, edges[::2], rng.integers(0, n_bins, 50).repeat(3)]).astype(np.int64)
+    rng.shuffle(values)
+    assert (n_bins + 1023) // 1024 in (1023, 1024, 1025, 2049) and values.max() == n_bins - 1 and values.min() == 0
+    uniq, counts = np.unique(values, return_counts=True)
+    assert counts.max() >= 3 and len(uniq) > 3000
+    zeros = np.zeros(len(uniq), np.uint64)
+    val = torch.from_numpy(values.astype(np.int32)).cuda()
+    state = dev.hist_init(n_bins)
+    dev.hist_update_coo(state, n_bins, torch.zeros_like(val), torch.ones_like(val), val)
+    check(emitted(state, n_bins), [uniq.astype(np.uint64), zeros, zeros, counts.astype(np.uint64)], ("scan seam", n_bins))
+
+
 def test_histogram_ties(hiplib, oracle, tmp_path):
     n, L = 200, 3000
     same = np.repeat(seqs_for(1, L, seed=4, p_n=0.0, p_partial=0.0), n, axis=0)

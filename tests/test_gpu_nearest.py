@@ -139,6 +139,44 @@ def test_knn_update_panel_splits(hiplib, oracle):
     aln.close()
 
 
+def seam_distances(n, xp):
+    """The scan-seam test's d[i][j], symmetric and in [0, max(5, n // 2)), from the indices alone; xp: numpy or torch-on-the-device
+    (arange, minimum, maximum).  About 4 partners of a sample have d <= 1, so lists of every length up to k = 3 occur."""
+    i, j = xp.arange(n).reshape(n, 1), xp.arange(n).reshape(1, n)
+    lo, hi = xp.minimum(i, j), xp.maximum(i, j)
+    return (lo * 7919 + hi * 104729 + lo * hi) % 1000003 % max(5, n // 2)
+
+
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 2048, 2049])
+def test_knn_emit_at_scan_seams(hiplib, n):
+    """tracs_knn_emit scans the lists' lengths in one workgroup that steps by 1 024 and writes the total at index n: n on, one below
+    and one above a multiple of the step, and more than one step.  The lists come from a formula, the expected ones from NumPy."""
+    import torch
+
+    from tracs_amd import device as dev
+    k, thr, ncomp = 3, 1, 777
+    D = seam_distances(n, np)
+    mask = (D <= thr) & ~np.eye(n, dtype=bool)
+    lengths = np.minimum(mask.sum(axis=1), k)
+    if n >= 1023:                                       # the offsets are not a constant stride
+        assert set(np.unique(lengths).tolist()) == {0, 1, 2, 3}
+    r, c = np.nonzero(mask)
+    o = np.lexsort((c, D[r, c], r))
+    r, c = r[o], c[o]
+    keep = np.arange(len(r)) - np.searchsorted(r, r) < k
+    exp = [r[keep], c[keep], D[r, c][keep], np.full(int(keep.sum()), ncomp)]
+    assert len(exp[0]) == int(lengths.sum())
+    class on_device:                                    # int64 index arithmetic on the GPU
+        arange = staticmethod(lambda m: torch.arange(m, dtype=torch.int64, device="cuda"))
+        minimum, maximum = torch.minimum, torch.maximum
+    d = seam_distances(n, on_device).to(torch.int32).contiguous()
+    nn = torch.full((n, n), ncomp, dtype=torch.int32, device="cuda")
+    state = dev.knn_init(n, k)
+    dev.knn_update(state, d, nn, n, k, dist_threshold=thr)
+    got = [t.cpu().numpy().astype(np.uint32) for t in dev.knn_emit(state, k, 0, n)]
+    check(got, [np.asarray(e).astype(np.uint64) for e in exp], ("scan seam", n))
+
+
 @pytest.mark.parametrize("k", [100, 300])
 def test_knn_update_panel_splits_large_k(hiplib, oracle, k):
     """K > 64: both parts merge into the lists in the state (wave_merge, four / sixteen entries per lane), the column part reads nn

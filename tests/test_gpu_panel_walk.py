@@ -3,7 +3,10 @@ every user takes -- `tracs distance` full output, the array route, --nearest, --
 at 7 rows and at 1 row per panel (TRACS_FOREST_PANEL_ROWS), the last panel ragged, one whole panel without a pair, the pair buffers
 regrown, device-to-host batches of 64 rows that end inside a panel.  Three pins: the same bytes at every panel height; the integer
 columns equal to the CPU oracle; the CSV files equal to what the library wrote BEFORE the entry points shared one walk
-(tests/golden/panel_walk_golden.json, written by tests/golden/make_panel_walk_golden.py from a build of that commit)."""
+(tests/golden/panel_walk_golden.json, written by tests/golden/make_panel_walk_golden.py from a build of that commit).  The --mst and
+--ancestors routes (u32, f64 ascending and f64 descending keys) were added with csrc/pair_select.h: their entries come from a build of
+commit 27c4601, the last one in which forest.hip and ancestors.hip each carried their own primitives; regenerating the file from that
+build reproduced the eight older entries unchanged."""
 import argparse
 import hashlib
 import json
@@ -54,7 +57,9 @@ def csv_routes(inp):
     return {"full_meta": one + meta, "full_nometa": one, "full_meta_filter": one + meta + ["--filter"],
             "full_db": two + meta + ["-K", "300"], "full_min_sites": one + meta + ["--min-sites", str(inp["min_sites"])],
             "nearest": one + ["--nearest", str(K)], "nearest_db": two + ["--nearest", str(K)],
-            "histogram_filter": one + ["--histogram", "--filter"]}
+            "histogram_filter": one + ["--histogram", "--filter"],
+            "mst_snp": one + meta + ["--mst", "snp"], "mst_expectedK": one + meta + ["--mst", "expectedK"],
+            "ancestors_snp": one + meta + ["--ancestors", "snp"], "ancestors_direct": one + meta + ["--ancestors", "direct"]}
 
 
 def run_routes(inp, td, height):
@@ -185,7 +190,8 @@ def test_integer_columns_equal_the_oracle(runs, inputs, oracle, height):
 
 
 def test_csv_files_equal_the_parent_commits(runs):
-    """the refactor's own pin: sha256 and row count of every CSV as the library wrote them before the entry points shared one walk"""
+    """the refactors' own pin: sha256 and row count of every CSV as the library wrote them before the entry points shared one walk
+    (--mst, --ancestors: before the selection states shared csrc/pair_select.h)"""
     with open(GOLDEN) as fh:
         golden = json.load(fh)
     csv, _ = runs[None]

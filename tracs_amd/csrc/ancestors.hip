@@ -3,47 +3,22 @@
 // For a sample s sampled on day t_s, a sample a is a candidate when {a, s} is an offered, eligible pair and t_a < t_s (strictly: equal
 // days never link, so the links cannot form a cycle).  The chosen source is the smallest candidate under (value key, t_s - t_a, a): a
 // strict total order, so the result does not depend on how the pairs are split into updates.  The value key is order-preserving in 64
-// bits: a uint32 value as is; an f64 value through forest.hip's sign flip (-0.0 -> +0.0, every NaN to one key above every number),
-// complemented for the descending kind.  (value, gap, a) does not fit in 64 bits, so the minimum is taken in two steps:
+// bits: a uint32 value as is; an f64 value through f64_key_up, or f64_key_down for the descending kind (pair_select.h).  (value, gap, a) does not fit in 64 bits, so the minimum is taken in two steps:
 //   pass 1   per candidate pair: its later endpoint takes the value key (atomicMin)
 //   settle   per vertex: a value key lowered by this update discards the tie key kept from earlier updates; one that stayed keeps it
 //   pass 2   per candidate pair that ties its later endpoint's value key: the endpoint takes gap << 32 | a (atomicMin)
 //   pass 3   the pair that won a vertex records its index in the batch (unique: every pair is offered once)
 //   gather   per vertex with a winner in this batch: the parent and the pair's values are copied from the batch
-// Every pair has one atomic target (its later endpoint).  Atomics are reduced across the wave first, as forest.hip does: a segmented
-// minimum over runs of one target leaves one atomic per run, and only when a plain read shows it can lower the target.
+// Every pair has one atomic target (its later endpoint).  Atomics are reduced across the wave first (wave_min_into, pair_select.h): a
+// segmented minimum over runs of one target leaves one atomic per run, and only when a plain read shows it can lower the target.
 // Emit sorts the links by i << 32 | j (rocprim radix sort) and finds every vertex's root and generation by pointer doubling in
 // ceil(log2 n) rounds -- a fixed bound, whatever the parent array holds.
 #include "common.h"
+#include "pair_select.h"
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include <algorithm>
+using namespace tracs;
 
 namespace {
-
-constexpr unsigned long long ANC_NONE = ~0ull;                      // no candidate yet
-constexpr unsigned long long ANC_NAN_KEY = 0xFFF8000000000000ull;   // every NaN: above every number's key (either direction), below ANC_NONE
-constexpr unsigned ANC_NO_VERT = 0xFFFFFFFFu;                       // no target / no parent / no winner in this batch
-constexpr int WS_SORT_TMP = 93;                                     // workspace slot (84 .. 90 are the forest's, 92 msa_out's)
-
-// State layout (byte offsets, every array 256-byte aligned; capacity cap = max(n, 1)): header, days, per-vertex best keys, the winning
-// pair's identity and values, then scratch for emit (sort keys and indices, two hop / generation buffers each)
-struct Layout {
-    size_t hdr, days, bv, bt, cv, win, pa, fd, fnn, ff, fp, fe, keys, idx, hop, gen, total;
-    explicit Layout(size_t n)
-    {
-        const size_t cap = std::max<size_t>(n, 1);
-        size_t o = 0;
-        auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-        hdr = take(64);
-        days = take(cap * 4);
-        bv = take(cap * 8); bt = take(cap * 8); cv = take(cap * 8); win = take(cap * 4);
-        pa = take(cap * 4); fd = take(cap * 4); fnn = take(cap * 4); ff = take(cap * 4); fp = take(cap * 8); fe = take(cap * 8);
-        keys = take(cap * 16); idx = take(cap * 8); hop = take(cap * 8); gen = take(cap * 8);
-        total = o;
-    }
-};
 
 struct Hdr {
     unsigned long long n;           // vertices the state was initialised for
@@ -51,78 +26,40 @@ struct Hdr {
     unsigned long long links;       // vertices with a parent (counted by emit)
 };
 
+// State (capacity cap = max(n, 1)): header, days, per-vertex best keys, the winning pair's identity and values, then scratch for emit
+// (sort keys and indices, two hop / generation buffers each)
 struct State {
     Hdr *hdr;
     int *days;
     unsigned long long *bv, *bt, *cv, *keys;
-    unsigned *win, *pa, *fd, *fnn, *ff, *idx, *hop, *gen;
-    double *fp, *fe;
+    unsigned *win, *pa, *idx, *hop, *gen;
+    PairColumns val;
     size_t cap;
-    State(void *base, size_t n)
+    State(void *base, size_t n, size_t *bytes = nullptr)
     {
-        const Layout L(n);
-        char *b = static_cast<char *>(base);
         cap = std::max<size_t>(n, 1);
-        hdr = reinterpret_cast<Hdr *>(b + L.hdr);
-        days = reinterpret_cast<int *>(b + L.days);
-        bv = reinterpret_cast<unsigned long long *>(b + L.bv); bt = reinterpret_cast<unsigned long long *>(b + L.bt);
-        cv = reinterpret_cast<unsigned long long *>(b + L.cv); keys = reinterpret_cast<unsigned long long *>(b + L.keys);
-        win = reinterpret_cast<unsigned *>(b + L.win); pa = reinterpret_cast<unsigned *>(b + L.pa);
-        fd = reinterpret_cast<unsigned *>(b + L.fd); fnn = reinterpret_cast<unsigned *>(b + L.fnn); ff = reinterpret_cast<unsigned *>(b + L.ff);
-        idx = reinterpret_cast<unsigned *>(b + L.idx); hop = reinterpret_cast<unsigned *>(b + L.hop); gen = reinterpret_cast<unsigned *>(b + L.gen);
-        fp = reinterpret_cast<double *>(b + L.fp); fe = reinterpret_cast<double *>(b + L.fe);
+        Arena a(base, bytes);
+        hdr = reinterpret_cast<Hdr *>(a.take<char>(64));
+        days = a.take<int>(cap);
+        bv = a.take<unsigned long long>(cap); bt = a.take<unsigned long long>(cap); cv = a.take<unsigned long long>(cap);
+        win = a.take<unsigned>(cap); pa = a.take<unsigned>(cap);
+        val.d = a.take<unsigned>(cap); val.nn = a.take<unsigned>(cap); val.f = a.take<unsigned>(cap);
+        val.p = a.take<double>(cap); val.e = a.take<double>(cap);
+        keys = a.take<unsigned long long>(2 * cap); idx = a.take<unsigned>(2 * cap); hop = a.take<unsigned>(2 * cap); gen = a.take<unsigned>(2 * cap);
     }
 };
 
-// ascending f64 key (forest.hip's): numbers in order, -0.0 == +0.0, every NaN above +inf
-__device__ __forceinline__ unsigned long long f64_key_up(double x)
-{
-    if (x != x) return ANC_NAN_KEY;
-    if (x == 0.0) return 0x8000000000000000ull;
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-// descending f64 key: the largest number first, -0.0 == +0.0, -inf (key 0xFFF0...) last of the numbers, every NaN after it
-__device__ __forceinline__ unsigned long long f64_key_down(double x)
-{
-    if (x != x) return ANC_NAN_KEY;
-    return ~f64_key_up(x);
-}
-
-// minimum of v over the lanes at and above this one that hold the same target c; lanes of other runs of the same c may contribute
-// too, which is harmless.  All 64 lanes call it.
-__device__ __forceinline__ unsigned long long seg_min(unsigned long long v, unsigned c, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long ov = __shfl_down(v, off, 64);
-        const unsigned oc = __shfl_down(c, off, 64);
-        if (lane + off < 64 && oc == c && ov < v) v = ov;
-    }
-    return v;
-}
-
-// one atomicMin per run of equal targets in the wave, and only when it can lower the value: dst[] only decreases while a pass runs,
-// so a plain (possibly stale) read is an upper bound of the current value, and a candidate at or above it cannot win
-__device__ __forceinline__ void wave_min_into(unsigned long long *dst, unsigned long long v, unsigned c, int lane)
-{
-    const unsigned long long m = seg_min(v, c, lane);
-    const unsigned prev = __shfl_up(c, 1, 64);
-    if (c != ANC_NO_VERT && (lane == 0 || prev != c) && m < dst[c]) atomicMin(&dst[c], m);
-}
-
-// Pair t of the batch as a candidate: -> its later-dated endpoint (ANC_NO_VERT: not a candidate), value key and tie key
+// Pair t of the batch as a candidate: -> its later-dated endpoint (NO_VERTEX: not a candidate), value key and tie key
 template <int KIND>   // 0: uint32 ascending, 1: f64 ascending, 2: f64 descending
 __device__ __forceinline__ unsigned candidate(const State &s, size_t n, size_t t, const unsigned *__restrict__ rows, const unsigned *__restrict__ cols,
                                               const void *__restrict__ value, const double *__restrict__ e_mask, double e_max,
                                               unsigned long long &key, unsigned long long &tie)
 {
     const unsigned r = rows[t], c = cols[t];
-    if (r == c || (size_t)r >= n || (size_t)c >= n) return ANC_NO_VERT;      // not a pair of this state: skipped
-    if (e_mask && !(e_max >= e_mask[t])) return ANC_NO_VERT;                   // the -K test (tracs/distance.py:222): NaN fails
+    if (r == c || (size_t)r >= n || (size_t)c >= n) return NO_VERTEX;      // not a pair of this state: skipped
+    if (e_mask && !(e_max >= e_mask[t])) return NO_VERTEX;                   // the -K test (tracs/distance.py:222): NaN fails
     const long long dr = s.days[r], dc = s.days[c];
-    if (dr == dc) return ANC_NO_VERT;                                          // same day: never each other's source
+    if (dr == dc) return NO_VERTEX;                                          // same day: never each other's source
     const unsigned later = dr > dc ? r : c, earlier = dr > dc ? c : r;
     const unsigned long long gap = (unsigned long long)(dr > dc ? dr - dc : dc - dr);      // <= 2^32 - 1: 64-bit, pre-1970 days too
     if (KIND == 0) key = static_cast<const unsigned *>(value)[t];
@@ -136,13 +73,13 @@ __global__ __launch_bounds__(256) void anc_init_kernel(State s, size_t n, const 
 {
     for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (size_t)gridDim.x * 256) {
         s.days[v] = days[v];
-        s.bv[v] = ANC_NONE; s.bt[v] = ANC_NONE; s.cv[v] = ANC_NONE; s.win[v] = ANC_NO_VERT;
-        s.pa[v] = ANC_NO_VERT; s.fd[v] = 0; s.fnn[v] = 0; s.ff[v] = 0; s.fp[v] = 0.0; s.fe[v] = 0.0;
+        s.bv[v] = KEY_NONE; s.bt[v] = KEY_NONE; s.cv[v] = KEY_NONE; s.win[v] = NO_VERTEX;
+        s.pa[v] = NO_VERTEX; s.val.d[v] = 0; s.val.nn[v] = 0; s.val.f[v] = 0; s.val.p[v] = 0.0; s.val.e[v] = 0.0;
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) { s.hdr->n = n; s.hdr->taken = 0; s.hdr->links = 0; }
 }
 
-// Pass 1: every candidate's later endpoint takes its value key; the candidates are counted (one atomic per wave, at the end)
+// Pass 1: every candidate's later endpoint takes its value key; the candidates are counted
 template <int KIND>
 __global__ __launch_bounds__(256) void anc_pass1_kernel(State s, size_t n, size_t m, const unsigned *__restrict__ rows, const unsigned *__restrict__ cols,
                                                         const void *__restrict__ value, const double *__restrict__ e_mask, double e_max)
@@ -151,23 +88,21 @@ __global__ __launch_bounds__(256) void anc_pass1_kernel(State s, size_t n, size_
     unsigned long long cnt = 0;
     for (size_t base = (size_t)blockIdx.x * 256; base < m; base += (size_t)gridDim.x * 256) {
         const size_t t = base + threadIdx.x;
-        unsigned tgt = ANC_NO_VERT;
-        unsigned long long key = ANC_NONE, tie = ANC_NONE;
+        unsigned tgt = NO_VERTEX;
+        unsigned long long key = KEY_NONE, tie = KEY_NONE;
         if (t < m) tgt = candidate<KIND>(s, n, t, rows, cols, value, e_mask, e_max, key, tie);
-        if (tgt == ANC_NO_VERT) key = ANC_NONE; else cnt++;
+        if (tgt == NO_VERTEX) key = KEY_NONE; else cnt++;
         wave_min_into(s.bv, key, tgt, lane);
     }
-#pragma unroll
-    for (int off = 32; off; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    if (lane == 0 && cnt) atomicAdd(&s.hdr->taken, cnt);
+    wave_add_into(&s.hdr->taken, cnt, lane);
 }
 
 // Settle: a vertex whose value key this update lowered forgets the tie key of its stored winner; every vertex forgets the last batch's index
 __global__ __launch_bounds__(256) void anc_settle_kernel(State s, size_t n)
 {
     for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (size_t)gridDim.x * 256) {
-        if (s.bv[v] != s.cv[v]) s.bt[v] = ANC_NONE;
-        s.win[v] = ANC_NO_VERT;
+        if (s.bv[v] != s.cv[v]) s.bt[v] = KEY_NONE;
+        s.win[v] = NO_VERTEX;
     }
 }
 
@@ -179,11 +114,11 @@ __global__ __launch_bounds__(256) void anc_pass2_kernel(State s, size_t n, size_
     const int lane = threadIdx.x & 63;
     for (size_t base = (size_t)blockIdx.x * 256; base < m; base += (size_t)gridDim.x * 256) {
         const size_t t = base + threadIdx.x;
-        unsigned tgt = ANC_NO_VERT;
-        unsigned long long key = ANC_NONE, tie = ANC_NONE;
+        unsigned tgt = NO_VERTEX;
+        unsigned long long key = KEY_NONE, tie = KEY_NONE;
         if (t < m) tgt = candidate<KIND>(s, n, t, rows, cols, value, e_mask, e_max, key, tie);
-        if (tgt != ANC_NO_VERT && key != s.bv[tgt]) tgt = ANC_NO_VERT;
-        if (tgt == ANC_NO_VERT) tie = ANC_NONE;
+        if (tgt != NO_VERTEX && key != s.bv[tgt]) tgt = NO_VERTEX;
+        if (tgt == NO_VERTEX) tie = KEY_NONE;
         wave_min_into(s.bt, tie, tgt, lane);
     }
 }
@@ -194,27 +129,25 @@ __global__ __launch_bounds__(256) void anc_pass3_kernel(State s, size_t n, size_
                                                         const void *__restrict__ value, const double *__restrict__ e_mask, double e_max)
 {
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < m; t += (size_t)gridDim.x * 256) {
-        unsigned long long key = ANC_NONE, tie = ANC_NONE;
+        unsigned long long key = KEY_NONE, tie = KEY_NONE;
         const unsigned tgt = candidate<KIND>(s, n, t, rows, cols, value, e_mask, e_max, key, tie);
-        if (tgt != ANC_NO_VERT && key == s.bv[tgt] && tie == s.bt[tgt]) s.win[tgt] = (unsigned)t;
+        if (tgt != NO_VERTEX && key == s.bv[tgt] && tie == s.bt[tgt]) s.win[tgt] = (unsigned)t;
     }
 }
 
 // Gather: a vertex won by a pair of this batch takes its parent and the pair's values; its committed value key follows
-__global__ __launch_bounds__(256) void anc_gather_kernel(State s, size_t n, size_t m, const unsigned *__restrict__ d, const unsigned *__restrict__ nn,
-                                                         const unsigned *__restrict__ filt, const double *__restrict__ p, const double *__restrict__ e)
+__global__ __launch_bounds__(256) void anc_gather_kernel(State s, size_t n, size_t m, PairColumns batch)
 {
     for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (size_t)gridDim.x * 256) {
         const size_t w = s.win[v];
-        if (w >= m) continue;                                     // (ANC_NO_VERT: the stored winner stays)
+        if (w >= m) continue;                                     // (NO_VERTEX: the stored winner stays)
         s.pa[v] = (unsigned)(s.bt[v] & 0xffffffffull);
-        s.fd[v] = d ? d[w] : 0u; s.fnn[v] = nn ? nn[w] : 0u; s.ff[v] = filt ? filt[w] : 0u;
-        s.fp[v] = p ? p[w] : 0.0; s.fe[v] = e ? e[w] : 0.0;
+        take_columns(s.val, v, batch, w);
         s.cv[v] = s.bv[v];
     }
 }
 
-// Emit, step 1: the sort key of every vertex's link (roots: ANC_NONE, sorted behind every link), the link count, and the first hop and
+// Emit, step 1: the sort key of every vertex's link (roots: KEY_NONE, sorted behind every link), the link count, and the first hop and
 // generation of the pointer doubling (a root points at itself, generation 0)
 __global__ __launch_bounds__(256) void anc_links_kernel(State s, size_t n)
 {
@@ -224,31 +157,26 @@ __global__ __launch_bounds__(256) void anc_links_kernel(State s, size_t n)
         const size_t v = base + threadIdx.x;
         if (v >= n) continue;
         const unsigned p = s.pa[v];
-        const bool link = p != ANC_NO_VERT && (size_t)p < n;
+        const bool link = p != NO_VERTEX && (size_t)p < n;
         const unsigned lo = (unsigned)v < p ? (unsigned)v : p, hi = (unsigned)v < p ? p : (unsigned)v;
-        s.keys[v] = link ? ((unsigned long long)lo << 32) | hi : ANC_NONE;
+        s.keys[v] = link ? ((unsigned long long)lo << 32) | hi : KEY_NONE;
         s.idx[v] = (unsigned)v;
         s.hop[v] = link ? p : (unsigned)v;
         s.gen[v] = link ? 1u : 0u;
         cnt += link ? 1 : 0;
     }
-#pragma unroll
-    for (int off = 32; off; off >>= 1) cnt += __shfl_down(cnt, off, 64);
-    if (lane == 0 && cnt) atomicAdd(&s.hdr->links, cnt);
+    wave_add_into(&s.hdr->links, cnt, lane);
 }
 
+// row k of the output: vertex order[k] and its parent, the smaller index first
 __global__ __launch_bounds__(256) void anc_emit_kernel(State s, size_t n_links, const unsigned *__restrict__ order, unsigned *rows, unsigned *cols,
-                                                       unsigned *d, unsigned *nn, unsigned *filt, double *p, double *e)
+                                                       PairColumns out)
 {
     for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n_links; k += (size_t)gridDim.x * 256) {
         const unsigned v = order[k], a = s.pa[v];
         if (rows) rows[k] = v < a ? v : a;
         if (cols) cols[k] = v < a ? a : v;
-        if (d) d[k] = s.fd[v];
-        if (nn) nn[k] = s.fnn[v];
-        if (filt) filt[k] = s.ff[v];
-        if (p) p[k] = s.fp[v];
-        if (e) e[k] = s.fe[v];
+        emit_columns(out, k, s.val, v);
     }
 }
 
@@ -264,15 +192,11 @@ __global__ __launch_bounds__(256) void anc_double_kernel(size_t n, const unsigne
     }
 }
 
-inline unsigned grid_for(size_t work) { return (unsigned)std::max<size_t>(1, std::min<size_t>((work + 255) / 256, 4096)); }
-
 }  // namespace
-
-using namespace tracs;
 
 extern "C" {
 
-size_t tracs_anc_state_bytes(size_t n) { return Layout(n).total; }
+size_t tracs_anc_state_bytes(size_t n) { return arena_bytes<State>(n); }
 
 int tracs_anc_init(void *state, size_t n, const int32_t *days_device, void *stream_)
 {
@@ -282,7 +206,7 @@ int tracs_anc_init(void *state, size_t n, const int32_t *days_device, void *stre
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     DeviceCall guard(stream);
     State s(state, n);
-    hipLaunchKernelGGL(anc_init_kernel, dim3(grid_for(n)), dim3(256), 0, stream, s, n, days_device);
+    hipLaunchKernelGGL(anc_init_kernel, dim3(grid_for(n, SELECT_BLOCKS)), dim3(256), 0, stream, s, n, days_device);
     TRACS_HIP_CHECK(hipGetLastError());
     return TRACS_OK;
 }
@@ -303,24 +227,22 @@ int tracs_anc_update_coo(void *state, size_t n, size_t m, const uint32_t *rows, 
     DeviceCall guard(stream);
     State s(state, n);
     Hdr h{};
-    TRACS_HIP_CHECK(hipMemcpyAsync(&h, s.hdr, sizeof(h), hipMemcpyDeviceToHost, stream));
-    TRACS_HIP_CHECK(hipStreamSynchronize(stream));
-    if (h.n != n) { set_error("tracs_anc_update_coo: the state was initialised for another vertex count"); return TRACS_E_ARG; }
+    int rc;
+    if ((rc = read_state_header(s.hdr, n, "tracs_anc_update_coo", stream, &h))) return rc;
     if (m == 0 || n < 2) return TRACS_OK;
-    const unsigned nb = grid_for(n), eb = grid_for(m);
+    const unsigned nb = grid_for(n, SELECT_BLOCKS), eb = grid_for(m, SELECT_BLOCKS);
     TRACS_HIP_CHECK(hipMemsetAsync(&s.hdr->taken, 0, 8, stream));
-#define ANC_PASS(kernel)                                                                                                             \
-    do {                                                                                                                             \
-        if (value_kind == 0) hipLaunchKernelGGL(kernel<0>, dim3(eb), dim3(256), 0, stream, s, n, m, rows, cols, value, e_mask, e_max); \
-        else if (value_kind == 1) hipLaunchKernelGGL(kernel<1>, dim3(eb), dim3(256), 0, stream, s, n, m, rows, cols, value, e_mask, e_max); \
-        else hipLaunchKernelGGL(kernel<2>, dim3(eb), dim3(256), 0, stream, s, n, m, rows, cols, value, e_mask, e_max);                 \
-    } while (0)
-    ANC_PASS(anc_pass1_kernel);
-    hipLaunchKernelGGL(anc_settle_kernel, dim3(nb), dim3(256), 0, stream, s, n);
-    ANC_PASS(anc_pass2_kernel);
-    ANC_PASS(anc_pass3_kernel);
-#undef ANC_PASS
-    hipLaunchKernelGGL(anc_gather_kernel, dim3(nb), dim3(256), 0, stream, s, n, m, d, nn, filt, p, e);
+    auto pass = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(eb), dim3(256), 0, stream, s, n, m, rows, cols, value, e_mask, e_max); };
+    auto passes = [&](auto pass1, auto pass2, auto pass3) {
+        pass(pass1);
+        hipLaunchKernelGGL(anc_settle_kernel, dim3(nb), dim3(256), 0, stream, s, n);
+        pass(pass2);
+        pass(pass3);
+    };
+    if (value_kind == 0) passes(anc_pass1_kernel<0>, anc_pass2_kernel<0>, anc_pass3_kernel<0>);
+    else if (value_kind == 1) passes(anc_pass1_kernel<1>, anc_pass2_kernel<1>, anc_pass3_kernel<1>);
+    else passes(anc_pass1_kernel<2>, anc_pass2_kernel<2>, anc_pass3_kernel<2>);
+    hipLaunchKernelGGL(anc_gather_kernel, dim3(nb), dim3(256), 0, stream, s, n, m, batch_columns(d, nn, filt, p, e));
     TRACS_HIP_CHECK(hipGetLastError());
     if (n_taken) {
         unsigned long long taken = 0;
@@ -340,11 +262,10 @@ int tracs_anc_emit(void *state, size_t n, size_t *n_links, uint32_t *rows, uint3
     DeviceCall guard(stream);
     State s(state, n);
     Hdr h{};
-    TRACS_HIP_CHECK(hipMemcpyAsync(&h, s.hdr, sizeof(h), hipMemcpyDeviceToHost, stream));
-    TRACS_HIP_CHECK(hipStreamSynchronize(stream));
-    if (h.n != n) { set_error("tracs_anc_emit: the state was initialised for another vertex count"); return TRACS_E_ARG; }
+    int rc;
+    if ((rc = read_state_header(s.hdr, n, "tracs_anc_emit", stream, &h))) return rc;
     if (n == 0) return TRACS_OK;
-    const unsigned nb = grid_for(n);
+    const unsigned nb = grid_for(n, SELECT_BLOCKS);
     TRACS_HIP_CHECK(hipMemsetAsync(&s.hdr->links, 0, 8, stream));
     hipLaunchKernelGGL(anc_links_kernel, dim3(nb), dim3(256), 0, stream, s, n);
     TRACS_HIP_CHECK(hipGetLastError());
@@ -354,16 +275,10 @@ int tracs_anc_emit(void *state, size_t n, size_t *n_links, uint32_t *rows, uint3
     const size_t nl = std::min<size_t>((size_t)links, n);
     *n_links = nl;
     if (nl && (rows || cols || d || nn || filt || p || e)) {
-        // every vertex's key is sorted (roots carry ANC_NONE and end up behind the links); the first nl entries are the links in (i, j) order
-        unsigned long long *keys = s.keys;
-        unsigned *idx = s.idx;
-        size_t tmp_bytes = 0;
-        TRACS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys + s.cap, idx, idx + s.cap, n, 0u, 64u, stream));
-        void *tmp;
-        int rc;
-        if ((rc = workspace_get(WS_SORT_TMP, std::max<size_t>(tmp_bytes, 1), &tmp))) return rc;
-        TRACS_HIP_CHECK(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys + s.cap, idx, idx + s.cap, n, 0u, 64u, stream));
-        hipLaunchKernelGGL(anc_emit_kernel, dim3(grid_for(nl)), dim3(256), 0, stream, s, nl, idx + s.cap, rows, cols, d, nn, filt, p, e);
+        // every vertex's key is sorted (roots carry KEY_NONE and end up behind the links); the first nl entries are the links in (i, j) order
+        if ((rc = sort_by_pair_key(s.keys, s.idx, n, s.cap, WS_ANC_SORT_TMP, stream))) return rc;
+        hipLaunchKernelGGL(anc_emit_kernel, dim3(grid_for(nl, SELECT_BLOCKS)), dim3(256), 0, stream, s, nl, s.idx + s.cap, rows, cols,
+                           PairColumns{d, nn, filt, p, e});
         TRACS_HIP_CHECK(hipGetLastError());
     }
     if (parent) TRACS_HIP_CHECK(hipMemcpyAsync(parent, s.pa, n * 4, hipMemcpyDeviceToDevice, stream));

@@ -7,24 +7,9 @@
 // under the smaller (so every component's root IS its smallest node, whatever the edge order),
 // then an exclusive scan over "is root" gives the SciPy numbering.  Integer work, HBM/atomic bound.
 #include "common.h"
+#include "pair_select.h"      // uf_load, uf_find
 
 namespace tracs {
-
-// parent[] only ever moves a node towards smaller ids (hook larger root under smaller, path
-// halving), so a stale read still lands on a valid ancestor: races cost retries, never a wrong
-// component.  Agent-scope relaxed atomics keep the loads out of the (non-coherent) vector L1.
-__device__ __forceinline__ int uf_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int uf_find(int *parent, int x)
-{
-    for (;;) {
-        const int p = uf_load(&parent[x]);
-        if (p == x) return x;
-        const int gp = uf_load(&parent[p]);
-        if (gp != p) __hip_atomic_store(&parent[x], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // path halving
-        x = gp;
-    }
-}
 
 __global__ void uf_init_kernel(int *__restrict__ parent, size_t n)
 {
@@ -91,8 +76,6 @@ __global__ void uf_label_kernel(const int *__restrict__ root, const int *__restr
     for (size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (size_t)gridDim.x * blockDim.x) labels[v] = id_of[root[v]];
 }
 
-struct CcWorkspaceIds { enum { PARENT = 16, FLAG, ROOT, TOTAL }; };
-
 }  // namespace tracs
 
 using namespace tracs;
@@ -110,10 +93,10 @@ int tracs_connected_components_device(const int32_t *I, const int32_t *J, size_t
     DeviceCall guard(stream);
     int *parent, *flag, *root, *total;
     int rc;
-    if ((rc = workspace_get(CcWorkspaceIds::PARENT, n_nodes * 4, reinterpret_cast<void **>(&parent)))) return rc;
-    if ((rc = workspace_get(CcWorkspaceIds::FLAG, n_nodes * 4, reinterpret_cast<void **>(&flag)))) return rc;
-    if ((rc = workspace_get(CcWorkspaceIds::ROOT, n_nodes * 4, reinterpret_cast<void **>(&root)))) return rc;
-    if ((rc = workspace_get(CcWorkspaceIds::TOTAL, 64, reinterpret_cast<void **>(&total)))) return rc;
+    if ((rc = workspace_get(WS_CC_PARENT, n_nodes, &parent))) return rc;
+    if ((rc = workspace_get(WS_CC_FLAG, n_nodes, &flag))) return rc;
+    if ((rc = workspace_get(WS_CC_ROOT, n_nodes, &root))) return rc;
+    if ((rc = workspace_get(WS_CC_TOTAL, 16, &total))) return rc;
     const unsigned nb = (unsigned)std::min<size_t>((n_nodes + 255) / 256, 256 * 16);
     hipLaunchKernelGGL(uf_init_kernel, dim3(nb), dim3(256), 0, stream, parent, n_nodes);
     if (n_edges) {

@@ -141,12 +141,64 @@ int pair_sites_write(const tracs_alignment *a, const char *const *names, const u
 hipError_t pack_alloc(tracs_alignment *a, size_t bytes, void **out);
 void pack_release(tracs_alignment *a);
 
-// Grow-only per-device scratch buffers (slot ids are small integers owned by each .hip file), shared by every entry point.
-// Entry points that use them, or the cached state of a tracs_alignment, hold a DeviceCall for their whole body:
+// Grow-only per-device scratch buffers, shared by every entry point.  Every slot of every file is declared here, once: a new buffer
+// takes a new name in its owner's group (the values are the library's own; nothing outside it sees them).
+enum WsSlot : int {
+    // transcluster.hip: the distinct (N, delta) keys of one call, their results and the optional (gap, M) / grid tables
+    WS_TC_SLOTS, WS_TC_ESLOT, WS_TC_SLOT_ID, WS_TC_NKEYS, WS_TC_KEY_ELEM, WS_TC_KEY_P0, WS_TC_KEY_EK, WS_TC_LONG_IDS, WS_TC_KEY_STATE,
+    WS_TC_TAB, WS_TC_TAB_LNS, WS_TC_TAB_POIS, WS_TC_GRID_BITS, WS_TC_GRID_TABLES, WS_TC_TAB_LNS_N, WS_TC_REST_IDS,
+    // transcluster.hip: the key split between ranks (tracs_trans_keys_*)
+    WS_KS_RANK, WS_KS_CHUNK, WS_KS_INFO,
+    // cluster.hip: union-find parents, root flags, roots, the component count
+    WS_CC_PARENT, WS_CC_FLAG, WS_CC_ROOT, WS_CC_TOTAL,
+    // dmultinomial.hip: the posterior table
+    WS_DM_TABLE,
+    // dirichlet.hip: count rows, per-block partial sums, kept rows, the fit's state, block counts (consecutive: used in this order)
+    WS_DIR_ROWS, WS_DIR_PARTIAL, WS_DIR_NKEPT, WS_DIR_STATE, WS_DIR_BLOCKS,
+    // site_lists.hip: the site-major N matrix of the rows fix-up
+    WS_SL_NROWS,
+    // pairsnp.hip: live tiles of a thresholded dense call
+    WS_PS_LIVE, WS_PS_LIVE_TILES, WS_PS_N_LIVE,
+    // site_classes.hip: per-group masks, offsets and counts of the class decision, and the dense / counted site lists
+    WS_SC_MASKS, WS_SC_OFFS, WS_SC_CNTS, WS_SC_GCNT, WS_SC_OFF64, WS_SC_TOTALS, WS_SC_FLAGS, WS_SC_LISTS,
+    // site_lists.hip: per-sample counts, per-group entry counts, the entries and (optional) their second sorting buffer
+    WS_SL_CNT, WS_SL_ECNT, WS_SL_ENTRIES, WS_SL_ENTRIES_TMP,
+    // pair_sites.hip: tile sums of the offsets scan, the bad-pair flag
+    WS_PSITES_SUMS, WS_PSITES_BAD,
+    // filter_lists.hip: the index build's per-chunk counts and the departure scratch of a filter pass
+    WS_FLT_CNT, WS_FLT_REL, WS_FLT_TOT, WS_FLT_STATS, WS_FLT_IDX, WS_FLT_SCRATCH,
+    // filter.hip: SNP positions of the listed pairs and their offsets scan
+    WS_FSCAN_POS, WS_FSCAN_FOUND, WS_FSCAN_OFF, WS_FSCAN_SUMS,
+    // forest.hip: the two working edge lists, the new forest's sources and values, emit's sort keys and indices
+    WS_MSF_W0, WS_MSF_W1, WS_MSF_FSRC, WS_MSF_FTMP, WS_MSF_SORT_KEYS, WS_MSF_SORT_IDX, WS_MSF_SORT_TMP,
+    // msa_out.hip: the differs bitmap of the site census
+    WS_MSA_DIFFERS,
+    // ancestors.hip: the radix sort's temporary storage
+    WS_ANC_SORT_TMP,
+    WS_SLOT_COUNT
+};
+
+// Entry points that use scratch buffers, or the cached state of a tracs_alignment, hold a DeviceCall for their whole body:
 //   * calls on one device are serialised (ctypes releases the GIL, so two Python threads can be inside the library);
 //   * scratch is only stream-ordered, so when a call arrives on a different stream than the previous call on that device
 //     the device is synchronised first.  Re-entrant on the owning thread (tracs_pairsnp calls the dense entry points).
-int workspace_get(int slot, size_t bytes, void **out);
+int workspace_bytes(WsSlot slot, size_t bytes, void **out);        // (capi.hip; callers use the typed forms below)
+// *out <- the slot's buffer, at least `count` elements of T
+template <class T>
+static int workspace_get(WsSlot slot, size_t count, T **out)
+{
+    return workspace_bytes(slot, count * sizeof(T), reinterpret_cast<void **>(out));
+}
+// an optional buffer: not getting it is not an error.  false leaves *out NULL, the error slot and HIP's last error clear
+template <class T>
+static bool workspace_try(WsSlot slot, size_t count, T **out)
+{
+    if (workspace_get(slot, count, out) == TRACS_OK) return true;
+    (void)hipGetLastError();
+    set_error("");
+    *out = nullptr;
+    return false;
+}
 void workspace_release_all();
 struct DeviceCall {
     explicit DeviceCall(hipStream_t stream);

@@ -199,18 +199,17 @@ int tracs_find_dirichlet_priors_device(const double *counts, size_t L, size_t K,
     unsigned *n_kept = nullptr;
     DmState *st = nullptr;
     int rc;
-    enum { WS_ROWS = 32, WS_PARTIAL, WS_NKEPT, WS_STATE, WS_BLOCKS };
-    if ((rc = workspace_get(WS_ROWS, std::max<size_t>(L, 1) * K * 8, reinterpret_cast<void **>(&rows)))) return rc;
-    if ((rc = workspace_get(WS_PARTIAL, (size_t)DM_BLOCKS * (DK + 1) * 8, reinterpret_cast<void **>(&partial)))) return rc;
-    if ((rc = workspace_get(WS_NKEPT, 64, reinterpret_cast<void **>(&n_kept)))) return rc;
-    if ((rc = workspace_get(WS_STATE, sizeof(DmState), reinterpret_cast<void **>(&st)))) return rc;
+    if ((rc = workspace_get(WS_DIR_ROWS, std::max<size_t>(L, 1) * K, &rows))) return rc;
+    if ((rc = workspace_get(WS_DIR_PARTIAL, (size_t)DM_BLOCKS * (DK + 1), &partial))) return rc;
+    if ((rc = workspace_get(WS_DIR_NKEPT, 16, &n_kept))) return rc;
+    if ((rc = workspace_get(WS_DIR_STATE, 1, &st))) return rc;
     TRACS_HIP_CHECK(hipMemsetAsync(n_kept, 0, 4, stream));
     TRACS_HIP_CHECK(hipMemsetAsync(st, 0, sizeof(DmState), stream));
     if (L) {
         const unsigned blocks = (unsigned)std::min<size_t>((L + 255) / 256, 1024);
         const size_t chunk = ((L + blocks - 1) / blocks + 255) / 256 * 256;           // contiguous sites per block, whole tiles
         unsigned *block_cnt = nullptr;
-        if ((rc = workspace_get(WS_BLOCKS, 2 * 1024 * sizeof(unsigned), reinterpret_cast<void **>(&block_cnt)))) return rc;
+        if ((rc = workspace_get(WS_DIR_BLOCKS, 2 * 1024, &block_cnt))) return rc;
         unsigned *block_off = block_cnt + 1024;
         const int use_filt = error_filt_threshold >= 0 ? 1 : 0;
         hipLaunchKernelGGL(dm_select_kernel<0>, dim3(blocks), dim3(256), 0, stream, counts, L, (int)K, error_filt_threshold, use_filt, chunk,

@@ -482,7 +482,7 @@ static int posterior_codes_impl(bool wide, const void *counts, size_t L, const d
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     DeviceCall guard(stream);
     uint4 *table = nullptr;
-    if ((rc = workspace_get(24, POST_TABLE_TOT * sizeof(uint4), reinterpret_cast<void **>(&table)))) return rc;
+    if ((rc = workspace_get(WS_DM_TABLE, POST_TABLE_TOT, &table))) return rc;
     hipLaunchKernelGGL(posterior_table_kernel, dim3(POST_TABLE_TOT * 4 / 256), dim3(256), 0, stream, A, keep, threshold, F.min_cov, F.band_lo,
                        F.band_span, reinterpret_cast<unsigned *>(table));
     const size_t rounds = (L / 2) / 256;                     // whole rounds of 256 site pairs

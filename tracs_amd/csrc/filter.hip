@@ -197,7 +197,6 @@ __global__ __launch_bounds__(256) void filter_found_check_kernel(const unsigned 
         if (found[t] != d[t]) atomicAdd(bad, 1u);
 }
 
-struct ScanWs { enum { POS = 76, FOUND, OFF, SUMS }; };
 
 // The scan of the planes for pairs whose SNP sites do not come from lists (filter_lists.hip): batches whose SNP-site lists fit
 // 2^28 entries, offsets scanned on the device, the two extraction kernels above, the window test with the callers' threshold rows.
@@ -216,10 +215,10 @@ int filter_scan_route(const tracs_alignment *a, const unsigned *rows, const unsi
     int rc;
     // (a batch is never less than one pair: a pair with more SNP sites than kMaxPos still needs room for all of them)
     const size_t pos_cap = std::max<size_t>(std::min<size_t>(per * std::max<size_t>(max_d, 1), kMaxPos), max_d);
-    if ((rc = workspace_get(ScanWs::POS, (pos_cap + 64) * 4, reinterpret_cast<void **>(&pos))) ||
-        (rc = workspace_get(ScanWs::FOUND, per * 4, reinterpret_cast<void **>(&found))) ||
-        (rc = workspace_get(ScanWs::OFF, (per + 1) * 8, reinterpret_cast<void **>(&off))) ||
-        (rc = workspace_get(ScanWs::SUMS, offsets_scan_sums(per) * 8, reinterpret_cast<void **>(&sums)))) return rc;
+    if ((rc = workspace_get(WS_FSCAN_POS, pos_cap + 64, &pos)) ||
+        (rc = workspace_get(WS_FSCAN_FOUND, per, &found)) ||
+        (rc = workspace_get(WS_FSCAN_OFF, per + 1, &off)) ||
+        (rc = workspace_get(WS_FSCAN_SUMS, offsets_scan_sums(per), &sums))) return rc;
     for (size_t t0 = 0; t0 < n_pairs; t0 += per) {
         const size_t np = std::min(per, n_pairs - t0);
         if ((rc = offsets_scan_launch(d + t0, np, sums, off, stream))) return rc;

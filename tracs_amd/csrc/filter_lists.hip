@@ -968,7 +968,6 @@ __global__ __launch_bounds__(256) void flt_max_kernel(const unsigned *__restrict
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-struct FltWs { enum { CNT = 70, REL, TOT, STATS, IDX, SCRATCH }; };
 
 static bool flt_env_off(const char *name)
 {
@@ -1027,10 +1026,10 @@ static int filter_index_get(tracs_alignment *a, hipStream_t stream)
     f->alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     unsigned *cnt, *rel, *tot, *stats;
     int rc;
-    if ((rc = workspace_get(FltWs::CNT, (size_t)chunks * n * 4, reinterpret_cast<void **>(&cnt))) ||
-        (rc = workspace_get(FltWs::REL, (size_t)chunks * n * 4, reinterpret_cast<void **>(&rel))) ||
-        (rc = workspace_get(FltWs::TOT, (size_t)n * 4, reinterpret_cast<void **>(&tot))) ||
-        (rc = workspace_get(FltWs::STATS, 64, reinterpret_cast<void **>(&stats)))) return done(rc);
+    if ((rc = workspace_get(WS_FLT_CNT, (size_t)chunks * n, &cnt)) ||
+        (rc = workspace_get(WS_FLT_REL, (size_t)chunks * n, &rel)) ||
+        (rc = workspace_get(WS_FLT_TOT, (size_t)n, &tot)) ||
+        (rc = workspace_get(WS_FLT_STATS, 16, &stats))) return done(rc);
 
     TRACS_HIP_CHECK(hipEventRecord(ev[0], stream));
     hipLaunchKernelGGL(flt_ref_kernel, dim3(groups), dim3(64), 0, stream, a->planes, a->n_pad, n, groups, f->ref);
@@ -1174,8 +1173,8 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
         const size_t slot = ((size_t)2 * f->max_len + 8 + 63) / 64 * 64;
         size_t waves = std::min<size_t>(n_left, 256 * TRACS_FLT_TGRID);
         while (waves > 256 && waves * slot * 4 > (3ull << 30)) waves /= 2;
-        if ((rc = workspace_get(FltWs::IDX, n_left * 4, reinterpret_cast<void **>(&idx))) ||
-            (rc = workspace_get(FltWs::SCRATCH, waves * slot * 4, reinterpret_cast<void **>(&scratch)))) return rc;
+        if ((rc = workspace_get(WS_FLT_IDX, n_left, &idx)) ||
+            (rc = workspace_get(WS_FLT_SCRATCH, waves * slot, &scratch))) return rc;
         TRACS_HIP_CHECK(hipMemsetAsync(f->counters + 4, 0, 4, stream));
         hipLaunchKernelGGL(flt_collect_kernel, dim3(blocks), dim3(256), 0, stream, filt, n_pairs, idx, f->counters + 4);
         FltPairArgs A;

@@ -1,8 +1,7 @@
 // forest.hip -- minimum spanning forest of the eligible pairs (tracs_msf_*, include/tracs_hip.h).
 //
 // Edges are ordered by (weight key, i, j) with i < j the pair's sample indices: a strict total order, so the forest is unique.  The
-// weight key is order-preserving in 64 bits: a uint32 weight as is; an f64 weight through the sign flip (-0.0 -> +0.0, every NaN to
-// one key above +inf).  A pair's (i, j) is a second 64-bit key, i << 32 | j: (weight, i, j) does not fit in 64 bits, so every
+// weight key is order-preserving in 64 bits: a uint32 weight as is; an f64 weight through f64_key_up (pair_select.h).  A pair's (i, j) is a second 64-bit key, i << 32 | j: (weight, i, j) does not fit in 64 bits, so every
 // minimum is taken in two steps, the weight first, then (i, j) among the edges that tie on it.
 //
 // State: the running forest F (at most n - 1 edges, each with the values its CSV row is written with) and per-vertex scratch.  An
@@ -13,43 +12,20 @@
 //   pass 2   per live edge that ties its component's minimum weight: the component takes its (i, j) (atomicMin)
 //   pass 3   the edge that won a component records its index
 //   hook     per component root with a winner: the edge goes into the new forest and the two components are joined, the larger
-//            root under the smaller (csrc/cluster.hip's discipline); a mutual pick of one edge (the only cycle a strict total order
+//            root under the smaller (pair_select.h's union-find, as csrc/cluster.hip); a mutual pick of one edge (the only cycle a strict total order
 //            lets Boruvka form) is counted once, by the smaller root
 //   flatten  every vertex's component label <- its root
-// Atomics are reduced across the wave first: in row-major COO consecutive edges share a row, so a segmented minimum over runs of
-// one component leaves one atomic per run.  The host reads one word per round (the live edge count) and stops when it is 0.
+// Atomics are reduced across the wave first (wave_min_into, pair_select.h): in row-major COO consecutive edges share a row, so a
+// segmented minimum over runs of one component leaves one atomic per run.  The host reads one word per round (the live edge count)
+// and stops when it is 0.
 // Emit sorts the forest by (i, j) (rocprim radix sort) and gathers the row values.
 #include "common.h"
+#include "pair_select.h"
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include <algorithm>
+using namespace tracs;
 
 namespace {
 
-constexpr unsigned long long MSF_NONE = ~0ull;                 // no candidate yet / skipped edge
-constexpr unsigned long long MSF_NAN_KEY = 0xFFF8000000000000ull;   // every NaN: above +inf (0xFFF0...), below MSF_NONE
-constexpr unsigned MSF_NO_COMP = 0xFFFFFFFFu;
-
-struct Ws { enum { W0 = 84, W1, FSRC, FTMP, SORT_KEYS, SORT_IDX, SORT_TMP }; };
-
-// State layout (byte offsets, every array 256-byte aligned): header, then the forest (capacity cap = max(n, 1)), then per-vertex scratch.
-struct Layout {
-    size_t hdr, fi, fj, fw, fd, fnn, ff, fp, fe, comp, par, bw, bij, win, total;
-    explicit Layout(size_t n)
-    {
-        const size_t cap = std::max<size_t>(n, 1);
-        size_t o = 0;
-        auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-        hdr = take(64);
-        fi = take(cap * 4); fj = take(cap * 4); fw = take(cap * 8); fd = take(cap * 4); fnn = take(cap * 4); ff = take(cap * 4);
-        fp = take(cap * 8); fe = take(cap * 8);
-        comp = take(cap * 4); par = take(cap * 4); bw = take(cap * 8); bij = take(cap * 8); win = take(cap * 4);
-        total = o;
-    }
-};
-
-// header words
 struct Hdr {
     unsigned long long nf;          // forest edges
     unsigned long long nf_new;      // forest edges chosen by the running update
@@ -57,72 +33,48 @@ struct Hdr {
     unsigned long long n;           // vertices the state was initialised for
 };
 
+// State: header, then the forest (capacity max(n, 1): endpoints, weight key, values), then per-vertex scratch
 struct State {
     Hdr *hdr;
-    unsigned *fi, *fj, *fd, *fnn, *ff, *win;
-    unsigned long long *fw, *bw, *bij;
-    double *fp, *fe;
+    unsigned *fi, *fj;
+    unsigned long long *fw;
+    PairColumns val;
     int *comp, *par;
-    State(void *base, size_t n)
+    unsigned long long *bw, *bij;
+    unsigned *win;
+    State(void *base, size_t n, size_t *bytes = nullptr)
     {
-        const Layout L(n);
-        char *b = static_cast<char *>(base);
-        hdr = reinterpret_cast<Hdr *>(b + L.hdr);
-        fi = reinterpret_cast<unsigned *>(b + L.fi); fj = reinterpret_cast<unsigned *>(b + L.fj);
-        fw = reinterpret_cast<unsigned long long *>(b + L.fw);
-        fd = reinterpret_cast<unsigned *>(b + L.fd); fnn = reinterpret_cast<unsigned *>(b + L.fnn); ff = reinterpret_cast<unsigned *>(b + L.ff);
-        fp = reinterpret_cast<double *>(b + L.fp); fe = reinterpret_cast<double *>(b + L.fe);
-        comp = reinterpret_cast<int *>(b + L.comp); par = reinterpret_cast<int *>(b + L.par);
-        bw = reinterpret_cast<unsigned long long *>(b + L.bw); bij = reinterpret_cast<unsigned long long *>(b + L.bij);
-        win = reinterpret_cast<unsigned *>(b + L.win);
+        const size_t cap = std::max<size_t>(n, 1);
+        Arena a(base, bytes);
+        hdr = reinterpret_cast<Hdr *>(a.take<char>(64));
+        fi = a.take<unsigned>(cap); fj = a.take<unsigned>(cap); fw = a.take<unsigned long long>(cap);
+        val.d = a.take<unsigned>(cap); val.nn = a.take<unsigned>(cap); val.f = a.take<unsigned>(cap);
+        val.p = a.take<double>(cap); val.e = a.take<double>(cap);
+        comp = a.take<int>(cap); par = a.take<int>(cap); bw = a.take<unsigned long long>(cap); bij = a.take<unsigned long long>(cap);
+        win = a.take<unsigned>(cap);
     }
 };
 
 // the working edge list of one round (struct of arrays): endpoints i < j, weight key, index into F u B (< nf: F, else B)
-struct Work { unsigned *i, *j, *src; unsigned long long *w; };
-
-__device__ __forceinline__ unsigned long long f64_key(double x)
-{
-    if (x != x) return MSF_NAN_KEY;
-    if (x == 0.0) return 0x8000000000000000ull;                 // -0.0 == +0.0
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-// minimum of v over the lanes at and above this one that hold the same component c (runs of one c are what row-major COO gives);
-// lanes of other runs of the same c may contribute too, which is harmless.  All 64 lanes call it.
-__device__ __forceinline__ unsigned long long seg_min(unsigned long long v, unsigned c, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned long long ov = __shfl_down(v, off, 64);
-        const unsigned oc = __shfl_down(c, off, 64);
-        if (lane + off < 64 && oc == c && ov < v) v = ov;
+struct Work {
+    unsigned *i, *j, *src; unsigned long long *w;
+    Work(void *base, size_t m, size_t *bytes = nullptr)
+    {
+        Arena a(base, bytes);
+        i = a.take<unsigned>(m); j = a.take<unsigned>(m); src = a.take<unsigned>(m); w = a.take<unsigned long long>(m);
     }
-    return v;
-}
+};
 
-// one atomicMin per run of equal components in the wave, and only when it can lower the value: dst[] only ever decreases, so a
-// plain (possibly stale) read is an upper bound of the current value, and a candidate at or above it cannot win
-__device__ __forceinline__ void wave_min_into(unsigned long long *dst, unsigned long long v, unsigned c, int lane)
-{
-    const unsigned long long m = seg_min(v, c, lane);
-    const unsigned prev = __shfl_up(c, 1, 64);
-    if (c != MSF_NO_COMP && m != MSF_NONE && (lane == 0 || prev != c) && m < dst[c]) atomicMin(&dst[c], m);
-}
-
-__device__ __forceinline__ int uf_load(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int uf_find(int *parent, int x)
-{
-    for (;;) {
-        const int p = uf_load(&parent[x]);
-        if (p == x) return x;
-        const int gp = uf_load(&parent[p]);
-        if (gp != p) __hip_atomic_store(&parent[x], gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = gp;
+// the new forest: fsrc[k] indexes F (< nf) or the batch (>= nf); its values gathered into the temporary forest `t` (capacity n)
+struct Forest {
+    unsigned *i, *j; unsigned long long *w; PairColumns val;
+    Forest(void *base, size_t n, size_t *bytes = nullptr)
+    {
+        Arena a(base, bytes);
+        w = a.take<unsigned long long>(n); val.p = a.take<double>(n); val.e = a.take<double>(n);
+        i = a.take<unsigned>(n); j = a.take<unsigned>(n); val.d = a.take<unsigned>(n); val.nn = a.take<unsigned>(n); val.f = a.take<unsigned>(n);
     }
-}
+};
 
 __global__ __launch_bounds__(256) void msf_init_kernel(State s, size_t n)
 {
@@ -132,7 +84,7 @@ __global__ __launch_bounds__(256) void msf_init_kernel(State s, size_t n)
 
 __global__ __launch_bounds__(256) void msf_reset_kernel(State s, size_t n)
 {
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (size_t)gridDim.x * 256) { s.bw[v] = MSF_NONE; s.bij[v] = MSF_NONE; }
+    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (size_t)gridDim.x * 256) { s.bw[v] = KEY_NONE; s.bij[v] = KEY_NONE; }
 }
 
 // Pass 1.  first != 0: the edges are F (index < nf) followed by the batch (rows, cols, weight, mask); else the working list `in`.
@@ -147,7 +99,7 @@ __global__ __launch_bounds__(256) void msf_pass1_kernel(State s, size_t n, int f
     for (size_t base = (size_t)blockIdx.x * 256; base < n_in; base += (size_t)gridDim.x * 256) {
         const size_t e = base + threadIdx.x;
         unsigned a = 0, b = 0, src = 0;
-        unsigned long long w = MSF_NONE;
+        unsigned long long w = KEY_NONE;
         if (e < n_in) {
             if (!first) { a = in.i[e]; b = in.j[e]; w = in.w[e]; src = in.src[e]; }
             else if (e < nf) { a = s.fi[e]; b = s.fj[e]; w = s.fw[e]; src = (unsigned)e; }
@@ -156,15 +108,15 @@ __global__ __launch_bounds__(256) void msf_pass1_kernel(State s, size_t n, int f
                 const unsigned r = rows[t], c = cols[t];
                 a = r < c ? r : c; b = r < c ? c : r; src = (unsigned)e;
                 if (KIND == 0) w = static_cast<const unsigned *>(weight)[t];
-                else w = f64_key(static_cast<const double *>(weight)[t]);
-                if (e_mask && !(e_max >= e_mask[t])) w = MSF_NONE;     // the -K test (tracs/distance.py:222): NaN fails
-                if (a == b || (size_t)b >= n) w = MSF_NONE;             // not an edge of this state: skipped
+                else w = f64_key_up(static_cast<const double *>(weight)[t]);
+                if (e_mask && !(e_max >= e_mask[t])) w = KEY_NONE;     // the -K test (tracs/distance.py:222): NaN fails
+                if (a == b || (size_t)b >= n) w = KEY_NONE;             // not an edge of this state: skipped
             }
         }
-        unsigned ca = MSF_NO_COMP, cb = MSF_NO_COMP;
-        if (w != MSF_NONE) { ca = (unsigned)s.comp[a]; cb = (unsigned)s.comp[b]; }
-        const bool live = w != MSF_NONE && ca != cb;
-        if (!live) { w = MSF_NONE; ca = cb = MSF_NO_COMP; }
+        unsigned ca = NO_VERTEX, cb = NO_VERTEX;
+        if (w != KEY_NONE) { ca = (unsigned)s.comp[a]; cb = (unsigned)s.comp[b]; }
+        const bool live = w != KEY_NONE && ca != cb;
+        if (!live) { w = KEY_NONE; ca = cb = NO_VERTEX; }
         // compaction: one slot reservation per wave
         const unsigned long long mask = __ballot(live);
         unsigned long long slot0 = 0;
@@ -185,14 +137,14 @@ __global__ __launch_bounds__(256) void msf_pass2_kernel(State s, size_t n_live, 
     const int lane = threadIdx.x & 63;
     for (size_t base = (size_t)blockIdx.x * 256; base < n_live; base += (size_t)gridDim.x * 256) {
         const size_t e = base + threadIdx.x;
-        unsigned ca = MSF_NO_COMP, cb = MSF_NO_COMP;
-        unsigned long long ka = MSF_NONE, kb = MSF_NONE;
+        unsigned ca = NO_VERTEX, cb = NO_VERTEX;
+        unsigned long long ka = KEY_NONE, kb = KEY_NONE;
         if (e < n_live) {
             const unsigned a = in.i[e], b = in.j[e];
             const unsigned long long w = in.w[e], ij = ((unsigned long long)a << 32) | b;
             ca = (unsigned)s.comp[a]; cb = (unsigned)s.comp[b];
-            if (w == s.bw[ca]) ka = ij; else ca = MSF_NO_COMP;
-            if (w == s.bw[cb]) kb = ij; else cb = MSF_NO_COMP;
+            if (w == s.bw[ca]) ka = ij; else ca = NO_VERTEX;
+            if (w == s.bw[cb]) kb = ij; else cb = NO_VERTEX;
         }
         wave_min_into(s.bij, ka, ca, lane);
         wave_min_into(s.bij, kb, cb, lane);
@@ -216,7 +168,7 @@ __global__ __launch_bounds__(256) void msf_pass3_kernel(State s, size_t n_live, 
 __global__ __launch_bounds__(256) void msf_hook_kernel(State s, size_t n, unsigned *__restrict__ fsrc)
 {
     for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (size_t)gridDim.x * 256) {
-        if (s.comp[v] != (int)v || s.bw[v] == MSF_NONE) continue;
+        if (s.comp[v] != (int)v || s.bw[v] == KEY_NONE) continue;
         const unsigned long long ij = s.bij[v];
         const int ci = s.comp[(unsigned)(ij >> 32)], cj = s.comp[(unsigned)(ij & 0xffffffffu)];
         const int o = ci == (int)v ? cj : ci;
@@ -247,28 +199,22 @@ __global__ __launch_bounds__(256) void msf_flatten_kernel(State s, size_t n)
     }
 }
 
-// the new forest: fsrc[k] indexes F (< nf) or the batch (>= nf); its values gathered into the temporary forest `t`
-struct Forest { unsigned *i, *j, *d, *nn, *f; unsigned long long *w; double *p, *e; };
-
 __global__ __launch_bounds__(256) void msf_gather_kernel(State s, const unsigned *__restrict__ fsrc, const unsigned *__restrict__ rows,
                                                          const unsigned *__restrict__ cols, const void *__restrict__ weight, int kind,
-                                                         const unsigned *__restrict__ d, const unsigned *__restrict__ nn,
-                                                         const unsigned *__restrict__ filt, const double *__restrict__ p,
-                                                         const double *__restrict__ e, Forest t, size_t n)
+                                                         PairColumns batch, Forest t, size_t n)
 {
     const size_t nf = (size_t)s.hdr->nf, nf_new = std::min<size_t>((size_t)s.hdr->nf_new, n);
     for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < nf_new; k += (size_t)gridDim.x * 256) {
         const size_t q = fsrc[k];
         if (q < nf) {
-            t.i[k] = s.fi[q]; t.j[k] = s.fj[q]; t.w[k] = s.fw[q]; t.d[k] = s.fd[q]; t.nn[k] = s.fnn[q]; t.f[k] = s.ff[q];
-            t.p[k] = s.fp[q]; t.e[k] = s.fe[q];
+            t.i[k] = s.fi[q]; t.j[k] = s.fj[q]; t.w[k] = s.fw[q];
+            copy_columns(t.val, k, s.val, q);
         } else {
             const size_t b = q - nf;
             const unsigned r = rows[b], c = cols[b];
             t.i[k] = r < c ? r : c; t.j[k] = r < c ? c : r;
-            t.w[k] = kind == 0 ? (unsigned long long)static_cast<const unsigned *>(weight)[b] : f64_key(static_cast<const double *>(weight)[b]);
-            t.d[k] = d ? d[b] : 0u; t.nn[k] = nn ? nn[b] : 0u; t.f[k] = filt ? filt[b] : 0u;
-            t.p[k] = p ? p[b] : 0.0; t.e[k] = e ? e[b] : 0.0;
+            t.w[k] = kind == 0 ? (unsigned long long)static_cast<const unsigned *>(weight)[b] : f64_key_up(static_cast<const double *>(weight)[b]);
+            take_columns(t.val, k, batch, b);
         }
     }
 }
@@ -277,8 +223,8 @@ __global__ __launch_bounds__(256) void msf_commit_kernel(State s, Forest t, size
 {
     const size_t nf_new = std::min<size_t>((size_t)s.hdr->nf_new, n);
     for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < nf_new; k += (size_t)gridDim.x * 256) {
-        s.fi[k] = t.i[k]; s.fj[k] = t.j[k]; s.fw[k] = t.w[k]; s.fd[k] = t.d[k]; s.fnn[k] = t.nn[k]; s.ff[k] = t.f[k];
-        s.fp[k] = t.p[k]; s.fe[k] = t.e[k];
+        s.fi[k] = t.i[k]; s.fj[k] = t.j[k]; s.fw[k] = t.w[k];
+        copy_columns(s.val, k, t.val, k);
     }
 }
 
@@ -295,36 +241,23 @@ __global__ __launch_bounds__(256) void msf_sort_keys_kernel(State s, size_t nf, 
     }
 }
 
+// row k of the output: the forest's edge order[k] with its stored endpoints
 __global__ __launch_bounds__(256) void msf_emit_kernel(State s, size_t nf, const unsigned *__restrict__ order, unsigned *rows, unsigned *cols,
-                                                       unsigned *d, unsigned *nn, unsigned *filt, double *p, double *e)
+                                                       PairColumns out)
 {
     for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < nf; k += (size_t)gridDim.x * 256) {
         const unsigned q = order[k];
         if (rows) rows[k] = s.fi[q];
         if (cols) cols[k] = s.fj[q];
-        if (d) d[k] = s.fd[q];
-        if (nn) nn[k] = s.fnn[q];
-        if (filt) filt[k] = s.ff[q];
-        if (p) p[k] = s.fp[q];
-        if (e) e[k] = s.fe[q];
+        emit_columns(out, k, s.val, q);
     }
-}
-
-inline unsigned grid_for(size_t work) { return (unsigned)std::max<size_t>(1, std::min<size_t>((work + 255) / 256, 4096)); }
-
-template <class T>
-int ws(int slot, size_t count, T **out)
-{
-    return tracs::workspace_get(slot, std::max<size_t>(count, 1) * sizeof(T), reinterpret_cast<void **>(out));
 }
 
 }  // namespace
 
-using namespace tracs;
-
 extern "C" {
 
-size_t tracs_msf_state_bytes(size_t n) { return Layout(n).total; }
+size_t tracs_msf_state_bytes(size_t n) { return arena_bytes<State>(n); }
 
 int tracs_msf_init(void *state, size_t n, void *stream_)
 {
@@ -352,22 +285,18 @@ int tracs_msf_update_coo(void *state, size_t n, size_t m, const uint32_t *rows, 
     DeviceCall guard(stream);
     State s(state, n);
     Hdr h{};
-    TRACS_HIP_CHECK(hipMemcpyAsync(&h, s.hdr, sizeof(h), hipMemcpyDeviceToHost, stream));
-    TRACS_HIP_CHECK(hipStreamSynchronize(stream));
-    if (h.n != n) { set_error("tracs_msf_update_coo: the state was initialised for another vertex count"); return TRACS_E_ARG; }
+    int rc;
+    if ((rc = read_state_header(s.hdr, n, "tracs_msf_update_coo", stream, &h))) return rc;
     const size_t nf = (size_t)h.nf, total = nf + m;
     if (total == 0 || n < 2) return TRACS_OK;
     if (total >= (1ull << 32)) { set_error("tracs_msf_update_coo: forest + batch exceed 2^32 - 1 edges"); return TRACS_E_ARG; }
-    Work w[2];
     unsigned *fsrc;
-    int rc;
-    for (int b = 0; b < 2; b++) {
-        if ((rc = ws(Ws::W0 + b, total * 20 + 8, reinterpret_cast<char **>(&w[b].i)))) return rc;
-        w[b].j = w[b].i + total; w[b].src = w[b].j + total;
-        w[b].w = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(w[b].i) + (total * 12 + 7) / 8 * 8);
-    }
-    if ((rc = ws(Ws::FSRC, n, &fsrc))) return rc;
-    const unsigned nb = grid_for(n);
+    char *wb[2], *tb;
+    if ((rc = workspace_get(WS_MSF_W0, arena_bytes<Work>(total), &wb[0]))) return rc;
+    if ((rc = workspace_get(WS_MSF_W1, arena_bytes<Work>(total), &wb[1]))) return rc;
+    Work w[2] = {Work(wb[0], total), Work(wb[1], total)};
+    if ((rc = workspace_get(WS_MSF_FSRC, n, &fsrc))) return rc;
+    const unsigned nb = grid_for(n, SELECT_BLOCKS);
     hipLaunchKernelGGL(msf_init_kernel, dim3(nb), dim3(256), 0, stream, s, n);
     size_t n_in = total;
     int cur = 0;
@@ -375,12 +304,8 @@ int tracs_msf_update_coo(void *state, size_t n, size_t m, const uint32_t *rows, 
         hipLaunchKernelGGL(msf_reset_kernel, dim3(nb), dim3(256), 0, stream, s, n);
         TRACS_HIP_CHECK(hipMemsetAsync(&s.hdr->live, 0, 8, stream));
         Work &out = w[cur ^ (round ? 1 : 0)];
-        if (weight_kind == 0)
-            hipLaunchKernelGGL(msf_pass1_kernel<0>, dim3(grid_for(n_in)), dim3(256), 0, stream, s, n, round == 0 ? 1 : 0, n_in, w[cur], rows,
-                               cols, weight, e_mask, e_max, out);
-        else
-            hipLaunchKernelGGL(msf_pass1_kernel<1>, dim3(grid_for(n_in)), dim3(256), 0, stream, s, n, round == 0 ? 1 : 0, n_in, w[cur], rows,
-                               cols, weight, e_mask, e_max, out);
+        hipLaunchKernelGGL(weight_kind == 0 ? msf_pass1_kernel<0> : msf_pass1_kernel<1>, dim3(grid_for(n_in, SELECT_BLOCKS)), dim3(256), 0,
+                           stream, s, n, round == 0 ? 1 : 0, n_in, w[cur], rows, cols, weight, e_mask, e_max, out);
         TRACS_HIP_CHECK(hipGetLastError());
         unsigned long long live = 0;                             // the one word per round
         TRACS_HIP_CHECK(hipMemcpyAsync(&live, &s.hdr->live, 8, hipMemcpyDeviceToHost, stream));
@@ -388,7 +313,7 @@ int tracs_msf_update_coo(void *state, size_t n, size_t m, const uint32_t *rows, 
         if (round == 0 && n_taken) *n_taken = live - nf;         // F's edges are all live in round 0: the rest are the batch's eligible ones
         if (live == 0) break;
         if (round) cur ^= 1;                                     // round 0 read F u B and wrote w[cur]; later rounds ping-pong
-        const unsigned eb = grid_for((size_t)live);
+        const unsigned eb = grid_for((size_t)live, SELECT_BLOCKS);
         hipLaunchKernelGGL(msf_pass2_kernel, dim3(eb), dim3(256), 0, stream, s, (size_t)live, w[cur]);
         hipLaunchKernelGGL(msf_pass3_kernel, dim3(eb), dim3(256), 0, stream, s, (size_t)live, w[cur]);
         hipLaunchKernelGGL(msf_hook_kernel, dim3(nb), dim3(256), 0, stream, s, n, fsrc);
@@ -397,13 +322,10 @@ int tracs_msf_update_coo(void *state, size_t n, size_t m, const uint32_t *rows, 
         n_in = (size_t)live;
     }
     // the new forest (< n edges): gather its values from F and the batch, then commit
-    char *tb;
-    if ((rc = ws(Ws::FTMP, n * 48, &tb))) return rc;
-    const size_t cap = std::max<size_t>(n, 1);
-    Forest t;
-    t.w = reinterpret_cast<unsigned long long *>(tb); t.p = reinterpret_cast<double *>(tb + cap * 8); t.e = reinterpret_cast<double *>(tb + cap * 16);
-    t.i = reinterpret_cast<unsigned *>(tb + cap * 24); t.j = t.i + cap; t.d = t.j + cap; t.nn = t.d + cap; t.f = t.nn + cap;
-    hipLaunchKernelGGL(msf_gather_kernel, dim3(nb), dim3(256), 0, stream, s, fsrc, rows, cols, weight, weight_kind, d, nn, filt, p, e, t, n);
+    if ((rc = workspace_get(WS_MSF_FTMP, arena_bytes<Forest>(n), &tb))) return rc;
+    const Forest t(tb, n);
+    hipLaunchKernelGGL(msf_gather_kernel, dim3(nb), dim3(256), 0, stream, s, fsrc, rows, cols, weight, weight_kind,
+                       batch_columns(d, nn, filt, p, e), t, n);
     hipLaunchKernelGGL(msf_commit_kernel, dim3(nb), dim3(256), 0, stream, s, t, n);
     hipLaunchKernelGGL(msf_count_kernel, dim3(1), dim3(64), 0, stream, s, n);
     TRACS_HIP_CHECK(hipGetLastError());
@@ -419,26 +341,20 @@ int tracs_msf_emit(void *state, size_t n, size_t *n_edges, uint32_t *rows, uint3
     DeviceCall guard(stream);
     State s(state, n);
     Hdr h{};
-    TRACS_HIP_CHECK(hipMemcpyAsync(&h, s.hdr, sizeof(h), hipMemcpyDeviceToHost, stream));
-    TRACS_HIP_CHECK(hipStreamSynchronize(stream));
-    if (h.n != n) { set_error("tracs_msf_emit: the state was initialised for another vertex count"); return TRACS_E_ARG; }
+    int rc;
+    if ((rc = read_state_header(s.hdr, n, "tracs_msf_emit", stream, &h))) return rc;
     const size_t nf = std::min<size_t>((size_t)h.nf, n);
     *n_edges = nf;
     if (nf == 0) return TRACS_OK;
     unsigned long long *keys;
     unsigned *idx;
-    int rc;
-    if ((rc = ws(Ws::SORT_KEYS, nf * 2, &keys))) return rc;
-    if ((rc = ws(Ws::SORT_IDX, nf * 2, &idx))) return rc;
-    hipLaunchKernelGGL(msf_sort_keys_kernel, dim3(grid_for(nf)), dim3(256), 0, stream, s, nf, keys, idx);
+    if ((rc = workspace_get(WS_MSF_SORT_KEYS, nf * 2, &keys))) return rc;
+    if ((rc = workspace_get(WS_MSF_SORT_IDX, nf * 2, &idx))) return rc;
+    hipLaunchKernelGGL(msf_sort_keys_kernel, dim3(grid_for(nf, SELECT_BLOCKS)), dim3(256), 0, stream, s, nf, keys, idx);
     TRACS_HIP_CHECK(hipGetLastError());
-    unsigned end_bit = 64;                                    // i << 32 | j with j < n: the bits above n's and i's are zero
-    size_t tmp_bytes = 0;
-    TRACS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys + nf, idx, idx + nf, nf, 0u, end_bit, stream));
-    void *tmp;
-    if ((rc = workspace_get(Ws::SORT_TMP, std::max<size_t>(tmp_bytes, 1), &tmp))) return rc;
-    TRACS_HIP_CHECK(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys + nf, idx, idx + nf, nf, 0u, end_bit, stream));
-    hipLaunchKernelGGL(msf_emit_kernel, dim3(grid_for(nf)), dim3(256), 0, stream, s, nf, idx + nf, rows, cols, d, nn, filt, p, e);
+    if ((rc = sort_by_pair_key(keys, idx, nf, nf, WS_MSF_SORT_TMP, stream))) return rc;
+    hipLaunchKernelGGL(msf_emit_kernel, dim3(grid_for(nf, SELECT_BLOCKS)), dim3(256), 0, stream, s, nf, idx + nf, rows, cols,
+                       PairColumns{d, nn, filt, p, e});
     TRACS_HIP_CHECK(hipGetLastError());
     TRACS_HIP_CHECK(hipStreamSynchronize(stream));
     return TRACS_OK;

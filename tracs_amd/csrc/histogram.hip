@@ -25,6 +25,7 @@
 // The panel is read once, coalesced: a wave per row, 4 x 64 consecutive cells per step, and the columns' labels as one int32 load
 // per cell from an array of n labels that stays in L2; the row's label is wave-uniform.
 #include "common.h"
+#include "scan_kernels.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -247,33 +248,6 @@ __global__ __launch_bounds__(256) void hist_count_kernel(const u64 *__restrict__
     if (threadIdx.x == 0) chunk[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
 }
 
-// in place: chunk[0..nc) -> exclusive offsets chunk[0..nc], one workgroup
-__global__ __launch_bounds__(1024) void hist_scan_kernel(long long *__restrict__ chunk, size_t nc)
-{
-    __shared__ long long part[1024];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (size_t base = 0; base < nc + 1; base += 1024) {
-        const size_t idx = base + threadIdx.x;
-        const long long v = idx < nc ? chunk[idx] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const long long t = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0;
-            __syncthreads();
-            part[threadIdx.x] += t;
-            __syncthreads();
-        }
-        const long long incl = part[threadIdx.x];
-        const long long c0 = carry;
-        __syncthreads();
-        if (idx <= nc) chunk[idx] = c0 + incl - v;
-        if (threadIdx.x == 1023) carry = c0 + incl;
-        __syncthreads();
-    }
-}
-
 // the non-empty bins of a chunk, ascending, at the chunk's offset: thread t holds the bins base + 4t .. 4t + 3
 __global__ __launch_bounds__(256) void hist_fill_kernel(const u64 *__restrict__ bins, size_t n_bins, const long long *__restrict__ chunk,
                                                         unsigned *__restrict__ value, u64 *__restrict__ within, u64 *__restrict__ between,
@@ -388,7 +362,7 @@ int tracs_hist_emit(void *state, size_t n_bins, size_t *n_rows, uint32_t *value,
     long long *chunk = hist_chunk_words(state, n_bins);
     const size_t nc = hist_chunks(n_bins);
     hipLaunchKernelGGL(hist_count_kernel, dim3((unsigned)nc), dim3(256), 0, stream, bins, n_bins, chunk);
-    hipLaunchKernelGGL(hist_scan_kernel, dim3(1), dim3(1024), 0, stream, chunk, nc);
+    hipLaunchKernelGGL(scan_i64_inplace_kernel, dim3(1), dim3(1024), 0, stream, chunk, nc);
     TRACS_HIP_CHECK(hipGetLastError());
     u64 over = 0;
     long long total = 0;

@@ -242,8 +242,6 @@ __global__ __launch_bounds__(256) void unpack_kernel(const uint4 *__restrict__ P
     }
 }
 
-constexpr int WS_DIFFERS = 92;      // workspace slot (84 .. 90 are the forest's): the differs bitmap on the device, 4 words per group
-
 // counts (device, may be NULL) and the differs bitmap into `differs_d` (device, 4 words per group)
 static int launch_census(const tracs_alignment *a, unsigned *counts, unsigned *differs_d, hipStream_t stream)
 {
@@ -266,10 +264,10 @@ int site_census(const tracs_alignment *a, uint32_t *counts, uint64_t *differs, s
         if (differs) std::memset(differs, 0, words64 * 8);
         return TRACS_OK;
     }
-    void *d = nullptr;
-    int rc = workspace_get(WS_DIFFERS, a->groups * 16, &d);
+    unsigned *d = nullptr;                                      // the differs bitmap on the device, 4 words per group
+    int rc = workspace_get(WS_MSA_DIFFERS, a->groups * 4, &d);
     if (rc) return rc;
-    if ((rc = launch_census(a, counts, static_cast<unsigned *>(d), stream))) return rc;
+    if ((rc = launch_census(a, counts, d, stream))) return rc;
     if (differs || n_differs) {
         std::vector<uint64_t> tmp;
         uint64_t *dst = differs;

@@ -18,6 +18,8 @@
 // plus the number of list keys below it (binary search over the list).  What lands at K or beyond is dropped.  The compared-site
 // count of a staged cell is read from ncomp when it is merged, while the panel is resident.
 #include "common.h"
+#include "pair_select.h"     // grid_for
+#include "scan_kernels.h"
 
 #include <algorithm>
 
@@ -26,6 +28,7 @@ namespace {
 constexpr unsigned long long KNN_SENT = ~0ull;
 constexpr int KNN_KMAX = 1024;
 constexpr int KNN_CW = 32;          // columns per workgroup of the column part (one 128-byte line of a row)
+constexpr size_t KNN_MAX_BLOCKS = 65536;     // of the grid-stride kernels (init, fill)
 
 inline size_t knn_stride(int k) { return ((size_t)k * 12 + 15) / 16 * 16; }
 
@@ -292,33 +295,6 @@ __global__ __launch_bounds__(256) void knn_count_kernel(void *state, size_t list
     counts[l] = r;
 }
 
-// in place: counts[0..nl) -> exclusive offsets[0..nl], one workgroup
-__global__ __launch_bounds__(1024) void knn_scan_kernel(long long *__restrict__ counts, size_t nl)
-{
-    __shared__ long long part[1024];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (size_t base = 0; base < nl + 1; base += 1024) {
-        const size_t idx = base + threadIdx.x;
-        const long long v = idx < nl ? counts[idx] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const long long t = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0;
-            __syncthreads();
-            part[threadIdx.x] += t;
-            __syncthreads();
-        }
-        const long long incl = part[threadIdx.x];
-        const long long c0 = carry;
-        __syncthreads();
-        if (idx <= nl) counts[idx] = c0 + incl - v;
-        if (threadIdx.x == 1023) carry = c0 + incl;
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(256) void knn_fill_kernel(void *state, size_t list_begin, size_t nl, int K, size_t stride,
                                                        const long long *__restrict__ offsets, unsigned *__restrict__ rows,
                                                        unsigned *__restrict__ cols, unsigned *__restrict__ d, unsigned *__restrict__ nn)
@@ -338,8 +314,6 @@ __global__ __launch_bounds__(256) void knn_fill_kernel(void *state, size_t list_
     }
 }
 
-unsigned grid_for(size_t items) { return (unsigned)std::max<size_t>(1, std::min<size_t>((items + 255) / 256, 65536)); }
-
 }  // namespace
 
 using namespace tracs;
@@ -357,7 +331,7 @@ int tracs_knn_init(void *state, size_t n_lists, int k, void *stream_)
     if (!state && n_lists) { set_error("tracs_knn_init: NULL state"); return TRACS_E_ARG; }
     if (!n_lists) return TRACS_OK;
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    hipLaunchKernelGGL(knn_init_kernel, dim3(grid_for(n_lists * (size_t)k)), dim3(256), 0, stream, state, n_lists, k, knn_stride(k));
+    hipLaunchKernelGGL(knn_init_kernel, dim3(grid_for(n_lists * (size_t)k, KNN_MAX_BLOCKS)), dim3(256), 0, stream, state, n_lists, k, knn_stride(k));
     TRACS_HIP_CHECK(hipGetLastError());
     return TRACS_OK;
 }
@@ -401,9 +375,9 @@ int tracs_knn_emit(void *state, size_t list_begin, size_t list_end, int k, int64
     const size_t stride = knn_stride(k);
     long long *off = reinterpret_cast<long long *>(offsets);
     if (nl) hipLaunchKernelGGL(knn_count_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, stream, state, list_begin, nl, k, stride, off);
-    hipLaunchKernelGGL(knn_scan_kernel, dim3(1), dim3(1024), 0, stream, off, nl);
+    hipLaunchKernelGGL(scan_i64_inplace_kernel, dim3(1), dim3(1024), 0, stream, off, nl);
     if (fill && nl)
-        hipLaunchKernelGGL(knn_fill_kernel, dim3(grid_for(nl * (size_t)k)), dim3(256), 0, stream, state, list_begin, nl, k, stride, off,
+        hipLaunchKernelGGL(knn_fill_kernel, dim3(grid_for(nl * (size_t)k, KNN_MAX_BLOCKS)), dim3(256), 0, stream, state, list_begin, nl, k, stride, off,
                            rows, cols, d, nn);
     TRACS_HIP_CHECK(hipGetLastError());
     return TRACS_OK;

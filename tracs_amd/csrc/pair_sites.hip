@@ -199,7 +199,6 @@ __global__ __launch_bounds__(64) void pair_sites_verdict_kernel(const unsigned *
 
 int get_lgamma_table_for_filter(hipStream_t stream, const double **out);   // transcluster.hip
 
-struct PairSitesWs { enum { SUMS = 64, BAD }; };
 
 static size_t pair_sites_lanes_min()
 {
@@ -227,8 +226,8 @@ int pair_sites_count(const tracs_alignment *a, const unsigned *rows, const unsig
     DeviceCall guard(stream);
     unsigned long long *sums;
     unsigned *bad;
-    if ((rc = workspace_get(PairSitesWs::SUMS, offsets_scan_sums(n_pairs) * 8, reinterpret_cast<void **>(&sums))) ||
-        (rc = workspace_get(PairSitesWs::BAD, 64, reinterpret_cast<void **>(&bad)))) return rc;
+    if ((rc = workspace_get(WS_PSITES_SUMS, offsets_scan_sums(n_pairs), &sums)) ||
+        (rc = workspace_get(WS_PSITES_BAD, 16, &bad))) return rc;
     TRACS_HIP_CHECK(hipMemsetAsync(bad, 0, 4, stream));
     if (n_pairs) {
         if (n_pairs >= pair_sites_lanes_min())

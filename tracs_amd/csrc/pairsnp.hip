@@ -18,6 +18,7 @@
 //   minority sites                                              general_fixup_kernel<MINOR>: distances from sparse lists
 //   counted / full sites                                        pairsnp_mfma_kernel<COUNT>: compared-sites counts, one operand plane
 #include "pairsnp_kernels.h"
+#include "scan_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -441,33 +442,6 @@ __global__ __launch_bounds__(64) void coo_count_kernel(const unsigned *__restric
     }
     for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
     if (threadIdx.x == 0) counts[blockIdx.x] = c;
-}
-
-// exclusive scan of per-row counts (rows <= a few 100k): single workgroup, serial over chunks
-__global__ __launch_bounds__(1024) void scan_rows_kernel(long long *__restrict__ counts, size_t nrows)
-{
-    __shared__ long long part[1024];
-    __shared__ long long carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (size_t base = 0; base < nrows + 1; base += 1024) {
-        const size_t idx = base + threadIdx.x;
-        const long long v = idx < nrows ? counts[idx] : 0;
-        part[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            long long t = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0;
-            __syncthreads();
-            part[threadIdx.x] += t;
-            __syncthreads();
-        }
-        const long long incl = part[threadIdx.x];
-        const long long c0 = carry;
-        __syncthreads();
-        if (idx <= nrows) counts[idx] = c0 + incl - v;      // exclusive
-        if (threadIdx.x == 1023) carry = c0 + incl;
-        __syncthreads();
-    }
 }
 
 __global__ __launch_bounds__(64) void coo_fill_kernel(const unsigned *__restrict__ dist,
@@ -1268,9 +1242,9 @@ static int pairsnp_dense_impl(const tracs_alignment *a_, size_t row_begin, size_
         int2 *live_tiles = nullptr;
         unsigned *n_live_d = nullptr;
         int rc;
-        if ((rc = tracs::workspace_get(48, T.n, reinterpret_cast<void **>(&live)))) return rc;
-        if ((rc = tracs::workspace_get(49, T.n * sizeof(int2), reinterpret_cast<void **>(&live_tiles)))) return rc;
-        if ((rc = tracs::workspace_get(50, 64, reinterpret_cast<void **>(&n_live_d)))) return rc;
+        if ((rc = tracs::workspace_get(tracs::WS_PS_LIVE, T.n, &live))) return rc;
+        if ((rc = tracs::workspace_get(tracs::WS_PS_LIVE_TILES, T.n, &live_tiles))) return rc;
+        if ((rc = tracs::workspace_get(tracs::WS_PS_N_LIVE, 16, &n_live_d))) return rc;
         TRACS_HIP_CHECK(hipMemsetAsync(n_live_d, 0, 4, stream));
         pair_mark(0, stream);
         if ((rc = launch(T.d, (unsigned)T.n, (int)T.n, prefix, prefix, 1, thr, TilePhase{1, 0, live}))) return rc;
@@ -1331,7 +1305,7 @@ int tracs_coo_count(const uint32_t *dist, size_t ld, size_t n, size_t row_begin,
         hipLaunchKernelGGL(coo_count_kernel, dim3((unsigned)nrows), dim3(64), 0, stream, dist, ld, (unsigned)n,
                            (unsigned)row_begin, (unsigned)row_end, (unsigned)col_begin, (int)thr,
                            reinterpret_cast<long long *>(offsets));
-    hipLaunchKernelGGL(scan_rows_kernel, dim3(1), dim3(1024), 0, stream, reinterpret_cast<long long *>(offsets), nrows);
+    hipLaunchKernelGGL(scan_i64_inplace_kernel, dim3(1), dim3(1024), 0, stream, reinterpret_cast<long long *>(offsets), nrows);
     TRACS_HIP_CHECK(hipGetLastError());
     return TRACS_OK;
 }
@@ -1376,7 +1350,7 @@ int tracs_edges_count_f64(const double *val, const uint32_t *dist, size_t ld, si
     if (nrows)
         hipLaunchKernelGGL(edge_count_f64_kernel, dim3((unsigned)nrows), dim3(64), 0, stream, val, dist, ld, (unsigned)n, (unsigned)row_begin,
                            (unsigned)row_end, (unsigned)col_begin, (int)dist_threshold, threshold, reinterpret_cast<long long *>(offsets));
-    hipLaunchKernelGGL(scan_rows_kernel, dim3(1), dim3(1024), 0, stream, reinterpret_cast<long long *>(offsets), nrows);
+    hipLaunchKernelGGL(scan_i64_inplace_kernel, dim3(1), dim3(1024), 0, stream, reinterpret_cast<long long *>(offsets), nrows);
     TRACS_HIP_CHECK(hipGetLastError());
     return TRACS_OK;
 }

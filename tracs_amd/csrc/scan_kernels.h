@@ -1,5 +1,8 @@
-// scan_kernels.h -- the exclusive scan of per-pair counts into list offsets, shared by the files that lay out one list per pair
-// (filter.hip: a pair's SNP positions; pair_sites.hip: its SNP entries).  Included by .hip files only.
+// scan_kernels.h -- the exclusive scans shared between files.  Included by .hip files only.
+//   offsets_scan_launch       per-pair counts (uint32) into list offsets, three launches (filter.hip: a pair's SNP positions;
+//                             pair_sites.hip: its SNP entries)
+//   scan_i64_inplace_kernel   int64 counts into offsets in place, one workgroup (pairsnp.hip: rows of the COO output; nearest.hip:
+//                             the samples' lists; histogram.hip: the chunks' non-empty bins)
 #pragma once
 #include "common.h"
 
@@ -68,6 +71,34 @@ static int offsets_scan_launch(const unsigned *d, size_t n, unsigned long long *
     hipLaunchKernelGGL(offsets_fill_kernel, dim3((unsigned)otiles), dim3(256), 0, stream, d, n, sums, off);
     TRACS_HIP_CHECK(hipGetLastError());
     return TRACS_OK;
+}
+
+// In place: counts[0 .. n) -> exclusive offsets counts[0 .. n] (index n takes the total).  One workgroup of 1 024, serial over tiles of
+// 1 024 (n up to a few 100k).
+static __global__ __launch_bounds__(1024) void scan_i64_inplace_kernel(long long *__restrict__ counts, size_t n)
+{
+    __shared__ long long part[1024];
+    __shared__ long long carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (size_t base = 0; base < n + 1; base += 1024) {
+        const size_t idx = base + threadIdx.x;
+        const long long v = idx < n ? counts[idx] : 0;
+        part[threadIdx.x] = v;
+        __syncthreads();
+        for (int off = 1; off < 1024; off <<= 1) {
+            const long long t = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0;
+            __syncthreads();
+            part[threadIdx.x] += t;
+            __syncthreads();
+        }
+        const long long incl = part[threadIdx.x];
+        const long long c0 = carry;
+        __syncthreads();
+        if (idx <= n) counts[idx] = c0 + incl - v;
+        if (threadIdx.x == 1023) carry = c0 + incl;
+        __syncthreads();
+    }
 }
 
 }  // namespace tracs

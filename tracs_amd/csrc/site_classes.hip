@@ -671,13 +671,13 @@ static int decide(tracs_alignment *a, bool allow_minor, bool allow_nnl, hipStrea
     unsigned long long *off64 = nullptr, *totals = nullptr, *flags = nullptr;
     int rc;
     // (two sets of class masks / sums / offsets / totals: the second holds the classes of the same pass under the other form's criterion)
-    if ((rc = workspace_get(52, 2 * M_SLOTS * groups * sizeof(uint4), reinterpret_cast<void **>(&masks)))) return rc;
-    if ((rc = workspace_get(53, 2 * 7 * groups * sizeof(unsigned), reinterpret_cast<void **>(&offs)))) return rc;
-    if ((rc = workspace_get(54, 2 * groups * SITES_PER_GROUP * sizeof(unsigned), reinterpret_cast<void **>(&cnts)))) return rc;
-    if ((rc = workspace_get(55, 2 * 7 * groups * sizeof(unsigned), reinterpret_cast<void **>(&gcnt)))) return rc;
-    if ((rc = workspace_get(56, 2 * 7 * (groups + 1) * sizeof(unsigned long long), reinterpret_cast<void **>(&off64)))) return rc;
-    if ((rc = workspace_get(57, 256, reinterpret_cast<void **>(&totals)))) return rc;
-    if ((rc = workspace_get(58, groups * flag_words * sizeof(unsigned long long), reinterpret_cast<void **>(&flags)))) return rc;
+    if ((rc = workspace_get(WS_SC_MASKS, 2 * M_SLOTS * groups, &masks))) return rc;
+    if ((rc = workspace_get(WS_SC_OFFS, 2 * 7 * groups, &offs))) return rc;
+    if ((rc = workspace_get(WS_SC_CNTS, 2 * groups * SITES_PER_GROUP, &cnts))) return rc;
+    if ((rc = workspace_get(WS_SC_GCNT, 2 * 7 * groups, &gcnt))) return rc;
+    if ((rc = workspace_get(WS_SC_OFF64, 2 * 7 * (groups + 1), &off64))) return rc;
+    if ((rc = workspace_get(WS_SC_TOTALS, 32, &totals))) return rc;
+    if ((rc = workspace_get(WS_SC_FLAGS, groups * flag_words, &flags))) return rc;
     d_flag = reinterpret_cast<unsigned *>(totals + 15);
     uint4 *const masks_ref = masks;                              // (the reference base bits are written with the first set only)
     uint4 *const masks2 = masks + (size_t)M_SLOTS * groups;
@@ -806,7 +806,7 @@ static int decide(tracs_alignment *a, bool allow_minor, bool allow_nnl, hipStrea
     const size_t gv = groups_for(L_dense), gi = in_place ? 0 : groups_for(L_count);
     const size_t vbytes = class_plane_bytes(a, gv, npv, PAD_GROUPS), ibytes = class_plane_bytes(a, gi, 1, PAD_GROUPS);
     unsigned *lists = nullptr;
-    if ((rc = workspace_get(59, (L_dense + L_count + 1) * sizeof(unsigned), reinterpret_cast<void **>(&lists)))) return rc;
+    if ((rc = workspace_get(WS_SC_LISTS, L_dense + L_count + 1, &lists))) return rc;
     if (pack_alloc(a, vbytes, reinterpret_cast<void **>(&a->vplanes)) != hipSuccess) return soft_fail();
     if (gi && pack_alloc(a, ibytes, reinterpret_cast<void **>(&a->iplanes)) != hipSuccess) return soft_fail();
     if (pack_alloc(a, a->n_pad * sizeof(unsigned), reinterpret_cast<void **>(&a->c_counted)) != hipSuccess) return soft_fail();

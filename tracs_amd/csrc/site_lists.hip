@@ -610,7 +610,7 @@ __global__ __launch_bounds__(ENT_TILE_THREADS) void buckets_to_samples_kernel(co
     }
 }
 
-// exclusive scan of v[0 .. count) -> out[0 .. count] (one workgroup; wave scans through shuffles); the largest element -> *vmax
+// exclusive scan of v[0 .. count) -> out[0 .. count] (out[count]: the total; one workgroup; wave scans through shuffles)
 __global__ __launch_bounds__(1024) void scan_counts_kernel(const unsigned *__restrict__ v, size_t count, unsigned long long *__restrict__ out)
 {
     __shared__ unsigned long long wave_tot[16];
@@ -1428,15 +1428,14 @@ int minority_lists_build(tracs_alignment *a, const MinorBuild &mb_, hipStream_t 
     // E: (sample, entry) of every p-list entry with w = 1: what the per-sample lists are bucketed from.  A group's entries sit in its run of
     // list positions -- closed up at the front (e_cnt[g] of them: p_lists_kernel) or where their list has them, holes between
     // (e_cnt[g] = all ones: site_lists_kernel; everywhere when the fill is the one-pass one)
-    if ((rc = workspace_get(60, (2 * std::max<size_t>(n, 1) + 8 + 256) * 4, reinterpret_cast<void **>(&cnt))) ||
-        (rc = workspace_get(61, std::max<size_t>(groups, 1) * sizeof(unsigned), reinterpret_cast<void **>(&e_cnt))) ||
-        (rc = workspace_get(62, std::max<size_t>(mb.tot_p, 1) * sizeof(uint2), reinterpret_cast<void **>(&E)))) { delete g; return rc; }
+    if ((rc = workspace_get(WS_SL_CNT, 2 * std::max<size_t>(n, 1) + 8 + 256, &cnt)) ||
+        (rc = workspace_get(WS_SL_ECNT, std::max<size_t>(groups, 1), &e_cnt)) ||
+        (rc = workspace_get(WS_SL_ENTRIES, std::max<size_t>(mb.tot_p, 1), &E))) { delete g; return rc; }
     unsigned *cur = cnt + std::max<size_t>(n, 1), *d_max = cur + std::max<size_t>(n, 1), *bcur = d_max + 8;
     unsigned shift = 0;
     while (n && ((n - 1) >> shift) >= 256u) shift++;                                  // at most 256 buckets of 2^shift samples
     const bool two_pass = mb.tot_p >= ENT_TILE && mb.tot_p < (1ull << 32) && shift <= 10 &&      // (32-bit run cursors; at most 1 024 samples per bucket)
-                          workspace_get(63, (size_t)mb.tot_p * sizeof(uint2), reinterpret_cast<void **>(&tmp)) == TRACS_OK;
-    if (!two_pass) { (void)hipGetLastError(); set_error(""); }
+                          workspace_try(WS_SL_ENTRIES_TMP, (size_t)mb.tot_p, &tmp);       // (optional: without it the fill is the one-pass one)
     SL_TRY(hipMemsetAsync(cnt, 0, (2 * std::max<size_t>(n, 1) + 8 + 256) * 4, stream));
     SL_TRY(hipMemsetAsync(g->c_p, 0, std::max<size_t>(n, 1) * 4, stream));
     SL_TRY(hipMemcpyAsync(g->lst_mask, mb.lst_mask, groups * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
@@ -1588,7 +1587,7 @@ int minority_fixup(tracs_alignment *a, size_t row_begin, size_t row_end, size_t 
     // scratch rows for the cells (y, x) with y < x that row x's walks feed: (n - row_begin) rows of (row_end - row_begin) columns
     const size_t s_pitch = (row_end - row_begin + 63) / 64 * 64;
     unsigned *S = nullptr;
-    const int rc = workspace_get(46, (n - row_begin) * s_pitch * sizeof(unsigned), reinterpret_cast<void **>(&S));
+    const int rc = workspace_get(WS_SL_NROWS, (n - row_begin) * s_pitch, &S);
     if (rc) return rc;
     const dim3 grid((unsigned)(n - row_begin), (unsigned)((n + chunk - 1) / chunk));
 #define TRACS_FIXUP_LAUNCH(CL, QWV) hipLaunchKernelGGL((minor_fixup_kernel<CL, QWV, GR, NR>), grid, dim3(1024), lds, stream, g->s_off, g->s_ent, g->p_off, g->p_ent, \

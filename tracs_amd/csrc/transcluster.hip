@@ -1216,7 +1216,6 @@ static int get_lgamma_table(hipStream_t stream, const double **out)
 
 int get_lgamma_table_for_filter(hipStream_t stream, const double **out) { return get_lgamma_table(stream, out); }
 
-struct TcWorkspaceIds { enum { SLOTS = 0, ESLOT, SLOT_ID, NKEYS, KEY_ELEM, KEY_P0, KEY_EK, LONG_IDS, KEY_STATE, TAB, TAB_LNS, TAB_POIS, GRID_BITS, GRID_TABLES, TAB_LNS_N, REST_IDS }; };
 constexpr unsigned long long TC_POIS_ELEMS = 16ull << 20;        // doubles in the pois table (128 MB)
 
 static unsigned long long g_last_keys = 0;        // distinct (N, delta) keys of the last entry-point call (bench.py reports it)
@@ -1240,11 +1239,11 @@ static int tc_evaluate_keys(const Src &src, const unsigned *key_elem, unsigned n
     int rc;
     unsigned *long_ids;
     double *key_p0, *key_eK;
-    if ((rc = workspace_get(TcWorkspaceIds::KEY_P0, (size_t)nk * 8, reinterpret_cast<void **>(&key_p0)))) return rc;
-    if ((rc = workspace_get(TcWorkspaceIds::KEY_EK, (size_t)nk * 8, reinterpret_cast<void **>(&key_eK)))) return rc;
-    if ((rc = workspace_get(TcWorkspaceIds::LONG_IDS, (size_t)nk * 4, reinterpret_cast<void **>(&long_ids)))) return rc;
+    if ((rc = workspace_get(WS_TC_KEY_P0, (size_t)nk, &key_p0))) return rc;
+    if ((rc = workspace_get(WS_TC_KEY_EK, (size_t)nk, &key_eK))) return rc;
+    if ((rc = workspace_get(WS_TC_LONG_IDS, (size_t)nk, &long_ids))) return rc;
     double *key_state = nullptr;
-    if ((rc = workspace_get(TcWorkspaceIds::KEY_STATE, (size_t)nk * 32, reinterpret_cast<void **>(&key_state)))) return rc;
+    if ((rc = workspace_get(WS_TC_KEY_STATE, (size_t)nk * 4, &key_state))) return rc;
     TcParams P;
     P.lamb = lamb; P.beta = beta; P.thr = thr;
     P.ln_lamb = P.ln_beta = P.ln_lb = 0.0;
@@ -1254,32 +1253,26 @@ static int tc_evaluate_keys(const Src &src, const unsigned *key_elem, unsigned n
     hipLaunchKernelGGL((tc_keys_kernel<Src>), dim3((nk + 63) / 64), dim3(64), 0, stream, src, key_elem, nk, P, lg, key_p0, key_eK,
                        long_ids, n_keys + 1, n_keys + 8, key_state, kt);
     // (gap, M) tables of the prefix sums, when the source has day gaps and the keys' bounds fit (decided on the device)
-    TcTables *tab = nullptr;
+    unsigned char *tab_block = nullptr;                                   // 256 bytes: the TcTables, the keys' bounds at byte 128
     double *tab_lnS = nullptr, *tab_pois = nullptr, *tab_lnS_n = nullptr;
-    if ((rc = workspace_get(TcWorkspaceIds::TAB, 256, reinterpret_cast<void **>(&tab)))) return rc;
+    if ((rc = workspace_get(WS_TC_TAB, 256, &tab_block))) return rc;
+    TcTables *tab = reinterpret_cast<TcTables *>(tab_block);
     TRACS_HIP_CHECK(hipMemsetAsync(tab, 0, 256, stream));                 // ok = 0
     // The tables are an optional speed-up (ok = 0 is a working path): only worth their 512 MB of workspace when there are enough
     // keys to share the per-gap sums, and not getting the memory -- e.g. beside a rank's alignment, panels and lists -- is not an error.
     if (Src::HAS_GAPS && nk >= 2048) {
-        const bool have = workspace_get(TcWorkspaceIds::TAB_LNS, TC_TABLE_ELEMS * 8, reinterpret_cast<void **>(&tab_lnS)) == TRACS_OK &&
-                          workspace_get(TcWorkspaceIds::TAB_POIS, TC_POIS_ELEMS * 8, reinterpret_cast<void **>(&tab_pois)) == TRACS_OK;
-        if (have) {
+        if (workspace_try(WS_TC_TAB_LNS, TC_TABLE_ELEMS, &tab_lnS) && workspace_try(WS_TC_TAB_POIS, TC_POIS_ELEMS, &tab_pois)) {
             // (the linear form needs ln S_N beside it; without that workspace the tables stay in log space)
-            if (workspace_get(TcWorkspaceIds::TAB_LNS_N, TC_POIS_ELEMS * 8, reinterpret_cast<void **>(&tab_lnS_n)) != TRACS_OK) {
-                (void)hipGetLastError(); set_error(""); tab_lnS_n = nullptr;
-            }
-            unsigned *bounds = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(tab) + 128);
+            workspace_try(WS_TC_TAB_LNS_N, TC_POIS_ELEMS, &tab_lnS_n);
+            unsigned *bounds = reinterpret_cast<unsigned *>(tab_block + 128);
             hipLaunchKernelGGL((tc_key_bounds_kernel<Src>), dim3(256), dim3(256), 0, stream, src, key_elem, n_keys, bounds);
             hipLaunchKernelGGL(tc_tables_kernel, dim3(1024), dim3(64), 0, stream, tab, bounds, n_keys, tab_lnS, tab_pois, tab_lnS_n, TC_POIS_ELEMS, P, lg);
-        } else {
-            (void)hipGetLastError();
-            set_error("");
         }
     }
     // long series (E(K) loop beyond TC_SERIAL_CAP terms): one wave per key -- the term-ratio loop where the linear tables hold the key,
     // the log-space loop for the rest (n_keys[9] of them, listed by the first kernel)
     unsigned *rest_ids = nullptr;
-    if ((rc = workspace_get(TcWorkspaceIds::REST_IDS, (size_t)nk * 4, reinterpret_cast<void **>(&rest_ids)))) return rc;
+    if ((rc = workspace_get(WS_TC_REST_IDS, (size_t)nk, &rest_ids))) return rc;
     hipLaunchKernelGGL((tc_ratio_keys_kernel<Src>), dim3(std::min<unsigned>(nk, 256u * 32u)), dim3(64), 0, stream, src, key_elem,
                        long_ids, n_keys + 1, n_keys + 8, nk, P, lg, key_p0, key_eK, key_state, kt, tab, rest_ids, n_keys + 9);
     hipLaunchKernelGGL((tc_long_keys_kernel<Src>), dim3(std::min<unsigned>(nk, 256u * 32u)), dim3(64), 0, stream, src, key_elem,
@@ -1304,13 +1297,13 @@ static int run_trans_dist(const Src &src, size_t total, double lamb, double beta
     while ((size_t)cap_max < 2 * total && cap_max < (1u << 31)) cap_max <<= 1;
     unsigned cap = std::min(cap_max, 1u << 20);
     unsigned *slots, *eslot, *slot_id, *n_keys, *key_elem;
-    if ((rc = workspace_get(TcWorkspaceIds::ESLOT, total * 4, reinterpret_cast<void **>(&eslot)))) return rc;
-    if ((rc = workspace_get(TcWorkspaceIds::NKEYS, 64, reinterpret_cast<void **>(&n_keys)))) return rc;
+    if ((rc = workspace_get(WS_TC_ESLOT, total, &eslot))) return rc;
+    if ((rc = workspace_get(WS_TC_NKEYS, 16, &n_keys))) return rc;
     const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 32);
     unsigned nk = 0;
     for (;;) {
-        if ((rc = workspace_get(TcWorkspaceIds::SLOTS, (size_t)cap * 4, reinterpret_cast<void **>(&slots)))) return rc;
-        if ((rc = workspace_get(TcWorkspaceIds::SLOT_ID, (size_t)cap * 4, reinterpret_cast<void **>(&slot_id)))) return rc;
+        if ((rc = workspace_get(WS_TC_SLOTS, (size_t)cap, &slots))) return rc;
+        if ((rc = workspace_get(WS_TC_SLOT_ID, (size_t)cap, &slot_id))) return rc;
         TRACS_HIP_CHECK(hipMemsetAsync(slots, 0xFF, (size_t)cap * 4, stream));
         TRACS_HIP_CHECK(hipMemsetAsync(n_keys, 0, 16, stream));     // [0] keys, [1] long keys, [2] overflow flag
         hipLaunchKernelGGL((dedup_insert_kernel<Src>), dim3(blocks), dim3(256), 0, stream, src, slots, cap - 1, eslot, n_keys + 2);
@@ -1332,7 +1325,7 @@ static int run_trans_dist(const Src &src, size_t total, double lamb, double beta
     }
     g_last_keys += nk;
     if (nk == 0) return TRACS_OK;
-    if ((rc = workspace_get(TcWorkspaceIds::KEY_ELEM, (size_t)nk * 4, reinterpret_cast<void **>(&key_elem)))) return rc;
+    if ((rc = workspace_get(WS_TC_KEY_ELEM, (size_t)nk, &key_elem))) return rc;
     TRACS_HIP_CHECK(hipMemsetAsync(n_keys, 0, 8, stream));          // [0] key counter, [1] long-key counter
     hipLaunchKernelGGL(dedup_collect_kernel, dim3((unsigned)std::min<size_t>((cap + 255) / 256, 256 * 32)), dim3(256), 0, stream,
                        slots, cap, slot_id, key_elem, n_keys);
@@ -1360,8 +1353,8 @@ static int run_trans_dist_grid(const DenseSource &src, size_t total, double lamb
     if (rc) return rc;
     unsigned *n_keys = nullptr, *bits = nullptr, *key_elem = nullptr;
     constexpr unsigned words = (unsigned)(TC_GRID_BITS / 32);
-    if ((rc = workspace_get(TcWorkspaceIds::NKEYS, 64, reinterpret_cast<void **>(&n_keys)))) return rc;
-    if ((rc = workspace_get(TcWorkspaceIds::GRID_BITS, (size_t)words * 4, reinterpret_cast<void **>(&bits)))) return rc;
+    if ((rc = workspace_get(WS_TC_NKEYS, 16, &n_keys))) return rc;
+    if ((rc = workspace_get(WS_TC_GRID_BITS, (size_t)words, &bits))) return rc;
     unsigned *cb = n_keys + 4;                                       // [4] max N, [5] min day, [6] max day, [7] does not fit
     const unsigned init[8] = {0u, 0u, 0u, 0u, 0u, 0xFFFFFFFFu, 0u, 0u};
     TRACS_HIP_CHECK(hipMemcpyAsync(n_keys, init, 32, hipMemcpyHostToDevice, stream));
@@ -1382,10 +1375,8 @@ static int run_trans_dist_grid(const DenseSource &src, size_t total, double lamb
     const unsigned n_max = h[4], d_max = h[6] - h[5];
     const size_t cells = ((size_t)n_max + 1) * ((size_t)d_max + 1);
     double *tables = nullptr;
-    if (workspace_get(TcWorkspaceIds::GRID_TABLES, cells * 16, reinterpret_cast<void **>(&tables)) != TRACS_OK) {
-        (void)hipGetLastError(); set_error(""); g_last_keys -= nk; *done = 0; return TRACS_OK;
-    }
-    if ((rc = workspace_get(TcWorkspaceIds::KEY_ELEM, (size_t)nk * 4, reinterpret_cast<void **>(&key_elem)))) return rc;
+    if (!workspace_try(WS_TC_GRID_TABLES, cells * 2, &tables)) { g_last_keys -= nk; *done = 0; return TRACS_OK; }
+    if ((rc = workspace_get(WS_TC_KEY_ELEM, (size_t)nk, &key_elem))) return rc;
     TRACS_HIP_CHECK(hipMemsetAsync(n_keys, 0, 8, stream));          // [0] key counter, [1] long-key counter
     hipLaunchKernelGGL(tc_bits_collect_kernel, dim3(1024), dim3(256), 0, stream, bits, words, key_elem, n_keys);
     KeyTable kt;
@@ -1414,7 +1405,6 @@ constexpr unsigned KS_TRAILER = 4;
 constexpr unsigned KS_CHUNK = 1024;                         // words per workgroup of the numbering
 constexpr unsigned KS_CHUNKS = KS_WORDS / KS_CHUNK;
 static_assert(KS_CHUNKS == 512, "ks_chunk_scan_kernel: one thread per chunk");
-struct KsWs { enum { RANK = 80, CHUNK, INFO }; };
 
 __global__ void ks_merge_kernel(unsigned *__restrict__ own, const unsigned *__restrict__ all, int parts)
 {
@@ -1509,8 +1499,8 @@ __global__ void ks_unpack_kernel(const unsigned *__restrict__ bits, const unsign
 static int ks_number(const unsigned *keys, unsigned **word_rank, unsigned **chunk_base, unsigned *total_dev, hipStream_t stream)
 {
     int rc;
-    if ((rc = workspace_get(KsWs::RANK, (size_t)KS_WORDS * 4, reinterpret_cast<void **>(word_rank)))) return rc;
-    if ((rc = workspace_get(KsWs::CHUNK, (size_t)KS_CHUNKS * 4, reinterpret_cast<void **>(chunk_base)))) return rc;
+    if ((rc = workspace_get(WS_KS_RANK, (size_t)KS_WORDS, word_rank))) return rc;
+    if ((rc = workspace_get(WS_KS_CHUNK, (size_t)KS_CHUNKS, chunk_base))) return rc;
     hipLaunchKernelGGL(ks_rank_kernel, dim3(KS_CHUNKS), dim3(256), 0, stream, keys, *word_rank, *chunk_base);
     hipLaunchKernelGGL(ks_chunk_scan_kernel, dim3(1), dim3(512), 0, stream, *chunk_base, total_dev);
     TRACS_HIP_CHECK(hipGetLastError());
@@ -1612,7 +1602,7 @@ int tracs_trans_keys_info(const uint32_t *keys, uint64_t *info, void *stream_)
     DeviceCall guard(stream);
     unsigned *word_rank = nullptr, *chunk_base = nullptr, *total = nullptr;
     int rc;
-    if ((rc = workspace_get(KsWs::INFO, 64, reinterpret_cast<void **>(&total)))) return rc;
+    if ((rc = workspace_get(WS_KS_INFO, 16, &total))) return rc;
     if ((rc = ks_number(keys, &word_rank, &chunk_base, total, stream))) return rc;
     unsigned h[1 + KS_TRAILER] = {0};
     TRACS_HIP_CHECK(hipMemcpyAsync(h, total, 4, hipMemcpyDeviceToHost, stream));
@@ -1642,11 +1632,11 @@ int tracs_trans_keys_evaluate(const uint32_t *keys, const uint64_t *info, int pa
     if ((rc = get_lgamma_table(stream, &lg))) return rc;
     unsigned *word_rank = nullptr, *chunk_base = nullptr, *n_keys = nullptr, *key_elem = nullptr;
     double *tables = nullptr;
-    if ((rc = workspace_get(TcWorkspaceIds::NKEYS, 64, reinterpret_cast<void **>(&n_keys)))) return rc;
+    if ((rc = workspace_get(WS_TC_NKEYS, 16, &n_keys))) return rc;
     if ((rc = ks_number(keys, &word_rank, &chunk_base, n_keys + 12, stream))) return rc;
     const size_t cells = (size_t)(k.n_max + 1) * (size_t)(k.d_max + 1);
-    if ((rc = workspace_get(TcWorkspaceIds::GRID_TABLES, cells * 16, reinterpret_cast<void **>(&tables)))) return rc;
-    if ((rc = workspace_get(TcWorkspaceIds::KEY_ELEM, (size_t)n_own * 4, reinterpret_cast<void **>(&key_elem)))) return rc;
+    if ((rc = workspace_get(WS_TC_GRID_TABLES, cells * 2, &tables))) return rc;
+    if ((rc = workspace_get(WS_TC_KEY_ELEM, (size_t)n_own, &key_elem))) return rc;
     hipLaunchKernelGGL(ks_collect_kernel, dim3(1024), dim3(256), 0, stream, keys, word_rank, chunk_base, (unsigned)part, (unsigned)parts, key_elem);
     const unsigned init[8] = {n_own, 0u, 0u, 0u, 0u, 0u, 0u, 0u};      // [0] keys, [1] long keys; [7] a key outside the table (cannot happen)
     TRACS_HIP_CHECK(hipMemcpyAsync(n_keys, init, sizeof(init), hipMemcpyHostToDevice, stream));
@@ -1680,10 +1670,10 @@ int tracs_trans_keys_gather(const uint32_t *dist, size_t ld, size_t n, const siz
     DeviceCall guard(stream);
     unsigned *word_rank = nullptr, *chunk_base = nullptr, *n_keys = nullptr;
     double *tables = nullptr;
-    if ((rc = workspace_get(TcWorkspaceIds::NKEYS, 64, reinterpret_cast<void **>(&n_keys)))) return rc;
+    if ((rc = workspace_get(WS_TC_NKEYS, 16, &n_keys))) return rc;
     if ((rc = ks_number(keys, &word_rank, &chunk_base, n_keys + 12, stream))) return rc;
     const size_t cells = (size_t)(k.n_max + 1) * (size_t)(k.d_max + 1);
-    if ((rc = workspace_get(TcWorkspaceIds::GRID_TABLES, cells * 16, reinterpret_cast<void **>(&tables)))) return rc;
+    if ((rc = workspace_get(WS_TC_GRID_TABLES, cells * 2, &tables))) return rc;
     hipLaunchKernelGGL(ks_unpack_kernel, dim3(1024), dim3(256), 0, stream, keys, word_rank, chunk_base, (unsigned)parts, per, vals_all, exp_p0, tables);
     KeyTable kt;
     kt.n_max = (unsigned)k.n_max; kt.d_max = (unsigned)k.d_max; kt.p0 = tables; kt.eK = tables + 1; kt.step = 2; kt.overflow = n_keys + 7;

@@ -378,24 +378,28 @@ def msf_init(n, device=None):
     return state
 
 
-def msf_update(state, n, rows, cols, weight, e_mask=None, e_max=-1.0, d=None, nn=None, filt=None, p=None, e=None):
-    """F <- MSF(F u batch) (tracs_msf_update_coo): rows / cols int32 or uint32 device tensors, weight uint32-valued (int32 / uint32
-    tensor, read as unsigned) or float64; e_mask (float64): only pairs with e_max >= e_mask are eligible.  d, nn, filt (32-bit) and
-    p, e (float64) are the values kept with a pair.  -> the batch's eligible pairs."""
-    L = _lib.require_gpu()
+def _check_pair_batch(rows, cols, key, e_mask, d, nn, filt, p, e):
+    """The tensor checks msf_update and anc_update share.  -> the batch's length, whether `key` (the weight / value) is float64"""
     m = int(rows.numel())
-    assert cols.numel() == m and weight.numel() == m
-    for t in (rows, cols, weight, e_mask, d, nn, filt, p, e):
+    assert cols.numel() == m and key.numel() == m
+    for t in (rows, cols, key, e_mask, d, nn, filt, p, e):
         assert t is None or (t.is_contiguous() and t.numel() == m)
     for t in (rows, cols, d, nn, filt):
         assert t is None or t.element_size() == 4
     for t in (e_mask, p, e):
         assert t is None or t.dtype == torch.float64
-    if weight.dtype == torch.float64:
-        kind = 1
-    else:
-        assert weight.element_size() == 4 and not weight.is_floating_point()
-        kind = 0
+    is_f64 = key.dtype == torch.float64
+    assert is_f64 or (key.element_size() == 4 and not key.is_floating_point())
+    return m, is_f64
+
+
+def msf_update(state, n, rows, cols, weight, e_mask=None, e_max=-1.0, d=None, nn=None, filt=None, p=None, e=None):
+    """F <- MSF(F u batch) (tracs_msf_update_coo): rows / cols int32 or uint32 device tensors, weight uint32-valued (int32 / uint32
+    tensor, read as unsigned) or float64; e_mask (float64): only pairs with e_max >= e_mask are eligible.  d, nn, filt (32-bit) and
+    p, e (float64) are the values kept with a pair.  -> the batch's eligible pairs."""
+    L = _lib.require_gpu()
+    m, is_f64 = _check_pair_batch(rows, cols, weight, e_mask, d, nn, filt, p, e)
+    kind = 1 if is_f64 else 0
     taken = C.c_uint64(0)
     _lib.check(L.tracs_msf_update_coo(_ptr(state), int(n), m, _ptr(rows), _ptr(cols), _ptr(weight), kind, _ptr(e_mask), float(e_max),
                                       _ptr(d), _ptr(nn), _ptr(filt), _ptr(p), _ptr(e), C.byref(taken), _stream()))
@@ -430,19 +434,9 @@ def anc_update(state, n, rows, cols, value, descending=False, e_mask=None, e_max
     only pairs with e_max >= e_mask are eligible.  d, nn, filt (32-bit) and p, e (float64) are the values kept with a pair.  -> the
     candidates offered (the batch's eligible pairs with unequal days)."""
     L = _lib.require_gpu()
-    m = int(rows.numel())
-    assert cols.numel() == m and value.numel() == m
-    for t in (rows, cols, value, e_mask, d, nn, filt, p, e):
-        assert t is None or (t.is_contiguous() and t.numel() == m)
-    for t in (rows, cols, d, nn, filt):
-        assert t is None or t.element_size() == 4
-    for t in (e_mask, p, e):
-        assert t is None or t.dtype == torch.float64
-    if value.dtype == torch.float64:
-        kind = 2 if descending else 1
-    else:
-        assert value.element_size() == 4 and not value.is_floating_point() and not descending
-        kind = 0
+    m, is_f64 = _check_pair_batch(rows, cols, value, e_mask, d, nn, filt, p, e)
+    assert is_f64 or not descending
+    kind = (2 if descending else 1) if is_f64 else 0
     taken = C.c_uint64(0)
     _lib.check(L.tracs_anc_update_coo(_ptr(state), int(n), m, _ptr(rows), _ptr(cols), _ptr(value), kind, _ptr(e_mask), float(e_max),
                                       _ptr(d), _ptr(nn), _ptr(filt), _ptr(p), _ptr(e), C.byref(taken), _stream()))
