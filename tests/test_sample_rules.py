@@ -83,23 +83,26 @@ def test_samples_out_writer(tmp_path):
 
 def test_api_refuses_bad_rule_arguments():
     """the keyword checks of the array entry points come before the library is asked for a GPU"""
-    from tracs_amd import api
+    from tracs_amd.handle import rules_struct
     from tracs_amd.sites import Sites
     with pytest.raises(ValueError, match="max_sample_n_share must be in"):
-        api._rules(None, 1.2, None, None)
+        rules_struct(None, 1.2, None, None)
     with pytest.raises(ValueError, match="max_n_share must be in"):
-        api._rules(None, None, -0.5, None)
+        rules_struct(None, None, -0.5, None)
     with pytest.raises(ValueError, match="min_sites must be in"):
-        api._rules(None, None, None, 0)
+        rules_struct(None, None, None, 0)
     with pytest.raises(ValueError, match="cannot be combined with max_sample_n_share"):
-        api._rules(Sites(max_n_samples=3), 0.5, None, None)
+        rules_struct(Sites(max_n_samples=3), 0.5, None, None)
     with pytest.raises(ValueError, match="two forms of one rule"):
-        api._rules(Sites(max_n_samples=3), None, 0.2, None)
-    assert api._rules(Sites(max_n_samples=3), None, None, None) == (None, None)        # the existing route stays as it is
-    r, alive = api._rules(Sites(np.array([True, False, True])), 0.5, 0.25, 7)
+        rules_struct(Sites(max_n_samples=3), None, 0.2, None)
+    r, alive = rules_struct(Sites(max_n_samples=3), None, None, None)                      # the threshold travels as it is
+    assert alive is None and not r.keep and (r.keep_len, r.max_n_share, r.max_sample_n_share, r.min_sites, r.max_n_samples) == (0, -1.0, -1.0, 0, 3)
+    r, alive = rules_struct(None, None, None, None)                                        # nothing given: no field set
+    assert alive is None and not r.keep and (r.keep_len, r.max_n_share, r.max_sample_n_share, r.min_sites, r.max_n_samples) == (0, -1.0, -1.0, 0, 0xFFFFFFFF)
+    r, alive = rules_struct(Sites(np.array([True, False, True])), 0.5, 0.25, 7)
     assert (r.keep_len, r.max_n_share, r.max_sample_n_share, r.min_sites, r.max_n_samples) == (3, 0.25, 0.5, 7, 0xFFFFFFFF)
     assert int(alive[0]) == 0b101
-    r, alive = api._rules(None, None, None, 9)
+    r, alive = rules_struct(None, None, None, 9)
     assert not r.keep and (r.max_n_share, r.max_sample_n_share, r.min_sites) == (-1.0, -1.0, 9)
 
 

@@ -10,56 +10,7 @@ import os
 import numpy as np
 
 from . import _lib
-
-
-def _paths(fasta):
-    if isinstance(fasta, (str, bytes, os.PathLike)):
-        raise TypeError("pairsnp(): fasta must be a list of paths")
-    return [os.fsencode(p) for p in fasta]
-
-
-def _site_args(sites):
-    """sites (tracs_amd.sites.Sites or None) -> (array kept alive, keep pointer, keep_len, max_n_samples) of the _sites entry points"""
-    if sites is None:
-        return None, None, 0, 0xFFFFFFFF
-    words, keep_len, max_n = sites.c_args()
-    return words, (words.ctypes.data_as(C.POINTER(C.c_uint64)) if words is not None else None), keep_len, max_n
-
-
-def _rules(sites, max_sample_n_share, max_n_share, min_sites):
-    """The sample / pair rules and the N share of the FASTA entry points -> (_lib.Rules, array kept alive), or
-    (None, None) when none of the three is given (the call then goes the way it always went)."""
-    if max_sample_n_share is None and max_n_share is None and min_sites is None:
-        return None, None
-    for name, share in (("max_sample_n_share", max_sample_n_share), ("max_n_share", max_n_share)):
-        if share is not None and not (0.0 <= float(share) <= 1.0):
-            raise ValueError("%s must be in [0, 1], got %r" % (name, share))
-    if min_sites is not None and not (1 <= int(min_sites) <= 0xFFFFFFFF):
-        raise ValueError("min_sites must be in [1, 2^32 - 1], got %r" % (min_sites,))
-    if sites is not None and sites.max_n_samples is not None:
-        if max_sample_n_share is not None:
-            raise ValueError("Sites(max_n_samples=...) cannot be combined with max_sample_n_share: the N rule counts over the samples "
-                             "that survive the sample rule, whose number is only known on the device; give max_n_share")
-        if max_n_share is not None:
-            raise ValueError("Sites(max_n_samples=...) and max_n_share are two forms of one rule; give one")
-    words, keep_len, max_n = (None, 0, 0xFFFFFFFF) if sites is None else sites.c_args()
-    r = _lib.Rules(words.ctypes.data_as(C.POINTER(C.c_uint64)) if words is not None else None, keep_len,
-                   -1.0 if max_n_share is None else float(max_n_share), -1.0 if max_sample_n_share is None else float(max_sample_n_share),
-                   0 if min_sites is None else int(min_sites), max_n)
-    return r, words
-
-
-def _source_info(L, h, kind, info):
-    """info <- what the sample rule saw (tracs_<kind>_source_*): the names of the records read, their N counts among the
-    "rule_sites" file-kept columns, and which stayed"""
-    if info is None:
-        return
-    get = lambda name: getattr(L, "tracs_%s_%s" % (kind, name))                     # noqa: E731
-    n = get("source_nseq")(h)
-    info["source_names"] = [get("source_name")(h, i).decode("utf-8", "replace") for i in range(n)]
-    info["n_counts"] = np.array([get("source_n_count")(h, i) for i in range(n)], np.uint32)
-    info["kept"] = np.array([get("source_kept")(h, i) != 0 for i in range(n)], bool)
-    info["rule_sites"] = int(get("rule_sites")(h))
+from .handle import DistanceHandle, input_paths, require_files, run_arrays
 
 
 def pairsnp_arrays(fasta, n_threads=1, dist=2147483647, filter=False, sites=None, info=None, max_sample_n_share=None, max_n_share=None,
@@ -71,28 +22,8 @@ def pairsnp_arrays(fasta, n_threads=1, dist=2147483647, filter=False, sites=None
     sites.keep leaves; max_n_share F: columns dropped where more than floor(F n') of the n' surviving samples are N; min_sites M:
     only pairs compared over at least M kept sites.  names, rows and cols are the surviving samples; info then
     also receives "source_names", "n_counts", "kept" (per record read) and "rule_sites" (L')."""
-    paths = _paths(fasta)
-    if len(paths) < 1 or len(paths) > 2:
-        raise RuntimeError("Invalid number of fasta files!")      # src/pairsnp.hpp:340-343
-    for p in paths:
-        if not os.path.exists(p):
-            # the reference passes a NULL gzFile on (src/pairsnp.hpp:75-76); we diagnose instead
-            raise FileNotFoundError(os.fsdecode(p))
-    L = _lib.require_gpu()
-    arr = (C.c_char_p * len(paths))(*paths)
-    h = C.c_void_p()
-    rules, alive = _rules(sites, max_sample_n_share, max_n_share, min_sites)
-    if rules is not None:
-        _lib.check(L.tracs_pairsnp_rules(arr, len(paths), int(n_threads), int(dist), int(bool(filter)), C.byref(rules), C.byref(h)))
-        _source_info(L, h, "pairsnp", info)
-    elif sites is None:
-        _lib.check(L.tracs_pairsnp(arr, len(paths), int(n_threads), int(dist), int(bool(filter)), C.byref(h)))
-    else:
-        alive, kp, keep_len, max_n = _site_args(sites)
-        _lib.check(L.tracs_pairsnp_sites(arr, len(paths), int(n_threads), int(dist), int(bool(filter)), kp, keep_len, max_n, C.byref(h)))
-    if info is not None:
-        info["seqlen"] = int(L.tracs_pairsnp_seqlen(h))
-    return _result_arrays(L, h)
+    return _result_arrays(*run_arrays("tracs_pairsnp_rules", input_paths(fasta), None, n_threads, dist, filter, sites, info,
+                                      max_sample_n_share, max_n_share, min_sites))
 
 
 def nearest_arrays(fasta, k, n_threads=1, dist=2147483647, filter=False, sites=None, info=None, max_sample_n_share=None, max_n_share=None,
@@ -103,30 +34,12 @@ def nearest_arrays(fasta, k, n_threads=1, dist=2147483647, filter=False, sites=N
     with d <= dist are eligible.  filter: the filtered distances of the emitted pairs (the ranking uses the raw distance).
     n_threads is accepted for parity with pairsnp_arrays and unused: every stage runs on the GPU.  sites, max_sample_n_share,
     max_n_share, min_sites, info: as pairsnp_arrays (the k nearest among the eligible pairs of the surviving samples)."""
-    paths = _paths(fasta)
-    if len(paths) < 1 or len(paths) > 2:
-        raise RuntimeError("Invalid number of fasta files!")
+    paths = input_paths(fasta, existing=False)
     k = int(k)
     if k < 1 or k > 1024:
         raise ValueError("nearest_arrays(): k must be in [1, 1024], got %d" % k)
-    for p in paths:
-        if not os.path.exists(p):
-            raise FileNotFoundError(os.fsdecode(p))
-    L = _lib.require_gpu()
-    arr = (C.c_char_p * len(paths))(*paths)
-    h = C.c_void_p()
-    rules, alive = _rules(sites, max_sample_n_share, max_n_share, min_sites)
-    if rules is not None:
-        _lib.check(L.tracs_nearest_rules(arr, len(paths), int(n_threads), k, int(dist), int(bool(filter)), C.byref(rules), C.byref(h)))
-        _source_info(L, h, "pairsnp", info)
-    elif sites is None:
-        _lib.check(L.tracs_nearest(arr, len(paths), int(n_threads), k, int(dist), int(bool(filter)), C.byref(h)))
-    else:
-        alive, kp, keep_len, max_n = _site_args(sites)
-        _lib.check(L.tracs_nearest_sites(arr, len(paths), int(n_threads), k, int(dist), int(bool(filter)), kp, keep_len, max_n, C.byref(h)))
-    if info is not None:
-        info["seqlen"] = int(L.tracs_pairsnp_seqlen(h))
-    return _result_arrays(L, h)
+    return _result_arrays(*run_arrays("tracs_nearest_rules", require_files(paths), k, n_threads, dist, filter, sites, info,
+                                      max_sample_n_share, max_n_share, min_sites))
 
 
 def group_labels(names, groups):
@@ -171,29 +84,9 @@ def distance_histogram(fasta, dist=2147483647, filter=False, groups=None, sites=
     distances of the same pairs.  sites, max_sample_n_share, max_n_share, min_sites, info: as pairsnp_arrays (names are the
     surviving samples, only eligible pairs are counted)."""
     import tempfile
-    paths = _paths(fasta)
-    if len(paths) < 1 or len(paths) > 2:
-        raise RuntimeError("Invalid number of fasta files!")
-    for p in paths:
-        if not os.path.exists(p):
-            raise FileNotFoundError(os.fsdecode(p))
-    L = _lib.require_gpu()
-    arr = (C.c_char_p * len(paths))(*paths)
-    h = C.c_void_p()
-    rules, alive = _rules(sites, max_sample_n_share, max_n_share, min_sites)
-    if rules is not None:
-        _lib.check(L.tracs_distance_open_rules(arr, len(paths), C.byref(rules), C.byref(h)))
-    elif sites is None:
-        _lib.check(L.tracs_distance_open(arr, len(paths), C.byref(h)))
-    else:
-        alive, kp, keep_len, max_n = _site_args(sites)
-        _lib.check(L.tracs_distance_open_sites(arr, len(paths), kp, keep_len, max_n, C.byref(h)))
-    try:
-        if rules is not None:
-            _source_info(L, h, "distance", info)
-        if info is not None:
-            info["seqlen"] = int(L.tracs_distance_len(h))
-        names = [L.tracs_distance_name(h, i).decode("utf-8", "replace") for i in range(L.tracs_distance_nseq(h))]
+    with DistanceHandle(fasta, sites, max_sample_n_share, max_n_share, min_sites) as h:
+        _handle_info(h, info, max_sample_n_share is not None or max_n_share is not None or min_sites is not None)
+        names = h.names
         labels = group_labels(names, groups)
         gp = labels.ctypes.data_as(C.POINTER(C.c_int32)) if labels is not None and len(labels) else None
         fd, tmp = tempfile.mkstemp(suffix=".csv")
@@ -202,13 +95,11 @@ def distance_histogram(fasta, dist=2147483647, filter=False, groups=None, sites=
             with open(tmp, "w") as fh:
                 fh.write("header\n")
             eligible, written = C.c_uint64(0), C.c_uint64(0)
-            _lib.check(L.tracs_distance_histogram(h, int(dist), int(bool(filter)), gp, os.fsencode(tmp), b"x", C.byref(eligible),
-                                                  C.byref(written)))
+            _lib.check(h.L.tracs_distance_histogram(h.h, int(dist), int(bool(filter)), gp, os.fsencode(tmp), b"x", C.byref(eligible),
+                                                    C.byref(written)))
             rows = read_histogram_rows(tmp)
         finally:
             os.unlink(tmp)
-    finally:
-        L.tracs_distance_free(h)
     empty = (np.zeros(0, np.uint32),) + tuple(np.zeros(0, np.uint64) for _ in range(3))
     out = {}
     for col in ("snp", "filter") if filter else ("snp",):
@@ -225,34 +116,11 @@ def pair_sites(fasta, pairs, filter=False, sites=None, info=None, max_sample_n_s
     an index into names (the surviving samples).  sites, max_sample_n_share, max_n_share, info: as pairsnp_arrays."""
     import torch
     from . import device as dev
-    from .sites import bitmap_to_bool
-    paths = _paths(fasta)
-    if len(paths) < 1 or len(paths) > 2:
-        raise RuntimeError("Invalid number of fasta files!")
-    for p in paths:
-        if not os.path.exists(p):
-            raise FileNotFoundError(os.fsdecode(p))
-    L = _lib.require_gpu()
-    arr = (C.c_char_p * len(paths))(*paths)
-    h = C.c_void_p()
-    rules, alive = _rules(sites, max_sample_n_share, max_n_share, None)
-    if rules is not None:
-        _lib.check(L.tracs_distance_open_rules(arr, len(paths), C.byref(rules), C.byref(h)))
-    elif sites is None:
-        _lib.check(L.tracs_distance_open(arr, len(paths), C.byref(h)))
-    else:
-        alive, kp, keep_len, max_n = _site_args(sites)
-        _lib.check(L.tracs_distance_open_sites(arr, len(paths), kp, keep_len, max_n, C.byref(h)))
-    try:
-        if rules is not None:
-            _source_info(L, h, "distance", info)
-        names = [L.tracs_distance_name(h, i).decode("utf-8", "replace") for i in range(L.tracs_distance_nseq(h))]
+    with DistanceHandle(fasta, sites, max_sample_n_share, max_n_share) as h:
+        _handle_info(h, info, max_sample_n_share is not None or max_n_share is not None)
+        names = h.names
         if info is not None:
-            info["seqlen"] = int(L.tracs_distance_len(h))
-            src_len = L.tracs_distance_source_len(h)
-            kept = np.zeros((src_len + 63) // 64, np.uint64)
-            _lib.check(L.tracs_distance_kept_sites(h, kept.ctypes.data_as(C.POINTER(C.c_uint64))))
-            info["positions"] = np.flatnonzero(bitmap_to_bool(kept, src_len))
+            info["positions"] = h.kept_positions()
         index = {}
         for i, name in enumerate(names):
             index[name] = -1 if name in index else i
@@ -268,14 +136,20 @@ def pair_sites(fasta, pairs, filter=False, sites=None, info=None, max_sample_n_s
                 raise ValueError("pair_sites(): sample index %d is outside [0, %d)" % (int(x), len(names)))
             return int(x)
         idx = np.array([(resolve(a), resolve(b)) for a, b in pairs], np.int32).reshape(-1, 2)
-        aln = dev.Alignment.borrowed(L, L.tracs_distance_alignment(h))      # the handle's alignment: freed with the handle below
+        aln = h.alignment()                                                 # the handle's alignment: freed with the handle below
         got = dev.pair_sites(aln, torch.from_numpy(np.ascontiguousarray(idx[:, 0])).cuda(),
                              torch.from_numpy(np.ascontiguousarray(idx[:, 1])).cuda(), filter=filter)
         off, site, bits = (t.cpu().numpy() for t in got)
         aln.close()
-    finally:
-        L.tracs_distance_free(h)
     return off, site.view(np.uint32), bits.view(np.uint32), names
+
+
+def _handle_info(h, info, ruled):
+    """info (a dict or None) <- what the sample rule saw (with one of the rule keywords), then "seqlen" (the kept columns)"""
+    if info is not None:
+        if ruled:
+            info.update(h.source())
+        info["seqlen"] = int(h.length)
 
 
 def _result_arrays(L, h):

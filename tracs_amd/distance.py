@@ -11,9 +11,11 @@ import logging
 import math
 import os
 import sys
+import time
 from datetime import date
 
 from . import _lib
+from .handle import OPEN_STAGE, DistanceHandle, require_files
 from .utils import check_nearest_k, check_positive_float, check_positive_int
 
 
@@ -33,11 +35,9 @@ def calculate_trans_prob(*args, **kwargs):
     from .transcluster import calculate_trans_prob as f
     return f(*args, **kwargs)
 
-# --mst WEIGHT -> tracs_distance_forest's weight (the columns `cluster -D` reads: snp 3, filter 6, direct 4, expectedK 5)
-MST_WEIGHTS = {"snp": 0, "filter": 1, "direct": 2, "expectedK": 3}
-
-# --ancestors WEIGHT -> tracs_distance_ancestors's weight: the same columns; direct (a probability) is read DESCENDING there
-ANCESTOR_WEIGHTS = {"snp": 0, "filter": 1, "direct": 2, "expectedK": 3}
+# --mst / --ancestors WEIGHT -> the weight of tracs_distance_forest and tracs_distance_ancestors (the columns `cluster -D` reads: snp 3,
+# filter 6, direct 4, expectedK 5); direct (a probability) is read DESCENDING by --ancestors
+WEIGHTS = {"snp": 0, "filter": 1, "direct": 2, "expectedK": 3}
 
 ANCESTORS_HEADER = "sample,date,ancestor,ancestor date,root,generation,MSA file\n"
 
@@ -91,13 +91,13 @@ def distance_parser(parser):
     snp.add_argument("--nearest", dest="nearest", type=check_nearest_k, default=None, metavar="K",
                      help="Only output each sample's K nearest samples (by SNP distance, then input order; 1 <= K <= 1024). "
                           "With --msa-db: the K nearest database samples of each query sample.  Not in the reference.")
-    snp.add_argument("--mst", dest="mst", choices=list(MST_WEIGHTS), default=None, metavar="WEIGHT",
+    snp.add_argument("--mst", dest="mst", choices=list(WEIGHTS), default=None, metavar="WEIGHT",
                      help="Only output the minimum spanning forest of the pairs the run would write, under the column that "
                           "`cluster -D WEIGHT` reads (snp | filter | direct | expectedK; filter needs --filter, direct and expectedK "
                           "need --meta): at most n - 1 rows, each identical to its row in the full output.  For every threshold T, "
                           "`cluster -c T -D WEIGHT` on this file puts the same samples into the same clusters as on the full file "
                           "(cluster numbers may be permuted).  With --meta every sample needs a date.  Not in the reference.")
-    snp.add_argument("--ancestors", dest="ancestors", choices=list(ANCESTOR_WEIGHTS), default=None, metavar="WEIGHT",
+    snp.add_argument("--ancestors", dest="ancestors", choices=list(WEIGHTS), default=None, metavar="WEIGHT",
                      help="Only output, for each sample, the pair that links it to its most likely earlier source (SeqTrack-style; "
                           "needs --meta): among the pairs the run would write, the candidates of a sample are its partners with a "
                           "strictly earlier sampling date, and the source is the best of them under (WEIGHT, date gap, input order).  "
@@ -215,16 +215,17 @@ class _MissingDate(KeyError):
     """a compared sample that --meta does not list (the full-output route then leaves the alignment to the array route)"""
 
 
-def _names_of(L, h):
-    return [L.tracs_distance_name(h, i).decode("utf-8", "replace") for i in range(L.tracs_distance_nseq(h))]
+def ref_of(msa):
+    """the `MSA file` column of an alignment's rows (:208-209)"""
+    return os.path.basename(msa).split(".")[0].replace("_combined", "")
 
 
-def _days_of(L, h, dates, option, metadata=None):
+def _days_of(h, dates, option, metadata=None):
     """The day numbers of the handle's samples, in order, as the c_int32 array the library takes.  A sample without a date:
     SystemExit naming `option` and the metadata file, or -- option None, the full-output route -- _MissingDate."""
     epoch = date(1970, 1, 1)
     got = []
-    for name in _names_of(L, h):
+    for name in h.names:
         if name not in dates:
             if option is None:
                 raise _MissingDate(name)
@@ -235,123 +236,138 @@ def _days_of(L, h, dates, option, metadata=None):
 
 @contextlib.contextmanager
 def _opened(msas, args, stage, rule=None, contigs=None):
-    """One alignment's handle for the body of a device-resident route: opened with the rule (tracs_distance_open*), its [sum] stage
-    line, -> (library, handle); after the body --msa-out / --site-table from the same handle; freed whatever happens (a body that
-    raises skips those outputs)."""
-    L = _lib.require_gpu()
-    h = _open(L, msas, rule, args)
-    try:
-        stage("[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)")
-        yield L, h
-        write_msa_outputs(L, h, args, msas[0], contigs)
-    finally:
-        L.tracs_distance_free(h)
+    """One alignment's handle for the body of a device-resident route: opened with the rule, its [sum] stage line; after the body
+    --msa-out / --site-table from the same handle; freed whatever happens (a body that raises skips those outputs)."""
+    with _open(msas, rule, args) as h:
+        stage(OPEN_STAGE)
+        yield h
+        write_msa_outputs(h, args, msas[0], contigs)
+
+
+def _model_args(h, dates, args, msa, option):
+    """What the transmission model of a device route takes from (handle, dates, args): (day numbers, clock rate, transmission rate,
+    precision, kmax), with the "Inferring ..." line; without dates: no day numbers, no line, no -K"""
+    days, kmax = None, -1.0
+    if dates is not None:
+        days = _days_of(h, dates, option, args.metadata)
+        logging.info("Inferring transmission probabilities for %s", msa)
+        kmax = -1.0 if args.trans_threshold is None else float(args.trans_threshold)
+    return days, float(args.clock_rate), float(args.trans_rate), float(args.precision), kmax
+
+
+def _counted(call, h, *head):
+    """One tracs_distance_<route> call: the handle, head, then the two counters the library fills -> their values"""
+    a, b = C.c_uint64(0), C.c_uint64(0)
+    _lib.check(call(h.h, *head, C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def _rows_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
-    """One alignment through libtracs_hip.so's device-resident path (tracs_distance_open / _run: include/tracs_hip.h): FASTA -> packed
+    """One alignment through libtracs_hip.so's device-resident path (handle.DistanceHandle, tracs_distance_run: include/tracs_hip.h): FASTA -> packed
     planes -> dense panels -> transcluster on the panels -> the pairs within the threshold with their P and E(K) -> ONE device-to-host
     pass, in batches -> the CSV rows, formatted and appended by the library's host threads.  Nothing comes back to Python but the
     sample names (to look the dates up).  -> False when the path does not apply: a sample without a date (the reference raises KeyError
     only if that sample's index is at most the largest index among the emitted pairs, tracs/transcluster.py:23-32: left to the
     array path below, which reproduces that)."""
     try:
-        with _opened(msas, args, stage, rule, contigs) as (L, h):
-            days = _days_of(L, h, dates, None) if dates is not None else None
-            written, pairs = C.c_uint64(0), C.c_uint64(0)
-            if dates is not None:
-                logging.info("Inferring transmission probabilities for %s", msas[0])
-            kmax = -1.0 if (args.trans_threshold is None or dates is None) else float(args.trans_threshold)
-            _lib.check(L.tracs_distance_run(h, int(args.snp_threshold), days, float(args.clock_rate), float(args.trans_rate), float(args.precision),
-                                            kmax, os.fsencode(args.output_file), ref.encode(), int(bool(args.recomb_filter)), C.byref(written),
-                                            C.byref(pairs)))
-            stage("[sum] tracs_distance_run (dense panels, transcluster, rows: %d pairs, %d rows written)" % (pairs.value, written.value))
+        with _opened(msas, args, stage, rule, contigs) as h:
+            model = _model_args(h, dates, args, msas[0], None)
+            written, pairs = _counted(h.L.tracs_distance_run, h, int(args.snp_threshold), *model, os.fsencode(args.output_file), ref.encode(),
+                                      int(bool(args.recomb_filter)))
+            stage("[sum] tracs_distance_run (dense panels, transcluster, rows: %d pairs, %d rows written)" % (pairs, written))
     except _MissingDate:
         return False
     return True
 
 
 def _forest_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
-    """--mst WEIGHT for one alignment (tracs_distance_open / _forest: include/tracs_hip.h): the panel walk of _rows_on_device up to the
+    """--mst WEIGHT for one alignment (handle.DistanceHandle, tracs_distance_forest: include/tracs_hip.h): the panel walk of _rows_on_device up to the
     pairs within the threshold with their P and E(K), then the minimum spanning forest of the eligible pairs on the device; only its
     rows are formatted and appended.  With metadata every sample needs a date (the full run's array route has KeyError rules of its
     own instead)."""
-    with _opened(msas, args, stage, rule, contigs) as (L, h):
-        days = None
-        if dates is not None:
-            days = _days_of(L, h, dates, "--mst", args.metadata)
-            logging.info("Inferring transmission probabilities for %s", msas[0])
-        written, eligible = C.c_uint64(0), C.c_uint64(0)
-        kmax = -1.0 if (args.trans_threshold is None or dates is None) else float(args.trans_threshold)
-        _lib.check(L.tracs_distance_forest(h, int(args.snp_threshold), days, float(args.clock_rate), float(args.trans_rate),
-                                           float(args.precision), kmax, int(bool(args.recomb_filter)), MST_WEIGHTS[args.mst],
-                                           os.fsencode(args.output_file), ref.encode(), C.byref(written), C.byref(eligible)))
-        stage("[sum] tracs_distance_forest (dense panels, transcluster, forest: %d eligible pairs, %d rows written)"
-              % (eligible.value, written.value))
+    with _opened(msas, args, stage, rule, contigs) as h:
+        model = _model_args(h, dates, args, msas[0], "--mst")
+        written, eligible = _counted(h.L.tracs_distance_forest, h, int(args.snp_threshold), *model, int(bool(args.recomb_filter)),
+                                     WEIGHTS[args.mst], os.fsencode(args.output_file), ref.encode())
+        stage("[sum] tracs_distance_forest (dense panels, transcluster, forest: %d eligible pairs, %d rows written)" % (eligible, written))
 
 
 def _ancestors_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
-    """--ancestors WEIGHT for one alignment (tracs_distance_open / _ancestors: include/tracs_hip.h): the panel walk of
+    """--ancestors WEIGHT for one alignment (handle.DistanceHandle, tracs_distance_ancestors: include/tracs_hip.h): the panel walk of
     _forest_on_device with, instead of the forest, each later-dated sample's best earlier partner kept on the device; only the chosen
     pairs' rows are formatted and appended, and --ancestors-out gets one line per compared sample.  Every compared sample needs a
     date (checked on the opened handle: samples the sample rule left out need none)."""
-    with _opened(msas, args, stage, rule, contigs) as (L, h):
-        days = _days_of(L, h, dates, "--ancestors", args.metadata)
-        tree = getattr(args, "ancestors_out", None)
-        meta_dates = None
+    with _opened(msas, args, stage, rule, contigs) as h:
+        model = _model_args(h, dates, args, msas[0], "--ancestors")
+        tree, meta_dates = args.ancestors_out, None
         if tree is not None:
-            text = [dates[name][0].encode() for name in _names_of(L, h)]
+            text = [dates[name][0].encode() for name in h.names]
             meta_dates = (C.c_char_p * max(len(text), 1))(*text)
-        logging.info("Inferring transmission probabilities for %s", msas[0])
-        written, eligible = C.c_uint64(0), C.c_uint64(0)
-        kmax = -1.0 if args.trans_threshold is None else float(args.trans_threshold)
-        _lib.check(L.tracs_distance_ancestors(h, int(args.snp_threshold), days, float(args.clock_rate), float(args.trans_rate),
-                                              float(args.precision), kmax, int(bool(args.recomb_filter)), ANCESTOR_WEIGHTS[args.ancestors],
-                                              os.fsencode(args.output_file), ref.encode(), os.fsencode(tree) if tree is not None else None,
-                                              meta_dates, C.byref(written), C.byref(eligible)))
-        stage("[sum] tracs_distance_ancestors (dense panels, transcluster, ancestors: %d candidates, %d rows written)"
-              % (eligible.value, written.value))
+        written, eligible = _counted(h.L.tracs_distance_ancestors, h, int(args.snp_threshold), *model, int(bool(args.recomb_filter)),
+                                     WEIGHTS[args.ancestors], os.fsencode(args.output_file), ref.encode(),
+                                     os.fsencode(tree) if tree is not None else None, meta_dates)
+        stage("[sum] tracs_distance_ancestors (dense panels, transcluster, ancestors: %d candidates, %d rows written)" % (eligible, written))
+
+
+def check_output_paths(command, inputs, outputs, own):
+    """The path collisions of a run, for its outputs `own` (options of `outputs`).  inputs, outputs: {option: path, list of paths or
+    None}.  Refused (SystemExit): an own output that is one of the input files; an own output that names the file of another output
+    (a single own option is named in the message)."""
+    def real(values):
+        return [os.path.realpath(p) for v in values for p in (v if isinstance(v, (list, tuple)) else [v]) if p is not None]
+    ins, outs = set(real(inputs.values())), real(outputs.values())
+    for opt in own:
+        if outputs[opt] is not None and os.path.realpath(outputs[opt]) in ins:
+            raise SystemExit("tracs %s: %s %s is one of the run's input files" % (command, opt, outputs[opt]))
+    if len(own) == 1:
+        if outputs[own[0]] is not None and outs.count(os.path.realpath(outputs[own[0]])) > 1:
+            raise SystemExit("tracs %s: %s %s is also another output of the run" % (command, own[0], outputs[own[0]]))
+    elif len(set(outs)) != len(outs):
+        raise SystemExit("tracs %s: two outputs of the run name the same file" % command)
+
+
+def _inputs(args):
+    return {"--msa": args.msa_files, "--meta": args.metadata, "--mask": args.mask_bed, "--keep": args.keep_bed,
+            "--mask-reference": args.mask_reference}
+
+
+def _outputs(args):
+    return {"-o": args.output_file, "--sites-out": args.sites_out, "--samples-out": args.samples_out, "--msa-out": args.msa_out,
+            "--site-table": args.site_table}
 
 
 def check_ancestors_args(args):
     """--ancestors' and --ancestors-out's argument checks, before anything touches the GPU (SystemExit with the message)."""
-    anc, out = getattr(args, "ancestors", None), getattr(args, "ancestors_out", None)
+    anc, out = args.ancestors, args.ancestors_out
     if anc is None:
         if out is not None:
             raise SystemExit("tracs distance: --ancestors-out needs --ancestors (it lists the trees that --ancestors builds)")
         return
-    if getattr(args, "mst", None) is not None:
+    if args.mst is not None:
         raise SystemExit("tracs distance: --ancestors and --mst cannot be combined")
-    if getattr(args, "nearest", None) is not None:
+    if args.nearest is not None:
         raise SystemExit("tracs distance: --ancestors and --nearest cannot be combined")
-    if getattr(args, "histogram", False):
+    if args.histogram:
         raise SystemExit("tracs distance: --ancestors and --histogram cannot be combined")
-    if getattr(args, "msa_db", None) is not None:
+    if args.msa_db is not None:
         raise SystemExit("tracs distance: --ancestors links the samples of one alignment and takes no --msa-db")
-    if getattr(args, "gpus", 1) > 1:
+    if args.gpus > 1:
         raise SystemExit("tracs distance: --ancestors runs on one GPU; use --gpus 1")
     if args.metadata is None:
         raise SystemExit("tracs distance: --ancestors %s needs --meta (the sampling dates that order the samples)" % anc)
     if anc == "filter" and not args.recomb_filter:
         raise SystemExit("tracs distance: --ancestors filter needs --filter (the filtered SNP distance column)")
-    if out is not None:
-        inputs = list(getattr(args, "msa_files", None) or [])
-        inputs += [getattr(args, k, None) for k in ("metadata", "mask_bed", "keep_bed", "mask_reference")]
-        if os.path.realpath(out) in {os.path.realpath(p) for p in inputs if p is not None}:
-            raise SystemExit("tracs distance: --ancestors-out %s is one of the run's input files" % out)
-        others = [getattr(args, k, None) for k in ("output_file", "sites_out", "samples_out", "msa_out", "site_table")]
-        if os.path.realpath(out) in {os.path.realpath(p) for p in others if p is not None}:
-            raise SystemExit("tracs distance: --ancestors-out %s is also another output of the run" % out)
+    check_output_paths("distance", _inputs(args), dict(_outputs(args), **{"--ancestors-out": out}), ["--ancestors-out"])
 
 
 def check_mst_args(args):
     """--mst's argument checks, before anything touches the GPU (SystemExit with the message)."""
-    mst = getattr(args, "mst", None)
+    mst = args.mst
     if mst is None:
         return
-    if getattr(args, "nearest", None) is not None:
+    if args.nearest is not None:
         raise SystemExit("tracs distance: --mst and --nearest cannot be combined")
-    if getattr(args, "gpus", 1) > 1:
+    if args.gpus > 1:
         raise SystemExit("tracs distance: --mst runs on one GPU; use --gpus 1")
     if mst == "filter" and not args.recomb_filter:
         raise SystemExit("tracs distance: --mst filter needs --filter (the filtered SNP distance column)")
@@ -359,108 +375,91 @@ def check_mst_args(args):
         raise SystemExit("tracs distance: --mst %s needs --meta (the sampling dates that transmission distances come from)" % mst)
 
 
-def check_site_args(args):
-    """The site rules' argument checks, before anything touches the GPU (SystemExit with the message)."""
-    mask, keep = getattr(args, "mask_bed", None), getattr(args, "keep_bed", None)
-    share, ref, out = getattr(args, "max_n_share", None), getattr(args, "mask_reference", None), getattr(args, "sites_out", None)
+def check_site_args(args, command="distance"):
+    """The site rules' argument checks, before anything touches the GPU (SystemExit with the message, under the command's name)."""
+    mask, keep, share, ref, out = args.mask_bed, args.keep_bed, args.max_n_share, args.mask_reference, args.sites_out
     if share is not None and not (0.0 <= share < 1.0):            # (a NaN fails too)
-        raise SystemExit("tracs distance: --max-n-share must be in [0, 1), got %r" % share)
+        raise SystemExit("tracs %s: --max-n-share must be in [0, 1), got %r" % (command, share))
     if ref is not None and mask is None and keep is None:
-        raise SystemExit("tracs distance: --mask-reference needs --mask or --keep (it only gives their contigs an offset)")
+        raise SystemExit("tracs %s: --mask-reference needs --mask or --keep (it only gives their contigs an offset)" % command)
     rule = mask is not None or keep is not None or share is not None
     if out is not None and not rule:
-        raise SystemExit("tracs distance: --sites-out needs a site rule (--mask, --keep or --max-n-share)")
+        raise SystemExit("tracs %s: --sites-out needs a site rule (--mask, --keep or --max-n-share)" % command)
     if not rule:
         return
-    if getattr(args, "gpus", 1) > 1:
-        raise SystemExit("tracs distance: site rules (--mask, --keep, --max-n-share) run on one GPU; use --gpus 1")
-    if out is not None and len(getattr(args, "msa_files", None) or []) > 1:
-        raise SystemExit("tracs distance: --sites-out describes one alignment; give one --msa file")
-    if out is not None and share is not None and getattr(args, "nearest", None) is not None:
-        raise SystemExit("tracs distance: --sites-out with --nearest takes file rules only (--mask, --keep), not --max-n-share")
+    if args.gpus > 1:
+        raise SystemExit("tracs %s: site rules (--mask, --keep, --max-n-share) run on one GPU; use --gpus 1" % command)
+    if out is not None and len(args.msa_files) > 1:
+        raise SystemExit("tracs %s: --sites-out describes one alignment; give one --msa file" % command)
+    if out is not None and share is not None and args.nearest is not None:
+        raise SystemExit("tracs %s: --sites-out with --nearest takes file rules only (--mask, --keep), not --max-n-share" % command)
 
 
 def check_msa_out_args(args):
     """--msa-out / --msa-out-sites / --site-table: argument checks, before anything touches the GPU (SystemExit with the message)."""
-    out, which, table = getattr(args, "msa_out", None), getattr(args, "msa_out_sites", None), getattr(args, "site_table", None)
+    out, which, table = args.msa_out, args.msa_out_sites, args.site_table
     if which is not None and out is None:
         raise SystemExit("tracs distance: --msa-out-sites needs --msa-out (it chooses the columns of that file)")
     if out is None and table is None:
         return
-    if getattr(args, "msa_db", None) is not None:
+    if args.msa_db is not None:
         raise SystemExit("tracs distance: --msa-out and --site-table describe one alignment and take no --msa-db")
-    if len(getattr(args, "msa_files", None) or []) > 1:
+    if len(args.msa_files) > 1:
         raise SystemExit("tracs distance: --msa-out and --site-table describe one alignment; give one --msa file")
-    if getattr(args, "gpus", 1) > 1:
+    if args.gpus > 1:
         raise SystemExit("tracs distance: --msa-out and --site-table run on one GPU; use --gpus 1")
-    inputs = list(getattr(args, "msa_files", None) or [])
-    inputs += [getattr(args, k, None) for k in ("metadata", "mask_bed", "keep_bed", "mask_reference", "groups")]
-    inputs = {os.path.realpath(p) for p in inputs if p is not None}
-    for opt, path in (("--msa-out", out), ("--site-table", table)):
-        if path is not None and os.path.realpath(path) in inputs:
-            raise SystemExit("tracs distance: %s %s is one of the run's input files" % (opt, path))
-    outs = [os.path.realpath(p) for p in (out, table, getattr(args, "output_file", None), getattr(args, "sites_out", None),
-                                          getattr(args, "samples_out", None)) if p is not None]
-    if len(set(outs)) != len(outs):
-        raise SystemExit("tracs distance: two outputs of the run name the same file")
+    check_output_paths("distance", dict(_inputs(args), **{"--groups": args.groups}), _outputs(args), ["--msa-out", "--site-table"])
 
 
-def write_msa_outputs(L, h, args, msa, contigs):
+def write_msa_outputs(h, args, msa, contigs):
     """--msa-out and --site-table for what the handle compares (the surviving samples, the kept columns): the census and the unpack
     run on the GPU (tracs_distance_site_census / _write_alignment), one INFO line per file.  The handle is left as it was."""
-    out, table = getattr(args, "msa_out", None), getattr(args, "site_table", None)
+    out, table = args.msa_out, args.site_table
     if out is None and table is None:
         return
     import numpy as np
     from . import sites as S
-    n, length = L.tracs_distance_nseq(h), L.tracs_distance_len(h)
-    u64p = C.POINTER(C.c_uint64)
+    L, n, length = h.L, h.n, h.length
     counts = np.zeros((6, length), np.uint32) if table is not None else None
     differs = np.zeros((length + 63) // 64, np.uint64)
     n_differs = C.c_size_t(0)
-    _lib.check(L.tracs_distance_site_census(h, counts.ctypes.data if counts is not None else None, differs.ctypes.data_as(u64p),
-                                            C.byref(n_differs)))
+    _lib.check(L.tracs_distance_site_census(h.h, counts.ctypes.data if counts is not None else None,
+                                            differs.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(n_differs)))
     if table is not None:
-        src_len = L.tracs_distance_source_len(h)
-        kept = np.zeros((src_len + 63) // 64, np.uint64)
-        _lib.check(L.tracs_distance_kept_sites(h, kept.ctypes.data_as(u64p)))
-        S.write_site_table(table, np.flatnonzero(S.bitmap_to_bool(kept, src_len)), counts, S.bitmap_to_bool(differs, length), contigs)
+        S.write_site_table(table, h.kept_positions(), counts, S.bitmap_to_bool(differs, length), contigs)
         logging.info("Site table for %s: %s (%d samples, %d columns, %d differing)", msa, table, n, length, n_differs.value)
     if out is not None:
         written = C.c_size_t(0)
-        _lib.check(L.tracs_distance_write_alignment(h, os.fsencode(out), 0, n, int(getattr(args, "msa_out_sites", None) == "differing"),
-                                                    int(args.n_cpu), -1, C.byref(written)))
+        _lib.check(L.tracs_distance_write_alignment(h.h, os.fsencode(out), 0, n, int(args.msa_out_sites == "differing"), int(args.n_cpu), -1,
+                                                    C.byref(written)))
         logging.info("Compared alignment of %s: %s (%d records, %d columns, %d differing)", msa, out, n, written.value, n_differs.value)
 
 
 def _msa_outputs_fresh(msas, args, rule, contigs):
     """write_msa_outputs for the routes without a distance handle: one is opened with the same rules for the write"""
-    if getattr(args, "msa_out", None) is None and getattr(args, "site_table", None) is None:
+    if args.msa_out is None and args.site_table is None:
         return
-    L = _lib.require_gpu()
-    h = _open(L, msas, rule, args)
-    try:
-        write_msa_outputs(L, h, args, msas[0], contigs)
-    finally:
-        L.tracs_distance_free(h)
+    with _open(msas, rule, args) as h:
+        write_msa_outputs(h, args, msas[0], contigs)
 
 
 SAMPLES_HEADER = "sample,MSA file,N sites,sites,kept\n"
 
 
-def check_sample_args(args):
-    """The sample and pair rules' argument checks, before anything touches the GPU (SystemExit with the message)."""
-    share, m, out = getattr(args, "max_sample_n_share", None), getattr(args, "min_sites", None), getattr(args, "samples_out", None)
+def check_sample_args(args, command="distance"):
+    """The sample and pair rules' argument checks, before anything touches the GPU (SystemExit with the message, under the command's
+    name)."""
+    share, m, out = args.max_sample_n_share, args.min_sites, args.samples_out
     if share is not None and not (0.0 <= share <= 1.0):            # (a NaN fails too)
-        raise SystemExit("tracs distance: --max-sample-n-share must be in [0, 1], got %r" % share)
+        raise SystemExit("tracs %s: --max-sample-n-share must be in [0, 1], got %r" % (command, share))
     if m is not None and not (1 <= m <= 0xFFFFFFFF):
-        raise SystemExit("tracs distance: --min-sites must be in [1, 2^32 - 1], got %r" % m)
+        raise SystemExit("tracs %s: --min-sites must be in [1, 2^32 - 1], got %r" % (command, m))
     if out is not None and share is None:
-        raise SystemExit("tracs distance: --samples-out needs --max-sample-n-share (it lists what the sample rule decided)")
-    if out is not None and len(getattr(args, "msa_files", None) or []) > 1:
-        raise SystemExit("tracs distance: --samples-out describes one alignment; give one --msa file")
-    if (share is not None or m is not None) and getattr(args, "gpus", 1) > 1:
-        raise SystemExit("tracs distance: the sample and pair rules (--max-sample-n-share, --min-sites) run on one GPU; use --gpus 1")
+        raise SystemExit("tracs %s: --samples-out needs --max-sample-n-share (it lists what the sample rule decided)" % command)
+    if out is not None and len(args.msa_files) > 1:
+        raise SystemExit("tracs %s: --samples-out describes one alignment; give one --msa file" % command)
+    if (share is not None or m is not None) and args.gpus > 1:
+        raise SystemExit("tracs %s: the sample and pair rules (--max-sample-n-share, --min-sites) run on one GPU; use --gpus 1" % command)
 
 
 def write_samples_out(path, names, ref, n_counts, sites, kept):
@@ -472,9 +471,9 @@ def write_samples_out(path, names, ref, n_counts, sites, kept):
 
 
 class _SiteRule:
-    """The rules of one alignment.  Site rules: the keep bitmap over its columns (None: files give none) and the N threshold (None: no
-    rule).  With the sample rule (sample_share) or the pair rule (min_sites) the N rule travels as its share instead (share), because
-    it counts over the samples that survive, and the route is the library's _rules entry points."""
+    """The rules of one alignment, as the keywords of the library's FASTA entry points.  Site rules: the keep bitmap over its columns
+    (None: files give none) and the N rule, as a threshold max_n (None: none) or -- with the sample rule (sample_share) or the pair rule
+    (min_sites), because it then counts over the samples that survive -- as its share."""
 
     def __init__(self, L, keep, max_n, contigs, share=None, sample_share=None, min_sites=None):
         from .sites import Sites
@@ -483,31 +482,32 @@ class _SiteRule:
         self.sites = Sites(keep, max_n)
         self.reported = False
 
-    def uses_rules(self):
-        return self.sample_share is not None or self.min_sites is not None
-
     def has_site_rule(self):
         return self.keep is not None or self.max_n is not None or self.share is not None
 
+    def rules(self):
+        """what handle.rules_struct (DistanceHandle) takes for this rule"""
+        return dict(sites=self.sites, max_sample_n_share=self.sample_share, max_n_share=self.share, min_sites=self.min_sites)
+
     def api_kwargs(self, info):
-        """what pairsnp_arrays / nearest_arrays take for this rule"""
-        if not self.uses_rules():
+        """what pairsnp_arrays / nearest_arrays take for this rule: the rule keywords only with the sample or the pair rule"""
+        if self.sample_share is None and self.min_sites is None:
             return dict(sites=self.sites, info=info)
-        return dict(sites=self.sites, info=info, max_sample_n_share=self.sample_share, max_n_share=self.share, min_sites=self.min_sites)
+        return dict(self.rules(), info=info)
 
     def report(self, args, msa, kept_words=None, n_kept=None, source=None):
-        """the INFO lines of the alignment, --sites-out and --samples-out, once.  source: (names, N counts, kept flags, L') of the
-        records read, with the sample rule"""
+        """the INFO lines of the alignment, --sites-out and --samples-out, once.  source: what the sample rule saw
+        (handle.source_records), with the sample rule"""
         from . import sites as S
         if self.reported:
             return
         self.reported = True
         if self.sample_share is not None and source is not None:
-            names, n_counts, kept, rule_sites = source
+            names, kept, rule_sites = source["source_names"], source["kept"], source["rule_sites"]
             logging.info("Sample rule for %s: kept %d of %d samples (dropped: N at more than %d of %d columns)", msa, int(sum(bool(k) for k in kept)),
                          len(names), math.floor(self.sample_share * rule_sites), rule_sites)
-            if getattr(args, "samples_out", None) is not None:
-                write_samples_out(args.samples_out, names, os.path.basename(msa).split(".")[0].replace("_combined", ""), n_counts, rule_sites, kept)
+            if args.samples_out is not None:
+                write_samples_out(args.samples_out, names, ref_of(msa), source["n_counts"], rule_sites, kept)
         if not self.has_site_rule():
             return
         by_files = self.L - int(self.keep.sum()) if self.keep is not None else 0
@@ -515,44 +515,43 @@ class _SiteRule:
             n_kept = int(S.bitmap_to_bool(kept_words, self.L).sum())
         logging.info("Site rules for %s: kept %d of %d columns (%d dropped by --mask / --keep, %d by --max-n-share)",
                      msa, n_kept, self.L, by_files, self.L - by_files - n_kept)
-        if getattr(args, "sites_out", None) is not None:
+        if args.sites_out is not None:
             S.write_kept_bed(args.sites_out, kept_words if kept_words is not None else self.keep, self.L, self.contigs)
 
 
-def read_site_files(args):
+def read_site_files(args, command="distance"):
     """--mask / --keep / --mask-reference, read once: (keep intervals or None, mask intervals or None, contigs or None); ValueError ->
     SystemExit with the message"""
     from . import sites as S
     contigs = None
     try:
-        if getattr(args, "mask_reference", None) is not None:
+        if args.mask_reference is not None:
             from .align_post import read_contigs
             contigs = read_contigs(args.mask_reference)
-        keep = S.read_bed(args.keep_bed, contigs) if getattr(args, "keep_bed", None) is not None else None
-        mask = S.read_bed(args.mask_bed, contigs) if getattr(args, "mask_bed", None) is not None else None
+        keep = S.read_bed(args.keep_bed, contigs) if args.keep_bed is not None else None
+        mask = S.read_bed(args.mask_bed, contigs) if args.mask_bed is not None else None
     except ValueError as e:
-        raise SystemExit("tracs distance: %s" % e)
+        raise SystemExit("tracs %s: %s" % (command, e))
     return keep, mask, contigs
 
 
-def site_rule_for(msas, args, files):
+def site_rule_for(msas, args, files, command="distance"):
     """The rule of one alignment (None without any site option).  The bitmap needs the alignment's length and the share the number of
     loaded samples before the library opens the files: the length comes from the first record; the sample count, only with
     --max-n-share, from a host-side read of the files (the library's own FASTA reader)."""
     from . import sites as S
     keep_iv, mask_iv, contigs = files
-    share = getattr(args, "max_n_share", None)
-    sample_share, min_sites = getattr(args, "max_sample_n_share", None), getattr(args, "min_sites", None)
+    share, sample_share, min_sites = args.max_n_share, args.max_sample_n_share, args.min_sites
     if keep_iv is None and mask_iv is None and share is None and sample_share is None and min_sites is None:
         return None
-    _require_files(msas)
+    require_files(msas)
     L = S.first_record_length(msas[0]) if (keep_iv is not None or mask_iv is not None or share is not None) else 0      # (0: no site rule)
     keep = None
     if keep_iv is not None or mask_iv is not None:
         try:
             keep = S.keep_bool(L, keep_iv, mask_iv)
         except ValueError as e:
-            raise SystemExit("tracs distance: %s: %s" % (msas[0], e))
+            raise SystemExit("tracs %s: %s: %s" % (command, msas[0], e))
     max_n = None
     if sample_share is not None or min_sites is not None:
         # the library takes F itself and computes floor(F n') over the samples that survive the sample rule: no host read for n
@@ -568,62 +567,34 @@ def site_rule_for(msas, args, files):
     return _SiteRule(L, keep, max_n, contigs)
 
 
-def _open(L, msas, rule, args):
-    """tracs_distance_open, or -- with a site rule -- tracs_distance_open_sites, its INFO line and --sites-out -> the handle"""
-    arr = (C.c_char_p * len(msas))(*[os.fsencode(p) for p in msas])
-    h = C.c_void_p()
-    if rule is None:
-        _lib.check(L.tracs_distance_open(arr, len(msas), C.byref(h)))
-        return h
-    import numpy as np
-    words, keep_len, max_n = rule.sites.c_args()
-    u64p = C.POINTER(C.c_uint64)
-    kp = words.ctypes.data_as(u64p) if words is not None else None
-    if rule.uses_rules():
-        rules = _lib.Rules(kp, keep_len, -1.0 if rule.share is None else float(rule.share),
-                           -1.0 if rule.sample_share is None else float(rule.sample_share), int(rule.min_sites or 0), 0xFFFFFFFF)
-        _lib.check(L.tracs_distance_open_rules(arr, len(msas), C.byref(rules), C.byref(h)))
-    else:
-        _lib.check(L.tracs_distance_open_sites(arr, len(msas), kp, keep_len, max_n, C.byref(h)))
-    try:
-        src_len = L.tracs_distance_source_len(h)
-        kept = np.zeros((src_len + 63) // 64, np.uint64)
-        _lib.check(L.tracs_distance_kept_sites(h, kept.ctypes.data_as(u64p)))
-        rule.L = src_len
-        source = None
-        if rule.sample_share is not None:
-            ns = L.tracs_distance_source_nseq(h)
-            source = ([L.tracs_distance_source_name(h, i).decode("utf-8", "replace") for i in range(ns)],
-                      [L.tracs_distance_source_n_count(h, i) for i in range(ns)], [L.tracs_distance_source_kept(h, i) for i in range(ns)],
-                      L.tracs_distance_rule_sites(h))
-        rule.report(args, msas[0], kept_words=kept, n_kept=L.tracs_distance_len(h), source=source)
-    except BaseException:
-        L.tracs_distance_free(h)
-        raise
-    return h
+@contextlib.contextmanager
+def _open(msas, rule, args):
+    """The alignment's handle, opened with the rule; with one: its INFO lines, --sites-out and --samples-out before the body"""
+    with DistanceHandle(msas, **(rule.rules() if rule is not None else {})) as h:
+        if rule is not None:
+            rule.L = h.source_len
+            rule.report(args, msas[0], kept_words=h.kept_words(), n_kept=h.length, source=h.source() if rule.sample_share is not None else None)
+        yield h
 
 
 def _report_arrays(rule, args, msa, info):
     """rule.report for the array routes: what pairsnp_arrays / nearest_arrays left in `info`"""
-    source = None
-    if "source_names" in info:
-        source = (info["source_names"], info["n_counts"], info["kept"], info["rule_sites"])
-    rule.report(args, msa, n_kept=info["seqlen"], source=source)
+    rule.report(args, msa, n_kept=info["seqlen"], source=info if "source_names" in info else None)
 
 
 def check_histogram_args(args):
     """--histogram's and --groups' argument checks, before anything touches the GPU (SystemExit with the message)."""
-    if not getattr(args, "histogram", False):
-        if getattr(args, "groups", None) is not None:
+    if not args.histogram:
+        if args.groups is not None:
             raise SystemExit("tracs distance: --groups needs --histogram (the labels only split the histogram's counts)")
         return
-    if getattr(args, "ancestors", None) is not None:
+    if args.ancestors is not None:
         raise SystemExit("tracs distance: --ancestors and --histogram cannot be combined")
-    if getattr(args, "nearest", None) is not None:
+    if args.nearest is not None:
         raise SystemExit("tracs distance: --histogram and --nearest cannot be combined")
-    if getattr(args, "mst", None) is not None:
+    if args.mst is not None:
         raise SystemExit("tracs distance: --histogram and --mst cannot be combined")
-    if getattr(args, "gpus", 1) > 1:
+    if args.gpus > 1:
         raise SystemExit("tracs distance: --histogram runs on one GPU; use --gpus 1")
     if args.metadata is not None:
         raise SystemExit("tracs distance: --histogram counts SNP distances and takes no --meta (no histogram of transmission distances)")
@@ -652,22 +623,21 @@ def read_groups(path):
 
 
 def _histogram_on_device(msas, args, groups, ref, stage, rule=None, contigs=None):
-    """--histogram for one alignment (tracs_distance_open / _histogram: include/tracs_hip.h): the panel walk of _rows_on_device with
+    """--histogram for one alignment (handle.DistanceHandle, tracs_distance_histogram: include/tracs_hip.h): the panel walk of _rows_on_device with
     a histogram update per panel instead of the rows; only the non-empty bins are formatted and appended."""
     from .api import group_labels
-    with _opened(msas, args, stage, rule, contigs) as (L, h):
+    with _opened(msas, args, stage, rule, contigs) as h:
         labels = None
         if groups is not None:
-            names = _names_of(L, h)
+            names = h.names
             n = len(names)
             lab = group_labels(names, groups)
             labels = (C.c_int32 * max(n, 1))(*[int(x) for x in lab])
             logging.info("%d of %d samples of %s have a group label (%d groups)", int((lab >= 0).sum()), n, msas[0],
                          int(lab.max()) + 1 if n else 0)
-        eligible, written = C.c_uint64(0), C.c_uint64(0)
-        _lib.check(L.tracs_distance_histogram(h, int(args.snp_threshold), int(bool(args.recomb_filter)), labels,
-                                              os.fsencode(args.output_file), ref.encode(), C.byref(eligible), C.byref(written)))
-        stage("[sum] tracs_distance_histogram (dense panels, histogram: %d pairs counted, %d rows written)" % (eligible.value, written.value))
+        eligible, written = _counted(h.L.tracs_distance_histogram, h, int(args.snp_threshold), int(bool(args.recomb_filter)), labels,
+                                     os.fsencode(args.output_file), ref.encode())
+        stage("[sum] tracs_distance_histogram (dense panels, histogram: %d pairs counted, %d rows written)" % (eligible, written))
 
 
 def _cli_of(args):
@@ -725,10 +695,35 @@ def _pairs_multi_gpu(msas, args, ctx):
     return host[0], host[1], host[2], names, filt, host[3]
 
 
-def _require_files(msas):
-    for p in msas:
-        if not os.path.exists(p):
-            raise FileNotFoundError(p)
+class _Stages:
+    """The "[stage] name seconds" lines on stderr under TRACS_STAGE_TRACE (scripts/bench_e2e.py reads them): each line the time since
+    the one before it, or since the alignment's start()"""
+
+    def __init__(self, lead):
+        self.on = lead and os.environ.get("TRACS_STAGE_TRACE") is not None
+        self.start()
+        if self.on:
+            try:
+                import psutil
+                sys.stderr.write("[stage] process start -> first alignment (interpreter, imports, metadata) %.4f s\n"
+                                 % (time.time() - psutil.Process().create_time()))
+            except Exception:
+                pass
+
+    def start(self):
+        self.t = time.perf_counter()
+
+    def __call__(self, name):
+        if self.on:
+            now = time.perf_counter()
+            sys.stderr.write("[stage] %s %.4f s\n" % (name, now - self.t))
+            self.t = now
+
+
+# option -> (the route that stays on the device until its rows, its INFO line); distance() looks the route up by name when it dispatches
+DEVICE_ROUTES = {"histogram": ("_histogram_on_device", "Saving the distance histogram for %s"),
+                 "mst": ("_forest_on_device", "Saving the minimum spanning forest for %s"),
+                 "ancestors": ("_ancestors_on_device", "Saving the ancestor links for %s")}
 
 
 def distance(args):
@@ -739,15 +734,12 @@ def distance(args):
     check_sample_args(args)
     check_msa_out_args(args)
     site_files = read_site_files(args)
-    histogram = getattr(args, "histogram", False)
-    groups = read_groups(args.groups) if histogram and args.groups is not None else None
-    mst = getattr(args, "mst", None)
-    ancestors = getattr(args, "ancestors", None)
-    nearest = getattr(args, "nearest", None)
-    if nearest is not None and getattr(args, "gpus", 1) > 1:
+    groups = read_groups(args.groups) if args.histogram and args.groups is not None else None
+    nearest = args.nearest
+    if nearest is not None and args.gpus > 1:
         raise SystemExit("tracs distance: --nearest runs on one GPU; use --gpus 1")
     from . import multigpu
-    if getattr(args, "gpus", 1) > 1 and not multigpu.in_worker():
+    if args.gpus > 1 and not multigpu.in_worker():
         rc = multigpu.spawn("tracs_amd", _cli_of(args), args.gpus)     # before anything here has touched the GPU
         if rc:
             raise SystemExit(rc)
@@ -755,7 +747,6 @@ def distance(args):
     ctx = multigpu.init() if multigpu.in_worker() else None
     if ctx is None:
         # the HIP runtime, the context and the library's kernels come up beside the metadata and the FASTA read (csrc/capi.hip)
-        from . import _lib
         try:
             _lib.load().tracs_warm_up()
         except Exception:                                        # (no library / no GPU: the first real call says so)
@@ -768,73 +759,42 @@ def distance(args):
     logging.info("Estimating transmission distances...")
     if lead:
         with open(args.output_file, "w") as out:
-            out.write(HISTOGRAM_HEADER if histogram else HEADER)
-        if ancestors is not None and getattr(args, "ancestors_out", None) is not None:
+            out.write(HISTOGRAM_HEADER if args.histogram else HEADER)
+        if args.ancestors is not None and args.ancestors_out is not None:
             with open(args.ancestors_out, "w") as out:
                 out.write(ANCESTORS_HEADER)
-    import time
-    trace = os.environ.get("TRACS_STAGE_TRACE") is not None      # "[stage] name seconds" lines on stderr (scripts/bench_e2e.py)
-    t_stage = [time.perf_counter()]
-    if trace and lead:
-        try:
-            import psutil
-            sys.stderr.write("[stage] process start -> first alignment (interpreter, imports, metadata) %.4f s\n"
-                             % (time.time() - psutil.Process().create_time()))
-        except Exception:
-            pass
-
-    def stage(name):
-        if trace and lead:
-            now = time.perf_counter()
-            sys.stderr.write("[stage] %s %.4f s\n" % (name, now - t_stage[0]))
-            t_stage[0] = now
+    stage = _Stages(lead)
+    route = next((r for opt, r in DEVICE_ROUTES.items() if vars(args)[opt]), None)
     for msa in args.msa_files:
         logging.info("Calculating pairwise snp distances for %s", msa)
         msas = [msa, args.msa_db] if args.msa_db is not None else [msa]
-        t_stage[0] = time.perf_counter()
-        ref = os.path.basename(msa).split(".")[0].replace("_combined", "")      # (:208-209)
+        stage.start()
+        ref = ref_of(msa)
         rule = site_rule_for(msas, args, site_files)
         ruled = dict(rule=rule) if rule is not None else {}                 # (no rule: every route is called as it always was)
-        msa_outputs = getattr(args, "msa_out", None) is not None or getattr(args, "site_table", None) is not None
-        if msa_outputs:
+        if args.msa_out is not None or args.site_table is not None:
             ruled["contigs"] = site_files[2]
-        if histogram:
-            # how many of the pairs the full run would write have each SNP distance (one GPU, counted on the device)
-            _require_files(msas)
-            _histogram_on_device(msas, args, groups, ref, stage, **ruled)
-            logging.info("Saving the distance histogram for %s", msa)
-            continue
-        if mst is not None:
-            # the minimum spanning forest of the pairs the full run would write (one GPU, on the device until its rows)
-            _require_files(msas)
-            _forest_on_device(msas, args, dates, ref, stage, **ruled)
-            logging.info("Saving the minimum spanning forest for %s", msa)
-            continue
-        if ancestors is not None:
-            # each sample's most likely earlier source among the pairs the full run would write (one GPU, on the device until its rows)
-            _require_files(msas)
-            _ancestors_on_device(msas, args, dates, ref, stage, **ruled)
-            logging.info("Saving the ancestor links for %s", msa)
+        if route is not None:
+            # one GPU, on the device until its rows: the histogram, the forest or the ancestor links of the pairs the full run would write
+            require_files(msas)
+            globals()[route[0]](msas, args, groups if args.histogram else dates, ref, stage, **ruled)      # (--histogram takes no --meta)
+            logging.info(route[1], msa)
             continue
         if ctx is None and nearest is None and os.environ.get("TRACS_DISTANCE_ARRAYS") is None:
             # one GPU: the results stay on the device until the CSV rows (with --filter: the filtered distances and the transmission
             # model they drive too)
-            _require_files(msas)                             # (api.pairsnp_arrays's diagnosis; the reference passes a NULL gzFile on)
+            require_files(msas)                              # (api.pairsnp_arrays's diagnosis; the reference passes a NULL gzFile on)
             if _rows_on_device(msas, args, dates, ref, stage, **ruled):
                 logging.info("Saving distances for %s", msa)
                 continue
-        if nearest is not None:
-            # each sample's K nearest (tracs_nearest), then the array route below: -K drops rows after the selection
+        if ctx is None:
+            # each sample's K nearest (tracs_nearest), or every pair; then the array route below: -K drops rows after the selection
             info = {}
-            ruled = rule.api_kwargs(info) if rule is not None else {}      # (no rule: the call as it always was)
-            res = nearest_arrays(fasta=msas, k=nearest, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter, **ruled)
-            if rule is not None:
-                _report_arrays(rule, args, msa, info)
-            _msa_outputs_fresh(msas, args, rule, site_files[2])
-        elif ctx is None:
-            info = {}
-            ruled = rule.api_kwargs(info) if rule is not None else {}
-            res = pairsnp_arrays(fasta=msas, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter, **ruled)
+            kw = rule.api_kwargs(info) if rule is not None else {}         # (no rule: the call as it always was)
+            if nearest is not None:
+                res = nearest_arrays(fasta=msas, k=nearest, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter, **kw)
+            else:
+                res = pairsnp_arrays(fasta=msas, n_threads=args.n_cpu, dist=args.snp_threshold, filter=args.recomb_filter, **kw)
             if rule is not None:
                 _report_arrays(rule, args, msa, info)
             _msa_outputs_fresh(msas, args, rule, site_files[2])

@@ -1,0 +1,147 @@
+"""The one place in Python that opens, reads and frees a tracs_distance and that builds a tracs_rules (include/tracs_hip.h).
+
+Python calls the _rules form of every FASTA entry point (tracs_pairsnp_rules, tracs_nearest_rules, tracs_distance_open_rules): a struct
+with no field set is the plain call and one with only keep / max_n_samples the _sites call (rules_from_struct, csrc/capi.hip); the other
+two forms stay in the C ABI.  numpy is imported where it is needed: the plain device route of `tracs distance` runs without it.
+"""
+import ctypes as C
+import os
+
+from . import _lib
+
+
+OPEN_STAGE = "[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)"      # the [stage] line of an open (TRACS_STAGE_TRACE)
+
+
+def input_paths(fasta, existing=True):
+    """The FASTA paths of an entry point, encoded; existing=False leaves the existence check to a later require_files."""
+    if isinstance(fasta, (str, bytes, os.PathLike)):
+        raise TypeError("pairsnp(): fasta must be a list of paths")
+    paths = [os.fsencode(p) for p in fasta]
+    if len(paths) < 1 or len(paths) > 2:
+        raise RuntimeError("Invalid number of fasta files!")      # src/pairsnp.hpp:340-343
+    return require_files(paths) if existing else paths
+
+
+def require_files(paths):
+    for p in paths:
+        if not os.path.exists(p):
+            # the reference passes a NULL gzFile on (src/pairsnp.hpp:75-76); we diagnose instead
+            raise FileNotFoundError(os.fsdecode(p))
+    return paths
+
+
+def rules_struct(sites=None, max_sample_n_share=None, max_n_share=None, min_sites=None):
+    """The site rule (tracs_amd.sites.Sites or None), the sample / pair rules and the N share of the FASTA entry points (DESIGN.md 3.12,
+    3.13) -> (_lib.Rules, array to keep alive for the call).  Nothing given: the struct with no field set."""
+    for name, share in (("max_sample_n_share", max_sample_n_share), ("max_n_share", max_n_share)):
+        if share is not None and not (0.0 <= float(share) <= 1.0):
+            raise ValueError("%s must be in [0, 1], got %r" % (name, share))
+    if min_sites is not None and not (1 <= int(min_sites) <= 0xFFFFFFFF):
+        raise ValueError("min_sites must be in [1, 2^32 - 1], got %r" % (min_sites,))
+    if sites is not None and sites.max_n_samples is not None:
+        if max_sample_n_share is not None:
+            raise ValueError("Sites(max_n_samples=...) cannot be combined with max_sample_n_share: the N rule counts over the samples "
+                             "that survive the sample rule, whose number is only known on the device; give max_n_share")
+        if max_n_share is not None:
+            raise ValueError("Sites(max_n_samples=...) and max_n_share are two forms of one rule; give one")
+    words, keep_len, max_n = (None, 0, 0xFFFFFFFF) if sites is None else sites.c_args()
+    r = _lib.Rules(words.ctypes.data_as(C.POINTER(C.c_uint64)) if words is not None else None, keep_len,
+                   -1.0 if max_n_share is None else float(max_n_share), -1.0 if max_sample_n_share is None else float(max_sample_n_share),
+                   0 if min_sites is None else int(min_sites), max_n)
+    return r, words
+
+
+def _names(count, name, h):
+    return [name(h, i).decode("utf-8", "replace") for i in range(count(h))]
+
+
+def source_records(L, kind, h):
+    """What the sample rule saw (tracs_<kind>_source_*): the names of the records read, their N counts among the "rule_sites"
+    file-kept columns, and which stayed -- under the keys of the array entry points' `info`"""
+    import numpy as np
+    get = lambda name: getattr(L, "tracs_%s_%s" % (kind, name))                     # noqa: E731
+    n = get("source_nseq")(h)
+    return {"source_names": _names(get("source_nseq"), get("source_name"), h),
+            "n_counts": np.array([get("source_n_count")(h, i) for i in range(n)], np.uint32),
+            "kept": np.array([get("source_kept")(h, i) != 0 for i in range(n)], bool),
+            "rule_sites": int(get("rule_sites")(h))}
+
+
+class DistanceHandle:
+    """One opened tracs_distance: `with DistanceHandle(fasta, sites=..) as h`.  Freed on every way out of the block, also when a step
+    between the open and the first use raises; close() may be called again."""
+
+    def __init__(self, fasta, sites=None, max_sample_n_share=None, max_n_share=None, min_sites=None):
+        paths = input_paths(fasta)
+        self.h = None
+        self.L = _lib.require_gpu()
+        rules, alive = rules_struct(sites, max_sample_n_share, max_n_share, min_sites)      # (alive: referenced until the call returns)
+        h = C.c_void_p()
+        _lib.check(self.L.tracs_distance_open_rules((C.c_char_p * len(paths))(*paths), len(paths), C.byref(rules), C.byref(h)))
+        self.h = h
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        h, self.h = self.h, None
+        if h is not None:
+            self.L.tracs_distance_free(h)
+
+    @property
+    def names(self):
+        return _names(self.L.tracs_distance_nseq, self.L.tracs_distance_name, self.h)
+
+    @property
+    def n(self):
+        return self.L.tracs_distance_nseq(self.h)
+
+    @property
+    def length(self):
+        """the columns compared (the kept ones)"""
+        return self.L.tracs_distance_len(self.h)
+
+    @property
+    def source_len(self):
+        """the columns of the files read"""
+        return self.L.tracs_distance_source_len(self.h)
+
+    def kept_words(self):
+        """the kept columns as a bitmap over the columns read (uint64 words)"""
+        import numpy as np
+        kept = np.zeros((self.source_len + 63) // 64, np.uint64)
+        _lib.check(self.L.tracs_distance_kept_sites(self.h, kept.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return kept
+
+    def kept_positions(self):
+        """the kept columns as indices into the columns read"""
+        import numpy as np
+        from .sites import bitmap_to_bool
+        return np.flatnonzero(bitmap_to_bool(self.kept_words(), self.source_len))
+
+    def source(self):
+        return source_records(self.L, "distance", self.h)
+
+    def alignment(self):
+        """the handle's packed alignment, borrowed: close it before the handle"""
+        from . import device as dev
+        return dev.Alignment.borrowed(self.L, self.L.tracs_distance_alignment(self.h))
+
+
+def run_arrays(entry, paths, k, n_threads, dist, filter, sites, info, max_sample_n_share, max_n_share, min_sites):
+    """tracs_pairsnp_rules (k None) or tracs_nearest_rules on checked input_paths -> (library, result handle); info (a dict or None)
+    <- "seqlen", and with one of the three rules what the sample rule saw"""
+    L = _lib.require_gpu()
+    rules, alive = rules_struct(sites, max_sample_n_share, max_n_share, min_sites)          # (alive: referenced until the call returns)
+    h = C.c_void_p()
+    head = (int(n_threads),) if k is None else (int(n_threads), k)
+    _lib.check(getattr(L, entry)((C.c_char_p * len(paths))(*paths), len(paths), *head, int(dist), int(bool(filter)), C.byref(rules), C.byref(h)))
+    if info is not None:
+        if not (max_sample_n_share is None and max_n_share is None and min_sites is None):
+            info.update(source_records(L, "pairsnp", h))
+        info["seqlen"] = int(L.tracs_pairsnp_seqlen(h))
+    return L, h

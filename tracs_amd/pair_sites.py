@@ -13,8 +13,9 @@ import logging
 import os
 
 from . import _lib
-from .distance import (_open, add_sample_rule_options, add_site_rule_options, check_sample_args, check_site_args, read_site_files,
-                       site_rule_for)
+from .distance import (_open, add_sample_rule_options, add_site_rule_options, check_output_paths, check_sample_args, check_site_args,
+                       read_site_files, site_rule_for)
+from .handle import require_files
 from .utils import check_positive_int
 
 HEADER = "sampleA,sampleB,contig,position,alleleA,alleleB,dropped\n"
@@ -63,7 +64,8 @@ def pair_sites_parser(parser):
                         help="number of threads that format the rows (default=1; the sites are found on the GPU)")
     parser.add_argument("--loglevel", type=str.upper, default="INFO",
                         choices=["DEBUG", "INFO", "WARNING", "ERROR", "CRITICAL"], help="Set the logging threshold.")
-    parser.set_defaults(func=pair_sites)
+    # what the checks shared with `distance` read and this command has no option for
+    parser.set_defaults(func=pair_sites, sites_out=None, samples_out=None, min_sites=None, gpus=1, nearest=None)
     return parser
 
 
@@ -109,46 +111,29 @@ def resolve_pairs(pairs, names, path, dropped=()):
     return rows, cols
 
 
-def _own_messages(fn, *a):
-    """the helpers shared with `distance` refuse under that command's name: the same refusal under this one's"""
-    try:
-        return fn(*a)
-    except SystemExit as e:
-        text = str(e)
-        if text.startswith("tracs distance:"):
-            raise SystemExit("tracs pair-sites:" + text[len("tracs distance:"):])
-        raise
-
-
 def check_args(args):
     if len(args.msa_files) != 1:
         raise SystemExit("tracs pair-sites: one alignment at a time; give one --msa file")
-    _own_messages(check_site_args, args)
-    _own_messages(check_sample_args, args)
-    inputs = {os.path.realpath(p) for p in (args.msa_files[0], args.msa_db, args.pairs, args.mask_bed, args.keep_bed, args.mask_reference)
-              if p is not None}
-    if os.path.realpath(args.output_file) in inputs:
-        raise SystemExit("tracs pair-sites: -o %s is one of the run's input files" % args.output_file)
+    check_site_args(args, "pair-sites")
+    check_sample_args(args, "pair-sites")
+    check_output_paths("pair-sites", {"--msa": args.msa_files[0], "--msa-db": args.msa_db, "--pairs": args.pairs, "--mask": args.mask_bed,
+                                      "--keep": args.keep_bed, "--mask-reference": args.mask_reference}, {"-o": args.output_file}, ["-o"])
 
 
 def pair_sites(args):
     check_args(args)
-    site_files = _own_messages(read_site_files, args)
+    site_files = read_site_files(args, "pair-sites")
     pairs = read_pairs(args.pairs)                       # (before anything touches the GPU)
     logging.basicConfig(level=args.loglevel, format="%(asctime)s - %(levelname)s - %(message)s", datefmt="%Y-%m-%d %H:%M:%S")
     msas = [args.msa_files[0], args.msa_db] if args.msa_db is not None else [args.msa_files[0]]
-    for p in msas:
-        if not os.path.exists(p):
-            raise FileNotFoundError(p)
-    rule = _own_messages(site_rule_for, msas, args, site_files)
-    L = _lib.require_gpu()
+    require_files(msas)
+    rule = site_rule_for(msas, args, site_files, "pair-sites")
+    _lib.require_gpu()
     logging.info("Reading %s", msas[0])
-    h = _open(L, msas, rule, args)
-    try:
-        names = [L.tracs_distance_name(h, i).decode("utf-8", "replace") for i in range(L.tracs_distance_nseq(h))]
-        dropped = [L.tracs_distance_source_name(h, i).decode("utf-8", "replace") for i in range(L.tracs_distance_source_nseq(h))
-                   if not L.tracs_distance_source_kept(h, i)]
-        rows, cols = resolve_pairs(pairs, names, args.pairs, dropped)
+    with _open(msas, rule, args) as h:
+        source = h.source()
+        dropped = [name for name, kept in zip(source["source_names"], source["kept"]) if not kept]
+        rows, cols = resolve_pairs(pairs, h.names, args.pairs, dropped)
         m = len(rows)
         u32 = C.c_uint32 * max(m, 1)
         contigs = site_files[2]
@@ -158,13 +143,11 @@ def pair_sites(args):
         written = C.c_uint64(0)
         logging.info("Listing the SNP sites of %d pairs", m)
         try:
-            _lib.check(L.tracs_distance_pair_sites(h, u32(*rows), u32(*cols), m, int(bool(args.recomb_filter)), int(args.max_entries),
-                                                   os.fsencode(args.output_file), cnames, clens, nc, int(args.n_cpu), C.byref(written)))
+            _lib.check(h.L.tracs_distance_pair_sites(h.h, u32(*rows), u32(*cols), m, int(bool(args.recomb_filter)), int(args.max_entries),
+                                                     os.fsencode(args.output_file), cnames, clens, nc, int(args.n_cpu), C.byref(written)))
         except RuntimeError as e:
             raise SystemExit("tracs pair-sites: %s" % e)
         logging.info("Saved %d rows to %s", written.value, args.output_file)
-    finally:
-        L.tracs_distance_free(h)
 
 
 def main():
