@@ -360,6 +360,53 @@ int tracs_anc_update_coo(void *state, size_t n, size_t m, const uint32_t *rows, 
 int tracs_anc_emit(void *state, size_t n, size_t *n_links, uint32_t *rows, uint32_t *cols, uint32_t *d, uint32_t *nn, uint32_t *filt,
                    double *p, double *e, uint32_t *parent, uint32_t *root, uint32_t *generation, void *stream);
 
+/* Neighbour joining on the dense distance matrix (csrc/nj.hip; what tracs_distance_tree runs).  Canonical neighbour
+ * joining (Saitou & Nei, Q as Studier & Keppler) in IEEE float64 with every operation and its order fixed and no fused multiply-add, so
+ * that a restatement on the host gives the same bits.  Leaves are the nodes [0, n); join number t makes the node n + t.  With r active
+ * nodes: Q_ab = (r - 2) D_ab - (R_a + R_b); the join is the smallest (Q, lower id, higher id); D_uk = ((D_ak + D_bk) - D_ab) / 2;
+ * R_k <- (R_k - (D_ak + D_bk)) + D_uk; R_u = ((R_a + R_b) - r D_ab) / 2.  At r = 3 one node joins the rest.  The state is a device
+ * buffer of tracs_nj_state_bytes(n) bytes (0: n is above 2^24): the matrix (n x n f64, full symmetric), row sums and node ids per
+ * slot, the join records, scratch.
+ *   tracs_nj_init        the zero matrix
+ *   tracs_nj_load_panel  the cells j > i of rows [row_begin, row_end) of dist / ncomp as tracs_pairsnp_dense writes them (device uint32,
+ *                        indexed by ABSOLUTE row, leading dimension ld >= n), mirrored: kind 0: D_ij = d; kind 1: D_ij = d / nn
+ *                        (substitutions per compared site; a cell with nn = 0 is remembered and tracs_nj_emit refuses).  ncomp may
+ *                        be NULL with kind 0.  Panels may arrive in any split.
+ *   tracs_nj_load_f64    the cells j > i of a device f64 matrix (leading dimension ld >= n), mirrored; the diagonal stays 0.
+ *                        Both loads are one stream-ordered launch and do not synchronise; n must be the n of tracs_nj_init (a
+ *                        load with another n writes nothing, and tracs_nj_run refuses the state).
+ *   tracs_nj_run         the row sums (R_k = the sum of D_mk over m = 0 .. n - 1, in that order) and the n - 3 joins, enqueued on the
+ *                        stream without a host read-back: per join a scan of the active triangle, the new row and row sums, and the
+ *                        commit that also moves the last active slot into the retired one (the scanned block stays dense).  Once
+ *                        per initialised state.  Reads the state's header first (one synchronisation of the stream, before
+ *                        anything is enqueued); tracs_nj_init synchronises once as well.
+ *   tracs_nj_emit        *n_joins <- max(n - 3, 0); unless NULL, the HOST arrays a, b (uint32: the joined nodes, a < b), d_ab, r_a,
+ *                        r_b (double: D_ab and the two row sums when they were joined, r = n - t), room for n - 3 entries;
+ *                        last_ids (HOST uint32[3]) and last_d (HOST double[3]): the last three nodes x < y < z and D_xy, D_xz, D_yz
+ *                        (n = 2: the two leaves and D_01; unused entries 0xFFFFFFFF and 0).  A remembered nn = 0 cell: TRACS_E_ARG,
+ *                        and zero_pair (HOST uint32[2], may be NULL; else 0xFFFFFFFF twice) receives its (i, j).  Synchronises.
+ *   tracs_nj_edges       host only: branch lengths from the records, l_a = D_ab / 2 + (R_a - R_b) / (2 (r - 2)), l_b = D_ab - l_a,
+ *                        for the top node l_x = ((D_xy + D_xz) - D_yz) / 2 and so on; negative lengths stay as computed.  parent,
+ *                        child, length: room for 2n - 3 edges, in creation order ((n + t, a), (n + t, b) per join, then the top
+ *                        node 2n - 3 with x, y, z).  n = 2: the one edge (0, 1, D_01); n < 2: none.
+ *   tracs_tree_write     host only: one Newick line for those edges appended to `path` (children in the edges' order, internal
+ *                        nodes unlabelled, a name with one of ()[]':;, or whitespace single-quoted with ' doubled, lengths in the
+ *                        shortest decimal form that reads back to the same double; n = 2: (A:d/2,B:d/2); n = 1: A;) and, with
+ *                        edges_path, the rows parent,child,length,ref appended to it, node n + t named #<t + 1>; names are written
+ *                        raw there, as in every other CSV of the library (a name with a comma adds fields).  No recursion.      */
+size_t tracs_nj_state_bytes(size_t n);
+int tracs_nj_init(void *state, size_t n, void *stream);
+int tracs_nj_load_panel(void *state, size_t n, const uint32_t *dist, const uint32_t *ncomp, size_t ld, size_t row_begin, size_t row_end,
+                        int kind, void *stream);
+int tracs_nj_load_f64(void *state, size_t n, const double *matrix, size_t ld, void *stream);
+int tracs_nj_run(void *state, size_t n, void *stream);
+int tracs_nj_emit(void *state, size_t n, size_t *n_joins, uint32_t *a, uint32_t *b, double *d_ab, double *r_a, double *r_b,
+                  uint32_t *last_ids, double *last_d, uint32_t *zero_pair, void *stream);
+int tracs_nj_edges(size_t n, const uint32_t *a, const uint32_t *b, const double *d_ab, const double *r_a, const double *r_b,
+                   const uint32_t *last_ids, const double *last_d, uint32_t *parent, uint32_t *child, double *length, size_t *n_edges);
+int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
+                     size_t n_edges, const char *path, const char *ref, const char *edges_path);
+
 /* Histogram of pair values over dense panels (csrc/histogram.hip; what tracs_distance_histogram runs).  The state is
  * a device buffer of tracs_hist_state_bytes(n_bins) bytes: per value v in [0, n_bins) three 64-bit counts -- pairs `within` a group
  * (both samples grouped, equal labels), `between` groups (both grouped, labels differ) and `ungrouped` (a sample with label < 0, or
@@ -609,6 +656,14 @@ int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, doub
 int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
                              int filter, int weight, const char *path, const char *ref, const char *tree_path,
                              const char *const *meta_dates, uint64_t *rows_written, uint64_t *n_eligible);
+/*   tracs_distance_tree `--tree nj` (not in the reference): the neighbour-joining tree (tracs_nj_*) of the handle's
+ *                         samples, one alignment (no second file).  The panel walk without a threshold and without the pair rule;
+ *                         every panel is loaded into the matrix (kind 0: SNP distances, 1: per compared site -- a pair compared
+ *                         over 0 sites is refused by name), the joins run on the device, lengths are computed on the host.  One
+ *                         Newick line is appended to `path`; edges_path != NULL: the 2n - 3 rows parent,child,length,ref are
+ *                         appended to it (tracs_tree_write).  n_joins: n - 3; rows_written: the edge rows.                     */
+int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint64_t *n_joins,
+                        uint64_t *rows_written);
 /*   tracs_distance_histogram `--histogram` (not in the reference): tracs_distance_run's panel loop without rows.  The
  *                         pairs it would write (d <= dist) are counted by SNP distance and class (tracs_hist_*; group: HOST int32[n]
  *                         in the order of tracs_distance_name, label < 0: ungrouped; NULL: every pair ungrouped) in min(L, dist) + 1

@@ -50,6 +50,8 @@ SYMBOLS = [
     "tracs_pair_sites_count", "tracs_pair_sites_fill", "tracs_distance_alignment", "tracs_distance_pair_sites",
     "tracs_distance_histogram", "tracs_hist_state_bytes", "tracs_hist_init", "tracs_hist_update", "tracs_hist_update_coo", "tracs_hist_emit",
     "tracs_distance_ancestors", "tracs_anc_state_bytes", "tracs_anc_init", "tracs_anc_update_coo", "tracs_anc_emit",
+    "tracs_distance_tree", "tracs_nj_state_bytes", "tracs_nj_init", "tracs_nj_load_panel", "tracs_nj_load_f64", "tracs_nj_run",
+    "tracs_nj_emit", "tracs_nj_edges", "tracs_tree_write",
 ]
 
 
@@ -194,6 +196,24 @@ def load():
     L.tracs_anc_update_coo.argtypes = [vp, sz, sz, vp, vp, vp, C.c_int, vp, dbl, vp, vp, vp, vp, vp, u64p, vp]
     L.tracs_anc_emit.restype = C.c_int
     L.tracs_anc_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tracs_distance_tree.restype = C.c_int
+    L.tracs_distance_tree.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, u64p, u64p]
+    L.tracs_nj_state_bytes.restype = sz
+    L.tracs_nj_state_bytes.argtypes = [sz]
+    L.tracs_nj_init.restype = C.c_int
+    L.tracs_nj_init.argtypes = [vp, sz, vp]
+    L.tracs_nj_load_panel.restype = C.c_int
+    L.tracs_nj_load_panel.argtypes = [vp, sz, vp, vp, sz, sz, sz, C.c_int, vp]
+    L.tracs_nj_load_f64.restype = C.c_int
+    L.tracs_nj_load_f64.argtypes = [vp, sz, vp, sz, vp]
+    L.tracs_nj_run.restype = C.c_int
+    L.tracs_nj_run.argtypes = [vp, sz, vp]
+    L.tracs_nj_emit.restype = C.c_int
+    L.tracs_nj_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tracs_nj_edges.restype = C.c_int
+    L.tracs_nj_edges.argtypes = [sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
+    L.tracs_tree_write.restype = C.c_int
+    L.tracs_tree_write.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, C.c_char_p, C.c_char_p, C.c_char_p]
     L.tracs_distance_histogram.restype = C.c_int
     L.tracs_distance_histogram.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_char_p, C.c_char_p, u64p, u64p]
     L.tracs_hist_state_bytes.restype = sz

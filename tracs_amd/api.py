@@ -108,6 +108,35 @@ def distance_histogram(fasta, dist=2147483647, filter=False, groups=None, sites=
     return names, out
 
 
+def neighbor_joining(D):
+    """The neighbour-joining tree of a symmetric distance matrix (tracs_nj_*): D is a host array or a torch tensor
+    (host or device), n x n, finite, non-negative, symmetric with a zero diagonal (else ValueError).  -> parent, child (uint32) and
+    length (float64): the 2n - 3 edges in creation order.  Leaves are 0 .. n - 1, join number t makes the node n + t, the last node
+    (2n - 3) joins the remaining three; n = 2: the one edge (0, 1, D_01).  Negative lengths are returned as computed."""
+    import torch
+    from . import device as dev
+    _lib.require_gpu()
+    M = D if isinstance(D, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(D, dtype=np.float64)))
+    if M.dim() != 2 or M.shape[0] != M.shape[1]:
+        raise ValueError("neighbor_joining(): D must be a square matrix, got shape %r" % (tuple(M.shape),))
+    M = M.to(device="cuda", dtype=torch.float64).contiguous()
+    n = int(M.shape[0])
+    if n:
+        if not bool(torch.isfinite(M).all()):
+            raise ValueError("neighbor_joining(): D has a non-finite entry")
+        if bool((M < 0).any()):
+            raise ValueError("neighbor_joining(): D has a negative entry")
+        if bool((torch.diagonal(M) != 0).any()):
+            raise ValueError("neighbor_joining(): D has a non-zero diagonal entry")
+        if not bool((M == M.t()).all()):
+            raise ValueError("neighbor_joining(): D is not symmetric")
+    state = dev.nj_init(n)
+    if n >= 2:
+        dev.nj_load_f64(state, n, M)
+    dev.nj_run(state, n)
+    return dev.nj_edges(n, *dev.nj_emit(state, n))
+
+
 def pair_sites(fasta, pairs, filter=False, sites=None, info=None, max_sample_n_share=None, max_n_share=None):
     """The SNP sites behind listed pairs -> (offsets int64[m + 1], site uint32[], info uint32[], names): pair t's
     entries are [offsets[t], offsets[t + 1]), ascending by site; site indexes the compared alignment (the kept columns; info receives

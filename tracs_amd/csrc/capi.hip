@@ -1218,6 +1218,59 @@ int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, d
     return rc;
 }
 
+// `tracs distance --tree nj` for one alignment (include/tracs_hip.h): the panel walk without a threshold and without
+// the pair rule (every pair has a distance), each dense panel loaded into the neighbour-joining state, the joins on the device, then
+// the records -> branch lengths -> one Newick line and the edge rows on the host.
+int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint64_t *n_joins,
+                        uint64_t *rows_written)
+{
+    if (n_joins) *n_joins = 0;
+    if (rows_written) *rows_written = 0;
+    if (!h || !h->a || !path || !ref) { set_error("tracs_distance_tree: NULL argument"); return TRACS_E_ARG; }
+    if (kind != 0 && kind != 1) { set_error("tracs_distance_tree: kind must be 0 (snp) or 1 (per-site)"); return TRACS_E_ARG; }
+    if (h->n_fasta != 1) { set_error("tracs_distance_tree: a tree joins the samples of one alignment"); return TRACS_E_ARG; }
+    SigintScope sigint;
+    const size_t n = h->a->n;
+    if (n && !tracs_nj_state_bytes(n)) { set_error("tracs_distance_tree: too many samples for one distance matrix"); return TRACS_E_ARG; }
+    StageClock clock;
+    int rc;
+    std::vector<uint32_t> ja, jb, parent, child;
+    std::vector<double> jd, jra, jrb, length;
+    uint32_t last_ids[3] = {0, n > 1 ? 1u : 0xFFFFFFFFu, 0xFFFFFFFFu};      // (n < 2: no pair exists, nothing runs on the device)
+    double last_d[3] = {0.0, 0.0, 0.0};
+    size_t nj = 0, ne = 0;
+    PanelWalk walk(h->a, 1, n, 2147483647, 0);
+    DeviceBuffer d_state;
+    if (walk.any()) {
+        if ((rc = d_state.alloc(tracs_nj_state_bytes(n))) || (rc = tracs_nj_init(d_state.ptr, n, nullptr))) return rc;
+        if ((rc = walk.begin(false, false))) return rc;
+        for (Panel pn; walk.more();) {
+            if ((rc = walk.next(pn)) || (rc = tracs_nj_load_panel(d_state.ptr, n, pn.bd, pn.bn, n, pn.r0, pn.r1, kind, nullptr))) return rc;
+        }
+        clock.mark("dense panels + matrix load");
+        if ((rc = tracs_nj_run(d_state.ptr, n, nullptr))) return rc;
+        TRACS_HIP_CHECK(hipDeviceSynchronize());
+        if (g_sigint) return interrupted();
+        clock.mark("join loop");
+        ja.resize(n); jb.resize(n); jd.resize(n); jra.resize(n); jrb.resize(n);
+        uint32_t zero[2];
+        rc = tracs_nj_emit(d_state.ptr, n, &nj, ja.data(), jb.data(), jd.data(), jra.data(), jrb.data(), last_ids, last_d, zero, nullptr);
+        if (rc == TRACS_E_ARG && zero[0] < n && zero[1] < n)
+            set_error(std::string("samples '") + h->name_ptr[zero[0]] + "' and '" + h->name_ptr[zero[1]] + "' have no site at which both are "
+                      "known: no per-site distance (--max-sample-n-share leaves out samples that are mostly N)");
+        if (rc) return rc;
+    }
+    parent.resize(2 * n + 1); child.resize(2 * n + 1); length.resize(2 * n + 1);
+    if ((rc = tracs_nj_edges(n, ja.data(), jb.data(), jd.data(), jra.data(), jrb.data(), last_ids, last_d, parent.data(), child.data(),
+                             length.data(), &ne))) return rc;
+    if ((rc = tracs_tree_write(h->name_ptr.data(), n, parent.data(), child.data(), length.data(), ne, path, ref, edges_path))) return rc;
+    clock.mark("tree: emit, lengths, format, write");
+    if (n_joins) *n_joins = nj;
+    if (rows_written) *rows_written = edges_path ? ne : 0;
+    if (g_sigint) return interrupted();
+    return TRACS_OK;
+}
+
 // `tracs distance --histogram` for one alignment (include/tracs_hip.h): the panel walk of tracs_distance_run with
 // tracs_hist_update on each dense panel instead of the rows; with --filter the panel's pairs within the threshold are extracted and
 // filtered by the same pair stage, and a second state counts their filtered distances.  What crosses to the host is the

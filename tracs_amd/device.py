@@ -457,6 +457,73 @@ def anc_emit(state, n):
     return [x[:k] for x in u + f] + [x[:int(n)] for x in t]
 
 
+def nj_init(n, device=None):
+    """A neighbour-joining state with the zero matrix for the leaves [0, n) (tracs_nj_init): a torch.uint8 device buffer."""
+    L = _lib.require_gpu()
+    nbytes = L.tracs_nj_state_bytes(int(n))
+    if nbytes == 0:
+        raise ValueError("nj_init(): at most 2^24 leaves, got %d" % int(n))
+    state = torch.empty(nbytes, dtype=torch.uint8, device=device if device is not None else "cuda")
+    _lib.check(L.tracs_nj_init(_ptr(state), int(n), _stream()))
+    return state
+
+
+def nj_load_panel(state, n, dist, ncomp=None, row_begin=0, row_end=None, per_site=False, base_row=0):
+    """The cells j > i of the panel rows [row_begin, row_end) of dist / ncomp (as pairsnp_dense wrote them; the panels hold rows
+    base_row..) into the matrix, mirrored (tracs_nj_load_panel): D = d, or with per_site d / nn."""
+    L = _lib.require_gpu()
+    row_end = n if row_end is None else row_end
+    ld = dist.stride(0)
+    assert dist.element_size() == 4 and base_row <= row_begin and row_end - base_row <= dist.shape[0]
+    assert ncomp is None or (ncomp.stride(0) == ld and ncomp.element_size() == 4)
+    _lib.check(L.tracs_nj_load_panel(_ptr(state), int(n), _panel_ptr(dist, base_row), _panel_ptr(ncomp, base_row), int(ld), int(row_begin),
+                                     int(row_end), int(bool(per_site)), _stream()))
+
+
+def nj_load_f64(state, n, matrix):
+    """The cells j > i of a torch.float64 device matrix [n, ld >= n] into the matrix, mirrored (tracs_nj_load_f64)."""
+    L = _lib.require_gpu()
+    assert matrix.dtype == torch.float64 and matrix.dim() == 2 and matrix.stride(1) == 1 and matrix.shape[0] >= n and matrix.shape[1] >= n
+    _lib.check(L.tracs_nj_load_f64(_ptr(state), int(n), _ptr(matrix), int(matrix.stride(0)), _stream()))
+
+
+def nj_run(state, n):
+    """The row sums and the n - 3 joins, enqueued on the current stream (tracs_nj_run)."""
+    _lib.check(_lib.require_gpu().tracs_nj_run(_ptr(state), int(n), _stream()))
+
+
+def nj_emit(state, n):
+    """The join records and the last three nodes (tracs_nj_emit), on the host: (a, b (uint32), d_ab, r_a, r_b (float64)), last_ids
+    (uint32[3]), last_d (float64[3]).  A per-site cell with nn = 0: ValueError carrying .pair = (i, j)."""
+    L = _lib.require_gpu()
+    m = max(int(n) - 3, 0)
+    a, b = np.zeros(max(m, 1), np.uint32), np.zeros(max(m, 1), np.uint32)
+    f = [np.zeros(max(m, 1), np.float64) for _ in range(3)]
+    last_ids, last_d, zero = np.zeros(3, np.uint32), np.zeros(3, np.float64), np.zeros(2, np.uint32)
+    cnt = C.c_size_t(0)
+    rc = L.tracs_nj_emit(_ptr(state), int(n), C.byref(cnt), *[C.c_void_p(x.ctypes.data) for x in [a, b] + f + [last_ids, last_d, zero]],
+                         _stream())
+    if rc and zero[0] != 0xFFFFFFFF:
+        err = ValueError("nj_emit(): samples %d and %d were compared over 0 sites: no per-site distance" % (zero[0], zero[1]))
+        err.pair = (int(zero[0]), int(zero[1]))
+        raise err
+    _lib.check(rc)
+    return (a[:m], b[:m], f[0][:m], f[1][:m], f[2][:m]), last_ids, last_d
+
+
+def nj_edges(n, records, last_ids, last_d):
+    """Branch lengths from nj_emit's output (tracs_nj_edges; host only) -> parent, child (uint32), length (float64): the tree's
+    2n - 3 edges in creation order (join t makes node n + t, the top node is 2n - 3)."""
+    L = _lib.load()
+    cap = max(2 * int(n), 1)
+    parent, child, length = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.float64)
+    arrs = [np.ascontiguousarray(x, dt) for x, dt in zip(records, (np.uint32, np.uint32, np.float64, np.float64, np.float64))]
+    arrs += [np.ascontiguousarray(last_ids, np.uint32), np.ascontiguousarray(last_d, np.float64)]
+    cnt = C.c_size_t(0)
+    _lib.check(L.tracs_nj_edges(int(n), *[C.c_void_p(x.ctypes.data) for x in arrs + [parent, child, length]], C.byref(cnt)))
+    return parent[:cnt.value], child[:cnt.value], length[:cnt.value]
+
+
 def hist_init(n_bins, device=None):
     """An all-zero histogram state for the values [0, n_bins) (tracs_hist_init): a torch.uint8 device buffer."""
     L = _lib.require_gpu()

@@ -43,6 +43,10 @@ ANCESTORS_HEADER = "sample,date,ancestor,ancestor date,root,generation,MSA file\
 
 HISTOGRAM_HEADER = "column,distance,within,between,ungrouped,MSA file\n"
 
+TREE_EDGES_HEADER = "parent,child,length,MSA file\n"
+
+TREE_DISTANCES = {"snp": 0, "per-site": 1}
+
 HEADER = ("sampleA,sampleB,date difference,SNP distance,transmission distance,expected K,"
           "filtered SNP distance,sites considered,MSA file\n")
 
@@ -112,6 +116,23 @@ def distance_parser(parser):
                      help="With --ancestors: write sample,date,ancestor,ancestor date,root,generation,MSA file for every compared "
                           "sample, in input order (dates as --meta gives them; a root has no ancestor, itself as root and generation 0; "
                           "else root is the sample reached by following sources and generation the number of links to it)")
+    snp.add_argument("--tree", dest="tree", choices=["nj"], default=None, metavar="METHOD",
+                     help="Instead of the pairs, output a phylogeny of each --msa file's samples: nj, the neighbour-joining tree "
+                          "(Saitou & Nei) of all pairwise distances, built on the GPU.  -o then holds one Newick tree per --msa file, "
+                          "one per line and without a header: unrooted, written from the last node joined, internal nodes unlabelled, "
+                          "names quoted where Newick needs it.  Branch lengths are in the unit of --tree-distance; neighbour joining "
+                          "can give negative lengths on data that is not tree-like, and they are written as computed.  Ties are "
+                          "broken by input order, so the tree is reproducible.  One GPU; takes the site and sample rules, no -D, -K, "
+                          "--filter, --meta, --min-sites or --msa-db; not with --nearest, --mst, --ancestors or --histogram.  Not in "
+                          "the reference.")
+    snp.add_argument("--tree-distance", dest="tree_distance", choices=list(TREE_DISTANCES), default=None,
+                     help="With --tree: snp (default), the SNP distance; per-site, the SNP distance divided by the sites the pair was "
+                          "compared over (substitutions per compared site).  per-site refuses a pair without any compared site: "
+                          "leave mostly-N samples out with --max-sample-n-share.")
+    snp.add_argument("--tree-edges", dest="tree_edges", default=None, type=str, metavar="FILE",
+                     help="With --tree: also write the tree's 2n - 3 edges as parent,child,length,MSA file, in the order they were "
+                          "made; internal nodes are named #1, #2, ... by join number, the last one (#(n-2)) joins the remaining three.  "
+                          "Sample names are written as they are, as in the other outputs (Newick quotes them)")
     snp.add_argument("--histogram", dest="histogram", action="store_true", default=False,
                      help="Instead of the pairs, output how many of them have each SNP distance (and, with --filter, each filtered "
                           "SNP distance): rows column,distance,within,between,ungrouped,MSA file, one per non-empty bin.  The pairs "
@@ -358,6 +379,43 @@ def check_ancestors_args(args):
     if anc == "filter" and not args.recomb_filter:
         raise SystemExit("tracs distance: --ancestors filter needs --filter (the filtered SNP distance column)")
     check_output_paths("distance", _inputs(args), dict(_outputs(args), **{"--ancestors-out": out}), ["--ancestors-out"])
+
+
+def check_tree_args(args):
+    """--tree's, --tree-distance's and --tree-edges' argument checks, before anything touches the GPU (SystemExit with the message)."""
+    if args.tree is None:
+        if args.tree_distance is not None:
+            raise SystemExit("tracs distance: --tree-distance needs --tree (it chooses the distances the tree is built from)")
+        if args.tree_edges is not None:
+            raise SystemExit("tracs distance: --tree-edges needs --tree (it lists the edges of the tree that --tree builds)")
+        return
+    for opt, given in (("--nearest", args.nearest is not None), ("--mst", args.mst is not None),
+                       ("--ancestors", args.ancestors is not None), ("--histogram", args.histogram)):
+        if given:
+            raise SystemExit("tracs distance: --tree and %s cannot be combined" % opt)
+    if args.snp_threshold != 2147483647:
+        raise SystemExit("tracs distance: --tree joins all samples and takes no -D (every pair's distance is used)")
+    if args.trans_threshold is not None:
+        raise SystemExit("tracs distance: --tree is built from SNP distances and takes no -K")
+    if args.recomb_filter:
+        raise SystemExit("tracs distance: --tree is built from the unfiltered SNP distances and takes no --filter")
+    if args.metadata is not None:
+        raise SystemExit("tracs distance: --tree is built from SNP distances and takes no --meta")
+    if args.min_sites is not None:
+        raise SystemExit("tracs distance: --tree needs every pair's distance and takes no --min-sites (use --max-sample-n-share)")
+    if args.msa_db is not None:
+        raise SystemExit("tracs distance: --tree joins the samples of one alignment and takes no --msa-db")
+    if args.gpus > 1:
+        raise SystemExit("tracs distance: --tree runs on one GPU; use --gpus 1")
+    check_output_paths("distance", _inputs(args), dict(_outputs(args), **{"--tree-edges": args.tree_edges}), ["--tree-edges"])
+
+
+def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
+    """--tree nj for one alignment (handle.DistanceHandle.tree, tracs_distance_tree: include/tracs_hip.h): every dense panel goes into the
+    distance matrix on the device, the joins run there, and one Newick line (and the edge rows) are appended by the library."""
+    with _opened(msas, args, stage, rule, contigs) as h:
+        joins, rows = h.tree(args.output_file, ref, per_site=TREE_DISTANCES[args.tree_distance or "snp"] == 1, edges_path=args.tree_edges)
+        stage("[sum] tracs_distance_tree (dense panels, joins, tree: %d joins, %d edge rows written)" % (joins, rows))
 
 
 def check_mst_args(args):
@@ -723,10 +781,12 @@ class _Stages:
 # option -> (the route that stays on the device until its rows, its INFO line); distance() looks the route up by name when it dispatches
 DEVICE_ROUTES = {"histogram": ("_histogram_on_device", "Saving the distance histogram for %s"),
                  "mst": ("_forest_on_device", "Saving the minimum spanning forest for %s"),
-                 "ancestors": ("_ancestors_on_device", "Saving the ancestor links for %s")}
+                 "ancestors": ("_ancestors_on_device", "Saving the ancestor links for %s"),
+                 "tree": ("_tree_on_device", "Saving the neighbour-joining tree for %s")}
 
 
 def distance(args):
+    check_tree_args(args)
     check_ancestors_args(args)
     check_mst_args(args)
     check_histogram_args(args)
@@ -759,7 +819,10 @@ def distance(args):
     logging.info("Estimating transmission distances...")
     if lead:
         with open(args.output_file, "w") as out:
-            out.write(HISTOGRAM_HEADER if args.histogram else HEADER)
+            out.write("" if args.tree is not None else HISTOGRAM_HEADER if args.histogram else HEADER)      # (Newick lines: no header)
+        if args.tree is not None and args.tree_edges is not None:
+            with open(args.tree_edges, "w") as out:
+                out.write(TREE_EDGES_HEADER)
         if args.ancestors is not None and args.ancestors_out is not None:
             with open(args.ancestors_out, "w") as out:
                 out.write(ANCESTORS_HEADER)
@@ -775,7 +838,7 @@ def distance(args):
         if args.msa_out is not None or args.site_table is not None:
             ruled["contigs"] = site_files[2]
         if route is not None:
-            # one GPU, on the device until its rows: the histogram, the forest or the ancestor links of the pairs the full run would write
+            # one GPU, on the device until its rows: the histogram, the forest or the ancestor links of the pairs the full run would write, or the tree
             require_files(msas)
             globals()[route[0]](msas, args, groups if args.histogram else dates, ref, stage, **ruled)      # (--histogram takes no --meta)
             logging.info(route[1], msa)

@@ -126,6 +126,14 @@ class DistanceHandle:
     def source(self):
         return source_records(self.L, "distance", self.h)
 
+    def tree(self, path, ref, per_site=False, edges_path=None):
+        """The neighbour-joining tree of the handle's samples (tracs_distance_tree): one Newick line appended to `path`, the edge rows
+        to edges_path.  -> (joins, edge rows written)"""
+        joins, rows = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(self.L.tracs_distance_tree(self.h, int(bool(per_site)), os.fsencode(path), ref.encode(),
+                                              os.fsencode(edges_path) if edges_path is not None else None, C.byref(joins), C.byref(rows)))
+        return joins.value, rows.value
+
     def alignment(self):
         """the handle's packed alignment, borrowed: close it before the handle"""
         from . import device as dev
