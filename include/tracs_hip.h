@@ -407,6 +407,34 @@ int tracs_nj_edges(size_t n, const uint32_t *a, const uint32_t *b, const double 
 int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
                      size_t n_edges, const char *path, const char *ref, const char *edges_path);
 
+/* Bootstrap support for the neighbour-joining tree (csrc/bootstrap.hip; what tracs_distance_tree_bootstrap runs).  One
+ * replicate is the run on an alignment whose L columns were drawn with replacement.  All arithmetic mod 2^64:
+ *     mix(x): z = x; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ *     G = 0x9E3779B97F4A7C15; key_b = mix(seed + G (b + 1)); u(b, t) = mix(key_b + G (t + 1)); c(b, t) = (u(b, t) L) >> 64
+ * for t = 0 .. L - 1; w_b(c) = the number of t with c(b, t) = c (they sum to L).
+ *   tracs_bootstrap_weights       weights (device uint32[L]) <- w_replicate.  One thread per draw, integer atomics.  Stream-ordered.
+ *   tracs_alignment_gather_sites  weights: device uint32[the handle's length].  *out: a NEW handle in which column c of src is repeated
+ *                                 weights[c] times, columns in ascending c, every sample: byte for byte what packing that text gives
+ *                                 (pad samples, tail bits, pad groups and slack zero, N = A & C & G & T); src is left as it was.
+ *                                 *n_out (may be NULL): its length, the sum of the weights.  A sum of 0 ("no column drawn") or of
+ *                                 2^32 and more is refused (TRACS_E_ARG).  Synchronises the stream.
+ *   tracs_tree_support            host only, no recursion: both trees as tracs_nj_edges gives them (2n - 3 edges over the same n
+ *                                 leaves, in creation order).  An internal edge is one whose child is an internal node; its split is
+ *                                 the set of leaves below the child, taken on the side without leaf 0 (bitsets of ceil(n / 64) words,
+ *                                 built bottom-up in the edges' order).  count[e] += 1 for every internal edge e of the first tree
+ *                                 whose split is the split of an internal edge of the second (a hash finds candidates, equality of
+ *                                 the bitsets decides); other entries of count are left alone.  n < 4: nothing to do.
+ *   tracs_tree_write_support      tracs_tree_write with support (uint32 per edge, 0xFFFFFFFF = none, else at most `replicates`): an
+ *                                 internal node whose edge has one carries it as a decimal label, `(A:1,B:2)87:0.5`; the edge rows
+ *                                 are parent,child,length,support,ref with NA on leaf edges and where there is none.              */
+int tracs_bootstrap_weights(size_t L, uint64_t seed, uint64_t replicate, uint32_t *weights, void *stream);
+int tracs_alignment_gather_sites(const tracs_alignment *src, const uint32_t *weights, tracs_alignment **out, size_t *n_out, void *stream);
+int tracs_tree_support(size_t n, const uint32_t *parent, const uint32_t *child, size_t n_edges, const uint32_t *rep_parent,
+                       const uint32_t *rep_child, size_t rep_n_edges, uint32_t *count);
+int tracs_tree_write_support(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
+                             size_t n_edges, const uint32_t *support, uint32_t replicates, const char *path, const char *ref,
+                             const char *edges_path);
+
 /* Histogram of pair values over dense panels (csrc/histogram.hip; what tracs_distance_histogram runs).  The state is
  * a device buffer of tracs_hist_state_bytes(n_bins) bytes: per value v in [0, n_bins) three 64-bit counts -- pairs `within` a group
  * (both samples grouped, equal labels), `between` groups (both grouped, labels differ) and `ungrouped` (a sample with label < 0, or
@@ -664,6 +692,17 @@ int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, d
  *                         appended to it (tracs_tree_write).  n_joins: n - 3; rows_written: the edge rows.                     */
 int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint64_t *n_joins,
                         uint64_t *rows_written);
+/*   tracs_distance_tree_bootstrap `--tree nj --bootstrap B` (not in the reference): tracs_distance_tree's main tree
+ *                         (kind 0 only), then `replicates` >= 1 bootstrap replicates b = 0 .. replicates - 1 under `seed`: the columns
+ *                         at which two samples differ are selected once (the others add nothing to any replicate's distances), and per
+ *                         replicate the draws are counted over them, the replicate is gathered into a handle of its own
+ *                         (tracs_alignment_gather_sites; none drawn: the zero matrix), the same panel walk, load, joins and lengths
+ *                         give its tree, tracs_tree_support counts its splits, and the handle is freed.  The Newick line carries the
+ *                         counts as labels and the edge rows a support field (tracs_tree_write_support); n < 4: no labels, NA.
+ *                         replicate_trees_path != NULL: each replicate's Newick line (no labels) is appended to it, in replicate
+ *                         order (n >= 4).  Bit-reproducible for a given (handle, replicates, seed).                             */
+int tracs_distance_tree_bootstrap(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint32_t replicates,
+                                  uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins, uint64_t *rows_written);
 /*   tracs_distance_histogram `--histogram` (not in the reference): tracs_distance_run's panel loop without rows.  The
  *                         pairs it would write (d <= dist) are counted by SNP distance and class (tracs_hist_*; group: HOST int32[n]
  *                         in the order of tracs_distance_name, label < 0: ungrouped; NULL: every pair ungrouped) in min(L, dist) + 1

@@ -52,6 +52,8 @@ SYMBOLS = [
     "tracs_distance_ancestors", "tracs_anc_state_bytes", "tracs_anc_init", "tracs_anc_update_coo", "tracs_anc_emit",
     "tracs_distance_tree", "tracs_nj_state_bytes", "tracs_nj_init", "tracs_nj_load_panel", "tracs_nj_load_f64", "tracs_nj_run",
     "tracs_nj_emit", "tracs_nj_edges", "tracs_tree_write",
+    "tracs_bootstrap_weights", "tracs_alignment_gather_sites", "tracs_tree_support", "tracs_tree_write_support",
+    "tracs_distance_tree_bootstrap",
 ]
 
 
@@ -214,6 +216,18 @@ def load():
     L.tracs_nj_edges.argtypes = [sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
     L.tracs_tree_write.restype = C.c_int
     L.tracs_tree_write.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, C.c_char_p, C.c_char_p, C.c_char_p]
+    L.tracs_bootstrap_weights.restype = C.c_int
+    L.tracs_bootstrap_weights.argtypes = [sz, C.c_uint64, C.c_uint64, vp, vp]
+    L.tracs_debug_bootstrap_replicate.restype = C.c_int
+    L.tracs_debug_bootstrap_replicate.argtypes = [vp, sz, u64p, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(sz)]
+    L.tracs_alignment_gather_sites.restype = C.c_int
+    L.tracs_alignment_gather_sites.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(sz), vp]
+    L.tracs_tree_support.restype = C.c_int
+    L.tracs_tree_support.argtypes = [sz, vp, vp, sz, vp, vp, sz, vp]
+    L.tracs_tree_write_support.restype = C.c_int
+    L.tracs_tree_write_support.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, vp, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p]
+    L.tracs_distance_tree_bootstrap.restype = C.c_int
+    L.tracs_distance_tree_bootstrap.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64, C.c_char_p, u64p, u64p]
     L.tracs_distance_histogram.restype = C.c_int
     L.tracs_distance_histogram.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_char_p, C.c_char_p, u64p, u64p]
     L.tracs_hist_state_bytes.restype = sz

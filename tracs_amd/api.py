@@ -137,6 +137,27 @@ def neighbor_joining(D):
     return dev.nj_edges(n, *dev.nj_emit(state, n))
 
 
+def tree_support(n, main_edges, replicate_edges):
+    """Bootstrap support (tracs_tree_support, host only): main_edges = (parent, child[, length]) of a tree over the
+    leaves 0 .. n - 1 as neighbor_joining returns it, replicate_edges = a list of such trees over the same leaves.  -> uint32 per edge
+    of the main tree: for an internal edge (its child is an internal node) the number of replicate trees that have an internal edge
+    with the same split of the leaves, else 0xFFFFFFFF.  n < 4: no internal edge."""
+    L = _lib.load()
+    n = int(n)
+    parent, child = (np.ascontiguousarray(x, np.uint32) for x in main_edges[:2])
+    if parent.shape != child.shape or parent.ndim != 1:
+        raise ValueError("tree_support(): parent and child must be two arrays of one length")
+    count = np.zeros(len(parent), np.uint32)
+    for rep in replicate_edges:
+        rp, rc = (np.ascontiguousarray(x, np.uint32) for x in rep[:2])
+        if rp.shape != rc.shape or rp.ndim != 1:
+            raise ValueError("tree_support(): parent and child must be two arrays of one length")
+        _lib.check(L.tracs_tree_support(n, parent.ctypes.data, child.ctypes.data, len(parent), rp.ctypes.data, rc.ctypes.data, len(rp),
+                                        count.ctypes.data))
+    count[(child < n) | (n < 4)] = 0xFFFFFFFF
+    return count
+
+
 def pair_sites(fasta, pairs, filter=False, sites=None, info=None, max_sample_n_share=None, max_n_share=None):
     """The SNP sites behind listed pairs -> (offsets int64[m + 1], site uint32[], info uint32[], names): pair t's
     entries are [offsets[t], offsets[t + 1]), ascending by site; site indexes the compared alignment (the kept columns; info receives

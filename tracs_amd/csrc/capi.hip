@@ -1220,7 +1220,64 @@ int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, d
 
 // `tracs distance --tree nj` for one alignment (include/tracs_hip.h): the panel walk without a threshold and without
 // the pair rule (every pair has a distance), each dense panel loaded into the neighbour-joining state, the joins on the device, then
-// the records -> branch lengths -> one Newick line and the edge rows on the host.
+// the records -> branch lengths on the host.  tracs_distance_tree writes them; tracs_distance_tree_bootstrap runs the
+// same body once for the handle and once per replicate, on one walk (its dense buffers) and one state.
+namespace {
+
+struct TreeEdges {
+    std::vector<uint32_t> parent, child;
+    std::vector<double> length;
+    size_t nj = 0, ne = 0;
+};
+
+// a stage of one tree: the main tree marks it on the stage clock, a replicate adds it to a sum
+void tree_stage(StageClock &clock, const char *name, double *acc)
+{
+    if (acc) lap(clock, *acc);
+    else clock.mark(name);
+}
+
+// a == NULL: the zero matrix (a replicate that drew no differing column); acc: NULL, or the replicates' three sums
+int tree_of_alignment(tracs_alignment *a, size_t n, const char *const *names, int kind, PanelWalk &walk, DeviceBuffer &d_state,
+                      StageClock &clock, double *acc, TreeEdges &t)
+{
+    int rc;
+    std::vector<uint32_t> ja, jb;
+    std::vector<double> jd, jra, jrb;
+    uint32_t last_ids[3] = {0, n > 1 ? 1u : 0xFFFFFFFFu, 0xFFFFFFFFu};      // (n < 2: no pair exists, nothing runs on the device)
+    double last_d[3] = {0.0, 0.0, 0.0};
+    t.nj = t.ne = 0;
+    if (walk.any()) {
+        if (!d_state.ptr && (rc = d_state.alloc(tracs_nj_state_bytes(n)))) return rc;
+        if ((rc = tracs_nj_init(d_state.ptr, n, nullptr))) return rc;
+        if (a) {
+            walk.a = a;
+            walk.at = 0;
+            if (!walk.height && (rc = walk.begin(false, false))) return rc;
+            for (Panel pn; walk.more();) {
+                if ((rc = walk.next(pn)) || (rc = tracs_nj_load_panel(d_state.ptr, n, pn.bd, pn.bn, n, pn.r0, pn.r1, kind, nullptr))) return rc;
+            }
+        }
+        tree_stage(clock, "dense panels + matrix load", acc);
+        if ((rc = tracs_nj_run(d_state.ptr, n, nullptr))) return rc;
+        TRACS_HIP_CHECK(hipDeviceSynchronize());
+        if (g_sigint) return interrupted();
+        tree_stage(clock, "join loop", acc ? acc + 1 : nullptr);
+        ja.resize(n); jb.resize(n); jd.resize(n); jra.resize(n); jrb.resize(n);
+        uint32_t zero[2];
+        rc = tracs_nj_emit(d_state.ptr, n, &t.nj, ja.data(), jb.data(), jd.data(), jra.data(), jrb.data(), last_ids, last_d, zero, nullptr);
+        if (rc == TRACS_E_ARG && zero[0] < n && zero[1] < n)
+            set_error(std::string("samples '") + names[zero[0]] + "' and '" + names[zero[1]] + "' have no site at which both are "
+                      "known: no per-site distance (--max-sample-n-share leaves out samples that are mostly N)");
+        if (rc) return rc;
+    }
+    t.parent.resize(2 * n + 1); t.child.resize(2 * n + 1); t.length.resize(2 * n + 1);
+    return tracs_nj_edges(n, ja.data(), jb.data(), jd.data(), jra.data(), jrb.data(), last_ids, last_d, t.parent.data(), t.child.data(),
+                          t.length.data(), &t.ne);
+}
+
+}  // namespace
+
 int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint64_t *n_joins,
                         uint64_t *rows_written)
 {
@@ -1234,39 +1291,96 @@ int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const cha
     if (n && !tracs_nj_state_bytes(n)) { set_error("tracs_distance_tree: too many samples for one distance matrix"); return TRACS_E_ARG; }
     StageClock clock;
     int rc;
-    std::vector<uint32_t> ja, jb, parent, child;
-    std::vector<double> jd, jra, jrb, length;
-    uint32_t last_ids[3] = {0, n > 1 ? 1u : 0xFFFFFFFFu, 0xFFFFFFFFu};      // (n < 2: no pair exists, nothing runs on the device)
-    double last_d[3] = {0.0, 0.0, 0.0};
-    size_t nj = 0, ne = 0;
+    TreeEdges t;
     PanelWalk walk(h->a, 1, n, 2147483647, 0);
     DeviceBuffer d_state;
-    if (walk.any()) {
-        if ((rc = d_state.alloc(tracs_nj_state_bytes(n))) || (rc = tracs_nj_init(d_state.ptr, n, nullptr))) return rc;
-        if ((rc = walk.begin(false, false))) return rc;
-        for (Panel pn; walk.more();) {
-            if ((rc = walk.next(pn)) || (rc = tracs_nj_load_panel(d_state.ptr, n, pn.bd, pn.bn, n, pn.r0, pn.r1, kind, nullptr))) return rc;
-        }
-        clock.mark("dense panels + matrix load");
-        if ((rc = tracs_nj_run(d_state.ptr, n, nullptr))) return rc;
-        TRACS_HIP_CHECK(hipDeviceSynchronize());
-        if (g_sigint) return interrupted();
-        clock.mark("join loop");
-        ja.resize(n); jb.resize(n); jd.resize(n); jra.resize(n); jrb.resize(n);
-        uint32_t zero[2];
-        rc = tracs_nj_emit(d_state.ptr, n, &nj, ja.data(), jb.data(), jd.data(), jra.data(), jrb.data(), last_ids, last_d, zero, nullptr);
-        if (rc == TRACS_E_ARG && zero[0] < n && zero[1] < n)
-            set_error(std::string("samples '") + h->name_ptr[zero[0]] + "' and '" + h->name_ptr[zero[1]] + "' have no site at which both are "
-                      "known: no per-site distance (--max-sample-n-share leaves out samples that are mostly N)");
-        if (rc) return rc;
-    }
-    parent.resize(2 * n + 1); child.resize(2 * n + 1); length.resize(2 * n + 1);
-    if ((rc = tracs_nj_edges(n, ja.data(), jb.data(), jd.data(), jra.data(), jrb.data(), last_ids, last_d, parent.data(), child.data(),
-                             length.data(), &ne))) return rc;
-    if ((rc = tracs_tree_write(h->name_ptr.data(), n, parent.data(), child.data(), length.data(), ne, path, ref, edges_path))) return rc;
+    if ((rc = tree_of_alignment(h->a, n, h->name_ptr.data(), kind, walk, d_state, clock, nullptr, t))) return rc;
+    if ((rc = tracs_tree_write(h->name_ptr.data(), n, t.parent.data(), t.child.data(), t.length.data(), t.ne, path, ref, edges_path))) return rc;
     clock.mark("tree: emit, lengths, format, write");
-    if (n_joins) *n_joins = nj;
-    if (rows_written) *rows_written = edges_path ? ne : 0;
+    if (n_joins) *n_joins = t.nj;
+    if (rows_written) *rows_written = edges_path ? t.ne : 0;
+    if (g_sigint) return interrupted();
+    return TRACS_OK;
+}
+
+// `tracs distance --tree nj --bootstrap B` (include/tracs_hip.h).  The main tree as above; then the columns at which two
+// samples differ are selected once (census bitmap -> tracs_alignment_select_sites: the other columns add nothing to any replicate's
+// distances), and per replicate: the draws counted over those columns, the replicate gathered into a handle of its own, the same
+// panel walk / load / joins / lengths, the splits compared, the handle freed.  One state, one walk, one replicate alive at a time.
+int tracs_distance_tree_bootstrap(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint32_t replicates,
+                                  uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins, uint64_t *rows_written)
+{
+    if (n_joins) *n_joins = 0;
+    if (rows_written) *rows_written = 0;
+    if (!h || !h->a || !path || !ref) { set_error("tracs_distance_tree_bootstrap: NULL argument"); return TRACS_E_ARG; }
+    if (kind != 0) { set_error("tracs_distance_tree_bootstrap: bootstrap replicates take the SNP distance (kind 0) only"); return TRACS_E_ARG; }
+    if (replicates < 1) { set_error("tracs_distance_tree_bootstrap: at least one replicate"); return TRACS_E_ARG; }
+    if (h->n_fasta != 1) { set_error("tracs_distance_tree_bootstrap: a tree joins the samples of one alignment"); return TRACS_E_ARG; }
+    SigintScope sigint;
+    tracs_alignment *a = h->a;
+    const size_t n = a->n, L = a->L;
+    if (n && !tracs_nj_state_bytes(n)) { set_error("tracs_distance_tree_bootstrap: too many samples for one distance matrix"); return TRACS_E_ARG; }
+    if (L >= 0xFFFFFFFFull) { set_error("tracs_distance_tree_bootstrap: too many columns"); return TRACS_E_ARG; }
+    StageClock clock;
+    int rc;
+    TreeEdges t, rep_t;
+    const char *const *names = h->name_ptr.data();
+    PanelWalk walk(a, 1, n, 2147483647, 0);
+    DeviceBuffer d_state;
+    if ((rc = tree_of_alignment(a, n, names, 0, walk, d_state, clock, nullptr, t))) return rc;
+    std::vector<uint32_t> support(t.ne, 0xFFFFFFFFu);
+    if (n >= 4) {                                                          // (else: no internal edge, nothing to label)
+        for (size_t e = 0; e < t.ne; e++) if (t.child[e] >= n) support[e] = 0;
+        std::vector<uint64_t> differs((L + 63) / 64 + 1, 0);
+        size_t V = 0;
+        AlignmentOwner var;
+        DeviceBuffer d_bits, d_woff, d_w;
+        if (L && (rc = site_census(a, nullptr, differs.data(), &V, nullptr))) return rc;
+        if (V) {
+            tracs_alignment *sel = nullptr;
+            if ((rc = select_sites(a, differs.data(), L, UINT32_MAX, &sel, nullptr, nullptr, nullptr, false))) return rc;
+            var.reset(sel);
+            const size_t words = (L + 31) / 32;
+            std::vector<unsigned> bits(words), woff(words);
+            unsigned run = 0;
+            for (size_t w = 0; w < words; w++) {
+                bits[w] = (unsigned)(differs[w >> 1] >> (32 * (w & 1)));
+                woff[w] = run;
+                run += (unsigned)__builtin_popcount(bits[w]);
+            }
+            if ((rc = d_bits.upload(bits.data(), words * 4)) || (rc = d_woff.upload(woff.data(), words * 4)) || (rc = d_w.alloc(V * 4))) return rc;
+        }
+        clock.mark("bootstrap: census + differing columns");
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};                               // weights + scan + gather; the three stages of a tree (+ support)
+        for (uint32_t b = 0; b < replicates; b++) {
+            if (g_sigint) return interrupted();
+            AlignmentOwner rep;
+            if (V) {
+                tracs_alignment *r = nullptr;
+                if ((rc = bootstrap_weights_launch(L, seed, b, d_bits.as<unsigned>(), d_woff.as<unsigned>(), d_w.as<uint32_t>(), V, nullptr)) ||
+                    (rc = gather_sites(var.get(), d_w.as<uint32_t>(), &r, nullptr, nullptr, true))) return rc;
+                rep.reset(r);
+            }
+            lap(clock, acc[0]);
+            if ((rc = tree_of_alignment(rep.get(), n, names, 0, walk, d_state, clock, acc + 1, rep_t))) return rc;
+            if ((rc = tracs_tree_support(n, t.parent.data(), t.child.data(), t.ne, rep_t.parent.data(), rep_t.child.data(), rep_t.ne, support.data()))) return rc;
+            if (replicate_trees_path &&
+                (rc = tracs_tree_write(names, n, rep_t.parent.data(), rep_t.child.data(), rep_t.length.data(), rep_t.ne, replicate_trees_path, ref, nullptr))) return rc;
+            lap(clock, acc[3]);
+        }
+        if (clock.on) {
+            std::fprintf(stderr, "[stage] bootstrap: %u replicates over %zu differing columns\n", (unsigned)replicates, V);
+            std::fprintf(stderr, "[stage] replicates: weights + scan + gather %.4f s\n", acc[0]);
+            std::fprintf(stderr, "[stage] replicates: dense panels + matrix load %.4f s\n", acc[1]);
+            std::fprintf(stderr, "[stage] replicates: join loop %.4f s\n", acc[2]);
+            std::fprintf(stderr, "[stage] replicates: emit, lengths, support %.4f s\n", acc[3]);
+        }
+    }
+    if ((rc = tracs_tree_write_support(names, n, t.parent.data(), t.child.data(), t.length.data(), t.ne, support.data(), replicates, path, ref,
+                                       edges_path))) return rc;
+    clock.mark("tree: emit, lengths, format, write");
+    if (n_joins) *n_joins = t.nj;
+    if (rows_written) *rows_written = edges_path ? t.ne : 0;
     if (g_sigint) return interrupted();
     return TRACS_OK;
 }

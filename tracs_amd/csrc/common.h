@@ -131,6 +131,15 @@ int pairs_min_sites(uint32_t *dist, const uint32_t *ncomp, size_t ld, size_t n, 
 int site_census(const tracs_alignment *a, uint32_t *counts, uint64_t *differs, size_t *n_differs, hipStream_t stream);
 int unpack_rows(const tracs_alignment *a, size_t first, size_t count, uint8_t *ascii, size_t stride, hipStream_t stream);
 
+// bootstrap.hip: a replicate's column counts and its planes (tracs_bootstrap_weights / tracs_alignment_gather_sites).  bits / woff: NULL
+// (weights over all L columns), or the differing-columns bitmap in 32-column words and the rank of each word's first differing column
+// (weights over the differing columns only: the form tracs_distance_tree_bootstrap uses).  empty_ok: a sum of 0 leaves *out NULL;
+// stage_s: NULL, or three wall times with the device drained (measurement)
+int bootstrap_weights_launch(size_t L, uint64_t seed, uint64_t replicate, const unsigned *bits, const unsigned *woff, uint32_t *weights,
+                             size_t weights_len, hipStream_t stream);
+int gather_sites(const tracs_alignment *src, const uint32_t *weights, tracs_alignment **out, size_t *n_out, hipStream_t stream, bool empty_ok,
+                 double *stage_s = nullptr);
+
 // pair_sites.hip: the SNP sites of listed pairs (tracs_pair_sites_count / _fill) and the rows of `tracs pair-sites`
 // (tracs_distance_pair_sites: names of the handle's samples, its kept-columns bitmap or NULL, the columns read)
 int pair_sites_write(const tracs_alignment *a, const char *const *names, const uint64_t *kept, size_t source_len, const uint32_t *rows,
@@ -175,6 +184,8 @@ enum WsSlot : int {
     WS_MSA_DIFFERS,
     // ancestors.hip: the radix sort's temporary storage
     WS_ANC_SORT_TMP,
+    // bootstrap.hip: the scanned column counts of a replicate and the first source column of every output group
+    WS_BS_OFFSETS, WS_BS_STARTS,
     WS_SLOT_COUNT
 };
 

@@ -454,20 +454,21 @@ void append_label(std::string &out, const char *name)
 
 }  // namespace
 
-extern "C" {
-
 // One Newick line appended to `path` and, with edges_path, the rows parent,child,length,MSA file (internal node n + t is "#t+1").
 // The edges are tracs_nj_edges's: a node's children are consecutive rows, in id order; the last row's parent is the top node.  The
 // writer walks the tree with a stack of its own: a caterpillar is n deep.
-int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length, size_t n_edges,
-                     const char *path, const char *ref, const char *edges_path)
+// support == NULL: tracs_tree_write, byte for byte.  Else (tracs_tree_write_support) an internal node whose edge has a support other than
+// NO_SUPPORT carries it as a decimal label, and the edge rows have a support field before ref ("NA" on leaf edges and where there is none).
+static int tree_write_body(const char *who, const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
+                           size_t n_edges, const uint32_t *support, const char *path, const char *ref, const char *edges_path)
 {
+    constexpr uint32_t NO_SUPPORT = 0xFFFFFFFFu;
     if (!path || (n && !names) || (n_edges && (!parent || !child || !length)) || (edges_path && !ref)) {
-        set_error("tracs_tree_write: NULL argument");
+        set_error(std::string(who) + ": NULL argument");
         return TRACS_E_ARG;
     }
     const size_t want = n >= 3 ? 2 * n - 3 : (n == 2 ? 1 : 0);
-    if (n_edges != want) { set_error("tracs_tree_write: a tree over n leaves has 2n - 3 edges"); return TRACS_E_ARG; }
+    if (n_edges != want) { set_error(std::string(who) + ": a tree over n leaves has 2n - 3 edges"); return TRACS_E_ARG; }
     const size_t n_nodes = n >= 3 ? 2 * n - 2 : n;
     std::string text;
     if (n == 1) append_label(text, names[0]);
@@ -483,7 +484,7 @@ int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent,
         for (size_t e = 0; e < n_edges; e++) {
             const uint32_t p = parent[e], c = child[e];
             if (p < n || p >= n_nodes || c >= n_nodes || c == p || up[c] != (size_t)-1 || (count[p] && first[p] + count[p] != e)) {
-                set_error("tracs_tree_write: the edges are not a tree in creation order");
+                set_error(std::string(who) + ": the edges are not a tree in creation order");
                 return TRACS_E_ARG;
             }
             if (!count[p]) first[p] = e;
@@ -501,14 +502,18 @@ int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent,
                 const uint32_t node = f.node;
                 stack.pop_back();
                 text.push_back(')');
-                if (node != top) { text.push_back(':'); append_length(text, length[up[node]]); }
+                if (node != top) {
+                    if (support && support[up[node]] != NO_SUPPORT) text += std::to_string(support[up[node]]);
+                    text.push_back(':');
+                    append_length(text, length[up[node]]);
+                }
                 continue;
             }
             if (f.next) text.push_back(',');
             const size_t e = first[f.node] + f.next++;
             const uint32_t c = child[e];
             if (c < n) { append_label(text, names[c]); text.push_back(':'); append_length(text, length[e]); }
-            else if (!count[c]) { set_error("tracs_tree_write: an internal node without children"); return TRACS_E_ARG; }
+            else if (!count[c]) { set_error(std::string(who) + ": an internal node without children"); return TRACS_E_ARG; }
             else { text.push_back('('); stack.push_back({c, 0}); }
         }
     }
@@ -529,6 +534,11 @@ int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent,
             node_name(parent[e]); rows.push_back(',');
             node_name(child[e]); rows.push_back(',');
             append_length(rows, length[e]); rows.push_back(',');
+            if (support) {
+                if (child[e] >= n && n >= 3 && support[e] != NO_SUPPORT) rows += std::to_string(support[e]);
+                else rows += "NA";
+                rows.push_back(',');
+            }
             rows += ref; rows.push_back('\n');
         }
         std::FILE *fh = std::fopen(edges_path, "ab");
@@ -537,6 +547,28 @@ int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent,
         if (std::fclose(fh) != 0 || !ok) { set_error(std::string("write to ") + edges_path + " failed"); return TRACS_E_OPEN; }
     }
     return TRACS_OK;
+}
+
+extern "C" {
+
+int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length, size_t n_edges,
+                     const char *path, const char *ref, const char *edges_path)
+{
+    return tree_write_body("tracs_tree_write", names, n, parent, child, length, n_edges, nullptr, path, ref, edges_path);
+}
+
+// tracs_tree_write with bootstrap support: `(A:1,B:2)87:0.5`, and the rows parent,child,length,support,ref.
+int tracs_tree_write_support(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
+                             size_t n_edges, const uint32_t *support, uint32_t replicates, const char *path, const char *ref, const char *edges_path)
+{
+    if (n_edges && !support) { set_error("tracs_tree_write_support: NULL argument"); return TRACS_E_ARG; }
+    static const uint32_t none = 0xFFFFFFFFu;
+    for (size_t e = 0; e < n_edges; e++)
+        if (support[e] != none && support[e] > replicates) {
+            set_error("tracs_tree_write_support: a support of " + std::to_string(support[e]) + " out of " + std::to_string(replicates) + " replicates");
+            return TRACS_E_ARG;
+        }
+    return tree_write_body("tracs_tree_write_support", names, n, parent, child, length, n_edges, n_edges ? support : &none, path, ref, edges_path);
 }
 
 }  // extern "C"

@@ -256,6 +256,39 @@ class Alignment:
             pass
 
 
+def bootstrap_weights(L, seed, b):
+    """torch.int32 [L] on the device (bit pattern uint32): how often bootstrap replicate b under `seed` draws each of L columns
+    (DESIGN.md 3.18); the counts sum to L.  tracs_bootstrap_weights."""
+    lib = _lib.require_gpu()
+    out = torch.empty(int(L), dtype=torch.int32, device="cuda")
+    _lib.check(lib.tracs_bootstrap_weights(int(L), int(seed), int(b), _ptr(out), _stream()))
+    return out
+
+
+def gather_sites(aln, weights):
+    """-> Alignment in which column c of `aln` is repeated weights[c] times, columns in ascending c: byte for byte what packing that
+    text gives; `aln` is left as it was.  weights: one non-negative integer per column (a device int32 / uint32 tensor is used where it
+    lies, anything else is copied).  A sum of 0 or of 2^32 and more is refused.  tracs_alignment_gather_sites."""
+    if isinstance(weights, torch.Tensor) and weights.is_cuda and weights.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)):
+        w = weights.contiguous()
+    else:
+        host = np.ascontiguousarray(weights.cpu().numpy() if isinstance(weights, torch.Tensor) else weights)
+        if host.size and (host.min() < 0 or host.max() > 0xFFFFFFFF):
+            raise ValueError("gather_sites(): a weight outside [0, 2^32)")
+        w = torch.from_numpy(host.astype(np.uint32).view(np.int32)).cuda()
+    if w.dim() != 1 or w.numel() != aln.L:
+        raise ValueError("gather_sites(): %d weights for an alignment of %d columns" % (w.numel(), aln.L))
+    h, n_out = C.c_void_p(), C.c_size_t(0)
+    _lib.check(aln._L.tracs_alignment_gather_sites(aln._h, _ptr(w), C.byref(h), C.byref(n_out), _stream()))
+    new = Alignment.__new__(Alignment)
+    new._L, new._h = aln._L, h
+    new.n, new.L = aln.n, int(n_out.value)
+    for attr in ("names", "n_first"):
+        if hasattr(aln, attr):
+            setattr(new, attr, getattr(aln, attr))
+    return new
+
+
 def notify_distances(event):
     """The next pairsnp_dense call records `event` (torch.cuda.Event) on its stream once the distances are final -- before the
     compared-sites counts are (include/tracs_hip.h, "Two streams")."""

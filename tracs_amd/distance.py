@@ -44,6 +44,7 @@ ANCESTORS_HEADER = "sample,date,ancestor,ancestor date,root,generation,MSA file\
 HISTOGRAM_HEADER = "column,distance,within,between,ungrouped,MSA file\n"
 
 TREE_EDGES_HEADER = "parent,child,length,MSA file\n"
+TREE_EDGES_SUPPORT_HEADER = "parent,child,length,support,MSA file\n"         # with --bootstrap
 
 TREE_DISTANCES = {"snp": 0, "per-site": 1}
 
@@ -133,6 +134,20 @@ def distance_parser(parser):
                      help="With --tree: also write the tree's 2n - 3 edges as parent,child,length,MSA file, in the order they were "
                           "made; internal nodes are named #1, #2, ... by join number, the last one (#(n-2)) joins the remaining three.  "
                           "Sample names are written as they are, as in the other outputs (Newick quotes them)")
+    snp.add_argument("--bootstrap", dest="bootstrap", default=None, type=int, metavar="B",
+                     help="With --tree: B >= 1 bootstrap replicates, resampled and built on the GPU.  A replicate draws as many columns "
+                          "as the run compares, with replacement, and goes through the same distances and the same neighbour joining.  "
+                          "Every internal node of the tree in -o is labelled with the NUMBER of replicates, 0 ... B (a count out of B, "
+                          "not a percentage), whose tree has the same split of the samples, as in (A:1,B:2)87:0.5; --tree-edges gains a "
+                          "support column (NA on the edges to samples).  The result is reproducible bit for bit for a given input, "
+                          "rules, B and --bootstrap-seed.  Ties are broken by input order in every replicate, so a group of identical "
+                          "samples gets the same arbitrary resolution every time and shows support B: read support only on branches of "
+                          "positive length (the edge file has both columns).  Not with --tree-distance per-site.  Not in the reference.")
+    snp.add_argument("--bootstrap-seed", dest="bootstrap_seed", default=None, type=int, metavar="S",
+                     help="With --bootstrap: the seed of the draws, an integer in [0, 2^64) (default 1)")
+    snp.add_argument("--bootstrap-trees", dest="bootstrap_trees", default=None, type=str, metavar="FILE",
+                     help="With --bootstrap: also write every replicate's tree, one unlabelled Newick line each, in replicate order "
+                          "(the B lines of the first --msa file, then the next file's)")
     snp.add_argument("--histogram", dest="histogram", action="store_true", default=False,
                      help="Instead of the pairs, output how many of them have each SNP distance (and, with --filter, each filtered "
                           "SNP distance): rows column,distance,within,between,ungrouped,MSA file, one per non-empty bin.  The pairs "
@@ -388,6 +403,9 @@ def check_tree_args(args):
             raise SystemExit("tracs distance: --tree-distance needs --tree (it chooses the distances the tree is built from)")
         if args.tree_edges is not None:
             raise SystemExit("tracs distance: --tree-edges needs --tree (it lists the edges of the tree that --tree builds)")
+        for opt, value in (("--bootstrap", args.bootstrap), ("--bootstrap-seed", args.bootstrap_seed), ("--bootstrap-trees", args.bootstrap_trees)):
+            if value is not None:
+                raise SystemExit("tracs distance: %s needs --tree (it resamples the alignment that --tree builds its tree from)" % opt)
         return
     for opt, given in (("--nearest", args.nearest is not None), ("--mst", args.mst is not None),
                        ("--ancestors", args.ancestors is not None), ("--histogram", args.histogram)):
@@ -407,13 +425,32 @@ def check_tree_args(args):
         raise SystemExit("tracs distance: --tree joins the samples of one alignment and takes no --msa-db")
     if args.gpus > 1:
         raise SystemExit("tracs distance: --tree runs on one GPU; use --gpus 1")
+    if args.bootstrap is None:
+        for opt, value in (("--bootstrap-seed", args.bootstrap_seed), ("--bootstrap-trees", args.bootstrap_trees)):
+            if value is not None:
+                raise SystemExit("tracs distance: %s needs --bootstrap (it belongs to the replicates that --bootstrap draws)" % opt)
+    else:
+        if not 1 <= args.bootstrap < 2 ** 32:
+            raise SystemExit("tracs distance: --bootstrap %d: the number of replicates must be at least 1 (and below 2^32)" % args.bootstrap)
+        if args.bootstrap_seed is not None and not 0 <= args.bootstrap_seed < 2 ** 64:
+            raise SystemExit("tracs distance: --bootstrap-seed %d is outside [0, 2^64)" % args.bootstrap_seed)
+        if TREE_DISTANCES[args.tree_distance or "snp"] == 1:
+            raise SystemExit("tracs distance: --bootstrap resamples SNP distances and takes no --tree-distance per-site (a replicate's "
+                             "compared-site counts need every column, not only the differing ones)")
     check_output_paths("distance", _inputs(args), dict(_outputs(args), **{"--tree-edges": args.tree_edges}), ["--tree-edges"])
+    check_output_paths("distance", _inputs(args), dict(_outputs(args), **{"--tree-edges": args.tree_edges, "--bootstrap-trees": args.bootstrap_trees}),
+                       ["--bootstrap-trees"])
 
 
 def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
     """--tree nj for one alignment (handle.DistanceHandle.tree, tracs_distance_tree: include/tracs_hip.h): every dense panel goes into the
     distance matrix on the device, the joins run there, and one Newick line (and the edge rows) are appended by the library."""
     with _opened(msas, args, stage, rule, contigs) as h:
+        if args.bootstrap is not None:
+            joins, rows = h.tree(args.output_file, ref, edges_path=args.tree_edges, bootstrap=args.bootstrap,
+                                 seed=1 if args.bootstrap_seed is None else args.bootstrap_seed, replicate_trees=args.bootstrap_trees)
+            stage("[sum] tracs_distance_tree_bootstrap (main tree, %d replicates: %d joins, %d edge rows written)" % (args.bootstrap, joins, rows))
+            return
         joins, rows = h.tree(args.output_file, ref, per_site=TREE_DISTANCES[args.tree_distance or "snp"] == 1, edges_path=args.tree_edges)
         stage("[sum] tracs_distance_tree (dense panels, joins, tree: %d joins, %d edge rows written)" % (joins, rows))
 
@@ -822,7 +859,9 @@ def distance(args):
             out.write("" if args.tree is not None else HISTOGRAM_HEADER if args.histogram else HEADER)      # (Newick lines: no header)
         if args.tree is not None and args.tree_edges is not None:
             with open(args.tree_edges, "w") as out:
-                out.write(TREE_EDGES_HEADER)
+                out.write(TREE_EDGES_HEADER if args.bootstrap is None else TREE_EDGES_SUPPORT_HEADER)
+        if args.tree is not None and args.bootstrap_trees is not None:
+            open(args.bootstrap_trees, "w").close()
         if args.ancestors is not None and args.ancestors_out is not None:
             with open(args.ancestors_out, "w") as out:
                 out.write(ANCESTORS_HEADER)

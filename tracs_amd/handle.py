@@ -126,12 +126,25 @@ class DistanceHandle:
     def source(self):
         return source_records(self.L, "distance", self.h)
 
-    def tree(self, path, ref, per_site=False, edges_path=None):
+    def tree(self, path, ref, per_site=False, edges_path=None, bootstrap=0, seed=1, replicate_trees=None):
         """The neighbour-joining tree of the handle's samples (tracs_distance_tree): one Newick line appended to `path`, the edge rows
-        to edges_path.  -> (joins, edge rows written)"""
+        to edges_path.  bootstrap = B > 0 (tracs_distance_tree_bootstrap): B bootstrap replicates under `seed`; the internal nodes are
+        labelled with the number of replicates that have their split, the edge rows gain a support field, and replicate_trees receives
+        each replicate's Newick line.  -> (joins, edge rows written)"""
         joins, rows = C.c_uint64(0), C.c_uint64(0)
-        _lib.check(self.L.tracs_distance_tree(self.h, int(bool(per_site)), os.fsencode(path), ref.encode(),
-                                              os.fsencode(edges_path) if edges_path is not None else None, C.byref(joins), C.byref(rows)))
+        enc = lambda p: os.fsencode(p) if p is not None else None         # noqa: E731
+        if not bootstrap:
+            if replicate_trees is not None:
+                raise ValueError("tree(): replicate_trees needs bootstrap > 0")
+            _lib.check(self.L.tracs_distance_tree(self.h, int(bool(per_site)), os.fsencode(path), ref.encode(), enc(edges_path),
+                                                  C.byref(joins), C.byref(rows)))
+            return joins.value, rows.value
+        if per_site:
+            raise ValueError("tree(): bootstrap replicates take the SNP distance only (per_site=False)")
+        if not (1 <= int(bootstrap) < 2 ** 32) or not (0 <= int(seed) < 2 ** 64):
+            raise ValueError("tree(): bootstrap must be in [1, 2^32) and seed in [0, 2^64)")
+        _lib.check(self.L.tracs_distance_tree_bootstrap(self.h, 0, os.fsencode(path), ref.encode(), enc(edges_path), int(bootstrap), int(seed),
+                                                        enc(replicate_trees), C.byref(joins), C.byref(rows)))
         return joins.value, rows.value
 
     def alignment(self):
