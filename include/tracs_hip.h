@@ -435,6 +435,47 @@ int tracs_tree_write_support(const char *const *names, size_t n, const uint32_t 
                              size_t n_edges, const uint32_t *support, uint32_t replicates, const char *path, const char *ref,
                              const char *edges_path);
 
+/* Transfer bootstrap support (csrc/transfer.hip; what tracs_distance_tree_bootstrap_transfer runs; Lemoine et al.,
+ * Nature 2018).  Both trees as tracs_nj_edges gives them: 2n - 3 edges over the same n leaves, in creation order, two children per
+ * joined node and three at the top.  T_f: the leaves below the child of an edge f (a leaf edge: the leaf).  For an internal edge e of
+ * the main tree (child >= n), S_e = T_e and p_e = min(|S_e|, n - |S_e|) >= 2.  Against one replicate tree:
+ *     h(e, f) = |S_e| + |T_f| - 2 |S_e & T_f|;  delta = min(h, n - h);  phi(e) = the smallest delta over ALL 2n - 3 edges f of the replicate
+ * so 0 <= phi <= p_e - 1, and phi = 0 exactly when the replicate has the split.  Over B replicates Phi_e = the integer sum of phi, and
+ * the transfer support is the double 1.0 - double(Phi_e) / double(B (p_e - 1)) (the product in 64-bit integers, every step rounded to
+ * nearest, computed on the host): in [0, 1], 1 = every replicate has the split, and a function of the trees alone, bit for bit.
+ *   tracs_tree_transfer_program   host only, no recursion: the replicate as a post-order program of exactly 2n - 3 uint32 entries --
+ *                                 a leaf l is the entry l, a joined node v the entry 0x80000000 | |T_v| after its two subtrees, the
+ *                                 top node nothing; children largest subtree first (ties: lower id).  Run as "leaf: push; joined node:
+ *                                 pop two, push the sum" the stack never holds more than floor(log2 n) + 3 values; *depth <- the most
+ *                                 it holds.  Malformed edges are refused as tracs_tree_support refuses them.  n < 4: nothing, depth 0.
+ *   tracs_transfer_state_bytes    the device state of a main tree over n leaves: a bit matrix [leaf][ceil((n - 3) / 64)] of 64-bit words
+ *                                 (is the leaf in S_e), |S_e|, the sums, one program; about n^2 / 8 bytes.  0: n is too large (> 2^24).
+ *   tracs_transfer_init           the main tree into the state (the matrix is built on the host and uploaded), the sums zeroed.
+ *                                 Synchronises the stream.
+ *   tracs_transfer_add            one replicate: its program is built and uploaded, transfer_phi_kernel (one lane per internal edge of
+ *                                 the main tree, one wave per 64) adds phi to every sum.  phi: NULL, or DEVICE uint32[2n - 3] that
+ *                                 receives this replicate's phi at the internal edges (other entries are left alone).  The kernel is
+ *                                 stream-ordered.  n < 4: nothing.
+ *   tracs_transfer_emit           sum_phi (host uint64 per edge) <- Phi_e, light (host uint32 per edge) <- p_e at the internal edges of
+ *                                 the main tree; entries of leaf edges are left alone; either may be NULL.  n < 4: nothing.
+ *   tracs_tree_transfer           the one-shot sibling of tracs_tree_support: host arrays, a state of its own, init + add; phi (host
+ *                                 uint32 per edge of the first tree) <- phi at its internal edges, other entries left alone.
+ *   tracs_tree_write_transfer     tracs_tree_write_support with the transfer support as the label, in the shortest decimal form that
+ *                                 reads back to the same double (as the lengths): `(A:1,B:2)0.875:0.5`; the edge rows are
+ *                                 parent,child,length,support,transfer,ref, both NA on leaf edges.  n < 4: no labels, NA.       */
+int tracs_tree_transfer_program(size_t n, const uint32_t *rep_parent, const uint32_t *rep_child, size_t n_edges, uint32_t *program,
+                                size_t *depth);
+size_t tracs_transfer_state_bytes(size_t n);
+int tracs_transfer_init(void *state, size_t n, const uint32_t *parent, const uint32_t *child, size_t n_edges, void *stream);
+int tracs_transfer_add(void *state, size_t n, const uint32_t *rep_parent, const uint32_t *rep_child, size_t rep_n_edges, uint32_t *phi,
+                       void *stream);
+int tracs_transfer_emit(void *state, size_t n, uint64_t *sum_phi, uint32_t *light);
+int tracs_tree_transfer(size_t n, const uint32_t *parent, const uint32_t *child, size_t n_edges, const uint32_t *rep_parent,
+                        const uint32_t *rep_child, size_t rep_n_edges, uint32_t *phi);
+int tracs_tree_write_transfer(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
+                              size_t n_edges, const uint32_t *support, const uint64_t *sum_phi, const uint32_t *light, uint32_t replicates,
+                              const char *path, const char *ref, const char *edges_path);
+
 /* Histogram of pair values over dense panels (csrc/histogram.hip; what tracs_distance_histogram runs).  The state is
  * a device buffer of tracs_hist_state_bytes(n_bins) bytes: per value v in [0, n_bins) three 64-bit counts -- pairs `within` a group
  * (both samples grouped, equal labels), `between` groups (both grouped, labels differ) and `ungrouped` (a sample with label < 0, or
@@ -703,6 +744,14 @@ int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const cha
  *                         order (n >= 4).  Bit-reproducible for a given (handle, replicates, seed).                             */
 int tracs_distance_tree_bootstrap(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint32_t replicates,
                                   uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins, uint64_t *rows_written);
+/*   tracs_distance_tree_bootstrap_transfer `--bootstrap-support transfer`: tracs_distance_tree_bootstrap -- the same
+ *                         arguments, the same body, the same main tree, replicates and --bootstrap-trees bytes -- with the transfer
+ *                         support beside the split count: after the main tree tracs_transfer_init, per replicate (after
+ *                         tracs_tree_support) its program and transfer_phi_kernel, after the last one tracs_transfer_emit.  The Newick
+ *                         labels are the transfer supports and the edge rows carry support,transfer (tracs_tree_write_transfer).  */
+int tracs_distance_tree_bootstrap_transfer(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path,
+                                           uint32_t replicates, uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins,
+                                           uint64_t *rows_written);
 /*   tracs_distance_histogram `--histogram` (not in the reference): tracs_distance_run's panel loop without rows.  The
  *                         pairs it would write (d <= dist) are counted by SNP distance and class (tracs_hist_*; group: HOST int32[n]
  *                         in the order of tracs_distance_name, label < 0: ungrouped; NULL: every pair ungrouped) in min(L, dist) + 1

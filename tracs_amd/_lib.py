@@ -54,6 +54,8 @@ SYMBOLS = [
     "tracs_nj_emit", "tracs_nj_edges", "tracs_tree_write",
     "tracs_bootstrap_weights", "tracs_alignment_gather_sites", "tracs_tree_support", "tracs_tree_write_support",
     "tracs_distance_tree_bootstrap",
+    "tracs_tree_transfer_program", "tracs_transfer_state_bytes", "tracs_transfer_init", "tracs_transfer_add", "tracs_transfer_emit",
+    "tracs_tree_transfer", "tracs_tree_write_transfer", "tracs_distance_tree_bootstrap_transfer",
 ]
 
 
@@ -228,6 +230,24 @@ def load():
     L.tracs_tree_write_support.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, vp, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p]
     L.tracs_distance_tree_bootstrap.restype = C.c_int
     L.tracs_distance_tree_bootstrap.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64, C.c_char_p, u64p, u64p]
+    L.tracs_distance_tree_bootstrap_transfer.restype = C.c_int
+    L.tracs_distance_tree_bootstrap_transfer.argtypes = L.tracs_distance_tree_bootstrap.argtypes
+    L.tracs_tree_transfer_program.restype = C.c_int
+    L.tracs_tree_transfer_program.argtypes = [sz, vp, vp, sz, vp, C.POINTER(sz)]
+    L.tracs_transfer_state_bytes.restype = sz
+    L.tracs_transfer_state_bytes.argtypes = [sz]
+    L.tracs_transfer_init.restype = C.c_int
+    L.tracs_transfer_init.argtypes = [vp, sz, vp, vp, sz, vp]
+    L.tracs_debug_transfer_init.restype = C.c_int
+    L.tracs_debug_transfer_init.argtypes = [vp, sz, vp, vp, sz, C.POINTER(C.c_double)]
+    L.tracs_transfer_add.restype = C.c_int
+    L.tracs_transfer_add.argtypes = [vp, sz, vp, vp, sz, vp, vp]
+    L.tracs_transfer_emit.restype = C.c_int
+    L.tracs_transfer_emit.argtypes = [vp, sz, vp, vp]
+    L.tracs_tree_transfer.restype = C.c_int
+    L.tracs_tree_transfer.argtypes = [sz, vp, vp, sz, vp, vp, sz, vp]
+    L.tracs_tree_write_transfer.restype = C.c_int
+    L.tracs_tree_write_transfer.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, vp, vp, vp, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p]
     L.tracs_distance_histogram.restype = C.c_int
     L.tracs_distance_histogram.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_char_p, C.c_char_p, u64p, u64p]
     L.tracs_hist_state_bytes.restype = sz

@@ -158,6 +158,45 @@ def tree_support(n, main_edges, replicate_edges):
     return count
 
 
+def tree_transfer(n, main_edges, replicate_edges):
+    """Transfer bootstrap support (tracs_transfer_*, needs a GPU): main_edges = (parent, child[, length]) of a tree over
+    the leaves 0 .. n - 1 as neighbor_joining returns it, replicate_edges = a list of such trees over the same leaves.  -> (sum_phi
+    uint64, light uint32, transfer float64), one entry per edge of the main tree: for an internal edge the sum over the replicates of
+    the transfer distance phi, the size p of its lighter side, and 1 - sum_phi / (B (p - 1)) in [0, 1]; 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFF
+    and NaN on leaf edges, and everywhere when n < 4 or there is no replicate."""
+    import torch
+    L = _lib.require_gpu()
+    n = int(n)
+    parent, child = (np.ascontiguousarray(x, np.uint32) for x in main_edges[:2])
+    if parent.shape != child.shape or parent.ndim != 1:
+        raise ValueError("tree_transfer(): parent and child must be two arrays of one length")
+    reps = []
+    for rep in replicate_edges:
+        rp, rc = (np.ascontiguousarray(x, np.uint32) for x in rep[:2])
+        if rp.shape != rc.shape or rp.ndim != 1:
+            raise ValueError("tree_transfer(): parent and child must be two arrays of one length")
+        reps.append((rp, rc))
+    sum_phi = np.full(len(parent), 0xFFFFFFFFFFFFFFFF, np.uint64)
+    light = np.full(len(parent), 0xFFFFFFFF, np.uint32)
+    transfer = np.full(len(parent), np.nan, np.float64)
+    if n < 4 or not reps:
+        return sum_phi, light, transfer
+    nbytes = L.tracs_transfer_state_bytes(n)
+    if not nbytes:
+        raise ValueError("tree_transfer(): too many leaves")
+    state = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    _lib.check(L.tracs_transfer_init(state.data_ptr(), n, parent.ctypes.data, child.ctypes.data, len(parent), stream))
+    for rp, rc in reps:
+        _lib.check(L.tracs_transfer_add(state.data_ptr(), n, rp.ctypes.data, rc.ctypes.data, len(rp), None, stream))
+    torch.cuda.synchronize()
+    _lib.check(L.tracs_transfer_emit(state.data_ptr(), n, sum_phi.ctypes.data, light.ctypes.data))
+    inner = child >= n
+    den = np.uint64(len(reps)) * (light[inner].astype(np.uint64) - np.uint64(1))
+    transfer[inner] = 1.0 - sum_phi[inner].astype(np.float64) / den.astype(np.float64)
+    return sum_phi, light, transfer
+
+
 def pair_sites(fasta, pairs, filter=False, sites=None, info=None, max_sample_n_share=None, max_n_share=None):
     """The SNP sites behind listed pairs -> (offsets int64[m + 1], site uint32[], info uint32[], names): pair t's
     entries are [offsets[t], offsets[t + 1]), ascending by site; site indexes the compared alignment (the kept columns; info receives

@@ -262,6 +262,35 @@ int gather_sites(const tracs_alignment *src, const uint32_t *weights, tracs_alig
     return TRACS_OK;
 }
 
+// Host only.  below[v]: the leaves under internal node v as a bitset of ceil(n / 64) words, built bottom-up in the edges' creation order
+// (a child's edges come before the edge that hangs it under its parent).  below == NULL: the edges are checked only; kids != NULL:
+// <- the number of children of every node (transfer.hip, which wants two per joined node and three at the top).
+int tree_bitsets(const char *who, size_t n, const uint32_t *parent, const uint32_t *child, size_t n_edges, std::vector<uint64_t> *below,
+                 std::vector<uint32_t> *kids)
+{
+    const size_t W = (n + 63) / 64, n_nodes = 2 * n - 2;
+    if (n_edges != 2 * n - 3) { set_error(std::string(who) + ": a tree over n leaves has 2n - 3 edges"); return TRACS_E_ARG; }
+    if (below) below->assign((n_nodes - n) * W, 0);
+    if (kids) kids->assign(n_nodes, 0);
+    std::vector<uint8_t> open(n_nodes, 0), hung(n_nodes, 0);              // open: has children; hung: is somebody's child
+    for (size_t e = 0; e < n_edges; e++) {
+        const uint32_t p = parent[e], c = child[e];
+        if (p < n || p >= n_nodes || c >= n_nodes || c == p || hung[c] || hung[p] || (c >= n && !open[c])) {
+            set_error(std::string(who) + ": the edges are not a tree in creation order");
+            return TRACS_E_ARG;
+        }
+        if (below) {
+            uint64_t *bp = &(*below)[(p - n) * W];
+            if (c < n) bp[c >> 6] |= 1ull << (c & 63);
+            else { const uint64_t *bc = &(*below)[(c - n) * W]; for (size_t w = 0; w < W; w++) bp[w] |= bc[w]; }
+        }
+        if (kids) (*kids)[p]++;
+        open[p] = 1;
+        hung[c] = 1;
+    }
+    return TRACS_OK;
+}
+
 }  // namespace tracs
 
 using namespace tracs;
@@ -316,31 +345,8 @@ int tracs_debug_bootstrap_replicate(const tracs_alignment *var, size_t L, const 
     return done(gather_sites(var, d + 2 * words, out, n_out, nullptr, true, seconds + 1));
 }
 
-// Host only.  below[v]: the leaves under internal node v as a bitset of ceil(n / 64) words, built bottom-up in the edges' creation order
-// (a child's edges come before the edge that hangs it under its parent).  A split is the bitset of an internal edge's child, turned to
-// the side without leaf 0.  The replicate's splits are sorted by a hash; a main split counts when one of the candidates under its hash
-// has the same words.
-static int tree_bitsets(const char *who, size_t n, const uint32_t *parent, const uint32_t *child, size_t n_edges, std::vector<uint64_t> &below)
-{
-    const size_t W = (n + 63) / 64, n_nodes = 2 * n - 2;
-    if (n_edges != 2 * n - 3) { set_error(std::string(who) + ": a tree over n leaves has 2n - 3 edges"); return TRACS_E_ARG; }
-    below.assign((n_nodes - n) * W, 0);
-    std::vector<uint8_t> open(n_nodes, 0), hung(n_nodes, 0);              // open: has children; hung: is somebody's child
-    for (size_t e = 0; e < n_edges; e++) {
-        const uint32_t p = parent[e], c = child[e];
-        if (p < n || p >= n_nodes || c >= n_nodes || c == p || hung[c] || hung[p] || (c >= n && !open[c])) {
-            set_error(std::string(who) + ": the edges are not a tree in creation order");
-            return TRACS_E_ARG;
-        }
-        uint64_t *bp = &below[(p - n) * W];
-        if (c < n) bp[c >> 6] |= 1ull << (c & 63);
-        else { const uint64_t *bc = &below[(c - n) * W]; for (size_t w = 0; w < W; w++) bp[w] |= bc[w]; }
-        open[p] = 1;
-        hung[c] = 1;
-    }
-    return TRACS_OK;
-}
-
+// Host only.  A split is the bitset of an internal edge's child (tree_bitsets), turned to the side without leaf 0.  The replicate's
+// splits are sorted by a hash; a main split counts when one of the candidates under its hash has the same words.
 static uint64_t split_of(size_t n, const uint64_t *below, uint64_t *out)
 {
     const size_t W = (n + 63) / 64;
@@ -365,8 +371,8 @@ int tracs_tree_support(size_t n, const uint32_t *parent, const uint32_t *child, 
     const size_t W = (n + 63) / 64;
     std::vector<uint64_t> below_m, below_r;
     int rc;
-    if ((rc = tree_bitsets("tracs_tree_support", n, parent, child, n_edges, below_m))) return rc;
-    if ((rc = tree_bitsets("tracs_tree_support", n, rep_parent, rep_child, rep_n_edges, below_r))) return rc;
+    if ((rc = tree_bitsets("tracs_tree_support", n, parent, child, n_edges, &below_m, nullptr))) return rc;
+    if ((rc = tree_bitsets("tracs_tree_support", n, rep_parent, rep_child, rep_n_edges, &below_r, nullptr))) return rc;
     // the replicate's splits, normalised in place of its bitsets (every internal node but the top one hangs on an internal edge)
     struct Key { uint64_t hash; size_t row; };
     std::vector<Key> keys;

@@ -1307,20 +1307,23 @@ int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const cha
 // samples differ are selected once (census bitmap -> tracs_alignment_select_sites: the other columns add nothing to any replicate's
 // distances), and per replicate: the draws counted over those columns, the replicate gathered into a handle of its own, the same
 // panel walk / load / joins / lengths, the splits compared, the handle freed.  One state, one walk, one replicate alive at a time.
-int tracs_distance_tree_bootstrap(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint32_t replicates,
-                                  uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins, uint64_t *rows_written)
+// transfer (tracs_distance_tree_bootstrap_transfer): the main tree's membership matrix goes into a transfer state once,
+// every replicate's program is built and run against it after its splits were compared, and the sums label the tree.
+static int tree_bootstrap_body(const std::string &who, bool transfer, tracs_distance *h, int kind, const char *path, const char *ref,
+                               const char *edges_path, uint32_t replicates, uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins,
+                               uint64_t *rows_written)
 {
     if (n_joins) *n_joins = 0;
     if (rows_written) *rows_written = 0;
-    if (!h || !h->a || !path || !ref) { set_error("tracs_distance_tree_bootstrap: NULL argument"); return TRACS_E_ARG; }
-    if (kind != 0) { set_error("tracs_distance_tree_bootstrap: bootstrap replicates take the SNP distance (kind 0) only"); return TRACS_E_ARG; }
-    if (replicates < 1) { set_error("tracs_distance_tree_bootstrap: at least one replicate"); return TRACS_E_ARG; }
-    if (h->n_fasta != 1) { set_error("tracs_distance_tree_bootstrap: a tree joins the samples of one alignment"); return TRACS_E_ARG; }
+    if (!h || !h->a || !path || !ref) { set_error(who + ": NULL argument"); return TRACS_E_ARG; }
+    if (kind != 0) { set_error(who + ": bootstrap replicates take the SNP distance (kind 0) only"); return TRACS_E_ARG; }
+    if (replicates < 1) { set_error(who + ": at least one replicate"); return TRACS_E_ARG; }
+    if (h->n_fasta != 1) { set_error(who + ": a tree joins the samples of one alignment"); return TRACS_E_ARG; }
     SigintScope sigint;
     tracs_alignment *a = h->a;
     const size_t n = a->n, L = a->L;
-    if (n && !tracs_nj_state_bytes(n)) { set_error("tracs_distance_tree_bootstrap: too many samples for one distance matrix"); return TRACS_E_ARG; }
-    if (L >= 0xFFFFFFFFull) { set_error("tracs_distance_tree_bootstrap: too many columns"); return TRACS_E_ARG; }
+    if (n && !tracs_nj_state_bytes(n)) { set_error(who + ": too many samples for one distance matrix"); return TRACS_E_ARG; }
+    if (L >= 0xFFFFFFFFull) { set_error(who + ": too many columns"); return TRACS_E_ARG; }
     StageClock clock;
     int rc;
     TreeEdges t, rep_t;
@@ -1329,8 +1332,16 @@ int tracs_distance_tree_bootstrap(tracs_distance *h, int kind, const char *path,
     DeviceBuffer d_state;
     if ((rc = tree_of_alignment(a, n, names, 0, walk, d_state, clock, nullptr, t))) return rc;
     std::vector<uint32_t> support(t.ne, 0xFFFFFFFFu);
+    std::vector<uint64_t> sum_phi(transfer ? t.ne : 0, 0);
+    std::vector<uint32_t> light(transfer ? t.ne : 0, 0), program(transfer && n >= 4 ? 2 * n - 3 : 0);
+    DeviceBuffer d_transfer;
     if (n >= 4) {                                                          // (else: no internal edge, nothing to label)
         for (size_t e = 0; e < t.ne; e++) if (t.child[e] >= n) support[e] = 0;
+        if (transfer) {
+            if ((rc = d_transfer.alloc(tracs_transfer_state_bytes(n))) ||
+                (rc = tracs_transfer_init(d_transfer.ptr, n, t.parent.data(), t.child.data(), t.ne, nullptr))) return rc;
+            clock.mark("transfer: membership matrix");
+        }
         std::vector<uint64_t> differs((L + 63) / 64 + 1, 0);
         size_t V = 0;
         AlignmentOwner var;
@@ -1351,7 +1362,8 @@ int tracs_distance_tree_bootstrap(tracs_distance *h, int kind, const char *path,
             if ((rc = d_bits.upload(bits.data(), words * 4)) || (rc = d_woff.upload(woff.data(), words * 4)) || (rc = d_w.alloc(V * 4))) return rc;
         }
         clock.mark("bootstrap: census + differing columns");
-        double acc[4] = {0.0, 0.0, 0.0, 0.0};                               // weights + scan + gather; the three stages of a tree (+ support)
+        double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};                     // weights + scan + gather; the three stages of a tree (+ support);
+                                                                            // transfer: the program on the host, the kernel
         for (uint32_t b = 0; b < replicates; b++) {
             if (g_sigint) return interrupted();
             AlignmentOwner rep;
@@ -1367,22 +1379,51 @@ int tracs_distance_tree_bootstrap(tracs_distance *h, int kind, const char *path,
             if (replicate_trees_path &&
                 (rc = tracs_tree_write(names, n, rep_t.parent.data(), rep_t.child.data(), rep_t.length.data(), rep_t.ne, replicate_trees_path, ref, nullptr))) return rc;
             lap(clock, acc[3]);
+            if (transfer) {
+                size_t depth = 0;
+                if ((rc = tracs_tree_transfer_program(n, rep_t.parent.data(), rep_t.child.data(), rep_t.ne, program.data(), &depth))) return rc;
+                lap(clock, acc[4]);
+                if ((rc = transfer_add_program(d_transfer.ptr, n, program.data(), depth, nullptr, nullptr))) return rc;
+                lap(clock, acc[5]);
+            }
         }
+        if (transfer && (rc = tracs_transfer_emit(d_transfer.ptr, n, sum_phi.data(), light.data()))) return rc;
         if (clock.on) {
             std::fprintf(stderr, "[stage] bootstrap: %u replicates over %zu differing columns\n", (unsigned)replicates, V);
             std::fprintf(stderr, "[stage] replicates: weights + scan + gather %.4f s\n", acc[0]);
             std::fprintf(stderr, "[stage] replicates: dense panels + matrix load %.4f s\n", acc[1]);
             std::fprintf(stderr, "[stage] replicates: join loop %.4f s\n", acc[2]);
             std::fprintf(stderr, "[stage] replicates: emit, lengths, support %.4f s\n", acc[3]);
+            if (transfer)
+                std::fprintf(stderr, "[stage] replicates: transfer distances %.4f s (program %.4f s, kernel %.4f s)\n", acc[4] + acc[5], acc[4], acc[5]);
         }
     }
-    if ((rc = tracs_tree_write_support(names, n, t.parent.data(), t.child.data(), t.length.data(), t.ne, support.data(), replicates, path, ref,
-                                       edges_path))) return rc;
+    if (transfer)
+        rc = tracs_tree_write_transfer(names, n, t.parent.data(), t.child.data(), t.length.data(), t.ne, support.data(), sum_phi.data(), light.data(),
+                                       replicates, path, ref, edges_path);
+    else
+        rc = tracs_tree_write_support(names, n, t.parent.data(), t.child.data(), t.length.data(), t.ne, support.data(), replicates, path, ref, edges_path);
+    if (rc) return rc;
     clock.mark("tree: emit, lengths, format, write");
     if (n_joins) *n_joins = t.nj;
     if (rows_written) *rows_written = edges_path ? t.ne : 0;
     if (g_sigint) return interrupted();
     return TRACS_OK;
+}
+
+int tracs_distance_tree_bootstrap(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint32_t replicates,
+                                  uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins, uint64_t *rows_written)
+{
+    return tree_bootstrap_body("tracs_distance_tree_bootstrap", false, h, kind, path, ref, edges_path, replicates, seed, replicate_trees_path,
+                               n_joins, rows_written);
+}
+
+int tracs_distance_tree_bootstrap_transfer(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path,
+                                           uint32_t replicates, uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins,
+                                           uint64_t *rows_written)
+{
+    return tree_bootstrap_body("tracs_distance_tree_bootstrap_transfer", true, h, kind, path, ref, edges_path, replicates, seed,
+                               replicate_trees_path, n_joins, rows_written);
 }
 
 // `tracs distance --histogram` for one alignment (include/tracs_hip.h): the panel walk of tracs_distance_run with

@@ -140,6 +140,15 @@ int bootstrap_weights_launch(size_t L, uint64_t seed, uint64_t replicate, const 
 int gather_sites(const tracs_alignment *src, const uint32_t *weights, tracs_alignment **out, size_t *n_out, hipStream_t stream, bool empty_ok,
                  double *stage_s = nullptr);
 
+// bootstrap.hip, host only: a tree's edges checked (2n - 3 of them, creation order) and, with below != NULL, the leaves under every internal
+// node v as a bitset of ceil(n / 64) words at (*below)[(v - n) * W]; kids != NULL: <- every node's number of children
+int tree_bitsets(const char *who, size_t n, const uint32_t *parent, const uint32_t *child, size_t n_edges, std::vector<uint64_t> *below,
+                 std::vector<uint32_t> *kids);
+
+// transfer.hip: one replicate's program (tracs_tree_transfer_program's output, `depth` as it returned it) run against the state's main
+// tree: tracs_transfer_add without the program build (tracs_distance_tree_bootstrap_transfer times the two apart)
+int transfer_add_program(void *state, size_t n, const uint32_t *program, size_t depth, uint32_t *phi, hipStream_t stream);
+
 // pair_sites.hip: the SNP sites of listed pairs (tracs_pair_sites_count / _fill) and the rows of `tracs pair-sites`
 // (tracs_distance_pair_sites: names of the handle's samples, its kept-columns bitmap or NULL, the columns read)
 int pair_sites_write(const tracs_alignment *a, const char *const *names, const uint64_t *kept, size_t source_len, const uint32_t *rows,

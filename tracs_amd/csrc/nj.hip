@@ -459,8 +459,11 @@ void append_label(std::string &out, const char *name)
 // writer walks the tree with a stack of its own: a caterpillar is n deep.
 // support == NULL: tracs_tree_write, byte for byte.  Else (tracs_tree_write_support) an internal node whose edge has a support other than
 // NO_SUPPORT carries it as a decimal label, and the edge rows have a support field before ref ("NA" on leaf edges and where there is none).
+// transfer != NULL (tracs_tree_write_transfer, with support): the label is the edge's transfer support instead, written like a length
+// (NaN: none), and the edge rows have a transfer field behind the support field.
 static int tree_write_body(const char *who, const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
-                           size_t n_edges, const uint32_t *support, const char *path, const char *ref, const char *edges_path)
+                           size_t n_edges, const uint32_t *support, const double *transfer, const char *path, const char *ref,
+                           const char *edges_path)
 {
     constexpr uint32_t NO_SUPPORT = 0xFFFFFFFFu;
     if (!path || (n && !names) || (n_edges && (!parent || !child || !length)) || (edges_path && !ref)) {
@@ -503,7 +506,8 @@ static int tree_write_body(const char *who, const char *const *names, size_t n, 
                 stack.pop_back();
                 text.push_back(')');
                 if (node != top) {
-                    if (support && support[up[node]] != NO_SUPPORT) text += std::to_string(support[up[node]]);
+                    if (transfer) { if (!std::isnan(transfer[up[node]])) append_length(text, transfer[up[node]]); }
+                    else if (support && support[up[node]] != NO_SUPPORT) text += std::to_string(support[up[node]]);
                     text.push_back(':');
                     append_length(text, length[up[node]]);
                 }
@@ -539,6 +543,11 @@ static int tree_write_body(const char *who, const char *const *names, size_t n, 
                 else rows += "NA";
                 rows.push_back(',');
             }
+            if (transfer) {
+                if (child[e] >= n && n >= 3 && !std::isnan(transfer[e])) append_length(rows, transfer[e]);
+                else rows += "NA";
+                rows.push_back(',');
+            }
             rows += ref; rows.push_back('\n');
         }
         std::FILE *fh = std::fopen(edges_path, "ab");
@@ -554,7 +563,7 @@ extern "C" {
 int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length, size_t n_edges,
                      const char *path, const char *ref, const char *edges_path)
 {
-    return tree_write_body("tracs_tree_write", names, n, parent, child, length, n_edges, nullptr, path, ref, edges_path);
+    return tree_write_body("tracs_tree_write", names, n, parent, child, length, n_edges, nullptr, nullptr, path, ref, edges_path);
 }
 
 // tracs_tree_write with bootstrap support: `(A:1,B:2)87:0.5`, and the rows parent,child,length,support,ref.
@@ -568,7 +577,36 @@ int tracs_tree_write_support(const char *const *names, size_t n, const uint32_t 
             set_error("tracs_tree_write_support: a support of " + std::to_string(support[e]) + " out of " + std::to_string(replicates) + " replicates");
             return TRACS_E_ARG;
         }
-    return tree_write_body("tracs_tree_write_support", names, n, parent, child, length, n_edges, n_edges ? support : &none, path, ref, edges_path);
+    return tree_write_body("tracs_tree_write_support", names, n, parent, child, length, n_edges, n_edges ? support : &none, nullptr, path, ref, edges_path);
+}
+
+// tracs_tree_write_support with the transfer support as the label: x_e = 1 - Phi_e / (B (p_e - 1)), one rounding per
+// operation, on the host; `(A:1,B:2)0.875:0.5`, and the rows parent,child,length,support,transfer,ref.
+int tracs_tree_write_transfer(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
+                              size_t n_edges, const uint32_t *support, const uint64_t *sum_phi, const uint32_t *light, uint32_t replicates,
+                              const char *path, const char *ref, const char *edges_path)
+{
+    if (n_edges && (!support || !sum_phi || !light || !child)) { set_error("tracs_tree_write_transfer: NULL argument"); return TRACS_E_ARG; }
+    if (replicates < 1) { set_error("tracs_tree_write_transfer: at least one replicate"); return TRACS_E_ARG; }
+    static const uint32_t none = 0xFFFFFFFFu;
+    std::vector<double> x(std::max<size_t>(n_edges, 1), std::nan(""));
+    for (size_t e = 0; e < n_edges; e++) {
+        if (support[e] != none && support[e] > replicates) {
+            set_error("tracs_tree_write_transfer: a support of " + std::to_string(support[e]) + " out of " + std::to_string(replicates) + " replicates");
+            return TRACS_E_ARG;
+        }
+        if (n < 4 || child[e] < n) continue;
+        const uint64_t den = (uint64_t)replicates * (uint64_t)(light[e] - 1u);
+        if (light[e] < 2 || light[e] > n / 2 || sum_phi[e] > den) {
+            set_error("tracs_tree_write_transfer: edge " + std::to_string(e) + " has the sum " + std::to_string(sum_phi[e]) + " over " +
+                      std::to_string(replicates) + " replicates with a lighter side of " + std::to_string(light[e]) + " leaves");
+            return TRACS_E_ARG;
+        }
+        const double q = (double)sum_phi[e] / (double)den;
+        x[e] = 1.0 - q;
+    }
+    return tree_write_body("tracs_tree_write_transfer", names, n, parent, child, length, n_edges, n_edges ? support : &none, x.data(), path, ref,
+                           edges_path);
 }
 
 }  // extern "C"

@@ -45,6 +45,7 @@ HISTOGRAM_HEADER = "column,distance,within,between,ungrouped,MSA file\n"
 
 TREE_EDGES_HEADER = "parent,child,length,MSA file\n"
 TREE_EDGES_SUPPORT_HEADER = "parent,child,length,support,MSA file\n"         # with --bootstrap
+TREE_EDGES_TRANSFER_HEADER = "parent,child,length,support,transfer,MSA file\n"      # with --bootstrap-support transfer
 
 TREE_DISTANCES = {"snp": 0, "per-site": 1}
 
@@ -143,6 +144,17 @@ def distance_parser(parser):
                           "rules, B and --bootstrap-seed.  Ties are broken by input order in every replicate, so a group of identical "
                           "samples gets the same arbitrary resolution every time and shows support B: read support only on branches of "
                           "positive length (the edge file has both columns).  Not with --tree-distance per-site.  Not in the reference.")
+    snp.add_argument("--bootstrap-support", dest="bootstrap_support", default=None, choices=["split", "transfer"],
+                     help="With --bootstrap: what labels the internal nodes.  split (the default): the count described above.  transfer: "
+                          "the transfer bootstrap expectation (Lemoine et al. 2018), computed on the GPU.  For a branch and one replicate "
+                          "it takes the smallest number of samples that would have to move to turn the branch into some branch of the "
+                          "replicate's tree, averages that over the replicates and divides it by the most it can be, the size of the "
+                          "branch's lighter side minus one; the label is 1 minus that.  It is a number in [0, 1], not a count: 1 means "
+                          "every replicate has the split, and a deep branch that loses one unstable sample in every replicate stays near "
+                          "1 where its count is 0.  --tree-edges then has the columns parent,child,length,support,transfer,MSA file (the "
+                          "count and the transfer support, both NA on the edges to samples); --bootstrap-trees is unchanged.  As with the "
+                          "count, a group of identical samples is resolved the same way in every replicate and shows 1: read the transfer "
+                          "support on branches of positive length only.  Not in the reference.")
     snp.add_argument("--bootstrap-seed", dest="bootstrap_seed", default=None, type=int, metavar="S",
                      help="With --bootstrap: the seed of the draws, an integer in [0, 2^64) (default 1)")
     snp.add_argument("--bootstrap-trees", dest="bootstrap_trees", default=None, type=str, metavar="FILE",
@@ -406,6 +418,9 @@ def check_tree_args(args):
         for opt, value in (("--bootstrap", args.bootstrap), ("--bootstrap-seed", args.bootstrap_seed), ("--bootstrap-trees", args.bootstrap_trees)):
             if value is not None:
                 raise SystemExit("tracs distance: %s needs --tree (it resamples the alignment that --tree builds its tree from)" % opt)
+        if args.bootstrap_support is not None:
+            raise SystemExit("tracs distance: --bootstrap-support needs --bootstrap, which needs --tree (it chooses what the replicates' trees "
+                             "say about the branches of the tree that --tree builds)")
         return
     for opt, given in (("--nearest", args.nearest is not None), ("--mst", args.mst is not None),
                        ("--ancestors", args.ancestors is not None), ("--histogram", args.histogram)):
@@ -426,7 +441,8 @@ def check_tree_args(args):
     if args.gpus > 1:
         raise SystemExit("tracs distance: --tree runs on one GPU; use --gpus 1")
     if args.bootstrap is None:
-        for opt, value in (("--bootstrap-seed", args.bootstrap_seed), ("--bootstrap-trees", args.bootstrap_trees)):
+        for opt, value in (("--bootstrap-seed", args.bootstrap_seed), ("--bootstrap-trees", args.bootstrap_trees),
+                           ("--bootstrap-support", args.bootstrap_support)):
             if value is not None:
                 raise SystemExit("tracs distance: %s needs --bootstrap (it belongs to the replicates that --bootstrap draws)" % opt)
     else:
@@ -448,8 +464,10 @@ def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
     with _opened(msas, args, stage, rule, contigs) as h:
         if args.bootstrap is not None:
             joins, rows = h.tree(args.output_file, ref, edges_path=args.tree_edges, bootstrap=args.bootstrap,
-                                 seed=1 if args.bootstrap_seed is None else args.bootstrap_seed, replicate_trees=args.bootstrap_trees)
-            stage("[sum] tracs_distance_tree_bootstrap (main tree, %d replicates: %d joins, %d edge rows written)" % (args.bootstrap, joins, rows))
+                                 seed=1 if args.bootstrap_seed is None else args.bootstrap_seed, replicate_trees=args.bootstrap_trees,
+                                 support=args.bootstrap_support or "split")
+            stage("[sum] tracs_distance_tree_bootstrap%s (main tree, %d replicates: %d joins, %d edge rows written)"
+                  % ("_transfer" if args.bootstrap_support == "transfer" else "", args.bootstrap, joins, rows))
             return
         joins, rows = h.tree(args.output_file, ref, per_site=TREE_DISTANCES[args.tree_distance or "snp"] == 1, edges_path=args.tree_edges)
         stage("[sum] tracs_distance_tree (dense panels, joins, tree: %d joins, %d edge rows written)" % (joins, rows))
@@ -859,7 +877,8 @@ def distance(args):
             out.write("" if args.tree is not None else HISTOGRAM_HEADER if args.histogram else HEADER)      # (Newick lines: no header)
         if args.tree is not None and args.tree_edges is not None:
             with open(args.tree_edges, "w") as out:
-                out.write(TREE_EDGES_HEADER if args.bootstrap is None else TREE_EDGES_SUPPORT_HEADER)
+                out.write(TREE_EDGES_HEADER if args.bootstrap is None else
+                          TREE_EDGES_TRANSFER_HEADER if args.bootstrap_support == "transfer" else TREE_EDGES_SUPPORT_HEADER)
         if args.tree is not None and args.bootstrap_trees is not None:
             open(args.bootstrap_trees, "w").close()
         if args.ancestors is not None and args.ancestors_out is not None:

@@ -126,16 +126,21 @@ class DistanceHandle:
     def source(self):
         return source_records(self.L, "distance", self.h)
 
-    def tree(self, path, ref, per_site=False, edges_path=None, bootstrap=0, seed=1, replicate_trees=None):
+    def tree(self, path, ref, per_site=False, edges_path=None, bootstrap=0, seed=1, replicate_trees=None, support="split"):
         """The neighbour-joining tree of the handle's samples (tracs_distance_tree): one Newick line appended to `path`, the edge rows
         to edges_path.  bootstrap = B > 0 (tracs_distance_tree_bootstrap): B bootstrap replicates under `seed`; the internal nodes are
         labelled with the number of replicates that have their split, the edge rows gain a support field, and replicate_trees receives
-        each replicate's Newick line.  -> (joins, edge rows written)"""
+        each replicate's Newick line.  support="transfer" (tracs_distance_tree_bootstrap_transfer): the labels are the transfer
+        supports, doubles in [0, 1], and the edge rows carry both the count and the transfer support.  -> (joins, edge rows written)"""
+        if support not in ("split", "transfer"):
+            raise ValueError("tree(): support is 'split' or 'transfer'")
         joins, rows = C.c_uint64(0), C.c_uint64(0)
         enc = lambda p: os.fsencode(p) if p is not None else None         # noqa: E731
         if not bootstrap:
             if replicate_trees is not None:
                 raise ValueError("tree(): replicate_trees needs bootstrap > 0")
+            if support != "split":
+                raise ValueError("tree(): support='transfer' needs bootstrap > 0")
             _lib.check(self.L.tracs_distance_tree(self.h, int(bool(per_site)), os.fsencode(path), ref.encode(), enc(edges_path),
                                                   C.byref(joins), C.byref(rows)))
             return joins.value, rows.value
@@ -143,8 +148,9 @@ class DistanceHandle:
             raise ValueError("tree(): bootstrap replicates take the SNP distance only (per_site=False)")
         if not (1 <= int(bootstrap) < 2 ** 32) or not (0 <= int(seed) < 2 ** 64):
             raise ValueError("tree(): bootstrap must be in [1, 2^32) and seed in [0, 2^64)")
-        _lib.check(self.L.tracs_distance_tree_bootstrap(self.h, 0, os.fsencode(path), ref.encode(), enc(edges_path), int(bootstrap), int(seed),
-                                                        enc(replicate_trees), C.byref(joins), C.byref(rows)))
+        entry = self.L.tracs_distance_tree_bootstrap_transfer if support == "transfer" else self.L.tracs_distance_tree_bootstrap
+        _lib.check(entry(self.h, 0, os.fsencode(path), ref.encode(), enc(edges_path), int(bootstrap), int(seed), enc(replicate_trees),
+                         C.byref(joins), C.byref(rows)))
         return joins.value, rows.value
 
     def alignment(self):
