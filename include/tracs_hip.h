@@ -407,6 +407,11 @@ int tracs_nj_edges(size_t n, const uint32_t *a, const uint32_t *b, const double 
 int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
                      size_t n_edges, const char *path, const char *ref, const char *edges_path);
 
+/*   tracs_tree_write_changes  tracs_tree_write with a number of changes per edge (uint32[n_edges]): the Newick line is
+ *                        tracs_tree_write's, byte for byte; the edge rows are parent,child,length,changes,ref.                  */
+int tracs_tree_write_changes(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
+                             size_t n_edges, const uint32_t *changes, const char *path, const char *ref, const char *edges_path);
+
 /* Bootstrap support for the neighbour-joining tree (csrc/bootstrap.hip; what tracs_distance_tree_bootstrap runs).  One
  * replicate is the run on an alignment whose L columns were drawn with replacement.  All arithmetic mod 2^64:
  *     mix(x): z = x; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
@@ -534,6 +539,33 @@ int tracs_pair_sites_count(const tracs_alignment *a, const uint32_t *rows, const
                            uint64_t *total, void *stream);
 int tracs_pair_sites_fill(const tracs_alignment *a, const uint32_t *rows, const uint32_t *cols, size_t n_pairs, const int64_t *off,
                           int64_t entry_base, uint32_t *site, uint32_t *info, size_t room, int filter, void *stream);
+
+/* Every site placed on a fixed tree: small parsimony, Fitch's two passes (csrc/fitch.hip; not in the reference).  The
+ * alignment's sample i has the mask m_i(s) at site s (A = 1, C = 2, G = 4, T = 8; N = 15).  parent / child: HOST uint32[n_edges], the
+ * tree exactly as tracs_nj_edges gives it for the alignment's n samples -- 2n - 3 edges in creation order, (n + t, a_t), (n + t, b_t)
+ * with a_t < b_t for join t = 0 .. n - 4, then the top node T = 2n - 3 with x < y < z (n = 2: the edge (0, 1); n = 1: none) --
+ * anything else is refused (TRACS_E_ARG) before a launch.  Per site, independently:
+ *     bottom-up, ascending node id: S_i = m_i for a leaf; join: I = S_a & S_b, S = I if I != 0, else S_a | S_b; top node: S_xy by
+ *         the same rule, then I = S_xy & S_z, S_T = I if I != 0, else S_xy
+ *     top-down: f_T = lowbit(S_T) (A before C before G before T); the edges by descending parent id, creation order within a parent;
+ *         f_child = f_parent if f_parent & S_child != 0, else lowbit(S_child); a CHANGE is an edge with f_child != f_parent
+ *     n = 2: f_0 = lowbit(m_0 & m_1), or lowbit(m_0) where that is empty; f_1 by the child rule (the changes number d(0, 1))
+ *     minimum(s) = (the smallest |H|, H a non-empty set of bases with m_i(s) & H != 0 for every i) - 1
+ * A leaf's state lies in its mask; an N leaf copies its parent; the number of changes of a site is its parsimony length on this tree
+ * (unique); their placement is ONE most-parsimonious reconstruction among possibly several.
+ *   tracs_fitch_count  device outputs: edge_changes uint32[n_edges], site_changes uint32[L], site_minimum uint8[L], off int64[L + 1] =
+ *                      the exclusive scan of site_changes; *total (host) = off[L].  Synchronises the stream.
+ *   tracs_fitch_fill   the entries of the sites [site_begin, site_end): those of site s at site / edge / info
+ *                      [off[s] - entry_base, off[s + 1] - entry_base) (device uint32, room entries each; nothing is stored outside
+ *                      [0, room)), in the order of the top-down walk (ancestors before descendants): site = the index into the packed
+ *                      alignment, edge = the index into the edge list, info = f_parent in bits 0-3 and f_child in bits 4-7, both
+ *                      one-hot.  Deterministic: no atomic decides a position.
+ * The sets of all nodes live in a workspace buffer for a slab of sites at a time, sized from a byte budget;
+ * TRACS_FITCH_SLAB_GROUPS (diagnostic): the slab's length in groups of 128 sites.                                                  */
+int tracs_fitch_count(const tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, uint32_t *edge_changes,
+                      uint32_t *site_changes, uint8_t *site_minimum, int64_t *off, uint64_t *total, void *stream);
+int tracs_fitch_fill(const tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, size_t site_begin, size_t site_end,
+                     const int64_t *off, int64_t entry_base, uint32_t *site, uint32_t *edge, uint32_t *info, size_t room, void *stream);
 
 /* transcluster on device arrays (same math as tracs_trans_dist).  workspace is managed
  * internally (hipMallocAsync on the stream).  exp_p0 != 0 writes exp(p0) (what
@@ -733,6 +765,22 @@ int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, d
  *                         appended to it (tracs_tree_write).  n_joins: n - 3; rows_written: the edge rows.                     */
 int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint64_t *n_joins,
                         uint64_t *rows_written);
+/*   tracs_distance_tree_changes `--tree nj --tree-changes / --tree-sites` (not in the reference): tracs_distance_tree's
+ *                         body (either kind), then tracs_fitch_count on that tree.  changes_path != NULL and more than max_entries
+ *                         changes in all: refused with a message that states it, before any file is touched.  create != 0: the
+ *                         four files are then created (the edge file with the header parent,child,length,changes,MSA file, the
+ *                         change file with parent,child,contig,position,alleleParent,alleleChild,MSA file, the site file with
+ *                         contig,position,changes,minimum,MSA file); 0: they are appended to (a second --msa file).  The Newick line
+ *                         and the edge rows come from tracs_tree_write_changes; the change rows -- sites ascending, walk order
+ *                         within a site, nodes named as in the edge rows, alleles A/C/G/T, contig / position as
+ *                         tracs_distance_pair_sites writes them -- from tracs_fitch_fill in batches of sites: two buffers (device,
+ *                         pinned host) of at most 256 MiB (TRACS_FITCH_BATCH: entries per batch, diagnostic), rows formatted on
+ *                         n_threads host threads (<= 0: up to 16); the site rows list the sites with a change.  n_changes: the
+ *                         tree's parsimony length; sum_minimum: the sum of `minimum` over the sites with a change.             */
+int tracs_distance_tree_changes(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, const char *changes_path,
+                                const char *sites_path, const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs,
+                                uint64_t max_entries, int n_threads, int create, uint64_t *n_joins, uint64_t *rows_written, uint64_t *n_changes,
+                                uint64_t *sum_minimum);
 /*   tracs_distance_tree_bootstrap `--tree nj --bootstrap B` (not in the reference): tracs_distance_tree's main tree
  *                         (kind 0 only), then `replicates` >= 1 bootstrap replicates b = 0 .. replicates - 1 under `seed`: the columns
  *                         at which two samples differ are selected once (the others add nothing to any replicate's distances), and per

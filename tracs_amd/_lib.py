@@ -56,6 +56,7 @@ SYMBOLS = [
     "tracs_distance_tree_bootstrap",
     "tracs_tree_transfer_program", "tracs_transfer_state_bytes", "tracs_transfer_init", "tracs_transfer_add", "tracs_transfer_emit",
     "tracs_tree_transfer", "tracs_tree_write_transfer", "tracs_distance_tree_bootstrap_transfer",
+    "tracs_fitch_count", "tracs_fitch_fill", "tracs_tree_write_changes", "tracs_distance_tree_changes",
 ]
 
 
@@ -218,6 +219,15 @@ def load():
     L.tracs_nj_edges.argtypes = [sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
     L.tracs_tree_write.restype = C.c_int
     L.tracs_tree_write.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, C.c_char_p, C.c_char_p, C.c_char_p]
+    L.tracs_tree_write_changes.restype = C.c_int
+    L.tracs_tree_write_changes.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, vp, C.c_char_p, C.c_char_p, C.c_char_p]
+    L.tracs_fitch_count.restype = C.c_int
+    L.tracs_fitch_count.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, u64p, vp]
+    L.tracs_fitch_fill.restype = C.c_int
+    L.tracs_fitch_fill.argtypes = [vp, vp, vp, sz, sz, sz, vp, i64, vp, vp, vp, sz, vp]
+    L.tracs_distance_tree_changes.restype = C.c_int
+    L.tracs_distance_tree_changes.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u64p, sz,
+                                              C.c_uint64, C.c_int, C.c_int, u64p, u64p, u64p, u64p]
     L.tracs_bootstrap_weights.restype = C.c_int
     L.tracs_bootstrap_weights.argtypes = [sz, C.c_uint64, C.c_uint64, vp, vp]
     L.tracs_debug_bootstrap_replicate.restype = C.c_int

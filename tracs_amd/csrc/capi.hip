@@ -1303,6 +1303,63 @@ int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const cha
     return TRACS_OK;
 }
 
+// `tracs distance --tree nj --tree-changes / --tree-sites` (include/tracs_hip.h): tracs_distance_tree's body, then the
+// count pass of csrc/fitch.hip on that tree; a total above max_entries is refused before any file is touched; then the tree with the
+// edges' counts, the change rows and the site rows.
+int tracs_distance_tree_changes(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, const char *changes_path,
+                                const char *sites_path, const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs,
+                                uint64_t max_entries, int n_threads, int create, uint64_t *n_joins, uint64_t *rows_written, uint64_t *n_changes,
+                                uint64_t *sum_minimum)
+{
+    for (uint64_t *p : {n_joins, rows_written, n_changes, sum_minimum}) if (p) *p = 0;
+    if (!h || !h->a || !path || !ref) { set_error("tracs_distance_tree_changes: NULL argument"); return TRACS_E_ARG; }
+    if (kind != 0 && kind != 1) { set_error("tracs_distance_tree_changes: kind must be 0 (snp) or 1 (per-site)"); return TRACS_E_ARG; }
+    if (h->n_fasta != 1) { set_error("tracs_distance_tree_changes: a tree joins the samples of one alignment"); return TRACS_E_ARG; }
+    SigintScope sigint;
+    const size_t n = h->a->n;
+    if (n && !tracs_nj_state_bytes(n)) { set_error("tracs_distance_tree_changes: too many samples for one distance matrix"); return TRACS_E_ARG; }
+    StageClock clock;
+    int rc;
+    TreeEdges t;
+    tracs::FitchTables ft;
+    {
+        PanelWalk walk(h->a, 1, n, 2147483647, 0);
+        DeviceBuffer d_state;
+        if ((rc = tree_of_alignment(h->a, n, h->name_ptr.data(), kind, walk, d_state, clock, nullptr, t))) return rc;
+    }
+    if (n && (rc = tracs::fitch_tables(h->a, t.parent.data(), t.child.data(), t.ne, ft))) return rc;
+    clock.mark("tree changes: count pass, offsets");
+    if (g_sigint) return interrupted();
+    if (changes_path && ft.total > max_entries) {
+        set_error("the tree has " + std::to_string(ft.total) + " changes in all, more than --max-entries " + std::to_string(max_entries) +
+                  "; nothing was written");
+        return TRACS_E_ARG;
+    }
+    if (create) {
+        const std::pair<const char *, const char *> made[4] = {{path, ""}, {edges_path, "parent,child,length,changes,MSA file\n"},
+            {changes_path, "parent,child,contig,position,alleleParent,alleleChild,MSA file\n"}, {sites_path, "contig,position,changes,minimum,MSA file\n"}};
+        for (const auto &m : made) {
+            if (!m.first) continue;
+            std::FILE *fh = std::fopen(m.first, "wb");
+            if (!fh || std::fputs(m.second, fh) < 0 || std::fclose(fh) != 0) { set_error(std::string("cannot write ") + m.first); return TRACS_E_OPEN; }
+        }
+    }
+    ft.edge_changes.resize(std::max<size_t>(t.ne, 1), 0);
+    if ((rc = tracs_tree_write_changes(h->name_ptr.data(), n, t.parent.data(), t.child.data(), t.length.data(), t.ne, ft.edge_changes.data(), path,
+                                       ref, edges_path))) return rc;
+    clock.mark("tree: emit, lengths, format, write");
+    if (n && (rc = tracs::fitch_write(h->a, h->name_ptr.data(), h->kept.empty() ? nullptr : h->kept.data(), h->source_len, t.parent.data(),
+                                      t.child.data(), t.ne, ft, changes_path, sites_path, ref, contig_names, contig_lengths, n_contigs, n_threads)))
+        return rc;
+    clock.mark("tree changes: fill, device -> host, format, write");
+    if (n_joins) *n_joins = t.nj;
+    if (rows_written) *rows_written = edges_path ? t.ne : 0;
+    if (n_changes) *n_changes = ft.total;
+    if (sum_minimum) *sum_minimum = ft.sum_minimum;
+    if (g_sigint) return interrupted();
+    return TRACS_OK;
+}
+
 // `tracs distance --tree nj --bootstrap B` (include/tracs_hip.h).  The main tree as above; then the columns at which two
 // samples differ are selected once (census bitmap -> tracs_alignment_select_sites: the other columns add nothing to any replicate's
 // distances), and per replicate: the draws counted over those columns, the replicate gathered into a handle of its own, the same

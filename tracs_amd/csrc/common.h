@@ -155,6 +155,27 @@ int pair_sites_write(const tracs_alignment *a, const char *const *names, const u
                      const uint32_t *cols, size_t n_pairs, int filter, uint64_t max_entries, const char *path, const char *const *contig_names,
                      const uint64_t *contig_lengths, size_t n_contigs, int n_threads, uint64_t *rows_written);
 
+// fitch.hip: every site placed on a fixed tree (tracs_fitch_count / _fill) and the rows of --tree-changes / --tree-sites
+// (tracs_distance_tree_changes: fitch_tables counts, the caller decides about --max-entries and writes the tree, fitch_write fills
+// and formats; names, kept-columns bitmap and contigs as pair_sites_write)
+struct FitchTables {
+    unsigned *d_edge = nullptr, *d_site = nullptr;
+    uint8_t *d_min = nullptr;
+    long long *d_off = nullptr;
+    std::vector<uint32_t> edge_changes;
+    std::vector<long long> off;
+    std::vector<uint8_t> minimum;
+    uint64_t total = 0, sum_minimum = 0;
+    FitchTables() = default;
+    FitchTables(const FitchTables &) = delete;
+    FitchTables &operator=(const FitchTables &) = delete;
+    ~FitchTables();
+};
+int fitch_tables(const tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, FitchTables &t);
+int fitch_write(const tracs_alignment *a, const char *const *names, const uint64_t *kept, size_t source_len, const uint32_t *parent,
+                const uint32_t *child, size_t n_edges, const FitchTables &t, const char *changes_path, const char *sites_path, const char *ref,
+                const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs, int n_threads);
+
 // device memory that lives until the alignment is packed again (site_classes_free releases all of it at once)
 hipError_t pack_alloc(tracs_alignment *a, size_t bytes, void **out);
 void pack_release(tracs_alignment *a);
@@ -195,6 +216,8 @@ enum WsSlot : int {
     WS_ANC_SORT_TMP,
     // bootstrap.hip: the scanned column counts of a replicate and the first source column of every output group
     WS_BS_OFFSETS, WS_BS_STARTS,
+    // fitch.hip: a slab's node sets [node][word], the edge list's child column, tile sums of the offsets scan
+    WS_FITCH_NODES, WS_FITCH_TREE, WS_FITCH_SUMS,
     WS_SLOT_COUNT
 };
 

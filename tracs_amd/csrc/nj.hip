@@ -461,9 +461,11 @@ void append_label(std::string &out, const char *name)
 // NO_SUPPORT carries it as a decimal label, and the edge rows have a support field before ref ("NA" on leaf edges and where there is none).
 // transfer != NULL (tracs_tree_write_transfer, with support): the label is the edge's transfer support instead, written like a length
 // (NaN: none), and the edge rows have a transfer field behind the support field.
+// changes != NULL (tracs_tree_write_changes, without support): the edge rows have a changes field before ref; the Newick line is
+// tracs_tree_write's.
 static int tree_write_body(const char *who, const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
                            size_t n_edges, const uint32_t *support, const double *transfer, const char *path, const char *ref,
-                           const char *edges_path)
+                           const char *edges_path, const uint32_t *changes = nullptr)
 {
     constexpr uint32_t NO_SUPPORT = 0xFFFFFFFFu;
     if (!path || (n && !names) || (n_edges && (!parent || !child || !length)) || (edges_path && !ref)) {
@@ -538,6 +540,7 @@ static int tree_write_body(const char *who, const char *const *names, size_t n, 
             node_name(parent[e]); rows.push_back(',');
             node_name(child[e]); rows.push_back(',');
             append_length(rows, length[e]); rows.push_back(',');
+            if (changes) { rows += std::to_string(changes[e]); rows.push_back(','); }
             if (support) {
                 if (child[e] >= n && n >= 3 && support[e] != NO_SUPPORT) rows += std::to_string(support[e]);
                 else rows += "NA";
@@ -564,6 +567,17 @@ int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent,
                      const char *path, const char *ref, const char *edges_path)
 {
     return tree_write_body("tracs_tree_write", names, n, parent, child, length, n_edges, nullptr, nullptr, path, ref, edges_path);
+}
+
+// tracs_tree_write with the number of changes on every edge: the same Newick line, and the rows
+// parent,child,length,changes,ref.
+int tracs_tree_write_changes(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
+                             size_t n_edges, const uint32_t *changes, const char *path, const char *ref, const char *edges_path)
+{
+    if (n_edges && !changes) { set_error("tracs_tree_write_changes: NULL argument"); return TRACS_E_ARG; }
+    static const uint32_t none = 0;
+    return tree_write_body("tracs_tree_write_changes", names, n, parent, child, length, n_edges, nullptr, nullptr, path, ref, edges_path,
+                           n_edges ? changes : &none);
 }
 
 // tracs_tree_write with bootstrap support: `(A:1,B:2)87:0.5`, and the rows parent,child,length,support,ref.

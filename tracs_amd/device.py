@@ -685,6 +685,58 @@ def pair_sites(aln, rows, cols, filter=False):
     return off, site[:k], info[:k]
 
 
+def _tree_arrays(parent, child):
+    parent, child = np.ascontiguousarray(parent, np.uint32), np.ascontiguousarray(child, np.uint32)
+    if parent.ndim != 1 or parent.shape != child.shape:
+        raise ValueError("parent and child must be two arrays of one length")
+    return parent, child
+
+
+def fitch_count(aln, parent, child):
+    """Every site of the alignment placed on a tree over its samples by Fitch's two passes (tracs_fitch_count).  parent,
+    child: the edges as nj_edges returns them (host arrays).  -> (edge_changes torch.int32 [2n - 3], site_changes torch.int32 [L],
+    site_minimum torch.uint8 [L], offsets torch.int64 [L + 1], total) on the device: the changes on every edge and at every site, the
+    fewest changes any tree needs at the site, and the exclusive scan of site_changes (total = offsets[L], the tree's parsimony
+    length)."""
+    L = _lib.require_gpu()
+    parent, child = _tree_arrays(parent, child)
+    ne, sites = len(parent), int(aln.L)
+    dev = "cuda"
+    edge = torch.zeros(max(ne, 1), dtype=torch.int32, device=dev)
+    site = torch.zeros(max(sites, 1), dtype=torch.int32, device=dev)
+    minimum = torch.zeros(max(sites, 1), dtype=torch.uint8, device=dev)
+    off = torch.zeros(sites + 1, dtype=torch.int64, device=dev)
+    total = C.c_uint64(0)
+    _lib.check(L.tracs_fitch_count(aln._h, parent.ctypes.data, child.ctypes.data, ne, _ptr(edge), _ptr(site), _ptr(minimum), _ptr(off),
+                                   C.byref(total), _stream()))
+    return edge[:ne], site[:sites], minimum[:sites], off, int(total.value)
+
+
+def fitch_fill(aln, parent, child, off, site_begin=0, site_end=None, entry_base=None, room=None, out=None):
+    """The changes of the sites [site_begin, site_end) (tracs_fitch_fill), after fitch_count gave `off`: -> (site, edge, info) torch.int32
+    on the device, the entries of site s at [off[s] - entry_base, off[s + 1] - entry_base) in the order of the top-down walk: the site,
+    the index into the edge list, and the parent's state in bits 0-3 / the child's in bits 4-7 of info (one-hot, A = 1 ... T = 8).
+    entry_base: off[site_begin] by default; room: the entries the buffers hold (by default what the range needs); out: three buffers
+    to fill instead of new ones (nothing is written beyond room)."""
+    L = _lib.require_gpu()
+    parent, child = _tree_arrays(parent, child)
+    sites = int(aln.L)
+    site_end = sites if site_end is None else int(site_end)
+    if entry_base is None:
+        entry_base = int(off[site_begin].item()) if sites else 0
+    need = (int(off[site_end].item()) - int(entry_base)) if sites else 0
+    room = max(need, 0) if room is None else int(room)
+    if out is None:
+        out = tuple(torch.zeros(max(room, 1), dtype=torch.int32, device=off.device) for _ in range(3))
+    for t in out:
+        assert t.is_cuda and t.is_contiguous() and t.element_size() == 4 and t.numel() >= room
+    _lib.check(L.tracs_fitch_fill(aln._h, parent.ctypes.data, child.ctypes.data, len(parent), int(site_begin), site_end, _ptr(off),
+                                  int(entry_base), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), room, _stream()))
+    torch.cuda.current_stream().synchronize()              # (the edges are host arrays of this call)
+    k = max(min(need, room), 0)
+    return out[0][:k], out[1][:k], out[2][:k]
+
+
 def filter_index_info(aln):
     """Diagnostics of the alignment's filter index (None before the first filter call)."""
     import ctypes as C

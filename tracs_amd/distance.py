@@ -47,10 +47,20 @@ TREE_EDGES_HEADER = "parent,child,length,MSA file\n"
 TREE_EDGES_SUPPORT_HEADER = "parent,child,length,support,MSA file\n"         # with --bootstrap
 TREE_EDGES_TRANSFER_HEADER = "parent,child,length,support,transfer,MSA file\n"      # with --bootstrap-support transfer
 
+TREE_EDGES_CHANGES_HEADER = "parent,child,length,changes,MSA file\n"         # with --tree-changes / --tree-sites
+TREE_CHANGES_HEADER = "parent,child,contig,position,alleleParent,alleleChild,MSA file\n"
+TREE_SITES_HEADER = "contig,position,changes,minimum,MSA file\n"
+
 TREE_DISTANCES = {"snp": 0, "per-site": 1}
 
 HEADER = ("sampleA,sampleB,date difference,SNP distance,transmission distance,expected K,"
           "filtered SNP distance,sites considered,MSA file\n")
+
+
+def check_max_entries(text):
+    """pair_sites.check_max_entries (that module imports this one)"""
+    from .pair_sites import check_max_entries as f
+    return f(text)
 
 
 def add_site_rule_options(st):
@@ -135,6 +145,24 @@ def distance_parser(parser):
                      help="With --tree: also write the tree's 2n - 3 edges as parent,child,length,MSA file, in the order they were "
                           "made; internal nodes are named #1, #2, ... by join number, the last one (#(n-2)) joins the remaining three.  "
                           "Sample names are written as they are, as in the other outputs (Newick quotes them)")
+    snp.add_argument("--tree-changes", dest="tree_changes", default=None, type=str, metavar="FILE",
+                     help="With --tree: place every site of the compared alignment on the tree by small parsimony (Fitch's two passes, "
+                          "on the GPU, an IUPAC code read as a set of bases) and write one row per change, "
+                          "parent,child,contig,position,alleleParent,alleleChild,MSA file: the SNPs that lie on each branch.  Sites "
+                          "ascending, within a site from the top node down; nodes named as in --tree-edges, alleles A/C/G/T, contig and "
+                          "position as `pair-sites` and --site-table write them (0-based, in the coordinates of the input file).  The "
+                          "NUMBER of changes at a site is its parsimony length on this tree and is unique; their placement on branches is "
+                          "one most-parsimonious reconstruction among possibly several (ties go to the parent's base, then A before C "
+                          "before G before T).  An N sample never carries a change.  --tree-edges gains a changes column, and one line "
+                          "on stderr gives the tree's parsimony length, the sum of the sites' minimum and the consistency index.  Not with "
+                          "--bootstrap.  Not in the reference.")
+    snp.add_argument("--tree-sites", dest="tree_sites", default=None, type=str, metavar="FILE",
+                     help="With --tree: write contig,position,changes,minimum,MSA file for every site with at least one change on the "
+                          "tree (see --tree-changes): minimum is the fewest changes any tree needs at the site, and changes - minimum is "
+                          "the site's homoplasy -- recombination, hotspots, mapping artefacts.  Not with --bootstrap.")
+    snp.add_argument("--max-entries", dest="max_entries", type=check_max_entries, default=None, metavar="N",
+                     help="With --tree-changes: refuse, before anything is written, when the tree has more than N changes in all "
+                          "(default=100000000)")
     snp.add_argument("--bootstrap", dest="bootstrap", default=None, type=int, metavar="B",
                      help="With --tree: B >= 1 bootstrap replicates, resampled and built on the GPU.  A replicate draws as many columns "
                           "as the run compares, with replacement, and goes through the same distances and the same neighbour joining.  "
@@ -421,6 +449,11 @@ def check_tree_args(args):
         if args.bootstrap_support is not None:
             raise SystemExit("tracs distance: --bootstrap-support needs --bootstrap, which needs --tree (it chooses what the replicates' trees "
                              "say about the branches of the tree that --tree builds)")
+        for opt, value in (("--tree-changes", args.tree_changes), ("--tree-sites", args.tree_sites)):
+            if value is not None:
+                raise SystemExit("tracs distance: %s needs --tree (it places the sites on the tree that --tree builds)" % opt)
+        if args.max_entries is not None:
+            raise SystemExit("tracs distance: --max-entries needs --tree-changes, which needs --tree (it bounds the rows of that file)")
         return
     for opt, given in (("--nearest", args.nearest is not None), ("--mst", args.mst is not None),
                        ("--ancestors", args.ancestors is not None), ("--histogram", args.histogram)):
@@ -453,15 +486,40 @@ def check_tree_args(args):
         if TREE_DISTANCES[args.tree_distance or "snp"] == 1:
             raise SystemExit("tracs distance: --bootstrap resamples SNP distances and takes no --tree-distance per-site (a replicate's "
                              "compared-site counts need every column, not only the differing ones)")
+    for opt, value in (("--tree-changes", args.tree_changes), ("--tree-sites", args.tree_sites)):
+        if value is not None and args.bootstrap is not None:
+            raise SystemExit("tracs distance: %s and --bootstrap cannot be combined yet (the tree is reproducible bit for bit: run once with "
+                             "each and join the two --tree-edges files on parent and child)" % opt)
+    if args.max_entries is not None and args.tree_changes is None:
+        raise SystemExit("tracs distance: --max-entries needs --tree-changes (it bounds the rows of that file; --tree-sites has at most one "
+                         "row per site)")
     check_output_paths("distance", _inputs(args), dict(_outputs(args), **{"--tree-edges": args.tree_edges}), ["--tree-edges"])
+    tree_outputs = dict(_outputs(args), **{"--tree-edges": args.tree_edges, "--tree-changes": args.tree_changes, "--tree-sites": args.tree_sites})
+    check_output_paths("distance", _inputs(args), tree_outputs, ["--tree-changes"])
+    check_output_paths("distance", _inputs(args), tree_outputs, ["--tree-sites"])
     check_output_paths("distance", _inputs(args), dict(_outputs(args), **{"--tree-edges": args.tree_edges, "--bootstrap-trees": args.bootstrap_trees}),
                        ["--bootstrap-trees"])
 
 
-def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None):
+def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None, tree_contigs=None):
     """--tree nj for one alignment (handle.DistanceHandle.tree, tracs_distance_tree: include/tracs_hip.h): every dense panel goes into the
     distance matrix on the device, the joins run there, and one Newick line (and the edge rows) are appended by the library."""
     with _opened(msas, args, stage, rule, contigs) as h:
+        if args.tree_changes is not None or args.tree_sites is not None:
+            # (the library creates the four files itself, once the count has passed --max-entries: a refusal touches nothing)
+            try:
+                joins, rows, changes, minimum = h.tree(args.output_file, ref, per_site=TREE_DISTANCES[args.tree_distance or "snp"] == 1,
+                                                       edges_path=args.tree_edges, changes_path=args.tree_changes, sites_path=args.tree_sites,
+                                                       max_entries=args.max_entries, contigs=tree_contigs, n_threads=args.n_cpu,
+                                                       create=not getattr(args, "tree_files_made", False))
+            except RuntimeError as e:
+                raise SystemExit("tracs distance: %s" % e)
+            args.tree_files_made = True
+            sys.stderr.write("tracs distance: %s: parsimony length %d, minimum %d, consistency index %s\n"
+                             % (ref, changes, minimum, repr(minimum / changes) if changes else "1"))
+            stage("[sum] tracs_distance_tree_changes (dense panels, joins, tree, Fitch count and fill: %d joins, %d edge rows, %d changes)"
+                  % (joins, rows, changes))
+            return
         if args.bootstrap is not None:
             joins, rows = h.tree(args.output_file, ref, edges_path=args.tree_edges, bootstrap=args.bootstrap,
                                  seed=1 if args.bootstrap_seed is None else args.bootstrap_seed, replicate_trees=args.bootstrap_trees,
@@ -872,7 +930,8 @@ def distance(args):
     logging.info("Loading metadata...")
     dates = _read_dates(args.metadata) if args.metadata is not None else None
     logging.info("Estimating transmission distances...")
-    if lead:
+    tree_changes = args.tree is not None and (args.tree_changes is not None or args.tree_sites is not None)
+    if lead and not tree_changes:                  # (--tree-changes / --tree-sites: tracs_distance_tree_changes creates the run's files)
         with open(args.output_file, "w") as out:
             out.write("" if args.tree is not None else HISTOGRAM_HEADER if args.histogram else HEADER)      # (Newick lines: no header)
         if args.tree is not None and args.tree_edges is not None:
@@ -895,6 +954,8 @@ def distance(args):
         ruled = dict(rule=rule) if rule is not None else {}                 # (no rule: every route is called as it always was)
         if args.msa_out is not None or args.site_table is not None:
             ruled["contigs"] = site_files[2]
+        if tree_changes:
+            ruled["tree_contigs"] = site_files[2]
         if route is not None:
             # one GPU, on the device until its rows: the histogram, the forest or the ancestor links of the pairs the full run would write, or the tree
             require_files(msas)

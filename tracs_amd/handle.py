@@ -126,16 +126,40 @@ class DistanceHandle:
     def source(self):
         return source_records(self.L, "distance", self.h)
 
-    def tree(self, path, ref, per_site=False, edges_path=None, bootstrap=0, seed=1, replicate_trees=None, support="split"):
+    def tree(self, path, ref, per_site=False, edges_path=None, bootstrap=0, seed=1, replicate_trees=None, support="split",
+             changes_path=None, sites_path=None, max_entries=None, contigs=None, n_threads=0, create=True):
         """The neighbour-joining tree of the handle's samples (tracs_distance_tree): one Newick line appended to `path`, the edge rows
         to edges_path.  bootstrap = B > 0 (tracs_distance_tree_bootstrap): B bootstrap replicates under `seed`; the internal nodes are
         labelled with the number of replicates that have their split, the edge rows gain a support field, and replicate_trees receives
         each replicate's Newick line.  support="transfer" (tracs_distance_tree_bootstrap_transfer): the labels are the transfer
-        supports, doubles in [0, 1], and the edge rows carry both the count and the transfer support.  -> (joins, edge rows written)"""
+        supports, doubles in [0, 1], and the edge rows carry both the count and the transfer support.  -> (joins, edge rows written)
+        changes_path / sites_path (tracs_distance_tree_changes; no bootstrap): every site placed on the tree by Fitch's
+        two passes -- one row per change, one per site with a change, and a changes field in the edge rows.  More than max_entries
+        (default 10^8) changes are refused before any file is touched; create: the files are created with their headers (False: appended
+        to); contigs: [(name, length)] or None.  -> (joins, edge rows written, changes, sum of the sites' minimum)"""
         if support not in ("split", "transfer"):
             raise ValueError("tree(): support is 'split' or 'transfer'")
         joins, rows = C.c_uint64(0), C.c_uint64(0)
         enc = lambda p: os.fsencode(p) if p is not None else None         # noqa: E731
+        if changes_path is not None or sites_path is not None:
+            if bootstrap:
+                raise ValueError("tree(): changes_path / sites_path take no bootstrap")
+            if max_entries is not None and changes_path is None:
+                raise ValueError("tree(): max_entries bounds the rows of changes_path")
+            max_entries = 100000000 if max_entries is None else int(max_entries)
+            if max_entries < 1:
+                raise ValueError("tree(): max_entries must be at least 1")
+            nc = len(contigs) if contigs is not None else 0
+            cnames = (C.c_char_p * max(nc, 1))(*[c[0].encode() for c in (contigs or [])])
+            clens = (C.c_uint64 * max(nc, 1))(*[int(c[1]) for c in (contigs or [])])
+            changes, minimum = C.c_uint64(0), C.c_uint64(0)
+            _lib.check(self.L.tracs_distance_tree_changes(self.h, int(bool(per_site)), os.fsencode(path), ref.encode(), enc(edges_path),
+                                                          enc(changes_path), enc(sites_path), cnames, clens, nc, max_entries, int(n_threads),
+                                                          int(bool(create)), C.byref(joins), C.byref(rows), C.byref(changes),
+                                                          C.byref(minimum)))
+            return joins.value, rows.value, changes.value, minimum.value
+        if max_entries is not None:
+            raise ValueError("tree(): max_entries needs changes_path")
         if not bootstrap:
             if replicate_trees is not None:
                 raise ValueError("tree(): replicate_trees needs bootstrap > 0")
