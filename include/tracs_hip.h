@@ -411,6 +411,11 @@ int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent,
  *                        tracs_tree_write's, byte for byte; the edge rows are parent,child,length,changes,ref.                  */
 int tracs_tree_write_changes(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
                              size_t n_edges, const uint32_t *changes, const char *path, const char *ref, const char *edges_path);
+/*   tracs_tree_write_filtered tracs_tree_write_changes with the changes the branch filter keeps per edge (uint32[n_edges]):
+ *                        the edge rows are parent,child,length,changes,filtered,ref.                                          */
+int tracs_tree_write_filtered(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
+                              size_t n_edges, const uint32_t *changes, const uint32_t *filtered, const char *path, const char *ref,
+                              const char *edges_path);
 
 /* Bootstrap support for the neighbour-joining tree (csrc/bootstrap.hip; what tracs_distance_tree_bootstrap runs).  One
  * replicate is the run on an alignment whose L columns were drawn with replacement.  All arithmetic mod 2^64:
@@ -566,6 +571,39 @@ int tracs_fitch_count(const tracs_alignment *a, const uint32_t *parent, const ui
                       uint32_t *site_changes, uint8_t *site_minimum, int64_t *off, uint64_t *total, void *stream);
 int tracs_fitch_fill(const tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, size_t site_begin, size_t site_end,
                      const int64_t *off, int64_t entry_base, uint32_t *site, uint32_t *edge, uint32_t *info, size_t room, void *stream);
+
+/* The recombination filter on the tree's branches (csrc/fitch.hip, csrc/filter_lists.hip; not in the reference).  The
+ * input is the packed alignment with its L sites in packed coordinates, exactly as the pair filter sees them, together with the tree
+ * and its Fitch reconstruction as defined above.
+ *     For edge e, C_e is the ascending list of the sites with a change on e and d_e = |C_e| (edge_changes[e] of tracs_fitch_count).
+ *     kept_e = filter_recomb(C_e, d_e, L) (src/pairsnp.hpp:251-318): d_e <= 1: everything is kept.  Otherwise p = d_e / L, the
+ *     threshold is 0.05 / d_e and the half window wh = clamp(int(1 / p / 2 + 1), 50, 5000).  A change at site s is DROPPED iff its
+ *     window [max(0, s - wh), min(L, s + wh + 1)) holds count > 1 changes of that edge, spanning `length` sites first to last, with
+ *     1 - BinomCDF(count; length, p) < 0.05 / d_e (count >= length: CDF = 1).  kept_e is the number of changes not dropped.
+ * Nothing else moves: the tree is built from the unfiltered distances and the filter is not iterated into the topology; the verdicts
+ * belong to the one reconstruction that the top-down pass picks.  An N leaf never carries a change, so it never carries a drop.
+ *   tracs_fitch_edge_sites    the changes regrouped by edge.  parent / child as above (HOST), edge_changes: tracs_fitch_count's (device).
+ *                             edge_off (device int64[n_edges + 1]) <- the exclusive scan of edge_changes; edge_site (device uint32[room])
+ *                             <- the sites of edge e at [edge_off[e], edge_off[e + 1]), ASCENDING; nothing is stored outside [0, room).
+ *                             Deterministic: no atomic decides a position -- the walk stores a wave's count per (chunk of 2 048 sites,
+ *                             edge), a column scan makes them bases, and the walk again places every change.  The [chunk][edge] matrix
+ *                             holds a range of sites at a time (256 MiB; TRACS_FITCH_MATRIX_CHUNKS: chunks per range, diagnostic).
+ *   tracs_filter_recomb_lists the window test on n_lists sorted lists (device): list t is pos[off[t] .. off[t + 1]), off int64[n_lists + 1]
+ *                             with off[0] = 0, pos uint32[n_entries].  filt[t] (device uint32[n_lists]) <- the entries kept, with L =
+ *                             a->L; dropped (device uint8[n_entries], or NULL) <- 1 on the entries dropped, 0 on the others.  Every
+ *                             list MUST be ascending and below L: that is not checked.  Offsets that decrease, or that end beyond
+ *                             n_entries, are refused (TRACS_E_ARG) before a launch.  The verdicts come from the same threshold rows
+ *                             and the same tail sum as tracs_filter_recomb_pairs's (rows kept on the handle; TRACS_FILTER_TABLE=0:
+ *                             the sum per entry); the departure lists of the pair routes are neither needed nor built.
+ *   tracs_fitch_mark_dropped  bit 8 of info (the bit tracs_pair_sites_fill sets with filter != 0) on the entries of a batch that
+ *                             tracs_fitch_fill filled and that `dropped` marks: entry k = (site[k], edge[k]) is looked up in its
+ *                             edge's segment of edge_site.  All arrays on the device.                                             */
+int tracs_fitch_edge_sites(const tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, const uint32_t *edge_changes,
+                           int64_t *edge_off, uint32_t *edge_site, size_t room, void *stream);
+int tracs_filter_recomb_lists(tracs_alignment *a, const int64_t *off, const uint32_t *pos, size_t n_lists, size_t n_entries, uint32_t *filt,
+                              uint8_t *dropped, void *stream);
+int tracs_fitch_mark_dropped(const uint32_t *site, const uint32_t *edge, uint32_t *info, size_t n_entries, size_t n_edges, const int64_t *edge_off,
+                             const uint32_t *edge_site, const uint8_t *dropped, void *stream);
 
 /* transcluster on device arrays (same math as tracs_trans_dist).  workspace is managed
  * internally (hipMallocAsync on the stream).  exp_p0 != 0 writes exp(p0) (what
@@ -781,6 +819,20 @@ int tracs_distance_tree_changes(tracs_distance *h, int kind, const char *path, c
                                 const char *sites_path, const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs,
                                 uint64_t max_entries, int n_threads, int create, uint64_t *n_joins, uint64_t *rows_written, uint64_t *n_changes,
                                 uint64_t *sum_minimum);
+/*   tracs_distance_tree_filter `--tree nj --tree-filter` (not in the reference): tracs_distance_tree_changes's body with
+ *                         the branch filter between the count and the files: tracs_fitch_edge_sites, then tracs_filter_recomb_lists on
+ *                         the edges' lists.  More than max_entries changes are refused before any file is touched, whether or not
+ *                         changes_path is given (the edge lists and their verdicts hold an entry per change).  The edge file's header
+ *                         is parent,child,length,changes,filtered,MSA file (filtered: the changes kept on the edge;
+ *                         tracs_tree_write_filtered), the change file's parent,child,contig,position,alleleParent,alleleChild,dropped,
+ *                         MSA file (dropped: 0 / 1, from tracs_fitch_mark_dropped on every batch); the site file is unchanged.
+ *                         filtered_path != NULL: one Newick line with the topology and labels of `path` and the kept changes as
+ *                         branch lengths (tracs_tree_write).  n_kept: the changes kept in all; n_edges_dropped: the edges with a
+ *                         dropped change.                                                                                       */
+int tracs_distance_tree_filter(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, const char *changes_path,
+                               const char *sites_path, const char *filtered_path, const char *const *contig_names, const uint64_t *contig_lengths,
+                               size_t n_contigs, uint64_t max_entries, int n_threads, int create, uint64_t *n_joins, uint64_t *rows_written,
+                               uint64_t *n_changes, uint64_t *sum_minimum, uint64_t *n_kept, uint64_t *n_edges_dropped);
 /*   tracs_distance_tree_bootstrap `--tree nj --bootstrap B` (not in the reference): tracs_distance_tree's main tree
  *                         (kind 0 only), then `replicates` >= 1 bootstrap replicates b = 0 .. replicates - 1 under `seed`: the columns
  *                         at which two samples differ are selected once (the others add nothing to any replicate's distances), and per

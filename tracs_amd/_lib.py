@@ -57,6 +57,8 @@ SYMBOLS = [
     "tracs_tree_transfer_program", "tracs_transfer_state_bytes", "tracs_transfer_init", "tracs_transfer_add", "tracs_transfer_emit",
     "tracs_tree_transfer", "tracs_tree_write_transfer", "tracs_distance_tree_bootstrap_transfer",
     "tracs_fitch_count", "tracs_fitch_fill", "tracs_tree_write_changes", "tracs_distance_tree_changes",
+    "tracs_fitch_edge_sites", "tracs_filter_recomb_lists", "tracs_fitch_mark_dropped", "tracs_tree_write_filtered",
+    "tracs_distance_tree_filter",
 ]
 
 
@@ -228,6 +230,17 @@ def load():
     L.tracs_distance_tree_changes.restype = C.c_int
     L.tracs_distance_tree_changes.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u64p, sz,
                                               C.c_uint64, C.c_int, C.c_int, u64p, u64p, u64p, u64p]
+    L.tracs_fitch_edge_sites.restype = C.c_int
+    L.tracs_fitch_edge_sites.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp]
+    L.tracs_filter_recomb_lists.restype = C.c_int
+    L.tracs_filter_recomb_lists.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+    L.tracs_fitch_mark_dropped.restype = C.c_int
+    L.tracs_fitch_mark_dropped.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+    L.tracs_tree_write_filtered.restype = C.c_int
+    L.tracs_tree_write_filtered.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, vp, vp, C.c_char_p, C.c_char_p, C.c_char_p]
+    L.tracs_distance_tree_filter.restype = C.c_int
+    L.tracs_distance_tree_filter.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p),
+                                             u64p, sz, C.c_uint64, C.c_int, C.c_int, u64p, u64p, u64p, u64p, u64p, u64p]
     L.tracs_bootstrap_weights.restype = C.c_int
     L.tracs_bootstrap_weights.argtypes = [sz, C.c_uint64, C.c_uint64, vp, vp]
     L.tracs_debug_bootstrap_replicate.restype = C.c_int

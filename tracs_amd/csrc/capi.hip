@@ -1305,19 +1305,23 @@ int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const cha
 
 // `tracs distance --tree nj --tree-changes / --tree-sites` (include/tracs_hip.h): tracs_distance_tree's body, then the
 // count pass of csrc/fitch.hip on that tree; a total above max_entries is refused before any file is touched; then the tree with the
-// edges' counts, the change rows and the site rows.
-int tracs_distance_tree_changes(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, const char *changes_path,
-                                const char *sites_path, const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs,
-                                uint64_t max_entries, int n_threads, int create, uint64_t *n_joins, uint64_t *rows_written, uint64_t *n_changes,
-                                uint64_t *sum_minimum)
+// edges' counts, the change rows and the site rows.  filter (`--tree-filter`, tracs_distance_tree_filter): the changes
+// regrouped by edge (tracs_fitch_edge_sites) and the recombination filter on every edge's list (tracs_filter_recomb_lists) between
+// the count and the files; the edge rows gain the kept changes, the change rows the verdict, and filtered_path the tree whose
+// lengths are the kept changes.
+static int tree_changes_body(const char *who_, bool filter, tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path,
+                             const char *changes_path, const char *sites_path, const char *filtered_path, const char *const *contig_names,
+                             const uint64_t *contig_lengths, size_t n_contigs, uint64_t max_entries, int n_threads, int create, uint64_t *n_joins,
+                             uint64_t *rows_written, uint64_t *n_changes, uint64_t *sum_minimum, uint64_t *n_kept, uint64_t *n_edges_dropped)
 {
-    for (uint64_t *p : {n_joins, rows_written, n_changes, sum_minimum}) if (p) *p = 0;
-    if (!h || !h->a || !path || !ref) { set_error("tracs_distance_tree_changes: NULL argument"); return TRACS_E_ARG; }
-    if (kind != 0 && kind != 1) { set_error("tracs_distance_tree_changes: kind must be 0 (snp) or 1 (per-site)"); return TRACS_E_ARG; }
-    if (h->n_fasta != 1) { set_error("tracs_distance_tree_changes: a tree joins the samples of one alignment"); return TRACS_E_ARG; }
+    const std::string who(who_);
+    for (uint64_t *p : {n_joins, rows_written, n_changes, sum_minimum, n_kept, n_edges_dropped}) if (p) *p = 0;
+    if (!h || !h->a || !path || !ref) { set_error(who + ": NULL argument"); return TRACS_E_ARG; }
+    if (kind != 0 && kind != 1) { set_error(who + ": kind must be 0 (snp) or 1 (per-site)"); return TRACS_E_ARG; }
+    if (h->n_fasta != 1) { set_error(who + ": a tree joins the samples of one alignment"); return TRACS_E_ARG; }
     SigintScope sigint;
     const size_t n = h->a->n;
-    if (n && !tracs_nj_state_bytes(n)) { set_error("tracs_distance_tree_changes: too many samples for one distance matrix"); return TRACS_E_ARG; }
+    if (n && !tracs_nj_state_bytes(n)) { set_error(who + ": too many samples for one distance matrix"); return TRACS_E_ARG; }
     StageClock clock;
     int rc;
     TreeEdges t;
@@ -1330,14 +1334,39 @@ int tracs_distance_tree_changes(tracs_distance *h, int kind, const char *path, c
     if (n && (rc = tracs::fitch_tables(h->a, t.parent.data(), t.child.data(), t.ne, ft))) return rc;
     clock.mark("tree changes: count pass, offsets");
     if (g_sigint) return interrupted();
-    if (changes_path && ft.total > max_entries) {
+    if ((changes_path || filter) && ft.total > max_entries) {             // (the edge lists and their verdicts hold one entry per change)
         set_error("the tree has " + std::to_string(ft.total) + " changes in all, more than --max-entries " + std::to_string(max_entries) +
                   "; nothing was written");
         return TRACS_E_ARG;
     }
+    // the branch filter: the changes by edge, their verdicts, the kept changes of every edge
+    DeviceBuffer d_edge_off, d_edge_site, d_dropped, d_filt;
+    std::vector<uint32_t> kept(std::max<size_t>(t.ne, 1), 0);
+    uint64_t kept_sum = 0, edges_dropped = 0;
+    tracs::FitchFilter ff = {nullptr, nullptr, nullptr};
+    if (filter && n && t.ne) {
+        if ((rc = d_edge_off.alloc((t.ne + 1) * 8)) || (rc = d_edge_site.alloc(std::max<uint64_t>(ft.total, 1) * 4)) ||
+            (rc = d_dropped.alloc(std::max<uint64_t>(ft.total, 1))) || (rc = d_filt.alloc(t.ne * 4))) return rc;
+        if ((rc = tracs_fitch_edge_sites(h->a, t.parent.data(), t.child.data(), t.ne, ft.d_edge, d_edge_off.as<int64_t>(), d_edge_site.as<uint32_t>(),
+                                         (size_t)ft.total, nullptr))) return rc;
+        clock.mark("tree filter: the changes by edge");
+        if ((rc = tracs_filter_recomb_lists(h->a, d_edge_off.as<int64_t>(), d_edge_site.as<uint32_t>(), t.ne, (size_t)ft.total, d_filt.as<uint32_t>(),
+                                            d_dropped.as<uint8_t>(), nullptr))) return rc;
+        TRACS_HIP_CHECK(hipMemcpy(kept.data(), d_filt.ptr, t.ne * 4, hipMemcpyDeviceToHost));
+        clock.mark("tree filter: window test on the edges' lists");
+        for (size_t e = 0; e < t.ne; e++) {
+            kept_sum += kept[e];
+            edges_dropped += kept[e] < ft.edge_changes[e];
+        }
+        ff.d_edge_off = d_edge_off.as<long long>(); ff.d_edge_site = d_edge_site.as<unsigned>(); ff.d_dropped = d_dropped.as<uint8_t>();
+        if (g_sigint) return interrupted();
+    }
     if (create) {
-        const std::pair<const char *, const char *> made[4] = {{path, ""}, {edges_path, "parent,child,length,changes,MSA file\n"},
-            {changes_path, "parent,child,contig,position,alleleParent,alleleChild,MSA file\n"}, {sites_path, "contig,position,changes,minimum,MSA file\n"}};
+        const std::pair<const char *, const char *> made[5] = {{path, ""},
+            {edges_path, filter ? "parent,child,length,changes,filtered,MSA file\n" : "parent,child,length,changes,MSA file\n"},
+            {changes_path, filter ? "parent,child,contig,position,alleleParent,alleleChild,dropped,MSA file\n"
+                                  : "parent,child,contig,position,alleleParent,alleleChild,MSA file\n"},
+            {sites_path, "contig,position,changes,minimum,MSA file\n"}, {filtered_path, ""}};
         for (const auto &m : made) {
             if (!m.first) continue;
             std::FILE *fh = std::fopen(m.first, "wb");
@@ -1345,19 +1374,49 @@ int tracs_distance_tree_changes(tracs_distance *h, int kind, const char *path, c
         }
     }
     ft.edge_changes.resize(std::max<size_t>(t.ne, 1), 0);
-    if ((rc = tracs_tree_write_changes(h->name_ptr.data(), n, t.parent.data(), t.child.data(), t.length.data(), t.ne, ft.edge_changes.data(), path,
-                                       ref, edges_path))) return rc;
+    if (filter) {
+        if ((rc = tracs_tree_write_filtered(h->name_ptr.data(), n, t.parent.data(), t.child.data(), t.length.data(), t.ne, ft.edge_changes.data(),
+                                            kept.data(), path, ref, edges_path))) return rc;
+        if (filtered_path) {
+            std::vector<double> kept_length(kept.begin(), kept.end());
+            if ((rc = tracs_tree_write(h->name_ptr.data(), n, t.parent.data(), t.child.data(), kept_length.data(), t.ne, filtered_path, ref, nullptr)))
+                return rc;
+        }
+    } else if ((rc = tracs_tree_write_changes(h->name_ptr.data(), n, t.parent.data(), t.child.data(), t.length.data(), t.ne, ft.edge_changes.data(),
+                                              path, ref, edges_path))) return rc;
     clock.mark("tree: emit, lengths, format, write");
     if (n && (rc = tracs::fitch_write(h->a, h->name_ptr.data(), h->kept.empty() ? nullptr : h->kept.data(), h->source_len, t.parent.data(),
-                                      t.child.data(), t.ne, ft, changes_path, sites_path, ref, contig_names, contig_lengths, n_contigs, n_threads)))
+                                      t.child.data(), t.ne, ft, changes_path, sites_path, ref, contig_names, contig_lengths, n_contigs, n_threads,
+                                      ff.d_dropped ? &ff : nullptr)))
         return rc;
     clock.mark("tree changes: fill, device -> host, format, write");
     if (n_joins) *n_joins = t.nj;
     if (rows_written) *rows_written = edges_path ? t.ne : 0;
     if (n_changes) *n_changes = ft.total;
     if (sum_minimum) *sum_minimum = ft.sum_minimum;
+    if (n_kept) *n_kept = kept_sum;
+    if (n_edges_dropped) *n_edges_dropped = edges_dropped;
     if (g_sigint) return interrupted();
     return TRACS_OK;
+}
+
+int tracs_distance_tree_changes(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, const char *changes_path,
+                                const char *sites_path, const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs,
+                                uint64_t max_entries, int n_threads, int create, uint64_t *n_joins, uint64_t *rows_written, uint64_t *n_changes,
+                                uint64_t *sum_minimum)
+{
+    return tree_changes_body("tracs_distance_tree_changes", false, h, kind, path, ref, edges_path, changes_path, sites_path, nullptr, contig_names,
+                             contig_lengths, n_contigs, max_entries, n_threads, create, n_joins, rows_written, n_changes, sum_minimum, nullptr, nullptr);
+}
+
+int tracs_distance_tree_filter(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, const char *changes_path,
+                               const char *sites_path, const char *filtered_path, const char *const *contig_names, const uint64_t *contig_lengths,
+                               size_t n_contigs, uint64_t max_entries, int n_threads, int create, uint64_t *n_joins, uint64_t *rows_written,
+                               uint64_t *n_changes, uint64_t *sum_minimum, uint64_t *n_kept, uint64_t *n_edges_dropped)
+{
+    return tree_changes_body("tracs_distance_tree_filter", true, h, kind, path, ref, edges_path, changes_path, sites_path, filtered_path, contig_names,
+                             contig_lengths, n_contigs, max_entries, n_threads, create, n_joins, rows_written, n_changes, sum_minimum, n_kept,
+                             n_edges_dropped);
 }
 
 // `tracs distance --tree nj --bootstrap B` (include/tracs_hip.h).  The main tree as above; then the columns at which two

@@ -171,10 +171,17 @@ struct FitchTables {
     FitchTables &operator=(const FitchTables &) = delete;
     ~FitchTables();
 };
+// the branch filter's device arrays (tracs_distance_tree_filter): the changes by edge and their verdicts
+struct FitchFilter {
+    const long long *d_edge_off;
+    const unsigned *d_edge_site;
+    const uint8_t *d_dropped;
+};
 int fitch_tables(const tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, FitchTables &t);
 int fitch_write(const tracs_alignment *a, const char *const *names, const uint64_t *kept, size_t source_len, const uint32_t *parent,
                 const uint32_t *child, size_t n_edges, const FitchTables &t, const char *changes_path, const char *sites_path, const char *ref,
-                const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs, int n_threads);
+                const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs, int n_threads,
+                const FitchFilter *flt = nullptr);
 
 // device memory that lives until the alignment is packed again (site_classes_free releases all of it at once)
 hipError_t pack_alloc(tracs_alignment *a, size_t bytes, void **out);
@@ -216,8 +223,9 @@ enum WsSlot : int {
     WS_ANC_SORT_TMP,
     // bootstrap.hip: the scanned column counts of a replicate and the first source column of every output group
     WS_BS_OFFSETS, WS_BS_STARTS,
-    // fitch.hip: a slab's node sets [node][word], the edge list's child column, tile sums of the offsets scan
-    WS_FITCH_NODES, WS_FITCH_TREE, WS_FITCH_SUMS,
+    // fitch.hip: a slab's node sets [node][word], the edge list's child column, tile sums of the offsets scan; the [chunk][edge] matrix of
+    // tracs_fitch_edge_sites and its per-edge cursor
+    WS_FITCH_NODES, WS_FITCH_TREE, WS_FITCH_SUMS, WS_FITCH_MATRIX, WS_FITCH_CURSOR,
     WS_SLOT_COUNT
 };
 

@@ -29,6 +29,8 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <string>
+#include <vector>
 
 namespace tracs {
 
@@ -305,6 +307,93 @@ __global__ __launch_bounds__(256) void flt_table_done_kernel(unsigned char *__re
 {
     const unsigned d = blockIdx.x * 256 + threadIdx.x;
     if (d <= FLT_DCAP && state[d] == 2) state[d] = 1;
+}
+
+// first index in [lo, hi) whose entry is >= key
+__device__ __forceinline__ int flt_lists_lower_bound(const unsigned *__restrict__ a, int lo, int hi, unsigned key)
+{
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// ---- sorted position lists (tracs_filter_recomb_lists) -------------------------------------------------------------
+// wanted rows: the lengths of this call's lists
+__global__ __launch_bounds__(256) void flt_mark_lists_kernel(const long long *__restrict__ off, size_t n_lists, unsigned char *__restrict__ state)
+{
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < n_lists; t += (size_t)gridDim.x * 256) {
+        const long long v = off[t + 1] - off[t];
+        if (v >= 2 && v <= (long long)FLT_DCAP && state[v] == 0) state[v] = 2;
+    }
+}
+
+// The window test (:273-314) on lists that are sorted already: one lane per entry of the flat array pos[0 .. n_entries).  The lane finds
+// its list in off (the last t with off[t] <= k: empty lists are passed over), the ends of its window inside the list's segment -- a
+// few steps to either side, then a binary search --, and its verdict in the threshold row of the list's length, or from filter_keep.
+// filt[t] (zeroed by the caller) takes the kept entries: the lanes of a wave hold consecutive entries, so each list is one run of
+// lanes, and the run's first lane adds the run's count (integer sums: no order depends on them).  dropped: NULL, or 1 per dropped
+// entry.  The lists must be ascending and below L; a span that such lists cannot have is clamped to the widest window, so that
+// no table is read outside its bounds whatever pos holds.
+__global__ __launch_bounds__(256) void flt_lists_kernel(const long long *__restrict__ off, const unsigned *__restrict__ pos, size_t n_lists,
+                                                        size_t n_entries, unsigned L, const unsigned *__restrict__ tbl,
+                                                        const unsigned char *__restrict__ tbl_state, const double *__restrict__ lg,
+                                                        unsigned *__restrict__ filt, uint8_t *__restrict__ dropped)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool active = k < n_entries;
+    unsigned t = 0xFFFFFFFFu;
+    bool keep = false;
+    if (active) {
+        size_t lo = 0, hi = n_lists;                                       // the last t in [0, n_lists) with off[t] <= k
+        while (hi - lo > 1) {
+            const size_t mid = (lo + hi) >> 1;
+            if (off[mid] <= (long long)k) lo = mid; else hi = mid;
+        }
+        t = (unsigned)lo;
+        const long long o0 = off[lo], o1 = off[lo + 1];
+        const long long dn = o1 - o0;
+        keep = true;                                                       // :259-261, :311
+        if (dn > 1 && (long long)k < o1) {
+            const FilterWindow fw = filter_window(dn, L);
+            const unsigned *S = pos + o0;
+            const int u = (int)((long long)k - o0), d = (int)dn;
+            const int x = (int)min(S[u], L - 1u);
+            const int left = max(0, x - fw.wh);                            // :284
+            const int right = min((int)L, x + fw.wh + 1);                  // :285
+            int f = u, l = u, steps = 0;
+            while (f > 0 && (int)S[f - 1] >= left) {
+                --f;
+                if (++steps == 6) { f = flt_lists_lower_bound(S, 0, f, (unsigned)left); break; }
+            }
+            steps = 0;
+            while (l + 1 < d && (int)S[l + 1] < right) {
+                ++l;
+                if (++steps == 6) { l = flt_lists_lower_bound(S, l + 1, d, (unsigned)right) - 1; break; }
+            }
+            const int count = l - f + 1;
+            if (count > 1) {                                               // :294
+                int length = (int)S[l] - (int)S[f] + 1;                    // :242
+                length = min(max(length, 1), 2 * fw.wh + 1);
+                if (tbl && dn <= (long long)FLT_DCAP && count < (int)FLT_KT && tbl_state[dn] == 1) keep = (unsigned)length >= tbl[(size_t)dn * FLT_KT + count];
+                else keep = filter_keep(length, count, fw.p, fw.thr, lg);
+            }
+        }
+        if (dropped) dropped[k] = keep ? 0 : 1;
+    }
+    // the runs of one list among the wave's lanes
+    const unsigned prev = __shfl_up(t, 1, 64);
+    const bool head = lane == 0 || prev != t;
+    const unsigned long long heads = __ballot(head), keeps = __ballot(active && keep);
+    if (active && head) {
+        const unsigned long long above = lane == 63 ? 0ull : (heads >> (lane + 1)) << (lane + 1);
+        const unsigned next = above ? (unsigned)__ffsll((long long)above) - 1u : 64u;
+        const unsigned long long run = (next == 64 ? ~0ull : ((1ull << next) - 1ull)) & ~((1ull << lane) - 1ull);
+        const unsigned c = (unsigned)__popcll(keeps & run);
+        if (c) atomicAdd(filt + t, c);
+    }
 }
 
 // ---- the pairs ----------------------------------------------------------------------------------------------------------------
@@ -1078,6 +1167,19 @@ static int filter_index_get(tracs_alignment *a, hipStream_t stream)
     return done(TRACS_OK);
 }
 
+// The threshold rows of the handle: allocated on first use, all marked "not built" when the alignment's length is another
+static int flt_table_rows(FilterIndex *f, const tracs_alignment *a, hipStream_t stream)
+{
+    if (f->tbl && f->tbl_L == (unsigned)a->L) return TRACS_OK;
+    if (!f->tbl) {
+        if (hipMalloc(reinterpret_cast<void **>(&f->tbl), ((size_t)FLT_DCAP + 1) * FLT_KT * 4) != hipSuccess) { f->tbl = nullptr; set_error("filter: out of device memory"); return TRACS_E_NOMEM; }
+        if (hipMalloc(reinterpret_cast<void **>(&f->tbl_state), FLT_DCAP + 256) != hipSuccess) { f->tbl_state = nullptr; set_error("filter: out of device memory"); return TRACS_E_NOMEM; }
+    }
+    TRACS_HIP_CHECK(hipMemsetAsync(f->tbl_state, 0, FLT_DCAP + 256, stream));
+    f->tbl_L = (unsigned)a->L;
+    return TRACS_OK;
+}
+
 }  // namespace tracs
 
 using namespace tracs;
@@ -1105,14 +1207,7 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
     // thresholds of the binomial test for the d of this call
     const bool use_tbl = !flt_env_off("TRACS_FILTER_TABLE");
     if (use_tbl) {
-        if (!f->tbl || f->tbl_L != (unsigned)a->L) {
-            if (!f->tbl) {
-                if (hipMalloc(reinterpret_cast<void **>(&f->tbl), ((size_t)FLT_DCAP + 1) * FLT_KT * 4) != hipSuccess) { f->tbl = nullptr; set_error("filter: out of device memory"); return TRACS_E_NOMEM; }
-                if (hipMalloc(reinterpret_cast<void **>(&f->tbl_state), FLT_DCAP + 256) != hipSuccess) { f->tbl_state = nullptr; set_error("filter: out of device memory"); return TRACS_E_NOMEM; }
-            }
-            TRACS_HIP_CHECK(hipMemsetAsync(f->tbl_state, 0, FLT_DCAP + 256, stream));
-            f->tbl_L = (unsigned)a->L;
-        }
+        if ((rc = flt_table_rows(f, a, stream))) return rc;
         const unsigned blocks = (unsigned)std::min<size_t>((n_pairs + 255) / 256, 256 * 16);
         hipLaunchKernelGGL(flt_mark_kernel, dim3(blocks), dim3(256), 0, stream, d, n_pairs, f->tbl_state);
         hipLaunchKernelGGL(flt_table_kernel, dim3(FLT_DCAP - 1), dim3(FLT_KT), 0, stream, (unsigned)a->L, lg, f->tbl_state, f->tbl);
@@ -1198,6 +1293,54 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
     TRACS_HIP_CHECK(hipMemcpyAsync(&bad, f->counters, 4, hipMemcpyDeviceToHost, stream));
     TRACS_HIP_CHECK(hipStreamSynchronize(stream));
     if (bad) { set_error("filter: SNP site list does not match the distance (internal error)"); return TRACS_E_HIP; }
+    return TRACS_OK;
+}
+
+// The recombination filter on sorted position lists (device arrays; include/tracs_hip.h): filt[t] = filter_recomb of the
+// ascending list pos[off[t] .. off[t + 1]) in an alignment of a->L sites; dropped (or NULL): 1 on the entries it drops.  The handle's
+// threshold rows are used and extended (the rows depend on L and d alone, so the pair routes find what they would have built); the
+// departure lists are neither needed nor built.
+int tracs_filter_recomb_lists(tracs_alignment *a, const int64_t *off, const uint32_t *pos, size_t n_lists, size_t n_entries, uint32_t *filt,
+                              uint8_t *dropped, void *stream_)
+{
+    if (n_lists == 0) return TRACS_OK;
+    if (!a || !off || !filt || (n_entries && !pos)) { set_error("tracs_filter_recomb_lists: NULL argument"); return TRACS_E_ARG; }
+    if (a->L >= (1ull << 31)) { set_error("filter: alignment longer than 2^31 sites"); return TRACS_E_ARG; }
+    if (n_lists >= (1ull << 31) || n_entries >= (1ull << 31)) { set_error("filter: more than 2^31 lists or entries per call"); return TRACS_E_ARG; }
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    DeviceCall guard(stream);
+    // the offsets are checked on the host before anything is launched
+    std::vector<long long> h_off(n_lists + 1);
+    TRACS_HIP_CHECK(hipMemcpyAsync(h_off.data(), off, (n_lists + 1) * 8, hipMemcpyDeviceToHost, stream));
+    TRACS_HIP_CHECK(hipStreamSynchronize(stream));
+    if (h_off[0] != 0) { set_error("tracs_filter_recomb_lists: off[0] must be 0"); return TRACS_E_ARG; }
+    for (size_t t = 0; t < n_lists; t++)
+        if (h_off[t + 1] < h_off[t]) { set_error("tracs_filter_recomb_lists: the offsets decrease at list " + std::to_string(t)); return TRACS_E_ARG; }
+    if ((unsigned long long)h_off[n_lists] > n_entries) {
+        set_error("tracs_filter_recomb_lists: the offsets end at " + std::to_string(h_off[n_lists]) + ", beyond the " + std::to_string(n_entries) +
+                  " entries given");
+        return TRACS_E_ARG;
+    }
+    const size_t total = (size_t)h_off[n_lists];
+    TRACS_HIP_CHECK(hipMemsetAsync(filt, 0, n_lists * 4, stream));
+    if (!total) return TRACS_OK;
+    if (!a->L) { set_error("tracs_filter_recomb_lists: entries in an alignment without sites"); return TRACS_E_ARG; }
+    const double *lg = nullptr;
+    int rc = get_lgamma_table_for_filter(stream, &lg);
+    if (rc) return rc;
+    if (!a->flt) { a->flt = new FilterIndex(); a->flt_stale = true; }     // (the rows only: a pair call builds the lists when it comes)
+    FilterIndex *f = a->flt;
+    const bool use_tbl = !flt_env_off("TRACS_FILTER_TABLE");
+    if (use_tbl) {
+        if ((rc = flt_table_rows(f, a, stream))) return rc;
+        const unsigned blocks = (unsigned)std::min<size_t>((n_lists + 255) / 256, 256 * 16);
+        hipLaunchKernelGGL(flt_mark_lists_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<const long long *>(off), n_lists, f->tbl_state);
+        hipLaunchKernelGGL(flt_table_kernel, dim3(FLT_DCAP - 1), dim3(FLT_KT), 0, stream, (unsigned)a->L, lg, f->tbl_state, f->tbl);
+        hipLaunchKernelGGL(flt_table_done_kernel, dim3((FLT_DCAP + 256) / 256), dim3(256), 0, stream, f->tbl_state);
+    }
+    hipLaunchKernelGGL(flt_lists_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const long long *>(off), pos,
+                       n_lists, total, (unsigned)a->L, use_tbl ? f->tbl : nullptr, f->tbl_state, lg, filt, dropped);
+    TRACS_HIP_CHECK(hipGetLastError());
     return TRACS_OK;
 }
 

@@ -21,6 +21,11 @@
 //                           depends on them), the sites' change counts from a bit-sliced counter (25 words per lane: one ripple add
 //                           per edge with a change), the sites' minimum.  FILL: the same walk; the entries of site s go to
 //                           off[s] - entry_base + (the site's counter so far), so they are in walk order without any atomic.
+//                           ECOUNT / EFILL (tracs_fitch_edge_sites): the changes regrouped by edge.  A wave holds 2 048
+//                           consecutive sites in lane order; ECOUNT stores the wave's popcount per edge into a [chunk][edge] matrix
+//                           (one chunk per wave), fitch_edge_scan_kernel turns every column into bases (and carries a per-edge cursor
+//                           from one range of chunks to the next), and EFILL walks again: a change goes to edge_off[e] +
+//                           base[chunk][e] + (the popcounts of the lower lanes) + (its rank inside the word).  Ascending, no atomic.
 //
 // The slab is sized from a byte budget, not from n x L (TRACS_FITCH_SLAB_GROUPS forces its length in groups of 128 sites).  Only the L
 // real bits of the last word count; pad samples are never read into the buffer; pad groups are never walked.  Every store of the
@@ -42,6 +47,11 @@ namespace {
 constexpr int FITCH_BITS = 25;                      // a site has at most 2n - 3 < 2^25 changes
 constexpr size_t FITCH_MAX_N = (size_t)1 << 21;     // (the leaves kernel's grid: n / 64 workgroups in y)
 constexpr size_t FITCH_SLAB_BYTES = 8ull << 30;     // the [node][word] buffer of one slab, at most
+constexpr size_t FITCH_MATRIX_BYTES = 256ull << 20; // the [chunk][edge] matrix of one range of tracs_fitch_edge_sites, at most
+constexpr unsigned FITCH_CHUNK_GROUPS = 16;         // a chunk is a wave of the walk: 64 words, 16 groups
+
+// what a walk leaves behind
+enum : int { FITCH_COUNT = 0, FITCH_FILL = 1, FITCH_ECOUNT = 2, FITCH_EFILL = 3 };
 
 __device__ __forceinline__ uint4 fitch_join(const uint4 a, const uint4 b)
 {
@@ -136,7 +146,9 @@ __global__ __launch_bounds__(256) void fitch_leaves_kernel(const uint4 *__restri
 
 // Both passes for the words [word0, word0 + n_words) of a slab (lane = word), sites [site_begin, site_end) only.  child: the edge
 // list's child column (device); every lane reads the same entries.
-template <bool FILL>
+// ECOUNT: edge_changes is the launch's part of the chunk matrix, [blockIdx.x][edge]; every (chunk, edge) is stored.  EFILL: edge_changes
+// is that part after the scan (bases), off is edge_off, site is edge_site and room its capacity; base, edge, info are not used.
+template <int MODE>
 __global__ __launch_bounds__(64) void fitch_walk_kernel(uint4 *__restrict__ buf, size_t stride, unsigned n, const unsigned *__restrict__ child,
                                                         unsigned word0, unsigned n_words, unsigned site_begin, unsigned site_end,
                                                         unsigned *__restrict__ edge_changes, unsigned *__restrict__ site_changes,
@@ -163,9 +175,37 @@ __global__ __launch_bounds__(64) void fitch_walk_kernel(uint4 *__restrict__ buf,
 #pragma unroll
     for (int k = 0; k < 14; k++) mn[k] = ~0u;
 
+    const size_t n_edges = n >= 3 ? 2 * (size_t)n - 3 : (size_t)n - 1;
     // one edge of the top-down walk: e, its changes among the valid sites, both states
     auto emit = [&](unsigned e, unsigned ch, const uint4 fp, const uint4 fc) {
-        if (!FILL) {
+        if (MODE == FITCH_ECOUNT) {
+            unsigned c = 0;
+            if (__ballot(ch != 0)) {                                       // (wave-uniform)
+                c = __popc(ch);
+                for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s, 64);
+            }
+            if (lane == 0) edge_changes[(size_t)blockIdx.x * n_edges + e] = c;
+            return;
+        }
+        if (MODE == FITCH_EFILL) {
+            if (!__ballot(ch != 0)) return;                                // (wave-uniform)
+            const unsigned c = __popc(ch);
+            unsigned incl = c;
+            for (int o = 1; o < 64; o <<= 1) { const unsigned x = __shfl_up(incl, o, 64); if (lane >= (unsigned)o) incl += x; }
+            if (ch) {
+                long long dst = off[e] + (long long)edge_changes[(size_t)blockIdx.x * n_edges + e] + (long long)(incl - c);
+                const long long cap = min(off[e + 1], room);
+                unsigned r = ch;
+                while (r) {
+                    const int b = __ffs(r) - 1;
+                    r &= r - 1;
+                    if (dst >= 0 && dst < cap) site[dst] = w * 32 + (unsigned)b;
+                    dst++;
+                }
+            }
+            return;
+        }
+        if (MODE == FITCH_COUNT) {
             if (__ballot(ch != 0)) {                                       // (wave-uniform)
                 unsigned c = __popc(ch);
                 for (int s = 32; s > 0; s >>= 1) c += __shfl_xor(c, s, 64);
@@ -202,14 +242,14 @@ __global__ __launch_bounds__(64) void fitch_walk_kernel(uint4 *__restrict__ buf,
     };
 
     if (n == 1) {
-        if (active && !FILL) fitch_min_add(mn, col[0]);
+        if (active && MODE == FITCH_COUNT) fitch_min_add(mn, col[0]);
     } else if (n == 2) {
         // the one edge (0, 1): f_0 = lowbit(m_0 & m_1), or lowbit(m_0) where that is empty
         uint4 f0 = zero4, f1 = zero4;
         unsigned ch = 0;
         if (active) {
             const uint4 m0 = col[0], m1 = col[stride];
-            if (!FILL) { fitch_min_add(mn, m0); fitch_min_add(mn, m1); }
+            if (MODE == FITCH_COUNT) { fitch_min_add(mn, m0); fitch_min_add(mn, m1); }
             f0 = fitch_low(fitch_top(m0, m1));
             f1 = fitch_child(f0, m1, ch);
             ch &= valid;
@@ -221,7 +261,7 @@ __global__ __launch_bounds__(64) void fitch_walk_kernel(uint4 *__restrict__ buf,
             const unsigned a = child[2 * t], b = child[2 * t + 1];
             if (active) {
                 const uint4 sa = col[(size_t)a * stride], sb = col[(size_t)b * stride];
-                if (!FILL) {
+                if (MODE == FITCH_COUNT) {
                     if (a < n) fitch_min_add(mn, sa);
                     if (b < n) fitch_min_add(mn, sb);
                 }
@@ -232,7 +272,7 @@ __global__ __launch_bounds__(64) void fitch_walk_kernel(uint4 *__restrict__ buf,
         uint4 ft = zero4;
         if (active) {
             const uint4 sx = col[(size_t)x * stride], sy = col[(size_t)y * stride], sz = col[(size_t)z * stride];
-            if (!FILL) {
+            if (MODE == FITCH_COUNT) {
                 if (x < n) fitch_min_add(mn, sx);
                 if (y < n) fitch_min_add(mn, sy);
                 if (z < n) fitch_min_add(mn, sz);
@@ -250,7 +290,7 @@ __global__ __launch_bounds__(64) void fitch_walk_kernel(uint4 *__restrict__ buf,
             down(2 * t + 1, b, fp);
         }
     }
-    if (!FILL && valid) {
+    if (MODE == FITCH_COUNT && valid) {
         const unsigned one = mn[0] | mn[1] | mn[2] | mn[3];
         const unsigned two = mn[4] | mn[5] | mn[6] | mn[7] | mn[8] | mn[9];
         const unsigned three = mn[10] | mn[11] | mn[12] | mn[13];
@@ -299,19 +339,22 @@ int fitch_check(const tracs_alignment *a, const char *who)
     return TRACS_OK;
 }
 
-// Sites [site_begin, site_end) slab by slab: the leaves, then the walk.  The tree was checked.
-template <bool FILL>
-int fitch_run(const tracs_alignment *a, const uint32_t *child, size_t n_edges, size_t site_begin, size_t site_end, unsigned *edge_changes,
-              unsigned *site_changes, uint8_t *site_minimum, const long long *off, long long base, size_t room, unsigned *site, unsigned *edge,
-              unsigned *info, hipStream_t stream)
+// The slabs of the groups [g_begin, g_end): the slab's length (at most max_slab groups when that is not 0), the node buffer and the
+// child column on the device.  The tree was checked.
+struct FitchSlabs {
+    size_t slab = 0, stride = 0, W = 0, nodes = 0;
+    uint4 *buf = nullptr;
+    unsigned *d_child = nullptr;
+};
+int fitch_slabs(const tracs_alignment *a, const uint32_t *child, size_t n_edges, size_t g_begin, size_t g_end, size_t max_slab, FitchSlabs &S,
+                hipStream_t stream)
 {
-    if (site_begin >= site_end) return TRACS_OK;
     const size_t n = a->n, nodes = n >= 3 ? 2 * n - 2 : n;
-    const size_t g_begin = site_begin / SITES_PER_GROUP, g_end = groups_for(site_end);
     size_t slab = std::max<size_t>(1, FITCH_SLAB_BYTES / (nodes * 64));
     if (slab >= 16) slab &= ~(size_t)15;                                   // (whole waves of words)
     if (const char *e = std::getenv("TRACS_FITCH_SLAB_GROUPS")) slab = std::max<size_t>(1, (size_t)std::strtoull(e, nullptr, 10));
     slab = std::min(slab, g_end - g_begin);
+    if (max_slab) slab = std::min(slab, max_slab);
     int rc;
     uint4 *buf = nullptr;
     while (!workspace_try(WS_FITCH_NODES, nodes * slab * 4, &buf)) {      // (no room for the budget: shorter slabs)
@@ -324,19 +367,81 @@ int fitch_run(const tracs_alignment *a, const uint32_t *child, size_t n_edges, s
         TRACS_HIP_CHECK(hipMemcpyAsync(d_child, child, n_edges * 4, hipMemcpyHostToDevice, stream));
         TRACS_HIP_CHECK(hipStreamSynchronize(stream));                     // (the edges are the caller's memory)
     }
-    const size_t stride = slab * 4;
-    const size_t W = (a->L + 31) / 32;
-    for (size_t g0 = g_begin; g0 < g_end; g0 += slab) {
-        const size_t sg = std::min(slab, g_end - g0);
-        const size_t words = std::min(sg * 4, W - g0 * 4);
-        hipLaunchKernelGGL(fitch_leaves_kernel, dim3((unsigned)((sg + 3) / 4), (unsigned)((n + 63) / 64)), dim3(256), 0, stream, a->planes,
-                           (unsigned)n, a->n_pad, g0, (unsigned)sg, buf, stride);
-        hipLaunchKernelGGL(fitch_walk_kernel<FILL>, dim3((unsigned)((words + 63) / 64)), dim3(64), 0, stream, buf, stride, (unsigned)n, d_child,
-                           (unsigned)(g0 * 4), (unsigned)words, (unsigned)site_begin, (unsigned)site_end, edge_changes, site_changes, site_minimum,
-                           off, base, (long long)room, site, edge, info);
-    }
+    S.slab = slab; S.stride = slab * 4; S.W = (a->L + 31) / 32; S.nodes = nodes; S.buf = buf; S.d_child = d_child;
+    return TRACS_OK;
+}
+
+// one slab from group g0: the leaves, then the walk; -> the waves (chunks) of the walk
+template <int MODE>
+size_t fitch_slab_launch(const tracs_alignment *a, const FitchSlabs &S, size_t g0, size_t g_end, size_t site_begin, size_t site_end,
+                         unsigned *edge_changes, unsigned *site_changes, uint8_t *site_minimum, const long long *off, long long base, size_t room,
+                         unsigned *site, unsigned *edge, unsigned *info, hipStream_t stream)
+{
+    const size_t n = a->n;
+    const size_t sg = std::min(S.slab, g_end - g0);
+    const size_t words = std::min(sg * 4, S.W - g0 * 4);
+    const size_t waves = (words + 63) / 64;
+    hipLaunchKernelGGL(fitch_leaves_kernel, dim3((unsigned)((sg + 3) / 4), (unsigned)((n + 63) / 64)), dim3(256), 0, stream, a->planes,
+                       (unsigned)n, a->n_pad, g0, (unsigned)sg, S.buf, S.stride);
+    hipLaunchKernelGGL(fitch_walk_kernel<MODE>, dim3((unsigned)waves), dim3(64), 0, stream, S.buf, S.stride, (unsigned)n, S.d_child,
+                       (unsigned)(g0 * 4), (unsigned)words, (unsigned)site_begin, (unsigned)site_end, edge_changes, site_changes, site_minimum,
+                       off, base, (long long)room, site, edge, info);
+    return waves;
+}
+
+// Sites [site_begin, site_end) slab by slab: the leaves, then the walk.  The tree was checked.
+template <int MODE>
+int fitch_run(const tracs_alignment *a, const uint32_t *child, size_t n_edges, size_t site_begin, size_t site_end, unsigned *edge_changes,
+              unsigned *site_changes, uint8_t *site_minimum, const long long *off, long long base, size_t room, unsigned *site, unsigned *edge,
+              unsigned *info, hipStream_t stream)
+{
+    if (site_begin >= site_end) return TRACS_OK;
+    const size_t g_begin = site_begin / SITES_PER_GROUP, g_end = groups_for(site_end);
+    FitchSlabs S;
+    int rc;
+    if ((rc = fitch_slabs(a, child, n_edges, g_begin, g_end, 0, S, stream))) return rc;
+    for (size_t g0 = g_begin; g0 < g_end; g0 += S.slab)
+        fitch_slab_launch<MODE>(a, S, g0, g_end, site_begin, site_end, edge_changes, site_changes, site_minimum, off, base, room, site, edge, info,
+                                stream);
     TRACS_HIP_CHECK(hipGetLastError());
     return TRACS_OK;
+}
+
+// Every column of a range's [chunks][n_edges] matrix from counts to bases: base[c][e] = cursor[e] + (the counts of the chunks before c);
+// cursor[e] moves on by the range's sum.  One thread per edge: the loads of a step are coalesced across edges.
+__global__ __launch_bounds__(256) void fitch_edge_scan_kernel(unsigned *__restrict__ matrix, size_t chunks, size_t n_edges,
+                                                              unsigned *__restrict__ cursor)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_edges) return;
+    unsigned run = cursor[e];
+    for (size_t c = 0; c < chunks; c++) {
+        const unsigned v = matrix[c * n_edges + e];
+        matrix[c * n_edges + e] = run;
+        run += v;
+    }
+    cursor[e] = run;
+}
+
+// info |= 256 on the entries (site, edge) of a filled batch that `dropped` marks: the entry is looked up in its edge's ascending
+// segment of edge_site.  An entry whose edge or site is not there is left alone.
+__global__ __launch_bounds__(256) void fitch_mark_kernel(const unsigned *__restrict__ site, const unsigned *__restrict__ edge,
+                                                         unsigned *__restrict__ info, size_t n_entries, size_t n_edges,
+                                                         const long long *__restrict__ edge_off, const unsigned *__restrict__ edge_site,
+                                                         const uint8_t *__restrict__ dropped)
+{
+    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n_entries; k += (size_t)gridDim.x * 256) {
+        const unsigned e = edge[k], s = site[k];
+        if (e >= n_edges) continue;
+        long long lo = edge_off[e];
+        const long long end = edge_off[e + 1];
+        long long hi = end;
+        while (lo < hi) {
+            const long long mid = (lo + hi) >> 1;
+            if (edge_site[mid] < s) lo = mid + 1; else hi = mid;
+        }
+        if (lo < end && edge_site[lo] == s && dropped[lo]) info[k] |= 256u;
+    }
 }
 
 }  // namespace
@@ -353,7 +458,7 @@ int fitch_count(const tracs_alignment *a, const uint32_t *parent, const uint32_t
     unsigned long long *sums;
     if ((rc = workspace_get(WS_FITCH_SUMS, offsets_scan_sums(a->L), &sums))) return rc;
     if (n_edges) TRACS_HIP_CHECK(hipMemsetAsync(edge_changes, 0, n_edges * 4, stream));
-    if ((rc = fitch_run<false>(a, child, n_edges, 0, a->L, edge_changes, site_changes, site_minimum, nullptr, 0, 0, nullptr, nullptr, nullptr, stream)) ||
+    if ((rc = fitch_run<FITCH_COUNT>(a, child, n_edges, 0, a->L, edge_changes, site_changes, site_minimum, nullptr, 0, 0, nullptr, nullptr, nullptr, stream)) ||
         (rc = offsets_scan_launch(site_changes, a->L, sums, off, stream))) return rc;
     long long tot = 0;
     TRACS_HIP_CHECK(hipMemcpyAsync(&tot, off + a->L, 8, hipMemcpyDeviceToHost, stream));
@@ -372,7 +477,67 @@ int fitch_fill(const tracs_alignment *a, const uint32_t *parent, const uint32_t 
     if (site_begin == site_end || !room || !n_edges) return TRACS_OK;
     if (!off || !site || !edge || !info) { set_error("tracs_fitch_fill: NULL argument"); return TRACS_E_ARG; }
     DeviceCall guard(stream);
-    return fitch_run<true>(a, child, n_edges, site_begin, site_end, nullptr, nullptr, nullptr, off, base, room, site, edge, info, stream);
+    return fitch_run<FITCH_FILL>(a, child, n_edges, site_begin, site_end, nullptr, nullptr, nullptr, off, base, room, site, edge, info, stream);
+}
+
+// The changes regrouped by edge.  edge_changes: fitch_count's (device); edge_off[0 .. n_edges] <- its exclusive scan;
+// edge_site[edge_off[e] .. edge_off[e + 1]) <- the sites with a change on e, ascending; nothing is stored outside [0, room).
+// The [chunk][edge] matrix holds a range of whole slabs at a time (FITCH_MATRIX_BYTES; TRACS_FITCH_MATRIX_CHUNKS: chunks per range,
+// diagnostic -- it also shortens the slab to that many chunks).
+int fitch_edge_sites(const tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, const unsigned *edge_changes,
+                     long long *edge_off, unsigned *edge_site, size_t room, hipStream_t stream)
+{
+    int rc = fitch_check(a, "tracs_fitch_edge_sites");
+    if (rc || (rc = fitch_tree_check("tracs_fitch_edge_sites", a->n, parent, child, n_edges))) return rc;
+    if (!edge_off || (n_edges && !edge_changes) || (room && !edge_site)) { set_error("tracs_fitch_edge_sites: NULL argument"); return TRACS_E_ARG; }
+    DeviceCall guard(stream);
+    if (!n_edges) {
+        TRACS_HIP_CHECK(hipMemsetAsync(edge_off, 0, 8, stream));
+        return TRACS_OK;
+    }
+    unsigned long long *sums;
+    if ((rc = workspace_get(WS_FITCH_SUMS, offsets_scan_sums(std::max<size_t>(n_edges, a->L)), &sums)) ||
+        (rc = offsets_scan_launch(edge_changes, n_edges, sums, edge_off, stream))) return rc;
+    if (!room || !a->L) return TRACS_OK;
+    const size_t g_end = groups_for(a->L);
+    size_t range_chunks = std::max<size_t>(1, FITCH_MATRIX_BYTES / (n_edges * 4));
+    if (const char *e = std::getenv("TRACS_FITCH_MATRIX_CHUNKS")) range_chunks = std::max<size_t>(1, (size_t)std::strtoull(e, nullptr, 10));
+    FitchSlabs S;
+    // (a slab of g groups walks ceil(g / 16) chunks: one that outgrows the range is cut to whole chunks)
+    if ((rc = fitch_slabs(a, child, n_edges, 0, g_end, range_chunks * FITCH_CHUNK_GROUPS, S, stream))) return rc;
+    const size_t slab_chunks = (S.slab * 4 + 63) / 64;
+    const size_t range_slabs = std::max<size_t>(1, range_chunks / slab_chunks);
+    const size_t total_slabs = (g_end + S.slab - 1) / S.slab;
+    unsigned *matrix, *cursor;
+    if ((rc = workspace_get(WS_FITCH_MATRIX, std::min(range_slabs, total_slabs) * slab_chunks * n_edges, &matrix)) ||
+        (rc = workspace_get(WS_FITCH_CURSOR, n_edges, &cursor))) return rc;
+    TRACS_HIP_CHECK(hipMemsetAsync(cursor, 0, n_edges * 4, stream));
+    for (size_t r0 = 0; r0 < g_end; r0 += range_slabs * S.slab) {
+        const size_t r1 = std::min(g_end, r0 + range_slabs * S.slab);
+        size_t chunks = 0;
+        for (size_t g0 = r0; g0 < r1; g0 += S.slab)
+            chunks += fitch_slab_launch<FITCH_ECOUNT>(a, S, g0, g_end, 0, a->L, matrix + chunks * n_edges, nullptr, nullptr, nullptr, 0, 0, nullptr,
+                                                      nullptr, nullptr, stream);
+        hipLaunchKernelGGL(fitch_edge_scan_kernel, dim3((unsigned)((n_edges + 255) / 256)), dim3(256), 0, stream, matrix, chunks, n_edges, cursor);
+        chunks = 0;
+        for (size_t g0 = r0; g0 < r1; g0 += S.slab)
+            chunks += fitch_slab_launch<FITCH_EFILL>(a, S, g0, g_end, 0, a->L, matrix + chunks * n_edges, nullptr, nullptr, edge_off, 0, room, edge_site,
+                                                     nullptr, nullptr, stream);
+    }
+    TRACS_HIP_CHECK(hipGetLastError());
+    return TRACS_OK;
+}
+
+// Bit 8 of info on the entries of a filled batch that the branch filter drops (tracs_fitch_mark_dropped)
+int fitch_mark_dropped(const unsigned *site, const unsigned *edge, unsigned *info, size_t n_entries, size_t n_edges, const long long *edge_off,
+                       const unsigned *edge_site, const uint8_t *dropped, hipStream_t stream)
+{
+    if (!n_entries) return TRACS_OK;
+    if (!site || !edge || !info || !edge_off || !edge_site || !dropped) { set_error("tracs_fitch_mark_dropped: NULL argument"); return TRACS_E_ARG; }
+    const unsigned blocks = (unsigned)std::min<size_t>((n_entries + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(fitch_mark_kernel, dim3(blocks), dim3(256), 0, stream, site, edge, info, n_entries, n_edges, edge_off, edge_site, dropped);
+    TRACS_HIP_CHECK(hipGetLastError());
+    return TRACS_OK;
 }
 
 // ---- the rows of --tree-changes and --tree-sites ---------------------------------------------------------------------------------------
@@ -417,10 +582,11 @@ int fitch_tables(const tracs_alignment *a, const uint32_t *parent, const uint32_
 // After fitch_tables: the change rows appended to changes_path (may be NULL) and the site rows to sites_path (may be NULL).  The
 // entries come in batches of sites: device entry buffer -> pinned host buffer -> rows formatted on host threads and appended in order.
 // The two buffers hold at most 256 MiB each (TRACS_FITCH_BATCH: entries per batch instead, for tests), or one site's entries when a
-// site has more.  kept / source_len / contigs: as pair_sites_write.
+// site has more.  kept / source_len / contigs: as pair_sites_write.  flt != NULL (--tree-filter): every batch is marked
+// with the branch filter's verdicts and the change rows carry a dropped field (0 / 1) before ref.
 int fitch_write(const tracs_alignment *a, const char *const *names, const uint64_t *kept, size_t source_len, const uint32_t *parent,
                 const uint32_t *child, size_t n_edges, const FitchTables &t, const char *changes_path, const char *sites_path, const char *ref,
-                const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs, int n_threads)
+                const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs, int n_threads, const FitchFilter *flt)
 {
     const size_t n = a->n, L = a->L;
     if (!names || !ref || (n_contigs && (!contig_names || !contig_lengths))) { set_error("tracs_distance_tree_changes: NULL argument"); return TRACS_E_ARG; }
@@ -524,6 +690,8 @@ int fitch_write(const tracs_alignment *a, const char *const *names, const uint64
         const size_t entries = (size_t)(off[s1] - base);
         if (entries) {
             if ((rc = fitch_fill(a, parent, child, n_edges, s0, s1, t.d_off, base, d_ent, d_ent + room, d_ent + 2 * room, room, nullptr))) return done(rc);
+            if (flt && (rc = fitch_mark_dropped(d_ent, d_ent + room, d_ent + 2 * room, entries, n_edges, flt->d_edge_off, flt->d_edge_site,
+                                                flt->d_dropped, nullptr))) return done(rc);
             for (int q = 0; q < 3; q++) FW_CHECK(hipMemcpy(h_ent + q * room, d_ent + q * room, entries * 4, hipMemcpyDeviceToHost));
             const unsigned *h_site = h_ent, *h_edge = h_ent + room, *h_info = h_ent + 2 * room;
             auto format = [&](size_t k, size_t e0, size_t e1) {
@@ -539,6 +707,7 @@ int fitch_write(const tracs_alignment *a, const char *const *names, const uint64
                     s += ',';
                     s += letters[(v >> 4) & 15u];
                     s += ',';
+                    if (flt) { s += (v & 256u) ? '1' : '0'; s += ','; }
                     s += ref;
                     s += '\n';
                 }
@@ -583,6 +752,21 @@ int tracs_fitch_fill(const tracs_alignment *a, const uint32_t *parent, const uin
 {
     return fitch_fill(a, parent, child, n_edges, site_begin, site_end, reinterpret_cast<const long long *>(off), (long long)entry_base, site, edge,
                       info, room, static_cast<hipStream_t>(stream));
+}
+
+int tracs_fitch_edge_sites(const tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, const uint32_t *edge_changes,
+                           int64_t *edge_off, uint32_t *edge_site, size_t room, void *stream)
+{
+    return fitch_edge_sites(a, parent, child, n_edges, edge_changes, reinterpret_cast<long long *>(edge_off), edge_site, room,
+                            static_cast<hipStream_t>(stream));
+}
+
+int tracs_fitch_mark_dropped(const uint32_t *site, const uint32_t *edge, uint32_t *info, size_t n_entries, size_t n_edges, const int64_t *edge_off,
+                             const uint32_t *edge_site, const uint8_t *dropped, void *stream)
+{
+    DeviceCall guard(static_cast<hipStream_t>(stream));
+    return fitch_mark_dropped(site, edge, info, n_entries, n_edges, reinterpret_cast<const long long *>(edge_off), edge_site, dropped,
+                              static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -462,10 +462,10 @@ void append_label(std::string &out, const char *name)
 // transfer != NULL (tracs_tree_write_transfer, with support): the label is the edge's transfer support instead, written like a length
 // (NaN: none), and the edge rows have a transfer field behind the support field.
 // changes != NULL (tracs_tree_write_changes, without support): the edge rows have a changes field before ref; the Newick line is
-// tracs_tree_write's.
+// tracs_tree_write's.  filtered != NULL (tracs_tree_write_filtered, with changes): a filtered field behind the changes field.
 static int tree_write_body(const char *who, const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
                            size_t n_edges, const uint32_t *support, const double *transfer, const char *path, const char *ref,
-                           const char *edges_path, const uint32_t *changes = nullptr)
+                           const char *edges_path, const uint32_t *changes = nullptr, const uint32_t *filtered = nullptr)
 {
     constexpr uint32_t NO_SUPPORT = 0xFFFFFFFFu;
     if (!path || (n && !names) || (n_edges && (!parent || !child || !length)) || (edges_path && !ref)) {
@@ -541,6 +541,7 @@ static int tree_write_body(const char *who, const char *const *names, size_t n, 
             node_name(child[e]); rows.push_back(',');
             append_length(rows, length[e]); rows.push_back(',');
             if (changes) { rows += std::to_string(changes[e]); rows.push_back(','); }
+            if (filtered) { rows += std::to_string(filtered[e]); rows.push_back(','); }
             if (support) {
                 if (child[e] >= n && n >= 3 && support[e] != NO_SUPPORT) rows += std::to_string(support[e]);
                 else rows += "NA";
@@ -578,6 +579,18 @@ int tracs_tree_write_changes(const char *const *names, size_t n, const uint32_t 
     static const uint32_t none = 0;
     return tree_write_body("tracs_tree_write_changes", names, n, parent, child, length, n_edges, nullptr, nullptr, path, ref, edges_path,
                            n_edges ? changes : &none);
+}
+
+// tracs_tree_write_changes with the changes the branch filter keeps on every edge: the same Newick line, and the rows
+// parent,child,length,changes,filtered,ref.
+int tracs_tree_write_filtered(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
+                              size_t n_edges, const uint32_t *changes, const uint32_t *filtered, const char *path, const char *ref,
+                              const char *edges_path)
+{
+    if (n_edges && (!changes || !filtered)) { set_error("tracs_tree_write_filtered: NULL argument"); return TRACS_E_ARG; }
+    static const uint32_t none = 0;
+    return tree_write_body("tracs_tree_write_filtered", names, n, parent, child, length, n_edges, nullptr, nullptr, path, ref, edges_path,
+                           n_edges ? changes : &none, n_edges ? filtered : &none);
 }
 
 // tracs_tree_write with bootstrap support: `(A:1,B:2)87:0.5`, and the rows parent,child,length,support,ref.

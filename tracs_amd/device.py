@@ -737,6 +737,53 @@ def fitch_fill(aln, parent, child, off, site_begin=0, site_end=None, entry_base=
     return out[0][:k], out[1][:k], out[2][:k]
 
 
+def fitch_edge_sites(aln, parent, child, edge_changes, room=None, out=None):
+    """The changes regrouped by edge (tracs_fitch_edge_sites), after fitch_count gave edge_changes: -> (edge_off torch.int64
+    [n_edges + 1], edge_site torch.int32) on the device, the sites with a change on edge e at [edge_off[e], edge_off[e + 1]), ascending.
+    room: the entries edge_site holds (by default the total); out: a buffer to fill instead of a new one (nothing is written beyond
+    room)."""
+    L = _lib.require_gpu()
+    parent, child = _tree_arrays(parent, child)
+    ne = len(parent)
+    assert edge_changes.is_cuda and edge_changes.is_contiguous() and edge_changes.element_size() == 4 and edge_changes.numel() >= ne
+    total = int(edge_changes[:ne].to(torch.int64).sum().item()) if ne else 0
+    room = total if room is None else int(room)
+    edge_off = torch.zeros(ne + 1, dtype=torch.int64, device=edge_changes.device)
+    if out is None:
+        out = torch.zeros(max(room, 1), dtype=torch.int32, device=edge_changes.device)
+    assert out.is_cuda and out.is_contiguous() and out.element_size() == 4 and out.numel() >= room
+    _lib.check(L.tracs_fitch_edge_sites(aln._h, parent.ctypes.data, child.ctypes.data, ne, _ptr(edge_changes), _ptr(edge_off), _ptr(out), room,
+                                        _stream()))
+    torch.cuda.current_stream().synchronize()              # (the edges are host arrays of this call)
+    return edge_off, out[:min(total, room)]
+
+
+def filter_recomb_lists(aln, off, pos, with_dropped=True):
+    """The recombination filter (src/pairsnp.hpp:251-318) on sorted position lists (tracs_filter_recomb_lists): list t is
+    pos[off[t] : off[t + 1]] (off torch.int64 [m + 1] from 0, pos 32-bit, both on the device; every list ascending and below aln.L)
+    -> (filt torch.int32 [m], the entries kept per list; dropped torch.uint8 [len(pos)], 1 on the entries dropped, or None)."""
+    L = _lib.require_gpu()
+    m = int(off.numel()) - 1
+    assert m >= 0 and off.is_cuda and off.is_contiguous() and off.dtype == torch.int64
+    assert pos.is_cuda and pos.is_contiguous() and pos.element_size() == 4 and not pos.is_floating_point()
+    k = int(pos.numel())
+    filt = torch.zeros(max(m, 1), dtype=torch.int32, device=off.device)
+    dropped = torch.zeros(max(k, 1), dtype=torch.uint8, device=off.device) if with_dropped else None
+    if m:
+        _lib.check(L.tracs_filter_recomb_lists(aln._h, _ptr(off), _ptr(pos), m, k, _ptr(filt), _ptr(dropped), _stream()))
+    return filt[:m], (dropped[:k] if with_dropped else None)
+
+
+def fitch_mark_dropped(site, edge, info, edge_off, edge_site, dropped):
+    """Bit 8 of info on the entries of fitch_fill that the branch filter drops (tracs_fitch_mark_dropped): in place, -> info."""
+    L = _lib.require_gpu()
+    k = int(info.numel())
+    assert site.numel() == k and edge.numel() == k
+    _lib.check(L.tracs_fitch_mark_dropped(_ptr(site), _ptr(edge), _ptr(info), k, int(edge_off.numel()) - 1, _ptr(edge_off), _ptr(edge_site),
+                                          _ptr(dropped), _stream()))
+    return info
+
+
 def filter_index_info(aln):
     """Diagnostics of the alignment's filter index (None before the first filter call)."""
     import ctypes as C

@@ -50,6 +50,8 @@ TREE_EDGES_TRANSFER_HEADER = "parent,child,length,support,transfer,MSA file\n"  
 TREE_EDGES_CHANGES_HEADER = "parent,child,length,changes,MSA file\n"         # with --tree-changes / --tree-sites
 TREE_CHANGES_HEADER = "parent,child,contig,position,alleleParent,alleleChild,MSA file\n"
 TREE_SITES_HEADER = "contig,position,changes,minimum,MSA file\n"
+TREE_EDGES_FILTER_HEADER = "parent,child,length,changes,filtered,MSA file\n"         # with --tree-filter
+TREE_CHANGES_FILTER_HEADER = "parent,child,contig,position,alleleParent,alleleChild,dropped,MSA file\n"
 
 TREE_DISTANCES = {"snp": 0, "per-site": 1}
 
@@ -161,8 +163,22 @@ def distance_parser(parser):
                           "tree (see --tree-changes): minimum is the fewest changes any tree needs at the site, and changes - minimum is "
                           "the site's homoplasy -- recombination, hotspots, mapping artefacts.  Not with --bootstrap.")
     snp.add_argument("--max-entries", dest="max_entries", type=check_max_entries, default=None, metavar="N",
-                     help="With --tree-changes: refuse, before anything is written, when the tree has more than N changes in all "
-                          "(default=100000000)")
+                     help="With --tree-changes or --tree-filter: refuse, before anything is written, when the tree has more than N "
+                          "changes in all (default=100000000)")
+    snp.add_argument("--tree-filter", dest="tree_filter", action="store_true", default=False,
+                     help="With --tree and at least one of --tree-edges, --tree-changes, --tree-filtered: run the recombination filter "
+                          "of --filter on the changes of every branch (see --tree-changes) instead of on pairs.  A branch's changes are "
+                          "what its parent and child states differ by; with d of them in an alignment of L compared sites, a change is "
+                          "dropped when the window around it (half width clamp(L / 2d + 1, 50, 5000) sites) holds more changes of that "
+                          "branch than a binomial density d / L explains at 0.05 / d.  --tree-edges gains a filtered column (the changes "
+                          "kept on the branch) after changes, --tree-changes a dropped column (0 / 1) before MSA file, and one line on "
+                          "stderr counts changes, kept, dropped and the branches with a drop.  The tree is still built from the "
+                          "UNFILTERED distances: the filter is not iterated into the topology.  The verdicts belong to the placement "
+                          "that --tree-changes writes, one most-parsimonious reconstruction among possibly several.  Not with "
+                          "--bootstrap.  Not in the reference.")
+    snp.add_argument("--tree-filtered", dest="tree_filtered", default=None, type=str, metavar="FILE",
+                     help="With --tree-filter: write one Newick tree per --msa file with the topology and labels of -o and the number "
+                          "of changes that --tree-filter keeps on each branch as its length")
     snp.add_argument("--bootstrap", dest="bootstrap", default=None, type=int, metavar="B",
                      help="With --tree: B >= 1 bootstrap replicates, resampled and built on the GPU.  A replicate draws as many columns "
                           "as the run compares, with replacement, and goes through the same distances and the same neighbour joining.  "
@@ -454,6 +470,11 @@ def check_tree_args(args):
                 raise SystemExit("tracs distance: %s needs --tree (it places the sites on the tree that --tree builds)" % opt)
         if args.max_entries is not None:
             raise SystemExit("tracs distance: --max-entries needs --tree-changes, which needs --tree (it bounds the rows of that file)")
+        if getattr(args, "tree_filter", False):
+            raise SystemExit("tracs distance: --tree-filter needs --tree (it filters the changes on the branches of the tree that --tree builds)")
+        if getattr(args, "tree_filtered", None) is not None:
+            raise SystemExit("tracs distance: --tree-filtered needs --tree-filter, which needs --tree (it holds the tree with the kept changes "
+                             "as branch lengths)")
         return
     for opt, given in (("--nearest", args.nearest is not None), ("--mst", args.mst is not None),
                        ("--ancestors", args.ancestors is not None), ("--histogram", args.histogram)):
@@ -490,7 +511,16 @@ def check_tree_args(args):
         if value is not None and args.bootstrap is not None:
             raise SystemExit("tracs distance: %s and --bootstrap cannot be combined yet (the tree is reproducible bit for bit: run once with "
                              "each and join the two --tree-edges files on parent and child)" % opt)
-    if args.max_entries is not None and args.tree_changes is None:
+    tree_filter, tree_filtered = getattr(args, "tree_filter", False), getattr(args, "tree_filtered", None)
+    if tree_filtered is not None and not tree_filter:
+        raise SystemExit("tracs distance: --tree-filtered needs --tree-filter (it holds the tree with the kept changes as branch lengths)")
+    if tree_filter:
+        if args.bootstrap is not None:
+            raise SystemExit("tracs distance: --tree-filter and --bootstrap cannot be combined yet (the tree is reproducible bit for bit: run "
+                             "once with each and join the two --tree-edges files on parent and child)")
+        if args.tree_edges is None and args.tree_changes is None and tree_filtered is None:
+            raise SystemExit("tracs distance: --tree-filter needs --tree-edges, --tree-changes or --tree-filtered (the files its verdicts go to)")
+    if args.max_entries is not None and args.tree_changes is None and not tree_filter:
         raise SystemExit("tracs distance: --max-entries needs --tree-changes (it bounds the rows of that file; --tree-sites has at most one "
                          "row per site)")
     check_output_paths("distance", _inputs(args), dict(_outputs(args), **{"--tree-edges": args.tree_edges}), ["--tree-edges"])
@@ -499,12 +529,32 @@ def check_tree_args(args):
     check_output_paths("distance", _inputs(args), tree_outputs, ["--tree-sites"])
     check_output_paths("distance", _inputs(args), dict(_outputs(args), **{"--tree-edges": args.tree_edges, "--bootstrap-trees": args.bootstrap_trees}),
                        ["--bootstrap-trees"])
+    if tree_filtered is not None:
+        check_output_paths("distance", _inputs(args), dict(tree_outputs, **{"--tree-filtered": tree_filtered}), ["--tree-filtered"])
 
 
 def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None, tree_contigs=None):
     """--tree nj for one alignment (handle.DistanceHandle.tree, tracs_distance_tree: include/tracs_hip.h): every dense panel goes into the
     distance matrix on the device, the joins run there, and one Newick line (and the edge rows) are appended by the library."""
     with _opened(msas, args, stage, rule, contigs) as h:
+        if getattr(args, "tree_filter", False):
+            # (as below: the library creates the files itself, once the count has passed --max-entries)
+            try:
+                joins, rows, changes, minimum, kept, branches = h.tree(
+                    args.output_file, ref, per_site=TREE_DISTANCES[args.tree_distance or "snp"] == 1, edges_path=args.tree_edges,
+                    changes_path=args.tree_changes, sites_path=args.tree_sites, max_entries=args.max_entries, contigs=tree_contigs,
+                    n_threads=args.n_cpu, create=not getattr(args, "tree_files_made", False), tree_filter=True, filtered_path=args.tree_filtered)
+            except RuntimeError as e:
+                raise SystemExit("tracs distance: %s" % e)
+            args.tree_files_made = True
+            if args.tree_changes is not None or args.tree_sites is not None:
+                sys.stderr.write("tracs distance: %s: parsimony length %d, minimum %d, consistency index %s\n"
+                                 % (ref, changes, minimum, repr(minimum / changes) if changes else "1"))
+            sys.stderr.write("tracs distance: %s: tree filter: %d changes, %d kept, %d dropped, %d branches with a drop\n"
+                             % (ref, changes, kept, changes - kept, branches))
+            stage("[sum] tracs_distance_tree_filter (dense panels, joins, tree, Fitch count, edge lists, filter, fill: %d joins, %d edge rows, "
+                  "%d changes, %d kept)" % (joins, rows, changes, kept))
+            return
         if args.tree_changes is not None or args.tree_sites is not None:
             # (the library creates the four files itself, once the count has passed --max-entries: a refusal touches nothing)
             try:
@@ -930,7 +980,7 @@ def distance(args):
     logging.info("Loading metadata...")
     dates = _read_dates(args.metadata) if args.metadata is not None else None
     logging.info("Estimating transmission distances...")
-    tree_changes = args.tree is not None and (args.tree_changes is not None or args.tree_sites is not None)
+    tree_changes = args.tree is not None and (args.tree_changes is not None or args.tree_sites is not None or getattr(args, "tree_filter", False))
     if lead and not tree_changes:                  # (--tree-changes / --tree-sites: tracs_distance_tree_changes creates the run's files)
         with open(args.output_file, "w") as out:
             out.write("" if args.tree is not None else HISTOGRAM_HEADER if args.histogram else HEADER)      # (Newick lines: no header)

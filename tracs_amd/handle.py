@@ -127,7 +127,8 @@ class DistanceHandle:
         return source_records(self.L, "distance", self.h)
 
     def tree(self, path, ref, per_site=False, edges_path=None, bootstrap=0, seed=1, replicate_trees=None, support="split",
-             changes_path=None, sites_path=None, max_entries=None, contigs=None, n_threads=0, create=True):
+             changes_path=None, sites_path=None, max_entries=None, contigs=None, n_threads=0, create=True, tree_filter=False,
+             filtered_path=None):
         """The neighbour-joining tree of the handle's samples (tracs_distance_tree): one Newick line appended to `path`, the edge rows
         to edges_path.  bootstrap = B > 0 (tracs_distance_tree_bootstrap): B bootstrap replicates under `seed`; the internal nodes are
         labelled with the number of replicates that have their split, the edge rows gain a support field, and replicate_trees receives
@@ -136,15 +137,23 @@ class DistanceHandle:
         changes_path / sites_path (tracs_distance_tree_changes; no bootstrap): every site placed on the tree by Fitch's
         two passes -- one row per change, one per site with a change, and a changes field in the edge rows.  More than max_entries
         (default 10^8) changes are refused before any file is touched; create: the files are created with their headers (False: appended
-        to); contigs: [(name, length)] or None.  -> (joins, edge rows written, changes, sum of the sites' minimum)"""
+        to); contigs: [(name, length)] or None.  -> (joins, edge rows written, changes, sum of the sites' minimum)
+        tree_filter (tracs_distance_tree_filter; no bootstrap): the recombination filter's window test on the changes of
+        every branch -- the edge rows gain the kept changes, the change rows a dropped field, and filtered_path receives the tree whose
+        branch lengths are the kept changes.  The tree itself is built from the unfiltered distances; max_entries then bounds the edge
+        lists too.  -> (joins, edge rows written, changes, sum of the sites' minimum, changes kept, branches with a drop)"""
         if support not in ("split", "transfer"):
             raise ValueError("tree(): support is 'split' or 'transfer'")
         joins, rows = C.c_uint64(0), C.c_uint64(0)
         enc = lambda p: os.fsencode(p) if p is not None else None         # noqa: E731
-        if changes_path is not None or sites_path is not None:
+        if filtered_path is not None and not tree_filter:
+            raise ValueError("tree(): filtered_path needs tree_filter")
+        if tree_filter and edges_path is None and changes_path is None and filtered_path is None:
+            raise ValueError("tree(): tree_filter needs edges_path, changes_path or filtered_path")
+        if changes_path is not None or sites_path is not None or tree_filter:
             if bootstrap:
-                raise ValueError("tree(): changes_path / sites_path take no bootstrap")
-            if max_entries is not None and changes_path is None:
+                raise ValueError("tree(): changes_path / sites_path / tree_filter take no bootstrap")
+            if max_entries is not None and changes_path is None and not tree_filter:
                 raise ValueError("tree(): max_entries bounds the rows of changes_path")
             max_entries = 100000000 if max_entries is None else int(max_entries)
             if max_entries < 1:
@@ -153,6 +162,13 @@ class DistanceHandle:
             cnames = (C.c_char_p * max(nc, 1))(*[c[0].encode() for c in (contigs or [])])
             clens = (C.c_uint64 * max(nc, 1))(*[int(c[1]) for c in (contigs or [])])
             changes, minimum = C.c_uint64(0), C.c_uint64(0)
+            if tree_filter:
+                kept, dropped_edges = C.c_uint64(0), C.c_uint64(0)
+                _lib.check(self.L.tracs_distance_tree_filter(self.h, int(bool(per_site)), os.fsencode(path), ref.encode(), enc(edges_path),
+                                                             enc(changes_path), enc(sites_path), enc(filtered_path), cnames, clens, nc, max_entries,
+                                                             int(n_threads), int(bool(create)), C.byref(joins), C.byref(rows), C.byref(changes),
+                                                             C.byref(minimum), C.byref(kept), C.byref(dropped_edges)))
+                return joins.value, rows.value, changes.value, minimum.value, kept.value, dropped_edges.value
             _lib.check(self.L.tracs_distance_tree_changes(self.h, int(bool(per_site)), os.fsencode(path), ref.encode(), enc(edges_path),
                                                           enc(changes_path), enc(sites_path), cnames, clens, nc, max_entries, int(n_threads),
                                                           int(bool(create)), C.byref(joins), C.byref(rows), C.byref(changes),
