@@ -795,60 +795,86 @@ int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, doub
 int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, double lamb, double beta, double precision, double k_max,
                              int filter, int weight, const char *path, const char *ref, const char *tree_path,
                              const char *const *meta_dates, uint64_t *rows_written, uint64_t *n_eligible);
-/*   tracs_distance_tree `--tree nj` (not in the reference): the neighbour-joining tree (tracs_nj_*) of the handle's
- *                         samples, one alignment (no second file).  The panel walk without a threshold and without the pair rule;
- *                         every panel is loaded into the matrix (kind 0: SNP distances, 1: per compared site -- a pair compared
- *                         over 0 sites is refused by name), the joins run on the device, lengths are computed on the host.  One
- *                         Newick line is appended to `path`; edges_path != NULL: the 2n - 3 rows parent,child,length,ref are
- *                         appended to it (tracs_tree_write).  n_joins: n - 3; rows_written: the edge rows.                     */
+/*   tracs_distance_tree_run `--tree nj` and everything behind it (not in the reference): one request, one
+ *                         result, one body.  The main tree: the neighbour-joining tree (tracs_nj_*) of the handle's samples, one
+ *                         alignment (no second file).  The panel walk without a threshold and without the pair rule; every panel is
+ *                         loaded into the matrix (kind 0: SNP distances, 1: per compared site -- a pair compared over 0 sites is
+ *                         refused by name), the joins run on the device, lengths are computed on the host.  One Newick line is
+ *                         appended to `path`; edges_path != NULL: the 2n - 3 rows parent,child,length,..,ref are appended to it.
+ *                         Then at most one of two stages; a request with both is refused.
+ *                         replicates >= 1 (`--bootstrap B`; kind 0 only): bootstrap replicates b = 0 .. replicates - 1
+ *                         under `seed`: the columns at which two samples differ are selected once (the others add nothing to any
+ *                         replicate's distances), and per replicate the draws are counted over them, the replicate is gathered
+ *                         into a handle of its own (tracs_alignment_gather_sites; none drawn: the zero matrix), the same panel
+ *                         walk, load, joins and lengths give its tree, tracs_tree_support counts its splits, and the handle is
+ *                         freed.  The Newick line carries the counts as labels and the edge rows a support field
+ *                         (tracs_tree_write_support); n < 4: no labels, NA.  replicate_trees_path != NULL: each replicate's Newick
+ *                         line (no labels) is appended to it, in replicate order (n >= 4).  Bit-reproducible for a given (handle,
+ *                         replicates, seed).  transfer != 0 (`--bootstrap-support transfer`; needs replicates): the
+ *                         same main tree, replicates and replicate_trees_path bytes, with the transfer support beside the split
+ *                         count: after the main tree tracs_transfer_init, per replicate (after tracs_tree_support) its program and
+ *                         transfer_phi_kernel, after the last one tracs_transfer_emit.  The Newick labels are the transfer supports
+ *                         and the edge rows carry support,transfer (tracs_tree_write_transfer).
+ *                         changes != 0 (`--tree-changes / --tree-sites`; either kind): tracs_fitch_count on the main
+ *                         tree.  changes_path != NULL (or filter) and more than max_entries changes in all: refused with a message
+ *                         that states it, before any file is touched.  create != 0: the files are then created (the edge file with
+ *                         the header parent,child,length,changes,MSA file, the change file with
+ *                         parent,child,contig,position,alleleParent,alleleChild,MSA file, the site file with
+ *                         contig,position,changes,minimum,MSA file); 0: they are appended to (a second --msa file).  The edge rows
+ *                         gain a changes field (tracs_tree_write_changes); the change rows -- sites ascending, walk order within a
+ *                         site, nodes named as in the edge rows, alleles A/C/G/T, contig / position as tracs_distance_pair_sites
+ *                         writes them (contig_names, contig_lengths, n_contigs) -- come from tracs_fitch_fill in batches of sites:
+ *                         two buffers (device, pinned host) of at most 256 MiB (TRACS_FITCH_BATCH: entries per batch, diagnostic),
+ *                         rows formatted on n_threads host threads (<= 0: up to 16); the site rows list the sites with a change.
+ *                         filter != 0 (`--tree-filter`; needs changes): the branch filter between the count and the
+ *                         files: tracs_fitch_edge_sites, then tracs_filter_recomb_lists on the edges' lists (max_entries bounds
+ *                         them whether or not changes_path is given: they hold an entry per change).  The edge file's header is
+ *                         parent,child,length,changes,filtered,MSA file (filtered: the changes kept on the edge;
+ *                         tracs_tree_write_filtered), the change file's parent,child,contig,position,alleleParent,alleleChild,
+ *                         dropped,MSA file (dropped: 0 / 1, from tracs_fitch_mark_dropped on every batch); the site file is
+ *                         unchanged.  filtered_path != NULL: one Newick line with the topology and labels of `path` and the kept
+ *                         changes as branch lengths (tracs_tree_write).
+ *                         The result: n_joins: n - 3; rows_written: the edge rows; n_changes: the tree's parsimony length;
+ *                         sum_minimum: the sum of `minimum` over the sites with a change; n_kept: the changes kept in all;
+ *                         n_edges_dropped: the edges with a dropped change.  What was not asked for is 0.                        */
+typedef struct tracs_tree_request {
+    int kind;                          /* 0 snp, 1 per-site */
+    const char *path, *ref, *edges_path;
+    uint32_t replicates;               /* 0: no bootstrap */
+    uint64_t seed;
+    int transfer;                      /* with replicates: the transfer support as well */
+    const char *replicate_trees_path;
+    int changes;                       /* the Fitch passes: --tree-changes / --tree-sites / --tree-filter */
+    const char *changes_path, *sites_path;
+    int filter;                        /* with changes: the branch filter */
+    const char *filtered_path;
+    const char *const *contig_names;
+    const uint64_t *contig_lengths;
+    size_t n_contigs;
+    uint64_t max_entries;
+    int n_threads, create;
+} tracs_tree_request;
+typedef struct tracs_tree_result {
+    uint64_t n_joins, rows_written, n_changes, sum_minimum, n_kept, n_edges_dropped;
+} tracs_tree_result;
+int tracs_distance_tree_run(tracs_distance *h, const tracs_tree_request *req, tracs_tree_result *res);
+/*   tracs_distance_tree   the request {kind, path, ref, edges_path}: the main tree alone                                         */
 int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint64_t *n_joins,
                         uint64_t *rows_written);
-/*   tracs_distance_tree_changes `--tree nj --tree-changes / --tree-sites` (not in the reference): tracs_distance_tree's
- *                         body (either kind), then tracs_fitch_count on that tree.  changes_path != NULL and more than max_entries
- *                         changes in all: refused with a message that states it, before any file is touched.  create != 0: the
- *                         four files are then created (the edge file with the header parent,child,length,changes,MSA file, the
- *                         change file with parent,child,contig,position,alleleParent,alleleChild,MSA file, the site file with
- *                         contig,position,changes,minimum,MSA file); 0: they are appended to (a second --msa file).  The Newick line
- *                         and the edge rows come from tracs_tree_write_changes; the change rows -- sites ascending, walk order
- *                         within a site, nodes named as in the edge rows, alleles A/C/G/T, contig / position as
- *                         tracs_distance_pair_sites writes them -- from tracs_fitch_fill in batches of sites: two buffers (device,
- *                         pinned host) of at most 256 MiB (TRACS_FITCH_BATCH: entries per batch, diagnostic), rows formatted on
- *                         n_threads host threads (<= 0: up to 16); the site rows list the sites with a change.  n_changes: the
- *                         tree's parsimony length; sum_minimum: the sum of `minimum` over the sites with a change.             */
+/*   tracs_distance_tree_changes  that request with changes = 1 and changes_path .. create                                        */
 int tracs_distance_tree_changes(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, const char *changes_path,
                                 const char *sites_path, const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs,
                                 uint64_t max_entries, int n_threads, int create, uint64_t *n_joins, uint64_t *rows_written, uint64_t *n_changes,
                                 uint64_t *sum_minimum);
-/*   tracs_distance_tree_filter `--tree nj --tree-filter` (not in the reference): tracs_distance_tree_changes's body with
- *                         the branch filter between the count and the files: tracs_fitch_edge_sites, then tracs_filter_recomb_lists on
- *                         the edges' lists.  More than max_entries changes are refused before any file is touched, whether or not
- *                         changes_path is given (the edge lists and their verdicts hold an entry per change).  The edge file's header
- *                         is parent,child,length,changes,filtered,MSA file (filtered: the changes kept on the edge;
- *                         tracs_tree_write_filtered), the change file's parent,child,contig,position,alleleParent,alleleChild,dropped,
- *                         MSA file (dropped: 0 / 1, from tracs_fitch_mark_dropped on every batch); the site file is unchanged.
- *                         filtered_path != NULL: one Newick line with the topology and labels of `path` and the kept changes as
- *                         branch lengths (tracs_tree_write).  n_kept: the changes kept in all; n_edges_dropped: the edges with a
- *                         dropped change.                                                                                       */
+/*   tracs_distance_tree_filter  the request of tracs_distance_tree_changes with filter = 1 and filtered_path                     */
 int tracs_distance_tree_filter(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, const char *changes_path,
                                const char *sites_path, const char *filtered_path, const char *const *contig_names, const uint64_t *contig_lengths,
                                size_t n_contigs, uint64_t max_entries, int n_threads, int create, uint64_t *n_joins, uint64_t *rows_written,
                                uint64_t *n_changes, uint64_t *sum_minimum, uint64_t *n_kept, uint64_t *n_edges_dropped);
-/*   tracs_distance_tree_bootstrap `--tree nj --bootstrap B` (not in the reference): tracs_distance_tree's main tree
- *                         (kind 0 only), then `replicates` >= 1 bootstrap replicates b = 0 .. replicates - 1 under `seed`: the columns
- *                         at which two samples differ are selected once (the others add nothing to any replicate's distances), and per
- *                         replicate the draws are counted over them, the replicate is gathered into a handle of its own
- *                         (tracs_alignment_gather_sites; none drawn: the zero matrix), the same panel walk, load, joins and lengths
- *                         give its tree, tracs_tree_support counts its splits, and the handle is freed.  The Newick line carries the
- *                         counts as labels and the edge rows a support field (tracs_tree_write_support); n < 4: no labels, NA.
- *                         replicate_trees_path != NULL: each replicate's Newick line (no labels) is appended to it, in replicate
- *                         order (n >= 4).  Bit-reproducible for a given (handle, replicates, seed).                             */
+/*   tracs_distance_tree_bootstrap  the request of tracs_distance_tree with replicates (here at least 1), seed, replicate_trees_path */
 int tracs_distance_tree_bootstrap(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint32_t replicates,
                                   uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins, uint64_t *rows_written);
-/*   tracs_distance_tree_bootstrap_transfer `--bootstrap-support transfer`: tracs_distance_tree_bootstrap -- the same
- *                         arguments, the same body, the same main tree, replicates and --bootstrap-trees bytes -- with the transfer
- *                         support beside the split count: after the main tree tracs_transfer_init, per replicate (after
- *                         tracs_tree_support) its program and transfer_phi_kernel, after the last one tracs_transfer_emit.  The Newick
- *                         labels are the transfer supports and the edge rows carry support,transfer (tracs_tree_write_transfer).  */
+/*   tracs_distance_tree_bootstrap_transfer  the request of tracs_distance_tree_bootstrap with transfer = 1                       */
 int tracs_distance_tree_bootstrap_transfer(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path,
                                            uint32_t replicates, uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins,
                                            uint64_t *rows_written);

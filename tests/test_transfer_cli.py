@@ -108,32 +108,41 @@ def test_transfer_takes_the_tree_route_with_its_own_header(tmp_path, monkeypatch
 
 
 def test_the_handle_chooses_the_entry_point():
-    """DistanceHandle.tree(support=...) calls tracs_distance_tree_bootstrap_transfer for "transfer" and the old entry point otherwise"""
-    from tracs_amd.handle import DistanceHandle
+    """DistanceHandle.tree() makes one tracs_tree_request of its keywords and calls tracs_distance_tree_run, whatever was asked: support=
+    "transfer" is the request's transfer field, the changes and the filter its two flags and four paths"""
+    from tracs_amd.handle import DistanceHandle, TreeResult
     calls = []
 
     class Lib:
-        def tracs_distance_tree_bootstrap(self, *a):
-            calls.append(("split", a[5], a[6]))
-            return 0
-
-        def tracs_distance_tree_bootstrap_transfer(self, *a):
-            calls.append(("transfer", a[5], a[6]))
-            return 0
-
-        def tracs_distance_tree(self, *a):
-            calls.append(("plain",))
+        def tracs_distance_tree_run(self, h, req, res):
+            q = req._obj
+            calls.append({name: getattr(q, name) for name, _ in q._fields_ if not name.startswith("contig_")})
+            res._obj.n_joins, res._obj.rows_written, res._obj.n_kept = 5, 13, 2
             return 0
     h = DistanceHandle.__new__(DistanceHandle)
     h.L, h.h = Lib(), None
-    h.tree("o", "r", bootstrap=4, seed=9)
-    h.tree("o", "r", bootstrap=4, seed=9, support="transfer")
-    h.tree("o", "r")
-    assert calls == [("split", 4, 9), ("transfer", 4, 9), ("plain",)]
+    assert h.tree("o", "r", bootstrap=4, seed=9) == TreeResult(joins=5, rows=13, changes=0, minimum=0, kept=2, branches=0)
+    h.tree("o", "r", bootstrap=4, seed=9, support="transfer", replicate_trees="t")
+    h.tree("o", "r", per_site=True, edges_path="e")
+    assert [(c["replicates"], c["seed"], c["transfer"]) for c in calls] == [(4, 9, 0), (4, 9, 1), (0, 1, 0)]
+    assert [(c["kind"], c["path"], c["ref"], c["edges_path"], c["replicate_trees_path"]) for c in calls] == \
+        [(0, b"o", b"r", None, None), (0, b"o", b"r", None, b"t"), (1, b"o", b"r", b"e", None)]
+    for c in calls:                                                         # nothing of the changes stage was asked for
+        assert (c["changes"], c["filter"], c["changes_path"], c["sites_path"], c["filtered_path"], c["max_entries"]) == (0, 0, None, None, None, 0)
+    del calls[:]
+    h.tree("o", "r", edges_path="e", changes_path="c", sites_path="s", max_entries=7, n_threads=3, create=False, contigs=[("k", 5)])
+    h.tree("o", "r", sites_path="s")
+    h.tree("o", "r", edges_path="e", changes_path="c", sites_path="s", tree_filter=True, filtered_path="f")
+    h.tree("o", "r", tree_filter=True, filtered_path="f")
+    assert [(c["changes"], c["filter"], c["edges_path"], c["changes_path"], c["sites_path"], c["filtered_path"]) for c in calls] == \
+        [(1, 0, b"e", b"c", b"s", None), (1, 0, None, None, b"s", None), (1, 1, b"e", b"c", b"s", b"f"), (1, 1, None, None, None, b"f")]
+    assert [(c["max_entries"], c["n_threads"], c["create"], c["n_contigs"]) for c in calls] == [(7, 3, 0, 1)] + [(100000000, 0, 1, 0)] * 3
+    assert all((c["replicates"], c["transfer"], c["replicate_trees_path"]) == (0, 0, None) for c in calls)
     with pytest.raises(ValueError, match="needs bootstrap"):
         h.tree("o", "r", support="transfer")
     with pytest.raises(ValueError, match="'split' or 'transfer'"):
         h.tree("o", "r", bootstrap=4, support="tbe")
+    assert len(calls) == 4                                                  # (a refusal does not reach the library)
 
 
 # ---- the library's host side ------------------------------------------------------------------------------------------------------

@@ -58,7 +58,7 @@ SYMBOLS = [
     "tracs_tree_transfer", "tracs_tree_write_transfer", "tracs_distance_tree_bootstrap_transfer",
     "tracs_fitch_count", "tracs_fitch_fill", "tracs_tree_write_changes", "tracs_distance_tree_changes",
     "tracs_fitch_edge_sites", "tracs_filter_recomb_lists", "tracs_fitch_mark_dropped", "tracs_tree_write_filtered",
-    "tracs_distance_tree_filter",
+    "tracs_distance_tree_filter", "tracs_distance_tree_run",
 ]
 
 
@@ -66,6 +66,19 @@ class Rules(C.Structure):
     """tracs_rules (include/tracs_hip.h): shares < 0, min_sites = 0 and max_n_samples = 2^32 - 1 mean no rule"""
     _fields_ = [("keep", C.POINTER(C.c_uint64)), ("keep_len", C.c_size_t), ("max_n_share", C.c_double),
                 ("max_sample_n_share", C.c_double), ("min_sites", C.c_uint32), ("max_n_samples", C.c_uint32)]
+
+
+class TreeRequest(C.Structure):
+    """tracs_tree_request (include/tracs_hip.h): what `--tree nj` is asked for; zero / NULL means not asked for"""
+    _fields_ = [("kind", C.c_int), ("path", C.c_char_p), ("ref", C.c_char_p), ("edges_path", C.c_char_p), ("replicates", C.c_uint32), ("seed", C.c_uint64),
+                ("transfer", C.c_int), ("replicate_trees_path", C.c_char_p), ("changes", C.c_int), ("changes_path", C.c_char_p), ("sites_path", C.c_char_p),
+                ("filter", C.c_int), ("filtered_path", C.c_char_p), ("contig_names", C.POINTER(C.c_char_p)), ("contig_lengths", C.POINTER(C.c_uint64)),
+                ("n_contigs", C.c_size_t), ("max_entries", C.c_uint64), ("n_threads", C.c_int), ("create", C.c_int)]
+
+
+class TreeResult(C.Structure):
+    """tracs_tree_result: the counters of a tree request; what was not asked for is 0"""
+    _fields_ = [(name, C.c_uint64) for name in ("n_joins", "rows_written", "n_changes", "sum_minimum", "n_kept", "n_edges_dropped")]
 
 
 class TracsError(RuntimeError):
@@ -203,8 +216,17 @@ def load():
     L.tracs_anc_update_coo.argtypes = [vp, sz, sz, vp, vp, vp, C.c_int, vp, dbl, vp, vp, vp, vp, vp, u64p, vp]
     L.tracs_anc_emit.restype = C.c_int
     L.tracs_anc_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.tracs_distance_tree.restype = C.c_int
-    L.tracs_distance_tree.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, u64p, u64p]
+    L.tracs_distance_tree_run.restype = C.c_int
+    L.tracs_distance_tree_run.argtypes = [vp, C.POINTER(TreeRequest), C.POINTER(TreeResult)]
+    # the five older forms of that request: (handle, kind, path, ref, edges_path), their own arguments, their counters
+    rows = [C.POINTER(C.c_char_p), u64p, sz, C.c_uint64, C.c_int, C.c_int]          # contigs .. create
+    for name, own in (("", [u64p] * 2), ("_changes", [C.c_char_p] * 2 + rows + [u64p] * 4), ("_filter", [C.c_char_p] * 3 + rows + [u64p] * 6),
+                      ("_bootstrap", [C.c_uint32, C.c_uint64, C.c_char_p] + [u64p] * 2), ("_bootstrap_transfer", [C.c_uint32, C.c_uint64, C.c_char_p] + [u64p] * 2)):
+        f = getattr(L, "tracs_distance_tree" + name)
+        f.restype = C.c_int
+        f.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p] + own
+    L.tracs_debug_tree_edges_header.restype = C.c_int
+    L.tracs_debug_tree_edges_header.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, sz]
     L.tracs_nj_state_bytes.restype = sz
     L.tracs_nj_state_bytes.argtypes = [sz]
     L.tracs_nj_init.restype = C.c_int
@@ -227,9 +249,6 @@ def load():
     L.tracs_fitch_count.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, u64p, vp]
     L.tracs_fitch_fill.restype = C.c_int
     L.tracs_fitch_fill.argtypes = [vp, vp, vp, sz, sz, sz, vp, i64, vp, vp, vp, sz, vp]
-    L.tracs_distance_tree_changes.restype = C.c_int
-    L.tracs_distance_tree_changes.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p), u64p, sz,
-                                              C.c_uint64, C.c_int, C.c_int, u64p, u64p, u64p, u64p]
     L.tracs_fitch_edge_sites.restype = C.c_int
     L.tracs_fitch_edge_sites.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp]
     L.tracs_filter_recomb_lists.restype = C.c_int
@@ -238,9 +257,6 @@ def load():
     L.tracs_fitch_mark_dropped.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     L.tracs_tree_write_filtered.restype = C.c_int
     L.tracs_tree_write_filtered.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, vp, vp, C.c_char_p, C.c_char_p, C.c_char_p]
-    L.tracs_distance_tree_filter.restype = C.c_int
-    L.tracs_distance_tree_filter.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_char_p),
-                                             u64p, sz, C.c_uint64, C.c_int, C.c_int, u64p, u64p, u64p, u64p, u64p, u64p]
     L.tracs_bootstrap_weights.restype = C.c_int
     L.tracs_bootstrap_weights.argtypes = [sz, C.c_uint64, C.c_uint64, vp, vp]
     L.tracs_debug_bootstrap_replicate.restype = C.c_int
@@ -251,10 +267,6 @@ def load():
     L.tracs_tree_support.argtypes = [sz, vp, vp, sz, vp, vp, sz, vp]
     L.tracs_tree_write_support.restype = C.c_int
     L.tracs_tree_write_support.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, vp, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p]
-    L.tracs_distance_tree_bootstrap.restype = C.c_int
-    L.tracs_distance_tree_bootstrap.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64, C.c_char_p, u64p, u64p]
-    L.tracs_distance_tree_bootstrap_transfer.restype = C.c_int
-    L.tracs_distance_tree_bootstrap_transfer.argtypes = L.tracs_distance_tree_bootstrap.argtypes
     L.tracs_tree_transfer_program.restype = C.c_int
     L.tracs_tree_transfer_program.argtypes = [sz, vp, vp, sz, vp, C.POINTER(sz)]
     L.tracs_transfer_state_bytes.restype = sz

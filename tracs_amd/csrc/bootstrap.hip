@@ -291,6 +291,19 @@ int tree_bitsets(const char *who, size_t n, const uint32_t *parent, const uint32
     return TRACS_OK;
 }
 
+size_t bootstrap_column_words(const uint64_t *differs, size_t L, std::vector<unsigned> &bits, std::vector<unsigned> &woff)
+{
+    const size_t words = (L + 31) / 32;
+    bits.resize(words); woff.resize(words);
+    unsigned run = 0;
+    for (size_t w = 0; w < words; w++) {
+        bits[w] = (unsigned)(differs[w >> 1] >> (32 * (w & 1)));
+        woff[w] = run;
+        run += (unsigned)__builtin_popcount(bits[w]);
+    }
+    return run;
+}
+
 }  // namespace tracs
 
 using namespace tracs;
@@ -320,14 +333,8 @@ int tracs_debug_bootstrap_replicate(const tracs_alignment *var, size_t L, const 
     if (out) *out = nullptr;
     if (!var || !differs || !seconds || !out || !L) { set_error("tracs_debug_bootstrap_replicate: bad argument"); return TRACS_E_ARG; }
     const size_t words = (L + 31) / 32, V = var->L;
-    std::vector<unsigned> bits(words), woff(words);
-    unsigned run = 0;
-    for (size_t w = 0; w < words; w++) {
-        bits[w] = (unsigned)(differs[w >> 1] >> (32 * (w & 1)));
-        woff[w] = run;
-        run += (unsigned)__builtin_popcount(bits[w]);
-    }
-    if (run != V) { set_error("tracs_debug_bootstrap_replicate: the bitmap does not have the handle's columns"); return TRACS_E_ARG; }
+    std::vector<unsigned> bits, woff;
+    if (bootstrap_column_words(differs, L, bits, woff) != V) { set_error("tracs_debug_bootstrap_replicate: the bitmap does not have the handle's columns"); return TRACS_E_ARG; }
     unsigned *d = nullptr;
     TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), (2 * words + V) * 4));
     auto done = [&](int r) { (void)hipDeviceSynchronize(); (void)hipFree(d); return r; };

@@ -90,6 +90,11 @@ struct StageClock {
         else std::fprintf(stderr, "[stage] %s %.4f s\n", name, s);
         t = std::chrono::steady_clock::now();
     }
+    void memory(const char *when)                                     // "[memory] when N MiB": what the device has in use, by every process
+    {
+        size_t idle = 0, all = 0;
+        if (on && hipMemGetInfo(&idle, &all) == hipSuccess) std::fprintf(stderr, "[memory] %s %.1f MiB\n", when, (double)(all - idle) / 1048576.0);
+    }
 };
 // the time since the clock's last mark or lap goes into `acc` (the entry points that print sums over their panels)
 static void lap(StageClock &clock, double &acc)
@@ -1218,10 +1223,8 @@ int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, d
     return rc;
 }
 
-// `tracs distance --tree nj` for one alignment (include/tracs_hip.h): the panel walk without a threshold and without
-// the pair rule (every pair has a distance), each dense panel loaded into the neighbour-joining state, the joins on the device, then
-// the records -> branch lengths on the host.  tracs_distance_tree writes them; tracs_distance_tree_bootstrap runs the
-// same body once for the handle and once per replicate, on one walk (its dense buffers) and one state.
+// `tracs distance --tree nj` for one alignment (include/tracs_hip.h: tracs_distance_tree_run).  tree_run is the
+// route: the request checked, the main tree, at most one of the two stages below, the files, the counters.
 namespace {
 
 struct TreeEdges {
@@ -1230,18 +1233,13 @@ struct TreeEdges {
     size_t nj = 0, ne = 0;
 };
 
-// a stage of one tree: the main tree marks it on the stage clock, a replicate adds it to a sum
-void tree_stage(StageClock &clock, const char *name, double *acc)
-{
-    if (acc) lap(clock, *acc);
-    else clock.mark(name);
-}
-
-// a == NULL: the zero matrix (a replicate that drew no differing column); acc: NULL, or the replicates' three sums
-int tree_of_alignment(tracs_alignment *a, size_t n, const char *const *names, int kind, PanelWalk &walk, DeviceBuffer &d_state,
-                      StageClock &clock, double *acc, TreeEdges &t)
+// One tree: the panel walk without a threshold and without the pair rule (every pair has a distance), each dense panel loaded into the
+// neighbour-joining state (about n^2 x 8 bytes; the first tree of a call allocates both), the joins on the device, the lengths on the host.
+// a == NULL: the zero matrix (a replicate that drew no differing column); acc: NULL (the main tree: stages marked), or the replicates' sums
+int tree_of_alignment(tracs_alignment *a, const char *const *names, int kind, PanelWalk &walk, DeviceBuffer &d_state, StageClock &clock, double *acc, TreeEdges &t)
 {
     int rc;
+    const size_t n = walk.n;
     std::vector<uint32_t> ja, jb;
     std::vector<double> jd, jra, jrb;
     uint32_t last_ids[3] = {0, n > 1 ? 1u : 0xFFFFFFFFu, 0xFFFFFFFFu};      // (n < 2: no pair exists, nothing runs on the device)
@@ -1249,23 +1247,24 @@ int tree_of_alignment(tracs_alignment *a, size_t n, const char *const *names, in
     t.nj = t.ne = 0;
     if (walk.any()) {
         if (!d_state.ptr && (rc = d_state.alloc(tracs_nj_state_bytes(n)))) return rc;
-        if ((rc = tracs_nj_init(d_state.ptr, n, nullptr))) return rc;
+        void *const state = d_state.ptr;
+        if ((rc = tracs_nj_init(state, n, nullptr))) return rc;
         if (a) {
             walk.a = a;
             walk.at = 0;
             if (!walk.height && (rc = walk.begin(false, false))) return rc;
             for (Panel pn; walk.more();) {
-                if ((rc = walk.next(pn)) || (rc = tracs_nj_load_panel(d_state.ptr, n, pn.bd, pn.bn, n, pn.r0, pn.r1, kind, nullptr))) return rc;
+                if ((rc = walk.next(pn)) || (rc = tracs_nj_load_panel(state, n, pn.bd, pn.bn, n, pn.r0, pn.r1, kind, nullptr))) return rc;
             }
         }
-        tree_stage(clock, "dense panels + matrix load", acc);
-        if ((rc = tracs_nj_run(d_state.ptr, n, nullptr))) return rc;
+        if (acc) lap(clock, acc[0]); else clock.mark("dense panels + matrix load");
+        if ((rc = tracs_nj_run(state, n, nullptr))) return rc;
         TRACS_HIP_CHECK(hipDeviceSynchronize());
         if (g_sigint) return interrupted();
-        tree_stage(clock, "join loop", acc ? acc + 1 : nullptr);
+        if (acc) lap(clock, acc[1]); else clock.mark("join loop");
         ja.resize(n); jb.resize(n); jd.resize(n); jra.resize(n); jrb.resize(n);
         uint32_t zero[2];
-        rc = tracs_nj_emit(d_state.ptr, n, &t.nj, ja.data(), jb.data(), jd.data(), jra.data(), jrb.data(), last_ids, last_d, zero, nullptr);
+        rc = tracs_nj_emit(state, n, &t.nj, ja.data(), jb.data(), jd.data(), jra.data(), jrb.data(), last_ids, last_d, zero, nullptr);
         if (rc == TRACS_E_ARG && zero[0] < n && zero[1] < n)
             set_error(std::string("samples '") + names[zero[0]] + "' and '" + names[zero[1]] + "' have no site at which both are "
                       "known: no per-site distance (--max-sample-n-share leaves out samples that are mostly N)");
@@ -1276,128 +1275,228 @@ int tree_of_alignment(tracs_alignment *a, size_t n, const char *const *names, in
                           t.length.data(), &t.ne);
 }
 
-}  // namespace
+// what a stage learns about the main tree's edges.  Bootstrap: the replicates with the edge's split; transfer: the sums of the transfer
+// distances, the lighter sides.  Changes: the Fitch tables; filter: the changes by edge and their verdicts, the edges' kept changes.
+struct TreeLabels {
+    std::vector<uint32_t> support, light, kept;
+    std::vector<uint64_t> sum_phi;
+    tracs::FitchTables ft;
+    DeviceBuffer d_edge_off, d_edge_site, d_dropped, d_filt;
+    tracs::FitchFilter ff = {nullptr, nullptr, nullptr};
+    uint64_t kept_sum = 0, edges_dropped = 0;
+};
 
-int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint64_t *n_joins,
-                        uint64_t *rows_written)
+// The replicates (include/tracs_hip.h): the differing columns selected once, then per replicate the draws, the gather into a handle of
+// its own, the main tree's walk / load / joins / lengths on the same walk and state, the splits compared and, with r.transfer, its
+// program run against the main tree's membership matrix.  One state, one walk, one replicate alive at a time.
+int tree_bootstrap_stage(tracs_distance *h, const tracs_tree_request &r, const TreeEdges &t, PanelWalk &walk, DeviceBuffer &d_state, StageClock &clock, TreeLabels &s)
 {
-    if (n_joins) *n_joins = 0;
-    if (rows_written) *rows_written = 0;
-    if (!h || !h->a || !path || !ref) { set_error("tracs_distance_tree: NULL argument"); return TRACS_E_ARG; }
-    if (kind != 0 && kind != 1) { set_error("tracs_distance_tree: kind must be 0 (snp) or 1 (per-site)"); return TRACS_E_ARG; }
-    if (h->n_fasta != 1) { set_error("tracs_distance_tree: a tree joins the samples of one alignment"); return TRACS_E_ARG; }
+    tracs_alignment *a = h->a;
+    const size_t n = a->n, L = a->L;
+    const char *const *names = h->name_ptr.data();
+    const bool transfer = r.transfer != 0;
+    int rc;
+    s.support.assign(t.ne, 0xFFFFFFFFu);
+    s.sum_phi.assign(t.ne, 0); s.light.assign(t.ne, 0);
+    if (n < 4) return TRACS_OK;                                            // (no internal edge, nothing to label)
+    TreeEdges rep_t;
+    std::vector<uint32_t> program(transfer ? 2 * n - 3 : 0);
+    DeviceBuffer d_transfer;
+    for (size_t e = 0; e < t.ne; e++) if (t.child[e] >= n) s.support[e] = 0;
+    if (transfer) {
+        if ((rc = d_transfer.alloc(tracs_transfer_state_bytes(n))) ||
+            (rc = tracs_transfer_init(d_transfer.ptr, n, t.parent.data(), t.child.data(), t.ne, nullptr))) return rc;
+        clock.mark("transfer: membership matrix");
+    }
+    std::vector<uint64_t> differs((L + 63) / 64 + 1, 0);
+    size_t V = 0;
+    AlignmentOwner var;
+    DeviceBuffer d_bits, d_woff, d_w;
+    if (L && (rc = site_census(a, nullptr, differs.data(), &V, nullptr))) return rc;
+    if (V) {
+        tracs_alignment *sel = nullptr;
+        if ((rc = select_sites(a, differs.data(), L, UINT32_MAX, &sel, nullptr, nullptr, nullptr, false))) return rc;
+        var.reset(sel);
+        std::vector<unsigned> bits, woff;
+        bootstrap_column_words(differs.data(), L, bits, woff);
+        if ((rc = d_bits.upload(bits.data(), bits.size() * 4)) || (rc = d_woff.upload(woff.data(), woff.size() * 4)) || (rc = d_w.alloc(V * 4))) return rc;
+    }
+    clock.mark("bootstrap: census + differing columns");
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};                         // weights + scan + gather; the three stages of a tree (+ support);
+                                                                            // transfer: the program on the host, the kernel
+    for (uint32_t b = 0; b < r.replicates; b++) {
+        if (g_sigint) return interrupted();
+        AlignmentOwner rep;
+        if (V) {
+            tracs_alignment *ra = nullptr;
+            if ((rc = bootstrap_weights_launch(L, r.seed, b, d_bits.as<unsigned>(), d_woff.as<unsigned>(), d_w.as<uint32_t>(), V, nullptr)) ||
+                (rc = gather_sites(var.get(), d_w.as<uint32_t>(), &ra, nullptr, nullptr, true))) return rc;
+            rep.reset(ra);
+        }
+        lap(clock, acc[0]);
+        if ((rc = tree_of_alignment(rep.get(), names, 0, walk, d_state, clock, acc + 1, rep_t))) return rc;
+        if ((rc = tracs_tree_support(n, t.parent.data(), t.child.data(), t.ne, rep_t.parent.data(), rep_t.child.data(), rep_t.ne, s.support.data()))) return rc;
+        if (r.replicate_trees_path && (rc = tracs_tree_write(names, n, rep_t.parent.data(), rep_t.child.data(), rep_t.length.data(), rep_t.ne,
+                                                             r.replicate_trees_path, r.ref, nullptr))) return rc;
+        lap(clock, acc[3]);
+        if (transfer) {
+            size_t depth = 0;
+            if ((rc = tracs_tree_transfer_program(n, rep_t.parent.data(), rep_t.child.data(), rep_t.ne, program.data(), &depth))) return rc;
+            lap(clock, acc[4]);
+            if ((rc = transfer_add_program(d_transfer.ptr, n, program.data(), depth, nullptr, nullptr))) return rc;
+            lap(clock, acc[5]);
+        }
+    }
+    if (transfer && (rc = tracs_transfer_emit(d_transfer.ptr, n, s.sum_phi.data(), s.light.data()))) return rc;
+    if (clock.on) {
+        std::fprintf(stderr, "[stage] bootstrap: %u replicates over %zu differing columns\n", (unsigned)r.replicates, V);
+        std::fprintf(stderr, "[stage] replicates: weights + scan + gather %.4f s\n", acc[0]);
+        std::fprintf(stderr, "[stage] replicates: dense panels + matrix load %.4f s\n", acc[1]);
+        std::fprintf(stderr, "[stage] replicates: join loop %.4f s\n", acc[2]);
+        std::fprintf(stderr, "[stage] replicates: emit, lengths, support %.4f s\n", acc[3]);
+        if (transfer)
+            std::fprintf(stderr, "[stage] replicates: transfer distances %.4f s (program %.4f s, kernel %.4f s)\n", acc[4] + acc[5], acc[4], acc[5]);
+    }
+    return TRACS_OK;
+}
+
+// The Fitch count pass on the main tree (include/tracs_hip.h); a total above r.max_entries is refused here, before any file is touched.
+// r.filter: the changes regrouped by edge and the recombination filter's window test on every edge's list.
+int tree_changes_stage(tracs_distance *h, const tracs_tree_request &r, const TreeEdges &t, StageClock &clock, TreeLabels &c)
+{
+    const size_t n = h->a->n;
+    int rc;
+    clock.memory("before the Fitch passes");                               // (the tree's matrix is gone)
+    if (n && (rc = tracs::fitch_tables(h->a, t.parent.data(), t.child.data(), t.ne, c.ft))) return rc;
+    clock.mark("tree changes: count pass, offsets");
+    if (g_sigint) return interrupted();
+    if ((r.changes_path || r.filter) && c.ft.total > r.max_entries) {      // (the edge lists and their verdicts hold one entry per change)
+        set_error("the tree has " + std::to_string(c.ft.total) + " changes in all, more than --max-entries " + std::to_string(r.max_entries) +
+                  "; nothing was written");
+        return TRACS_E_ARG;
+    }
+    c.kept.assign(std::max<size_t>(t.ne, 1), 0);
+    if (r.filter && n && t.ne) {
+        const size_t total = (size_t)c.ft.total;
+        if ((rc = c.d_edge_off.alloc((t.ne + 1) * 8)) || (rc = c.d_edge_site.alloc(std::max<size_t>(total, 1) * 4)) ||
+            (rc = c.d_dropped.alloc(std::max<size_t>(total, 1))) || (rc = c.d_filt.alloc(t.ne * 4))) return rc;
+        if ((rc = tracs_fitch_edge_sites(h->a, t.parent.data(), t.child.data(), t.ne, c.ft.d_edge, c.d_edge_off.as<int64_t>(),
+                                         c.d_edge_site.as<uint32_t>(), total, nullptr))) return rc;
+        clock.mark("tree filter: the changes by edge");
+        if ((rc = tracs_filter_recomb_lists(h->a, c.d_edge_off.as<int64_t>(), c.d_edge_site.as<uint32_t>(), t.ne, total, c.d_filt.as<uint32_t>(),
+                                            c.d_dropped.as<uint8_t>(), nullptr))) return rc;
+        TRACS_HIP_CHECK(hipMemcpy(c.kept.data(), c.d_filt.ptr, t.ne * 4, hipMemcpyDeviceToHost));
+        clock.mark("tree filter: window test on the edges' lists");
+        for (size_t e = 0; e < t.ne; e++) {
+            c.kept_sum += c.kept[e];
+            c.edges_dropped += c.kept[e] < c.ft.edge_changes[e];
+        }
+        c.ff = {c.d_edge_off.as<long long>(), c.d_edge_site.as<unsigned>(), c.d_dropped.as<uint8_t>()};
+        if (g_sigint) return interrupted();
+    }
+    c.ft.edge_changes.resize(std::max<size_t>(t.ne, 1), 0);
+    return TRACS_OK;
+}
+
+int tree_run(const std::string &who, tracs_distance *h, const tracs_tree_request &r, tracs_tree_result &res)
+{
+    // (a) the request
+    res = tracs_tree_result();
+    const bool boot = r.replicates || r.transfer || r.replicate_trees_path, changes = r.changes || r.filter;
+    if (!h || !h->a || !r.path || !r.ref) { set_error(who + ": NULL argument"); return TRACS_E_ARG; }
+    if (boot && changes) {
+        set_error(who + ": the changes on the tree and bootstrap replicates cannot be combined yet (the tree is reproducible bit for bit: "
+                        "run once with each and join the two --tree-edges files on parent and child)");
+        return TRACS_E_ARG;
+    }
+    if (boot && r.kind != 0) { set_error(who + ": bootstrap replicates take the SNP distance (kind 0) only"); return TRACS_E_ARG; }
+    if (r.kind != 0 && r.kind != 1) { set_error(who + ": kind must be 0 (snp) or 1 (per-site)"); return TRACS_E_ARG; }
+    if (boot && r.replicates < 1) { set_error(who + ": at least one replicate"); return TRACS_E_ARG; }
+    if (h->n_fasta != 1) { set_error(who + ": a tree joins the samples of one alignment"); return TRACS_E_ARG; }
     SigintScope sigint;
     const size_t n = h->a->n;
-    if (n && !tracs_nj_state_bytes(n)) { set_error("tracs_distance_tree: too many samples for one distance matrix"); return TRACS_E_ARG; }
+    const char *const *names = h->name_ptr.data();
+    if (n && !tracs_nj_state_bytes(n)) { set_error(who + ": too many samples for one distance matrix"); return TRACS_E_ARG; }
+    if (boot && h->a->L >= 0xFFFFFFFFull) { set_error(who + ": too many columns"); return TRACS_E_ARG; }
     StageClock clock;
     int rc;
+    // (b) the main tree
     TreeEdges t;
     PanelWalk walk(h->a, 1, n, 2147483647, 0);
     DeviceBuffer d_state;
-    if ((rc = tree_of_alignment(h->a, n, h->name_ptr.data(), kind, walk, d_state, clock, nullptr, t))) return rc;
-    if ((rc = tracs_tree_write(h->name_ptr.data(), n, t.parent.data(), t.child.data(), t.length.data(), t.ne, path, ref, edges_path))) return rc;
+    if ((rc = tree_of_alignment(h->a, names, r.kind, walk, d_state, clock, nullptr, t))) return rc;
+    // (c) at most one stage.  The replicates are joined on the main tree's walk and state, which stay until the call returns; the Fitch
+    // passes need neither, so both go first: at n = 10000 the state alone is 0.8 GB that must not sit under them.
+    TreeLabels ch;
+    if (boot && (rc = tree_bootstrap_stage(h, r, t, walk, d_state, clock, ch))) return rc;
+    if (changes) {
+        walk.d_dist.release(); walk.d_nn.release(); d_state.release();
+        if ((rc = tree_changes_stage(h, r, t, clock, ch))) return rc;
+    }
+    // (d) the files
+    const uint32_t *edge_changes = changes ? ch.ft.edge_changes.data() : nullptr, *kept = r.filter ? ch.kept.data() : nullptr;
+    const uint32_t *const parent = t.parent.data(), *const child = t.child.data();
+    if (changes && r.create) {                                             // (tracs/distance.py leaves the run's files to the library then)
+        const std::pair<const char *, std::string> made[5] = {{r.path, ""}, {r.edges_path, tree_edges_header({nullptr, nullptr, edge_changes, kept})},
+            {r.changes_path, std::string("parent,child,contig,position,alleleParent,alleleChild,") + (r.filter ? "dropped," : "") + "MSA file\n"},
+            {r.sites_path, "contig,position,changes,minimum,MSA file\n"}, {r.filtered_path, ""}};
+        for (const auto &f : made) {
+            if (!f.first) continue;
+            std::FILE *fh = std::fopen(f.first, "wb");
+            if (!fh || std::fputs(f.second.c_str(), fh) < 0 || std::fclose(fh) != 0) { set_error(std::string("cannot write ") + f.first); return TRACS_E_OPEN; }
+        }
+    }
+    if (r.filter) rc = tracs_tree_write_filtered(names, n, parent, child, t.length.data(), t.ne, edge_changes, kept, r.path, r.ref, r.edges_path);
+    else if (changes) rc = tracs_tree_write_changes(names, n, parent, child, t.length.data(), t.ne, edge_changes, r.path, r.ref, r.edges_path);
+    else if (r.transfer) rc = tracs_tree_write_transfer(names, n, parent, child, t.length.data(), t.ne, ch.support.data(), ch.sum_phi.data(),
+                                                        ch.light.data(), r.replicates, r.path, r.ref, r.edges_path);
+    else if (boot) rc = tracs_tree_write_support(names, n, parent, child, t.length.data(), t.ne, ch.support.data(), r.replicates, r.path, r.ref, r.edges_path);
+    else rc = tracs_tree_write(names, n, parent, child, t.length.data(), t.ne, r.path, r.ref, r.edges_path);
+    if (!rc && r.filter && r.filtered_path) {
+        const std::vector<double> kept_length(ch.kept.begin(), ch.kept.end());
+        rc = tracs_tree_write(names, n, parent, child, kept_length.data(), t.ne, r.filtered_path, r.ref, nullptr);
+    }
+    if (rc) return rc;
     clock.mark("tree: emit, lengths, format, write");
-    if (n_joins) *n_joins = t.nj;
-    if (rows_written) *rows_written = edges_path ? t.ne : 0;
+    if (changes) {
+        if (n && (rc = tracs::fitch_write(h->a, names, h->kept.empty() ? nullptr : h->kept.data(), h->source_len, parent, child, t.ne, ch.ft,
+                                          r.changes_path, r.sites_path, r.ref, r.contig_names, r.contig_lengths, r.n_contigs, r.n_threads,
+                                          ch.ff.d_dropped ? &ch.ff : nullptr)))
+            return rc;
+        clock.mark("tree changes: fill, device -> host, format, write");
+        clock.memory("after the Fitch passes");
+    }
+    // (e) the counters
+    res = {t.nj, r.edges_path ? t.ne : 0, ch.ft.total, ch.ft.sum_minimum, ch.kept_sum, ch.edges_dropped};
     if (g_sigint) return interrupted();
     return TRACS_OK;
 }
 
-// `tracs distance --tree nj --tree-changes / --tree-sites` (include/tracs_hip.h): tracs_distance_tree's body, then the
-// count pass of csrc/fitch.hip on that tree; a total above max_entries is refused before any file is touched; then the tree with the
-// edges' counts, the change rows and the site rows.  filter (`--tree-filter`, tracs_distance_tree_filter): the changes
-// regrouped by edge (tracs_fitch_edge_sites) and the recombination filter on every edge's list (tracs_filter_recomb_lists) between
-// the count and the files; the edge rows gain the kept changes, the change rows the verdict, and filtered_path the tree whose
-// lengths are the kept changes.
-static int tree_changes_body(const char *who_, bool filter, tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path,
-                             const char *changes_path, const char *sites_path, const char *filtered_path, const char *const *contig_names,
-                             const uint64_t *contig_lengths, size_t n_contigs, uint64_t max_entries, int n_threads, int create, uint64_t *n_joins,
-                             uint64_t *rows_written, uint64_t *n_changes, uint64_t *sum_minimum, uint64_t *n_kept, uint64_t *n_edges_dropped)
+// the five older entry points: their arguments as a request (its first fields in order, the others 0), the result into their out-parameters
+int tree_run_out(const char *who, tracs_distance *h, const tracs_tree_request &r, std::initializer_list<uint64_t *> out)
 {
-    const std::string who(who_);
-    for (uint64_t *p : {n_joins, rows_written, n_changes, sum_minimum, n_kept, n_edges_dropped}) if (p) *p = 0;
-    if (!h || !h->a || !path || !ref) { set_error(who + ": NULL argument"); return TRACS_E_ARG; }
-    if (kind != 0 && kind != 1) { set_error(who + ": kind must be 0 (snp) or 1 (per-site)"); return TRACS_E_ARG; }
-    if (h->n_fasta != 1) { set_error(who + ": a tree joins the samples of one alignment"); return TRACS_E_ARG; }
-    SigintScope sigint;
-    const size_t n = h->a->n;
-    if (n && !tracs_nj_state_bytes(n)) { set_error(who + ": too many samples for one distance matrix"); return TRACS_E_ARG; }
-    StageClock clock;
-    int rc;
-    TreeEdges t;
-    tracs::FitchTables ft;
-    {
-        PanelWalk walk(h->a, 1, n, 2147483647, 0);
-        DeviceBuffer d_state;
-        if ((rc = tree_of_alignment(h->a, n, h->name_ptr.data(), kind, walk, d_state, clock, nullptr, t))) return rc;
-    }
-    if (n && (rc = tracs::fitch_tables(h->a, t.parent.data(), t.child.data(), t.ne, ft))) return rc;
-    clock.mark("tree changes: count pass, offsets");
-    if (g_sigint) return interrupted();
-    if ((changes_path || filter) && ft.total > max_entries) {             // (the edge lists and their verdicts hold one entry per change)
-        set_error("the tree has " + std::to_string(ft.total) + " changes in all, more than --max-entries " + std::to_string(max_entries) +
-                  "; nothing was written");
-        return TRACS_E_ARG;
-    }
-    // the branch filter: the changes by edge, their verdicts, the kept changes of every edge
-    DeviceBuffer d_edge_off, d_edge_site, d_dropped, d_filt;
-    std::vector<uint32_t> kept(std::max<size_t>(t.ne, 1), 0);
-    uint64_t kept_sum = 0, edges_dropped = 0;
-    tracs::FitchFilter ff = {nullptr, nullptr, nullptr};
-    if (filter && n && t.ne) {
-        if ((rc = d_edge_off.alloc((t.ne + 1) * 8)) || (rc = d_edge_site.alloc(std::max<uint64_t>(ft.total, 1) * 4)) ||
-            (rc = d_dropped.alloc(std::max<uint64_t>(ft.total, 1))) || (rc = d_filt.alloc(t.ne * 4))) return rc;
-        if ((rc = tracs_fitch_edge_sites(h->a, t.parent.data(), t.child.data(), t.ne, ft.d_edge, d_edge_off.as<int64_t>(), d_edge_site.as<uint32_t>(),
-                                         (size_t)ft.total, nullptr))) return rc;
-        clock.mark("tree filter: the changes by edge");
-        if ((rc = tracs_filter_recomb_lists(h->a, d_edge_off.as<int64_t>(), d_edge_site.as<uint32_t>(), t.ne, (size_t)ft.total, d_filt.as<uint32_t>(),
-                                            d_dropped.as<uint8_t>(), nullptr))) return rc;
-        TRACS_HIP_CHECK(hipMemcpy(kept.data(), d_filt.ptr, t.ne * 4, hipMemcpyDeviceToHost));
-        clock.mark("tree filter: window test on the edges' lists");
-        for (size_t e = 0; e < t.ne; e++) {
-            kept_sum += kept[e];
-            edges_dropped += kept[e] < ft.edge_changes[e];
-        }
-        ff.d_edge_off = d_edge_off.as<long long>(); ff.d_edge_site = d_edge_site.as<unsigned>(); ff.d_dropped = d_dropped.as<uint8_t>();
-        if (g_sigint) return interrupted();
-    }
-    if (create) {
-        const std::pair<const char *, const char *> made[5] = {{path, ""},
-            {edges_path, filter ? "parent,child,length,changes,filtered,MSA file\n" : "parent,child,length,changes,MSA file\n"},
-            {changes_path, filter ? "parent,child,contig,position,alleleParent,alleleChild,dropped,MSA file\n"
-                                  : "parent,child,contig,position,alleleParent,alleleChild,MSA file\n"},
-            {sites_path, "contig,position,changes,minimum,MSA file\n"}, {filtered_path, ""}};
-        for (const auto &m : made) {
-            if (!m.first) continue;
-            std::FILE *fh = std::fopen(m.first, "wb");
-            if (!fh || std::fputs(m.second, fh) < 0 || std::fclose(fh) != 0) { set_error(std::string("cannot write ") + m.first); return TRACS_E_OPEN; }
-        }
-    }
-    ft.edge_changes.resize(std::max<size_t>(t.ne, 1), 0);
-    if (filter) {
-        if ((rc = tracs_tree_write_filtered(h->name_ptr.data(), n, t.parent.data(), t.child.data(), t.length.data(), t.ne, ft.edge_changes.data(),
-                                            kept.data(), path, ref, edges_path))) return rc;
-        if (filtered_path) {
-            std::vector<double> kept_length(kept.begin(), kept.end());
-            if ((rc = tracs_tree_write(h->name_ptr.data(), n, t.parent.data(), t.child.data(), kept_length.data(), t.ne, filtered_path, ref, nullptr)))
-                return rc;
-        }
-    } else if ((rc = tracs_tree_write_changes(h->name_ptr.data(), n, t.parent.data(), t.child.data(), t.length.data(), t.ne, ft.edge_changes.data(),
-                                              path, ref, edges_path))) return rc;
-    clock.mark("tree: emit, lengths, format, write");
-    if (n && (rc = tracs::fitch_write(h->a, h->name_ptr.data(), h->kept.empty() ? nullptr : h->kept.data(), h->source_len, t.parent.data(),
-                                      t.child.data(), t.ne, ft, changes_path, sites_path, ref, contig_names, contig_lengths, n_contigs, n_threads,
-                                      ff.d_dropped ? &ff : nullptr)))
-        return rc;
-    clock.mark("tree changes: fill, device -> host, format, write");
-    if (n_joins) *n_joins = t.nj;
-    if (rows_written) *rows_written = edges_path ? t.ne : 0;
-    if (n_changes) *n_changes = ft.total;
-    if (sum_minimum) *sum_minimum = ft.sum_minimum;
-    if (n_kept) *n_kept = kept_sum;
-    if (n_edges_dropped) *n_edges_dropped = edges_dropped;
-    if (g_sigint) return interrupted();
-    return TRACS_OK;
+    tracs_tree_result res;
+    const int rc = tree_run(who, h, r, res);
+    const uint64_t field[6] = {res.n_joins, res.rows_written, res.n_changes, res.sum_minimum, res.n_kept, res.n_edges_dropped};
+    size_t k = 0;
+    for (uint64_t *p : out) { if (p) *p = field[k]; k++; }
+    return rc;
+}
+
+}  // namespace
+
+int tracs_distance_tree_run(tracs_distance *h, const tracs_tree_request *req, tracs_tree_result *res)
+{
+    tracs_tree_result none = {};
+    if (res) *res = none;
+    if (!req) { set_error("tracs_distance_tree_run: NULL argument"); return TRACS_E_ARG; }
+    return tree_run("tracs_distance_tree_run", h, *req, res ? *res : none);
+}
+
+int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint64_t *n_joins,
+                        uint64_t *rows_written)
+{
+    return tree_run_out("tracs_distance_tree", h, {kind, path, ref, edges_path}, {n_joins, rows_written});
 }
 
 int tracs_distance_tree_changes(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, const char *changes_path,
@@ -1405,8 +1504,10 @@ int tracs_distance_tree_changes(tracs_distance *h, int kind, const char *path, c
                                 uint64_t max_entries, int n_threads, int create, uint64_t *n_joins, uint64_t *rows_written, uint64_t *n_changes,
                                 uint64_t *sum_minimum)
 {
-    return tree_changes_body("tracs_distance_tree_changes", false, h, kind, path, ref, edges_path, changes_path, sites_path, nullptr, contig_names,
-                             contig_lengths, n_contigs, max_entries, n_threads, create, n_joins, rows_written, n_changes, sum_minimum, nullptr, nullptr);
+    tracs_tree_request r = {kind, path, ref, edges_path};
+    r.changes = 1; r.changes_path = changes_path; r.sites_path = sites_path; r.contig_names = contig_names; r.contig_lengths = contig_lengths;
+    r.n_contigs = n_contigs; r.max_entries = max_entries; r.n_threads = n_threads; r.create = create;
+    return tree_run_out("tracs_distance_tree_changes", h, r, {n_joins, rows_written, n_changes, sum_minimum});
 }
 
 int tracs_distance_tree_filter(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, const char *changes_path,
@@ -1414,132 +1515,26 @@ int tracs_distance_tree_filter(tracs_distance *h, int kind, const char *path, co
                                size_t n_contigs, uint64_t max_entries, int n_threads, int create, uint64_t *n_joins, uint64_t *rows_written,
                                uint64_t *n_changes, uint64_t *sum_minimum, uint64_t *n_kept, uint64_t *n_edges_dropped)
 {
-    return tree_changes_body("tracs_distance_tree_filter", true, h, kind, path, ref, edges_path, changes_path, sites_path, filtered_path, contig_names,
-                             contig_lengths, n_contigs, max_entries, n_threads, create, n_joins, rows_written, n_changes, sum_minimum, n_kept,
-                             n_edges_dropped);
-}
-
-// `tracs distance --tree nj --bootstrap B` (include/tracs_hip.h).  The main tree as above; then the columns at which two
-// samples differ are selected once (census bitmap -> tracs_alignment_select_sites: the other columns add nothing to any replicate's
-// distances), and per replicate: the draws counted over those columns, the replicate gathered into a handle of its own, the same
-// panel walk / load / joins / lengths, the splits compared, the handle freed.  One state, one walk, one replicate alive at a time.
-// transfer (tracs_distance_tree_bootstrap_transfer): the main tree's membership matrix goes into a transfer state once,
-// every replicate's program is built and run against it after its splits were compared, and the sums label the tree.
-static int tree_bootstrap_body(const std::string &who, bool transfer, tracs_distance *h, int kind, const char *path, const char *ref,
-                               const char *edges_path, uint32_t replicates, uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins,
-                               uint64_t *rows_written)
-{
-    if (n_joins) *n_joins = 0;
-    if (rows_written) *rows_written = 0;
-    if (!h || !h->a || !path || !ref) { set_error(who + ": NULL argument"); return TRACS_E_ARG; }
-    if (kind != 0) { set_error(who + ": bootstrap replicates take the SNP distance (kind 0) only"); return TRACS_E_ARG; }
-    if (replicates < 1) { set_error(who + ": at least one replicate"); return TRACS_E_ARG; }
-    if (h->n_fasta != 1) { set_error(who + ": a tree joins the samples of one alignment"); return TRACS_E_ARG; }
-    SigintScope sigint;
-    tracs_alignment *a = h->a;
-    const size_t n = a->n, L = a->L;
-    if (n && !tracs_nj_state_bytes(n)) { set_error(who + ": too many samples for one distance matrix"); return TRACS_E_ARG; }
-    if (L >= 0xFFFFFFFFull) { set_error(who + ": too many columns"); return TRACS_E_ARG; }
-    StageClock clock;
-    int rc;
-    TreeEdges t, rep_t;
-    const char *const *names = h->name_ptr.data();
-    PanelWalk walk(a, 1, n, 2147483647, 0);
-    DeviceBuffer d_state;
-    if ((rc = tree_of_alignment(a, n, names, 0, walk, d_state, clock, nullptr, t))) return rc;
-    std::vector<uint32_t> support(t.ne, 0xFFFFFFFFu);
-    std::vector<uint64_t> sum_phi(transfer ? t.ne : 0, 0);
-    std::vector<uint32_t> light(transfer ? t.ne : 0, 0), program(transfer && n >= 4 ? 2 * n - 3 : 0);
-    DeviceBuffer d_transfer;
-    if (n >= 4) {                                                          // (else: no internal edge, nothing to label)
-        for (size_t e = 0; e < t.ne; e++) if (t.child[e] >= n) support[e] = 0;
-        if (transfer) {
-            if ((rc = d_transfer.alloc(tracs_transfer_state_bytes(n))) ||
-                (rc = tracs_transfer_init(d_transfer.ptr, n, t.parent.data(), t.child.data(), t.ne, nullptr))) return rc;
-            clock.mark("transfer: membership matrix");
-        }
-        std::vector<uint64_t> differs((L + 63) / 64 + 1, 0);
-        size_t V = 0;
-        AlignmentOwner var;
-        DeviceBuffer d_bits, d_woff, d_w;
-        if (L && (rc = site_census(a, nullptr, differs.data(), &V, nullptr))) return rc;
-        if (V) {
-            tracs_alignment *sel = nullptr;
-            if ((rc = select_sites(a, differs.data(), L, UINT32_MAX, &sel, nullptr, nullptr, nullptr, false))) return rc;
-            var.reset(sel);
-            const size_t words = (L + 31) / 32;
-            std::vector<unsigned> bits(words), woff(words);
-            unsigned run = 0;
-            for (size_t w = 0; w < words; w++) {
-                bits[w] = (unsigned)(differs[w >> 1] >> (32 * (w & 1)));
-                woff[w] = run;
-                run += (unsigned)__builtin_popcount(bits[w]);
-            }
-            if ((rc = d_bits.upload(bits.data(), words * 4)) || (rc = d_woff.upload(woff.data(), words * 4)) || (rc = d_w.alloc(V * 4))) return rc;
-        }
-        clock.mark("bootstrap: census + differing columns");
-        double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};                     // weights + scan + gather; the three stages of a tree (+ support);
-                                                                            // transfer: the program on the host, the kernel
-        for (uint32_t b = 0; b < replicates; b++) {
-            if (g_sigint) return interrupted();
-            AlignmentOwner rep;
-            if (V) {
-                tracs_alignment *r = nullptr;
-                if ((rc = bootstrap_weights_launch(L, seed, b, d_bits.as<unsigned>(), d_woff.as<unsigned>(), d_w.as<uint32_t>(), V, nullptr)) ||
-                    (rc = gather_sites(var.get(), d_w.as<uint32_t>(), &r, nullptr, nullptr, true))) return rc;
-                rep.reset(r);
-            }
-            lap(clock, acc[0]);
-            if ((rc = tree_of_alignment(rep.get(), n, names, 0, walk, d_state, clock, acc + 1, rep_t))) return rc;
-            if ((rc = tracs_tree_support(n, t.parent.data(), t.child.data(), t.ne, rep_t.parent.data(), rep_t.child.data(), rep_t.ne, support.data()))) return rc;
-            if (replicate_trees_path &&
-                (rc = tracs_tree_write(names, n, rep_t.parent.data(), rep_t.child.data(), rep_t.length.data(), rep_t.ne, replicate_trees_path, ref, nullptr))) return rc;
-            lap(clock, acc[3]);
-            if (transfer) {
-                size_t depth = 0;
-                if ((rc = tracs_tree_transfer_program(n, rep_t.parent.data(), rep_t.child.data(), rep_t.ne, program.data(), &depth))) return rc;
-                lap(clock, acc[4]);
-                if ((rc = transfer_add_program(d_transfer.ptr, n, program.data(), depth, nullptr, nullptr))) return rc;
-                lap(clock, acc[5]);
-            }
-        }
-        if (transfer && (rc = tracs_transfer_emit(d_transfer.ptr, n, sum_phi.data(), light.data()))) return rc;
-        if (clock.on) {
-            std::fprintf(stderr, "[stage] bootstrap: %u replicates over %zu differing columns\n", (unsigned)replicates, V);
-            std::fprintf(stderr, "[stage] replicates: weights + scan + gather %.4f s\n", acc[0]);
-            std::fprintf(stderr, "[stage] replicates: dense panels + matrix load %.4f s\n", acc[1]);
-            std::fprintf(stderr, "[stage] replicates: join loop %.4f s\n", acc[2]);
-            std::fprintf(stderr, "[stage] replicates: emit, lengths, support %.4f s\n", acc[3]);
-            if (transfer)
-                std::fprintf(stderr, "[stage] replicates: transfer distances %.4f s (program %.4f s, kernel %.4f s)\n", acc[4] + acc[5], acc[4], acc[5]);
-        }
-    }
-    if (transfer)
-        rc = tracs_tree_write_transfer(names, n, t.parent.data(), t.child.data(), t.length.data(), t.ne, support.data(), sum_phi.data(), light.data(),
-                                       replicates, path, ref, edges_path);
-    else
-        rc = tracs_tree_write_support(names, n, t.parent.data(), t.child.data(), t.length.data(), t.ne, support.data(), replicates, path, ref, edges_path);
-    if (rc) return rc;
-    clock.mark("tree: emit, lengths, format, write");
-    if (n_joins) *n_joins = t.nj;
-    if (rows_written) *rows_written = edges_path ? t.ne : 0;
-    if (g_sigint) return interrupted();
-    return TRACS_OK;
+    tracs_tree_request r = {kind, path, ref, edges_path};
+    r.changes = r.filter = 1; r.changes_path = changes_path; r.sites_path = sites_path; r.filtered_path = filtered_path; r.contig_names = contig_names;
+    r.contig_lengths = contig_lengths; r.n_contigs = n_contigs; r.max_entries = max_entries; r.n_threads = n_threads; r.create = create;
+    return tree_run_out("tracs_distance_tree_filter", h, r, {n_joins, rows_written, n_changes, sum_minimum, n_kept, n_edges_dropped});
 }
 
 int tracs_distance_tree_bootstrap(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint32_t replicates,
                                   uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins, uint64_t *rows_written)
 {
-    return tree_bootstrap_body("tracs_distance_tree_bootstrap", false, h, kind, path, ref, edges_path, replicates, seed, replicate_trees_path,
-                               n_joins, rows_written);
+    // (no replicates: a plain tree to a request, a refusal here -- as transfer support without replicates it stays one)
+    return tree_run_out("tracs_distance_tree_bootstrap", h, {kind, path, ref, edges_path, replicates, seed, !replicates, replicate_trees_path},
+                        {n_joins, rows_written});
 }
 
 int tracs_distance_tree_bootstrap_transfer(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path,
                                            uint32_t replicates, uint64_t seed, const char *replicate_trees_path, uint64_t *n_joins,
                                            uint64_t *rows_written)
 {
-    return tree_bootstrap_body("tracs_distance_tree_bootstrap_transfer", true, h, kind, path, ref, edges_path, replicates, seed,
-                               replicate_trees_path, n_joins, rows_written);
+    return tree_run_out("tracs_distance_tree_bootstrap_transfer", h, {kind, path, ref, edges_path, replicates, seed, 1, replicate_trees_path},
+                        {n_joins, rows_written});
 }
 
 // `tracs distance --histogram` for one alignment (include/tracs_hip.h): the panel walk of tracs_distance_run with

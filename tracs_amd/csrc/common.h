@@ -139,7 +139,32 @@ int bootstrap_weights_launch(size_t L, uint64_t seed, uint64_t replicate, const 
                              size_t weights_len, hipStream_t stream);
 int gather_sites(const tracs_alignment *src, const uint32_t *weights, tracs_alignment **out, size_t *n_out, hipStream_t stream, bool empty_ok,
                  double *stage_s = nullptr);
+// host only: the census bitmap `differs` (ceil(L / 64) words) as the bits / woff of bootstrap_weights_launch -> the differing columns
+size_t bootstrap_column_words(const uint64_t *differs, size_t L, std::vector<unsigned> &bits, std::vector<unsigned> &woff);
 
+// nj.hip: what the tracs_tree_write* functions write beside the tree itself (each NULL, or one value per edge), and the header of an edge
+// file with those columns.  support == NULL: tracs_tree_write, byte for byte.  Else (tracs_tree_write_support) an internal node whose
+// edge has a support other than 0xFFFFFFFF carries it as a decimal label, and the edge rows have a support field before ref ("NA" on
+// leaf edges and where there is none).  transfer != NULL (tracs_tree_write_transfer, with support): the label is the edge's transfer
+// support instead, written like a length (NaN: none), and the edge rows have a transfer field behind the support field.
+// changes != NULL (tracs_tree_write_changes, without support): the edge rows have a changes field before ref; the Newick line is
+// tracs_tree_write's.  filtered != NULL (tracs_tree_write_filtered, with changes): a filtered field behind the changes field.
+struct TreeColumns {
+    const uint32_t *support;
+    const double *transfer;
+    const uint32_t *changes, *filtered;
+};
+std::string tree_edges_header(const TreeColumns &cols);
+
+// Four host-side checks take an edge list, each for what its caller reads out of it, and each accepts another set of lists:
+//   * the loop in nj.hip's tree_write_body (tracs_tree_write*): 2n - 3 edges (n = 2: one, n < 2: none); every parent an internal node, no
+//     node hung twice, a parent's rows consecutive; any number of children, in any order of the nodes -- what a Newick line can say;
+//   * tree_bitsets (tracs_tree_support): n >= 4, 2n - 3 edges, no node hung twice, a parent not yet hung, an internal child already
+//     given its own children -- creation order, which the bottom-up bitsets need; any number of children;
+//   * transfer.hip's binary_tree_check (tracs_tree_transfer_program, tracs_transfer_init): tree_bitsets, and two children per joined
+//     node, three at the top one;
+//   * fitch.hip's fitch_tree_check (tracs_fitch_*): exactly the rows of tracs_nj_edges -- node n + t is the parent of rows 2t and 2t + 1,
+//     the top node of the last three, children ascending within a node and older than their parent; n = 1 and n = 2 as tracs_nj_edges.
 // bootstrap.hip, host only: a tree's edges checked (2n - 3 of them, creation order) and, with below != NULL, the leaves under every internal
 // node v as a bitset of ceil(n / 64) words at (*below)[(v - n) * W]; kids != NULL: <- every node's number of children
 int tree_bitsets(const char *who, size_t n, const uint32_t *parent, const uint32_t *child, size_t n_edges, std::vector<uint64_t> *below,

@@ -454,18 +454,19 @@ void append_label(std::string &out, const char *name)
 
 }  // namespace
 
+// the header of the edge file whose rows tree_write_body writes under the same columns: the fields in the row loop's order
+std::string tracs::tree_edges_header(const TreeColumns &cols)
+{
+    return std::string("parent,child,length,") + (cols.changes ? "changes," : "") + (cols.filtered ? "filtered," : "") +
+           (cols.support ? "support," : "") + (cols.transfer ? "transfer," : "") + "MSA file\n";
+}
+
 // One Newick line appended to `path` and, with edges_path, the rows parent,child,length,MSA file (internal node n + t is "#t+1").
 // The edges are tracs_nj_edges's: a node's children are consecutive rows, in id order; the last row's parent is the top node.  The
 // writer walks the tree with a stack of its own: a caterpillar is n deep.
-// support == NULL: tracs_tree_write, byte for byte.  Else (tracs_tree_write_support) an internal node whose edge has a support other than
-// NO_SUPPORT carries it as a decimal label, and the edge rows have a support field before ref ("NA" on leaf edges and where there is none).
-// transfer != NULL (tracs_tree_write_transfer, with support): the label is the edge's transfer support instead, written like a length
-// (NaN: none), and the edge rows have a transfer field behind the support field.
-// changes != NULL (tracs_tree_write_changes, without support): the edge rows have a changes field before ref; the Newick line is
-// tracs_tree_write's.  filtered != NULL (tracs_tree_write_filtered, with changes): a filtered field behind the changes field.
+// cols (common.h): the labels of the internal nodes and the further fields of the edge rows.
 static int tree_write_body(const char *who, const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
-                           size_t n_edges, const uint32_t *support, const double *transfer, const char *path, const char *ref,
-                           const char *edges_path, const uint32_t *changes = nullptr, const uint32_t *filtered = nullptr)
+                           size_t n_edges, const TreeColumns &cols, const char *path, const char *ref, const char *edges_path)
 {
     constexpr uint32_t NO_SUPPORT = 0xFFFFFFFFu;
     if (!path || (n && !names) || (n_edges && (!parent || !child || !length)) || (edges_path && !ref)) {
@@ -508,8 +509,8 @@ static int tree_write_body(const char *who, const char *const *names, size_t n, 
                 stack.pop_back();
                 text.push_back(')');
                 if (node != top) {
-                    if (transfer) { if (!std::isnan(transfer[up[node]])) append_length(text, transfer[up[node]]); }
-                    else if (support && support[up[node]] != NO_SUPPORT) text += std::to_string(support[up[node]]);
+                    if (cols.transfer) { if (!std::isnan(cols.transfer[up[node]])) append_length(text, cols.transfer[up[node]]); }
+                    else if (cols.support && cols.support[up[node]] != NO_SUPPORT) text += std::to_string(cols.support[up[node]]);
                     text.push_back(':');
                     append_length(text, length[up[node]]);
                 }
@@ -540,15 +541,15 @@ static int tree_write_body(const char *who, const char *const *names, size_t n, 
             node_name(parent[e]); rows.push_back(',');
             node_name(child[e]); rows.push_back(',');
             append_length(rows, length[e]); rows.push_back(',');
-            if (changes) { rows += std::to_string(changes[e]); rows.push_back(','); }
-            if (filtered) { rows += std::to_string(filtered[e]); rows.push_back(','); }
-            if (support) {
-                if (child[e] >= n && n >= 3 && support[e] != NO_SUPPORT) rows += std::to_string(support[e]);
+            if (cols.changes) { rows += std::to_string(cols.changes[e]); rows.push_back(','); }
+            if (cols.filtered) { rows += std::to_string(cols.filtered[e]); rows.push_back(','); }
+            if (cols.support) {
+                if (child[e] >= n && n >= 3 && cols.support[e] != NO_SUPPORT) rows += std::to_string(cols.support[e]);
                 else rows += "NA";
                 rows.push_back(',');
             }
-            if (transfer) {
-                if (child[e] >= n && n >= 3 && !std::isnan(transfer[e])) append_length(rows, transfer[e]);
+            if (cols.transfer) {
+                if (child[e] >= n && n >= 3 && !std::isnan(cols.transfer[e])) append_length(rows, cols.transfer[e]);
                 else rows += "NA";
                 rows.push_back(',');
             }
@@ -567,7 +568,18 @@ extern "C" {
 int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length, size_t n_edges,
                      const char *path, const char *ref, const char *edges_path)
 {
-    return tree_write_body("tracs_tree_write", names, n, parent, child, length, n_edges, nullptr, nullptr, path, ref, edges_path);
+    return tree_write_body("tracs_tree_write", names, n, parent, child, length, n_edges, {nullptr, nullptr, nullptr, nullptr}, path, ref, edges_path);
+}
+
+// tests: tree_edges_header for the columns that are named (non-zero) into out[cap]
+int tracs_debug_tree_edges_header(int support, int transfer, int changes, int filtered, char *out, size_t cap)
+{
+    static const uint32_t u = 0;
+    static const double d = 0.0;
+    const std::string head = tree_edges_header({support ? &u : nullptr, transfer ? &d : nullptr, changes ? &u : nullptr, filtered ? &u : nullptr});
+    if (!out || cap <= head.size()) { set_error("tracs_debug_tree_edges_header: the buffer is too small"); return TRACS_E_ARG; }
+    std::memcpy(out, head.c_str(), head.size() + 1);
+    return TRACS_OK;
 }
 
 // tracs_tree_write with the number of changes on every edge: the same Newick line, and the rows
@@ -576,9 +588,7 @@ int tracs_tree_write_changes(const char *const *names, size_t n, const uint32_t 
                              size_t n_edges, const uint32_t *changes, const char *path, const char *ref, const char *edges_path)
 {
     if (n_edges && !changes) { set_error("tracs_tree_write_changes: NULL argument"); return TRACS_E_ARG; }
-    static const uint32_t none = 0;
-    return tree_write_body("tracs_tree_write_changes", names, n, parent, child, length, n_edges, nullptr, nullptr, path, ref, edges_path,
-                           n_edges ? changes : &none);
+    return tree_write_body("tracs_tree_write_changes", names, n, parent, child, length, n_edges, {nullptr, nullptr, changes, nullptr}, path, ref, edges_path);
 }
 
 // tracs_tree_write_changes with the changes the branch filter keeps on every edge: the same Newick line, and the rows
@@ -588,9 +598,7 @@ int tracs_tree_write_filtered(const char *const *names, size_t n, const uint32_t
                               const char *edges_path)
 {
     if (n_edges && (!changes || !filtered)) { set_error("tracs_tree_write_filtered: NULL argument"); return TRACS_E_ARG; }
-    static const uint32_t none = 0;
-    return tree_write_body("tracs_tree_write_filtered", names, n, parent, child, length, n_edges, nullptr, nullptr, path, ref, edges_path,
-                           n_edges ? changes : &none, n_edges ? filtered : &none);
+    return tree_write_body("tracs_tree_write_filtered", names, n, parent, child, length, n_edges, {nullptr, nullptr, changes, filtered}, path, ref, edges_path);
 }
 
 // tracs_tree_write with bootstrap support: `(A:1,B:2)87:0.5`, and the rows parent,child,length,support,ref.
@@ -604,7 +612,7 @@ int tracs_tree_write_support(const char *const *names, size_t n, const uint32_t 
             set_error("tracs_tree_write_support: a support of " + std::to_string(support[e]) + " out of " + std::to_string(replicates) + " replicates");
             return TRACS_E_ARG;
         }
-    return tree_write_body("tracs_tree_write_support", names, n, parent, child, length, n_edges, n_edges ? support : &none, nullptr, path, ref, edges_path);
+    return tree_write_body("tracs_tree_write_support", names, n, parent, child, length, n_edges, {support, nullptr, nullptr, nullptr}, path, ref, edges_path);
 }
 
 // tracs_tree_write_support with the transfer support as the label: x_e = 1 - Phi_e / (B (p_e - 1)), one rounding per
@@ -632,8 +640,7 @@ int tracs_tree_write_transfer(const char *const *names, size_t n, const uint32_t
         const double q = (double)sum_phi[e] / (double)den;
         x[e] = 1.0 - q;
     }
-    return tree_write_body("tracs_tree_write_transfer", names, n, parent, child, length, n_edges, n_edges ? support : &none, x.data(), path, ref,
-                           edges_path);
+    return tree_write_body("tracs_tree_write_transfer", names, n, parent, child, length, n_edges, {support, x.data(), nullptr, nullptr}, path, ref, edges_path);
 }
 
 }  // extern "C"

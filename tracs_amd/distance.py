@@ -470,9 +470,9 @@ def check_tree_args(args):
                 raise SystemExit("tracs distance: %s needs --tree (it places the sites on the tree that --tree builds)" % opt)
         if args.max_entries is not None:
             raise SystemExit("tracs distance: --max-entries needs --tree-changes, which needs --tree (it bounds the rows of that file)")
-        if getattr(args, "tree_filter", False):
+        if args.tree_filter:
             raise SystemExit("tracs distance: --tree-filter needs --tree (it filters the changes on the branches of the tree that --tree builds)")
-        if getattr(args, "tree_filtered", None) is not None:
+        if args.tree_filtered is not None:
             raise SystemExit("tracs distance: --tree-filtered needs --tree-filter, which needs --tree (it holds the tree with the kept changes "
                              "as branch lengths)")
         return
@@ -507,20 +507,16 @@ def check_tree_args(args):
         if TREE_DISTANCES[args.tree_distance or "snp"] == 1:
             raise SystemExit("tracs distance: --bootstrap resamples SNP distances and takes no --tree-distance per-site (a replicate's "
                              "compared-site counts need every column, not only the differing ones)")
-    for opt, value in (("--tree-changes", args.tree_changes), ("--tree-sites", args.tree_sites)):
-        if value is not None and args.bootstrap is not None:
+    for opt, given in (("--tree-changes", args.tree_changes is not None), ("--tree-sites", args.tree_sites is not None),
+                       ("--tree-filter", args.tree_filter)):
+        if given and args.bootstrap is not None:
             raise SystemExit("tracs distance: %s and --bootstrap cannot be combined yet (the tree is reproducible bit for bit: run once with "
                              "each and join the two --tree-edges files on parent and child)" % opt)
-    tree_filter, tree_filtered = getattr(args, "tree_filter", False), getattr(args, "tree_filtered", None)
-    if tree_filtered is not None and not tree_filter:
+    if args.tree_filtered is not None and not args.tree_filter:
         raise SystemExit("tracs distance: --tree-filtered needs --tree-filter (it holds the tree with the kept changes as branch lengths)")
-    if tree_filter:
-        if args.bootstrap is not None:
-            raise SystemExit("tracs distance: --tree-filter and --bootstrap cannot be combined yet (the tree is reproducible bit for bit: run "
-                             "once with each and join the two --tree-edges files on parent and child)")
-        if args.tree_edges is None and args.tree_changes is None and tree_filtered is None:
-            raise SystemExit("tracs distance: --tree-filter needs --tree-edges, --tree-changes or --tree-filtered (the files its verdicts go to)")
-    if args.max_entries is not None and args.tree_changes is None and not tree_filter:
+    if args.tree_filter and args.tree_edges is None and args.tree_changes is None and args.tree_filtered is None:
+        raise SystemExit("tracs distance: --tree-filter needs --tree-edges, --tree-changes or --tree-filtered (the files its verdicts go to)")
+    if args.max_entries is not None and args.tree_changes is None and not args.tree_filter:
         raise SystemExit("tracs distance: --max-entries needs --tree-changes (it bounds the rows of that file; --tree-sites has at most one "
                          "row per site)")
     check_output_paths("distance", _inputs(args), dict(_outputs(args), **{"--tree-edges": args.tree_edges}), ["--tree-edges"])
@@ -529,56 +525,55 @@ def check_tree_args(args):
     check_output_paths("distance", _inputs(args), tree_outputs, ["--tree-sites"])
     check_output_paths("distance", _inputs(args), dict(_outputs(args), **{"--tree-edges": args.tree_edges, "--bootstrap-trees": args.bootstrap_trees}),
                        ["--bootstrap-trees"])
-    if tree_filtered is not None:
-        check_output_paths("distance", _inputs(args), dict(tree_outputs, **{"--tree-filtered": tree_filtered}), ["--tree-filtered"])
+    if args.tree_filtered is not None:
+        check_output_paths("distance", _inputs(args), dict(tree_outputs, **{"--tree-filtered": args.tree_filtered}), ["--tree-filtered"])
+
+
+def tree_changes_on(args):
+    """the run places the sites on the tree (the changes stage of the tree request): the library then creates the run's files itself"""
+    return args.tree is not None and (args.tree_changes is not None or args.tree_sites is not None or args.tree_filter)
+
+
+def tree_edges_header(args):
+    """the header of --tree-edges for what the run asks of the tree"""
+    return (TREE_EDGES_FILTER_HEADER if args.tree_filter else TREE_EDGES_CHANGES_HEADER if tree_changes_on(args) else
+            TREE_EDGES_HEADER if args.bootstrap is None else
+            TREE_EDGES_TRANSFER_HEADER if args.bootstrap_support == "transfer" else TREE_EDGES_SUPPORT_HEADER)
 
 
 def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None, tree_contigs=None):
-    """--tree nj for one alignment (handle.DistanceHandle.tree, tracs_distance_tree: include/tracs_hip.h): every dense panel goes into the
-    distance matrix on the device, the joins run there, and one Newick line (and the edge rows) are appended by the library."""
+    """--tree nj for one alignment (handle.DistanceHandle.tree, tracs_distance_tree_run: include/tracs_hip.h): every dense panel goes into
+    the distance matrix on the device, the joins run there, and one Newick line (and the edge rows) are appended by the library."""
+    changes_on = tree_changes_on(args)
     with _opened(msas, args, stage, rule, contigs) as h:
-        if getattr(args, "tree_filter", False):
-            # (as below: the library creates the files itself, once the count has passed --max-entries)
-            try:
-                joins, rows, changes, minimum, kept, branches = h.tree(
-                    args.output_file, ref, per_site=TREE_DISTANCES[args.tree_distance or "snp"] == 1, edges_path=args.tree_edges,
-                    changes_path=args.tree_changes, sites_path=args.tree_sites, max_entries=args.max_entries, contigs=tree_contigs,
-                    n_threads=args.n_cpu, create=not getattr(args, "tree_files_made", False), tree_filter=True, filtered_path=args.tree_filtered)
-            except RuntimeError as e:
-                raise SystemExit("tracs distance: %s" % e)
-            args.tree_files_made = True
-            if args.tree_changes is not None or args.tree_sites is not None:
-                sys.stderr.write("tracs distance: %s: parsimony length %d, minimum %d, consistency index %s\n"
-                                 % (ref, changes, minimum, repr(minimum / changes) if changes else "1"))
-            sys.stderr.write("tracs distance: %s: tree filter: %d changes, %d kept, %d dropped, %d branches with a drop\n"
-                             % (ref, changes, kept, changes - kept, branches))
-            stage("[sum] tracs_distance_tree_filter (dense panels, joins, tree, Fitch count, edge lists, filter, fill: %d joins, %d edge rows, "
-                  "%d changes, %d kept)" % (joins, rows, changes, kept))
-            return
+        try:
+            # (the changes stage: the library creates the files itself, once the count has passed --max-entries: a refusal touches nothing)
+            t = h.tree(args.output_file, ref, per_site=TREE_DISTANCES[args.tree_distance or "snp"] == 1, edges_path=args.tree_edges,
+                       bootstrap=args.bootstrap or 0, seed=1 if args.bootstrap_seed is None else args.bootstrap_seed,
+                       replicate_trees=args.bootstrap_trees, support=args.bootstrap_support or "split", changes_path=args.tree_changes,
+                       sites_path=args.tree_sites, max_entries=args.max_entries, contigs=tree_contigs, n_threads=args.n_cpu,
+                       create=not args.tree_files_made, tree_filter=args.tree_filter, filtered_path=args.tree_filtered)
+        except RuntimeError as e:
+            if not changes_on:                                              # (the plain and the bootstrap run pass the library's error on)
+                raise
+            raise SystemExit("tracs distance: %s" % e)
+        args.tree_files_made = True                                        # (read by the changes stage only)
         if args.tree_changes is not None or args.tree_sites is not None:
-            # (the library creates the four files itself, once the count has passed --max-entries: a refusal touches nothing)
-            try:
-                joins, rows, changes, minimum = h.tree(args.output_file, ref, per_site=TREE_DISTANCES[args.tree_distance or "snp"] == 1,
-                                                       edges_path=args.tree_edges, changes_path=args.tree_changes, sites_path=args.tree_sites,
-                                                       max_entries=args.max_entries, contigs=tree_contigs, n_threads=args.n_cpu,
-                                                       create=not getattr(args, "tree_files_made", False))
-            except RuntimeError as e:
-                raise SystemExit("tracs distance: %s" % e)
-            args.tree_files_made = True
             sys.stderr.write("tracs distance: %s: parsimony length %d, minimum %d, consistency index %s\n"
-                             % (ref, changes, minimum, repr(minimum / changes) if changes else "1"))
+                             % (ref, t.changes, t.minimum, repr(t.minimum / t.changes) if t.changes else "1"))
+        if args.tree_filter:
+            sys.stderr.write("tracs distance: %s: tree filter: %d changes, %d kept, %d dropped, %d branches with a drop\n"
+                             % (ref, t.changes, t.kept, t.changes - t.kept, t.branches))
+            stage("[sum] tracs_distance_tree_filter (dense panels, joins, tree, Fitch count, edge lists, filter, fill: %d joins, %d edge rows, "
+                  "%d changes, %d kept)" % (t.joins, t.rows, t.changes, t.kept))
+        elif changes_on:
             stage("[sum] tracs_distance_tree_changes (dense panels, joins, tree, Fitch count and fill: %d joins, %d edge rows, %d changes)"
-                  % (joins, rows, changes))
-            return
-        if args.bootstrap is not None:
-            joins, rows = h.tree(args.output_file, ref, edges_path=args.tree_edges, bootstrap=args.bootstrap,
-                                 seed=1 if args.bootstrap_seed is None else args.bootstrap_seed, replicate_trees=args.bootstrap_trees,
-                                 support=args.bootstrap_support or "split")
+                  % (t.joins, t.rows, t.changes))
+        elif args.bootstrap is not None:
             stage("[sum] tracs_distance_tree_bootstrap%s (main tree, %d replicates: %d joins, %d edge rows written)"
-                  % ("_transfer" if args.bootstrap_support == "transfer" else "", args.bootstrap, joins, rows))
-            return
-        joins, rows = h.tree(args.output_file, ref, per_site=TREE_DISTANCES[args.tree_distance or "snp"] == 1, edges_path=args.tree_edges)
-        stage("[sum] tracs_distance_tree (dense panels, joins, tree: %d joins, %d edge rows written)" % (joins, rows))
+                  % ("_transfer" if args.bootstrap_support == "transfer" else "", args.bootstrap, t.joins, t.rows))
+        else:
+            stage("[sum] tracs_distance_tree (dense panels, joins, tree: %d joins, %d edge rows written)" % (t.joins, t.rows))
 
 
 def check_mst_args(args):
@@ -980,14 +975,13 @@ def distance(args):
     logging.info("Loading metadata...")
     dates = _read_dates(args.metadata) if args.metadata is not None else None
     logging.info("Estimating transmission distances...")
-    tree_changes = args.tree is not None and (args.tree_changes is not None or args.tree_sites is not None or getattr(args, "tree_filter", False))
-    if lead and not tree_changes:                  # (--tree-changes / --tree-sites: tracs_distance_tree_changes creates the run's files)
+    tree_changes, args.tree_files_made = tree_changes_on(args), False
+    if lead and not tree_changes:                  # (the changes stage of the tree request: the library creates the run's files)
         with open(args.output_file, "w") as out:
             out.write("" if args.tree is not None else HISTOGRAM_HEADER if args.histogram else HEADER)      # (Newick lines: no header)
         if args.tree is not None and args.tree_edges is not None:
             with open(args.tree_edges, "w") as out:
-                out.write(TREE_EDGES_HEADER if args.bootstrap is None else
-                          TREE_EDGES_TRANSFER_HEADER if args.bootstrap_support == "transfer" else TREE_EDGES_SUPPORT_HEADER)
+                out.write(tree_edges_header(args))
         if args.tree is not None and args.bootstrap_trees is not None:
             open(args.bootstrap_trees, "w").close()
         if args.ancestors is not None and args.ancestors_out is not None:

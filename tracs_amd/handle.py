@@ -4,11 +4,14 @@ Python calls the _rules form of every FASTA entry point (tracs_pairsnp_rules, tr
 with no field set is the plain call and one with only keep / max_n_samples the _sites call (rules_from_struct, csrc/capi.hip); the other
 two forms stay in the C ABI.  numpy is imported where it is needed: the plain device route of `tracs distance` runs without it.
 """
+import collections
 import ctypes as C
 import os
 
 from . import _lib
 
+
+TreeResult = collections.namedtuple("TreeResult", "joins rows changes minimum kept branches")
 
 OPEN_STAGE = "[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)"      # the [stage] line of an open (TRACS_STAGE_TRACE)
 
@@ -129,28 +132,19 @@ class DistanceHandle:
     def tree(self, path, ref, per_site=False, edges_path=None, bootstrap=0, seed=1, replicate_trees=None, support="split",
              changes_path=None, sites_path=None, max_entries=None, contigs=None, n_threads=0, create=True, tree_filter=False,
              filtered_path=None):
-        """The neighbour-joining tree of the handle's samples (tracs_distance_tree): one Newick line appended to `path`, the edge rows
-        to edges_path.  bootstrap = B > 0 (tracs_distance_tree_bootstrap): B bootstrap replicates under `seed`; the internal nodes are
-        labelled with the number of replicates that have their split, the edge rows gain a support field, and replicate_trees receives
-        each replicate's Newick line.  support="transfer" (tracs_distance_tree_bootstrap_transfer): the labels are the transfer
-        supports, doubles in [0, 1], and the edge rows carry both the count and the transfer support.  -> (joins, edge rows written)
-        changes_path / sites_path (tracs_distance_tree_changes; no bootstrap): every site placed on the tree by Fitch's
-        two passes -- one row per change, one per site with a change, and a changes field in the edge rows.  More than max_entries
-        (default 10^8) changes are refused before any file is touched; create: the files are created with their headers (False: appended
-        to); contigs: [(name, length)] or None.  -> (joins, edge rows written, changes, sum of the sites' minimum)
-        tree_filter (tracs_distance_tree_filter; no bootstrap): the recombination filter's window test on the changes of
-        every branch -- the edge rows gain the kept changes, the change rows a dropped field, and filtered_path receives the tree whose
-        branch lengths are the kept changes.  The tree itself is built from the unfiltered distances; max_entries then bounds the edge
-        lists too.  -> (joins, edge rows written, changes, sum of the sites' minimum, changes kept, branches with a drop)"""
+        """The neighbour-joining tree of the handle's samples: the keywords as one tracs_tree_request (include/tracs_hip.h describes every
+        field) -> TreeResult, 0 where nothing was asked for.  One Newick line is appended to `path`, the edge rows to
+        edges_path.  bootstrap = B > 0: B replicates under `seed`, support "split" or "transfer", each replicate's line to replicate_trees.
+        changes_path / sites_path / tree_filter (no bootstrap): every site placed on the tree, at most max_entries (default 10^8) changes,
+        contigs [(name, length)] or None; create: the library creates the files with their headers (False: it appends to them)."""
         if support not in ("split", "transfer"):
             raise ValueError("tree(): support is 'split' or 'transfer'")
-        joins, rows = C.c_uint64(0), C.c_uint64(0)
-        enc = lambda p: os.fsencode(p) if p is not None else None         # noqa: E731
         if filtered_path is not None and not tree_filter:
             raise ValueError("tree(): filtered_path needs tree_filter")
         if tree_filter and edges_path is None and changes_path is None and filtered_path is None:
             raise ValueError("tree(): tree_filter needs edges_path, changes_path or filtered_path")
-        if changes_path is not None or sites_path is not None or tree_filter:
+        changes = changes_path is not None or sites_path is not None or tree_filter
+        if changes:
             if bootstrap:
                 raise ValueError("tree(): changes_path / sites_path / tree_filter take no bootstrap")
             if max_entries is not None and changes_path is None and not tree_filter:
@@ -158,40 +152,29 @@ class DistanceHandle:
             max_entries = 100000000 if max_entries is None else int(max_entries)
             if max_entries < 1:
                 raise ValueError("tree(): max_entries must be at least 1")
-            nc = len(contigs) if contigs is not None else 0
-            cnames = (C.c_char_p * max(nc, 1))(*[c[0].encode() for c in (contigs or [])])
-            clens = (C.c_uint64 * max(nc, 1))(*[int(c[1]) for c in (contigs or [])])
-            changes, minimum = C.c_uint64(0), C.c_uint64(0)
-            if tree_filter:
-                kept, dropped_edges = C.c_uint64(0), C.c_uint64(0)
-                _lib.check(self.L.tracs_distance_tree_filter(self.h, int(bool(per_site)), os.fsencode(path), ref.encode(), enc(edges_path),
-                                                             enc(changes_path), enc(sites_path), enc(filtered_path), cnames, clens, nc, max_entries,
-                                                             int(n_threads), int(bool(create)), C.byref(joins), C.byref(rows), C.byref(changes),
-                                                             C.byref(minimum), C.byref(kept), C.byref(dropped_edges)))
-                return joins.value, rows.value, changes.value, minimum.value, kept.value, dropped_edges.value
-            _lib.check(self.L.tracs_distance_tree_changes(self.h, int(bool(per_site)), os.fsencode(path), ref.encode(), enc(edges_path),
-                                                          enc(changes_path), enc(sites_path), cnames, clens, nc, max_entries, int(n_threads),
-                                                          int(bool(create)), C.byref(joins), C.byref(rows), C.byref(changes),
-                                                          C.byref(minimum)))
-            return joins.value, rows.value, changes.value, minimum.value
-        if max_entries is not None:
+        elif max_entries is not None:
             raise ValueError("tree(): max_entries needs changes_path")
-        if not bootstrap:
+        elif not bootstrap:
             if replicate_trees is not None:
                 raise ValueError("tree(): replicate_trees needs bootstrap > 0")
             if support != "split":
                 raise ValueError("tree(): support='transfer' needs bootstrap > 0")
-            _lib.check(self.L.tracs_distance_tree(self.h, int(bool(per_site)), os.fsencode(path), ref.encode(), enc(edges_path),
-                                                  C.byref(joins), C.byref(rows)))
-            return joins.value, rows.value
-        if per_site:
+        elif per_site:
             raise ValueError("tree(): bootstrap replicates take the SNP distance only (per_site=False)")
-        if not (1 <= int(bootstrap) < 2 ** 32) or not (0 <= int(seed) < 2 ** 64):
+        elif not (1 <= int(bootstrap) < 2 ** 32) or not (0 <= int(seed) < 2 ** 64):
             raise ValueError("tree(): bootstrap must be in [1, 2^32) and seed in [0, 2^64)")
-        entry = self.L.tracs_distance_tree_bootstrap_transfer if support == "transfer" else self.L.tracs_distance_tree_bootstrap
-        _lib.check(entry(self.h, 0, os.fsencode(path), ref.encode(), enc(edges_path), int(bootstrap), int(seed), enc(replicate_trees),
-                         C.byref(joins), C.byref(rows)))
-        return joins.value, rows.value
+        enc = lambda p: os.fsencode(p) if p is not None else None         # noqa: E731
+        contigs = contigs if changes and contigs else []                    # (read by the change and site rows only)
+        req = _lib.TreeRequest(
+            kind=int(bool(per_site)), path=os.fsencode(path), ref=ref.encode(), edges_path=enc(edges_path), replicates=int(bootstrap),
+            seed=int(seed), transfer=int(bool(bootstrap) and support == "transfer"), replicate_trees_path=enc(replicate_trees) if bootstrap else None,
+            changes=int(changes), changes_path=enc(changes_path), sites_path=enc(sites_path), filter=int(bool(tree_filter)),
+            filtered_path=enc(filtered_path), contig_names=(C.c_char_p * len(contigs))(*[c[0].encode() for c in contigs]),
+            contig_lengths=(C.c_uint64 * len(contigs))(*[int(c[1]) for c in contigs]), n_contigs=len(contigs),
+            max_entries=max_entries or 0, n_threads=int(n_threads), create=int(bool(create)))
+        res = _lib.TreeResult()
+        _lib.check(self.L.tracs_distance_tree_run(self.h, C.byref(req), C.byref(res)))
+        return TreeResult(*(getattr(res, name) for name, _ in res._fields_))
 
     def alignment(self):
         """the handle's packed alignment, borrowed: close it before the handle"""
