@@ -87,6 +87,22 @@ def ref_module():
         return None
 
 
+def ref_pairsnp_module(strict=False):
+    """The reference's src/pairsnp.hpp compiled in place over oracle/boost_standin (oracle/_ref), or None: ref_pairsnp(fastas,
+    n_threads = 1, dist, filter), ref_filter_recomb_positions(L, positions), ref_range_count, ref_cached_binomial_cdf.
+    strict: the IEEE-strict twin.  The default build carries -ffast-math: load it in a child process."""
+    d = os.path.join(_HERE, "_ref")
+    if not os.path.isdir(d):
+        return None
+    if d not in sys.path:
+        sys.path.insert(0, d)
+    try:
+        import importlib
+        return importlib.import_module("_tracs_ref_pairsnp_strict" if strict else "_tracs_ref_pairsnp")
+    except ImportError:
+        return None
+
+
 def kseq_dump_path():
     p = os.path.join(_HERE, "_ref", "kseq_dump")
     return p if os.path.exists(p) else None
@@ -178,8 +194,9 @@ def filter_recomb_positions(pos, L):
 
 
 def filter_recomb_pairs(seqs, rows, cols, n_threads=1):
-    """Filtered SNP distance (src/pairsnp.hpp:251-318) of the listed pairs.  No comparison with Boost; pinned to the
-    definition at 50 digits on crafted boundary cases (tests/test_filter_hp.py)."""
+    """Filtered SNP distance (src/pairsnp.hpp:251-318) of the listed pairs.  Equal to the reference's own filter_recomb compiled
+    over the stand-in CDF (tests/test_pairsnp_ref.py); no comparison with Boost's CDF itself: the decision is pinned to the definition at
+    50 digits on crafted boundary cases (tests/test_filter_hp.py)."""
     seqs = np.ascontiguousarray(seqs, dtype=np.uint8)
     n, L = seqs.shape
     planes = pack(seqs)

@@ -7,8 +7,9 @@
 //   src/transcluster.hpp   -- needs only libstdc++/libm (it relies on pybind11/stl.h having
 //                             pulled in <vector>/<unordered_map>, as python_bindings.cpp does)
 //   src/dmultinomial.hpp   -- needs pybind11 + numpy (both present in the image)
-//   src/pairsnp.hpp        -- NOT built: needs boost/dynamic_bitset.hpp and
-//                             boost/math/distributions/binomial.hpp, absent from the image.
+//   src/pairsnp.hpp        -- built by ref_pairsnp_shim.cpp into a module of its own (_tracs_ref_pairsnp): it needs
+//                             boost/dynamic_bitset.hpp and boost/math/distributions/binomial.hpp, absent from the
+//                             image, and gets our stand-ins for the two (oracle/boost_standin).
 //
 // Module name `_tracs_ref`; function names are prefixed ref_ so nothing can mistake it for
 // the product's `TRACS` module.  Extra entry points (ref_lprob_k_given_N_2, ref_expected_k,

@@ -14,11 +14,17 @@
  *     src/transcluster.hpp + src/dmultinomial.hpp compiled from where they lie with
  *     setup.py's flags) through tests/golden/ fixtures.
  *   - orc_read_fasta: PINNED against oracle/_ref/kseq_dump (reference src/kseq.h).
- *   - orc_pairsnp / orc_pack: PARITY UNPINNED.  src/pairsnp.hpp needs Boost
- *     (dynamic_bitset, math/binomial) which this image lacks, so it is unbuildable
- *     here, and the reference's golden inputs (ambig.aln, long_filt.aln) are not in
- *     the tree.  The restatement is cross-checked against an independent per-site
- *     numpy brute force (oracle/oracle.py: brute_pairsnp) instead.
+ *   - orc_pairsnp / orc_pack / orc_filter_recomb_*: PINNED against the reference's own
+ *     src/pairsnp.hpp, compiled unmodified from where it lies into
+ *     oracle/_ref/_tracs_ref_pairsnp (ref_pairsnp_shim.cpp).  The two Boost headers it
+ *     includes are absent from the image; oracle/boost_standin (our own code) stands in
+ *     for them.  So load_seqs, the pair loop, the emission rule and order, range_count
+ *     and filter_recomb's control flow are the reference's (tests/test_pairsnp_ref.py,
+ *     fixture tests/golden/pairsnp_ref_golden.npz); the binomial CDF's numerics are the
+ *     stand-in's, held to the definition at 50 digits, NOT Boost's.  Still unpinned: the
+ *     reference's known answers for ambig.aln / long_filt.aln (inputs not in its tree).
+ *     An independent per-site numpy brute force (oracle/oracle.py: brute_pairsnp) is
+ *     compared as well.
  */
 #include <ctype.h>
 #include <math.h>

@@ -6,9 +6,12 @@ Sources of truth, in order of authority:
     from where they lie under /root/reference with setup.py's flags (oracle/Makefile);
   * the reference's Python drivers imported from /root/reference (tracs/transcluster.py, tracs/cluster.py,
     tracs/distance.py, tracs/dirichlet_multinomial.py) with a stub `TRACS` module whose trans_dist /
-    calculate_posteriors / lprob_k_given_N are oracle/_ref and whose pairsnp is OUR oracle
-    (src/pairsnp.hpp cannot be built here: Boost is absent -- pairsnp fixtures are therefore
-    "unpinned" and additionally cross-checked against an independent numpy brute force).
+    calculate_posteriors / lprob_k_given_N are oracle/_ref and whose pairsnp is the reference's own
+    src/pairsnp.hpp, compiled in place over oracle/boost_standin (oracle/_ref/_tracs_ref_pairsnp: Boost is
+    absent here, so the bitset and the binomial CDF it includes are our stand-ins; everything else --
+    load_seqs, the pair loop, range_count, filter_recomb's control flow -- is the reference's).
+    `pairsnp-ref` records that module's outputs (pairsnp_ref_golden.npz); pairsnp_unpinned.json holds the
+    oracle's values, asserted equal to the reference's and to an independent numpy brute force.
 Only DATA is written (inputs + expected outputs); no reference source text is stored.
 """
 import json
@@ -207,7 +210,17 @@ def oracle_vs_ref():
     print("wrote oracle_vs_ref_golden.npz")
 
 
+def _ref_pairsnp_both(fastas, dist, filt):
+    """ref_pairsnp through both builds of the reference's source (setup.py's flags, IEEE-strict): equal, or nothing is recorded"""
+    a = O.ref_pairsnp_module().ref_pairsnp(fastas, 1, int(dist), bool(filt))
+    b = O.ref_pairsnp_module(strict=True).ref_pairsnp(fastas, 1, int(dist), bool(filt))
+    assert a == b, ("the fast-math and the strict build of the reference disagree", fastas, dist, filt)
+    return a
+
+
 def pairsnp_unpinned():
+    sys.path.insert(0, os.path.dirname(HERE))
+    import pairsnp_ref_cases as PC
     cases = {}
     specs = {"iupac_small": dict(n=7, L=61, seed=3, mu_lineage=0.05, mu_sample=0.03, p_n=0.05, p_partial=0.1, p_lower=0.2, p_other=0.05),
              "tail_129": dict(n=12, L=129, seed=4, mu_lineage=0.02, mu_sample=0.02, p_n=0.02, p_partial=0.02),
@@ -218,18 +231,234 @@ def pairsnp_unpinned():
             a = O.pairsnp_arrays(seqs, n0=n0, dist=dist)
             b = O.brute_pairsnp(seqs, n0=n0, dist=dist)
             assert all(np.array_equal(x, y) for x, y in zip(a, b)), "oracle != brute force"
+            with tempfile.TemporaryDirectory() as td:           # and the reference's own pair loop on the same samples
+                fas = PC.write_fastas(dict(name=name + mode, n0=n0, width=0, crlf=False, gz=False), seqs, td)
+                ref = _ref_pairsnp_both(fas, dist, False)
+            assert all(np.array_equal(x, np.asarray(y, np.uint64)) for x, y in zip(a, (ref[0], ref[1], ref[2], ref[5]))), "oracle != reference"
             cases["%s/%s" % (name, mode)] = {"seqs": [row.tobytes().decode("ascii") for row in seqs], "n0": n0, "dist": dist,
                                              "rows": a[0].tolist(), "cols": a[1].tolist(), "d": a[2].tolist(),
                                              "nn": a[3].tolist()}
-    jdump("pairsnp_unpinned.json", {"status": "PARITY UNPINNED: produced by oracle/tracs_oracle.c (reference src/pairsnp.hpp is "
-                                              "unbuildable here: Boost absent), cross-checked against oracle.brute_pairsnp",
+    jdump("pairsnp_unpinned.json", {"status": "formerly PARITY UNPINNED, now pinned: produced by oracle/tracs_oracle.c, and asserted by the generator "
+                                              "to equal the reference's own src/pairsnp.hpp compiled in place over oracle/boost_standin "
+                                              "(oracle/_ref/_tracs_ref_pairsnp, both builds) and oracle.brute_pairsnp",
                                     "cases": cases})
+
+# ---------------------------------------------------------------------------------------
+# The reference's own pair loop and recombination filter (oracle/_ref/_tracs_ref_pairsnp: src/pairsnp.hpp compiled in place over
+# oracle/boost_standin), recorded with its inputs: tests/golden/pairsnp_ref_golden.npz (layout: tests/pairsnp_ref_cases.py).
+_SUBST = np.zeros(256, np.uint8)
+for _a, _b in zip(b"ACGTacgt", b"CGTAcgta"):
+    _SUBST[_a] = _b
+
+
+def _plant(seqs, samples, a, b, share, seed):
+    """an import: the same substitutions on `share` of the sites [a, b) in every listed sample (N and partial codes stay)"""
+    hit = a + np.nonzero(np.random.default_rng(seed).random(b - a) < share)[0]
+    for s in samples:
+        row = seqs[s, hit]
+        seqs[s, hit] = np.where(_SUBST[row] != 0, _SUBST[row], row)
+
+
+def _pairsnp_ref_alignments():
+    alns = {}
+    with open(os.path.join(HERE, "pairsnp_unpinned.json")) as fh:
+        unp = json.load(fh)["cases"]
+    for name in ("iupac_small", "tail_129", "consensus_300"):
+        alns[name] = np.array([np.frombuffer(r.encode("ascii"), np.uint8) for r in unp[name + "/all"]["seqs"]])
+    # every printable byte but the three kseq reads as the start of a record or of a quality line, against each base: the switch's
+    # default branch and toupper
+    by = np.array([b for b in range(33, 127) if b not in b">+@"], np.uint8)
+    rng = np.random.default_rng(11)
+    rows = [np.tile(by, 4), np.repeat(np.frombuffer(b"ACGT", np.uint8), len(by)), np.tile(by[::-1], 4), np.tile(np.roll(by, 7), 4),
+            np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 4 * len(by))]]
+    swap = rows[0].copy()
+    up, lo = (swap >= 65) & (swap <= 90), (swap >= 97) & (swap <= 122)
+    swap[up] += 32
+    swap[lo] -= 32
+    alns["bytes"] = np.array(rows + [swap])
+    for L in (1, 63, 64, 65, 127, 128, 129):
+        alns["len_%d" % L] = synth.alignment(9, L, seed=100 + L, mu_lineage=0.1, mu_sample=0.1, n_lineages=2, p_n=0.05, p_partial=0.05,
+                                             p_lower=0.1, p_other=0.02)
+    alns["n70"] = synth.alignment(70, 4133, seed=70, mu_lineage=4e-3, mu_sample=2e-3, n_lineages=4, p_n=0.01, p_partial=0.003, p_lower=0.01)
+    a = synth.alignment(130, 1000, seed=130, mu_lineage=1e-2, mu_sample=4e-3, n_lineages=6, p_n=0.01, p_partial=0.004, p_lower=0.01,
+                        p_other=0.001)
+    a[77] = a[12]                                              # two identical samples: dist = 0 emits a pair
+    alns["n130"] = a
+    same = synth.alignment(1, 200, seed=5, p_n=0.05, p_partial=0.05, p_lower=0.1)
+    alns["identical"] = np.repeat(same, 5, axis=0)
+    alns["all_differ"] = np.array([np.full(130, b, np.uint8) for b in b"ACGTa"])            # 'a' = 'A': one pair at d = 0 among them
+    alln = synth.alignment(6, 100, seed=6, mu_sample=0.05, p_n=0.03)
+    alln[2] = ord("N")
+    alln[4] = np.frombuffer(b"n-?.*Xx", np.uint8)[np.arange(100) % 7]
+    alns["all_n"] = alln
+    return alns
+
+
+def _filter_alignment(kind, seed):
+    n, L = 8, 30000
+    seqs = synth.alignment(n, L, seed=seed, mu_lineage=3e-3, mu_sample=1e-3, n_lineages=2, p_n=0.005, p_partial=0.001, p_lower=0.005)
+    if kind == "dense_one":                                     # a dense stretch on one sample
+        _plant(seqs, [3], 12000, 12300, 0.4, seed)
+    elif kind == "lineage":                                     # the same stretch on every sample of one lineage
+        _plant(seqs, [1, 3, 5, 7], 5000, 5400, 0.3, seed)
+    else:                                                       # stretches that touch either end of the alignment
+        _plant(seqs, [2], L - 250, L, 0.5, seed)
+        _plant(seqs, [5], 0, 150, 0.6, seed + 1)
+    return seqs
+
+
+def _pair_windows(H, seqs, i, j):
+    """-> (sorted SNP sites of the pair, [(count, length)] of its windows with count > 1)"""
+    m = O._MASK[seqs]
+    pos = np.nonzero((m[i] & m[j]) == 0)[0].astype(np.int64)
+    L, d = seqs.shape[1], len(pos)
+    if d <= 1:
+        return pos, []
+    _, _, wh = H.window(L, d)
+    lo = np.searchsorted(pos, np.maximum(0, pos - wh), "left")
+    hi = np.searchsorted(pos, np.minimum(L, pos + wh + 1), "left")
+    count, length = hi - lo, pos[hi - 1] - pos[lo] + 1
+    return pos, sorted({(int(k), int(n)) for k, n in zip(count, length) if k > 1})
+
+
+def _hp_list_one(args):
+    """one position list of filter_hp_golden.json through both builds of the reference and the definition"""
+    import hp_filter as H
+    L, d, pos = args
+    a = O.ref_pairsnp_module().ref_filter_recomb_positions(L, pos.tolist())
+    b = O.ref_pairsnp_module(strict=True).ref_filter_recomb_positions(L, pos.tolist())
+    assert a == b, ("the two builds disagree", L, d)
+    kept, _, ill, margin = H.filter_positions(pos, L)
+    assert ill == 0 and margin > H.MARGIN, ("a window within the margin of its threshold", L, d, margin)
+    assert kept == a, ("reference != definition", L, d, a, kept)
+    return a, margin
+
+
+def pairsnp_ref():
+    import multiprocessing
+    sys.path.insert(0, os.path.dirname(HERE))
+    import hp_filter as H
+    import pairsnp_ref_cases as PC
+    RS = O.ref_pairsnp_module(strict=True)
+    assert O.ref_pairsnp_module() is not None and RS is not None, "oracle/_ref/_tracs_ref_pairsnp is not built (make -C oracle)"
+    alns = _pairsnp_ref_alignments()
+    arrays, cases, filter_cases = {}, [], []
+    plain = dict(n0=None, dist=PC.INT_MAX, filter=False, width=0, crlf=False, gz=False)
+
+    def record(case, into):
+        seqs = alns[case["aln"]]
+        with tempfile.TemporaryDirectory() as td:
+            out = _ref_pairsnp_both(PC.write_fastas(case, seqs, td), case["dist"], case["filter"])
+        assert out[3] == PC.names_of(seqs.shape[0])
+        for col, v in zip(PC.COLUMNS, (out[0], out[1], out[2], out[5], out[4])):
+            arrays["%s/%s" % (case["name"], col)] = np.asarray(v, np.int64)
+        into.append(case)
+        return out
+
+    for name in ("iupac_small", "tail_129", "consensus_300"):   # the alignments and modes of pairsnp_unpinned.json
+        n = alns[name].shape[0]
+        for mode, n0, dist in (("all", None, PC.INT_MAX), ("thr", None, 4), ("twofile", n // 3, PC.INT_MAX)):
+            record(dict(plain, name="%s/%s" % (name, mode), aln=name, n0=n0, dist=dist), cases)
+    for name in ["bytes"] + ["len_%d" % L for L in (1, 63, 64, 65, 127, 128, 129)] + ["n70", "identical", "all_differ", "all_n"]:
+        record(dict(plain, name=name + "/all", aln=name), cases)
+    full = record(dict(plain, name="n130/all", aln="n130"), cases)
+    D = int(np.percentile(np.asarray(full[2]), 5))             # the exact d of some pair, so that d <= dist and d < dist differ
+    assert D >= 2 and D in full[2] and 0 in full[2]
+    for tag, dist in (("dist_minus1", -1), ("dist_0", 0), ("dist_d", D), ("dist_d_minus1", D - 1)):
+        out = record(dict(plain, name="n130/" + tag, aln="n130", dist=dist), cases)
+        assert len(out[2]) == int((np.asarray(full[2]) <= dist).sum())
+    assert len(arrays["n130/dist_minus1/d"]) == 0 and len(arrays["n130/dist_0/d"]) >= 1
+    assert len(arrays["n130/dist_d/d"]) > len(arrays["n130/dist_d_minus1/d"]) > 0
+    for n0 in (1, 130 // 3, 129):
+        record(dict(plain, name="n130/n0_%d" % n0, aln="n130", n0=n0), cases)
+    record(dict(plain, name="n70/twofile_thr", aln="n70", n0=23, dist=int(np.median(arrays["n70/all/d"]))), cases)
+    # the FASTA reader in front of the pair loop: wrapped lines, CRLF, gzip, and all three in two files
+    record(dict(plain, name="tail_129/wrapped", aln="tail_129", width=60), cases)
+    record(dict(plain, name="tail_129/crlf", aln="tail_129", crlf=True), cases)
+    record(dict(plain, name="tail_129/gz", aln="tail_129", gz=True), cases)
+    record(dict(plain, name="consensus_300/wrapped_crlf_gz_twofile", aln="consensus_300", n0=7, width=70, crlf=True, gz=True), cases)
+    for a, b in (("tail_129/wrapped", "tail_129/all"), ("tail_129/crlf", "tail_129/all"), ("tail_129/gz", "tail_129/all")):
+        assert all(np.array_equal(arrays["%s/%s" % (a, c)], arrays["%s/%s" % (b, c)]) for c in PC.COLUMNS)
+    assert all(not arrays["%s/filt" % c["name"]].any() and len(arrays["%s/filt" % c["name"]]) == len(arrays["%s/d" % c["name"]])
+               for c in cases)                                   # filter = False: a zero for every emitted pair
+
+    # (b) planted imports through ref_pairsnp(filter = True); a seed with a window inside the margin is replaced, never tolerated
+    cells, smallest, rejected = set(), 1.0, []
+    for kind, first_seed in (("dense_one", 31), ("lineage", 41), ("end", 51)):
+        for seed in range(first_seed, first_seed + 10):
+            seqs = _filter_alignment(kind, seed)
+            worst, kept_all, mine = 1.0, [], set()
+            r, c, d, _ = O.brute_pairsnp(seqs)
+            for i, j in zip(r.tolist(), c.tolist()):
+                pos, win = _pair_windows(H, seqs, i, j)
+                kept, _, ill, margin = H.filter_positions(pos, seqs.shape[1])
+                worst = min(worst, margin if ill == 0 else 0.0)
+                kept_all.append(kept)
+                mine |= {(seqs.shape[1], len(pos), n, k) for k, n in win}
+            if worst > H.MARGIN:
+                break
+            rejected.append((kind, seed, worst))
+        else:
+            raise AssertionError("no seed without an ill cell: " + kind)
+        alns["filter_" + kind] = seqs
+        out = record(dict(plain, name="filter_%s/filtered" % kind, aln="filter_" + kind, filter=True, width=80), filter_cases)
+        assert out[4] == kept_all, ("reference != definition", kind)
+        assert (np.asarray(out[4]) < np.asarray(out[2])).any() and (np.asarray(out[4]) <= np.asarray(out[2])).all()
+        cells |= mine
+        smallest = min(smallest, worst)
+    off = record(dict(plain, name="filter_dense_one/unfiltered", aln="filter_dense_one", width=80), cases)
+    assert off[4] == [0] * len(off[2]) and off[2] == arrays["filter_dense_one/filtered/d"].tolist()
+    thr = record(dict(plain, name="filter_end/filtered_thr", aln="filter_end", filter=True,
+                      dist=int(np.median(arrays["filter_end/filtered/d"]))), filter_cases)
+    assert 0 < len(thr[2]) < len(arrays["filter_end/filtered/d"])
+
+    # (a) every position list of filter_hp_golden.json through ref_filter_recomb_positions
+    with open(os.path.join(HERE, "filter_hp_golden.json")) as fh:
+        hp_cases = json.load(fh)["cases"]
+    lists = PC.hp_lists(H, hp_cases)
+    order = sorted(range(len(lists)), key=lambda t: -lists[t][1])          # the reference's filter is quadratic in d: longest first
+    with multiprocessing.Pool(min(16, os.cpu_count() or 1)) as pool:
+        res = pool.map(_hp_list_one, [lists[t] for t in order], chunksize=1)
+    got = [None] * len(lists)
+    for t, r in zip(order, res):
+        got[t] = r
+    arrays["hp/ref"] = np.asarray([g[0] for g in got], np.int64).reshape(len(hp_cases), 3)
+    want = np.asarray([[c["expected"], c["probe"][1], c["probe"][2]] for c in hp_cases], np.int64)
+    assert np.array_equal(arrays["hp/ref"], want), "reference != the 50-digit fixture"
+    smallest = min([smallest] + [g[1] for g in got])
+
+    # the stand-in CDF on the cells above and on n*, n* - 1 of every hp row: values of the strict build, and their error
+    for c in hp_cases:
+        cells |= {(c["L"], c["d"], n - e, k) for k, n in enumerate(c["row"], start=2) if n is not None for e in (0, 1)}
+    cells = np.asarray(sorted(cells), np.int64)
+    value = np.asarray([RS.ref_cached_binomial_cdf(int(n), float(d) / int(L), int(k)) for L, d, n, k in cells], np.float64)
+    fast = O.ref_pairsnp_module()
+    ratio = 0.0
+    with H.mp.workdps(H.DPS):
+        for (L, d, n, k), v in zip(cells.tolist(), value.tolist()):
+            p, thr_, _ = H.window(L, d)
+            for x in (v, fast.ref_cached_binomial_cdf(n, p, k)):
+                ratio = max(ratio, float(abs(H.mpf(1.0 - x) - H.tail(n, k, p)) / H.mpf(thr_)))
+    assert ratio <= H.MARGIN, ("the stand-in CDF misses the bound", ratio)
+    arrays["cdf/cells"], arrays["cdf/value"] = cells, value
+    for key, a in alns.items():
+        arrays["aln/" + key] = a
+    meta = {"about": "inputs, and what the reference's own src/pairsnp.hpp returned for them (oracle/_ref/_tracs_ref_pairsnp over "
+                     "oracle/boost_standin; both builds equal); layout: tests/pairsnp_ref_cases.py",
+            "cases": cases, "filter_cases": filter_cases, "hp_lists": len(lists), "margin": H.MARGIN, "digits": H.DPS, "dist_d": D,
+            "measured": {"ill_cells": 0, "min_relative_margin": float("%.3g" % smallest), "cdf_cells": int(len(cells)),
+                         "standin_max_error_over_threshold": float("%.3g" % ratio),
+                         "rejected_seeds": [[k, s_, float("%.3g" % w)] for k, s_, w in rejected]}}
+    PC.save(PC.FIXTURE, meta, arrays)
+    print("wrote pairsnp_ref_golden.npz", os.path.getsize(PC.FIXTURE), "bytes;", len(cases), "+", len(filter_cases), "cases;",
+          json.dumps(meta["measured"]))
 
 
 def python_reference():
     """Golden outputs of the reference's Python drivers (imported from /root/reference)."""
     stub = types.ModuleType("TRACS")
-    stub.pairsnp = O.pairsnp
+    ref_pairsnp = O.ref_pairsnp_module().ref_pairsnp            # the reference's own pairsnp (oracle/_ref), no longer the oracle's
+    stub.pairsnp = lambda fasta, n_threads, dist, filter: ref_pairsnp(fasta, 1, dist, filter)   # under the binding's argument names
     stub.trans_dist = R.ref_trans_dist
     stub.calculate_posteriors = R.ref_calculate_posteriors
     stub.lprob_k_given_N = R.ref_lprob_k_given_N
@@ -271,7 +500,7 @@ def python_reference():
         out["distance"] = {"seqs": [r.tobytes().decode() for r in seqs], "names": names, "dates": iso,
                            "runs": {k: {"argv": [a.replace(td, "TMP") for a in v], "csv": csvs[k]} for k, v in runs.items()}}
         # calculate_trans_prob (dates -> delta bits)
-        rr, cc, dd, nm, _, _ = O.pairsnp([msa], 1, 2147483647, False)
+        rr, cc, dd, nm, _, _ = stub.pairsnp([msa], 1, 2147483647, False)
         dates = {n: (i, __import__("datetime").date.fromisoformat(i)) for n, i in zip(names, iso)}
         p0, ek, td_ = ref_tc.calculate_trans_prob([rr, cc, dd], sample_dates=dates, K=100, lamb=5.3, beta=6.0,
                                                   samplenames=nm, log=False, precision=0.01)
@@ -545,6 +774,15 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["large-n"]:              # only the fixture added in round 2
         transcluster_large_n()
         sys.exit(0)
+    if sys.argv[1:] == ["pairsnp-ref"]:          # only the fixture of tests/test_pairsnp_ref.py / tests/test_gpu_pairsnp_ref.py
+        pairsnp_ref()
+        sys.exit(0)
+    if sys.argv[1:] == ["python-reference"]:     # only the Python drivers' golden
+        python_reference()
+        sys.exit(0)
+    if sys.argv[1:] == ["pairsnp-unpinned"]:
+        pairsnp_unpinned()
+        sys.exit(0)
     if sys.argv[1:] == ["oracle-vs-ref"]:        # only the fixture of tests/test_oracle_vs_ref.py
         oracle_vs_ref()
         sys.exit(0)
@@ -553,4 +791,5 @@ if __name__ == "__main__":
     posteriors()
     kseq()
     pairsnp_unpinned()
+    pairsnp_ref()
     python_reference()
