@@ -539,8 +539,6 @@ __global__ __launch_bounds__(64) void edge_fill_f64_kernel(const double *__restr
     }
 }
 
-
-
 // tile schedule: upper-trapezoid tiles of the block, supertile-major so that consecutive
 // entries (= tiles resident together on one XCD after xcd_remap) share row/column panels.
 static void build_tiles(size_t n, size_t row_begin, size_t row_end, size_t col_begin, int ti, int tj,
@@ -904,127 +902,84 @@ static inline void pair_mark(int k, hipStream_t stream)
     if (k == 4) g_pair_calls++;
 }
 
-static int pairsnp_dense_impl(const tracs_alignment *a_, size_t row_begin, size_t row_end, size_t col_begin, uint32_t *dist,
-                              uint32_t *ncomp, size_t ld, void *stream_, unsigned thr);
+static int env_flag(const char *name) { const char *e = std::getenv(name); return e ? std::atoi(e) : -1; }
 
-int tracs_pairsnp_dense(const tracs_alignment *a_, size_t row_begin, size_t row_end, size_t col_begin, uint32_t *dist,
-                        uint32_t *ncomp, size_t ld, void *stream_)
-{
-    return pairsnp_dense_impl(a_, row_begin, row_end, col_begin, dist, ncomp, ld, stream_, 0xFFFFFFFFu);
+// ---- host driver of the dense call --------------------------------------------------------------------------
+// Its switches.  mfma_off .. thr_one_pass are read once per process, when a call first gets there; ksplit and thr_prefix by every call
+namespace dense_switch {
+static bool mfma_off()      { static const bool v = env_flag("TRACS_MFMA") == 0 || std::getenv("TRACS_TILE_VARIANT") != nullptr; return v; }
+static bool force_general() { static const bool v = std::getenv("TRACS_FORCE_GENERAL") != nullptr; return v; }
+static int general_mfma()   { static const int v = env_flag("TRACS_GENERAL_MFMA"); return v; }   // 1: always, 0: never the matrix cores for general alignments
+static bool thr_one_pass()  { static const bool v = std::getenv("TRACS_THR_ONE_PASS") != nullptr; return v; }
+static int ksplit()         { const char *e = std::getenv("TRACS_KSPLIT"); return e ? std::atoi(e) : 0; }
+static int thr_prefix()     { const char *e = std::getenv("TRACS_THR_PREFIX"); return e ? std::atoi(e) : 0; }
 }
 
-int tracs_pairsnp_dense_thr(const tracs_alignment *a_, size_t row_begin, size_t row_end, size_t col_begin, uint32_t *dist,
-                            uint32_t *ncomp, size_t ld, int32_t dist_threshold, void *stream_)
+// ---- once per pack: encoding and site classes, decided together from the general planes (site_classes.hip) --------------------
+// Classes in use: the pair kernels read `vplanes` (consensus form when no sample carries a partial IUPAC code), nothing else
+// is derived.  Classes not in use: the consensus planes (3 of 5: a second, smaller copy) are derived when the alignment has
+// a consensus form and there is room for them; otherwise the general planes are read as they are.
+static int decide_pack(tracs_alignment *a, hipStream_t stream, bool mfma_off)
 {
-    // a negative threshold emits nothing; any d > threshold may come back as 0xFFFFFFFF
-    const unsigned thr = dist_threshold < 0 ? 0u : (unsigned)dist_threshold;
-    return pairsnp_dense_impl(a_, row_begin, row_end, col_begin, dist, ncomp, ld, stream_, dist_threshold == 2147483647 ? 0xFFFFFFFFu : thr);
-}
-
-static int env_flag(const char *name)
-{
-    const char *e = std::getenv(name);
-    return e ? std::atoi(e) : -1;
-}
-
-static int pairsnp_dense_impl(const tracs_alignment *a_, size_t row_begin, size_t row_end, size_t col_begin, uint32_t *dist,
-                              uint32_t *ncomp, size_t ld, void *stream_, unsigned thr)
-{
-    tracs_alignment *a = const_cast<tracs_alignment *>(a_);
-    if (!a || !dist) { set_error("tracs_pairsnp_dense: NULL argument"); return TRACS_E_ARG; }
-    if (row_end > a->n) row_end = a->n;
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    // an event armed by tracs_pairsnp_notify_distances belongs to THIS call: recorded when the distances are final, or -- on every
-    // other way out, errors included -- recorded at the exit, never left armed for an unrelated later call
-    struct DistEventGuard { hipStream_t s; ~DistEventGuard() { dist_final(s); } } dist_guard{stream};
-    if (row_begin >= row_end || a->n < 2) return TRACS_OK;
-    if (ld < a->n) { set_error("tracs_pairsnp_dense: ld < n"); return TRACS_E_ARG; }
-    DeviceCall guard(stream);
-    if (a->n_row_hint) {
-        bool inside = false;
-        for (int k = 0; k < a->n_row_hint; k++) inside = inside || (row_begin >= a->row_hint[2 * k] && row_end <= std::min(a->n, a->row_hint[2 * k + 1]));
-        if (!inside) { set_error("tracs_pairsnp_dense: rows outside the ranges given to tracs_alignment_hint_rows"); return TRACS_E_ARG; }
-    }
-
-    if (a->L == 0) {   // every pair: d = 0, nn = 0
-        dim3 grid(64, (unsigned)std::min<size_t>(row_end - row_begin, 65535));
-        hipLaunchKernelGGL(init_cells_kernel, grid, dim3(256), 0, stream, dist, ncomp, ld, (unsigned)a->n,
-                           (unsigned)row_begin, (unsigned)row_end, (unsigned)col_begin, 0u);
-        dist_final(stream);
-        TRACS_HIP_CHECK(hipGetLastError());
-        return TRACS_OK;
-    }
-
-    // ---- kernel family: matrix cores unless switched off (TRACS_MFMA=0, or an explicit TRACS_TILE_VARIANT) ----------------------
-    // (the matrix-core kernels keep 32-bit element offsets inside a stage: n_pad < 2^28 samples)
-    static const bool mfma_env_off = env_flag("TRACS_MFMA") == 0 || std::getenv("TRACS_TILE_VARIANT") != nullptr;
-    const bool mfma_off = mfma_env_off || a->n_pad >= (1ull << 28);
-
-    // ---- once per pack: encoding and site classes, decided together from the general planes (site_classes.hip) -----------------
-    // Classes in use: the pair kernels read `vplanes` (consensus form when no sample carries a partial IUPAC code), nothing else
-    // is derived.  Classes not in use: the consensus planes (3 of 5: a second, smaller copy) are derived when the alignment has
-    // a consensus form and there is room for them; otherwise the general planes are read as they are.
-    if (a->dirty) {
-        a->enc = 0;
-        general_sparse_free(a);
-        site_classes_free(a);
-        pack_stage_begin(stream);
-        int partial = -1;
-        if (!mfma_off) {
-            const int rc = site_classes_decide(a, stream, &partial);
-            if (rc) { pack_stage_end(); return rc; }
+    a->enc = 0;
+    general_sparse_free(a); site_classes_free(a);
+    pack_stage_begin(stream);
+    struct StageClock { ~StageClock() { pack_stage_end(); } } clock;      // closed on every way out, the error returns included
+    int partial = -1;
+    if (!mfma_off) { if (const int rc = site_classes_decide(a, stream, &partial)) return rc; }
+    const bool force_general = dense_switch::force_general();
+    if (a->classes_state == 1) {
+        a->enc = a->classes_cons ? 1 : 0;
+        if (a->cplanes) { TRACS_HIP_CHECK(hipFree(a->cplanes)); a->cplanes = nullptr; }
+    } else if (!force_general && partial != 1) {
+        const size_t cbytes = plane_bytes(a, 3);
+        if (!a->cplanes) {
+            // no room for the second copy (very large alignments): stay on the general encoding
+            if (hipMalloc(reinterpret_cast<void **>(&a->cplanes), cbytes) == hipSuccess) TRACS_HIP_CHECK(hipMemsetAsync(a->cplanes, 0, cbytes, stream));
+            else { a->cplanes = nullptr; (void)hipGetLastError(); }
         }
-        static const bool force_general = std::getenv("TRACS_FORCE_GENERAL") != nullptr;
-        if (a->classes_state == 1) {
-            a->enc = a->classes_cons ? 1 : 0;
-            if (a->cplanes) { TRACS_HIP_CHECK(hipFree(a->cplanes)); a->cplanes = nullptr; }
-        } else if (!force_general && partial != 1) {
-            const size_t cbytes = plane_bytes(a, 3);
-            bool have = a->cplanes != nullptr;
-            if (!have) {
-                // no room for the second copy (very large alignments): stay on the general encoding
-                if (hipMalloc(reinterpret_cast<void **>(&a->cplanes), cbytes) == hipSuccess) {
-                    have = true;
-                    TRACS_HIP_CHECK(hipMemsetAsync(a->cplanes, 0, cbytes, stream));
-                } else {
-                    a->cplanes = nullptr;
-                    (void)hipGetLastError();
-                }
-            }
-            if (have) {
-                if (!a->d_flag) TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&a->d_flag), 64));
-                TRACS_HIP_CHECK(hipMemsetAsync(a->d_flag, 0, 4, stream));
-                hipLaunchKernelGGL(derive_consensus_kernel, dim3(256 * 16), dim3(256), 0, stream, a->planes, a->cplanes, a->n_pad,
-                                   a->groups, a->d_flag);
-                unsigned flag = 1;
-                TRACS_HIP_CHECK(hipMemcpyAsync(&flag, a->d_flag, 4, hipMemcpyDeviceToHost, stream));
-                TRACS_HIP_CHECK(hipStreamSynchronize(stream));
-                if (flag == 0) a->enc = 1;
-                else { TRACS_HIP_CHECK(hipFree(a->cplanes)); a->cplanes = nullptr; }
-            }
-            pack_stage_mark("consensus planes", stream);
-        } else if (a->cplanes) {
-            TRACS_HIP_CHECK(hipFree(a->cplanes));
-            a->cplanes = nullptr;
+        if (a->cplanes) {
+            if (!a->d_flag) TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&a->d_flag), 64));
+            TRACS_HIP_CHECK(hipMemsetAsync(a->d_flag, 0, 4, stream));
+            hipLaunchKernelGGL(derive_consensus_kernel, dim3(256 * 16), dim3(256), 0, stream, a->planes, a->cplanes, a->n_pad,
+                               a->groups, a->d_flag);
+            unsigned flag = 1;
+            TRACS_HIP_CHECK(hipMemcpyAsync(&flag, a->d_flag, 4, hipMemcpyDeviceToHost, stream));
+            TRACS_HIP_CHECK(hipStreamSynchronize(stream));
+            if (flag == 0) a->enc = 1;
+            else { TRACS_HIP_CHECK(hipFree(a->cplanes)); a->cplanes = nullptr; }
         }
-        pack_stage_end();
-        a->dirty = false;
-    }
-    const bool cons = a->enc == 1;
-    const TileVariant &V = current_variant(cons);
-    const double cells = (double)(row_end - row_begin) * (double)a->n;      // upper bound of the cells of this call
+        pack_stage_mark("consensus planes", stream);
+    } else if (a->cplanes) { TRACS_HIP_CHECK(hipFree(a->cplanes)); a->cplanes = nullptr; }
+    a->dirty = false;                                                      // only on success: a failed decision is made again
+    return TRACS_OK;
+}
 
-    bool mfma = cons && !mfma_off;
-    bool mfma_general = false;
-    static const int gen_force = env_flag("TRACS_GENERAL_MFMA");          // 1: always, 0: never the matrix cores for general alignments
-    for (int attempt = 0; attempt < 2 && !cons && !mfma_off && pair_L(a) < (1ull << 27) && pair_L(a) > 0; attempt++) {
+// ---- which kernel, which tile, how many groups: what the rest of a call reads ---------------------------------------------------
+struct DenseRoute {
+    bool cons, mfma, mfma_general, no_dense_site;
+    bool classes, gram;                // site classes in use; nw_gram: the counting passes also add to the distances (count_pass)
+    int groups, shape_id;              // groups the pair kernel reads; matrix-core shape
+    int gc, ti, tj, wg_per_cu;         // groups per LDS stage, workgroup tile, resident workgroups per CU of the pair kernel
+    int max_gps;                       // groups per range at most: the matrix-core kernels' fp32 partial sums stay below 2^24 (choose_route)
+    unsigned *ncomp_pair;              // null with the in-place counting source: the counting pass alone makes nn, the others write d only
+    int kernel() const { return (mfma_general || no_dense_site) ? 2 : mfma ? 1 : 0; }
+};
+
+// the VALU kernel reads the whole alignment: the site classes (and the lists built on them) go when it is chosen
+static void drop_classes(tracs_alignment *a) { general_sparse_free(a); site_classes_free(a); a->classes_state = -1; }
+static int choose_route(tracs_alignment *a, hipStream_t stream, double cells /* of this call, upper bound */, bool mfma_off, unsigned *ncomp, DenseRoute *out)
+{
+    DenseRoute R{};
+    R.cons = a->enc == 1; R.mfma = R.cons && !mfma_off;
+    const int gen_force = dense_switch::general_mfma();
+    for (int attempt = 0; attempt < 2 && !R.cons && !mfma_off && pair_L(a) < (1ull << 27) && pair_L(a) > 0; attempt++) {
         // general alignment: one-hot Gram on the matrix cores + the sparse partial-code terms, when the side lists exist (or
         // can be built) and the sparse work is small beside what the VALU kernel would cost.  Thresholded passes too: the
         // kernel's value bounds the distance from below, so tiles it declares dead are dead (pairsnp_mfma.hip)
         int ok = 0;
         double updates = 0.0;
-        const int rc = general_sparse_get(a, stream, &ok, &updates);
-        if (rc) return rc;
+        if (const int rc = general_sparse_get(a, stream, &ok, &updates)) return rc;
         if (ok) {
             const double all_cells = 0.5 * (double)a->n * (double)a->n;
             const double frac = std::min(1.0, cells / std::max(1.0, all_cells));
@@ -1032,106 +987,171 @@ static int pairsnp_dense_impl(const tracs_alignment *a_, size_t row_begin, size_
             const double count_sites = a->classes_state != 1 ? 0.0 : (double)(a->count_in_place ? a->L : a->L_inv) + (a->nw_gram ? (double)a->L : 0.0);
             const double t_mfma = cells * ((double)pair_L(a) * 10.0 + count_sites * 2.0) / 5.4e15
                                   + updates * frac / 3.0e11;                  // measured: 5.4 PFLOP/s, 4 x 10^11 list entries/s
-            mfma_general = gen_force == 1 || (gen_force != 0 && t_mfma < t_valu);
+            R.mfma_general = gen_force == 1 || (gen_force != 0 && t_mfma < t_valu);
         }
-        if (mfma_general || a->classes_state != 1) break;
-        // the VALU kernel reads the whole alignment: drop the classes (and the lists built on them) and look again
-        general_sparse_free(a);
-        site_classes_free(a);
-        a->classes_state = -1;
+        if (R.mfma_general || a->classes_state != 1) break;
+        drop_classes(a);                                     // ... and look again
     }
     // (a general alignment whose variable sites all went to the minority lists has no dense site left: nothing for the pair
     // kernel to read, the lists and the counting pass do everything)
-    const bool no_dense_site = !cons && !mfma_off && gen_force != 0 && a->classes_state == 1 && pair_L(a) == 0;
-    if (!cons && !mfma_general && !no_dense_site && a->classes_state == 1) { general_sparse_free(a); site_classes_free(a); a->classes_state = -1; }
-    mfma = mfma || mfma_general || no_dense_site;
-    const bool classes = a->classes_state == 1;
-    const int groups = (int)pair_groups(a);
-    const int shape_id = mfma_shape_current(mfma_general);
-    const MfmaShape &S = mfma_shape(shape_id);
-    const int kGC = mfma ? (mfma_general ? S.gc_gen : S.gc_cons) : V.gc;
-    const int kTI = mfma ? S.ti : V.ti, kTJ = mfma ? S.tj : V.tj;
-    a->last_kernel = (mfma_general || no_dense_site) ? 2 : mfma ? 1 : 0;
+    R.no_dense_site = !R.cons && !mfma_off && gen_force != 0 && a->classes_state == 1 && pair_L(a) == 0;
+    if (!R.cons && !R.mfma_general && !R.no_dense_site && a->classes_state == 1) drop_classes(a);
+    R.mfma = R.mfma || R.mfma_general || R.no_dense_site;
+    R.classes = a->classes_state == 1;
+    R.gram = R.classes && a->nw_gram && !a->nw_rows;
+    R.groups = (int)pair_groups(a);
+    R.shape_id = mfma_shape_current(R.mfma_general);
+    const MfmaShape &S = mfma_shape(R.shape_id);
+    const TileVariant &V = current_variant(R.cons);
+    R.gc = R.mfma ? (R.mfma_general ? S.gc_gen : S.gc_cons) : V.gc;
+    R.ti = R.mfma ? S.ti : V.ti, R.tj = R.mfma ? S.tj : V.tj;
+    R.wg_per_cu = R.mfma ? S.wg_per_cu : V.wg_per_cu[R.cons ? 1 : 0];
+    // fp32 accumulators of the matrix-core kernels are exact while every partial sum stays below 2^24:
+    // consensus |S| <= 3 sites -> 2^22 sites per range; general G <= 4 sites -> 2^21
+    R.max_gps = R.mfma ? (1 << (R.mfma_general ? 21 : 22)) / SITES_PER_GROUP : R.groups;
+    R.ncomp_pair = (R.classes && a->count_in_place) ? nullptr : ncomp;
+    *out = R;
+    return TRACS_OK;
+}
 
-    // ---- (re)build the cached tile schedule ------------------------------------------------------------------------------
-    auto ensure_tiles = [&](int ti, int tj, tracs_alignment::TileCache **out) -> int {
+// ---- launch arithmetic ------------------------------------------------------------------------------------------------------------
+static int cu_count()                                      // looked up once per process
+{
+    static const int cus = [] { hipDeviceProp_t pr; int dv = 0; (void)hipGetDevice(&dv); return (hipGetDeviceProperties(&pr, dv) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }();
+    return cus;
+}
+// Split the group range over workgroups (integer atomics, still exact) when that fills the chip better:
+// too few tiles (config 2), or a ragged last round of resident workgroups (tail effect).  slots: resident workgroups of the chip.
+static int pick_split(size_t n_tiles, int range, int gc, double slots)
+{
+    int pick = 1; double best = -1.0;
+    const int max_split = std::max(1, range / (8 * gc));
+    for (int k = 1; k <= std::min(max_split, 64); k++) {
+        const double wgs = (double)n_tiles * k;
+        const double rounds = std::ceil(wgs / slots);
+        const double eff = wgs / (rounds * slots) - 0.002 * (k - 1);     // small bias towards fewer splits
+        if (eff > best + 1e-9) { best = eff; pick = k; }
+        if (rounds >= 40) break;                                         // tail < 2.5 % from here on
+    }
+    if (const int v = dense_switch::ksplit(); v >= 1 && v <= max_split) pick = v;
+    return pick;
+}
+// k workgroups over `range` groups, stage aligned: the ranges there are then, *gps groups each
+static int stage_split(int range, int k, int gc, int *gps)
+{
+    *gps = ((range + k - 1) / k + gc - 1) / gc * gc;
+    return (range + *gps - 1) / *gps;
+}
+// two-pass thresholded run: groups of the prefix pass (1/8 of them, whole stages), ...
+static int thr_prefix_groups(int groups, int gc, int max_gps)
+{
+    const int v = dense_switch::thr_prefix() / gc * gc;
+    return (v >= gc && v < groups) ? v : std::min(max_gps / gc * gc, std::max(8 * gc, groups / 8 / gc * gc));
+}
+// ... and ranges of the remainder pass over the `rest`: ~4 rounds of the chip, never more than 32 ranges (each costs one atomic per cell)
+static int thr_remainder_split(int rest, int gc, int max_gps, double slots, unsigned n_live, int *gps)
+{
+    const int want = (int)std::ceil(4.0 * slots / (double)n_live);
+    return stage_split(rest, std::max({1, std::min({32, want, rest / (16 * gc)}), (rest + max_gps - 1) / max_gps}), gc, gps);
+}
+
+// ---- one dense call: the region, where its results go, the route, and what has been zeroed ------------------------------------
+struct DenseCall {
+    tracs_alignment *a; size_t row_begin, row_end, col_begin;
+    unsigned *dist, *ncomp; size_t ld; hipStream_t stream; unsigned thr;
+    DenseRoute R;
+    bool nn_zeroed = false;                                // this call has set the region's nn cells to 0
+    double slots(int wg_per_cu) const { return (double)wg_per_cu * cu_count(); }
+    // the cached tile schedule of the region in ti x tj tiles, (re)built when none of the four has it
+    int tiles(int ti, int tj, tracs_alignment::TileCache **out)
+    {
         for (auto &c : a->tile_cache)
             if (c.rb == row_begin && c.re == row_end && c.cb == col_begin && c.ti == ti && c.tj == tj) { *out = &c; return TRACS_OK; }
         tracs_alignment::TileCache &c = a->tile_cache[a->tile_next];
         a->tile_next = (a->tile_next + 1) % 4;
         c.rb = (size_t)-1;                                   // not valid until filled
-        std::vector<int2> tiles;
-        build_tiles(a->n, row_begin, row_end, col_begin, ti, tj, tiles);
-        if (tiles.size() > c.cap) {
+        std::vector<int2> tl;
+        build_tiles(a->n, row_begin, row_end, col_begin, ti, tj, tl);
+        if (tl.size() > c.cap) {
             if (c.d) TRACS_HIP_CHECK(hipFree(c.d));
-            c.d = nullptr;
-            c.cap = tiles.size() * 2 + 64;
+            c.d = nullptr; c.cap = tl.size() * 2 + 64;
             TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&c.d), c.cap * sizeof(int2)));
         }
-        if (!tiles.empty()) {
-            TRACS_HIP_CHECK(hipMemcpyAsync(c.d, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice, stream));
-            TRACS_HIP_CHECK(hipStreamSynchronize(stream));   // `tiles` is a stack vector
+        if (!tl.empty()) {
+            TRACS_HIP_CHECK(hipMemcpyAsync(c.d, tl.data(), tl.size() * sizeof(int2), hipMemcpyHostToDevice, stream));
+            TRACS_HIP_CHECK(hipStreamSynchronize(stream));   // `tl` is a stack vector
         }
-        c.n = tiles.size();
-        c.rb = row_begin; c.re = row_end; c.cb = col_begin; c.ti = ti; c.tj = tj;
-        *out = &c;
-        return TRACS_OK;
-    };
-    tracs_alignment::TileCache *main_tiles = nullptr;
-    { const int rc = ensure_tiles(kTI, kTJ, &main_tiles); if (rc) return rc; }
-    const tracs_alignment::TileCache &T = *main_tiles;
-    if (T.n == 0) { dist_final(stream); return TRACS_OK; }
-
-    // Split the group range over workgroups (integer atomics, still exact) when that fills the chip better:
-    // too few tiles (config 2), or a ragged last round of resident workgroups (tail effect).
-    double slots = 512.0;
-    {
-        static int cus = 0;
-        if (!cus) { hipDeviceProp_t pr; int dv = 0; (void)hipGetDevice(&dv); cus = (hipGetDeviceProperties(&pr, dv) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256; }
-        slots = (double)(mfma ? S.wg_per_cu : V.wg_per_cu[cons ? 1 : 0]) * cus;
+        c.n = tl.size(); c.rb = row_begin; c.re = row_end; c.cb = col_begin; c.ti = ti; c.tj = tj;
+        *out = &c; return TRACS_OK;
     }
-    auto pick_split = [&](size_t n_tiles, int range, int gc) {
-        int pick = 1;
-        const int max_split = std::max(1, range / (8 * gc));
-        double best = -1.0;
-        for (int k = 1; k <= std::min(max_split, 64); k++) {
-            const double wgs = (double)n_tiles * k;
-            const double rounds = std::ceil(wgs / slots);
-            const double eff = wgs / (rounds * slots) - 0.002 * (k - 1);     // small bias towards fewer splits
-            if (eff > best + 1e-9) { best = eff; pick = k; }
-            if (rounds >= 40) break;                                         // tail < 2.5 % from here on
-        }
-        if (const char *e = std::getenv("TRACS_KSPLIT")) { const int v = std::atoi(e); if (v >= 1 && v <= max_split) pick = v; }
-        return pick;
-    };
-    int ksplit = pick_split(T.n, groups, kGC);
-    auto stage_split = [&](int range, int k, int &gps_out) {       // k workgroups over `range` groups, stage aligned
-        int g = (range + k - 1) / k;
-        g = (g + kGC - 1) / kGC * kGC;
-        gps_out = g;
-        return (range + g - 1) / g;
-    };
-    // fp32 accumulators of the matrix-core kernels are exact while every partial sum stays below 2^24:
-    // consensus |S| <= 3 sites -> 2^22 sites per range; general G <= 4 sites -> 2^21
-    const int max_gps = mfma ? (1 << (mfma_general ? 21 : 22)) / SITES_PER_GROUP : groups;
-    // in-place counting source: the counting pass alone makes nn, the pair kernels (and the partial-code correction) write d only
-    unsigned *const ncomp_pair = (classes && a->count_in_place) ? nullptr : ncomp;
-    bool nn_zeroed = false;                                // this call has set the region's nn cells to 0
-    auto launch = [&](const int2 *tl, unsigned nwg, int ntl, int g_end, int gps, int k, unsigned t, TilePhase ph) -> int {
-        if (mfma) {
+    // every cell j > i of the region: d = 0 (when given), nn = value (when given)
+    void zero_cells(unsigned *d, unsigned *nc, unsigned value)
+    {
+        dim3 grid(64, (unsigned)std::min<size_t>(row_end - row_begin, 65535));
+        hipLaunchKernelGGL(init_cells_kernel, grid, dim3(256), 0, stream, d, nc, ld, (unsigned)a->n, (unsigned)row_begin, (unsigned)row_end, (unsigned)col_begin, value);
+    }
+    // the pair kernel of the route: groups up to g_end of `ntl` tiles, k ranges of gps groups per tile
+    int launch_pairs(const int2 *tl, unsigned nwg, int ntl, int g_end, int gps, int k, TilePhase ph)
+    {
+        if (R.mfma) {
             MfmaArgs A;
-            A.P = pair_planes(a, !mfma_general);
+            A.P = pair_planes(a, !R.mfma_general);
             A.n_pad = a->n_pad; A.groups = g_end; A.tiles = tl; A.n_tiles = ntl; A.gps = gps; A.ksplit = k;
             A.L = (unsigned)pair_L(a); A.n = (unsigned)a->n; A.row_end = (unsigned)row_end; A.col_begin = (unsigned)col_begin;
-            A.dist = dist; A.ncomp = ncomp_pair; A.ld = ld; A.thr = t; A.ph = ph;
-            A.keep_bound = (classes && a->lists) ? 1 : 0;      // terms are added to the cells afterwards: no flag values
-            return launch_pairsnp_mfma(shape_id, mfma_general, nwg, stream, A);
+            A.dist = dist; A.ncomp = R.ncomp_pair; A.ld = ld; A.thr = thr; A.ph = ph;
+            A.keep_bound = (R.classes && a->lists) ? 1 : 0;      // terms are added to the cells afterwards: no flag values
+            return launch_pairsnp_mfma(R.shape_id, R.mfma_general, nwg, stream, A);
         }
-        V.launch[cons ? 1 : 0](ncomp != nullptr, nwg, stream, cons ? a->cplanes : a->planes, a->n_pad, g_end, tl, ntl, gps, k,
-                               (unsigned)a->L, (unsigned)a->n, (unsigned)row_end, (unsigned)col_begin, dist, ncomp, ld, t, ph);
+        current_variant(R.cons).launch[R.cons ? 1 : 0](ncomp != nullptr, nwg, stream, R.cons ? a->cplanes : a->planes, a->n_pad, g_end, tl, ntl, gps, k,
+                                                       (unsigned)a->L, (unsigned)a->n, (unsigned)row_end, (unsigned)col_begin, dist, ncomp, ld, thr, ph);
         return TRACS_OK;
-    };
+    }
 
+    // ---- the three pair stages; each opens the call's event sequence --------------------------------------------------------
+    // no dense site at all: the distances come from the lists, the compared-sites counts from the counting pass
+    void pairs_none() { pair_mark(0, stream); zero_cells(dist, ncomp, 0u); nn_zeroed = true; }
+    // everything in one launch
+    int pairs_one_launch(const tracs_alignment::TileCache &T)
+    {
+        int gps = 0, ksplit = pick_split(T.n, R.groups, R.gc, slots(R.wg_per_cu));
+        if (R.mfma) ksplit = std::max(ksplit, (R.groups + R.max_gps - 1) / R.max_gps);
+        ksplit = stage_split(R.groups, ksplit, R.gc, &gps);
+        pair_mark(0, stream);
+        if (ksplit > 1) {                                  // the ranges add onto the cells
+            zero_cells(dist, ncomp, (R.cons || R.mfma) ? 0u : (unsigned)a->L);
+            nn_zeroed = R.cons || R.mfma;
+        }
+        return launch_pairs(T.d, (unsigned)(T.n * (size_t)ksplit), (int)T.n, R.groups, gps, ksplit, TilePhase{0, 0, nullptr});
+    }
+
+    // Thresholded run on a long alignment: two passes.  The prefix pass (1/8 of the groups, one workgroup per tile) leaves
+    // exact partial counts and a live flag per tile; the remainder pass visits the live tiles only, its range split so that the
+    // few surviving tiles still fill the chip.  Dead tiles cost 1/8 of a full pass or less (they also stop inside the prefix).
+    // *live_out, *n_live_out: the live tiles, all the counting pass has to complete.
+    int pairs_two_pass(const tracs_alignment::TileCache &T, const int2 **live_out, size_t *n_live_out)
+    {
+        const int prefix = thr_prefix_groups(R.groups, R.gc, R.max_gps);
+        unsigned char *live = nullptr; int2 *live_tiles = nullptr;
+        unsigned *n_live_d = nullptr, n_live = 0;
+        int rc;
+        if ((rc = tracs::workspace_get(tracs::WS_PS_LIVE, T.n, &live))) return rc;
+        if ((rc = tracs::workspace_get(tracs::WS_PS_LIVE_TILES, T.n, &live_tiles))) return rc;
+        if ((rc = tracs::workspace_get(tracs::WS_PS_N_LIVE, 16, &n_live_d))) return rc;
+        TRACS_HIP_CHECK(hipMemsetAsync(n_live_d, 0, 4, stream));
+        pair_mark(0, stream);
+        if ((rc = launch_pairs(T.d, (unsigned)T.n, (int)T.n, prefix, prefix, 1, TilePhase{1, 0, live}))) return rc;
+        hipLaunchKernelGGL(compact_live_kernel, dim3((unsigned)((T.n + 255) / 256)), dim3(256), 0, stream, T.d, live,
+                           (unsigned)T.n, live_tiles, n_live_d);
+        TRACS_HIP_CHECK(hipMemcpyAsync(&n_live, n_live_d, 4, hipMemcpyDeviceToHost, stream));
+        TRACS_HIP_CHECK(hipStreamSynchronize(stream));
+        if (n_live) {
+            int gps2 = 0;
+            const int k2 = thr_remainder_split(R.groups - prefix, R.gc, R.max_gps, slots(R.wg_per_cu), n_live, &gps2);
+            if ((rc = launch_pairs(live_tiles, (unsigned)(n_live * (size_t)k2), (int)n_live, R.groups, gps2, k2, TilePhase{2, prefix, nullptr}))) return rc;
+        }
+        *live_out = live_tiles; *n_live_out = n_live;
+        return TRACS_OK;
+    }
     // Site classes: the compared-sites counts of every site the pair kernel does not read.  Over those sites U (in place: over
     // every site, and the pair kernels wrote d only)   nn = |U| - c_i - c_j + NN,   NN = sum n_i n_j  (n = "is N here"):
     //   matrix cores  pairsnp_mfma_kernel<COUNT> over the N plane of the sites with many N samples (or of every site, in place),
@@ -1141,47 +1161,35 @@ static int pairsnp_dense_impl(const tracs_alignment *a_, size_t row_begin, size_
     //   neither       sites with one N sample or none only add their part of |U| - c_i - c_j.
     // nw_gram (site_classes.hip): the same pass over the stored N plane also ADDS n n^T to the distances, and a second one over the
     // U plane subtracts U U^T -- the minority sites' N x listed terms; both run whether or not the caller wants nn.
-    // (nw_rows: the same terms from the rows of the site-major N matrix inside the fix-up -- the passes below then count compared sites only)
-    const bool gram = classes && a->nw_gram && !a->nw_rows;
-    auto count_pass = [&](const int2 *tl, size_t ntl) -> int {
-        if (!classes || (!ncomp && !gram) || (a->L_un == 0 && a->L_full == 0 && !gram)) { pair_mark(3, stream); return TRACS_OK; }
+    int count_pass(const int2 *tl, size_t ntl)
+    {
+        const bool gram = R.gram;      // (not with nw_rows: the same terms inside the fix-up, the passes below then count compared sites only)
+        if (!R.classes || (!ncomp && !gram) || (a->L_un == 0 && a->L_full == 0 && !gram)) { pair_mark(3, stream); return TRACS_OK; }
         const bool in_place = a->count_in_place;
         const unsigned lu = (unsigned)(in_place ? a->L : a->L_full + a->L_un);
         bool terms_added = false;
         if (a->L_inv > 0 || gram) {
             // tl == nullptr: every tile of the region, in the counting pass's own workgroup tile (its own cached schedule);
             // otherwise the given tiles (the live ones of a thresholded run) in the pair kernel's geometry
-            CountShape C = count_shape_like(kTI, kTJ);
+            CountShape C = count_shape_like(R.ti, R.tj);
             if (tl && !C.fn) tl = nullptr;                     // no counting kernel with the pair kernel's tile: count every tile
             if (!tl) {
                 C = count_shape_current();
                 tracs_alignment::TileCache *ct = nullptr;
-                const int rc = ensure_tiles(C.ti, C.tj, &ct);
-                if (rc) return rc;
+                if (const int rc = tiles(C.ti, C.tj, &ct)) return rc;
                 tl = ct->d; ntl = ct->n;
             }
-            const int gi = (int)(in_place ? a->groups : a->groups_inv), gcc = C.gc;
-            const double keep_slots = slots;
-            slots = (double)C.wg_per_cu * (slots / (double)(mfma ? S.wg_per_cu : V.wg_per_cu[cons ? 1 : 0]));
-            int k = std::max(pick_split(std::max<size_t>(ntl, 1), gi, gcc), (gi + (1 << 16) - 1) >> 16);
-            slots = keep_slots;
-            int g = (gi + k - 1) / k;
-            g = (g + gcc - 1) / gcc * gcc;
-            k = (gi + g - 1) / g;
-            if (in_place && k > 1 && !nn_zeroed && ncomp) {
-                // several ranges add onto the cells: zero them first (nothing else has written nn) -- unless the call already has
-                dim3 grid(64, (unsigned)std::min<size_t>(row_end - row_begin, 65535));
-                hipLaunchKernelGGL(init_cells_kernel, grid, dim3(256), 0, stream, (unsigned *)nullptr, ncomp, ld, (unsigned)a->n,
-                                   (unsigned)row_begin, (unsigned)row_end, (unsigned)col_begin, 0u);
-            }
+            const int gi = (int)(in_place ? a->groups : a->groups_inv);
+            int g = 0;                                         // at most 2^16 groups per range; the chip's slots at the pass's own occupancy
+            const int k = stage_split(gi, std::max(pick_split(std::max<size_t>(ntl, 1), gi, C.gc, slots(C.wg_per_cu)), (gi + (1 << 16) - 1) >> 16), C.gc, &g);
+            // several ranges add onto the cells: zero them first (nothing else has written nn) -- unless the call already has
+            if (in_place && k > 1 && !nn_zeroed && ncomp) zero_cells(nullptr, ncomp, 0u);
             if (ntl) {
                 MfmaArgs A;
                 A.P = in_place ? a->planes + 4 * a->n_pad : a->iplanes;
-                A.count_gp = in_place ? NPLANES : 1;
-                A.count_store = (in_place && k == 1) ? 1 : 0;
+                A.count_gp = in_place ? NPLANES : 1; A.count_store = (in_place && k == 1) ? 1 : 0;
                 A.n_pad = a->n_pad; A.groups = gi; A.tiles = tl; A.n_tiles = (int)ntl; A.gps = g; A.ksplit = k;
-                A.L = lu;                                      // range 0 adds |U| - c_i - c_j once per cell
-                A.c_n = a->c_counted;
+                A.L = lu; A.c_n = a->c_counted;                // range 0 adds |U| - c_i - c_j once per cell
                 A.n = (unsigned)a->n; A.row_end = (unsigned)row_end; A.col_begin = (unsigned)col_begin;
                 A.dist = dist; A.ncomp = ncomp; A.ld = ld; A.thr = 0xFFFFFFFFu; A.ph = TilePhase{0, 0, nullptr};
                 A.count_mode = gram ? 1 : 0;
@@ -1198,8 +1206,7 @@ static int pairsnp_dense_impl(const tracs_alignment *a_, size_t row_begin, size_
         pair_mark(3, stream);
         if (!ncomp) return TRACS_OK;                           // (gram without nn: the distances' passes were all there was to do)
         if (a->L_nnl > 0) {
-            const int rc = nn_rows_add(a, row_begin, row_end, col_begin, ncomp, ld, terms_added ? 0 : 1, lu, stream);
-            if (rc) return rc;
+            if (const int rc = nn_rows_add(a, row_begin, row_end, col_begin, ncomp, ld, terms_added ? 0 : 1, lu, stream)) return rc;
             terms_added = true;
         }
         if (!terms_added) {                                    // no pair of N samples anywhere outside the dense sites
@@ -1208,90 +1215,83 @@ static int pairsnp_dense_impl(const tracs_alignment *a_, size_t row_begin, size_
                                (unsigned)col_begin, lu, a->L_un ? a->c_counted : (const unsigned *)nullptr);
         }
         return TRACS_OK;
-    };
-    // Site classes, consensus form: the minority sites' distances from their lists (general_sparse.hip, general_fixup_kernel<MINOR>)
-    auto minor_pass = [&]() -> int {
-        return (classes && a->lists) ? minority_fixup(a, row_begin, row_end, col_begin, dist, ld, stream) : TRACS_OK;
-    };
-    if (classes && groups == 0) {
-        // no dense site at all: the distances come from the lists, the compared-sites counts from the counting pass
-        dim3 grid(64, (unsigned)std::min<size_t>(row_end - row_begin, 65535));
-        pair_mark(0, stream);
-        hipLaunchKernelGGL(init_cells_kernel, grid, dim3(256), 0, stream, dist, ncomp, ld, (unsigned)a->n,
-                           (unsigned)row_begin, (unsigned)row_end, (unsigned)col_begin, 0u);
-        nn_zeroed = true;
-        pair_mark(1, stream);
-        int rc = minor_pass();
-        if (rc) return rc;
-        pair_mark(2, stream);
-        if (!gram) dist_final(stream);                         // (gram: the counting passes still add to the distances)
-        if ((rc = count_pass(nullptr, 0))) return rc;
-        pair_mark(4, stream);
-        TRACS_HIP_CHECK(hipGetLastError());
-        return TRACS_OK;
     }
-
-    // Thresholded run on a long alignment: two passes.  The prefix pass (1/8 of the groups, one workgroup per tile) leaves
-    // exact partial counts and a live flag per tile; the remainder pass visits the live tiles only, its range split so that the
-    // few surviving tiles still fill the chip.  Dead tiles cost 1/8 of a full pass or less (they also stop inside the prefix).
-    static const bool no_two_pass = std::getenv("TRACS_THR_ONE_PASS") != nullptr;
-    if (thr != 0xFFFFFFFFu && !no_two_pass && groups >= 64 * kGC) {
-        int prefix = std::min(max_gps / kGC * kGC, std::max(8 * kGC, groups / 8 / kGC * kGC));
-        if (const char *e = std::getenv("TRACS_THR_PREFIX")) { const int v = std::atoi(e) / kGC * kGC; if (v >= kGC && v < groups) prefix = v; }
-        unsigned char *live = nullptr;
-        int2 *live_tiles = nullptr;
-        unsigned *n_live_d = nullptr;
+    // The tail of every pair stage.  live: the tiles the counting pass gets (nullptr: every tile of the region)
+    int finish(const int2 *live, size_t n_live)
+    {
         int rc;
-        if ((rc = tracs::workspace_get(tracs::WS_PS_LIVE, T.n, &live))) return rc;
-        if ((rc = tracs::workspace_get(tracs::WS_PS_LIVE_TILES, T.n, &live_tiles))) return rc;
-        if ((rc = tracs::workspace_get(tracs::WS_PS_N_LIVE, 16, &n_live_d))) return rc;
-        TRACS_HIP_CHECK(hipMemsetAsync(n_live_d, 0, 4, stream));
-        pair_mark(0, stream);
-        if ((rc = launch(T.d, (unsigned)T.n, (int)T.n, prefix, prefix, 1, thr, TilePhase{1, 0, live}))) return rc;
-        hipLaunchKernelGGL(compact_live_kernel, dim3((unsigned)((T.n + 255) / 256)), dim3(256), 0, stream, T.d, live,
-                           (unsigned)T.n, live_tiles, n_live_d);
-        unsigned n_live = 0;
-        TRACS_HIP_CHECK(hipMemcpyAsync(&n_live, n_live_d, 4, hipMemcpyDeviceToHost, stream));
-        TRACS_HIP_CHECK(hipStreamSynchronize(stream));
-        if (n_live) {
-            // enough workgroups for ~4 rounds of the chip, never more than 32 ranges (each range costs one atomic per cell)
-            int gps2 = 0;
-            const int want = (int)std::ceil(4.0 * slots / (double)n_live);
-            const int k2 = stage_split(groups - prefix, std::max({1, std::min({32, want, (groups - prefix) / (16 * kGC)}), (groups - prefix + max_gps - 1) / max_gps}), gps2);
-            if ((rc = launch(live_tiles, (unsigned)(n_live * (size_t)k2), (int)n_live, groups, gps2, k2, thr, TilePhase{2, prefix, nullptr}))) return rc;
-        }
         pair_mark(1, stream);
-        if (mfma_general && (rc = general_sparse_fixup(a, row_begin, row_end, col_begin, dist, ncomp_pair, ld, stream))) return rc;
-        if ((rc = minor_pass())) return rc;
+        // (mfma_general is false on the no-dense-site route -- pair_L == 0 never enters choose_route's loop: one tail serves all three stages)
+        if (R.mfma_general && (rc = general_sparse_fixup(a, row_begin, row_end, col_begin, dist, R.ncomp_pair, ld, stream))) return rc;
+        // site classes: the minority sites' distances from their lists (general_sparse.hip, general_fixup_kernel<MINOR>)
+        if (R.classes && a->lists && (rc = minority_fixup(a, row_begin, row_end, col_begin, dist, ld, stream))) return rc;
         pair_mark(2, stream);
-        if (!gram) dist_final(stream);                         // (gram: the counting passes still add to the distances)
-        if ((rc = count_pass(live_tiles, n_live))) return rc;
+        if (!R.gram) dist_final(stream);                       // (gram: the counting passes still add to the distances)
+        if ((rc = count_pass(live, n_live))) return rc;
         pair_mark(4, stream);
         TRACS_HIP_CHECK(hipGetLastError());
         return TRACS_OK;
     }
+};
 
-    if (mfma) ksplit = std::max(ksplit, (groups + max_gps - 1) / max_gps);
-    int gps = 0;
-    ksplit = stage_split(groups, ksplit, gps);
-    pair_mark(0, stream);
-    if (ksplit > 1) {
-        dim3 grid(64, (unsigned)std::min<size_t>(row_end - row_begin, 65535));
-        hipLaunchKernelGGL(init_cells_kernel, grid, dim3(256), 0, stream, dist, ncomp, ld, (unsigned)a->n,
-                           (unsigned)row_begin, (unsigned)row_end, (unsigned)col_begin, (cons || mfma) ? 0u : (unsigned)a->L);
-        nn_zeroed = cons || mfma;
+static int pairsnp_dense_impl(const tracs_alignment *a_, size_t row_begin, size_t row_end, size_t col_begin, uint32_t *dist,
+                              uint32_t *ncomp, size_t ld, void *stream_, unsigned thr)
+{
+    // 1. checks
+    tracs_alignment *a = const_cast<tracs_alignment *>(a_);
+    if (!a || !dist) { set_error("tracs_pairsnp_dense: NULL argument"); return TRACS_E_ARG; }
+    if (row_end > a->n) row_end = a->n;
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    // an event armed by tracs_pairsnp_notify_distances belongs to THIS call: recorded when the distances are final, or -- on every
+    // other way out, errors included -- recorded at the exit, never left armed for an unrelated later call
+    struct DistEventGuard { hipStream_t s; ~DistEventGuard() { dist_final(s); } } dist_guard{stream};
+    if (row_begin >= row_end || a->n < 2) return TRACS_OK;
+    if (ld < a->n) { set_error("tracs_pairsnp_dense: ld < n"); return TRACS_E_ARG; }
+    DeviceCall guard(stream);
+    if (a->n_row_hint) {
+        bool inside = false;
+        for (int k = 0; k < a->n_row_hint; k++) inside = inside || (row_begin >= a->row_hint[2 * k] && row_end <= std::min(a->n, a->row_hint[2 * k + 1]));
+        if (!inside) { set_error("tracs_pairsnp_dense: rows outside the ranges given to tracs_alignment_hint_rows"); return TRACS_E_ARG; }
     }
-    int rc = launch(T.d, (unsigned)(T.n * (size_t)ksplit), (int)T.n, groups, gps, ksplit, thr, TilePhase{0, 0, nullptr});
-    if (rc) return rc;
-    pair_mark(1, stream);
-    if (mfma_general && (rc = general_sparse_fixup(a, row_begin, row_end, col_begin, dist, ncomp_pair, ld, stream))) return rc;
-    if ((rc = minor_pass())) return rc;
-    pair_mark(2, stream);
-    if (!gram) dist_final(stream);
-    if ((rc = count_pass(nullptr, 0))) return rc;
-    pair_mark(4, stream);
-    TRACS_HIP_CHECK(hipGetLastError());
-    return TRACS_OK;
+    DenseCall call{a, row_begin, row_end, col_begin, dist, ncomp, ld, stream, thr, DenseRoute{}};
+    if (a->L == 0) {                                       // 2. no sites -- every pair: d = 0, nn = 0
+        call.zero_cells(dist, ncomp, 0u);
+        dist_final(stream);
+        TRACS_HIP_CHECK(hipGetLastError());
+        return TRACS_OK;
+    }
+    // 3. once per pack.  (Matrix cores unless switched off; their kernels keep 32-bit element offsets inside a stage: n_pad < 2^28 samples)
+    const bool mfma_off = dense_switch::mfma_off() || a->n_pad >= (1ull << 28);
+    int rc;
+    if (a->dirty && (rc = decide_pack(a, stream, mfma_off))) return rc;
+    // 4. the route
+    if ((rc = choose_route(a, stream, (double)(row_end - row_begin) * (double)a->n, mfma_off, ncomp, &call.R))) return rc;
+    const DenseRoute &R = call.R;
+    a->last_kernel = R.kernel();
+    // 5. tiles; none: nothing to do
+    tracs_alignment::TileCache *T = nullptr;
+    if ((rc = call.tiles(R.ti, R.tj, &T))) return rc;
+    if (T->n == 0) { dist_final(stream); return TRACS_OK; }
+    // 6. one of three pair stages; each yields the tiles the counting pass gets (nullptr: every tile of the region)
+    const int2 *live = nullptr; size_t n_live = 0;
+    if (R.classes && R.groups == 0) call.pairs_none();
+    else if (!dense_switch::thr_one_pass() && thr != 0xFFFFFFFFu && R.groups >= 64 * R.gc) rc = call.pairs_two_pass(*T, &live, &n_live);
+    else rc = call.pairs_one_launch(*T);
+    return rc ? rc : call.finish(live, n_live);    // 7. the tail
+}
+
+int tracs_pairsnp_dense(const tracs_alignment *a_, size_t row_begin, size_t row_end, size_t col_begin, uint32_t *dist,
+                        uint32_t *ncomp, size_t ld, void *stream_)
+{
+    return pairsnp_dense_impl(a_, row_begin, row_end, col_begin, dist, ncomp, ld, stream_, 0xFFFFFFFFu);
+}
+
+int tracs_pairsnp_dense_thr(const tracs_alignment *a_, size_t row_begin, size_t row_end, size_t col_begin, uint32_t *dist,
+                            uint32_t *ncomp, size_t ld, int32_t dist_threshold, void *stream_)
+{
+    // a negative threshold emits nothing; any d > threshold may come back as 0xFFFFFFFF
+    const unsigned thr = dist_threshold < 0 ? 0u : (unsigned)dist_threshold;
+    return pairsnp_dense_impl(a_, row_begin, row_end, col_begin, dist, ncomp, ld, stream_, dist_threshold == 2147483647 ? 0xFFFFFFFFu : thr);
 }
 
 int tracs_coo_count(const uint32_t *dist, size_t ld, size_t n, size_t row_begin, size_t row_end, size_t col_begin,
