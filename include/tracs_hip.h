@@ -605,6 +605,34 @@ int tracs_filter_recomb_lists(tracs_alignment *a, const int64_t *off, const uint
 int tracs_fitch_mark_dropped(const uint32_t *site, const uint32_t *edge, uint32_t *info, size_t n_entries, size_t n_edges, const int64_t *edge_off,
                              const uint32_t *edge_site, const uint8_t *dropped, void *stream);
 
+/* The branch filter's verdicts turned back into an alignment (csrc/tree_mask.hip; not in the reference): what one
+ * iteration of tracs_distance_tree_iterate masks.
+ *   tracs_alignment_clone          *out: a NEW handle with src's n, L and planes, byte for byte (a device-to-device copy; no existing
+ *                                  entry gives one: tracs_alignment_select_sites and _gather_sites re-pack through a gather); src is left
+ *                                  as it was.  A copy that does not fit in the device's memory is refused (TRACS_E_NOMEM) with a message
+ *                                  that says so.  Stream-ordered.
+ *   tracs_alignment_restore        dst's planes <- src's, the same copy into an existing handle of src's n and L (anything else is
+ *                                  refused): what tracs_distance_tree_iterate does to its clone between iterations.  It counts as a
+ *                                  re-pack of dst.  Stream-ordered.
+ *   tracs_alignment_mask_subtrees  parent / child: HOST uint32[n_edges], the tree exactly as tracs_fitch_count takes it for a's n samples;
+ *                                  anything else is refused (TRACS_E_ARG) before a launch.  edge_off (device int64[n_edges + 1]),
+ *                                  edge_site (device uint32[n_entries]) and dropped (device uint8[n_entries]): what
+ *                                  tracs_fitch_edge_sites and tracs_filter_recomb_lists leave.  Offsets that do not start at 0, that
+ *                                  decrease, or that end beyond n_entries are refused before a launch.  For every entry k of edge e
+ *                                  with dropped[k] != 0 and every sample i below e (the leaves in the subtree of e's child, the side away
+ *                                  from the top node; n = 2: the sample 1) the cell (i, edge_site[k]) becomes N: the site's bit is
+ *                                  set in the four allele planes and the N plane.  The host derives a leaf order (depth-first from the
+ *                                  top node) in which every edge's leaves are an interval; the device gives every entry the weight
+ *                                  |below(e)| or 0, scans the weights (the total W is 64-bit and is run over in ranges) and takes one
+ *                                  (entry, leaf) cell per lane with an atomic OR per plane word.  An entry with site >= L stores
+ *                                  nothing; tail bits and pad samples stay 0.  *n_cells (may be NULL) <- the cells that were not N and
+ *                                  now are (a set, so deterministic).  Masking counts as a re-pack of `a`: what the handle caches per
+ *                                  pack is rebuilt by the next call.  Synchronises the stream.                                       */
+int tracs_alignment_clone(const tracs_alignment *src, tracs_alignment **out, void *stream);
+int tracs_alignment_restore(tracs_alignment *dst, const tracs_alignment *src, void *stream);
+int tracs_alignment_mask_subtrees(tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, const int64_t *edge_off,
+                                  const uint32_t *edge_site, const uint8_t *dropped, size_t n_entries, uint64_t *n_cells, void *stream);
+
 /* transcluster on device arrays (same math as tracs_trans_dist).  workspace is managed
  * internally (hipMallocAsync on the stream).  exp_p0 != 0 writes exp(p0) (what
  * tracs/transcluster.py:38-39 returns with log=False).                                     */
@@ -858,6 +886,46 @@ typedef struct tracs_tree_result {
     uint64_t n_joins, rows_written, n_changes, sum_minimum, n_kept, n_edges_dropped;
 } tracs_tree_result;
 int tracs_distance_tree_run(tracs_distance *h, const tracs_tree_request *req, tracs_tree_result *res);
+/*   tracs_distance_tree_iterate  `--tree-filter --tree-iterate K` (not in the reference): the branch filter iterated into
+ *                         the topology.  it == NULL: tracs_distance_tree_run, byte for byte.  Else the request needs filter and takes no
+ *                         replicates, and 1 <= max_iterations <= 100 (TRACS_E_ARG otherwise).  A is the handle's packed alignment after
+ *                         every site and sample rule, n samples, L sites.  NJ(X): the tree of tracs_nj_* from alignment X (kind 0 or
+ *                         1, the same operation order and tie rule).  V(T): the dropped (edge e, site s) of the branch filter: Fitch's
+ *                         two passes of A on T, then the window test per edge.  below(T, e): the samples in the subtree of e's child,
+ *                         the side away from T's top node (n = 2: {1}).
+ *                             T_0 = NJ(A).  For k = 1 .. K:
+ *                                 M_k = A with the cell (i, s) set to N (mask 15 in the four allele planes, and the N plane) for every
+ *                                       (e, s) in V(T_{k-1}) and every i in below(T_{k-1}, e); always from A, never from M_{k-1}
+ *                                 T_k = NJ(M_k)
+ *                                 T_k has the set of non-trivial splits of some T_j, j < k (tracs_tree_support's comparison): stop;
+ *                                       same_as = the smallest such j (j = k - 1: converged; smaller: a cycle)
+ *                                 k = K without a repeat: stop at the limit (same_as = -1)
+ *                         n < 4 has no non-trivial split: T_1 repeats T_0 and the run ends at k = 1; on two samples the final length is
+ *                         the pair's filtered distance.  The final tree is the last T_k: it decides `path`, with lengths as NJ(M_k)
+ *                         computes them; edges_path, changes_path, sites_path and filtered_path are what the filter request writes,
+ *                         for (A, T_final): Fitch of the ORIGINAL alignment on the final tree, and its verdicts.  Nothing is written
+ *                         before the loop ends; max_entries is checked against every iteration's change count.  Kind 1 with a pair
+ *                         compared over 0 sites after masking is refused by name, and the message names the iteration.  The masked
+ *                         cells of tree k are the cells that are not N in A and are N in M_{k+1} (a set, so deterministic).
+ *                         M_k lives in one tracs_alignment_clone of A, restored from A between iterations.
+ *                         iterations_path != NULL: one row per tree k = 0 .. final is appended (create != 0: after the header
+ *                         iteration,changes,kept,dropped,branches with a drop,masked cells,shared splits,same as,MSA file): the counts
+ *                         of V(T_k); masked cells (NA on the final row); shared splits: the non-trivial splits of T_k that T_{k-1}
+ *                         has (NA for k = 0); same as: same_as on the final row of a run that stopped on a repeat, NA elsewhere.
+ *                         res: the result of the filter request for (A, T_final).  ires: iterations: the final k; same_as;
+ *                         masked_cells_last: the masked cells of tree final - 1 (the N cells M_final adds to A); mask_work_max: the
+ *                         largest W of tracs_alignment_mask_subtrees over the iterations.                                            */
+typedef struct tracs_tree_iterate {
+    uint32_t max_iterations;
+    const char *iterations_path;
+} tracs_tree_iterate;
+typedef struct tracs_tree_iterate_result {
+    uint32_t iterations;
+    int32_t same_as;
+    uint64_t masked_cells_last, mask_work_max;
+} tracs_tree_iterate_result;
+int tracs_distance_tree_iterate(tracs_distance *h, const tracs_tree_request *req, const tracs_tree_iterate *it, tracs_tree_result *res,
+                                tracs_tree_iterate_result *ires);
 /*   tracs_distance_tree   the request {kind, path, ref, edges_path}: the main tree alone                                         */
 int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint64_t *n_joins,
                         uint64_t *rows_written);

@@ -59,6 +59,7 @@ SYMBOLS = [
     "tracs_fitch_count", "tracs_fitch_fill", "tracs_tree_write_changes", "tracs_distance_tree_changes",
     "tracs_fitch_edge_sites", "tracs_filter_recomb_lists", "tracs_fitch_mark_dropped", "tracs_tree_write_filtered",
     "tracs_distance_tree_filter", "tracs_distance_tree_run",
+    "tracs_alignment_clone", "tracs_alignment_restore", "tracs_alignment_mask_subtrees", "tracs_distance_tree_iterate",
 ]
 
 
@@ -79,6 +80,16 @@ class TreeRequest(C.Structure):
 class TreeResult(C.Structure):
     """tracs_tree_result: the counters of a tree request; what was not asked for is 0"""
     _fields_ = [(name, C.c_uint64) for name in ("n_joins", "rows_written", "n_changes", "sum_minimum", "n_kept", "n_edges_dropped")]
+
+
+class TreeIterate(C.Structure):
+    """tracs_tree_iterate (include/tracs_hip.h): the branch filter iterated into the topology, at most max_iterations times"""
+    _fields_ = [("max_iterations", C.c_uint32), ("iterations_path", C.c_char_p)]
+
+
+class TreeIterateResult(C.Structure):
+    """tracs_tree_iterate_result: the final k, the earlier tree it repeats (-1: none), the cells the last mask made N, the largest W"""
+    _fields_ = [("iterations", C.c_uint32), ("same_as", C.c_int32), ("masked_cells_last", C.c_uint64), ("mask_work_max", C.c_uint64)]
 
 
 class TracsError(RuntimeError):
@@ -218,6 +229,14 @@ def load():
     L.tracs_anc_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tracs_distance_tree_run.restype = C.c_int
     L.tracs_distance_tree_run.argtypes = [vp, C.POINTER(TreeRequest), C.POINTER(TreeResult)]
+    L.tracs_distance_tree_iterate.restype = C.c_int
+    L.tracs_distance_tree_iterate.argtypes = [vp, C.POINTER(TreeRequest), C.POINTER(TreeIterate), C.POINTER(TreeResult), C.POINTER(TreeIterateResult)]
+    L.tracs_alignment_clone.restype = C.c_int
+    L.tracs_alignment_clone.argtypes = [vp, C.POINTER(vp), vp]
+    L.tracs_alignment_restore.restype = C.c_int
+    L.tracs_alignment_restore.argtypes = [vp, vp, vp]
+    L.tracs_alignment_mask_subtrees.restype = C.c_int
+    L.tracs_alignment_mask_subtrees.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, u64p, vp]
     # the five older forms of that request: (handle, kind, path, ref, edges_path), their own arguments, their counters
     rows = [C.POINTER(C.c_char_p), u64p, sz, C.c_uint64, C.c_int, C.c_int]          # contigs .. create
     for name, own in (("", [u64p] * 2), ("_changes", [C.c_char_p] * 2 + rows + [u64p] * 4), ("_filter", [C.c_char_p] * 3 + rows + [u64p] * 6),

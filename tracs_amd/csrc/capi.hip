@@ -1366,7 +1366,8 @@ int tree_changes_stage(tracs_distance *h, const tracs_tree_request &r, const Tre
 {
     const size_t n = h->a->n;
     int rc;
-    clock.memory("before the Fitch passes");                               // (the tree's matrix is gone)
+    clock.memory("before the Fitch passes");                               // (the tree's matrix is gone; under the iteration it, the walk's
+                                                                           // panels and the clone stay until the loop ends)
     if (n && (rc = tracs::fitch_tables(h->a, t.parent.data(), t.child.data(), t.ne, c.ft))) return rc;
     clock.mark("tree changes: count pass, offsets");
     if (g_sigint) return interrupted();
@@ -1398,10 +1399,115 @@ int tree_changes_stage(tracs_distance *h, const tracs_tree_request &r, const Tre
     return TRACS_OK;
 }
 
-int tree_run(const std::string &who, tracs_distance *h, const tracs_tree_request &r, tracs_tree_result &res)
+// One tree's row of the iterations file (include/tracs_hip.h: tracs_distance_tree_iterate)
+struct TreeIterRow {
+    uint64_t changes, kept, edges_dropped, masked;
+    bool has_masked;
+    int64_t shared;                                                        // -1: NA
+    int32_t same_as;                                                       // -1: NA
+};
+
+// the non-trivial splits of `t` that `other` has (tracs_tree_support's comparison); n < 4: there is none
+int tree_shared_splits(size_t n, const TreeEdges &t, const TreeEdges &other, size_t &shared)
+{
+    shared = 0;
+    if (n < 4) return TRACS_OK;
+    std::vector<uint32_t> count(t.ne, 0);
+    const int rc = tracs_tree_support(n, t.parent.data(), t.child.data(), t.ne, other.parent.data(), other.child.data(), other.ne, count.data());
+    for (size_t e = 0; e < t.ne; e++) if (t.child[e] >= n) shared += count[e];
+    return rc;
+}
+
+// The branch filter iterated into the topology (include/tracs_hip.h: tracs_distance_tree_iterate).  t comes in as T_0 and
+// goes out as the final tree, ch as its labels: the changes stage runs on every T_k with the handle's own alignment, its verdicts mask
+// one clone (restored from the handle's planes between iterations), and the clone goes through the main tree's walk, state and joins as
+// a bootstrap replicate does.  Earlier trees stay on the host for the split comparison.
+int tree_iterate_stage(tracs_distance *h, const tracs_tree_request &r, const tracs_tree_iterate &it, PanelWalk &walk, DeviceBuffer &d_state,
+                       StageClock &clock, TreeEdges &t, std::unique_ptr<TreeLabels> &ch, std::vector<TreeIterRow> &rows,
+                       tracs_tree_iterate_result &ires)
+{
+    const size_t n = h->a->n;
+    const char *const *names = h->name_ptr.data();
+    const bool has_planes = tracs_alignment_bytes(h->a) != 0;
+    std::vector<TreeEdges> seen;
+    AlignmentOwner clone;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};                                  // the two stages of a tree; clone / restore; the mask
+    uint32_t k = 0;
+    bool stop = false;
+    int32_t same = -1;
+    int64_t shared_prev = -1;
+    int rc;
+    ires = tracs_tree_iterate_result();
+    ires.same_as = -1;
+    for (;;) {
+        ch.reset(new TreeLabels());
+        if ((rc = tree_changes_stage(h, r, t, clock, *ch))) return rc;
+        TreeIterRow row = {ch->ft.total, ch->kept_sum, ch->edges_dropped, 0, false, shared_prev, -1};
+        if (stop) {
+            row.same_as = same;
+            rows.push_back(row);
+            break;
+        }
+        // M_{k + 1}: the handle's planes, then the verdicts of T_k
+        uint64_t cells = 0, work = 0;
+        if (has_planes) {
+            if (!clone) {
+                tracs_alignment *c = nullptr;
+                if ((rc = tracs_alignment_clone(h->a, &c, nullptr))) return rc;
+                clone.reset(c);
+            } else if ((rc = copy_planes("tracs_distance_tree_iterate", clone.get(), h->a, nullptr))) return rc;
+            lap(clock, acc[2]);
+            if (ch->d_dropped.ptr && ch->ft.total &&
+                (rc = mask_subtrees(clone.get(), t.parent.data(), t.child.data(), t.ne, ch->d_edge_off.as<int64_t>(), ch->d_edge_site.as<uint32_t>(),
+                                    ch->d_dropped.as<uint8_t>(), (size_t)ch->ft.total, &cells, &work, nullptr))) return rc;
+            lap(clock, acc[3]);
+        }
+        row.masked = cells; row.has_masked = true;
+        rows.push_back(row);
+        ires.masked_cells_last = cells;
+        ires.mask_work_max = std::max<uint64_t>(ires.mask_work_max, work);
+        ch.reset();                                                        // (the Fitch tables and lists of T_k go before the next matrix)
+        seen.emplace_back(std::move(t));
+        t = TreeEdges();
+        k++;
+        if (g_sigint) return interrupted();
+        // T_k = NJ(M_k)
+        if ((rc = tree_of_alignment(has_planes ? clone.get() : h->a, names, r.kind, walk, d_state, clock, acc, t))) {
+            if (rc == TRACS_E_ARG) set_error("iteration " + std::to_string(k) + " of --tree-iterate: " + std::string(tracs_last_error()));
+            return rc;
+        }
+        same = -1;
+        size_t shared = 0;
+        for (size_t j = 0; j < seen.size(); j++) {                         // (the smallest j with T_k's splits; then T_{k-1} alone)
+            if (same >= 0 && j + 1 < seen.size()) continue;
+            if ((rc = tree_shared_splits(n, t, seen[j], shared))) return rc;
+            if (same < 0 && (n < 4 || shared == n - 3)) same = (int32_t)j;
+        }
+        shared_prev = (int64_t)shared;                                     // (the last comparison is the one with T_{k-1})
+        stop = same >= 0 || k >= it.max_iterations;
+    }
+    ires.iterations = k;
+    ires.same_as = same;
+    if (clock.on) {
+        std::fprintf(stderr, "[stage] iterations: %u trees after the first, %s\n", (unsigned)k,
+                     same < 0 ? "stopped at the limit" : same + 1 == (int32_t)k ? "converged" : "a cycle");
+        std::fprintf(stderr, "[stage] iterations: clone / restore %.4f s\n", acc[2]);
+        std::fprintf(stderr, "[stage] iterations: mask %.4f s (largest W %llu)\n", acc[3], (unsigned long long)ires.mask_work_max);
+        std::fprintf(stderr, "[stage] iterations: dense panels + matrix load %.4f s\n", acc[0]);
+        std::fprintf(stderr, "[stage] iterations: join loop %.4f s\n", acc[1]);
+    }
+    return TRACS_OK;
+}
+
+int tree_run(const std::string &who, tracs_distance *h, const tracs_tree_request &r, tracs_tree_result &res,
+             const tracs_tree_iterate *it = nullptr, tracs_tree_iterate_result *ires = nullptr)
 {
     // (a) the request
     res = tracs_tree_result();
+    tracs_tree_iterate_result ires_none;
+    tracs_tree_iterate_result &ir = ires ? *ires : ires_none;
+    ir = tracs_tree_iterate_result();
+    ir.same_as = -1;
     const bool boot = r.replicates || r.transfer || r.replicate_trees_path, changes = r.changes || r.filter;
     if (!h || !h->a || !r.path || !r.ref) { set_error(who + ": NULL argument"); return TRACS_E_ARG; }
     if (boot && changes) {
@@ -1409,6 +1515,8 @@ int tree_run(const std::string &who, tracs_distance *h, const tracs_tree_request
                         "run once with each and join the two --tree-edges files on parent and child)");
         return TRACS_E_ARG;
     }
+    if (it && (!r.filter || boot)) { set_error(who + ": the iteration needs the branch filter (filter != 0) and takes no replicates"); return TRACS_E_ARG; }
+    if (it && (it->max_iterations < 1 || it->max_iterations > 100)) { set_error(who + ": max_iterations must be in [1, 100]"); return TRACS_E_ARG; }
     if (boot && r.kind != 0) { set_error(who + ": bootstrap replicates take the SNP distance (kind 0) only"); return TRACS_E_ARG; }
     if (r.kind != 0 && r.kind != 1) { set_error(who + ": kind must be 0 (snp) or 1 (per-site)"); return TRACS_E_ARG; }
     if (boot && r.replicates < 1) { set_error(who + ": at least one replicate"); return TRACS_E_ARG; }
@@ -1427,17 +1535,27 @@ int tree_run(const std::string &who, tracs_distance *h, const tracs_tree_request
     if ((rc = tree_of_alignment(h->a, names, r.kind, walk, d_state, clock, nullptr, t))) return rc;
     // (c) at most one stage.  The replicates are joined on the main tree's walk and state, which stay until the call returns; the Fitch
     // passes need neither, so both go first: at n = 10000 the state alone is 0.8 GB that must not sit under them.
-    TreeLabels ch;
-    if (boot && (rc = tree_bootstrap_stage(h, r, t, walk, d_state, clock, ch))) return rc;
-    if (changes) {
+    std::unique_ptr<TreeLabels> labels(new TreeLabels());
+    std::vector<TreeIterRow> iter_rows;
+    if (boot && (rc = tree_bootstrap_stage(h, r, t, walk, d_state, clock, *labels))) return rc;
+    if (it) {                                                              // (the walk and the state stay: every iteration joins on them)
+        if ((rc = tree_iterate_stage(h, r, *it, walk, d_state, clock, t, labels, iter_rows, ir))) {
+            ir = tracs_tree_iterate_result();                              // (a run that failed reports nothing of its iterations)
+            ir.same_as = -1;
+            return rc;
+        }
         walk.d_dist.release(); walk.d_nn.release(); d_state.release();
-        if ((rc = tree_changes_stage(h, r, t, clock, ch))) return rc;
+    } else if (changes) {
+        walk.d_dist.release(); walk.d_nn.release(); d_state.release();
+        if ((rc = tree_changes_stage(h, r, t, clock, *labels))) return rc;
     }
+    TreeLabels &ch = *labels;
     // (d) the files
     const uint32_t *edge_changes = changes ? ch.ft.edge_changes.data() : nullptr, *kept = r.filter ? ch.kept.data() : nullptr;
     const uint32_t *const parent = t.parent.data(), *const child = t.child.data();
     if (changes && r.create) {                                             // (tracs/distance.py leaves the run's files to the library then)
-        const std::pair<const char *, std::string> made[5] = {{r.path, ""}, {r.edges_path, tree_edges_header({nullptr, nullptr, edge_changes, kept})},
+        const std::pair<const char *, std::string> made[6] = {{r.path, ""}, {r.edges_path, tree_edges_header({nullptr, nullptr, edge_changes, kept})},
+            {it ? it->iterations_path : nullptr, "iteration,changes,kept,dropped,branches with a drop,masked cells,shared splits,same as,MSA file\n"},
             {r.changes_path, std::string("parent,child,contig,position,alleleParent,alleleChild,") + (r.filter ? "dropped," : "") + "MSA file\n"},
             {r.sites_path, "contig,position,changes,minimum,MSA file\n"}, {r.filtered_path, ""}};
         for (const auto &f : made) {
@@ -1457,6 +1575,18 @@ int tree_run(const std::string &who, tracs_distance *h, const tracs_tree_request
         rc = tracs_tree_write(names, n, parent, child, kept_length.data(), t.ne, r.filtered_path, r.ref, nullptr);
     }
     if (rc) return rc;
+    if (it && it->iterations_path) {
+        std::FILE *fh = std::fopen(it->iterations_path, "ab");
+        if (!fh) { set_error(std::string("cannot open ") + it->iterations_path + " for appending"); return TRACS_E_OPEN; }
+        const auto na = [](bool have, long long v) { return have ? std::to_string(v) : std::string("NA"); };
+        for (size_t k = 0; k < iter_rows.size(); k++) {
+            const TreeIterRow &w = iter_rows[k];
+            std::fprintf(fh, "%zu,%llu,%llu,%llu,%llu,%s,%s,%s,%s\n", k, (unsigned long long)w.changes, (unsigned long long)w.kept,
+                         (unsigned long long)(w.changes - w.kept), (unsigned long long)w.edges_dropped, na(w.has_masked, (long long)w.masked).c_str(),
+                         na(w.shared >= 0, w.shared).c_str(), na(w.same_as >= 0, w.same_as).c_str(), r.ref);
+        }
+        if (std::fclose(fh) != 0) { set_error(std::string("write failed: ") + it->iterations_path); return TRACS_E_OPEN; }
+    }
     clock.mark("tree: emit, lengths, format, write");
     if (changes) {
         if (n && (rc = tracs::fitch_write(h->a, names, h->kept.empty() ? nullptr : h->kept.data(), h->source_len, parent, child, t.ne, ch.ft,
@@ -1491,6 +1621,16 @@ int tracs_distance_tree_run(tracs_distance *h, const tracs_tree_request *req, tr
     if (res) *res = none;
     if (!req) { set_error("tracs_distance_tree_run: NULL argument"); return TRACS_E_ARG; }
     return tree_run("tracs_distance_tree_run", h, *req, res ? *res : none);
+}
+
+int tracs_distance_tree_iterate(tracs_distance *h, const tracs_tree_request *req, const tracs_tree_iterate *it, tracs_tree_result *res,
+                                tracs_tree_iterate_result *ires)
+{
+    tracs_tree_result none = {};
+    if (res) *res = none;
+    if (ires) { *ires = tracs_tree_iterate_result(); ires->same_as = -1; }
+    if (!req) { set_error("tracs_distance_tree_iterate: NULL argument"); return TRACS_E_ARG; }
+    return tree_run(it ? "tracs_distance_tree_iterate" : "tracs_distance_tree_run", h, *req, res ? *res : none, it, ires);
 }
 
 int tracs_distance_tree(tracs_distance *h, int kind, const char *path, const char *ref, const char *edges_path, uint64_t *n_joins,

@@ -208,6 +208,16 @@ int fitch_write(const tracs_alignment *a, const char *const *names, const uint64
                 const char *const *contig_names, const uint64_t *contig_lengths, size_t n_contigs, int n_threads,
                 const FitchFilter *flt = nullptr);
 
+// fitch.hip: the tree check of tracs_fitch_* (the rows of tracs_nj_edges, nothing else) for the other files that take such a tree
+int nj_tree_check(const char *who, size_t n, const uint32_t *parent, const uint32_t *child, size_t n_edges);
+
+// tree_mask.hip: dst's planes <- src's (same n and L; tracs_alignment_clone's copy, and the restore between the iterations of
+// tracs_distance_tree_iterate); dst counts as packed again.  who: the entry point an error message names
+int copy_planes(const char *who, tracs_alignment *dst, const tracs_alignment *src, hipStream_t stream);
+// tree_mask.hip: tracs_alignment_mask_subtrees; work (may be NULL) <- W, the (entry, leaf) cells the scatter ran over
+int mask_subtrees(tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, const int64_t *edge_off,
+                  const uint32_t *edge_site, const uint8_t *dropped, size_t n_entries, uint64_t *n_cells, uint64_t *work, hipStream_t stream);
+
 // device memory that lives until the alignment is packed again (site_classes_free releases all of it at once)
 hipError_t pack_alloc(tracs_alignment *a, size_t bytes, void **out);
 void pack_release(tracs_alignment *a);
@@ -251,6 +261,9 @@ enum WsSlot : int {
     // fitch.hip: a slab's node sets [node][word], the edge list's child column, tile sums of the offsets scan; the [chunk][edge] matrix of
     // tracs_fitch_edge_sites and its per-edge cursor
     WS_FITCH_NODES, WS_FITCH_TREE, WS_FITCH_SUMS, WS_FITCH_MATRIX, WS_FITCH_CURSOR,
+    // tree_mask.hip: the leaf order and the edges' intervals in it, per entry its weight and its interval's start, the scanned weights
+    // and their tile sums, the count of newly masked cells
+    WS_MASK_TREE, WS_MASK_WEIGHT, WS_MASK_LO, WS_MASK_OFF, WS_MASK_SUMS, WS_MASK_CELLS,
     WS_SLOT_COUNT
 };
 

@@ -446,6 +446,12 @@ __global__ __launch_bounds__(256) void fitch_mark_kernel(const unsigned *__restr
 
 }  // namespace
 
+// fitch_tree_check for the other files that take the tree of tracs_nj_edges (tree_mask.hip)
+int nj_tree_check(const char *who, size_t n, const uint32_t *parent, const uint32_t *child, size_t n_edges)
+{
+    return fitch_tree_check(who, n, parent, child, n_edges);
+}
+
 // edge_changes[0 .. n_edges), site_changes[0 .. L), site_minimum[0 .. L), off[0 .. L] (device); *total (host) = off[L].  Synchronises.
 int fitch_count(const tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, unsigned *edge_changes,
                 unsigned *site_changes, uint8_t *site_minimum, long long *off, uint64_t *total, hipStream_t stream)

@@ -784,6 +784,43 @@ def fitch_mark_dropped(site, edge, info, edge_off, edge_site, dropped):
     return info
 
 
+def clone_alignment(aln):
+    """-> a new Alignment with the n, L and planes of `aln`, byte for byte (a device-to-device copy; tracs_alignment_clone); `aln` is
+    left as it was.  A copy that does not fit in the device's memory is refused."""
+    h = C.c_void_p()
+    _lib.check(aln._L.tracs_alignment_clone(aln._h, C.byref(h), _stream()))
+    new = Alignment.__new__(Alignment)
+    new._L, new._h = aln._L, h
+    new.n, new.L = aln.n, aln.L
+    for attr in ("names", "n_first"):
+        if hasattr(aln, attr):
+            setattr(new, attr, getattr(aln, attr))
+    return new
+
+
+def restore_alignment(dst, src):
+    """dst's planes <- src's (two handles of one shape; tracs_alignment_restore): a clone put back to its source after mask_subtrees"""
+    _lib.check(dst._L.tracs_alignment_restore(dst._h, src._h, _stream()))
+
+
+def mask_subtrees(aln, parent, child, edge_off, edge_site, dropped):
+    """The branch filter's verdicts into the alignment, in place (tracs_alignment_mask_subtrees): for every entry k with
+    dropped[k] != 0 of edge e (edge_off torch.int64 [n_edges + 1], edge_site 32-bit, dropped torch.uint8, on the device: what
+    fitch_edge_sites and filter_recomb_lists return) the cell (i, edge_site[k]) becomes N for every sample i below e, the side away
+    from the tree's top node.  parent, child: the edges as nj_edges returns them (host arrays).  -> the cells that were not N and now
+    are.  What the handle caches per pack is rebuilt by its next call."""
+    L = _lib.require_gpu()
+    parent, child = _tree_arrays(parent, child)
+    k = int(edge_site.numel())
+    assert edge_off.is_cuda and edge_off.is_contiguous() and edge_off.dtype == torch.int64
+    assert k == 0 or (edge_site.is_cuda and edge_site.is_contiguous() and edge_site.element_size() == 4 and not edge_site.is_floating_point())
+    assert int(dropped.numel()) >= k and (k == 0 or (dropped.is_cuda and dropped.is_contiguous() and dropped.dtype == torch.uint8))
+    cells = C.c_uint64(0)
+    _lib.check(L.tracs_alignment_mask_subtrees(aln._h, parent.ctypes.data, child.ctypes.data, len(parent), _ptr(edge_off), _ptr(edge_site),
+                                               _ptr(dropped), k, C.byref(cells), _stream()))
+    return int(cells.value)
+
+
 def filter_index_info(aln):
     """Diagnostics of the alignment's filter index (None before the first filter call)."""
     import ctypes as C

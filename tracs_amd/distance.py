@@ -173,12 +173,31 @@ def distance_parser(parser):
                           "branch than a binomial density d / L explains at 0.05 / d.  --tree-edges gains a filtered column (the changes "
                           "kept on the branch) after changes, --tree-changes a dropped column (0 / 1) before MSA file, and one line on "
                           "stderr counts changes, kept, dropped and the branches with a drop.  The tree is still built from the "
-                          "UNFILTERED distances: the filter is not iterated into the topology.  The verdicts belong to the placement "
+                          "UNFILTERED distances: the filter is not iterated into the topology (--tree-iterate does that).  The verdicts belong to the placement "
                           "that --tree-changes writes, one most-parsimonious reconstruction among possibly several.  Not with "
                           "--bootstrap.  Not in the reference.")
     snp.add_argument("--tree-filtered", dest="tree_filtered", default=None, type=str, metavar="FILE",
                      help="With --tree-filter: write one Newick tree per --msa file with the topology and labels of -o and the number "
                           "of changes that --tree-filter keeps on each branch as its length")
+    snp.add_argument("--tree-iterate", dest="tree_iterate", default=None, type=int, metavar="K",
+                     help="With --tree-filter: iterate the filter into the tree, at most K times (1 <= K <= 100).  The changes that "
+                          "--tree-filter drops are masked (set to N) in a copy of the compared alignment, in every sample below their "
+                          "branch -- the side of the branch away from the tree's top node, the last node neighbour joining makes --, the "
+                          "distances are recomputed, the tree rebuilt and the ORIGINAL alignment placed and filtered on the new tree, "
+                          "until the tree has the splits of an earlier one (converged, or a cycle back to an earlier tree) or K trees "
+                          "were rebuilt.  -o, --tree-edges, --tree-changes, --tree-sites and --tree-filtered then describe the final "
+                          "tree; branch lengths in -o come from the masked distances.  One line on stderr gives the number of trees "
+                          "built, how the run ended and the final tree's changes, kept and dropped counts.  The verdicts still belong "
+                          "to one Fitch placement among possibly several, and the filter is a screen, not a test: it drops about 13 %% "
+                          "of the changes on data without any recombination (DESIGN.md 3.21), so the final tree is built from fewer "
+                          "sites than -o without the flag.  Needs a second copy of the alignment on the GPU.  Not with --bootstrap.  "
+                          "Not in the reference.")
+    snp.add_argument("--tree-iterate-out", dest="tree_iterate_out", default=None, type=str, metavar="FILE",
+                     help="With --tree-iterate: write iteration,changes,kept,dropped,branches with a drop,masked cells,shared splits,"
+                          "same as,MSA file, one row per tree from the unfiltered one (iteration 0) to the final one: the filter's "
+                          "counts on that tree, the cells its verdicts mask (NA on the final row), the splits it shares with the tree "
+                          "before (NA on the first row) and, on the final row of a run that ended on a repeat, the iteration whose "
+                          "tree it repeats")
     snp.add_argument("--bootstrap", dest="bootstrap", default=None, type=int, metavar="B",
                      help="With --tree: B >= 1 bootstrap replicates, resampled and built on the GPU.  A replicate draws as many columns "
                           "as the run compares, with replacement, and goes through the same distances and the same neighbour joining.  "
@@ -472,6 +491,9 @@ def check_tree_args(args):
             raise SystemExit("tracs distance: --max-entries needs --tree-changes, which needs --tree (it bounds the rows of that file)")
         if args.tree_filter:
             raise SystemExit("tracs distance: --tree-filter needs --tree (it filters the changes on the branches of the tree that --tree builds)")
+        if args.tree_iterate is not None or args.tree_iterate_out is not None:
+            raise SystemExit("tracs distance: --tree-iterate needs --tree-filter, which needs --tree (it rebuilds the tree that --tree builds "
+                             "without the changes that --tree-filter drops)")
         if args.tree_filtered is not None:
             raise SystemExit("tracs distance: --tree-filtered needs --tree-filter, which needs --tree (it holds the tree with the kept changes "
                              "as branch lengths)")
@@ -514,6 +536,17 @@ def check_tree_args(args):
                              "each and join the two --tree-edges files on parent and child)" % opt)
     if args.tree_filtered is not None and not args.tree_filter:
         raise SystemExit("tracs distance: --tree-filtered needs --tree-filter (it holds the tree with the kept changes as branch lengths)")
+    if args.tree_iterate is None:
+        if args.tree_iterate_out is not None:
+            raise SystemExit("tracs distance: --tree-iterate-out needs --tree-iterate (it lists the trees that --tree-iterate builds)")
+    else:
+        if args.bootstrap is not None:
+            raise SystemExit("tracs distance: --tree-iterate and --bootstrap cannot be combined (the replicates would have to be drawn from "
+                             "the masked alignment of the final tree)")
+        if not args.tree_filter:
+            raise SystemExit("tracs distance: --tree-iterate needs --tree-filter (it masks the changes that --tree-filter drops)")
+        if not 1 <= args.tree_iterate <= 100:
+            raise SystemExit("tracs distance: --tree-iterate %d: the number of iterations must be in [1, 100]" % args.tree_iterate)
     if args.tree_filter and args.tree_edges is None and args.tree_changes is None and args.tree_filtered is None:
         raise SystemExit("tracs distance: --tree-filter needs --tree-edges, --tree-changes or --tree-filtered (the files its verdicts go to)")
     if args.max_entries is not None and args.tree_changes is None and not args.tree_filter:
@@ -527,6 +560,9 @@ def check_tree_args(args):
                        ["--bootstrap-trees"])
     if args.tree_filtered is not None:
         check_output_paths("distance", _inputs(args), dict(tree_outputs, **{"--tree-filtered": args.tree_filtered}), ["--tree-filtered"])
+    if args.tree_iterate_out is not None:
+        check_output_paths("distance", _inputs(args), dict(tree_outputs, **{"--tree-filtered": args.tree_filtered,
+                                                                            "--tree-iterate-out": args.tree_iterate_out}), ["--tree-iterate-out"])
 
 
 def tree_changes_on(args):
@@ -552,7 +588,8 @@ def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None, tree
                        bootstrap=args.bootstrap or 0, seed=1 if args.bootstrap_seed is None else args.bootstrap_seed,
                        replicate_trees=args.bootstrap_trees, support=args.bootstrap_support or "split", changes_path=args.tree_changes,
                        sites_path=args.tree_sites, max_entries=args.max_entries, contigs=tree_contigs, n_threads=args.n_cpu,
-                       create=not args.tree_files_made, tree_filter=args.tree_filter, filtered_path=args.tree_filtered)
+                       create=not args.tree_files_made, tree_filter=args.tree_filter, filtered_path=args.tree_filtered,
+                       **({} if args.tree_iterate is None else {"iterate": args.tree_iterate, "iterations_path": args.tree_iterate_out}))
         except RuntimeError as e:
             if not changes_on:                                              # (the plain and the bootstrap run pass the library's error on)
                 raise
@@ -564,8 +601,16 @@ def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None, tree
         if args.tree_filter:
             sys.stderr.write("tracs distance: %s: tree filter: %d changes, %d kept, %d dropped, %d branches with a drop\n"
                              % (ref, t.changes, t.kept, t.changes - t.kept, t.branches))
-            stage("[sum] tracs_distance_tree_filter (dense panels, joins, tree, Fitch count, edge lists, filter, fill: %d joins, %d edge rows, "
-                  "%d changes, %d kept)" % (t.joins, t.rows, t.changes, t.kept))
+            if args.tree_iterate is not None:
+                how = ("stopped at the limit" if t.same_as is None else "converged" if t.same_as == t.iterations - 1 else
+                       "cycle back to %d" % t.same_as)
+                sys.stderr.write("tracs distance: %s: tree iterate: %d trees built, %s; final tree: %d changes, %d kept, %d dropped\n"
+                                 % (ref, t.iterations + 1, how, t.changes, t.kept, t.changes - t.kept))
+                stage("[sum] tracs_distance_tree_iterate (%d trees: dense panels, joins, Fitch count, edge lists, filter, mask each; tree, fill: "
+                      "%d joins, %d edge rows, %d changes, %d kept)" % (t.iterations + 1, t.joins, t.rows, t.changes, t.kept))
+            else:
+                stage("[sum] tracs_distance_tree_filter (dense panels, joins, tree, Fitch count, edge lists, filter, fill: %d joins, %d edge rows, "
+                      "%d changes, %d kept)" % (t.joins, t.rows, t.changes, t.kept))
         elif changes_on:
             stage("[sum] tracs_distance_tree_changes (dense panels, joins, tree, Fitch count and fill: %d joins, %d edge rows, %d changes)"
                   % (t.joins, t.rows, t.changes))

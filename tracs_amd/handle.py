@@ -12,6 +12,9 @@ from . import _lib
 
 
 TreeResult = collections.namedtuple("TreeResult", "joins rows changes minimum kept branches")
+# tree(iterate=K): the same counters for the final tree, then the final k, the earlier tree it repeats (None: stopped at the limit),
+# the cells the last mask made N and the largest mask work W
+TreeIterateResult = collections.namedtuple("TreeIterateResult", TreeResult._fields + ("iterations", "same_as", "masked_cells", "mask_work"))
 
 OPEN_STAGE = "[sum] tracs_distance_open (read FASTA, allocate, H2D + pack)"      # the [stage] line of an open (TRACS_STAGE_TRACE)
 
@@ -131,12 +134,24 @@ class DistanceHandle:
 
     def tree(self, path, ref, per_site=False, edges_path=None, bootstrap=0, seed=1, replicate_trees=None, support="split",
              changes_path=None, sites_path=None, max_entries=None, contigs=None, n_threads=0, create=True, tree_filter=False,
-             filtered_path=None):
+             filtered_path=None, iterate=None, iterations_path=None):
         """The neighbour-joining tree of the handle's samples: the keywords as one tracs_tree_request (include/tracs_hip.h describes every
         field) -> TreeResult, 0 where nothing was asked for.  One Newick line is appended to `path`, the edge rows to
         edges_path.  bootstrap = B > 0: B replicates under `seed`, support "split" or "transfer", each replicate's line to replicate_trees.
         changes_path / sites_path / tree_filter (no bootstrap): every site placed on the tree, at most max_entries (default 10^8) changes,
-        contigs [(name, length)] or None; create: the library creates the files with their headers (False: it appends to them)."""
+        contigs [(name, length)] or None; create: the library creates the files with their headers (False: it appends to them).
+        iterate = K in [1, 100] (with tree_filter; tracs_distance_tree_iterate): the dropped changes are masked below
+        their branches, the tree rebuilt, until its splits repeat or K trees were rebuilt; every file is then the final tree's, and
+        iterations_path gets a row per tree -> TreeIterateResult."""
+        if iterate is None:
+            if iterations_path is not None:
+                raise ValueError("tree(): iterations_path needs iterate")
+        elif not tree_filter:
+            raise ValueError("tree(): iterate needs tree_filter")
+        elif bootstrap:
+            raise ValueError("tree(): iterate takes no bootstrap")
+        elif not 1 <= int(iterate) <= 100:
+            raise ValueError("tree(): iterate must be in [1, 100]")
         if support not in ("split", "transfer"):
             raise ValueError("tree(): support is 'split' or 'transfer'")
         if filtered_path is not None and not tree_filter:
@@ -173,6 +188,11 @@ class DistanceHandle:
             contig_lengths=(C.c_uint64 * len(contigs))(*[int(c[1]) for c in contigs]), n_contigs=len(contigs),
             max_entries=max_entries or 0, n_threads=int(n_threads), create=int(bool(create)))
         res = _lib.TreeResult()
+        if iterate is not None:
+            it, ires = _lib.TreeIterate(int(iterate), enc(iterations_path)), _lib.TreeIterateResult()
+            _lib.check(self.L.tracs_distance_tree_iterate(self.h, C.byref(req), C.byref(it), C.byref(res), C.byref(ires)))
+            return TreeIterateResult(*(getattr(res, name) for name, _ in res._fields_), ires.iterations,
+                                     ires.same_as if ires.same_as >= 0 else None, ires.masked_cells_last, ires.mask_work_max)
         _lib.check(self.L.tracs_distance_tree_run(self.h, C.byref(req), C.byref(res)))
         return TreeResult(*(getattr(res, name) for name, _ in res._fields_))
 
