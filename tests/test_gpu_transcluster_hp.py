@@ -1,7 +1,8 @@
 """Every transcluster route against tests/golden/transcluster_hp_golden.json (p0 and E(K) from the series' definition at 40
 digits, tests/hp_transcluster.py), at N up to 100 000, day gaps up to 9 000 and seven (lamb, beta, thr) sets.  Each call asserts the
 route it was meant to take (device.trans_routes): the array entry points, the dense block with linear (gap, M) tables, with tables
-in log space, without tables, the hash route (TRACS_TC_GRID=0, a child process) and the key split over three ranks on one GPU.
+in log space, without tables, the hash route (TRACS_TC_GRID=0, a child process), the key split over three ranks on one GPU and the
+key-table route (device.trans_dist_dense_partitioned) with three parts played in turn.
 
 Tolerances: p0 |d ln P| <= 1e-12 max(1, |ln P|).  E(K) of determined and saturated keys: relative <= max(1e-10, 4e-16 lgG(N +
 k_stop + 1)) -- the rounding of the reference formula's largest log term -- where the exact value is >= 1e-290, else <= 1e-290.
@@ -247,3 +248,22 @@ def test_key_split_matches_high_precision():
         ek[masks[q]] = eq[masks[q]]
     m = len(ks)
     _check("keysplit", ks, p0[0, 1:1 + m].cpu().numpy(), ek[0, 1:1 + m].cpu().numpy())
+
+
+def test_key_table_matches_high_precision():
+    """device.trans_dist_dense_partitioned (the key-table route of several ranks), three parts played one after the other
+    (tests/test_gpu_key_table.py: the all-reduce is the sum of the parts' tables) on the 'linear' block: every part's row 0 against
+    the fixture."""
+    import torch
+    from test_gpu_key_table import play_parts
+    from tracs_amd import device as dev
+    ks, (lamb, beta, thr), d, days = _dense_case("linear")
+    n, parts = d.shape[0], 3
+    dm, dy = torch.from_numpy(d).cuda(), torch.from_numpy(days).cuda()
+    got = play_parts(dev, dm, n, dy, lamb, beta, thr, parts, False, 2147483647, n)
+    # (keys / tables / linear describe all the parts' keys together: tests/test_gpu_key_table.py)
+    r = dev.trans_routes()
+    assert r["keys"] == _distinct("linear") and r["route"] == "hash" and r["tables"] and r["linear"], r
+    m = len(ks)
+    for p0, ek in got:
+        _check("keytable", ks, p0[0, 1:1 + m].cpu().numpy(), ek[0, 1:1 + m].cpu().numpy())
