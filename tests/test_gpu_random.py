@@ -91,9 +91,10 @@ def _has_partial(seqs):
 
 
 def test_matrix_core_kernel_extremes(hiplib, oracle):
-    """The consensus pass accumulates S = 4 * matches - nn and nn in fp32 matrix-core accumulators.  Push both to their extremes
-    over a range longer than one exact chunk (2^22 sites, so the host must split it): samples that differ at EVERY site
-    (S = -nn = -L), that agree everywhere (S = 3 L), that share no compared site, and patterned ones."""
+    """The consensus pass accumulates S = 4 * matches - nn and nn in fp32 matrix-core accumulators.  Push both to their VALUE
+    extremes: samples that differ at EVERY site (S = -nn = -L), that agree everywhere (S = 3 L), that share no compared site, and
+    patterned ones.  This does not test the host's exact-range bound: at L = 2^22 + 70 003 the largest sum, 3 L ~ 12.8 M, stays below
+    2^24 even in one unsplit range -- tests/test_gpu_exact_range.py has the inputs whose sums pass 2^24."""
     import torch
     from tracs_amd import device as dev
     L = (1 << 22) + 70003

@@ -1042,11 +1042,12 @@ static int stage_split(int range, int k, int gc, int *gps)
     *gps = ((range + k - 1) / k + gc - 1) / gc * gc;
     return (range + *gps - 1) / *gps;
 }
-// two-pass thresholded run: groups of the prefix pass (1/8 of them, whole stages), ...
+// two-pass thresholded run: groups of the prefix pass (1/8 of them, whole stages), ...  The prefix is ONE range per tile: a forced
+// value is held to max_gps like the default
 static int thr_prefix_groups(int groups, int gc, int max_gps)
 {
     const int v = dense_switch::thr_prefix() / gc * gc;
-    return (v >= gc && v < groups) ? v : std::min(max_gps / gc * gc, std::max(8 * gc, groups / 8 / gc * gc));
+    return std::min(max_gps / gc * gc, (v >= gc && v < groups) ? v : std::max(8 * gc, groups / 8 / gc * gc));
 }
 // ... and ranges of the remainder pass over the `rest`: ~4 rounds of the chip, never more than 32 ranges (each costs one atomic per cell)
 static int thr_remainder_split(int rest, int gc, int max_gps, double slots, unsigned n_live, int *gps)
