@@ -406,6 +406,26 @@ int tracs_nj_edges(size_t n, const uint32_t *a, const uint32_t *b, const double 
                    const uint32_t *last_ids, const double *last_d, uint32_t *parent, uint32_t *child, double *length, size_t *n_edges);
 int tracs_tree_write(const char *const *names, size_t n, const uint32_t *parent, const uint32_t *child, const double *length,
                      size_t n_edges, const char *path, const char *ref, const char *edges_path);
+/* BIONJ (Gascuel 1997; csrc/nj.hip): neighbour joining with a second matrix V of variances (V = D and RV = R at the
+ * start, bit for bit) that weights every reduction.  Q, the tie rule, the record (a, b, D_ab, R_a, R_b; a the LOWER ID), the lengths,
+ * the three-node end and n <= 3 are neighbour joining's; with r active nodes and one rounding per operation, bracketed as written:
+ *   l_a = (0.5 D_ab) + ((R_a - R_b) / (2 (r - 2))), l_b = D_ab - l_a              (tracs_nj_edges's own operations)
+ *   lambda = 0.5 if V_ab == 0, else 0.5 + ((RV_b - RV_a) / ((2 (r - 2)) V_ab)) clamped to [0, 1]; mu = 1 - lambda
+ *   D_uk = (lambda (D_ak - l_a)) + (mu (D_bk - l_b));    V_uk = ((lambda V_ak) + (mu V_bk)) - ((lambda mu) V_ab)
+ *   R_k <- (R_k - (D_ak + D_bk)) + D_uk;                 RV_k <- (RV_k - (V_ak + V_bk)) + V_uk
+ *   R_u = (lambda ((R_a - D_ab) - ((r - 2) l_a))) + (mu ((R_b - D_ab) - ((r - 2) l_b)))
+ *   RV_u = ((lambda (RV_a - V_ab)) + (mu (RV_b - V_ab))) - ((r - 2) ((lambda mu) V_ab))
+ * RV_b - RV_a is Gascuel's sum over k of V_bk - V_ak (zero diagonal, symmetric V): no order-dependent reduction.  mu is rounded, so
+ * the formulas are not symmetric in a and b.  Nothing is clamped but lambda: D, V and lengths may go negative.
+ *   tracs_bionj_state_bytes  the bytes of a BIONJ state (0: n is above 2^24): a neighbour-joining state followed by V, RV and two
+ *                            scratch rows, about 2 n^2 doubles.  A state does not record its size: as with every state of this
+ *                            library the caller allocates what the method asks for.  tracs_nj_init, tracs_nj_load_panel,
+ *                            tracs_nj_load_f64, tracs_nj_emit and tracs_nj_edges serve both methods (they touch the common prefix
+ *                            only), and tracs_nj_run on a BIONJ-sized state runs neighbour joining.
+ *   tracs_bionj_run          tracs_nj_run's contract with the BIONJ reduction: three stream-ordered launches per join, no
+ *                            read-back.  The state MUST have tracs_bionj_state_bytes(n) bytes.                                     */
+size_t tracs_bionj_state_bytes(size_t n);
+int tracs_bionj_run(void *state, size_t n, void *stream);
 
 /*   tracs_tree_write_changes  tracs_tree_write with a number of changes per edge (uint32[n_edges]): the Newick line is
  *                        tracs_tree_write's, byte for byte; the edge rows are parent,child,length,changes,ref.                  */
@@ -864,9 +884,15 @@ int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, d
  *                         changes as branch lengths (tracs_tree_write).
  *                         The result: n_joins: n - 3; rows_written: the edge rows; n_changes: the tree's parsimony length;
  *                         sum_minimum: the sum of `minimum` over the sites with a change; n_kept: the changes kept in all;
- *                         n_edges_dropped: the edges with a dropped change.  What was not asked for is 0.                        */
+ *                         n_edges_dropped: the edges with a dropped change.  What was not asked for is 0.
+ *                         kind | TRACS_TREE_BIONJ (kinds 2 and 3; `--tree bionj`): every tree of the request -- the
+ *                         main tree, each bootstrap replicate, each rebuild of tracs_distance_tree_iterate -- is the BIONJ tree
+ *                         (tracs_bionj_run on a state of tracs_bionj_state_bytes) of the same distances; everything else reads
+ *                         the same 2n - 3 edges.  Kind 3 with replicates is refused as kind 1 is; any other kind is refused.  The
+ *                         five entry points below and tracs_distance_tree_iterate pass kind through.                             */
+#define TRACS_TREE_BIONJ 2             /* bit 1 of tracs_tree_request.kind: the BIONJ tree (tracs_bionj_run) instead of neighbour joining */
 typedef struct tracs_tree_request {
-    int kind;                          /* 0 snp, 1 per-site */
+    int kind;                          /* bit 0: 0 snp, 1 per-site; bit 1: TRACS_TREE_BIONJ */
     const char *path, *ref, *edges_path;
     uint32_t replicates;               /* 0: no bootstrap */
     uint64_t seed;

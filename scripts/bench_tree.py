@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""The neighbour-joining tree on bench.py's workload.  Prints one JSON line; --out FILE also writes it there.
+"""The neighbour-joining tree on bench.py's workload, or with --method bionj the BIONJ tree.  Prints
+one JSON line; --out FILE also writes it there.
 
-    python scripts/bench_tree.py [--samples 10000] [--sites 5000000] [--steps 3] [--warmup 1] [--workload sparse] [--per-site]
-    python scripts/bench_tree.py --cli [--samples 10000] [--sites 20000]      # `tracs distance --tree nj`, the entry point itself
+    python scripts/bench_tree.py [--samples 10000] [--sites 5000000] [--steps 3] [--warmup 1] [--workload sparse] [--per-site] [--method nj]
+    python scripts/bench_tree.py --cli [--samples 10000] [--sites 20000] [--method nj]      # `tracs distance --tree METHOD`, the entry point itself
 
 The alignment is synthesised on the device (synth.pack_synthetic_device, as bench.py does), then each call runs what
 tracs_distance_tree runs: row panels of tracs_pairsnp_dense_thr without a threshold (~1 GiB per matrix) -> tracs_nj_load_panel ->
@@ -43,7 +44,7 @@ def cli(args):
         del seqs
         nwk, edges = os.path.join(tmp, "t.nwk"), os.path.join(tmp, "e.csv")
         t0 = time.perf_counter()
-        rc = subprocess.run([sys.executable, "-m", "tracs_amd", "distance", "--msa", fa, "--tree", "nj", "-o", nwk, "--tree-edges", edges,
+        rc = subprocess.run([sys.executable, "-m", "tracs_amd", "distance", "--msa", fa, "--tree", args.method, "-o", nwk, "--tree-edges", edges,
                              "--loglevel", "ERROR"], cwd=ROOT, capture_output=True, text=True, env=dict(os.environ, TRACS_STAGE_TRACE="1"))
         dt = time.perf_counter() - t0
         if rc.returncode != 0:
@@ -59,7 +60,7 @@ def cli(args):
         import hashlib
         with open(nwk, "rb") as fh:
             digest = hashlib.sha256(fh.read()).hexdigest()
-        out = dict(metric="tree_cli_s", value=dt, unit="s", higher_is_better=False, n=n, L=L, stages_s=stages, edge_rows=rows,
+        out = dict(metric="tree_cli_s", value=dt, unit="s", higher_is_better=False, n=n, L=L, method=args.method, stages_s=stages, edge_rows=rows,
                    panel_rows=os.environ.get("TRACS_FOREST_PANEL_ROWS"), newick_bytes=os.path.getsize(nwk),
                    edges_bytes=os.path.getsize(edges), newick_sha256=digest)
         line = json.dumps(out)
@@ -82,6 +83,7 @@ def main():
     ap.add_argument("--per-site", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--cli", action="store_true")
+    ap.add_argument("--method", choices=["nj", "bionj"], default="nj")
     args = ap.parse_args()
     if args.cli:
         return cli(args)
@@ -102,18 +104,19 @@ def main():
     names = ["sample_%05d" % i for i in range(n)]
     cnames = (C.c_char_p * n)(*[x.encode() for x in names])
     lib = _lib.load()
+    state_bytes = (lib.tracs_bionj_state_bytes if args.method == "bionj" else lib.tracs_nj_state_bytes)(n)
     tmp = tempfile.mkdtemp(prefix="tracs_tree_")
 
     def call():
         t = [time.perf_counter()]
-        state = dev.nj_init(n)
+        state = dev.nj_init(n, method=args.method)
         for r0 in range(0, n, panel):
             r1 = min(n, r0 + panel)
             dev.pairsnp_dense(aln, d, nn, row_begin=r0, row_end=r1, dist_threshold=2147483647, base_row=r0)
             dev.nj_load_panel(state, n, d, nn, row_begin=r0, row_end=r1, per_site=args.per_site, base_row=r0)
         torch.cuda.synchronize()
         t.append(time.perf_counter())
-        dev.nj_run(state, n)
+        (dev.bionj_run if args.method == "bionj" else dev.nj_run)(state, n)
         torch.cuda.synchronize()
         t.append(time.perf_counter())
         parent, child, length = dev.nj_edges(n, *dev.nj_emit(state, n))
@@ -136,8 +139,8 @@ def main():
     total = np.median(stages.sum(axis=1))
     floor_bytes = sum(r * (r - 1) // 2 * 8 for r in range(4, n + 1))
     floor_s = floor_bytes / STREAM_BYTES_PER_S
-    out = dict(metric="tree_call_s", value=float(total), unit="s", higher_is_better=False, n=n, L=L, workload=args.workload,
-               per_site=bool(args.per_site), steps=args.steps, warmup=args.warmup, panel_rows=panel,
+    out = dict(metric="tree_call_s", value=float(total), unit="s", higher_is_better=False, n=n, L=L, workload=args.workload, method=args.method,
+               state_bytes=int(state_bytes), per_site=bool(args.per_site), steps=args.steps, warmup=args.warmup, panel_rows=panel,
                dense_panels_and_load_s=float(med[0]), join_loop_s=float(med[1]), emit_and_write_s=float(med[2]),
                stage_s=[[float(x) for x in row] for row in stages], joins=max(n - 3, 0), launches=3 * max(n - 3, 0) + 2,
                scan_floor_bytes=floor_bytes, stream_bytes_per_s=STREAM_BYTES_PER_S, scan_floor_s=floor_s,

@@ -51,7 +51,7 @@ SYMBOLS = [
     "tracs_distance_histogram", "tracs_hist_state_bytes", "tracs_hist_init", "tracs_hist_update", "tracs_hist_update_coo", "tracs_hist_emit",
     "tracs_distance_ancestors", "tracs_anc_state_bytes", "tracs_anc_init", "tracs_anc_update_coo", "tracs_anc_emit",
     "tracs_distance_tree", "tracs_nj_state_bytes", "tracs_nj_init", "tracs_nj_load_panel", "tracs_nj_load_f64", "tracs_nj_run",
-    "tracs_nj_emit", "tracs_nj_edges", "tracs_tree_write",
+    "tracs_nj_emit", "tracs_nj_edges", "tracs_tree_write", "tracs_bionj_state_bytes", "tracs_bionj_run",
     "tracs_bootstrap_weights", "tracs_alignment_gather_sites", "tracs_tree_support", "tracs_tree_write_support",
     "tracs_distance_tree_bootstrap",
     "tracs_tree_transfer_program", "tracs_transfer_state_bytes", "tracs_transfer_init", "tracs_transfer_add", "tracs_transfer_emit",
@@ -67,6 +67,9 @@ class Rules(C.Structure):
     """tracs_rules (include/tracs_hip.h): shares < 0, min_sites = 0 and max_n_samples = 2^32 - 1 mean no rule"""
     _fields_ = [("keep", C.POINTER(C.c_uint64)), ("keep_len", C.c_size_t), ("max_n_share", C.c_double),
                 ("max_sample_n_share", C.c_double), ("min_sites", C.c_uint32), ("max_n_samples", C.c_uint32)]
+
+
+TREE_BIONJ = 2          # TRACS_TREE_BIONJ (include/tracs_hip.h): bit 1 of TreeRequest.kind
 
 
 class TreeRequest(C.Structure):
@@ -256,6 +259,10 @@ def load():
     L.tracs_nj_load_f64.argtypes = [vp, sz, vp, sz, vp]
     L.tracs_nj_run.restype = C.c_int
     L.tracs_nj_run.argtypes = [vp, sz, vp]
+    L.tracs_bionj_state_bytes.restype = sz
+    L.tracs_bionj_state_bytes.argtypes = [sz]
+    L.tracs_bionj_run.restype = C.c_int
+    L.tracs_bionj_run.argtypes = [vp, sz, vp]
     L.tracs_nj_emit.restype = C.c_int
     L.tracs_nj_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tracs_nj_edges.restype = C.c_int

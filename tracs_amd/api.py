@@ -108,13 +108,16 @@ def distance_histogram(fasta, dist=2147483647, filter=False, groups=None, sites=
     return names, out
 
 
-def neighbor_joining(D):
-    """The neighbour-joining tree of a symmetric distance matrix (tracs_nj_*): D is a host array or a torch tensor
+def neighbor_joining(D, method="nj"):
+    """The neighbour-joining tree of a symmetric distance matrix (tracs_nj_*), or with method="bionj" its BIONJ tree
+    (tracs_bionj_run: the same edges' shape, the reductions weighted by variance): D is a host array or a torch tensor
     (host or device), n x n, finite, non-negative, symmetric with a zero diagonal (else ValueError).  -> parent, child (uint32) and
     length (float64): the 2n - 3 edges in creation order.  Leaves are 0 .. n - 1, join number t makes the node n + t, the last node
     (2n - 3) joins the remaining three; n = 2: the one edge (0, 1, D_01).  Negative lengths are returned as computed."""
     import torch
     from . import device as dev
+    if method not in dev.TREE_METHODS:
+        raise ValueError("neighbor_joining(): method is 'nj' or 'bionj'")
     _lib.require_gpu()
     M = D if isinstance(D, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(D, dtype=np.float64)))
     if M.dim() != 2 or M.shape[0] != M.shape[1]:
@@ -130,10 +133,10 @@ def neighbor_joining(D):
             raise ValueError("neighbor_joining(): D has a non-zero diagonal entry")
         if not bool((M == M.t()).all()):
             raise ValueError("neighbor_joining(): D is not symmetric")
-    state = dev.nj_init(n)
+    state = dev.nj_init(n, method=method)
     if n >= 2:
         dev.nj_load_f64(state, n, M)
-    dev.nj_run(state, n)
+    (dev.bionj_run if method == "bionj" else dev.nj_run)(state, n)
     return dev.nj_edges(n, *dev.nj_emit(state, n))
 
 

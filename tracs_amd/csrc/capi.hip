@@ -1236,17 +1236,19 @@ struct TreeEdges {
 // One tree: the panel walk without a threshold and without the pair rule (every pair has a distance), each dense panel loaded into the
 // neighbour-joining state (about n^2 x 8 bytes; the first tree of a call allocates both), the joins on the device, the lengths on the host.
 // a == NULL: the zero matrix (a replicate that drew no differing column); acc: NULL (the main tree: stages marked), or the replicates' sums
+// kind: the request's -- bit 0 the distance, TRACS_TREE_BIONJ the method, whose state (about 2 n^2 x 8 bytes) and join loop then run
 int tree_of_alignment(tracs_alignment *a, const char *const *names, int kind, PanelWalk &walk, DeviceBuffer &d_state, StageClock &clock, double *acc, TreeEdges &t)
 {
     int rc;
     const size_t n = walk.n;
+    const bool bionj = (kind & TRACS_TREE_BIONJ) != 0;
     std::vector<uint32_t> ja, jb;
     std::vector<double> jd, jra, jrb;
     uint32_t last_ids[3] = {0, n > 1 ? 1u : 0xFFFFFFFFu, 0xFFFFFFFFu};      // (n < 2: no pair exists, nothing runs on the device)
     double last_d[3] = {0.0, 0.0, 0.0};
     t.nj = t.ne = 0;
     if (walk.any()) {
-        if (!d_state.ptr && (rc = d_state.alloc(tracs_nj_state_bytes(n)))) return rc;
+        if (!d_state.ptr && (rc = d_state.alloc(bionj ? tracs_bionj_state_bytes(n) : tracs_nj_state_bytes(n)))) return rc;
         void *const state = d_state.ptr;
         if ((rc = tracs_nj_init(state, n, nullptr))) return rc;
         if (a) {
@@ -1254,14 +1256,14 @@ int tree_of_alignment(tracs_alignment *a, const char *const *names, int kind, Pa
             walk.at = 0;
             if (!walk.height && (rc = walk.begin(false, false))) return rc;
             for (Panel pn; walk.more();) {
-                if ((rc = walk.next(pn)) || (rc = tracs_nj_load_panel(state, n, pn.bd, pn.bn, n, pn.r0, pn.r1, kind, nullptr))) return rc;
+                if ((rc = walk.next(pn)) || (rc = tracs_nj_load_panel(state, n, pn.bd, pn.bn, n, pn.r0, pn.r1, kind & 1, nullptr))) return rc;
             }
         }
         if (acc) lap(clock, acc[0]); else clock.mark("dense panels + matrix load");
-        if ((rc = tracs_nj_run(state, n, nullptr))) return rc;
+        if ((rc = bionj ? tracs_bionj_run(state, n, nullptr) : tracs_nj_run(state, n, nullptr))) return rc;
         TRACS_HIP_CHECK(hipDeviceSynchronize());
         if (g_sigint) return interrupted();
-        if (acc) lap(clock, acc[1]); else clock.mark("join loop");
+        if (acc) lap(clock, acc[1]); else clock.mark(bionj ? "join loop (bionj)" : "join loop");
         ja.resize(n); jb.resize(n); jd.resize(n); jra.resize(n); jrb.resize(n);
         uint32_t zero[2];
         rc = tracs_nj_emit(state, n, &t.nj, ja.data(), jb.data(), jd.data(), jra.data(), jrb.data(), last_ids, last_d, zero, nullptr);
@@ -1334,7 +1336,7 @@ int tree_bootstrap_stage(tracs_distance *h, const tracs_tree_request &r, const T
             rep.reset(ra);
         }
         lap(clock, acc[0]);
-        if ((rc = tree_of_alignment(rep.get(), names, 0, walk, d_state, clock, acc + 1, rep_t))) return rc;
+        if ((rc = tree_of_alignment(rep.get(), names, r.kind, walk, d_state, clock, acc + 1, rep_t))) return rc;
         if ((rc = tracs_tree_support(n, t.parent.data(), t.child.data(), t.ne, rep_t.parent.data(), rep_t.child.data(), rep_t.ne, s.support.data()))) return rc;
         if (r.replicate_trees_path && (rc = tracs_tree_write(names, n, rep_t.parent.data(), rep_t.child.data(), rep_t.length.data(), rep_t.ne,
                                                              r.replicate_trees_path, r.ref, nullptr))) return rc;
@@ -1352,7 +1354,7 @@ int tree_bootstrap_stage(tracs_distance *h, const tracs_tree_request &r, const T
         std::fprintf(stderr, "[stage] bootstrap: %u replicates over %zu differing columns\n", (unsigned)r.replicates, V);
         std::fprintf(stderr, "[stage] replicates: weights + scan + gather %.4f s\n", acc[0]);
         std::fprintf(stderr, "[stage] replicates: dense panels + matrix load %.4f s\n", acc[1]);
-        std::fprintf(stderr, "[stage] replicates: join loop %.4f s\n", acc[2]);
+        std::fprintf(stderr, "[stage] replicates: join loop%s %.4f s\n", (r.kind & TRACS_TREE_BIONJ) ? " (bionj)" : "", acc[2]);
         std::fprintf(stderr, "[stage] replicates: emit, lengths, support %.4f s\n", acc[3]);
         if (transfer)
             std::fprintf(stderr, "[stage] replicates: transfer distances %.4f s (program %.4f s, kernel %.4f s)\n", acc[4] + acc[5], acc[4], acc[5]);
@@ -1494,7 +1496,7 @@ int tree_iterate_stage(tracs_distance *h, const tracs_tree_request &r, const tra
         std::fprintf(stderr, "[stage] iterations: clone / restore %.4f s\n", acc[2]);
         std::fprintf(stderr, "[stage] iterations: mask %.4f s (largest W %llu)\n", acc[3], (unsigned long long)ires.mask_work_max);
         std::fprintf(stderr, "[stage] iterations: dense panels + matrix load %.4f s\n", acc[0]);
-        std::fprintf(stderr, "[stage] iterations: join loop %.4f s\n", acc[1]);
+        std::fprintf(stderr, "[stage] iterations: join loop%s %.4f s\n", (r.kind & TRACS_TREE_BIONJ) ? " (bionj)" : "", acc[1]);
     }
     return TRACS_OK;
 }
@@ -1517,13 +1519,14 @@ int tree_run(const std::string &who, tracs_distance *h, const tracs_tree_request
     }
     if (it && (!r.filter || boot)) { set_error(who + ": the iteration needs the branch filter (filter != 0) and takes no replicates"); return TRACS_E_ARG; }
     if (it && (it->max_iterations < 1 || it->max_iterations > 100)) { set_error(who + ": max_iterations must be in [1, 100]"); return TRACS_E_ARG; }
-    if (boot && r.kind != 0) { set_error(who + ": bootstrap replicates take the SNP distance (kind 0) only"); return TRACS_E_ARG; }
-    if (r.kind != 0 && r.kind != 1) { set_error(who + ": kind must be 0 (snp) or 1 (per-site)"); return TRACS_E_ARG; }
+    if (boot && (r.kind & ~TRACS_TREE_BIONJ) != 0) { set_error(who + ": bootstrap replicates take the SNP distance (kind 0) only"); return TRACS_E_ARG; }
+    if (r.kind < 0 || r.kind > (1 | TRACS_TREE_BIONJ)) { set_error(who + ": kind must be 0 (snp) or 1 (per-site)"); return TRACS_E_ARG; }
     if (boot && r.replicates < 1) { set_error(who + ": at least one replicate"); return TRACS_E_ARG; }
     if (h->n_fasta != 1) { set_error(who + ": a tree joins the samples of one alignment"); return TRACS_E_ARG; }
     SigintScope sigint;
     const size_t n = h->a->n;
     const char *const *names = h->name_ptr.data();
+    // (the BIONJ state has the same limit)
     if (n && !tracs_nj_state_bytes(n)) { set_error(who + ": too many samples for one distance matrix"); return TRACS_E_ARG; }
     if (boot && h->a->L >= 0xFFFFFFFFull) { set_error(who + ": too many columns"); return TRACS_E_ARG; }
     StageClock clock;

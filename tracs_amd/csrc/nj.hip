@@ -17,6 +17,15 @@
 // so no launch reads a cell of D that the same launch writes.  The formulas are symmetric in a and b and the order is on node ids:
 // the result depends on neither the slot layout nor the move.  The host knows r at every step: the whole loop is enqueued without
 // a read-back.
+//
+// BIONJ (Gascuel 1997; tracs_bionj_*, DESIGN.md 3.23, restated in tests/bionj_ref.py) is the same loop with a second matrix V of
+// variances (V = D at the start) and its running row sums RV: the scan, the record and the three-node end are neighbour joining's, and
+// the reduction weights the rows of a and b with the lambda that minimises the variance of the new row.  Gascuel's sum over k of
+// V_bk - V_ak is RV_b - RV_a (the diagonal is 0 and V is symmetric, so the cells of a and b cancel): no order-dependent reduction and
+// no further kernel.  lambda, mu = 1 - lambda, the two lengths and the new node's two sums are computed ONCE per join, by the thread
+// that writes the record, and travel in the header; the rows kernel writes the scratch rows of both matrices, the commit kernel both
+// matrices.  mu is rounded, so the formulas are NOT symmetric in a and b: a is the lower id (hdr->sa), never the lower slot.
+// A BIONJ state is a neighbour-joining state followed by V, RV and V's two scratch rows: every other entry point sees the prefix.
 #include "common.h"
 #include "pair_select.h"
 
@@ -39,6 +48,8 @@ struct Hdr {
     unsigned sa, sb;                // the winning slots of the last scan (sa holds the lower id)
     unsigned last_ids[3];           // the last three nodes, by id (n = 2: the two leaves)
     double last_d[3];               // D_xy, D_xz, D_yz (n = 2: D_01)
+    // BIONJ, the running join: lambda, mu, l_a, l_b, (lambda mu) V_ab, and the sums R_u, RV_u of the new node
+    double lam, mu, la, lb, lmv, ru, rvu;
 };
 
 struct State {
@@ -48,7 +59,8 @@ struct State {
     unsigned *rec_a, *rec_b;
     double *rec_d, *rec_ra, *rec_rb;
     unsigned long long *pq, *pids, *pslots;
-    State(void *base, size_t n, size_t *bytes = nullptr)
+    double *V = nullptr, *RV = nullptr, *vurow = nullptr, *vlrow = nullptr;      // BIONJ only, after everything else
+    State(void *base, size_t n, size_t *bytes = nullptr, bool bionj = false)
     {
         const size_t cap = std::max<size_t>(n, 1);
         Arena a(base, bytes);
@@ -60,6 +72,10 @@ struct State {
         rec_d = a.take<double>(cap); rec_ra = a.take<double>(cap); rec_rb = a.take<double>(cap);
         pq = a.take<unsigned long long>(NJ_SCAN_BLOCKS); pids = a.take<unsigned long long>(NJ_SCAN_BLOCKS);
         pslots = a.take<unsigned long long>(NJ_SCAN_BLOCKS);
+        if (bionj) {
+            V = a.take<double>(cap * cap);
+            RV = a.take<double>(cap); vurow = a.take<double>(cap); vlrow = a.take<double>(cap);
+        }
     }
 };
 
@@ -149,6 +165,30 @@ __device__ __forceinline__ Cand block_best(Cand c, Cand *sh)
 // tiles are interleaved over the grid.  t: the join's number.
 constexpr unsigned NJ_TILE = 2048;
 
+// BIONJ: what one join needs besides its record, from the record's own values (a = the lower id, in slot sa), one rounding per
+// operation, in the order tests/bionj_ref.py fixes.  The lengths are tracs_nj_edges's formula with the same operations.
+__device__ __forceinline__ void bionj_scalars(const State &s, size_t n, unsigned r, unsigned sa, unsigned sb)
+{
+    Hdr *h = s.hdr;
+    const double rm2 = (double)(r - 2), den = 2.0 * rm2;
+    const double d = s.D[(size_t)sa * n + sb], v = s.V[(size_t)sa * n + sb];
+    const double Ra = s.R[sa], Rb = s.R[sb], RVa = s.RV[sa], RVb = s.RV[sb];
+    const double la = (0.5 * d) + ((Ra - Rb) / den);
+    const double lb = d - la;
+    double lam = 0.5;
+    if (v != 0.0) {
+        lam = 0.5 + ((RVb - RVa) / (den * v));
+        if (lam < 0.0) lam = 0.0;
+        if (lam > 1.0) lam = 1.0;
+    }
+    const double mu = 1.0 - lam;
+    const double lmv = (lam * mu) * v;
+    h->lam = lam; h->mu = mu; h->la = la; h->lb = lb; h->lmv = lmv;
+    h->ru = (lam * ((Ra - d) - (rm2 * la))) + (mu * ((Rb - d) - (rm2 * lb)));
+    h->rvu = ((lam * (RVa - v)) + (mu * (RVb - v))) - (rm2 * lmv);
+}
+
+template <bool BIONJ>
 __global__ __launch_bounds__(256) void nj_scan_kernel(State s, size_t n, unsigned r, unsigned t)
 {
     __shared__ Cand sh[4];
@@ -210,6 +250,7 @@ __global__ __launch_bounds__(256) void nj_scan_kernel(State s, size_t n, unsigne
         s.hdr->sa = sa; s.hdr->sb = sb;
         s.rec_a[t] = s.ids[sa]; s.rec_b[t] = s.ids[sb];
         s.rec_d[t] = s.D[(size_t)sa * n + sb]; s.rec_ra[t] = s.R[sa]; s.rec_rb[t] = s.R[sb];
+        if (BIONJ) bionj_scalars(s, n, r, sa, sb);
         __hip_atomic_store(&s.hdr->counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
@@ -235,20 +276,51 @@ __global__ __launch_bounds__(256) void nj_rows_kernel(State s, size_t n, unsigne
     s.R[k == last ? ret : k] = (s.R[k] - sum) + duk;
 }
 
+// BIONJ's rows: the same slots, both matrices, the scalars of the join from the header
+__global__ __launch_bounds__(256) void bionj_rows_kernel(State s, size_t n, unsigned r)
+{
+    const unsigned k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= r) return;
+    const Hdr *h = s.hdr;
+    const unsigned sa = h->sa, sb = h->sb, keep = sa < sb ? sa : sb, ret = sa < sb ? sb : sa, last = r - 1;
+    s.lrow[k] = s.D[(size_t)last * n + k];
+    s.vlrow[k] = s.V[(size_t)last * n + k];
+    if (k == keep) { s.R[keep] = h->ru; s.RV[keep] = h->rvu; return; }
+    if (k == ret) return;
+    const double lam = h->lam, mu = h->mu;
+    const double dak = s.D[(size_t)sa * n + k], dbk = s.D[(size_t)sb * n + k], vak = s.V[(size_t)sa * n + k], vbk = s.V[(size_t)sb * n + k];
+    const double duk = (lam * (dak - h->la)) + (mu * (dbk - h->lb));
+    const double vuk = ((lam * vak) + (mu * vbk)) - h->lmv;
+    s.urow[k] = duk;
+    s.vurow[k] = vuk;
+    const unsigned to = k == last ? ret : k;
+    s.R[to] = (s.R[k] - (dak + dbk)) + duk;
+    s.RV[to] = (s.RV[k] - (vak + vbk)) + vuk;
+}
+
+// slot j of the new, (r - 1) x (r - 1) block of one matrix M from its two scratch rows
+__device__ __forceinline__ void commit_cells(double *M, const double *urow, const double *lrow, size_t n, unsigned j, unsigned keep, unsigned ret,
+                                             unsigned last)
+{
+    const bool inner = j != keep && j != ret;                        // the column cells of keep and ret are their rows' cells
+    const double uv = j == keep ? 0.0 : urow[j == ret ? last : j];
+    M[(size_t)keep * n + j] = uv;
+    if (inner) M[(size_t)j * n + keep] = uv;
+    if (ret != last) {
+        const double mv = j == ret ? 0.0 : j == keep ? urow[last] : lrow[j];
+        M[(size_t)ret * n + j] = mv;
+        if (inner) M[(size_t)j * n + ret] = mv;
+    }
+}
+
+template <bool BIONJ>
 __global__ __launch_bounds__(256) void nj_commit_kernel(State s, size_t n, unsigned r, unsigned t)
 {
     const unsigned j = blockIdx.x * 256 + threadIdx.x;              // a slot of the new, (r - 1) x (r - 1) block
     if (j + 1 >= r) return;
     const unsigned sa = s.hdr->sa, sb = s.hdr->sb, keep = sa < sb ? sa : sb, ret = sa < sb ? sb : sa, last = r - 1;
-    const bool inner = j != keep && j != ret;                        // the column cells of keep and ret are their rows' cells
-    const double uv = j == keep ? 0.0 : s.urow[j == ret ? last : j];
-    s.D[(size_t)keep * n + j] = uv;
-    if (inner) s.D[(size_t)j * n + keep] = uv;
-    if (ret != last) {
-        const double mv = j == ret ? 0.0 : j == keep ? s.urow[last] : s.lrow[j];
-        s.D[(size_t)ret * n + j] = mv;
-        if (inner) s.D[(size_t)j * n + ret] = mv;
-    }
+    commit_cells(s.D, s.urow, s.lrow, n, j, keep, ret, last);
+    if (BIONJ) commit_cells(s.V, s.vurow, s.vlrow, n, j, keep, ret, last);
     if (j == 0) {
         const unsigned moved = s.ids[last];
         s.ids[keep] = (unsigned)n + t;
@@ -292,6 +364,45 @@ static int load_cells(const char *who, void *state, size_t n, const void *src, c
     return TRACS_OK;
 }
 
+// The row sums and the n - 3 joins, enqueued.  bionj: the state has tracs_bionj_state_bytes(n) bytes (the caller's word, as the size of
+// every state is); V <- D and RV <- R are two device copies, bit for bit, before the first scan.
+static int run_joins(const char *who, void *state, size_t n, bool bionj, hipStream_t stream)
+{
+    if (!state) { set_error(std::string(who) + ": NULL state"); return TRACS_E_ARG; }
+    if (n > NJ_MAX_NODES) { set_error(std::string(who) + ": more than 2^24 leaves"); return TRACS_E_ARG; }
+    DeviceCall guard(stream);
+    State s(state, n, nullptr, bionj);
+    Hdr h{};
+    int rc;
+    if ((rc = read_state_header(s.hdr, n, who, stream, &h))) return rc;
+    if (h.ran) { set_error(std::string(who) + ": the state has been run; initialise and load it again"); return TRACS_E_ARG; }
+    if (n == 0) return TRACS_OK;
+    hipLaunchKernelGGL(nj_rowsum_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, s, n);
+    TRACS_HIP_CHECK(hipGetLastError());
+    if (bionj && n > 3) {
+        TRACS_HIP_CHECK(hipMemcpyAsync(s.V, s.D, n * n * 8, hipMemcpyDeviceToDevice, stream));
+        TRACS_HIP_CHECK(hipMemcpyAsync(s.RV, s.R, n * 8, hipMemcpyDeviceToDevice, stream));
+    }
+    for (size_t r = n; r > 3; r--) {
+        const unsigned t = (unsigned)(n - r), blocks = (unsigned)((r + 255) / 256);
+        const size_t tiles = (r / 2) * ((r + NJ_TILE - 1) / NJ_TILE);
+        const dim3 scan_grid((unsigned)std::min<size_t>(tiles, NJ_SCAN_BLOCKS));
+        if (bionj) {
+            hipLaunchKernelGGL(nj_scan_kernel<true>, scan_grid, dim3(256), 0, stream, s, n, (unsigned)r, t);
+            hipLaunchKernelGGL(bionj_rows_kernel, dim3(blocks), dim3(256), 0, stream, s, n, (unsigned)r);
+            hipLaunchKernelGGL(nj_commit_kernel<true>, dim3(blocks), dim3(256), 0, stream, s, n, (unsigned)r, t);
+        } else {
+            hipLaunchKernelGGL(nj_scan_kernel<false>, scan_grid, dim3(256), 0, stream, s, n, (unsigned)r, t);
+            hipLaunchKernelGGL(nj_rows_kernel, dim3(blocks), dim3(256), 0, stream, s, n, (unsigned)r, t);
+            hipLaunchKernelGGL(nj_commit_kernel<false>, dim3(blocks), dim3(256), 0, stream, s, n, (unsigned)r, t);
+        }
+        TRACS_HIP_CHECK(hipGetLastError());                      // (a failed launch ends the loop: nothing more is enqueued)
+    }
+    hipLaunchKernelGGL(nj_final_kernel, dim3(1), dim3(64), 0, stream, s, n);
+    TRACS_HIP_CHECK(hipGetLastError());
+    return TRACS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -326,31 +437,16 @@ int tracs_nj_load_f64(void *state, size_t n, const double *matrix, size_t ld, vo
     return load_cells("tracs_nj_load_f64", state, n, matrix, nullptr, ld, 0, n, 2, static_cast<hipStream_t>(stream));
 }
 
-int tracs_nj_run(void *state, size_t n, void *stream_)
+int tracs_nj_run(void *state, size_t n, void *stream) { return run_joins("tracs_nj_run", state, n, false, static_cast<hipStream_t>(stream)); }
+
+size_t tracs_bionj_state_bytes(size_t n)
 {
-    if (!state) { set_error("tracs_nj_run: NULL state"); return TRACS_E_ARG; }
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    DeviceCall guard(stream);
-    State s(state, n);
-    Hdr h{};
-    int rc;
-    if ((rc = read_state_header(s.hdr, n, "tracs_nj_run", stream, &h))) return rc;
-    if (h.ran) { set_error("tracs_nj_run: the state has been run; initialise and load it again"); return TRACS_E_ARG; }
-    if (n == 0) return TRACS_OK;
-    hipLaunchKernelGGL(nj_rowsum_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, s, n);
-    TRACS_HIP_CHECK(hipGetLastError());
-    for (size_t r = n; r > 3; r--) {
-        const unsigned t = (unsigned)(n - r), blocks = (unsigned)((r + 255) / 256);
-        const size_t tiles = (r / 2) * ((r + NJ_TILE - 1) / NJ_TILE);
-        hipLaunchKernelGGL(nj_scan_kernel, dim3((unsigned)std::min<size_t>(tiles, NJ_SCAN_BLOCKS)), dim3(256), 0, stream, s, n, (unsigned)r, t);
-        hipLaunchKernelGGL(nj_rows_kernel, dim3(blocks), dim3(256), 0, stream, s, n, (unsigned)r, t);
-        hipLaunchKernelGGL(nj_commit_kernel, dim3(blocks), dim3(256), 0, stream, s, n, (unsigned)r, t);
-        TRACS_HIP_CHECK(hipGetLastError());                      // (a failed launch ends the loop: nothing more is enqueued)
-    }
-    hipLaunchKernelGGL(nj_final_kernel, dim3(1), dim3(64), 0, stream, s, n);
-    TRACS_HIP_CHECK(hipGetLastError());
-    return TRACS_OK;
+    size_t bytes = 0;
+    if (n <= NJ_MAX_NODES) (void)State(nullptr, n, &bytes, true);
+    return bytes;
 }
+
+int tracs_bionj_run(void *state, size_t n, void *stream) { return run_joins("tracs_bionj_run", state, n, true, static_cast<hipStream_t>(stream)); }
 
 int tracs_nj_emit(void *state, size_t n, size_t *n_joins, uint32_t *a, uint32_t *b, double *d_ab, double *r_a, double *r_b,
                   uint32_t *last_ids, double *last_d, uint32_t *zero_pair, void *stream_)

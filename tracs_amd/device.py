@@ -490,10 +490,16 @@ def anc_emit(state, n):
     return [x[:k] for x in u + f] + [x[:int(n)] for x in t]
 
 
-def nj_init(n, device=None):
-    """A neighbour-joining state with the zero matrix for the leaves [0, n) (tracs_nj_init): a torch.uint8 device buffer."""
+TREE_METHODS = ("nj", "bionj")         # what --tree, DistanceHandle.tree(method=) and api.neighbor_joining(method=) take
+
+
+def nj_init(n, device=None, method="nj"):
+    """A neighbour-joining state with the zero matrix for the leaves [0, n) (tracs_nj_init): a torch.uint8 device buffer.  method
+    "bionj": a state of tracs_bionj_state_bytes, which bionj_run needs (every other nj_* call serves both)."""
+    if method not in TREE_METHODS:
+        raise ValueError("nj_init(): method is 'nj' or 'bionj'")
     L = _lib.require_gpu()
-    nbytes = L.tracs_nj_state_bytes(int(n))
+    nbytes = (L.tracs_bionj_state_bytes if method == "bionj" else L.tracs_nj_state_bytes)(int(n))
     if nbytes == 0:
         raise ValueError("nj_init(): at most 2^24 leaves, got %d" % int(n))
     state = torch.empty(nbytes, dtype=torch.uint8, device=device if device is not None else "cuda")
@@ -523,6 +529,13 @@ def nj_load_f64(state, n, matrix):
 def nj_run(state, n):
     """The row sums and the n - 3 joins, enqueued on the current stream (tracs_nj_run)."""
     _lib.check(_lib.require_gpu().tracs_nj_run(_ptr(state), int(n), _stream()))
+
+
+def bionj_run(state, n):
+    """nj_run with the BIONJ reduction (tracs_bionj_run): state from nj_init(n, method="bionj")."""
+    if state.numel() < _lib.require_gpu().tracs_bionj_state_bytes(int(n)):
+        raise ValueError("bionj_run(): the state is smaller than a BIONJ state for %d leaves" % int(n))
+    _lib.check(_lib.require_gpu().tracs_bionj_run(_ptr(state), int(n), _stream()))
 
 
 def nj_emit(state, n):

@@ -54,6 +54,7 @@ TREE_EDGES_FILTER_HEADER = "parent,child,length,changes,filtered,MSA file\n"    
 TREE_CHANGES_FILTER_HEADER = "parent,child,contig,position,alleleParent,alleleChild,dropped,MSA file\n"
 
 TREE_DISTANCES = {"snp": 0, "per-site": 1}
+TREE_METHODS = ("nj", "bionj")                       # --tree METHOD; the second travels as TRACS_TREE_BIONJ in the request's kind
 
 HEADER = ("sampleA,sampleB,date difference,SNP distance,transmission distance,expected K,"
           "filtered SNP distance,sites considered,MSA file\n")
@@ -130,7 +131,7 @@ def distance_parser(parser):
                      help="With --ancestors: write sample,date,ancestor,ancestor date,root,generation,MSA file for every compared "
                           "sample, in input order (dates as --meta gives them; a root has no ancestor, itself as root and generation 0; "
                           "else root is the sample reached by following sources and generation the number of links to it)")
-    snp.add_argument("--tree", dest="tree", choices=["nj"], default=None, metavar="METHOD",
+    snp.add_argument("--tree", dest="tree", choices=list(TREE_METHODS), default=None, metavar="METHOD",
                      help="Instead of the pairs, output a phylogeny of each --msa file's samples: nj, the neighbour-joining tree "
                           "(Saitou & Nei) of all pairwise distances, built on the GPU.  -o then holds one Newick tree per --msa file, "
                           "one per line and without a header: unrooted, written from the last node joined, internal nodes unlabelled, "
@@ -138,7 +139,11 @@ def distance_parser(parser):
                           "can give negative lengths on data that is not tree-like, and they are written as computed.  Ties are "
                           "broken by input order, so the tree is reproducible.  One GPU; takes the site and sample rules, no -D, -K, "
                           "--filter, --meta, --min-sites or --msa-db; not with --nearest, --mst, --ancestors or --histogram.  Not in "
-                          "the reference.")
+                          "the reference.  bionj: the BIONJ tree (Gascuel 1997), neighbour joining that also keeps the variance of every "
+                          "distance (a SNP count's variance grows with the count) and weights each reduction of the matrix to minimise "
+                          "the variance of the new row.  It has the same output, options and cost class as nj, about twice its memory, "
+                          "and is closer to the true tree when distances are noisy and lineages unequal; every tree of the run "
+                          "(--bootstrap replicates, --tree-iterate rebuilds) is then a BIONJ tree.")
     snp.add_argument("--tree-distance", dest="tree_distance", choices=list(TREE_DISTANCES), default=None,
                      help="With --tree: snp (default), the SNP distance; per-site, the SNP distance divided by the sites the pair was "
                           "compared over (substitutions per compared site).  per-site refuses a pair without any compared site: "
@@ -578,9 +583,11 @@ def tree_edges_header(args):
 
 
 def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None, tree_contigs=None):
-    """--tree nj for one alignment (handle.DistanceHandle.tree, tracs_distance_tree_run: include/tracs_hip.h): every dense panel goes into
+    """--tree nj / bionj for one alignment (handle.DistanceHandle.tree, tracs_distance_tree_run: include/tracs_hip.h): every dense panel goes into
     the distance matrix on the device, the joins run there, and one Newick line (and the edge rows) are appended by the library."""
     changes_on = tree_changes_on(args)
+    # (the [sum] lines name the method; nj's stay as they were)
+    named = stage if args.tree == "nj" else lambda line: stage("%s [%s]" % (line, args.tree))
     with _opened(msas, args, stage, rule, contigs) as h:
         try:
             # (the changes stage: the library creates the files itself, once the count has passed --max-entries: a refusal touches nothing)
@@ -589,7 +596,8 @@ def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None, tree
                        replicate_trees=args.bootstrap_trees, support=args.bootstrap_support or "split", changes_path=args.tree_changes,
                        sites_path=args.tree_sites, max_entries=args.max_entries, contigs=tree_contigs, n_threads=args.n_cpu,
                        create=not args.tree_files_made, tree_filter=args.tree_filter, filtered_path=args.tree_filtered,
-                       **({} if args.tree_iterate is None else {"iterate": args.tree_iterate, "iterations_path": args.tree_iterate_out}))
+                       **({} if args.tree_iterate is None else {"iterate": args.tree_iterate, "iterations_path": args.tree_iterate_out}),
+                       **({} if args.tree == "nj" else {"method": args.tree}))
         except RuntimeError as e:
             if not changes_on:                                              # (the plain and the bootstrap run pass the library's error on)
                 raise
@@ -606,19 +614,19 @@ def _tree_on_device(msas, args, dates, ref, stage, rule=None, contigs=None, tree
                        "cycle back to %d" % t.same_as)
                 sys.stderr.write("tracs distance: %s: tree iterate: %d trees built, %s; final tree: %d changes, %d kept, %d dropped\n"
                                  % (ref, t.iterations + 1, how, t.changes, t.kept, t.changes - t.kept))
-                stage("[sum] tracs_distance_tree_iterate (%d trees: dense panels, joins, Fitch count, edge lists, filter, mask each; tree, fill: "
+                named("[sum] tracs_distance_tree_iterate (%d trees: dense panels, joins, Fitch count, edge lists, filter, mask each; tree, fill: "
                       "%d joins, %d edge rows, %d changes, %d kept)" % (t.iterations + 1, t.joins, t.rows, t.changes, t.kept))
             else:
-                stage("[sum] tracs_distance_tree_filter (dense panels, joins, tree, Fitch count, edge lists, filter, fill: %d joins, %d edge rows, "
+                named("[sum] tracs_distance_tree_filter (dense panels, joins, tree, Fitch count, edge lists, filter, fill: %d joins, %d edge rows, "
                       "%d changes, %d kept)" % (t.joins, t.rows, t.changes, t.kept))
         elif changes_on:
-            stage("[sum] tracs_distance_tree_changes (dense panels, joins, tree, Fitch count and fill: %d joins, %d edge rows, %d changes)"
+            named("[sum] tracs_distance_tree_changes (dense panels, joins, tree, Fitch count and fill: %d joins, %d edge rows, %d changes)"
                   % (t.joins, t.rows, t.changes))
         elif args.bootstrap is not None:
-            stage("[sum] tracs_distance_tree_bootstrap%s (main tree, %d replicates: %d joins, %d edge rows written)"
+            named("[sum] tracs_distance_tree_bootstrap%s (main tree, %d replicates: %d joins, %d edge rows written)"
                   % ("_transfer" if args.bootstrap_support == "transfer" else "", args.bootstrap, t.joins, t.rows))
         else:
-            stage("[sum] tracs_distance_tree (dense panels, joins, tree: %d joins, %d edge rows written)" % (t.joins, t.rows))
+            named("[sum] tracs_distance_tree (dense panels, joins, tree: %d joins, %d edge rows written)" % (t.joins, t.rows))
 
 
 def check_mst_args(args):

@@ -134,8 +134,9 @@ class DistanceHandle:
 
     def tree(self, path, ref, per_site=False, edges_path=None, bootstrap=0, seed=1, replicate_trees=None, support="split",
              changes_path=None, sites_path=None, max_entries=None, contigs=None, n_threads=0, create=True, tree_filter=False,
-             filtered_path=None, iterate=None, iterations_path=None):
-        """The neighbour-joining tree of the handle's samples: the keywords as one tracs_tree_request (include/tracs_hip.h describes every
+             filtered_path=None, iterate=None, iterations_path=None, method="nj"):
+        """The neighbour-joining tree of the handle's samples, or with method="bionj" their BIONJ tree (every tree of the
+        call, replicates and rebuilds included; it travels as bit 1 of the request's kind): the keywords as one tracs_tree_request (include/tracs_hip.h describes every
         field) -> TreeResult, 0 where nothing was asked for.  One Newick line is appended to `path`, the edge rows to
         edges_path.  bootstrap = B > 0: B replicates under `seed`, support "split" or "transfer", each replicate's line to replicate_trees.
         changes_path / sites_path / tree_filter (no bootstrap): every site placed on the tree, at most max_entries (default 10^8) changes,
@@ -152,6 +153,8 @@ class DistanceHandle:
             raise ValueError("tree(): iterate takes no bootstrap")
         elif not 1 <= int(iterate) <= 100:
             raise ValueError("tree(): iterate must be in [1, 100]")
+        if method not in ("nj", "bionj"):
+            raise ValueError("tree(): method is 'nj' or 'bionj'")
         if support not in ("split", "transfer"):
             raise ValueError("tree(): support is 'split' or 'transfer'")
         if filtered_path is not None and not tree_filter:
@@ -181,7 +184,7 @@ class DistanceHandle:
         enc = lambda p: os.fsencode(p) if p is not None else None         # noqa: E731
         contigs = contigs if changes and contigs else []                    # (read by the change and site rows only)
         req = _lib.TreeRequest(
-            kind=int(bool(per_site)), path=os.fsencode(path), ref=ref.encode(), edges_path=enc(edges_path), replicates=int(bootstrap),
+            kind=int(bool(per_site)) | (_lib.TREE_BIONJ if method == "bionj" else 0), path=os.fsencode(path), ref=ref.encode(), edges_path=enc(edges_path), replicates=int(bootstrap),
             seed=int(seed), transfer=int(bool(bootstrap) and support == "transfer"), replicate_trees_path=enc(replicate_trees) if bootstrap else None,
             changes=int(changes), changes_path=enc(changes_path), sites_path=enc(sites_path), filter=int(bool(tree_filter)),
             filtered_path=enc(filtered_path), contig_names=(C.c_char_p * len(contigs))(*[c[0].encode() for c in contigs]),
