@@ -725,6 +725,23 @@ int tracs_find_dirichlet_priors_device(const double *counts, size_t L, size_t K,
                                        void *stream);
 /* Tests only: the digamma the fit sums (csrc/dirichlet.hip digamma_pos), evaluated on the device for n host doubles > 0.  */
 int tracs_debug_digamma(const double *x, size_t n, double *out);
+/* Tests only: the contents of memory the library should not be reading, as a controlled input.
+ *   tracs_debug_poison_scratch(byte)   0 .. 255: on; -1 (the default; any other value too): off.  While on, every OUTERMOST entry-point
+ *                                      call that uses the scratch pool (an entry point that calls another one counts once: what the
+ *                                      outer call holds is left alone) first drains the device, fills every allocated scratch slot
+ *                                      of its device with `byte` and drains again; a slot allocated or regrown inside a call is
+ *                                      filled before it is handed out.  Nothing in a slot survives from one entry-point call to the
+ *                                      next -- which is the library's contract for its scratch anyway: results are the same with
+ *                                      poison on, only slower.  (The one reader of scratch outside a call is a diagnostic this header
+ *                                      does not declare, tracs_debug_trans_routes in csrc/transcluster.hip: the counters of the last
+ *                                      key evaluation, valid only until the next entry-point call; the contract is at its definition.)  Off costs one untaken branch per call.  Caller-owned states, outputs
+ *                                      and what a tracs_alignment caches are not touched.  Process-wide; not meant to be switched
+ *                                      while another thread is inside the library.
+ *   tracs_debug_scratch_hits(hits, n)  returns the number of scratch slots S; hits[s] (s < min(n, S); hits may be NULL) <- how often
+ *                                      slot s has been handed out, by any device, since the previous call of this function.  Every
+ *                                      count is then reset to zero.  Slots are numbered as csrc/common.h's enum WsSlot.             */
+void tracs_debug_poison_scratch(int byte);
+size_t tracs_debug_scratch_hits(uint64_t *hits, size_t room);
 
 /* The same with the align stage's coverage rules (tracs/align.py:599-613): sites with total count < min_cov, or with
  * cov_lo <= total <= cov_hi (outlier band; pass cov_lo > cov_hi to disable), become fully ambiguous (mask 15).        */

@@ -26,6 +26,25 @@ def test_library_exports_every_declared_symbol(hiplib):
     assert hiplib.tracs_abi_version() == 1
 
 
+def test_scratch_diagnostics_are_declared_exported_and_bound(hiplib):
+    """tracs_debug_poison_scratch / tracs_debug_scratch_hits (tests/test_gpu_scratch_poison.py runs on them): in the header, in
+    the library and in the binding's list.  Switching poison on and off and reading the counts touch no device."""
+    from tracs_amd import _lib
+    for name in ("tracs_debug_poison_scratch", "tracs_debug_scratch_hits"):
+        assert name in _declared(), name + " is not declared in include/tracs_hip.h"
+        assert hasattr(hiplib, name), "libtracs_hip.so does not export " + name
+        assert name in _lib.SYMBOLS, name
+    hiplib.tracs_debug_poison_scratch(0xFF)
+    hiplib.tracs_debug_poison_scratch(-1)
+    hits = (C.c_uint64 * 4)(7, 7, 7, 7)
+    n_slots = hiplib.tracs_debug_scratch_hits(hits, 4)
+    enum = re.search(r"enum WsSlot : int \{(.*?)\};", open(os.path.join(ROOT, "tracs_amd", "csrc", "common.h")).read(), flags=re.S).group(1)
+    names = re.findall(r"\bWS_[A-Z0-9_]+", re.sub(r"//[^\n]*", "", enum))
+    assert names[-1] == "WS_SLOT_COUNT" and n_slots == len(names) - 1
+    assert hiplib.tracs_debug_scratch_hits(hits, 4) == n_slots and list(hits) == [0, 0, 0, 0]      # reading the counts resets them
+    assert hiplib.tracs_debug_scratch_hits(None, 0) == n_slots
+
+
 def test_built_for_gfx950():
     from tracs_amd import _lib
     blob = open(_lib.LIB_PATH, "rb").read()

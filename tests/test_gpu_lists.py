@@ -92,8 +92,8 @@ def test_lists_against_numpy(hiplib, case, nn_lists):
     if nn_lists == "always":
         env["TRACS_NN_LIST_K"] = "1"
     env.update(CASES[case].get("env", {}))
-    code = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_gpu_lists as T; T.run_case(T.CASES[%d], %r)" % (
-        root, os.path.join(root, "tests"), case, nn_lists)
+    code = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); import scratch_poison; scratch_poison.enter_child(%r); import test_gpu_lists as T; T.run_case(T.CASES[%d], %r)" % (
+        root, os.path.join(root, "tests"), "lists:c%d:%s" % (case, nn_lists), case, nn_lists)
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=900, cwd=root)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
 

@@ -28,8 +28,8 @@ def _child(case, env, out=None):
         e.pop(k, None)
     e["TRACS_NN_LIST_K"] = "1"
     e.update(env)
-    code = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_gpu_row_slots as T; T.run_case(%r, %r)" % (
-        ROOT, os.path.join(ROOT, "tests"), case, out)
+    code = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); import scratch_poison; scratch_poison.enter_child(%r); import test_gpu_row_slots as T; T.run_case(%r, %r)" % (
+        ROOT, os.path.join(ROOT, "tests"), "row_slots:%s:TRACS_ROW_LISTS=%s" % (case, e.get("TRACS_ROW_LISTS")), case, out)
     res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=e, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-3000:]
     return res.stdout

@@ -328,8 +328,10 @@ def test_row_hint_builds_lists_for_those_rows_only(hiplib, oracle):
 
 
 LONG_LISTS_CHILD = r'''
-import sys, numpy as np, torch
-sys.path.insert(0, %(root)r)
+import os, sys, numpy as np, torch
+sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, "tests"))
+import scratch_poison
+scratch_poison.enter_child("long_n_lists:%(p_n)g")
 from oracle import oracle as O
 from tracs_amd import device as dev, synth
 n, L = 1500, 6000

@@ -39,15 +39,20 @@ def _plane_bytes(aln):
     return torch.as_tensor(_DeviceBytes(aln.planes_ptr(), aln.nbytes), device="cuda").cpu().numpy().copy()
 
 
-@pytest.fixture(scope="module", params=SHAPES, ids=["%dx%d" % s for s in SHAPES])
-def case(request, hiplib):
-    n, L = request.param
+def make_case(n, L, hiplib):
+    """one alignment of the module's shapes, packed, with what the tests compare against (a generator: closes the handle at the end;
+    tests/test_gpu_scratch_poison.py builds the same cases per test)"""
     seqs = _input(n, L)
     table = _mask_table(hiplib)
     assert (table[seqs] != 0).all() and table[ord("-")] == 15 and table[0x07] == 15 and table[0xC3] == 15 and table[ord("r")] == 5
     src = _packed(seqs)
     yield dict(n=n, L=L, seqs=seqs, expect=LUT[table[seqs]], src=src, before=_plane_bytes(src))
     src.close()
+
+
+@pytest.fixture(scope="module", params=SHAPES, ids=["%dx%d" % s for s in SHAPES])
+def case(request, hiplib):
+    yield from make_case(*request.param, hiplib)
 
 
 def _ranges(n):

@@ -18,6 +18,7 @@ SYMBOLS = [
     "tracs_pairsnp_name", "tracs_pairsnp_free",
     "tracs_trans_dist", "tracs_lprob_k_given_N", "tracs_calculate_posteriors", "tracs_connected_components",
     "tracs_find_dirichlet_priors", "tracs_find_dirichlet_priors_device", "tracs_debug_digamma",
+    "tracs_debug_poison_scratch", "tracs_debug_scratch_hits",
     "tracs_alignment_create", "tracs_alignment_free", "tracs_alignment_n", "tracs_alignment_len",
     "tracs_alignment_bytes", "tracs_alignment_planes", "tracs_alignment_touch", "tracs_alignment_hint_rows", "tracs_pairsnp_notify_distances", "tracs_set_stream_policy", "tracs_alignment_pack", "tracs_alignment_from_fasta",
     "tracs_free",
@@ -159,6 +160,10 @@ def load():
     L.tracs_find_dirichlet_priors_device.argtypes = [vp, sz, sz, C.c_int, dbl, C.c_int, dbl, dp, C.POINTER(C.c_int), vp]
     L.tracs_debug_digamma.restype = C.c_int
     L.tracs_debug_digamma.argtypes = [dp, sz, dp]
+    L.tracs_debug_poison_scratch.restype = None
+    L.tracs_debug_poison_scratch.argtypes = [C.c_int]
+    L.tracs_debug_scratch_hits.restype = sz
+    L.tracs_debug_scratch_hits.argtypes = [u64p, sz]
     L.tracs_connected_components.restype = C.c_int
     L.tracs_connected_components.argtypes = [C.POINTER(i32), C.POINTER(i32), sz, sz, C.POINTER(i32), C.POINTER(i32)]
     L.tracs_alignment_create.restype = C.c_int

@@ -8,6 +8,7 @@
 #include "rowwriter.h"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <csignal>
@@ -28,6 +29,10 @@ void set_error(const std::string &msg) { g_error = msg; }
 struct Scratch { void *ptr = nullptr; size_t bytes = 0; };
 static Scratch g_scratch[8][WS_SLOT_COUNT];
 static std::mutex g_scratch_mu;
+// diagnostics (tracs_debug_poison_scratch / tracs_debug_scratch_hits): the byte every outermost DeviceCall fills the device's slots
+// with (-1: off), and how often each slot has been handed out since the counts were last read
+static std::atomic<int> g_poison{-1};         // (relaxed: a tests-only switch, read once per DeviceCall)
+static uint64_t g_slot_hits[WS_SLOT_COUNT];
 
 int workspace_bytes(WsSlot slot, size_t bytes, void **out)
 {
@@ -36,12 +41,17 @@ int workspace_bytes(WsSlot slot, size_t bytes, void **out)
     if (dev < 0 || dev >= 8 || slot < 0 || slot >= WS_SLOT_COUNT) { set_error("workspace_get: bad device/slot"); return TRACS_E_ARG; }
     std::lock_guard<std::mutex> lock(g_scratch_mu);
     Scratch &s = g_scratch[dev][slot];
+    g_slot_hits[slot]++;
     if (s.bytes < bytes) {
         if (s.ptr) { TRACS_HIP_CHECK(hipDeviceSynchronize()); TRACS_HIP_CHECK(hipFree(s.ptr)); s.ptr = nullptr; s.bytes = 0; }
         const size_t want = bytes + bytes / 4 + 256;
         hipError_t e = hipMalloc(&s.ptr, want);
         if (e != hipSuccess) { s.ptr = nullptr; set_error(std::string("hipMalloc(workspace): ") + hipGetErrorString(e)); return TRACS_E_NOMEM; }
         s.bytes = want;
+        if (const int poison = g_poison.load(std::memory_order_relaxed); poison >= 0) {      // growth inside a call: the new buffer starts as the rest of the pool did
+            TRACS_HIP_CHECK(hipMemset(s.ptr, poison, s.bytes));
+            TRACS_HIP_CHECK(hipDeviceSynchronize());
+        }
     }
     *out = s.ptr;
     return TRACS_OK;
@@ -50,7 +60,20 @@ int workspace_bytes(WsSlot slot, size_t bytes, void **out)
 static std::recursive_mutex g_call_mu[8];
 static hipStream_t g_last_stream[8];
 static bool g_have_stream[8];
+static int g_call_depth[8];                      // DeviceCalls the owning thread holds on the device (under g_call_mu)
 static bool g_caller_orders_streams = false;     // tracs_set_stream_policy
+
+// every allocated slot of `dev` <- the poison byte, with the device drained before and after (the outermost DeviceCall, poison on)
+static void poison_scratch(int dev, int byte)
+{
+    (void)hipDeviceSynchronize();
+    {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        for (Scratch &s : g_scratch[dev])
+            if (s.ptr) (void)hipMemset(s.ptr, byte, s.bytes);
+    }
+    (void)hipDeviceSynchronize();
+}
 
 DeviceCall::DeviceCall(hipStream_t stream) : dev(0)
 {
@@ -59,8 +82,14 @@ DeviceCall::DeviceCall(hipStream_t stream) : dev(0)
     if (g_have_stream[dev] && g_last_stream[dev] != stream && !g_caller_orders_streams) (void)hipDeviceSynchronize();
     g_last_stream[dev] = stream;
     g_have_stream[dev] = true;
+    const int poison = g_poison.load(std::memory_order_relaxed);
+    if (g_call_depth[dev]++ == 0 && poison >= 0) poison_scratch(dev, poison);
 }
-DeviceCall::~DeviceCall() { g_call_mu[dev].unlock(); }
+DeviceCall::~DeviceCall()
+{
+    g_call_depth[dev]--;
+    g_call_mu[dev].unlock();
+}
 
 void workspace_release_all()
 {
@@ -73,6 +102,22 @@ void workspace_release_all()
 }  // namespace tracs
 
 using namespace tracs;
+
+void tracs_debug_poison_scratch(int byte)
+{
+    std::lock_guard<std::mutex> lock(g_scratch_mu);
+    g_poison.store(byte >= 0 && byte <= 255 ? byte : -1, std::memory_order_relaxed);
+}
+
+size_t tracs_debug_scratch_hits(uint64_t *hits, size_t room)
+{
+    std::lock_guard<std::mutex> lock(g_scratch_mu);
+    for (size_t s = 0; s < (size_t)WS_SLOT_COUNT; s++) {
+        if (hits && s < room) hits[s] = g_slot_hits[s];
+        g_slot_hits[s] = 0;
+    }
+    return (size_t)WS_SLOT_COUNT;
+}
 
 // TRACS_STAGE_TRACE=1: wall time of the stages of the host-level entry points on stderr, one "[stage] name seconds" line each
 // (scripts/bench_e2e.py collects them into the end-to-end table of DESIGN.md 5)

@@ -1531,6 +1531,10 @@ unsigned long long tracs_debug_last_trans_dist_keys(void) { return g_last_keys; 
 // out[0] distinct keys, out[1] finished by the serial kernel, [2] by the term-ratio loop, [3] by the same-day ratio loop,
 // [4] by the log-space wave loop, [5] (gap, M) tables built, [6] ... in linear form, [7] 1 = grid route, 0 = hash route.
 // -> 8, or 0 before any evaluation.
+// Contract: this is the one reader of scratch outside an entry-point call.  It reads, without a DeviceCall, the slots WS_TC_NKEYS
+// ([1], [8], [9]), WS_TC_TAB, WS_TC_LONG_IDS and WS_TC_REST_IDS where the last key evaluation of this process left them: valid only
+// until the next entry-point call on the device (any call may reuse or regrow a slot; under tracs_debug_poison_scratch the next call
+// fills them), and only from the thread that made the evaluation, with no other thread inside the library.  No entry point relies on it.
 int tracs_debug_trans_routes(double *out)
 {
     const TcRoutes r = g_routes;

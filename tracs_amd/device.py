@@ -4,6 +4,7 @@ torch is used for device memory, streams and torch.distributed only -- plumbing;
 in libtracs_hip.so.  Import torch BEFORE this module's first call so that both share one HIP
 runtime (torch ships its own libamdhip64.so with the same soname).
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -303,6 +304,30 @@ def notify_distances(event):
 
 def set_stream_policy(caller_orders_streams):
     _lib.load().tracs_set_stream_policy(1 if caller_orders_streams else 0)
+
+
+@contextlib.contextmanager
+def poison_scratch(byte):
+    """Tests: while inside, every outermost entry-point call first fills the device's scratch slots with `byte` (0 .. 255), and
+    a slot that grows inside a call starts as `byte` (tracs_debug_poison_scratch).  Switched off on the way out."""
+    if not 0 <= int(byte) <= 255:
+        raise ValueError("poison_scratch: byte must be 0 .. 255")
+    lib = _lib.load()
+    lib.tracs_debug_poison_scratch(int(byte))
+    try:
+        yield
+    finally:
+        lib.tracs_debug_poison_scratch(-1)
+
+
+def scratch_hits():
+    """How often each scratch slot (csrc/common.h's WsSlot, in order) has been handed out since the previous call; the counts
+    are reset (tracs_debug_scratch_hits)."""
+    lib = _lib.load()
+    hits = (C.c_uint64 * 1024)()          # (one call: reading the counts resets them)
+    n = lib.tracs_debug_scratch_hits(hits, len(hits))
+    assert n <= len(hits)
+    return [int(x) for x in hits[:n]]
 
 
 def pack_stages():
