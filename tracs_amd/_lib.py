@@ -2,6 +2,11 @@
 
 The HIP library IS the product: there is no CPU fallback.  If the shared library is missing,
 does not load, or no GPU is visible, calls raise -- they never route through oracle/.
+
+Every entry point is one row of BINDINGS (declared in include/tracs_hip.h) or DEBUG_BINDINGS (the diagnostics of
+tracs_amd/csrc/debug_api.h): name -> (restype, [argtypes]); load() applies the rows.  A new entry point takes one prototype
+in its header and one row here, and no test of its own for declaration, export or binding: tests/test_bindings.py compares
+every row with its prototype, the library's exported symbols with the rows, and the structs and constants below with the header.
 """
 import ctypes as C
 import os
@@ -10,58 +15,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libtracs_hip.so")
 _lib = None
 
-# every symbol include/tracs_hip.h declares (tests/test_cabi.py checks the .so exports them all)
-SYMBOLS = [
-    "tracs_last_error", "tracs_abi_version", "tracs_device_count",
-    "tracs_pairsnp", "tracs_pairsnp_len", "tracs_pairsnp_nseq", "tracs_pairsnp_seqlen", "tracs_pairsnp_rows",
-    "tracs_pairsnp_cols", "tracs_pairsnp_distances", "tracs_pairsnp_filt_distances", "tracs_pairsnp_ncompared",
-    "tracs_pairsnp_name", "tracs_pairsnp_free",
-    "tracs_trans_dist", "tracs_lprob_k_given_N", "tracs_calculate_posteriors", "tracs_connected_components",
-    "tracs_find_dirichlet_priors", "tracs_find_dirichlet_priors_device", "tracs_debug_digamma",
-    "tracs_debug_poison_scratch", "tracs_debug_scratch_hits",
-    "tracs_alignment_create", "tracs_alignment_free", "tracs_alignment_n", "tracs_alignment_len",
-    "tracs_alignment_bytes", "tracs_alignment_planes", "tracs_alignment_touch", "tracs_alignment_hint_rows", "tracs_pairsnp_notify_distances", "tracs_set_stream_policy", "tracs_alignment_pack", "tracs_alignment_from_fasta",
-    "tracs_free",
-    "tracs_pairsnp_dense", "tracs_pairsnp_dense_thr", "tracs_coo_count", "tracs_coo_fill", "tracs_filter_recomb_device", "tracs_filter_recomb_pairs",
-    "tracs_trans_dist_device", "tracs_trans_dist_dense", "tracs_trans_dist_dense2", "tracs_trans_table_dense", "tracs_trans_table_gather",
-    "tracs_trans_keys_words", "tracs_trans_keys_mark", "tracs_trans_keys_merge", "tracs_trans_keys_info", "tracs_trans_keys_evaluate", "tracs_trans_keys_gather",
-    "tracs_calculate_posteriors_device", "tracs_posterior_codes_device", "tracs_posterior_codes_cov_device",
-    "tracs_codes_to_iupac_device", "tracs_alignment_pack_codes", "tracs_alignment_pack_codes_batch", "tracs_edges_count_f64", "tracs_edges_fill_f64",
-    "tracs_coverage_profile_device32", "tracs_posterior_codes_cov_device32", "tracs_consensus_codes_device32", "tracs_coverage_profile_device",
-    "tracs_consensus_codes_device",
-    "tracs_connected_components_device",
-    "tracs_pileup_counts", "tracs_write_posterior_csv", "tracs_combine_fasta", "tracs_write_distance_rows",
-    "tracs_read_distance_edges", "tracs_edges_count", "tracs_edges_rows", "tracs_edges_n_names", "tracs_edges_name", "tracs_edges_i",
-    "tracs_edges_j", "tracs_edges_free",
-    "tracs_comm_unique_id", "tracs_comm_create", "tracs_comm_free", "tracs_comm_rank", "tracs_comm_world", "tracs_bcast",
-    "tracs_bcast_planes", "tracs_allgather_panels", "tracs_allreduce", "tracs_reduce_scatter", "tracs_send", "tracs_recv",
-    "tracs_alltoall", "tracs_tri_pack", "tracs_tri_sum", "tracs_rccl_version",
-    "tracs_coo_fill_f64", "tracs_distance_open", "tracs_distance_nseq", "tracs_distance_name", "tracs_distance_run", "tracs_distance_free",
-    "tracs_warm_up",
-    "tracs_nearest", "tracs_knn_state_bytes", "tracs_knn_init", "tracs_knn_update", "tracs_knn_emit",
-    "tracs_distance_forest", "tracs_msf_state_bytes", "tracs_msf_init", "tracs_msf_update_coo", "tracs_msf_emit",
-    "tracs_alignment_site_n_counts", "tracs_alignment_select_sites", "tracs_pairsnp_sites", "tracs_nearest_sites",
-    "tracs_distance_open_sites", "tracs_distance_source_len", "tracs_distance_len", "tracs_distance_kept_sites",
-    "tracs_alignment_sample_n_counts", "tracs_alignment_select_samples", "tracs_pairs_min_sites", "tracs_pairsnp_rules",
-    "tracs_nearest_rules", "tracs_distance_open_rules", "tracs_pairsnp_source_nseq", "tracs_pairsnp_source_name",
-    "tracs_pairsnp_source_n_count", "tracs_pairsnp_source_kept", "tracs_pairsnp_rule_sites", "tracs_distance_source_nseq",
-    "tracs_distance_source_name", "tracs_distance_source_n_count", "tracs_distance_source_kept", "tracs_distance_rule_sites",
-    "tracs_alignment_site_census", "tracs_alignment_unpack", "tracs_write_fasta_rows", "tracs_distance_site_census",
-    "tracs_distance_write_alignment",
-    "tracs_pair_sites_count", "tracs_pair_sites_fill", "tracs_distance_alignment", "tracs_distance_pair_sites",
-    "tracs_distance_histogram", "tracs_hist_state_bytes", "tracs_hist_init", "tracs_hist_update", "tracs_hist_update_coo", "tracs_hist_emit",
-    "tracs_distance_ancestors", "tracs_anc_state_bytes", "tracs_anc_init", "tracs_anc_update_coo", "tracs_anc_emit",
-    "tracs_distance_tree", "tracs_nj_state_bytes", "tracs_nj_init", "tracs_nj_load_panel", "tracs_nj_load_f64", "tracs_nj_run",
-    "tracs_nj_emit", "tracs_nj_edges", "tracs_tree_write", "tracs_bionj_state_bytes", "tracs_bionj_run",
-    "tracs_bootstrap_weights", "tracs_alignment_gather_sites", "tracs_tree_support", "tracs_tree_write_support",
-    "tracs_distance_tree_bootstrap",
-    "tracs_tree_transfer_program", "tracs_transfer_state_bytes", "tracs_transfer_init", "tracs_transfer_add", "tracs_transfer_emit",
-    "tracs_tree_transfer", "tracs_tree_write_transfer", "tracs_distance_tree_bootstrap_transfer",
-    "tracs_fitch_count", "tracs_fitch_fill", "tracs_tree_write_changes", "tracs_distance_tree_changes",
-    "tracs_fitch_edge_sites", "tracs_filter_recomb_lists", "tracs_fitch_mark_dropped", "tracs_tree_write_filtered",
-    "tracs_distance_tree_filter", "tracs_distance_tree_run",
-    "tracs_alignment_clone", "tracs_alignment_restore", "tracs_alignment_mask_subtrees", "tracs_distance_tree_iterate",
-]
+# TRACS_E_* (include/tracs_hip.h): what an entry point returns instead of 0
+E_ARG, E_FASTA, E_RAGGED, E_OPEN, E_HIP, E_NOMEM, E_INTERRUPTED = -1, -2, -4, -5, -6, -7, -8
+
+P = C.POINTER
+vp, cs, ci, sz, dbl = C.c_void_p, C.c_char_p, C.c_int, C.c_size_t, C.c_double
+i32, i64, u32, u64 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
+vpp, cpp, ip, i32p, u8p, u32p, u64p, szp, fp, dp = P(vp), P(cs), P(ci), P(i32), P(C.c_uint8), P(u32), P(u64), P(sz), P(C.c_float), P(dbl)
 
 
 class Rules(C.Structure):
@@ -94,6 +54,240 @@ class TreeIterate(C.Structure):
 class TreeIterateResult(C.Structure):
     """tracs_tree_iterate_result: the final k, the earlier tree it repeats (-1: none), the cells the last mask made N, the largest W"""
     _fields_ = [("iterations", C.c_uint32), ("same_as", C.c_int32), ("masked_cells_last", C.c_uint64), ("mask_work_max", C.c_uint64)]
+
+
+# include/tracs_hip.h, in its order.  Pointers to device memory, opaque handles, streams and plain host buffers are vp.
+BINDINGS = {
+    "tracs_last_error": (cs, []),
+    "tracs_abi_version": (ci, []),
+    "tracs_device_count": (ci, []),
+    "tracs_pairsnp": (ci, [cpp, ci, ci, ci, ci, vpp]),
+    "tracs_pairsnp_len": (sz, [vp]),
+    "tracs_pairsnp_nseq": (sz, [vp]),
+    "tracs_pairsnp_seqlen": (sz, [vp]),
+    "tracs_pairsnp_rows": (u64p, [vp]),
+    "tracs_pairsnp_cols": (u64p, [vp]),
+    "tracs_pairsnp_distances": (u64p, [vp]),
+    "tracs_pairsnp_filt_distances": (u64p, [vp]),
+    "tracs_pairsnp_ncompared": (u64p, [vp]),
+    "tracs_pairsnp_name": (cs, [vp, sz]),
+    "tracs_pairsnp_free": (None, [vp]),
+    "tracs_nearest": (ci, [cpp, ci, ci, ci, ci, ci, vpp]),
+    "tracs_pairsnp_sites": (ci, [cpp, ci, ci, ci, ci, u64p, sz, u32, vpp]),
+    "tracs_nearest_sites": (ci, [cpp, ci, ci, ci, ci, ci, u64p, sz, u32, vpp]),
+    "tracs_trans_dist": (ci, [i32p, dp, sz, dbl, dbl, dbl, dp, dp]),
+    "tracs_lprob_k_given_N": (ci, [u64p, u64p, dp, sz, dbl, dbl, dp, sz, dp, dp]),
+    "tracs_calculate_posteriors": (ci, [dp, sz, sz, dp, ci, dbl, dp]),
+    "tracs_find_dirichlet_priors": (ci, [dp, sz, sz, ci, dbl, ci, dbl, dp, ip]),
+    "tracs_connected_components": (ci, [i32p, i32p, sz, sz, i32p, i32p]),
+    "tracs_alignment_create": (ci, [sz, sz, vpp]),
+    "tracs_alignment_free": (None, [vp]),
+    "tracs_alignment_n": (sz, [vp]),
+    "tracs_alignment_len": (sz, [vp]),
+    "tracs_alignment_bytes": (sz, [vp]),
+    "tracs_alignment_planes": (vp, [vp]),
+    "tracs_alignment_touch": (ci, [vp]),
+    "tracs_alignment_hint_rows": (ci, [vp, szp, ci]),
+    "tracs_alignment_pack": (ci, [vp, vp, sz, sz, ci, vp]),
+    "tracs_alignment_from_fasta": (ci, [cpp, ci, vpp, vpp, szp, szp]),
+    "tracs_free": (None, [vp]),
+    "tracs_alignment_site_n_counts": (ci, [vp, vp, vp]),
+    "tracs_alignment_select_sites": (ci, [vp, u64p, sz, u32, vpp, u64p, szp, vp]),
+    "tracs_alignment_sample_n_counts": (ci, [vp, u64p, sz, vp, vp]),
+    "tracs_alignment_select_samples": (ci, [vp, u8p, vpp, vp]),
+    "tracs_pairs_min_sites": (ci, [vp, vp, sz, sz, sz, sz, sz, i32, u32, vp]),
+    "tracs_alignment_site_census": (ci, [vp, vp, u64p, szp, vp]),
+    "tracs_alignment_unpack": (ci, [vp, sz, sz, vp, sz, vp]),
+    "tracs_pairsnp_rules": (ci, [cpp, ci, ci, ci, ci, P(Rules), vpp]),
+    "tracs_nearest_rules": (ci, [cpp, ci, ci, ci, ci, ci, P(Rules), vpp]),
+    "tracs_pairsnp_source_nseq": (sz, [vp]),
+    "tracs_pairsnp_source_name": (cs, [vp, sz]),
+    "tracs_pairsnp_source_n_count": (u32, [vp, sz]),
+    "tracs_pairsnp_source_kept": (ci, [vp, sz]),
+    "tracs_pairsnp_rule_sites": (sz, [vp]),
+    "tracs_pairsnp_dense": (ci, [vp, sz, sz, sz, vp, vp, sz, vp]),
+    "tracs_pairsnp_notify_distances": (None, [vp]),
+    "tracs_set_stream_policy": (None, [ci]),
+    "tracs_pairsnp_dense_thr": (ci, [vp, sz, sz, sz, vp, vp, sz, i32, vp]),
+    "tracs_coo_count": (ci, [vp, sz, sz, sz, sz, sz, i32, vp, vp]),
+    "tracs_coo_fill": (ci, [vp, vp, sz, sz, sz, sz, sz, i32, vp, vp, vp, vp, vp, vp]),
+    "tracs_coo_fill_f64": (ci, [vp, sz, sz, sz, sz, sz, i32, vp, vp, vp, vp, vp, vp]),
+    "tracs_edges_count_f64": (ci, [vp, vp, sz, sz, sz, sz, sz, i32, dbl, vp, vp]),
+    "tracs_edges_fill_f64": (ci, [vp, vp, sz, sz, sz, sz, sz, i32, dbl, vp, vp, vp, vp, vp]),
+    "tracs_knn_state_bytes": (sz, [sz, ci]),
+    "tracs_knn_init": (ci, [vp, sz, ci, vp]),
+    "tracs_knn_update": (ci, [vp, vp, sz, sz, sz, sz, sz, i32, ci, ci, vp, vp]),
+    "tracs_knn_emit": (ci, [vp, sz, sz, ci, vp, vp, vp, vp, vp, vp]),
+    "tracs_msf_state_bytes": (sz, [sz]),
+    "tracs_msf_init": (ci, [vp, sz, vp]),
+    "tracs_msf_update_coo": (ci, [vp, sz, sz, vp, vp, vp, ci, vp, dbl, vp, vp, vp, vp, vp, u64p, vp]),
+    "tracs_msf_emit": (ci, [vp, sz, szp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tracs_anc_state_bytes": (sz, [sz]),
+    "tracs_anc_init": (ci, [vp, sz, vp, vp]),
+    "tracs_anc_update_coo": (ci, [vp, sz, sz, vp, vp, vp, ci, vp, dbl, vp, vp, vp, vp, vp, u64p, vp]),
+    "tracs_anc_emit": (ci, [vp, sz, szp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tracs_nj_state_bytes": (sz, [sz]),
+    "tracs_nj_init": (ci, [vp, sz, vp]),
+    "tracs_nj_load_panel": (ci, [vp, sz, vp, vp, sz, sz, sz, ci, vp]),
+    "tracs_nj_load_f64": (ci, [vp, sz, vp, sz, vp]),
+    "tracs_nj_run": (ci, [vp, sz, vp]),
+    "tracs_nj_emit": (ci, [vp, sz, szp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "tracs_nj_edges": (ci, [sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, szp]),
+    "tracs_tree_write": (ci, [cpp, sz, vp, vp, vp, sz, cs, cs, cs]),
+    "tracs_bionj_state_bytes": (sz, [sz]),
+    "tracs_bionj_run": (ci, [vp, sz, vp]),
+    "tracs_tree_write_changes": (ci, [cpp, sz, vp, vp, vp, sz, vp, cs, cs, cs]),
+    "tracs_tree_write_filtered": (ci, [cpp, sz, vp, vp, vp, sz, vp, vp, cs, cs, cs]),
+    "tracs_bootstrap_weights": (ci, [sz, u64, u64, vp, vp]),
+    "tracs_alignment_gather_sites": (ci, [vp, vp, vpp, szp, vp]),
+    "tracs_tree_support": (ci, [sz, vp, vp, sz, vp, vp, sz, vp]),
+    "tracs_tree_write_support": (ci, [cpp, sz, vp, vp, vp, sz, vp, u32, cs, cs, cs]),
+    "tracs_tree_transfer_program": (ci, [sz, vp, vp, sz, vp, szp]),
+    "tracs_transfer_state_bytes": (sz, [sz]),
+    "tracs_transfer_init": (ci, [vp, sz, vp, vp, sz, vp]),
+    "tracs_transfer_add": (ci, [vp, sz, vp, vp, sz, vp, vp]),
+    "tracs_transfer_emit": (ci, [vp, sz, vp, vp]),
+    "tracs_tree_transfer": (ci, [sz, vp, vp, sz, vp, vp, sz, vp]),
+    "tracs_tree_write_transfer": (ci, [cpp, sz, vp, vp, vp, sz, vp, vp, vp, u32, cs, cs, cs]),
+    "tracs_hist_state_bytes": (sz, [sz]),
+    "tracs_hist_init": (ci, [vp, sz, vp]),
+    "tracs_hist_update": (ci, [vp, sz, sz, sz, sz, sz, i32, vp, vp, sz, vp]),
+    "tracs_hist_update_coo": (ci, [vp, vp, vp, sz, vp, vp, sz, vp]),
+    "tracs_hist_emit": (ci, [vp, sz, szp, vp, vp, vp, vp, vp]),
+    "tracs_filter_recomb_device": (ci, [vp, vp, vp, sz, vp, vp, vp, vp, vp]),
+    "tracs_filter_recomb_pairs": (ci, [vp, vp, vp, vp, sz, vp, vp]),
+    "tracs_pair_sites_count": (ci, [vp, vp, vp, sz, vp, vp, u64p, vp]),
+    "tracs_pair_sites_fill": (ci, [vp, vp, vp, sz, vp, i64, vp, vp, sz, ci, vp]),
+    "tracs_fitch_count": (ci, [vp, vp, vp, sz, vp, vp, vp, vp, u64p, vp]),
+    "tracs_fitch_fill": (ci, [vp, vp, vp, sz, sz, sz, vp, i64, vp, vp, vp, sz, vp]),
+    "tracs_fitch_edge_sites": (ci, [vp, vp, vp, sz, vp, vp, vp, sz, vp]),
+    "tracs_filter_recomb_lists": (ci, [vp, vp, vp, sz, sz, vp, vp, vp]),
+    "tracs_fitch_mark_dropped": (ci, [vp, vp, vp, sz, sz, vp, vp, vp, vp]),
+    "tracs_alignment_clone": (ci, [vp, vpp, vp]),
+    "tracs_alignment_restore": (ci, [vp, vp, vp]),
+    "tracs_alignment_mask_subtrees": (ci, [vp, vp, vp, sz, vp, vp, vp, sz, u64p, vp]),
+    "tracs_trans_dist_device": (ci, [vp, vp, sz, dbl, dbl, dbl, ci, vp, vp, vp]),
+    "tracs_trans_dist_dense": (ci, [vp, sz, sz, sz, sz, sz, i32, vp, dbl, dbl, dbl, ci, vp, vp, vp]),
+    "tracs_trans_dist_dense2": (ci, [vp, sz, sz, szp, ci, sz, i32, vp, dbl, dbl, dbl, ci, vp, vp, vp]),
+    "tracs_trans_table_dense": (ci, [vp, sz, sz, sz, sz, sz, i32, vp, dbl, dbl, dbl, ci, ci, u32, u32, vp, vp, vp, vp]),
+    "tracs_trans_table_gather": (ci, [vp, sz, sz, sz, sz, sz, i32, vp, u32, u32, vp, vp, ci, vp, vp, vp, vp]),
+    "tracs_trans_keys_words": (sz, []),
+    "tracs_trans_keys_mark": (ci, [vp, sz, sz, szp, ci, sz, i32, vp, vp, vp]),
+    "tracs_trans_keys_merge": (ci, [vp, vp, ci, vp]),
+    "tracs_trans_keys_info": (ci, [vp, u64p, vp]),
+    "tracs_trans_keys_evaluate": (ci, [vp, u64p, ci, ci, dbl, dbl, dbl, vp, sz, vp]),
+    "tracs_trans_keys_gather": (ci, [vp, sz, sz, szp, ci, sz, i32, vp, vp, u64p, vp, ci, sz, ci, vp, vp, vp]),
+    "tracs_calculate_posteriors_device": (ci, [vp, sz, sz, dp, ci, dbl, vp, vp]),
+    "tracs_posterior_codes_device": (ci, [vp, sz, dp, ci, dbl, vp, vp]),
+    "tracs_find_dirichlet_priors_device": (ci, [vp, sz, sz, ci, dbl, ci, dbl, dp, ip, vp]),
+    "tracs_debug_digamma": (ci, [dp, sz, dp]),
+    "tracs_debug_poison_scratch": (None, [ci]),
+    "tracs_debug_scratch_hits": (sz, [u64p, sz]),
+    "tracs_posterior_codes_cov_device": (ci, [vp, sz, dp, ci, dbl, u32, dbl, dbl, vp, vp]),
+    "tracs_coverage_profile_device": (ci, [vp, sz, vp, sz, vp, vp, vp]),
+    "tracs_consensus_codes_device": (ci, [vp, sz, u32, vp, vp]),
+    "tracs_coverage_profile_device32": (ci, [vp, sz, vp, sz, vp, vp, vp]),
+    "tracs_posterior_codes_cov_device32": (ci, [vp, sz, dp, ci, dbl, u32, dbl, dbl, vp, vp]),
+    "tracs_consensus_codes_device32": (ci, [vp, sz, u32, vp, vp]),
+    "tracs_codes_to_iupac_device": (ci, [vp, sz, vp, vp]),
+    "tracs_alignment_pack_codes": (ci, [vp, vp, sz, vp]),
+    "tracs_alignment_pack_codes_batch": (ci, [vp, vp, sz, sz, sz, vp]),
+    "tracs_connected_components_device": (ci, [vp, vp, sz, sz, vp, i32p, vp]),
+    "tracs_pileup_counts": (ci, [cs, cpp, u64p, sz, ci, dp, u64p]),
+    "tracs_write_posterior_csv": (ci, [cs, dp, sz, sz, ci]),
+    "tracs_warm_up": (None, []),
+    "tracs_distance_open": (ci, [cpp, ci, vpp]),
+    "tracs_distance_open_sites": (ci, [cpp, ci, u64p, sz, u32, vpp]),
+    "tracs_distance_open_rules": (ci, [cpp, ci, P(Rules), vpp]),
+    "tracs_distance_source_nseq": (sz, [vp]),
+    "tracs_distance_source_name": (cs, [vp, sz]),
+    "tracs_distance_source_n_count": (u32, [vp, sz]),
+    "tracs_distance_source_kept": (ci, [vp, sz]),
+    "tracs_distance_rule_sites": (sz, [vp]),
+    "tracs_distance_source_len": (sz, [vp]),
+    "tracs_distance_len": (sz, [vp]),
+    "tracs_distance_kept_sites": (ci, [vp, u64p]),
+    "tracs_distance_nseq": (sz, [vp]),
+    "tracs_distance_name": (cs, [vp, sz]),
+    "tracs_distance_run": (ci, [vp, ci, i32p, dbl, dbl, dbl, dbl, cs, cs, ci, u64p, u64p]),
+    "tracs_distance_forest": (ci, [vp, ci, i32p, dbl, dbl, dbl, dbl, ci, ci, cs, cs, u64p, u64p]),
+    "tracs_distance_ancestors": (ci, [vp, ci, i32p, dbl, dbl, dbl, dbl, ci, ci, cs, cs, cs, cpp, u64p, u64p]),
+    "tracs_distance_tree_run": (ci, [vp, P(TreeRequest), P(TreeResult)]),
+    "tracs_distance_tree_iterate": (ci, [vp, P(TreeRequest), P(TreeIterate), P(TreeResult), P(TreeIterateResult)]),
+    "tracs_distance_tree": (ci, [vp, ci, cs, cs, cs, u64p, u64p]),
+    "tracs_distance_tree_changes": (ci, [vp, ci, cs, cs, cs, cs, cs, cpp, u64p, sz, u64, ci, ci, u64p, u64p, u64p, u64p]),
+    "tracs_distance_tree_filter": (ci, [vp, ci, cs, cs, cs, cs, cs, cs, cpp, u64p, sz, u64, ci, ci, u64p, u64p, u64p, u64p, u64p, u64p]),
+    "tracs_distance_tree_bootstrap": (ci, [vp, ci, cs, cs, cs, u32, u64, cs, u64p, u64p]),
+    "tracs_distance_tree_bootstrap_transfer": (ci, [vp, ci, cs, cs, cs, u32, u64, cs, u64p, u64p]),
+    "tracs_distance_histogram": (ci, [vp, ci, ci, i32p, cs, cs, u64p, u64p]),
+    "tracs_distance_site_census": (ci, [vp, vp, u64p, szp]),
+    "tracs_distance_write_alignment": (ci, [vp, cs, sz, sz, ci, ci, ci, szp]),
+    "tracs_distance_alignment": (vp, [vp]),
+    "tracs_distance_pair_sites": (ci, [vp, u32p, u32p, sz, ci, u64, cs, cpp, u64p, sz, ci, u64p]),
+    "tracs_distance_free": (None, [vp]),
+    "tracs_write_distance_rows": (ci, [cs, cpp, u64p, u64p, u64p, u64p, u64p, dp, dp, dp, sz, ci, dbl, cs, u64p]),
+    "tracs_read_distance_edges": (ci, [cs, ci, dbl, cpp, sz, vpp]),
+    "tracs_edges_count": (sz, [vp]),
+    "tracs_edges_rows": (u64, [vp]),
+    "tracs_edges_n_names": (sz, [vp]),
+    "tracs_edges_name": (cs, [vp, sz]),
+    "tracs_edges_i": (i32p, [vp]),
+    "tracs_edges_j": (i32p, [vp]),
+    "tracs_edges_free": (None, [vp]),
+    "tracs_combine_fasta": (ci, [cs, cpp, cpp, sz, ci, ci, dp, u64p]),
+    "tracs_write_fasta_rows": (ci, [cs, cpp, vp, sz, sz, sz, ci, ci, ci]),
+    "tracs_comm_unique_id": (ci, [vp, sz]),
+    "tracs_comm_create": (ci, [vp, ci, ci, vpp]),
+    "tracs_comm_free": (None, [vp]),
+    "tracs_comm_rank": (ci, [vp]),
+    "tracs_comm_world": (ci, [vp]),
+    "tracs_bcast": (ci, [vp, vp, sz, ci, vp]),
+    "tracs_bcast_planes": (ci, [vp, vp, ci, vp]),
+    "tracs_allgather_panels": (ci, [vp, vp, szp, sz, vp]),
+    "tracs_allreduce": (ci, [vp, vp, sz, ci, ci, vp]),
+    "tracs_reduce_scatter": (ci, [vp, vp, sz, ci, ci, vp]),
+    "tracs_alltoall": (ci, [vp, vp, vp, sz, vp]),
+    "tracs_tri_pack": (ci, [vp, sz, sz, sz, sz, sz, vp, ci, u32, ci, vp, vp, vp]),
+    "tracs_tri_sum": (ci, [vp, sz, sz, sz, sz, sz, vp, ci, vp, sz, ci, ci, u32, ci, vp]),
+    "tracs_rccl_version": (ci, []),
+    "tracs_send": (ci, [vp, vp, sz, ci, vp]),
+    "tracs_recv": (ci, [vp, vp, sz, ci, vp]),
+}
+
+# tracs_amd/csrc/debug_api.h, in its order: exported and bound, but in no public header
+DEBUG_BINDINGS = {
+    "tracs_debug_iupac_mask": (ci, [ci]),
+    "tracs_debug_tile_variant": (cs, []),
+    "tracs_debug_mfma_shape": (cs, []),
+    "tracs_debug_alignment_encoding": (ci, [vp]),
+    "tracs_debug_alignment_kernel": (ci, [vp]),
+    "tracs_debug_alignment_site_classes": (ci, [vp, u64p]),
+    "tracs_debug_alignment_nw_gram": (ci, [vp]),
+    "tracs_debug_alignment_count_source": (ci, [vp, u64p]),
+    "tracs_debug_pair_timing": (None, [ci]),
+    "tracs_debug_pair_ms_mean": (ci, [ci, fp]),
+    "tracs_debug_last_pair_ms": (ci, [fp]),
+    "tracs_debug_force_site_classes": (None, [ci]),
+    "tracs_debug_pack_timing": (None, [ci]),
+    "tracs_debug_pack_stages": (ci, [cs, sz, fp, ci]),
+    "tracs_debug_pack_stage_bytes": (ci, [dp, dp, ci]),
+    "tracs_debug_site_select_timing": (ci, [vp, u64p, sz, u32, ci, fp, szp, ip]),
+    "tracs_debug_sample_select_timing": (ci, [vp, u64p, sz, u8p, ci, fp, szp]),
+    "tracs_debug_lists": (sz, [vp, ci, vp, sz]),
+    "tracs_debug_filter_index": (ci, [vp, dp]),
+    "tracs_debug_last_trans_dist_keys": (u64, []),
+    "tracs_debug_trans_routes": (ci, [dp]),
+    "tracs_debug_hist_routes": (ci, [vp, dp]),
+    "tracs_debug_bootstrap_replicate": (ci, [vp, sz, u64p, u64, u64, dp, vpp, szp]),
+    "tracs_debug_transfer_init": (ci, [vp, sz, vp, vp, sz, dp]),
+    "tracs_debug_differs_table": (ci, [vp, sz]),
+    "tracs_debug_tree_edges_header": (ci, [ci, ci, ci, ci, cs, sz]),
+    "tracs_debug_format_floats": (C.c_long, [dp, sz, cs, sz]),
+    "tracs_debug_read_fasta": (ci, [cs, szp, szp, u64p]),
+}
+
+# every symbol include/tracs_hip.h declares (tests/test_cabi.py checks the .so exports them all)
+SYMBOLS = list(BINDINGS)
 
 
 class TracsError(RuntimeError):
@@ -129,425 +323,9 @@ def load():
         raise TracsError("libtracs_hip.so is missing (%s): build it with `python -m tracs_amd.build`; "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    vp, sz, i32, i64, dbl = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_double
-    u64p, dp = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
-    L.tracs_last_error.restype = C.c_char_p
-    L.tracs_abi_version.restype = C.c_int
-    L.tracs_device_count.restype = C.c_int
-    L.tracs_pairsnp.restype = C.c_int
-    L.tracs_pairsnp.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
-    for name in ("len", "nseq", "seqlen"):
-        f = getattr(L, "tracs_pairsnp_" + name)
-        f.restype = sz
-        f.argtypes = [vp]
-    for name in ("rows", "cols", "distances", "filt_distances", "ncompared"):
-        f = getattr(L, "tracs_pairsnp_" + name)
-        f.restype = u64p
-        f.argtypes = [vp]
-    L.tracs_pairsnp_name.restype = C.c_char_p
-    L.tracs_pairsnp_name.argtypes = [vp, sz]
-    L.tracs_pairsnp_free.restype = None
-    L.tracs_pairsnp_free.argtypes = [vp]
-    L.tracs_trans_dist.restype = C.c_int
-    L.tracs_trans_dist.argtypes = [C.POINTER(i32), dp, sz, dbl, dbl, dbl, dp, dp]
-    L.tracs_lprob_k_given_N.restype = C.c_int
-    L.tracs_lprob_k_given_N.argtypes = [u64p, u64p, dp, sz, dbl, dbl, dp, sz, dp, dp]
-    L.tracs_calculate_posteriors.restype = C.c_int
-    L.tracs_calculate_posteriors.argtypes = [dp, sz, sz, dp, C.c_int, dbl, dp]
-    L.tracs_find_dirichlet_priors.restype = C.c_int
-    L.tracs_find_dirichlet_priors.argtypes = [dp, sz, sz, C.c_int, dbl, C.c_int, dbl, dp, C.POINTER(C.c_int)]
-    L.tracs_find_dirichlet_priors_device.restype = C.c_int
-    L.tracs_find_dirichlet_priors_device.argtypes = [vp, sz, sz, C.c_int, dbl, C.c_int, dbl, dp, C.POINTER(C.c_int), vp]
-    L.tracs_debug_digamma.restype = C.c_int
-    L.tracs_debug_digamma.argtypes = [dp, sz, dp]
-    L.tracs_debug_poison_scratch.restype = None
-    L.tracs_debug_poison_scratch.argtypes = [C.c_int]
-    L.tracs_debug_scratch_hits.restype = sz
-    L.tracs_debug_scratch_hits.argtypes = [u64p, sz]
-    L.tracs_connected_components.restype = C.c_int
-    L.tracs_connected_components.argtypes = [C.POINTER(i32), C.POINTER(i32), sz, sz, C.POINTER(i32), C.POINTER(i32)]
-    L.tracs_alignment_create.restype = C.c_int
-    L.tracs_alignment_create.argtypes = [sz, sz, C.POINTER(vp)]
-    L.tracs_alignment_free.restype = None
-    L.tracs_alignment_free.argtypes = [vp]
-    for name in ("n", "len", "bytes"):
-        f = getattr(L, "tracs_alignment_" + name)
-        f.restype = sz
-        f.argtypes = [vp]
-    L.tracs_alignment_planes.restype = vp
-    L.tracs_alignment_planes.argtypes = [vp]
-    L.tracs_alignment_touch.restype = C.c_int
-    L.tracs_alignment_touch.argtypes = [vp]
-    L.tracs_alignment_pack.restype = C.c_int
-    L.tracs_alignment_pack.argtypes = [vp, vp, sz, sz, C.c_int, vp]
-    L.tracs_alignment_from_fasta.restype = C.c_int
-    L.tracs_alignment_from_fasta.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.POINTER(vp), C.POINTER(vp),
-                                             C.POINTER(sz), C.POINTER(sz)]
-    L.tracs_free.restype = None
-    L.tracs_free.argtypes = [vp]
-    L.tracs_pairsnp_dense.restype = C.c_int
-    L.tracs_pairsnp_dense.argtypes = [vp, sz, sz, sz, vp, vp, sz, vp]
-    L.tracs_pairsnp_dense_thr.restype = C.c_int
-    L.tracs_pairsnp_dense_thr.argtypes = [vp, sz, sz, sz, vp, vp, sz, i32, vp]
-    L.tracs_coo_count.restype = C.c_int
-    L.tracs_coo_count.argtypes = [vp, sz, sz, sz, sz, sz, i32, vp, vp]
-    L.tracs_coo_fill.restype = C.c_int
-    L.tracs_coo_fill.argtypes = [vp, vp, sz, sz, sz, sz, sz, i32, vp, vp, vp, vp, vp, vp]
-    L.tracs_coo_fill_f64.restype = C.c_int
-    L.tracs_coo_fill_f64.argtypes = [vp, sz, sz, sz, sz, sz, i32, vp, vp, vp, vp, vp, vp]
-    L.tracs_distance_open.restype = C.c_int
-    L.tracs_distance_open.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.POINTER(vp)]
-    L.tracs_distance_nseq.restype = sz
-    L.tracs_distance_nseq.argtypes = [vp]
-    L.tracs_distance_name.restype = C.c_char_p
-    L.tracs_distance_name.argtypes = [vp, sz]
-    L.tracs_distance_run.restype = C.c_int
-    L.tracs_distance_run.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dbl, dbl, dbl, dbl, C.c_char_p, C.c_char_p, C.c_int, u64p, u64p]
-    L.tracs_nearest.restype = C.c_int
-    L.tracs_nearest.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
-    L.tracs_knn_state_bytes.restype = sz
-    L.tracs_knn_state_bytes.argtypes = [sz, C.c_int]
-    L.tracs_knn_init.restype = C.c_int
-    L.tracs_knn_init.argtypes = [vp, sz, C.c_int, vp]
-    L.tracs_knn_update.restype = C.c_int
-    L.tracs_knn_update.argtypes = [vp, vp, sz, sz, sz, sz, sz, i32, C.c_int, C.c_int, vp, vp]
-    L.tracs_knn_emit.restype = C.c_int
-    L.tracs_knn_emit.argtypes = [vp, sz, sz, C.c_int, vp, vp, vp, vp, vp, vp]
-    L.tracs_distance_forest.restype = C.c_int
-    L.tracs_distance_forest.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dbl, dbl, dbl, dbl, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
-                                        u64p, u64p]
-    L.tracs_msf_state_bytes.restype = sz
-    L.tracs_msf_state_bytes.argtypes = [sz]
-    L.tracs_msf_init.restype = C.c_int
-    L.tracs_msf_init.argtypes = [vp, sz, vp]
-    L.tracs_msf_update_coo.restype = C.c_int
-    L.tracs_msf_update_coo.argtypes = [vp, sz, sz, vp, vp, vp, C.c_int, vp, dbl, vp, vp, vp, vp, vp, u64p, vp]
-    L.tracs_msf_emit.restype = C.c_int
-    L.tracs_msf_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp]
-    L.tracs_distance_ancestors.restype = C.c_int
-    L.tracs_distance_ancestors.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), dbl, dbl, dbl, dbl, C.c_int, C.c_int, C.c_char_p, C.c_char_p,
-                                           C.c_char_p, C.POINTER(C.c_char_p), u64p, u64p]
-    L.tracs_anc_state_bytes.restype = sz
-    L.tracs_anc_state_bytes.argtypes = [sz]
-    L.tracs_anc_init.restype = C.c_int
-    L.tracs_anc_init.argtypes = [vp, sz, vp, vp]
-    L.tracs_anc_update_coo.restype = C.c_int
-    L.tracs_anc_update_coo.argtypes = [vp, sz, sz, vp, vp, vp, C.c_int, vp, dbl, vp, vp, vp, vp, vp, u64p, vp]
-    L.tracs_anc_emit.restype = C.c_int
-    L.tracs_anc_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.tracs_distance_tree_run.restype = C.c_int
-    L.tracs_distance_tree_run.argtypes = [vp, C.POINTER(TreeRequest), C.POINTER(TreeResult)]
-    L.tracs_distance_tree_iterate.restype = C.c_int
-    L.tracs_distance_tree_iterate.argtypes = [vp, C.POINTER(TreeRequest), C.POINTER(TreeIterate), C.POINTER(TreeResult), C.POINTER(TreeIterateResult)]
-    L.tracs_alignment_clone.restype = C.c_int
-    L.tracs_alignment_clone.argtypes = [vp, C.POINTER(vp), vp]
-    L.tracs_alignment_restore.restype = C.c_int
-    L.tracs_alignment_restore.argtypes = [vp, vp, vp]
-    L.tracs_alignment_mask_subtrees.restype = C.c_int
-    L.tracs_alignment_mask_subtrees.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, u64p, vp]
-    # the five older forms of that request: (handle, kind, path, ref, edges_path), their own arguments, their counters
-    rows = [C.POINTER(C.c_char_p), u64p, sz, C.c_uint64, C.c_int, C.c_int]          # contigs .. create
-    for name, own in (("", [u64p] * 2), ("_changes", [C.c_char_p] * 2 + rows + [u64p] * 4), ("_filter", [C.c_char_p] * 3 + rows + [u64p] * 6),
-                      ("_bootstrap", [C.c_uint32, C.c_uint64, C.c_char_p] + [u64p] * 2), ("_bootstrap_transfer", [C.c_uint32, C.c_uint64, C.c_char_p] + [u64p] * 2)):
-        f = getattr(L, "tracs_distance_tree" + name)
-        f.restype = C.c_int
-        f.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p] + own
-    L.tracs_debug_tree_edges_header.restype = C.c_int
-    L.tracs_debug_tree_edges_header.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, sz]
-    L.tracs_nj_state_bytes.restype = sz
-    L.tracs_nj_state_bytes.argtypes = [sz]
-    L.tracs_nj_init.restype = C.c_int
-    L.tracs_nj_init.argtypes = [vp, sz, vp]
-    L.tracs_nj_load_panel.restype = C.c_int
-    L.tracs_nj_load_panel.argtypes = [vp, sz, vp, vp, sz, sz, sz, C.c_int, vp]
-    L.tracs_nj_load_f64.restype = C.c_int
-    L.tracs_nj_load_f64.argtypes = [vp, sz, vp, sz, vp]
-    L.tracs_nj_run.restype = C.c_int
-    L.tracs_nj_run.argtypes = [vp, sz, vp]
-    L.tracs_bionj_state_bytes.restype = sz
-    L.tracs_bionj_state_bytes.argtypes = [sz]
-    L.tracs_bionj_run.restype = C.c_int
-    L.tracs_bionj_run.argtypes = [vp, sz, vp]
-    L.tracs_nj_emit.restype = C.c_int
-    L.tracs_nj_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.tracs_nj_edges.restype = C.c_int
-    L.tracs_nj_edges.argtypes = [sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(sz)]
-    L.tracs_tree_write.restype = C.c_int
-    L.tracs_tree_write.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, C.c_char_p, C.c_char_p, C.c_char_p]
-    L.tracs_tree_write_changes.restype = C.c_int
-    L.tracs_tree_write_changes.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, vp, C.c_char_p, C.c_char_p, C.c_char_p]
-    L.tracs_fitch_count.restype = C.c_int
-    L.tracs_fitch_count.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, u64p, vp]
-    L.tracs_fitch_fill.restype = C.c_int
-    L.tracs_fitch_fill.argtypes = [vp, vp, vp, sz, sz, sz, vp, i64, vp, vp, vp, sz, vp]
-    L.tracs_fitch_edge_sites.restype = C.c_int
-    L.tracs_fitch_edge_sites.argtypes = [vp, vp, vp, sz, vp, vp, vp, sz, vp]
-    L.tracs_filter_recomb_lists.restype = C.c_int
-    L.tracs_filter_recomb_lists.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
-    L.tracs_fitch_mark_dropped.restype = C.c_int
-    L.tracs_fitch_mark_dropped.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
-    L.tracs_tree_write_filtered.restype = C.c_int
-    L.tracs_tree_write_filtered.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, vp, vp, C.c_char_p, C.c_char_p, C.c_char_p]
-    L.tracs_bootstrap_weights.restype = C.c_int
-    L.tracs_bootstrap_weights.argtypes = [sz, C.c_uint64, C.c_uint64, vp, vp]
-    L.tracs_debug_bootstrap_replicate.restype = C.c_int
-    L.tracs_debug_bootstrap_replicate.argtypes = [vp, sz, u64p, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(vp), C.POINTER(sz)]
-    L.tracs_alignment_gather_sites.restype = C.c_int
-    L.tracs_alignment_gather_sites.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(sz), vp]
-    L.tracs_tree_support.restype = C.c_int
-    L.tracs_tree_support.argtypes = [sz, vp, vp, sz, vp, vp, sz, vp]
-    L.tracs_tree_write_support.restype = C.c_int
-    L.tracs_tree_write_support.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, vp, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p]
-    L.tracs_tree_transfer_program.restype = C.c_int
-    L.tracs_tree_transfer_program.argtypes = [sz, vp, vp, sz, vp, C.POINTER(sz)]
-    L.tracs_transfer_state_bytes.restype = sz
-    L.tracs_transfer_state_bytes.argtypes = [sz]
-    L.tracs_transfer_init.restype = C.c_int
-    L.tracs_transfer_init.argtypes = [vp, sz, vp, vp, sz, vp]
-    L.tracs_debug_transfer_init.restype = C.c_int
-    L.tracs_debug_transfer_init.argtypes = [vp, sz, vp, vp, sz, C.POINTER(C.c_double)]
-    L.tracs_transfer_add.restype = C.c_int
-    L.tracs_transfer_add.argtypes = [vp, sz, vp, vp, sz, vp, vp]
-    L.tracs_transfer_emit.restype = C.c_int
-    L.tracs_transfer_emit.argtypes = [vp, sz, vp, vp]
-    L.tracs_tree_transfer.restype = C.c_int
-    L.tracs_tree_transfer.argtypes = [sz, vp, vp, sz, vp, vp, sz, vp]
-    L.tracs_tree_write_transfer.restype = C.c_int
-    L.tracs_tree_write_transfer.argtypes = [C.POINTER(C.c_char_p), sz, vp, vp, vp, sz, vp, vp, vp, C.c_uint32, C.c_char_p, C.c_char_p, C.c_char_p]
-    L.tracs_distance_histogram.restype = C.c_int
-    L.tracs_distance_histogram.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_char_p, C.c_char_p, u64p, u64p]
-    L.tracs_hist_state_bytes.restype = sz
-    L.tracs_hist_state_bytes.argtypes = [sz]
-    L.tracs_hist_init.restype = C.c_int
-    L.tracs_hist_init.argtypes = [vp, sz, vp]
-    L.tracs_hist_update.restype = C.c_int
-    L.tracs_hist_update.argtypes = [vp, sz, sz, sz, sz, sz, i32, vp, vp, sz, vp]
-    L.tracs_hist_update_coo.restype = C.c_int
-    L.tracs_hist_update_coo.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
-    L.tracs_hist_emit.restype = C.c_int
-    L.tracs_hist_emit.argtypes = [vp, sz, C.POINTER(sz), vp, vp, vp, vp, vp]
-    L.tracs_alignment_site_n_counts.restype = C.c_int
-    L.tracs_alignment_site_n_counts.argtypes = [vp, vp, vp]
-    L.tracs_alignment_select_sites.restype = C.c_int
-    L.tracs_alignment_select_sites.argtypes = [vp, u64p, sz, C.c_uint32, C.POINTER(vp), u64p, C.POINTER(sz), vp]
-    L.tracs_pairsnp_sites.restype = C.c_int
-    L.tracs_pairsnp_sites.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, u64p, sz, C.c_uint32, C.POINTER(vp)]
-    L.tracs_nearest_sites.restype = C.c_int
-    L.tracs_nearest_sites.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u64p, sz, C.c_uint32, C.POINTER(vp)]
-    L.tracs_distance_open_sites.restype = C.c_int
-    L.tracs_distance_open_sites.argtypes = [C.POINTER(C.c_char_p), C.c_int, u64p, sz, C.c_uint32, C.POINTER(vp)]
-    L.tracs_distance_source_len.restype = sz
-    L.tracs_distance_source_len.argtypes = [vp]
-    L.tracs_distance_len.restype = sz
-    L.tracs_distance_len.argtypes = [vp]
-    L.tracs_distance_kept_sites.restype = C.c_int
-    L.tracs_distance_kept_sites.argtypes = [vp, u64p]
-    L.tracs_alignment_sample_n_counts.restype = C.c_int
-    L.tracs_alignment_sample_n_counts.argtypes = [vp, u64p, sz, vp, vp]
-    L.tracs_alignment_select_samples.restype = C.c_int
-    L.tracs_alignment_select_samples.argtypes = [vp, C.POINTER(C.c_uint8), C.POINTER(vp), vp]
-    L.tracs_pairs_min_sites.restype = C.c_int
-    L.tracs_pairs_min_sites.argtypes = [vp, vp, sz, sz, sz, sz, sz, i32, C.c_uint32, vp]
-    rp = C.POINTER(Rules)
-    L.tracs_pairsnp_rules.restype = C.c_int
-    L.tracs_pairsnp_rules.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, rp, C.POINTER(vp)]
-    L.tracs_nearest_rules.restype = C.c_int
-    L.tracs_nearest_rules.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, rp, C.POINTER(vp)]
-    L.tracs_distance_open_rules.restype = C.c_int
-    L.tracs_distance_open_rules.argtypes = [C.POINTER(C.c_char_p), C.c_int, rp, C.POINTER(vp)]
-    for kind in ("pairsnp", "distance"):
-        for name, res, args in (("source_nseq", sz, [vp]), ("source_name", C.c_char_p, [vp, sz]), ("source_n_count", C.c_uint32, [vp, sz]),
-                                ("source_kept", C.c_int, [vp, sz]), ("rule_sites", sz, [vp])):
-            f = getattr(L, "tracs_%s_%s" % (kind, name))
-            f.restype = res
-            f.argtypes = args
-    L.tracs_debug_sample_select_timing.restype = C.c_int
-    L.tracs_debug_sample_select_timing.argtypes = [vp, u64p, sz, C.POINTER(C.c_uint8), C.c_int, C.POINTER(C.c_float), C.POINTER(sz)]
-    L.tracs_debug_site_select_timing.restype = C.c_int
-    L.tracs_debug_site_select_timing.argtypes = [vp, u64p, sz, C.c_uint32, C.c_int, C.POINTER(C.c_float), C.POINTER(sz), C.POINTER(C.c_int)]
-    L.tracs_debug_hist_routes.restype = C.c_int
-    L.tracs_debug_hist_routes.argtypes = [vp, C.POINTER(C.c_double)]
-    L.tracs_warm_up.restype = None
-    L.tracs_warm_up.argtypes = []
-    L.tracs_distance_free.restype = None
-    L.tracs_distance_free.argtypes = [vp]
-    L.tracs_edges_count_f64.restype = C.c_int
-    L.tracs_edges_count_f64.argtypes = [vp, vp, sz, sz, sz, sz, sz, C.c_int32, dbl, vp, vp]
-    L.tracs_edges_fill_f64.restype = C.c_int
-    L.tracs_edges_fill_f64.argtypes = [vp, vp, sz, sz, sz, sz, sz, C.c_int32, dbl, vp, vp, vp, vp, vp]
-    L.tracs_filter_recomb_device.restype = C.c_int
-    L.tracs_filter_recomb_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp]
-    L.tracs_filter_recomb_pairs.restype = C.c_int
-    L.tracs_filter_recomb_pairs.argtypes = [vp, vp, vp, vp, sz, vp, vp]
-    L.tracs_debug_filter_index.restype = C.c_int
-    L.tracs_debug_filter_index.argtypes = [vp, C.POINTER(C.c_double)]
-    L.tracs_trans_dist_device.restype = C.c_int
-    L.tracs_trans_dist_device.argtypes = [vp, vp, sz, dbl, dbl, dbl, C.c_int, vp, vp, vp]
-    L.tracs_trans_dist_dense.restype = C.c_int
-    L.tracs_trans_dist_dense.argtypes = [vp, sz, sz, sz, sz, sz, i32, vp, dbl, dbl, dbl, C.c_int, vp, vp, vp]
-    L.tracs_trans_dist_dense2.restype = C.c_int
-    L.tracs_trans_dist_dense2.argtypes = [vp, sz, sz, C.POINTER(sz), C.c_int, sz, i32, vp, dbl, dbl, dbl, C.c_int, vp, vp, vp]
-    L.tracs_trans_table_dense.restype = C.c_int
-    L.tracs_trans_table_dense.argtypes = [vp, sz, sz, sz, sz, sz, C.c_int32, vp, dbl, dbl, dbl, C.c_int, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
-    L.tracs_trans_table_gather.restype = C.c_int
-    L.tracs_trans_table_gather.argtypes = [vp, sz, sz, sz, sz, sz, C.c_int32, vp, C.c_uint32, C.c_uint32, vp, vp, C.c_int, vp, vp, vp, vp]
-    L.tracs_trans_keys_words.restype = sz
-    L.tracs_trans_keys_words.argtypes = []
-    L.tracs_trans_keys_mark.restype = C.c_int
-    L.tracs_trans_keys_mark.argtypes = [vp, sz, sz, C.POINTER(sz), C.c_int, sz, C.c_int32, vp, vp, vp]
-    L.tracs_trans_keys_merge.restype = C.c_int
-    L.tracs_trans_keys_merge.argtypes = [vp, vp, C.c_int, vp]
-    L.tracs_trans_keys_info.restype = C.c_int
-    L.tracs_trans_keys_info.argtypes = [vp, C.POINTER(C.c_uint64), vp]
-    L.tracs_trans_keys_evaluate.restype = C.c_int
-    L.tracs_trans_keys_evaluate.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int, C.c_int, dbl, dbl, dbl, vp, sz, vp]
-    L.tracs_trans_keys_gather.restype = C.c_int
-    L.tracs_trans_keys_gather.argtypes = [vp, sz, sz, C.POINTER(sz), C.c_int, sz, C.c_int32, vp, vp, C.POINTER(C.c_uint64), vp, C.c_int, sz, C.c_int, vp, vp, vp]
-    L.tracs_calculate_posteriors_device.restype = C.c_int
-    L.tracs_calculate_posteriors_device.argtypes = [vp, sz, sz, dp, C.c_int, dbl, vp, vp]
-    L.tracs_posterior_codes_device.restype = C.c_int
-    L.tracs_posterior_codes_device.argtypes = [vp, sz, dp, C.c_int, dbl, vp, vp]
-    L.tracs_posterior_codes_cov_device.restype = C.c_int
-    L.tracs_posterior_codes_cov_device.argtypes = [vp, sz, dp, C.c_int, dbl, C.c_uint32, dbl, dbl, vp, vp]
-    L.tracs_codes_to_iupac_device.restype = C.c_int
-    L.tracs_codes_to_iupac_device.argtypes = [vp, sz, vp, vp]
-    L.tracs_alignment_pack_codes.restype = C.c_int
-    L.tracs_alignment_pack_codes.argtypes = [vp, vp, sz, vp]
-    L.tracs_alignment_pack_codes_batch.restype = C.c_int
-    L.tracs_alignment_pack_codes_batch.argtypes = [vp, vp, sz, sz, sz, vp]
-    L.tracs_connected_components_device.restype = C.c_int
-    L.tracs_connected_components_device.argtypes = [vp, vp, sz, sz, vp, C.POINTER(i32), vp]
-    cpp = C.POINTER(C.c_char_p)
-    L.tracs_coverage_profile_device.restype = C.c_int
-    L.tracs_coverage_profile_device.argtypes = [vp, sz, vp, sz, vp, vp, vp]
-    L.tracs_consensus_codes_device.restype = C.c_int
-    L.tracs_consensus_codes_device.argtypes = [vp, sz, C.c_uint32, vp, vp]
-    L.tracs_coverage_profile_device32.restype = C.c_int
-    L.tracs_coverage_profile_device32.argtypes = [vp, sz, vp, sz, vp, vp, vp]
-    L.tracs_posterior_codes_cov_device32.restype = C.c_int
-    L.tracs_posterior_codes_cov_device32.argtypes = [vp, sz, dp, C.c_int, dbl, C.c_uint32, dbl, dbl, vp, vp]
-    L.tracs_consensus_codes_device32.restype = C.c_int
-    L.tracs_consensus_codes_device32.argtypes = [vp, sz, C.c_uint32, vp, vp]
-    L.tracs_pileup_counts.restype = C.c_int
-    L.tracs_pileup_counts.argtypes = [C.c_char_p, cpp, u64p, sz, C.c_int, dp, u64p]
-    L.tracs_write_posterior_csv.restype = C.c_int
-    L.tracs_write_posterior_csv.argtypes = [C.c_char_p, dp, sz, sz, C.c_int]
-    L.tracs_write_distance_rows.restype = C.c_int
-    L.tracs_write_distance_rows.argtypes = [C.c_char_p, cpp, u64p, u64p, u64p, u64p, u64p, dp, dp, dp, sz, C.c_int, dbl, C.c_char_p, u64p]
-    L.tracs_debug_format_floats.restype = C.c_long
-    L.tracs_debug_format_floats.argtypes = [dp, sz, C.c_char_p, sz]
-    L.tracs_read_distance_edges.restype = C.c_int
-    L.tracs_read_distance_edges.argtypes = [C.c_char_p, C.c_int, dbl, cpp, sz, C.POINTER(vp)]
-    L.tracs_edges_count.restype = sz
-    L.tracs_edges_count.argtypes = [vp]
-    L.tracs_edges_rows.restype = C.c_uint64
-    L.tracs_edges_rows.argtypes = [vp]
-    L.tracs_edges_n_names.restype = sz
-    L.tracs_edges_n_names.argtypes = [vp]
-    L.tracs_edges_name.restype = C.c_char_p
-    L.tracs_edges_name.argtypes = [vp, sz]
-    L.tracs_edges_i.restype = C.POINTER(i32)
-    L.tracs_edges_i.argtypes = [vp]
-    L.tracs_edges_j.restype = C.POINTER(i32)
-    L.tracs_edges_j.argtypes = [vp]
-    L.tracs_edges_free.restype = None
-    L.tracs_edges_free.argtypes = [vp]
-    L.tracs_combine_fasta.restype = C.c_int
-    L.tracs_combine_fasta.argtypes = [C.c_char_p, cpp, cpp, sz, C.c_int, C.c_int, dp, u64p]
-    L.tracs_debug_read_fasta.restype = C.c_int
-    L.tracs_debug_read_fasta.argtypes = [C.c_char_p, C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_uint64)]
-    L.tracs_debug_alignment_encoding.restype = C.c_int
-    L.tracs_debug_alignment_encoding.argtypes = [vp]
-    L.tracs_debug_alignment_kernel.restype = C.c_int
-    L.tracs_debug_alignment_kernel.argtypes = [vp]
-    L.tracs_debug_alignment_site_classes.restype = C.c_int
-    L.tracs_debug_alignment_site_classes.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.tracs_pairsnp_notify_distances.restype = None
-    L.tracs_pairsnp_notify_distances.argtypes = [vp]
-    L.tracs_set_stream_policy.restype = None
-    L.tracs_set_stream_policy.argtypes = [C.c_int]
-    L.tracs_alignment_hint_rows.restype = C.c_int
-    L.tracs_alignment_hint_rows.argtypes = [vp, C.POINTER(sz), C.c_int]
-    L.tracs_debug_alignment_nw_gram.restype = C.c_int
-    L.tracs_debug_alignment_nw_gram.argtypes = [vp]
-    L.tracs_debug_alignment_count_source.restype = C.c_int
-    L.tracs_debug_alignment_count_source.argtypes = [vp, C.POINTER(C.c_uint64)]
-    L.tracs_debug_force_site_classes.restype = None
-    L.tracs_debug_force_site_classes.argtypes = [C.c_int]
-    L.tracs_debug_pack_timing.restype = None
-    L.tracs_debug_pack_timing.argtypes = [C.c_int]
-    L.tracs_debug_pack_stages.restype = C.c_int
-    L.tracs_debug_pack_stages.argtypes = [C.c_char_p, sz, C.POINTER(C.c_float), C.c_int]
-    L.tracs_debug_pack_stage_bytes.restype = C.c_int
-    L.tracs_debug_pack_stage_bytes.argtypes = [dp, dp, C.c_int]
-    L.tracs_comm_unique_id.restype = C.c_int
-    L.tracs_comm_unique_id.argtypes = [vp, sz]
-    L.tracs_comm_create.restype = C.c_int
-    L.tracs_comm_create.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
-    L.tracs_comm_free.restype = None
-    L.tracs_comm_free.argtypes = [vp]
-    L.tracs_comm_rank.restype = C.c_int
-    L.tracs_comm_rank.argtypes = [vp]
-    L.tracs_comm_world.restype = C.c_int
-    L.tracs_comm_world.argtypes = [vp]
-    L.tracs_bcast.restype = C.c_int
-    L.tracs_bcast.argtypes = [vp, vp, sz, C.c_int, vp]
-    L.tracs_bcast_planes.restype = C.c_int
-    L.tracs_bcast_planes.argtypes = [vp, vp, C.c_int, vp]
-    L.tracs_allgather_panels.restype = C.c_int
-    L.tracs_allgather_panels.argtypes = [vp, vp, C.POINTER(sz), sz, vp]
-    L.tracs_allreduce.restype = C.c_int
-    L.tracs_allreduce.argtypes = [vp, vp, sz, C.c_int, C.c_int, vp]
-    L.tracs_reduce_scatter.restype = C.c_int
-    L.tracs_reduce_scatter.argtypes = [vp, vp, sz, C.c_int, C.c_int, vp]
-    L.tracs_alltoall.restype = C.c_int
-    L.tracs_alltoall.argtypes = [vp, vp, vp, sz, vp]
-    L.tracs_tri_pack.restype = C.c_int
-    L.tracs_tri_pack.argtypes = [vp, sz, sz, sz, sz, sz, vp, C.c_int, C.c_uint32, C.c_int, vp, vp, vp]
-    L.tracs_tri_sum.restype = C.c_int
-    L.tracs_tri_sum.argtypes = [vp, sz, sz, sz, sz, sz, vp, C.c_int, vp, sz, C.c_int, C.c_int, C.c_uint32, C.c_int, vp]
-    L.tracs_rccl_version.restype = C.c_int
-    L.tracs_rccl_version.argtypes = []
-    L.tracs_send.restype = C.c_int
-    L.tracs_send.argtypes = [vp, vp, sz, C.c_int, vp]
-    L.tracs_recv.restype = C.c_int
-    L.tracs_recv.argtypes = [vp, vp, sz, C.c_int, vp]
-    L.tracs_debug_lists.restype = sz
-    L.tracs_debug_lists.argtypes = [vp, C.c_int, vp, sz]
-    L.tracs_debug_pair_timing.restype = None
-    L.tracs_debug_pair_timing.argtypes = [C.c_int]
-    L.tracs_debug_last_pair_ms.restype = C.c_int
-    L.tracs_debug_pair_ms_mean.restype = C.c_int
-    L.tracs_debug_pair_ms_mean.argtypes = [C.c_int, C.POINTER(C.c_float)]
-    L.tracs_debug_last_pair_ms.argtypes = [C.POINTER(C.c_float)]
-    L.tracs_debug_tile_variant.restype = C.c_char_p
-    L.tracs_debug_mfma_shape.restype = C.c_char_p
-    L.tracs_debug_last_trans_dist_keys.restype = C.c_uint64
-    L.tracs_debug_trans_routes.restype = C.c_int
-    L.tracs_debug_trans_routes.argtypes = [C.POINTER(C.c_double)]
-    L.tracs_debug_iupac_mask.restype = C.c_int
-    L.tracs_debug_iupac_mask.argtypes = [C.c_int]
-    L.tracs_alignment_site_census.restype = C.c_int
-    L.tracs_alignment_site_census.argtypes = [vp, vp, u64p, C.POINTER(sz), vp]
-    L.tracs_alignment_unpack.restype = C.c_int
-    L.tracs_alignment_unpack.argtypes = [vp, sz, sz, vp, sz, vp]
-    L.tracs_write_fasta_rows.restype = C.c_int
-    L.tracs_write_fasta_rows.argtypes = [C.c_char_p, cpp, vp, sz, sz, sz, C.c_int, C.c_int, C.c_int]
-    L.tracs_distance_site_census.restype = C.c_int
-    L.tracs_distance_site_census.argtypes = [vp, vp, u64p, C.POINTER(sz)]
-    L.tracs_distance_write_alignment.restype = C.c_int
-    L.tracs_distance_write_alignment.argtypes = [vp, C.c_char_p, sz, sz, C.c_int, C.c_int, C.c_int, C.POINTER(sz)]
-    L.tracs_pair_sites_count.restype = C.c_int
-    L.tracs_pair_sites_count.argtypes = [vp, vp, vp, sz, vp, vp, u64p, vp]
-    L.tracs_pair_sites_fill.restype = C.c_int
-    L.tracs_pair_sites_fill.argtypes = [vp, vp, vp, sz, vp, i64, vp, vp, sz, C.c_int, vp]
-    L.tracs_distance_alignment.restype = vp
-    L.tracs_distance_alignment.argtypes = [vp]
-    L.tracs_distance_pair_sites.restype = C.c_int
-    L.tracs_distance_pair_sites.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), sz, C.c_int, C.c_uint64, C.c_char_p, cpp, u64p, sz,
-                                            C.c_int, u64p]
-    L.tracs_debug_differs_table.restype = C.c_int
-    L.tracs_debug_differs_table.argtypes = [vp, sz]
+    for name, (restype, argtypes) in {**BINDINGS, **DEBUG_BINDINGS}.items():
+        f = getattr(L, name)                    # a name the library does not export: ctypes' AttributeError, as it is
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -555,7 +333,7 @@ def load():
 def check(rc):
     """Raise RuntimeError with the library's message (the reference raises RuntimeError with the
     same strings: src/pairsnp.hpp:86,96-97,342) on a non-zero return code."""
-    if rc == -8:                                   # TRACS_E_INTERRUPTED: Ctrl-C arrived while the library held the call
+    if rc == E_INTERRUPTED:                        # Ctrl-C arrived while the library held the call
         raise KeyboardInterrupt("Interrupted by user!")
     if rc != 0:
         msg = load().tracs_last_error()

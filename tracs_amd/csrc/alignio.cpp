@@ -26,6 +26,7 @@
 
 #include "fasta.h"
 #include "rowwriter.h"
+#include "debug_api.h"
 
 namespace tracs {
 void set_error(const std::string &msg);

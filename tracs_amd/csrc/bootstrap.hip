@@ -13,6 +13,7 @@
 // and, on the host, the comparison of two trees' splits (tracs_tree_support).
 #include "common.h"
 #include "scan_kernels.h"
+#include "debug_api.h"
 
 #include <algorithm>
 #include <chrono>

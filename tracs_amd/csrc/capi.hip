@@ -6,6 +6,7 @@
 #include "common.h"
 #include "fasta.h"
 #include "rowwriter.h"
+#include "debug_api.h"
 
 #include <algorithm>
 #include <atomic>

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "filter_math.h"
 #include "pairsnp_kernels.h"
+#include "debug_api.h"
 
 #include <algorithm>
 #include <chrono>

@@ -26,6 +26,7 @@
 // per cell from an array of n labels that stays in L2; the row's label is wave-uniform.
 #include "common.h"
 #include "scan_kernels.h"
+#include "debug_api.h"
 
 #include <algorithm>
 #include <cstdlib>

@@ -7,6 +7,7 @@
 //                          the site DIFFERS -- two samples with disjoint masks, the condition under which it adds 1 to some d(i, j)
 //     unpack_kernel        samples [first, first + count) -> canonical text ("XACMGRSVTWYHKDBN"[mask]), one row per sample
 #include "common.h"
+#include "debug_api.h"
 
 #include <algorithm>
 #include <cstring>

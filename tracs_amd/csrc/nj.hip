@@ -28,6 +28,7 @@
 // A BIONJ state is a neighbour-joining state followed by V, RV and V's two scratch rows: every other entry point sees the prefix.
 #include "common.h"
 #include "pair_select.h"
+#include "debug_api.h"
 
 #include <charconv>
 #include <cmath>

@@ -19,6 +19,7 @@
 //   counted / full sites                                        pairsnp_mfma_kernel<COUNT>: compared-sites counts, one operand plane
 #include "pairsnp_kernels.h"
 #include "scan_kernels.h"
+#include "debug_api.h"
 
 #include <algorithm>
 #include <cmath>

@@ -11,6 +11,7 @@
 //     select_samples_kernel    the five planes of the kept samples
 //     pair_min_sites_kernel    the veto pass over the cells of one dense call
 #include "common.h"
+#include "debug_api.h"
 
 #include <algorithm>
 #include <cstring>

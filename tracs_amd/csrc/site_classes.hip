@@ -39,6 +39,7 @@
 //     minority lists          general_sparse.hip: per-site lists from the N plane + the flagged samples only, per-sample
 //                             lists from the N plane: 3 reads of ONE plane instead of 4 reads of the alignment.
 #include "pairsnp_kernels.h"
+#include "debug_api.h"
 
 #include <algorithm>
 #include <chrono>

@@ -24,6 +24,7 @@
 // samples (k walks of a cN-entry list, not cN walks of a k-entry list), and the per-sample streams of N entries that rounds 2-3
 // built (s_nn, s_inl: 3.3 GB written once per pack from two more reads of the N plane) do not exist.
 #include "pairsnp_kernels.h"
+#include "debug_api.h"
 
 #include <algorithm>
 #include <cstdio>

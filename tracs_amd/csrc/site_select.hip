@@ -11,6 +11,7 @@
 //     site_list_kernel       the kept sites in order (what an output group's first and last site are looked up in)
 //     select_sites_kernel    the five planes of the kept sites
 #include "common.h"
+#include "debug_api.h"
 
 #include <algorithm>
 #include <cstring>

@@ -15,6 +15,7 @@
 //      same quantities in the same order, so the truncation point k_stop is the reference's.
 //   3. gather: each element copies the result of its slot.
 #include "common.h"
+#include "debug_api.h"
 
 #include <cmath>
 #include <algorithm>

@@ -14,6 +14,7 @@
 //                  one Mt word the wave needs for a leaf are wave-uniform; only the counts are per lane.
 #include "common.h"
 #include "pair_select.h"
+#include "debug_api.h"
 
 #include <algorithm>
 #include <chrono>
