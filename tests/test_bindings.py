@@ -16,7 +16,7 @@ from tracs_amd import _lib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PUBLIC_H = os.path.join(ROOT, "include", "tracs_hip.h")
 DEBUG_H = os.path.join(ROOT, "tracs_amd", "csrc", "debug_api.h")
-N_DEBUG_ONLY = 28                     # the tracs_debug_* entry points debug_api.h declares (three more are in the public header)
+N_DEBUG_ONLY = 30                     # the tracs_debug_* entry points debug_api.h declares (three more are in the public header)
 
 # the ctypes mirror of every struct the public header defines with a body
 MIRRORS = {"tracs_rules": _lib.Rules, "tracs_tree_request": _lib.TreeRequest, "tracs_tree_result": _lib.TreeResult,

@@ -282,6 +282,8 @@ DEBUG_BINDINGS = {
     "tracs_debug_transfer_init": (ci, [vp, sz, vp, vp, sz, dp]),
     "tracs_debug_differs_table": (ci, [vp, sz]),
     "tracs_debug_tree_edges_header": (ci, [ci, ci, ci, ci, cs, sz]),
+    "tracs_debug_alloc_stats": (None, [u64p]),
+    "tracs_debug_fail_alloc": (None, [C.c_long]),
     "tracs_debug_format_floats": (C.c_long, [dp, sz, cs, sz]),
     "tracs_debug_read_fasta": (ci, [cs, szp, szp, u64p]),
 }

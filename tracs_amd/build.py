@@ -8,7 +8,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libtracs_hip.so")
 SOURCES = ["capi.hip", "pairsnp.hip", "pairsnp_mfma.hip", "general_sparse.hip", "site_lists.hip", "site_classes.hip", "site_select.hip", "sample_select.hip", "msa_out.hip", "transcluster.hip", "dmultinomial.hip", "cluster.hip", "filter.hip", "filter_lists.hip", "pair_sites.hip", "nearest.hip", "forest.hip", "ancestors.hip", "nj.hip", "bootstrap.hip", "transfer.hip", "fitch.hip", "tree_mask.hip", "histogram.hip", "dirichlet.hip", "exchange.hip", "fasta.cpp", "alignio.cpp", "comm.cpp"]
-HEADERS = ["common.h", "pairsnp_kernels.h", "filter_math.h", "scan_kernels.h", "pair_select.h", "fasta.h", "rowwriter.h", "debug_api.h", os.path.join("..", "..", "include", "tracs_hip.h")]
+HEADERS = ["common.h", "alloc_path.h", "pairsnp_kernels.h", "filter_math.h", "scan_kernels.h", "pair_select.h", "fasta.h", "rowwriter.h", "debug_api.h", os.path.join("..", "..", "include", "tracs_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fgpu-rdc" if False else "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function", "-ffp-contract=off"]

@@ -222,31 +222,30 @@ int gather_sites(const tracs_alignment *src, const uint32_t *weights, tracs_alig
     unsigned *first = nullptr;
     int rc;
     if ((rc = workspace_get(WS_BS_OFFSETS, L + 1, &off))) return rc;
-    tracs_alignment *dst = nullptr;
-    auto fail = [&](int r) { (void)hipStreamSynchronize(stream); if (dst) tracs_alignment_free(dst); return r; };
-#define GS_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { set_error(std::string(#x ": ") + hipGetErrorString(e__)); return fail(TRACS_E_HIP); } } while (0)
     hipLaunchKernelGGL(widen_weights_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, stream, weights, L, off);
     hipLaunchKernelGGL(scan_i64_inplace_kernel, dim3(1), dim3(1024), 0, stream, off, L);
-    GS_CHECK(hipGetLastError());
+    TRACS_HIP_CHECK(hipGetLastError());
     long long total = 0;
-    GS_CHECK(hipMemcpyAsync(&total, off + L, 8, hipMemcpyDeviceToHost, stream));
-    GS_CHECK(hipStreamSynchronize(stream));
+    TRACS_HIP_CHECK(hipMemcpyAsync(&total, off + L, 8, hipMemcpyDeviceToHost, stream));
+    TRACS_HIP_CHECK(hipStreamSynchronize(stream));
     if (total <= 0) {
-        if (empty_ok) return fail(TRACS_OK);
+        if (empty_ok) return TRACS_OK;
         set_error("tracs_alignment_gather_sites: no column drawn");
-        return fail(TRACS_E_ARG);
+        return TRACS_E_ARG;
     }
     if ((unsigned long long)total >= (1ull << 32)) {
         set_error("tracs_alignment_gather_sites: the weights sum to " + std::to_string(total) + " columns, 2^32 or more");
-        return fail(TRACS_E_ARG);
+        return TRACS_E_ARG;
     }
     const unsigned groups_dst = (unsigned)groups_for((size_t)total);
-    if ((rc = workspace_get(WS_BS_STARTS, groups_dst, &first))) return fail(rc);
+    if ((rc = workspace_get(WS_BS_STARTS, groups_dst, &first))) return rc;
     hipLaunchKernelGGL(gather_starts_kernel, dim3((groups_dst + 255) / 256), dim3(256), 0, stream, off, (unsigned)L, groups_dst, first);
-    GS_CHECK(hipGetLastError());
+    TRACS_HIP_CHECK(hipGetLastError());
     stage(0);
-    if ((rc = tracs_alignment_create(src->n, (size_t)total, &dst))) return fail(rc);
-    GS_CHECK(hipStreamSynchronize(nullptr));               // the new planes are cleared on the null stream
+    tracs_alignment *made = nullptr;
+    if ((rc = tracs_alignment_create(src->n, (size_t)total, &made))) return rc;
+    AlignmentOwner dst(made);
+    TRACS_HIP_CHECK(hipStreamSynchronize(nullptr));               // the new planes are cleared on the null stream
     stage(1);
     const size_t blocks_y = src->n_pad / 64, slice = 65535;
     for (size_t y0 = 0; y0 < blocks_y; y0 += slice) {
@@ -254,12 +253,11 @@ int gather_sites(const tracs_alignment *src, const uint32_t *weights, tracs_alig
         hipLaunchKernelGGL(gather_sites_kernel, grid, dim3(256), 0, stream, src->planes, off, first, (unsigned)L, (unsigned long long)total, dst->planes,
                            src->n_pad, (unsigned)(y0 * 64), (unsigned)src->n, groups_dst);
     }
-    GS_CHECK(hipGetLastError());
-    GS_CHECK(hipStreamSynchronize(stream));
+    TRACS_HIP_CHECK(hipGetLastError());
+    TRACS_HIP_CHECK(hipStreamSynchronize(stream));
     stage(2);
-#undef GS_CHECK
     if (n_out) *n_out = (size_t)total;
-    *out = dst;
+    *out = dst.release();
     return TRACS_OK;
 }
 
@@ -336,21 +334,19 @@ int tracs_debug_bootstrap_replicate(const tracs_alignment *var, size_t L, const 
     const size_t words = (L + 31) / 32, V = var->L;
     std::vector<unsigned> bits, woff;
     if (bootstrap_column_words(differs, L, bits, woff) != V) { set_error("tracs_debug_bootstrap_replicate: the bitmap does not have the handle's columns"); return TRACS_E_ARG; }
-    unsigned *d = nullptr;
-    TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), (2 * words + V) * 4));
-    auto done = [&](int r) { (void)hipDeviceSynchronize(); (void)hipFree(d); return r; };
-    if (hipMemcpy(d, bits.data(), words * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + words, woff.data(), words * 4, hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        set_error("tracs_debug_bootstrap_replicate: upload failed");
-        return done(TRACS_E_HIP);
-    }
+    DeviceArray<unsigned> buf;
+    int rc = buf.alloc(2 * words + V, "replicate bitmap and weights");
+    if (rc) return rc;
+    unsigned *const d = buf.get();
+    TRACS_HIP_CHECK(hipMemcpy(d, bits.data(), words * 4, hipMemcpyHostToDevice));
+    TRACS_HIP_CHECK(hipMemcpy(d + words, woff.data(), words * 4, hipMemcpyHostToDevice));
+    TRACS_HIP_CHECK(hipDeviceSynchronize());
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = bootstrap_weights_launch(L, seed, replicate, d, d + words, d + 2 * words, V, nullptr);
-    if (rc) return done(rc);
-    if (hipDeviceSynchronize() != hipSuccess) { set_error("tracs_debug_bootstrap_replicate: the weights kernel failed"); return done(TRACS_E_HIP); }
+    if ((rc = bootstrap_weights_launch(L, seed, replicate, d, d + words, d + 2 * words, V, nullptr))) return rc;
+    TRACS_HIP_CHECK(hipDeviceSynchronize());
     seconds[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     seconds[1] = seconds[2] = seconds[3] = 0.0;
-    return done(gather_sites(var, d + 2 * words, out, n_out, nullptr, true, seconds + 1));
+    return gather_sites(var, d + 2 * words, out, n_out, nullptr, true, seconds + 1);      // (drains the stream before it returns)
 }
 
 // Host only.  A split is the bitset of an internal edge's child (tree_bitsets), turned to the side without leaf 0.  The replicate's

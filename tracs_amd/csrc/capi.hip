@@ -7,6 +7,7 @@
 #include "fasta.h"
 #include "rowwriter.h"
 #include "debug_api.h"
+#include "alloc_path.h"
 
 #include <algorithm>
 #include <atomic>
@@ -44,10 +45,9 @@ int workspace_bytes(WsSlot slot, size_t bytes, void **out)
     Scratch &s = g_scratch[dev][slot];
     g_slot_hits[slot]++;
     if (s.bytes < bytes) {
-        if (s.ptr) { TRACS_HIP_CHECK(hipDeviceSynchronize()); TRACS_HIP_CHECK(hipFree(s.ptr)); s.ptr = nullptr; s.bytes = 0; }
+        if (s.ptr) { TRACS_HIP_CHECK(hipDeviceSynchronize()); device_free(s.ptr); s.ptr = nullptr; s.bytes = 0; }
         const size_t want = bytes + bytes / 4 + 256;
-        hipError_t e = hipMalloc(&s.ptr, want);
-        if (e != hipSuccess) { s.ptr = nullptr; set_error(std::string("hipMalloc(workspace): ") + hipGetErrorString(e)); return TRACS_E_NOMEM; }
+        if (const int rc = device_alloc(want, "workspace", &s.ptr)) return rc;
         s.bytes = want;
         if (const int poison = g_poison.load(std::memory_order_relaxed); poison >= 0) {      // growth inside a call: the new buffer starts as the rest of the pool did
             TRACS_HIP_CHECK(hipMemset(s.ptr, poison, s.bytes));
@@ -97,7 +97,7 @@ void workspace_release_all()
     std::lock_guard<std::mutex> lock(g_scratch_mu);
     for (auto &dev : g_scratch)
         for (auto &s : dev)
-            if (s.ptr) { (void)hipFree(s.ptr); s.ptr = nullptr; s.bytes = 0; }
+            if (s.ptr) { device_free(s.ptr); s.ptr = nullptr; s.bytes = 0; }
 }
 
 }  // namespace tracs
@@ -119,6 +119,12 @@ size_t tracs_debug_scratch_hits(uint64_t *hits, size_t room)
     }
     return (size_t)WS_SLOT_COUNT;
 }
+
+// The allocation path's counters (alloc_path.h).  out[4] <- live device blocks, live device bytes, live pinned blocks and the allocations
+// (device or pinned, failed ones included) since the last reading; reading resets the fourth.
+void tracs_debug_alloc_stats(uint64_t *out) { alloc_stats(out); }
+// The nth allocation from now (1-based, device or pinned) fails as out of memory without reaching HIP.  One shot; 0 turns it off.
+void tracs_debug_fail_alloc(long nth) { fail_alloc(nth); }
 
 // TRACS_STAGE_TRACE=1: wall time of the stages of the host-level entry points on stderr, one "[stage] name seconds" line each
 // (scripts/bench_e2e.py collects them into the end-to-end table of DESIGN.md 5)
@@ -220,45 +226,6 @@ extern "C" __global__ __launch_bounds__(256) void coo_delta_kernel(const unsigne
 // ---- what the host entry points below share: owners, the row-panel walk, the pair-extraction stage ------------------------------------
 namespace {
 
-// Owners: what an entry point allocates is freed when it returns, on every path.  The device and the pinned buffer are move-only;
-// alloc() replaces what is held, grow() only when it is too small (an exact fit: the pair buffers never hold slack).
-template <bool kPinned> struct OwnedBuffer {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    OwnedBuffer() = default;
-    OwnedBuffer(OwnedBuffer &&o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
-    OwnedBuffer &operator=(OwnedBuffer &&o) noexcept
-    {
-        if (this != &o) { release(); ptr = o.ptr; bytes = o.bytes; o.ptr = nullptr; o.bytes = 0; }
-        return *this;
-    }
-    ~OwnedBuffer() { release(); }
-    void release()
-    {
-        if (ptr) (void)(kPinned ? hipHostFree(ptr) : hipFree(ptr));
-        ptr = nullptr; bytes = 0;
-    }
-    int alloc(size_t want)
-    {
-        release();
-        const hipError_t e = kPinned ? hipHostMalloc(&ptr, want, hipHostMallocDefault) : hipMalloc(&ptr, want);
-        if (e != hipSuccess) { ptr = nullptr; set_error(std::string(kPinned ? "hipHostMalloc: " : "hipMalloc: ") + hipGetErrorString(e)); return TRACS_E_HIP; }
-        bytes = want;
-        return TRACS_OK;
-    }
-    int grow(size_t want) { return want > bytes ? alloc(want) : TRACS_OK; }
-    int upload(const void *host, size_t count)
-    {
-        const int rc = alloc(count);
-        if (rc) return rc;
-        TRACS_HIP_CHECK(hipMemcpy(ptr, host, count, hipMemcpyHostToDevice));
-        return TRACS_OK;
-    }
-    template <class T> T *as() const { return static_cast<T *>(ptr); }
-};
-using DeviceBuffer = OwnedBuffer<false>;
-using PinnedBuffer = OwnedBuffer<true>;
-
 // the copy stream of tracs_distance_run and its events; declared AFTER the pinned buffers it copies into, so that it is drained and
 // destroyed before they are freed
 struct CopyLane {
@@ -283,8 +250,6 @@ struct CopyLane {
     }
 };
 
-struct AlignmentFree { void operator()(tracs_alignment *a) const { tracs_alignment_free(a); } };
-using AlignmentOwner = std::unique_ptr<tracs_alignment, AlignmentFree>;
 struct ResultFree { void operator()(tracs_pairsnp_result *r) const { delete r; } };
 using ResultOwner = std::unique_ptr<tracs_pairsnp_result, ResultFree>;
 
@@ -331,9 +296,9 @@ struct PanelWalk {
         const size_t rows = env_rows("TRACS_FOREST_PANEL_ROWS", 1);
         height = rows ? std::min(rows, i_end) : std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
         int rc;
-        if ((rc = d_dist.alloc(height * n * 4)) || (rc = d_nn.alloc(height * n * 4))) return rc;
-        if (with_off && (rc = d_off.alloc((height + 1) * 8))) return rc;
-        if (with_f64 && ((rc = d_p.alloc(height * n * 8)) || (rc = d_e.alloc(height * n * 8)))) return rc;
+        if ((rc = d_dist.alloc(height * n * 4, "dist")) || (rc = d_nn.alloc(height * n * 4, "nn"))) return rc;
+        if (with_off && (rc = d_off.alloc((height + 1) * 8, "off"))) return rc;
+        if (with_f64 && ((rc = d_p.alloc(height * n * 8, "p")) || (rc = d_e.alloc(height * n * 8, "e")))) return rc;
         return TRACS_OK;
     }
     bool more() const { return at < i_end; }
@@ -371,7 +336,7 @@ struct PairStage {
 
     PairStage(const PanelWalk &walk, int filter_, double lamb_ = 0.0, double beta_ = 0.0, double precision_ = 0.0)
         : w(walk), filter(filter_ != 0), lamb(lamb_), beta(beta_), precision(precision_) {}
-    int set_days(const int32_t *days) { return d_days.upload(days, w.n * 4); }
+    int set_days(const int32_t *days) { return d_days.upload(days, w.n * 4, "days"); }
     bool with_dates() const { return d_days.ptr != nullptr; }
     bool dense_tc() const { return with_dates() && !filter; }
     const int *days() const { return d_days.as<int>(); }
@@ -390,8 +355,8 @@ struct PairStage {
         TRACS_HIP_CHECK(hipMemcpy(&total, w.off() + (pn.r1 - pn.r0), 8, hipMemcpyDeviceToHost));
         if (total <= 0) return TRACS_OK;
         const size_t t = (size_t)total;
-        if ((rc = coo.grow(t * 4 * (filter ? 5 : 4)))) return rc;
-        if (with_dates() && (rc = cp.grow(t * (filter ? 24 : 16)))) return rc;
+        if ((rc = coo.grow(t * 4 * (filter ? 5 : 4), "coo"))) return rc;
+        if (with_dates() && (rc = cp.grow(t * (filter ? 24 : 16), "cp"))) return rc;
         c.rows = coo.as<unsigned>(); c.cols = c.rows + t; c.d = c.rows + 2 * t; c.nn = c.rows + 3 * t;
         c.filt = filter ? c.rows + 4 * t : nullptr;
         c.p = with_dates() ? cp.as<double>() : nullptr;
@@ -605,16 +570,10 @@ static int apply_sample_rule(tracs_alignment **pa, FastaData &fd, size_t *n0, in
     }
     if (!n) { set_error("no sample left after the sample rule"); return TRACS_E_ARG; }
     if (a->L) {
-        unsigned *d_counts = nullptr;
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_counts), n * 4);
-        if (e != hipSuccess) { (void)hipGetLastError(); set_error(std::string("hipMalloc(sample counts): ") + hipGetErrorString(e)); return TRACS_E_NOMEM; }
-        int rc = sample_n_counts(a, rule->keep, rule->keep_len, d_counts, nullptr);
-        if (!rc && (e = hipMemcpy(src.n_count.data(), d_counts, n * 4, hipMemcpyDeviceToHost)) != hipSuccess) {
-            set_error(std::string("hipMemcpy(sample counts): ") + hipGetErrorString(e));
-            rc = TRACS_E_HIP;
-        }
-        (void)hipFree(d_counts);
-        if (rc) return rc;
+        DeviceArray<unsigned> d_counts;
+        int rc = d_counts.alloc(n, "sample counts");
+        if (rc || (rc = sample_n_counts(a, rule->keep, rule->keep_len, d_counts.get(), nullptr))) return rc;
+        TRACS_HIP_CHECK(hipMemcpy(src.n_count.data(), d_counts.get(), n * 4, hipMemcpyDeviceToHost));
     }
     const double limit = std::floor(rule->max_sample_share * (double)src.rule_sites);
     size_t kept0 = 0, kept1 = 0;
@@ -813,7 +772,7 @@ static int nearest_run(const char *const *fasta, int n_fasta, int k, int dist, i
     DeviceBuffer d_state, d_off, d_out;
     StageClock clock;
     if (walk.any()) {
-        if ((rc = d_state.alloc(tracs_knn_state_bytes(n_lists, k))) || (rc = tracs_knn_init(d_state.ptr, n_lists, k, nullptr))) return rc;
+        if ((rc = d_state.alloc(tracs_knn_state_bytes(n_lists, k), "state")) || (rc = tracs_knn_init(d_state.ptr, n_lists, k, nullptr))) return rc;
         if ((rc = walk.begin(false, false))) return rc;
         for (Panel pn; walk.more();) {
             if ((rc = walk.next(pn))) return rc;
@@ -822,7 +781,7 @@ static int nearest_run(const char *const *fasta, int n_fasta, int k, int dist, i
         clock.mark("dense panels + selection");
         // rows, cols, d, nn, filt (and the filter's ordered pairs) in one block: one copy back
         const size_t cap = n_lists * (size_t)k;
-        if ((rc = d_off.alloc((n_lists + 1) * 8)) || (rc = d_out.alloc(cap * 4 * (filter ? 7 : 4)))) return rc;
+        if ((rc = d_off.alloc((n_lists + 1) * 8, "off")) || (rc = d_out.alloc(cap * 4 * (filter ? 7 : 4), "out"))) return rc;
         unsigned *c_rows = d_out.as<unsigned>(), *c_cols = c_rows + cap, *c_d = c_rows + 2 * cap, *c_n = c_rows + 3 * cap;
         if ((rc = tracs_knn_emit(d_state.ptr, 0, n_lists, k, d_off.as<int64_t>(), c_rows, c_cols, c_d, c_n, nullptr))) return rc;
         long long tot = 0;
@@ -962,18 +921,11 @@ int tracs_distance_site_census(tracs_distance *h, uint32_t *counts_host, uint64_
     if (!h || !h->a) { set_error("tracs_distance_site_census: NULL argument"); return TRACS_E_ARG; }
     const tracs_alignment *a = h->a;
     if (!a->L) return TRACS_OK;
-    uint32_t *d_counts = nullptr;
-    if (counts_host) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_counts), a->L * 6 * 4);
-        if (e != hipSuccess) { (void)hipGetLastError(); set_error(std::string("hipMalloc(site census): ") + hipGetErrorString(e)); return TRACS_E_NOMEM; }
-    }
-    int rc = site_census(a, d_counts, differs_host, n_differs, nullptr);
-    if (!rc && counts_host) {
-        const hipError_t e = hipMemcpy(counts_host, d_counts, a->L * 6 * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { set_error(std::string("hipMemcpy(site census): ") + hipGetErrorString(e)); rc = TRACS_E_HIP; }
-    }
-    if (d_counts) (void)hipFree(d_counts);
-    return rc;
+    DeviceArray<uint32_t> d_counts;
+    int rc = counts_host ? d_counts.alloc(a->L * 6, "site census") : TRACS_OK;
+    if (rc || (rc = site_census(a, d_counts.get(), differs_host, n_differs, nullptr))) return rc;
+    if (counts_host) TRACS_HIP_CHECK(hipMemcpy(counts_host, d_counts.get(), a->L * 6 * 4, hipMemcpyDeviceToHost));
+    return TRACS_OK;
 }
 
 // Batches of samples: device buffer -> pinned host buffer -> writer.  The two buffers hold `batch` rows of `stride` bytes (the row
@@ -1002,7 +954,7 @@ int tracs_distance_write_alignment(tracs_distance *h, const char *path, size_t s
     const size_t batch = std::max<size_t>(1, std::min<size_t>(count, stride ? (256ull << 20) / stride : count));
     DeviceBuffer d_buf;
     PinnedBuffer h_buf;
-    if (count && L && ((rc = d_buf.alloc(batch * stride)) || (rc = h_buf.alloc(batch * stride)))) return rc;
+    if (count && L && ((rc = d_buf.alloc(batch * stride, "buf")) || (rc = h_buf.alloc(batch * stride, "buf")))) return rc;
     if ((rc = tracs_write_fasta_rows(path, nullptr, nullptr, stride, 0, L, 0, n_threads, gzip_level))) return rc;     // truncate
     for (size_t s = sample_begin; s < sample_end; s += batch) {
         const size_t cnt = std::min(batch, sample_end - s);
@@ -1061,7 +1013,7 @@ int tracs_distance_run(tracs_distance *h, int dist, const int32_t *days, double 
         const size_t n32 = filter ? 5 : 4;
         const size_t batch_bytes = CH * (n32 * 4 + (with_dates ? 16 : 0) + 4);
         const size_t f64_at = (CH * n32 * 4 + 7) / 8 * 8;
-        for (auto &q : pin) if ((rc = q.alloc(batch_bytes))) return rc;
+        for (auto &q : pin) if ((rc = q.alloc(batch_bytes, "row batch"))) return rc;
         if ((rc = lane.create())) return rc;
         std::vector<uint32_t> zeros;                                  // the filtered column without metadata: `len` zeros (:240-258)
         if (!with_dates) zeros.assign(CH, 0u);
@@ -1125,7 +1077,7 @@ static int write_emitted_rows(size_t count, const EmitFn &emit, tracs::DistanceR
 {
     DeviceBuffer coo, cp;
     int rc;
-    if ((rc = coo.alloc(count * 4 * 5)) || (rc = cp.alloc(count * 16))) return rc;
+    if ((rc = coo.alloc(count * 4 * 5, "coo")) || (rc = cp.alloc(count * 16, "cp"))) return rc;
     unsigned *c = coo.as<unsigned>();
     double *f = cp.as<double>();
     if ((rc = emit(c, c + count, c + 2 * count, c + 3 * count, c + 4 * count, f, f + count))) return rc;
@@ -1169,7 +1121,7 @@ int tracs_distance_forest(tracs_distance *h, int dist, const int32_t *days, doub
     PairStage stage(walk, filter, lamb, beta, precision);
     DeviceBuffer d_state;
     if (walk.any()) {
-        if ((rc = d_state.alloc(tracs_msf_state_bytes(n))) || (rc = tracs_msf_init(d_state.ptr, n, nullptr))) return rc;
+        if ((rc = d_state.alloc(tracs_msf_state_bytes(n), "state")) || (rc = tracs_msf_init(d_state.ptr, n, nullptr))) return rc;
         if (days && (rc = stage.set_days(days))) return rc;
         if ((rc = walk.begin(true, stage.dense_tc()))) return rc;
         PairColumns c;
@@ -1227,7 +1179,7 @@ int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, d
     if (walk.any()) {
         // the day numbers on the device first: they order the samples of the state
         if ((rc = stage.set_days(days))) return rc;
-        if ((rc = d_state.alloc(tracs_anc_state_bytes(n))) || (rc = tracs_anc_init(d_state.ptr, n, stage.days(), nullptr))) return rc;
+        if ((rc = d_state.alloc(tracs_anc_state_bytes(n), "state")) || (rc = tracs_anc_init(d_state.ptr, n, stage.days(), nullptr))) return rc;
         if ((rc = walk.begin(true, stage.dense_tc()))) return rc;
         PairColumns c;
         for (Panel pn; walk.more();) {
@@ -1241,7 +1193,7 @@ int tracs_distance_ancestors(tracs_distance *h, int dist, const int32_t *days, d
         }
         clock.mark("dense panels + transcluster + ancestor updates");
         size_t nl = 0;
-        if ((rc = d_tree.alloc(n * 12))) return rc;
+        if ((rc = d_tree.alloc(n * 12, "tree"))) return rc;
         unsigned *t = d_tree.as<unsigned>();
         if ((rc = tracs_anc_emit(d_state.ptr, n, &nl, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, t, t + n, t + 2 * n, nullptr))) return rc;
         TRACS_HIP_CHECK(hipMemcpy(tree.data(), t, n * 12, hipMemcpyDeviceToHost));
@@ -1294,7 +1246,7 @@ int tree_of_alignment(tracs_alignment *a, const char *const *names, int kind, Pa
     double last_d[3] = {0.0, 0.0, 0.0};
     t.nj = t.ne = 0;
     if (walk.any()) {
-        if (!d_state.ptr && (rc = d_state.alloc(bionj ? tracs_bionj_state_bytes(n) : tracs_nj_state_bytes(n)))) return rc;
+        if (!d_state.ptr && (rc = d_state.alloc(bionj ? tracs_bionj_state_bytes(n) : tracs_nj_state_bytes(n), "state"))) return rc;
         void *const state = d_state.ptr;
         if ((rc = tracs_nj_init(state, n, nullptr))) return rc;
         if (a) {
@@ -1352,7 +1304,7 @@ int tree_bootstrap_stage(tracs_distance *h, const tracs_tree_request &r, const T
     DeviceBuffer d_transfer;
     for (size_t e = 0; e < t.ne; e++) if (t.child[e] >= n) s.support[e] = 0;
     if (transfer) {
-        if ((rc = d_transfer.alloc(tracs_transfer_state_bytes(n))) ||
+        if ((rc = d_transfer.alloc(tracs_transfer_state_bytes(n), "transfer")) ||
             (rc = tracs_transfer_init(d_transfer.ptr, n, t.parent.data(), t.child.data(), t.ne, nullptr))) return rc;
         clock.mark("transfer: membership matrix");
     }
@@ -1367,7 +1319,7 @@ int tree_bootstrap_stage(tracs_distance *h, const tracs_tree_request &r, const T
         var.reset(sel);
         std::vector<unsigned> bits, woff;
         bootstrap_column_words(differs.data(), L, bits, woff);
-        if ((rc = d_bits.upload(bits.data(), bits.size() * 4)) || (rc = d_woff.upload(woff.data(), woff.size() * 4)) || (rc = d_w.alloc(V * 4))) return rc;
+        if ((rc = d_bits.upload(bits.data(), bits.size() * 4, "bits")) || (rc = d_woff.upload(woff.data(), woff.size() * 4, "woff")) || (rc = d_w.alloc(V * 4, "w"))) return rc;
     }
     clock.mark("bootstrap: census + differing columns");
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};                         // weights + scan + gather; the three stages of a tree (+ support);
@@ -1427,9 +1379,9 @@ int tree_changes_stage(tracs_distance *h, const tracs_tree_request &r, const Tre
     c.kept.assign(std::max<size_t>(t.ne, 1), 0);
     if (r.filter && n && t.ne) {
         const size_t total = (size_t)c.ft.total;
-        if ((rc = c.d_edge_off.alloc((t.ne + 1) * 8)) || (rc = c.d_edge_site.alloc(std::max<size_t>(total, 1) * 4)) ||
-            (rc = c.d_dropped.alloc(std::max<size_t>(total, 1))) || (rc = c.d_filt.alloc(t.ne * 4))) return rc;
-        if ((rc = tracs_fitch_edge_sites(h->a, t.parent.data(), t.child.data(), t.ne, c.ft.d_edge, c.d_edge_off.as<int64_t>(),
+        if ((rc = c.d_edge_off.alloc((t.ne + 1) * 8, "edge_off")) || (rc = c.d_edge_site.alloc(std::max<size_t>(total, 1) * 4, "edge_site")) ||
+            (rc = c.d_dropped.alloc(std::max<size_t>(total, 1), "dropped")) || (rc = c.d_filt.alloc(t.ne * 4, "filt"))) return rc;
+        if ((rc = tracs_fitch_edge_sites(h->a, t.parent.data(), t.child.data(), t.ne, c.ft.d_edge.get(), c.d_edge_off.as<int64_t>(),
                                          c.d_edge_site.as<uint32_t>(), total, nullptr))) return rc;
         clock.mark("tree filter: the changes by edge");
         if ((rc = tracs_filter_recomb_lists(h->a, c.d_edge_off.as<int64_t>(), c.d_edge_site.as<uint32_t>(), t.ne, total, c.d_filt.as<uint32_t>(),
@@ -1752,9 +1704,9 @@ int tracs_distance_histogram(tracs_distance *h, int dist, int filter, const int3
         int rc;
         const int n_states = filter ? 2 : 1;
         for (int s = 0; s < n_states; s++)
-            if ((rc = d_state[s].alloc(tracs_hist_state_bytes(n_bins))) || (rc = tracs_hist_init(d_state[s].ptr, n_bins, nullptr))) return rc;
+            if ((rc = d_state[s].alloc(tracs_hist_state_bytes(n_bins), "state")) || (rc = tracs_hist_init(d_state[s].ptr, n_bins, nullptr))) return rc;
         if ((rc = walk.begin(filter != 0, false))) return rc;
-        if (group && (rc = d_group.upload(group, n * 4))) return rc;
+        if (group && (rc = d_group.upload(group, n * 4, "group"))) return rc;
         PairColumns c;
         for (Panel pn; walk.more();) {
             if ((rc = walk.next(pn))) return rc;
@@ -1771,7 +1723,7 @@ int tracs_distance_histogram(tracs_distance *h, int dist, int filter, const int3
             size_t nr = 0;
             if ((rc = tracs_hist_emit(d_state[s].ptr, n_bins, &nr, nullptr, nullptr, nullptr, nullptr, nullptr))) return rc;
             if (!nr) continue;
-            if ((rc = d_val.alloc(nr * 4)) || (rc = d_cnt.alloc(nr * 8 * 3))) return rc;
+            if ((rc = d_val.alloc(nr * 4, "val")) || (rc = d_cnt.alloc(nr * 8 * 3, "cnt"))) return rc;
             uint64_t *cnt = d_cnt.as<uint64_t>();
             if ((rc = tracs_hist_emit(d_state[s].ptr, n_bins, &nr, d_val.as<unsigned>(), cnt, cnt + nr, cnt + 2 * nr, nullptr))) return rc;
             std::vector<uint32_t> hv(nr);

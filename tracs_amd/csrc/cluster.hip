@@ -122,21 +122,16 @@ int tracs_connected_components(const int32_t *I, const int32_t *J, size_t n_edge
     if (!labels || (n_edges && (!I || !J))) { set_error("tracs_connected_components: NULL argument"); return TRACS_E_ARG; }
     for (size_t e = 0; e < n_edges; e++)
         if (I[e] < 0 || J[e] < 0 || (size_t)I[e] >= n_nodes || (size_t)J[e] >= n_nodes) { set_error("connected_components: edge endpoint out of range"); return TRACS_E_ARG; }
-    int *dI = nullptr, *dJ = nullptr, *dL = nullptr;
-    auto cleanup = [&]() { if (dI) (void)hipFree(dI); if (dJ) (void)hipFree(dJ); if (dL) (void)hipFree(dL); };
-#define CC_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
+    DeviceArray<int> dI, dJ, dL;
+    int rc;
     if (n_edges) {
-        CC_CHECK(hipMalloc(reinterpret_cast<void **>(&dI), n_edges * 4));
-        CC_CHECK(hipMalloc(reinterpret_cast<void **>(&dJ), n_edges * 4));
-        CC_CHECK(hipMemcpy(dI, I, n_edges * 4, hipMemcpyHostToDevice));
-        CC_CHECK(hipMemcpy(dJ, J, n_edges * 4, hipMemcpyHostToDevice));
+        if ((rc = dI.alloc(n_edges, "edge rows")) || (rc = dJ.alloc(n_edges, "edge columns"))) return rc;
+        TRACS_HIP_CHECK(hipMemcpy(dI.get(), I, n_edges * 4, hipMemcpyHostToDevice));
+        TRACS_HIP_CHECK(hipMemcpy(dJ.get(), J, n_edges * 4, hipMemcpyHostToDevice));
     }
-    CC_CHECK(hipMalloc(reinterpret_cast<void **>(&dL), n_nodes * 4));
-    int rc = tracs_connected_components_device(dI, dJ, n_edges, n_nodes, dL, n_components, nullptr);
-    if (rc) { cleanup(); return rc; }
-    CC_CHECK(hipMemcpy(labels, dL, n_nodes * 4, hipMemcpyDeviceToHost));
-#undef CC_CHECK
-    cleanup();
+    if ((rc = dL.alloc(n_nodes, "labels")) ||
+        (rc = tracs_connected_components_device(dI.get(), dJ.get(), n_edges, n_nodes, dL.get(), n_components, nullptr))) return rc;
+    TRACS_HIP_CHECK(hipMemcpy(labels, dL.get(), n_nodes * 4, hipMemcpyDeviceToHost));
     return TRACS_OK;
 }
 

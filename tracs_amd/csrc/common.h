@@ -1,8 +1,9 @@
-// common.h -- shared host-side helpers of libtracs_hip.so (error slot, layout constants).
+// common.h -- shared host-side helpers of libtracs_hip.so (error slot, the owners of device and pinned memory, layout constants).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -20,6 +21,78 @@ void set_error(const std::string &msg);
             return TRACS_E_HIP;                                                                 \
         }                                                                                       \
     } while (0)
+
+// ---- device and pinned memory ----------------------------------------------------------
+// Every byte the library owns comes from these four (alloc_path.h, part of capi.hip): nothing else in csrc/ calls hipMalloc,
+// hipHostMalloc, hipFree or hipHostFree.  A failed allocation sets the error slot to "hipMalloc(<what>, <bytes> bytes): <HIP's
+// text>" ("hipHostMalloc(..." for pinned memory), leaves *out NULL and HIP's last error clear, and returns TRACS_E_NOMEM.  The frees
+// take NULL.  tracs_debug_alloc_stats / tracs_debug_fail_alloc read and steer the path's counters.
+int device_alloc(size_t bytes, const char *what, void **out);
+void device_free(void *p);
+int pinned_alloc(size_t bytes, const char *what, void **out);
+void pinned_free(void *p);
+// an optional block: not getting it is not an error.  false leaves *out NULL and the error slot clear (as workspace_try)
+bool device_try_alloc(size_t bytes, void **out);
+
+// Owners: what a call allocates is freed when it returns, on every path, and what a structure holds goes with it.  Move-only.
+// alloc() replaces what is held, grow() only when it is too small (an exact fit: the pair buffers never hold slack).  The destructor
+// relies on hipFree waiting for the device; an owner is declared BEFORE whatever still uses it at scope exit (a stream that copies
+// into it, see capi.hip's CopyLane), so that it is destroyed after it.
+template <bool kPinned> struct OwnedBuffer {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    OwnedBuffer() = default;
+    OwnedBuffer(OwnedBuffer &&o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+    OwnedBuffer &operator=(OwnedBuffer &&o) noexcept
+    {
+        if (this != &o) { release(); ptr = o.ptr; bytes = o.bytes; o.ptr = nullptr; o.bytes = 0; }
+        return *this;
+    }
+    ~OwnedBuffer() { release(); }
+    void release()
+    {
+        if (kPinned) pinned_free(ptr); else device_free(ptr);
+        ptr = nullptr; bytes = 0;
+    }
+    int alloc(size_t want, const char *what)
+    {
+        release();
+        const int rc = kPinned ? pinned_alloc(want, what, &ptr) : device_alloc(want, what, &ptr);
+        if (rc == TRACS_OK) bytes = want;
+        return rc;
+    }
+    int grow(size_t want, const char *what) { return want > bytes ? alloc(want, what) : TRACS_OK; }
+    int upload(const void *host, size_t count, const char *what)
+    {
+        const int rc = alloc(count, what);
+        if (rc) return rc;
+        TRACS_HIP_CHECK(hipMemcpy(ptr, host, count, hipMemcpyHostToDevice));
+        return TRACS_OK;
+    }
+    void *detach() { void *p = ptr; ptr = nullptr; bytes = 0; return p; }      // the block is the caller's now (device_free / pinned_free)
+    template <class T> T *as() const { return static_cast<T *>(ptr); }
+};
+using DeviceBuffer = OwnedBuffer<false>;
+using PinnedBuffer = OwnedBuffer<true>;
+
+// the typed form: `count` elements of T.  Kernels keep taking raw pointers: pass get()
+template <class T, bool kPinned = false> struct DeviceArray {
+    OwnedBuffer<kPinned> buf;
+    int alloc(size_t count, const char *what) { return buf.alloc(count * sizeof(T), what); }
+    bool try_alloc(size_t count)
+    {
+        static_assert(!kPinned, "optional blocks are device memory");
+        buf.release();
+        if (!device_try_alloc(count * sizeof(T), &buf.ptr)) return false;
+        buf.bytes = count * sizeof(T);
+        return true;
+    }
+    T *get() const { return static_cast<T *>(buf.ptr); }
+    size_t count() const { return buf.bytes / sizeof(T); }
+    void release() { buf.release(); }
+    T *detach() { return static_cast<T *>(buf.detach()); }
+};
+template <class T> using PinnedArray = DeviceArray<T, true>;
 
 // ---- packed alignment layout -----------------------------------------------------------
 // Sites are cut into groups of 128 (one uint4 = 4 x 32 sites).  For group g, plane p
@@ -80,7 +153,7 @@ struct tracs_alignment {
     int classes_state = 0;       // 0 not decided, 1 in use, -1 not in use for this alignment
     // Arena for what is built once per pack (vplanes, iplanes, N counts, minority lists): reserved together with the planes at
     // tracs_alignment_create, because a fresh device allocation costs ~24 ms per GB on this platform (the driver clears VRAM) and
-    // would otherwise land inside the first pass.  pack_alloc falls back to hipMalloc when the arena is too small.
+    // would otherwise land inside the first pass.  pack_alloc falls back to device_alloc when the arena is too small.
     uint8_t *arena = nullptr;
     size_t arena_bytes = 0, arena_used = 0;
     struct PackBlock { void *p; size_t bytes; };
@@ -105,6 +178,19 @@ struct tracs_alignment {
 };
 
 namespace tracs {
+struct AlignmentFree { void operator()(tracs_alignment *a) const { tracs_alignment_free(a); } };
+using AlignmentOwner = std::unique_ptr<tracs_alignment, AlignmentFree>;
+// the HIP events of a measurement (the tracs_debug_*_timing entry points); declared before the buffers the timed kernels use
+template <int N> struct OwnedEvents {
+    hipEvent_t ev[N] = {};
+    OwnedEvents() = default;
+    OwnedEvents(const OwnedEvents &) = delete;
+    OwnedEvents &operator=(const OwnedEvents &) = delete;
+    ~OwnedEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    int create() { for (auto &e : ev) TRACS_HIP_CHECK(hipEventCreate(&e)); return TRACS_OK; }
+    hipEvent_t operator[](int k) const { return ev[k]; }
+};
+
 // what the pair kernels read: the whole alignment, or its variable sites (site classes in use)
 static inline const uint4 *pair_planes(const tracs_alignment *a, bool consensus)
 {
@@ -184,17 +270,13 @@ int pair_sites_write(const tracs_alignment *a, const char *const *names, const u
 // (tracs_distance_tree_changes: fitch_tables counts, the caller decides about --max-entries and writes the tree, fitch_write fills
 // and formats; names, kept-columns bitmap and contigs as pair_sites_write)
 struct FitchTables {
-    unsigned *d_edge = nullptr, *d_site = nullptr;
-    uint8_t *d_min = nullptr;
-    long long *d_off = nullptr;
+    DeviceArray<unsigned> d_edge, d_site;
+    DeviceArray<uint8_t> d_min;
+    DeviceArray<long long> d_off;
     std::vector<uint32_t> edge_changes;
     std::vector<long long> off;
     std::vector<uint8_t> minimum;
     uint64_t total = 0, sum_minimum = 0;
-    FitchTables() = default;
-    FitchTables(const FitchTables &) = delete;
-    FitchTables &operator=(const FitchTables &) = delete;
-    ~FitchTables();
 };
 // the branch filter's device arrays (tracs_distance_tree_filter): the changes by edge and their verdicts
 struct FitchFilter {
@@ -219,7 +301,7 @@ int mask_subtrees(tracs_alignment *a, const uint32_t *parent, const uint32_t *ch
                   const uint32_t *edge_site, const uint8_t *dropped, size_t n_entries, uint64_t *n_cells, uint64_t *work, hipStream_t stream);
 
 // device memory that lives until the alignment is packed again (site_classes_free releases all of it at once)
-hipError_t pack_alloc(tracs_alignment *a, size_t bytes, void **out);
+bool pack_alloc(tracs_alignment *a, size_t bytes, void **out);      // false: no memory (never an error: the callers fall back)
 void pack_release(tracs_alignment *a);
 
 // Grow-only per-device scratch buffers, shared by every entry point.  Every slot of every file is declared here, once: a new buffer

@@ -60,6 +60,10 @@ int tracs_debug_transfer_init(void *state, size_t n, const uint32_t *parent, con
 int tracs_debug_differs_table(uint8_t *out, size_t bytes);                        /* the 2 048-byte table behind the census's differs bit */
 int tracs_debug_tree_edges_header(int support, int transfer, int changes, int filtered, char *out, size_t cap);   /* the edge file's header line */
 
+/* capi.hip: the allocation path (alloc_path.h) */
+void tracs_debug_alloc_stats(uint64_t *out);                                      /* out[4]: live device blocks and bytes, live pinned blocks, allocations since the last reading */
+void tracs_debug_fail_alloc(long nth);                                            /* the nth allocation from now fails as out of memory, once; 0: off */
+
 /* alignio.cpp, capi.hip */
 long tracs_debug_format_floats(const double *x, size_t n, char *buf, size_t cap); /* str(float) of n doubles as the row writer prints them */
 int tracs_debug_read_fasta(const char *path, size_t *n, size_t *L, uint64_t *hash);     /* records, length and a hash of a FASTA file as parsed */

@@ -265,14 +265,10 @@ int tracs_find_dirichlet_priors(const double *counts, size_t L, size_t K, int ma
                                 double error_filt_threshold, double *alphas_out, int *iters_out)
 {
     if (!counts || !alphas_out) { set_error("tracs_find_dirichlet_priors: NULL argument"); return TRACS_E_ARG; }
-    double *d = nullptr;
-    const size_t bytes = std::max<size_t>(L * K, 1) * 8;
-    TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), bytes));
-    hipError_t e = L ? hipMemcpy(d, counts, L * K * 8, hipMemcpyHostToDevice) : hipSuccess;
-    if (e != hipSuccess) { (void)hipFree(d); set_error(std::string("H2D counts: ") + hipGetErrorString(e)); return TRACS_E_HIP; }
-    const int rc = tracs_find_dirichlet_priors_device(d, L, K, max_iter, tol, method, error_filt_threshold, alphas_out, iters_out, nullptr);
-    (void)hipFree(d);
-    return rc;
+    DeviceArray<double> d;
+    if (const int rc = d.alloc(std::max<size_t>(L * K, 1), "counts")) return rc;
+    if (L) TRACS_HIP_CHECK(hipMemcpy(d.get(), counts, L * K * 8, hipMemcpyHostToDevice));
+    return tracs_find_dirichlet_priors_device(d.get(), L, K, max_iter, tol, method, error_filt_threshold, alphas_out, iters_out, nullptr);
 }
 
 // digamma_pos of n host doubles (all > 0) -> n host doubles: the function the fit sums, for tests/test_gpu_dirichlet_hp.py
@@ -280,16 +276,12 @@ int tracs_debug_digamma(const double *x, size_t n, double *out)
 {
     if (n == 0) return TRACS_OK;
     if (!x || !out) { set_error("tracs_debug_digamma: NULL argument"); return TRACS_E_ARG; }
-    double *d = nullptr;
-    TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), 2 * n * 8));
-    hipError_t e = hipMemcpy(d, x, n * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(dm_digamma_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, nullptr, d, n, d + n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d + n, n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) { set_error(std::string("tracs_debug_digamma: ") + hipGetErrorString(e)); return TRACS_E_HIP; }
+    DeviceArray<double> d;
+    if (const int rc = d.alloc(2 * n, "digamma in and out")) return rc;
+    TRACS_HIP_CHECK(hipMemcpy(d.get(), x, n * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(dm_digamma_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, nullptr, d.get(), n, d.get() + n);
+    TRACS_HIP_CHECK(hipGetLastError());
+    TRACS_HIP_CHECK(hipMemcpy(out, d.get() + n, n * 8, hipMemcpyDeviceToHost));
     return TRACS_OK;
 }
 

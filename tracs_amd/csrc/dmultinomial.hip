@@ -569,18 +569,12 @@ int tracs_calculate_posteriors(const double *counts, size_t L, size_t K, const d
 {
     if (L == 0) return TRACS_OK;
     if (!counts || !alphas || !posterior) { set_error("tracs_calculate_posteriors: NULL argument"); return TRACS_E_ARG; }
-    double *dC = nullptr, *dP = nullptr;
-    const size_t bytes = L * K * sizeof(double);
-    auto cleanup = [&]() { if (dC) (void)hipFree(dC); if (dP) (void)hipFree(dP); };
-#define CP_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
-    CP_CHECK(hipMalloc(reinterpret_cast<void **>(&dC), bytes));
-    CP_CHECK(hipMalloc(reinterpret_cast<void **>(&dP), bytes));
-    CP_CHECK(hipMemcpy(dC, counts, bytes, hipMemcpyHostToDevice));
-    int rc = tracs_calculate_posteriors_device(dC, L, K, alphas, keep, threshold, dP, nullptr);
-    if (rc) { cleanup(); return rc; }
-    CP_CHECK(hipMemcpy(posterior, dP, bytes, hipMemcpyDeviceToHost));
-#undef CP_CHECK
-    cleanup();
+    DeviceArray<double> dC, dP;
+    int rc;
+    if ((rc = dC.alloc(L * K, "counts")) || (rc = dP.alloc(L * K, "posterior"))) return rc;
+    TRACS_HIP_CHECK(hipMemcpy(dC.get(), counts, L * K * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = tracs_calculate_posteriors_device(dC.get(), L, K, alphas, keep, threshold, dP.get(), nullptr))) return rc;
+    TRACS_HIP_CHECK(hipMemcpy(posterior, dP.get(), L * K * sizeof(double), hipMemcpyDeviceToHost));
     return TRACS_OK;
 }
 

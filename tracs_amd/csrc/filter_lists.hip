@@ -53,28 +53,23 @@ __device__ __forceinline__ uint4 flt_nt_load(const uint4 *p)
 }
 
 struct FilterIndex {
-    unsigned *dep = nullptr;                  // departure entries, sample-major, sorted by site
+    DeviceArray<unsigned> dep;                // departure entries, sample-major, sorted by site
     size_t dep_cap = 0;
-    unsigned long long *dep_off = nullptr;    // n + 1
-    uint4 *ref = nullptr;                     // per group: one-hot reference planes A, C, G, T
-    uint4 *nt = nullptr;                      // [sample][nt_groups] N words
-    unsigned *ns = nullptr;                   // [site][ns_words] sample bits
+    DeviceArray<unsigned long long> dep_off;  // n + 1
+    DeviceArray<uint4> ref;                   // per group: one-hot reference planes A, C, G, T
+    DeviceArray<uint4> nt;                    // [sample][nt_groups] N words
+    DeviceArray<unsigned> ns;                 // [site][ns_words] sample bits
     size_t nt_groups = 0, ns_words = 0;
-    unsigned *tbl = nullptr;                  // [FLT_DCAP + 1][FLT_KT] smallest surviving span
-    unsigned char *tbl_state = nullptr;       // per d: bit 0 built, bit 1 wanted by the current call
+    DeviceArray<unsigned> tbl;                // [FLT_DCAP + 1][FLT_KT] smallest surviving span
+    DeviceArray<unsigned char> tbl_state;     // per d: bit 0 built, bit 1 wanted by the current call
     unsigned tbl_L = 0;
-    unsigned *counters = nullptr;             // [0] pairs whose SNP count differs from d, [1] pairs left to the scan, [2] largest d among those
+    DeviceArray<unsigned> counters;           // [0] pairs whose SNP count differs from d, [1] pairs left to the scan, [2] largest d among those
     unsigned long long total = 0;
     unsigned max_len = 0;
     size_t n = 0, L = 0;
     bool usable = false;                      // the lists exist (else: every pair takes the scan)
     double build_ms[6] = {0, 0, 0, 0, 0, 0};  // ref, count, offsets, fill, NT, NS
     double alloc_ms = 0.0;
-    ~FilterIndex()
-    {
-        void *p[] = {dep, dep_off, ref, nt, ns, tbl, tbl_state, counters};
-        for (void *q : p) if (q) (void)hipFree(q);
-    }
 };
 
 // ---- reference base per site ------------------------------------------------------------------------------------------
@@ -1065,15 +1060,9 @@ static bool flt_env_off(const char *name)
     return e && e[0] == '0';
 }
 
+// a part that is kept from one build of the handle to the next: allocated once
 template <class T>
-static bool flt_alloc(T **p, size_t bytes)
-{
-    if (*p) return true;
-    if (hipMalloc(reinterpret_cast<void **>(p), bytes) == hipSuccess) return true;
-    *p = nullptr;
-    (void)hipGetLastError();
-    return false;
-}
+static bool flt_alloc(DeviceArray<T> &p, size_t count) { return p.get() || p.try_alloc(count); }
 
 struct FltEvents {
     hipEvent_t ev[8];
@@ -1110,9 +1099,8 @@ static int filter_index_get(tracs_alignment *a, hipStream_t stream)
     // fixed-size parts (kept from one build of the handle to the next)
     const size_t nt_groups = (groups + 31) / 32 * 32, ns_words = ns_words_for(a->n_pad);
     f->nt_groups = nt_groups; f->ns_words = ns_words;
-    if (!flt_alloc(&f->ref, (size_t)groups * 4 * sizeof(uint4)) || !flt_alloc(&f->dep_off, ((size_t)n + 1) * 8) ||
-        !flt_alloc(&f->counters, 64) || !flt_alloc(&f->nt, (size_t)n * nt_groups * sizeof(uint4)) ||
-        !flt_alloc(&f->ns, (size_t)groups * 128 * ns_words * 4)) return soft_fail();
+    if (!flt_alloc(f->ref, (size_t)groups * 4) || !flt_alloc(f->dep_off, (size_t)n + 1) || !flt_alloc(f->counters, 16) ||
+        !flt_alloc(f->nt, (size_t)n * nt_groups) || !flt_alloc(f->ns, (size_t)groups * 128 * ns_words)) return soft_fail();
     f->alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     unsigned *cnt, *rel, *tot, *stats;
     int rc;
@@ -1122,17 +1110,17 @@ static int filter_index_get(tracs_alignment *a, hipStream_t stream)
         (rc = workspace_get(WS_FLT_STATS, 16, &stats))) return done(rc);
 
     TRACS_HIP_CHECK(hipEventRecord(ev[0], stream));
-    hipLaunchKernelGGL(flt_ref_kernel, dim3(groups), dim3(64), 0, stream, a->planes, a->n_pad, n, groups, f->ref);
+    hipLaunchKernelGGL(flt_ref_kernel, dim3(groups), dim3(64), 0, stream, a->planes, a->n_pad, n, groups, f->ref.get());
     TRACS_HIP_CHECK(hipEventRecord(ev[1], stream));
-    hipLaunchKernelGGL((flt_dep_kernel<false>), dim3((n + 255) / 256, chunks), dim3(256), 0, stream, a->planes, a->n_pad, n, groups, f->ref,
+    hipLaunchKernelGGL((flt_dep_kernel<false>), dim3((n + 255) / 256, chunks), dim3(256), 0, stream, a->planes, a->n_pad, n, groups, f->ref.get(),
                        cnt, nullptr, nullptr, nullptr);
     TRACS_HIP_CHECK(hipEventRecord(ev[2], stream));
     hipLaunchKernelGGL(flt_rel_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, cnt, n, chunks, rel, tot);
-    hipLaunchKernelGGL(flt_scan_kernel, dim3(1), dim3(1024), 0, stream, tot, n, f->dep_off, stats);
+    hipLaunchKernelGGL(flt_scan_kernel, dim3(1), dim3(1024), 0, stream, tot, n, f->dep_off.get(), stats);
     TRACS_HIP_CHECK(hipGetLastError());
     unsigned long long total = 0;
     unsigned max_len = 0;
-    TRACS_HIP_CHECK(hipMemcpyAsync(&total, f->dep_off + n, 8, hipMemcpyDeviceToHost, stream));
+    TRACS_HIP_CHECK(hipMemcpyAsync(&total, f->dep_off.get() + n, 8, hipMemcpyDeviceToHost, stream));
     TRACS_HIP_CHECK(hipMemcpyAsync(&max_len, stats, 4, hipMemcpyDeviceToHost, stream));
     TRACS_HIP_CHECK(hipEventRecord(ev[3], stream));
     TRACS_HIP_CHECK(hipStreamSynchronize(stream));
@@ -1141,18 +1129,19 @@ static int filter_index_get(tracs_alignment *a, hipStream_t stream)
     // most), its scan 8 planes' bits (1 byte per site)
     if (max_len == 0xFFFFFFFFu || total >= (1ull << 32) || (double)total > 0.10 * (double)a->L * (double)n) return soft_fail();
     if (total + 64 > f->dep_cap) {
-        if (f->dep) { (void)hipFree(f->dep); f->dep = nullptr; f->dep_cap = 0; }
+        f->dep.release();
+        f->dep_cap = 0;
         const size_t want = (size_t)total + (size_t)total / 8 + 4096;
-        if (hipMalloc(reinterpret_cast<void **>(&f->dep), want * 4) != hipSuccess) { f->dep = nullptr; return soft_fail(); }
+        if (!f->dep.try_alloc(want)) return soft_fail();
         f->dep_cap = want;
     }
-    hipLaunchKernelGGL((flt_dep_kernel<true>), dim3((n + 255) / 256, chunks), dim3(256), 0, stream, a->planes, a->n_pad, n, groups, f->ref,
-                       nullptr, rel, f->dep_off, f->dep);
+    hipLaunchKernelGGL((flt_dep_kernel<true>), dim3((n + 255) / 256, chunks), dim3(256), 0, stream, a->planes, a->n_pad, n, groups, f->ref.get(),
+                       nullptr, rel, f->dep_off.get(), f->dep.get());
     TRACS_HIP_CHECK(hipEventRecord(ev[4], stream));
     hipLaunchKernelGGL(flt_nt_kernel, dim3((unsigned)(nt_groups / 32), (n + 63) / 64), dim3(256), 0, stream, a->planes, a->n_pad, n, groups,
-                       f->nt, nt_groups);
+                       f->nt.get(), nt_groups);
     TRACS_HIP_CHECK(hipEventRecord(ev[5], stream));
-    launch_ns_build(a->planes, a->n_pad, groups, f->ns, ns_words, stream);
+    launch_ns_build(a->planes, a->n_pad, groups, f->ns.get(), ns_words, stream);
     TRACS_HIP_CHECK(hipEventRecord(ev[6], stream));
     TRACS_HIP_CHECK(hipGetLastError());
     TRACS_HIP_CHECK(hipStreamSynchronize(stream));
@@ -1171,12 +1160,12 @@ static int filter_index_get(tracs_alignment *a, hipStream_t stream)
 // The threshold rows of the handle: allocated on first use, all marked "not built" when the alignment's length is another
 static int flt_table_rows(FilterIndex *f, const tracs_alignment *a, hipStream_t stream)
 {
-    if (f->tbl && f->tbl_L == (unsigned)a->L) return TRACS_OK;
-    if (!f->tbl) {
-        if (hipMalloc(reinterpret_cast<void **>(&f->tbl), ((size_t)FLT_DCAP + 1) * FLT_KT * 4) != hipSuccess) { f->tbl = nullptr; set_error("filter: out of device memory"); return TRACS_E_NOMEM; }
-        if (hipMalloc(reinterpret_cast<void **>(&f->tbl_state), FLT_DCAP + 256) != hipSuccess) { f->tbl_state = nullptr; set_error("filter: out of device memory"); return TRACS_E_NOMEM; }
+    if (f->tbl.get() && f->tbl_L == (unsigned)a->L) return TRACS_OK;
+    if (!f->tbl.get() || !f->tbl_state.get()) {
+        int rc;
+        if ((rc = f->tbl.alloc(((size_t)FLT_DCAP + 1) * FLT_KT, "filter thresholds")) || (rc = f->tbl_state.alloc(FLT_DCAP + 256, "filter threshold states"))) return rc;
     }
-    TRACS_HIP_CHECK(hipMemsetAsync(f->tbl_state, 0, FLT_DCAP + 256, stream));
+    TRACS_HIP_CHECK(hipMemsetAsync(f->tbl_state.get(), 0, FLT_DCAP + 256, stream));
     f->tbl_L = (unsigned)a->L;
     return TRACS_OK;
 }
@@ -1203,18 +1192,18 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
     if (rc) return rc;
     if ((rc = filter_index_get(a, stream))) return rc;
     FilterIndex *f = a->flt;
-    if (!f->counters && hipMalloc(reinterpret_cast<void **>(&f->counters), 64) != hipSuccess) { f->counters = nullptr; set_error("filter: out of device memory"); return TRACS_E_NOMEM; }
-    TRACS_HIP_CHECK(hipMemsetAsync(f->counters, 0, 64, stream));
+    if (!f->counters.get() && (rc = f->counters.alloc(16, "filter counters"))) return rc;
+    TRACS_HIP_CHECK(hipMemsetAsync(f->counters.get(), 0, 64, stream));
     // thresholds of the binomial test for the d of this call
     const bool use_tbl = !flt_env_off("TRACS_FILTER_TABLE");
     if (use_tbl) {
         if ((rc = flt_table_rows(f, a, stream))) return rc;
         const unsigned blocks = (unsigned)std::min<size_t>((n_pairs + 255) / 256, 256 * 16);
-        hipLaunchKernelGGL(flt_mark_kernel, dim3(blocks), dim3(256), 0, stream, d, n_pairs, f->tbl_state);
-        hipLaunchKernelGGL(flt_table_kernel, dim3(FLT_DCAP - 1), dim3(FLT_KT), 0, stream, (unsigned)a->L, lg, f->tbl_state, f->tbl);
-        hipLaunchKernelGGL(flt_table_done_kernel, dim3((FLT_DCAP + 256) / 256), dim3(256), 0, stream, f->tbl_state);
+        hipLaunchKernelGGL(flt_mark_kernel, dim3(blocks), dim3(256), 0, stream, d, n_pairs, f->tbl_state.get());
+        hipLaunchKernelGGL(flt_table_kernel, dim3(FLT_DCAP - 1), dim3(FLT_KT), 0, stream, (unsigned)a->L, lg, f->tbl_state.get(), f->tbl.get());
+        hipLaunchKernelGGL(flt_table_done_kernel, dim3((FLT_DCAP + 256) / 256), dim3(256), 0, stream, f->tbl_state.get());
     }
-    const unsigned *tbl = use_tbl ? f->tbl : nullptr;
+    const unsigned *tbl = use_tbl ? f->tbl.get() : nullptr;
     size_t n_left = n_pairs;
     unsigned max_d_left = 0;
     bool all_left = true;
@@ -1223,12 +1212,12 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
         if (const char *e = std::getenv("TRACS_FILTER_CAP")) cap = std::max(64u, std::min(FLT_CAP_MAX, (unsigned)std::atoi(e) / 64u * 64u));
         FltPairArgs A;
         A.rows = rows; A.cols = cols; A.d = d; A.n_pairs = n_pairs;
-        A.dep = f->dep; A.dep_off = f->dep_off;
-        A.nt = reinterpret_cast<const unsigned *>(f->nt); A.ns = f->ns;
+        A.dep = f->dep.get(); A.dep_off = f->dep_off.get();
+        A.nt = reinterpret_cast<const unsigned *>(f->nt.get()); A.ns = f->ns.get();
         A.nt_words = f->nt_groups * 4; A.ns_words = f->ns_words;
         A.L = (unsigned)a->L; A.cap = cap;
-        A.tbl = tbl; A.tbl_state = f->tbl_state; A.lg = lg;
-        A.filt = filt; A.counters = f->counters;
+        A.tbl = tbl; A.tbl_state = f->tbl_state.get(); A.lg = lg;
+        A.filt = filt; A.counters = f->counters.get();
         const char *form_env = std::getenv("TRACS_FILTER_KERNEL");
         const int form = form_env ? std::atoi(form_env) : 2;
         if (form == 2 && cap <= 1024) {
@@ -1247,7 +1236,7 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
             hipLaunchKernelGGL((flt_pairs_kernel<1>), dim3((unsigned)n_pairs), dim3(64), (size_t)cap * 16, stream, A);
         TRACS_HIP_CHECK(hipGetLastError());
         unsigned h[4] = {0, 0, 0, 0};
-        TRACS_HIP_CHECK(hipMemcpyAsync(h, f->counters, 16, hipMemcpyDeviceToHost, stream));
+        TRACS_HIP_CHECK(hipMemcpyAsync(h, f->counters.get(), 16, hipMemcpyDeviceToHost, stream));
         TRACS_HIP_CHECK(hipStreamSynchronize(stream));
         if (h[0]) { set_error("filter: SNP site list does not match the distance (internal error)"); return TRACS_E_HIP; }
         n_left = h[1];
@@ -1256,13 +1245,13 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
     }
     if (n_left == 0) return TRACS_OK;
     // the scan of the planes for what is left (filter.hip)
-    TRACS_HIP_CHECK(hipMemsetAsync(f->counters, 0, 4, stream));
+    TRACS_HIP_CHECK(hipMemsetAsync(f->counters.get(), 0, 4, stream));
     const unsigned blocks = (unsigned)std::min<size_t>((n_pairs + 255) / 256, 256 * 16);
     if (all_left) {
-        hipLaunchKernelGGL(flt_max_kernel, dim3(blocks), dim3(256), 0, stream, d, n_pairs, f->counters + 2);
-        TRACS_HIP_CHECK(hipMemcpyAsync(&max_d_left, f->counters + 2, 4, hipMemcpyDeviceToHost, stream));
+        hipLaunchKernelGGL(flt_max_kernel, dim3(blocks), dim3(256), 0, stream, d, n_pairs, f->counters.get() + 2);
+        TRACS_HIP_CHECK(hipMemcpyAsync(&max_d_left, f->counters.get() + 2, 4, hipMemcpyDeviceToHost, stream));
         TRACS_HIP_CHECK(hipStreamSynchronize(stream));
-        if ((rc = filter_scan_route(a, rows, cols, d, n_pairs, max_d_left, filt, tbl, f->tbl_state, lg, f->counters, stream))) return rc;
+        if ((rc = filter_scan_route(a, rows, cols, d, n_pairs, max_d_left, filt, tbl, f->tbl_state.get(), lg, f->counters.get(), stream))) return rc;
     } else {
         // lists too long for a wave's LDS: the same merge over global memory (flt_pairs_long_kernel)
         unsigned *idx, *scratch;
@@ -1271,16 +1260,16 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
         while (waves > 256 && waves * slot * 4 > (3ull << 30)) waves /= 2;
         if ((rc = workspace_get(WS_FLT_IDX, n_left, &idx)) ||
             (rc = workspace_get(WS_FLT_SCRATCH, waves * slot, &scratch))) return rc;
-        TRACS_HIP_CHECK(hipMemsetAsync(f->counters + 4, 0, 4, stream));
-        hipLaunchKernelGGL(flt_collect_kernel, dim3(blocks), dim3(256), 0, stream, filt, n_pairs, idx, f->counters + 4);
+        TRACS_HIP_CHECK(hipMemsetAsync(f->counters.get() + 4, 0, 4, stream));
+        hipLaunchKernelGGL(flt_collect_kernel, dim3(blocks), dim3(256), 0, stream, filt, n_pairs, idx, f->counters.get() + 4);
         FltPairArgs A;
         A.rows = rows; A.cols = cols; A.d = d; A.n_pairs = n_pairs;
-        A.dep = f->dep; A.dep_off = f->dep_off;
-        A.nt = reinterpret_cast<const unsigned *>(f->nt); A.ns = f->ns;
+        A.dep = f->dep.get(); A.dep_off = f->dep_off.get();
+        A.nt = reinterpret_cast<const unsigned *>(f->nt.get()); A.ns = f->ns.get();
         A.nt_words = f->nt_groups * 4; A.ns_words = f->ns_words;
         A.L = (unsigned)a->L; A.cap = 0;
-        A.tbl = tbl; A.tbl_state = f->tbl_state; A.lg = lg;
-        A.filt = filt; A.counters = f->counters;
+        A.tbl = tbl; A.tbl_state = f->tbl_state.get(); A.lg = lg;
+        A.filt = filt; A.counters = f->counters.get();
         // (TRACS_FILTER_LONG=seq: the per-lane sequential merge over global memory instead of the tiled one: tests, A/B)
         const char *lf = std::getenv("TRACS_FILTER_LONG");
         if (lf && lf[0] == 's')
@@ -1291,7 +1280,7 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
     }
     TRACS_HIP_CHECK(hipGetLastError());
     unsigned bad = 0;
-    TRACS_HIP_CHECK(hipMemcpyAsync(&bad, f->counters, 4, hipMemcpyDeviceToHost, stream));
+    TRACS_HIP_CHECK(hipMemcpyAsync(&bad, f->counters.get(), 4, hipMemcpyDeviceToHost, stream));
     TRACS_HIP_CHECK(hipStreamSynchronize(stream));
     if (bad) { set_error("filter: SNP site list does not match the distance (internal error)"); return TRACS_E_HIP; }
     return TRACS_OK;
@@ -1335,12 +1324,12 @@ int tracs_filter_recomb_lists(tracs_alignment *a, const int64_t *off, const uint
     if (use_tbl) {
         if ((rc = flt_table_rows(f, a, stream))) return rc;
         const unsigned blocks = (unsigned)std::min<size_t>((n_lists + 255) / 256, 256 * 16);
-        hipLaunchKernelGGL(flt_mark_lists_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<const long long *>(off), n_lists, f->tbl_state);
-        hipLaunchKernelGGL(flt_table_kernel, dim3(FLT_DCAP - 1), dim3(FLT_KT), 0, stream, (unsigned)a->L, lg, f->tbl_state, f->tbl);
-        hipLaunchKernelGGL(flt_table_done_kernel, dim3((FLT_DCAP + 256) / 256), dim3(256), 0, stream, f->tbl_state);
+        hipLaunchKernelGGL(flt_mark_lists_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<const long long *>(off), n_lists, f->tbl_state.get());
+        hipLaunchKernelGGL(flt_table_kernel, dim3(FLT_DCAP - 1), dim3(FLT_KT), 0, stream, (unsigned)a->L, lg, f->tbl_state.get(), f->tbl.get());
+        hipLaunchKernelGGL(flt_table_done_kernel, dim3((FLT_DCAP + 256) / 256), dim3(256), 0, stream, f->tbl_state.get());
     }
     hipLaunchKernelGGL(flt_lists_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const long long *>(off), pos,
-                       n_lists, total, (unsigned)a->L, use_tbl ? f->tbl : nullptr, f->tbl_state, lg, filt, dropped);
+                       n_lists, total, (unsigned)a->L, use_tbl ? f->tbl.get() : nullptr, f->tbl_state.get(), lg, filt, dropped);
     TRACS_HIP_CHECK(hipGetLastError());
     return TRACS_OK;
 }

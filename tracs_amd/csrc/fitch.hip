@@ -36,6 +36,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -555,11 +556,6 @@ static inline void fitch_append_u64(std::string &s, uint64_t v)
     s.append(buf + k, 24 - k);
 }
 
-FitchTables::~FitchTables()
-{
-    for (void *p : {(void *)d_edge, (void *)d_site, (void *)d_min, (void *)d_off}) if (p) (void)hipFree(p);
-}
-
 // The count pass for the handle's tree; what the writer needs stays in `t` (the device arrays; on the host the edges' counts, the
 // offsets and the minimum).  sum_minimum: over the sites with a change.
 int fitch_tables(const tracs_alignment *a, const uint32_t *parent, const uint32_t *child, size_t n_edges, FitchTables &t)
@@ -567,19 +563,15 @@ int fitch_tables(const tracs_alignment *a, const uint32_t *parent, const uint32_
     int rc = fitch_check(a, "tracs_distance_tree_changes");
     if (rc) return rc;
     const size_t L = a->L;
-#define FT_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { (void)hipGetLastError(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
-    FT_CHECK(hipMalloc(reinterpret_cast<void **>(&t.d_edge), std::max<size_t>(n_edges, 1) * 4));
-    FT_CHECK(hipMalloc(reinterpret_cast<void **>(&t.d_site), std::max<size_t>(L, 1) * 4));
-    FT_CHECK(hipMalloc(reinterpret_cast<void **>(&t.d_min), std::max<size_t>(L, 1)));
-    FT_CHECK(hipMalloc(reinterpret_cast<void **>(&t.d_off), (L + 1) * 8));
-    if ((rc = fitch_count(a, parent, child, n_edges, t.d_edge, t.d_site, t.d_min, t.d_off, &t.total, nullptr))) return rc;
+    if ((rc = t.d_edge.alloc(std::max<size_t>(n_edges, 1), "changes by edge")) || (rc = t.d_site.alloc(std::max<size_t>(L, 1), "changes by site")) ||
+        (rc = t.d_min.alloc(std::max<size_t>(L, 1), "site minimum")) || (rc = t.d_off.alloc(L + 1, "site offsets"))) return rc;
+    if ((rc = fitch_count(a, parent, child, n_edges, t.d_edge.get(), t.d_site.get(), t.d_min.get(), t.d_off.get(), &t.total, nullptr))) return rc;
     t.edge_changes.assign(n_edges, 0);
     t.off.assign(L + 1, 0);
     t.minimum.assign(L, 0);
-    if (n_edges) FT_CHECK(hipMemcpy(t.edge_changes.data(), t.d_edge, n_edges * 4, hipMemcpyDeviceToHost));
-    FT_CHECK(hipMemcpy(t.off.data(), t.d_off, (L + 1) * 8, hipMemcpyDeviceToHost));
-    if (L) FT_CHECK(hipMemcpy(t.minimum.data(), t.d_min, L, hipMemcpyDeviceToHost));
-#undef FT_CHECK
+    if (n_edges) TRACS_HIP_CHECK(hipMemcpy(t.edge_changes.data(), t.d_edge.get(), n_edges * 4, hipMemcpyDeviceToHost));
+    TRACS_HIP_CHECK(hipMemcpy(t.off.data(), t.d_off.get(), (L + 1) * 8, hipMemcpyDeviceToHost));
+    if (L) TRACS_HIP_CHECK(hipMemcpy(t.minimum.data(), t.d_min.get(), L, hipMemcpyDeviceToHost));
     t.sum_minimum = 0;
     for (size_t s = 0; s < L; s++) if (t.off[s + 1] > t.off[s]) t.sum_minimum += t.minimum[s];
     return TRACS_OK;
@@ -653,15 +645,8 @@ int fitch_write(const tracs_alignment *a, const char *const *names, const uint64
     }
     if (!changes_path) return TRACS_OK;
     DeviceCall guard(nullptr);
-    unsigned *d_ent = nullptr, *h_ent = nullptr;
-    FILE *fp = nullptr;
-    auto done = [&](int r) {
-        if (d_ent) (void)hipFree(d_ent);
-        if (h_ent) (void)hipHostFree(h_ent);
-        if (fp) std::fclose(fp);
-        return r;
-    };
-#define FW_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { (void)hipGetLastError(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return done(TRACS_E_HIP); } } while (0)
+    DeviceArray<unsigned> ent_buf;
+    PinnedArray<unsigned> host_buf;
     const std::vector<long long> &off = t.off;
     const uint64_t total = t.total;
     size_t cap = (256ull << 20) / 12;                                      // entries per batch: 12 bytes each
@@ -669,12 +654,11 @@ int fitch_write(const tracs_alignment *a, const char *const *names, const uint64
     long long max_c = 0;
     for (size_t s = 0; s < L; s++) max_c = std::max(max_c, off[s + 1] - off[s]);
     const size_t room = std::max<size_t>(std::max<size_t>(std::min<size_t>(cap, total), (size_t)max_c), 1);
-    if (total) {
-        FW_CHECK(hipMalloc(reinterpret_cast<void **>(&d_ent), room * 12));
-        FW_CHECK(hipHostMalloc(reinterpret_cast<void **>(&h_ent), room * 12, hipHostMallocDefault));
-    }
-    fp = std::fopen(changes_path, "ab");
-    if (!fp) { set_error(std::string("cannot open ") + changes_path + " for appending"); return done(TRACS_E_OPEN); }
+    if (total && ((rc = ent_buf.alloc(room * 3, "tree-change entries")) || (rc = host_buf.alloc(room * 3, "tree-change entries")))) return rc;
+    unsigned *const d_ent = ent_buf.get(), *const h_ent = host_buf.get();
+    std::unique_ptr<FILE, int (*)(FILE *)> file(std::fopen(changes_path, "ab"), std::fclose);
+    FILE *fp = file.get();
+    if (!fp) { set_error(std::string("cannot open ") + changes_path + " for appending"); return TRACS_E_OPEN; }
     // "parent,child," of every edge (internal node n + t is "#t+1", as in the edge rows)
     std::vector<std::string> head(n_edges);
     for (size_t e = 0; e < n_edges; e++) {
@@ -695,10 +679,10 @@ int fitch_write(const tracs_alignment *a, const char *const *names, const uint64
         const long long base = off[s0];
         const size_t entries = (size_t)(off[s1] - base);
         if (entries) {
-            if ((rc = fitch_fill(a, parent, child, n_edges, s0, s1, t.d_off, base, d_ent, d_ent + room, d_ent + 2 * room, room, nullptr))) return done(rc);
+            if ((rc = fitch_fill(a, parent, child, n_edges, s0, s1, t.d_off.get(), base, d_ent, d_ent + room, d_ent + 2 * room, room, nullptr))) return rc;
             if (flt && (rc = fitch_mark_dropped(d_ent, d_ent + room, d_ent + 2 * room, entries, n_edges, flt->d_edge_off, flt->d_edge_site,
-                                                flt->d_dropped, nullptr))) return done(rc);
-            for (int q = 0; q < 3; q++) FW_CHECK(hipMemcpy(h_ent + q * room, d_ent + q * room, entries * 4, hipMemcpyDeviceToHost));
+                                                flt->d_dropped, nullptr))) return rc;
+            for (int q = 0; q < 3; q++) TRACS_HIP_CHECK(hipMemcpy(h_ent + q * room, d_ent + q * room, entries * 4, hipMemcpyDeviceToHost));
             const unsigned *h_site = h_ent, *h_edge = h_ent + room, *h_info = h_ent + 2 * room;
             auto format = [&](size_t k, size_t e0, size_t e1) {
                 std::string &s = text[k];
@@ -728,16 +712,13 @@ int fitch_write(const tracs_alignment *a, const char *const *names, const uint64
                     for (auto &th : pool) th.join();
                 }
                 for (size_t k = 0; k < used; k++)
-                    if ((rc = append_file(changes_path, text[k], fp))) return done(rc);
+                    if ((rc = append_file(changes_path, text[k], fp))) return rc;
             }
         }
         s0 = s1;
     }
-#undef FW_CHECK
-    FILE *f = fp;
-    fp = nullptr;
-    if (std::fclose(f) != 0) { set_error(std::string("write error on ") + changes_path); return done(TRACS_E_OPEN); }
-    return done(TRACS_OK);
+    if (std::fclose(file.release()) != 0) { set_error(std::string("write error on ") + changes_path); return TRACS_E_OPEN; }
+    return TRACS_OK;
 }
 
 }  // namespace tracs

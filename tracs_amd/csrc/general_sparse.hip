@@ -23,14 +23,15 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <vector>
 
 namespace tracs {
 
 struct GeneralSparse {
-    unsigned long long *s_off = nullptr, *p_off = nullptr, *n_off = nullptr;
-    unsigned *s_ent = nullptr, *p_ent = nullptr, *n_ent = nullptr;
-    unsigned *c_n = nullptr, *c_p = nullptr;      // per sample: its N sites, the sum of w over its listed (partial) sites
+    DeviceArray<unsigned long long> s_off, p_off, n_off;
+    DeviceArray<unsigned> s_ent, p_ent, n_ent;
+    DeviceArray<unsigned> c_n, c_p;               // per sample: its N sites, the sum of w over its listed (partial) sites
     double est_updates = 0.0;
     unsigned long long tot_s = 0;                 // entries of the per-sample lists
     unsigned long long max_row = 0;               // the longest per-sample list
@@ -328,18 +329,10 @@ __global__ __launch_bounds__(1024) void general_fixup_kernel(const unsigned long
         }
 }
 
-static void gs_free(GeneralSparse *g)
-{
-    if (!g) return;
-    void *p[] = {g->s_off, g->p_off, g->n_off, g->s_ent, g->p_ent, g->n_ent, g->c_n, g->c_p};
-    for (void *q : p) if (q) (void)hipFree(q);
-    delete g;
-}
-
 void general_sparse_free(tracs_alignment *a)
 {
     if (!a) return;
-    gs_free(a->sparse);
+    delete a->sparse;
     a->sparse = nullptr;
     a->sparse_state = 0;
 }
@@ -353,62 +346,52 @@ static int gs_build(const SRC src, size_t n, size_t L, size_t groups, double max
 {
     *out = nullptr;
     if (L >= (1ull << 27) || n >= (1ull << 27) || L == 0) return TRACS_OK;        // entries hold site << 5 / sample << 5
-    auto *g = new GeneralSparse();
-    unsigned *cnt = nullptr, *cn = nullptr, *cw = nullptr, *cntP = nullptr, *cntN = nullptr;
-    unsigned long long *off = nullptr;
-    double *d_est = nullptr;
-    auto tmp_free = [&]() { void *p[] = {cnt, cn, cw, cntP, cntN, off, d_est}; for (void *q : p) if (q) (void)hipFree(q); };
-    auto fail_soft = [&]() { tmp_free(); (void)hipGetLastError(); gs_free(g); return TRACS_OK; };
-#define GS_TRY(x) do { if ((x) != hipSuccess) return fail_soft(); } while (0)
+    std::unique_ptr<GeneralSparse> g(new GeneralSparse());
+    DeviceArray<unsigned> cnt_buf, cn_buf, cw_buf, cntP_buf, cntN_buf;
+    DeviceArray<unsigned long long> off_buf;
+    DeviceArray<double> est_buf;
+    const auto fail_soft = [] { (void)hipGetLastError(); return TRACS_OK; };       // (the owners free what was allocated)
+    const auto failed = [](hipError_t e) { return e != hipSuccess; };
     const size_t nsc = n * GS_CHUNKS;
     const size_t gpc = (groups + GS_CHUNKS - 1) / GS_CHUNKS;
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&cnt), nsc * 4));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&cn), nsc * 4));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&cw), nsc * 4));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&off), (nsc + 1) * 8));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&cntP), (L + 1) * 4));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&cntN), (L + 1) * 4));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&d_est), 8));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&g->s_off), (n + 1) * 8));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&g->p_off), (L + 1) * 8));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&g->n_off), (L + 1) * 8));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&g->c_n), std::max<size_t>(n, 1) * 4));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&g->c_p), std::max<size_t>(n, 1) * 4));
-    GS_TRY(hipMemsetAsync(d_est, 0, 8, stream));
+    if (!cnt_buf.try_alloc(nsc) || !cn_buf.try_alloc(nsc) || !cw_buf.try_alloc(nsc) || !off_buf.try_alloc(nsc + 1) || !cntP_buf.try_alloc(L + 1) ||
+        !cntN_buf.try_alloc(L + 1) || !est_buf.try_alloc(1) || !g->s_off.try_alloc(n + 1) || !g->p_off.try_alloc(L + 1) || !g->n_off.try_alloc(L + 1) ||
+        !g->c_n.try_alloc(std::max<size_t>(n, 1)) || !g->c_p.try_alloc(std::max<size_t>(n, 1))) return fail_soft();
+    unsigned *const cnt = cnt_buf.get(), *const cn = cn_buf.get(), *const cw = cw_buf.get(), *const cntP = cntP_buf.get(), *const cntN = cntN_buf.get();
+    unsigned long long *const off = off_buf.get();
+    double *const d_est = est_buf.get();
+    if (failed(hipMemsetAsync(d_est, 0, 8, stream))) return fail_soft();
 
     const dim3 sgrid((unsigned)((n + 63) / 64), GS_CHUNKS / 4);
     hipLaunchKernelGGL((gs_sample_kernel<false, SRC>), sgrid, dim3(256), 0, stream, src, n, groups, gpc, cnt, cn, cw, nullptr, nullptr);
     hipLaunchKernelGGL(gs_scan_kernel, dim3(1), dim3(1024), 0, stream, cnt, nsc, off);
-    hipLaunchKernelGGL(gs_sample_totals_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, stream, cw, cn, n, g->c_n, g->c_p, off, g->s_off);
-    GS_TRY(hipMemsetAsync(cntP, 0, (L + 1) * 4, stream));
-    GS_TRY(hipMemsetAsync(cntN, 0, (L + 1) * 4, stream));
+    hipLaunchKernelGGL(gs_sample_totals_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, stream, cw, cn, n, g->c_n.get(), g->c_p.get(), off, g->s_off.get());
+    if (failed(hipMemsetAsync(cntP, 0, (L + 1) * 4, stream))) return fail_soft();
+    if (failed(hipMemsetAsync(cntN, 0, (L + 1) * 4, stream))) return fail_soft();
     hipLaunchKernelGGL((gs_site_kernel<false, SRC>), dim3((unsigned)groups), dim3(256), 0, stream, src, n, L, cntP, cntN,
                        nullptr, nullptr, nullptr, nullptr, d_est);
-    hipLaunchKernelGGL(gs_scan_kernel, dim3(1), dim3(1024), 0, stream, cntP, L, g->p_off);
-    hipLaunchKernelGGL(gs_scan_kernel, dim3(1), dim3(1024), 0, stream, cntN, L, g->n_off);
+    hipLaunchKernelGGL(gs_scan_kernel, dim3(1), dim3(1024), 0, stream, cntP, L, g->p_off.get());
+    hipLaunchKernelGGL(gs_scan_kernel, dim3(1), dim3(1024), 0, stream, cntN, L, g->n_off.get());
     unsigned long long tot_s = 0, tot_p = 0, tot_n = 0;
     double est = 0.0;
-    GS_TRY(hipMemcpyAsync(&tot_s, off + nsc, 8, hipMemcpyDeviceToHost, stream));
-    GS_TRY(hipMemcpyAsync(&tot_p, g->p_off + L, 8, hipMemcpyDeviceToHost, stream));
-    GS_TRY(hipMemcpyAsync(&tot_n, g->n_off + L, 8, hipMemcpyDeviceToHost, stream));
-    GS_TRY(hipMemcpyAsync(&est, d_est, 8, hipMemcpyDeviceToHost, stream));
-    GS_TRY(hipStreamSynchronize(stream));
-    if (tot_s != tot_p + tot_n) { tmp_free(); gs_free(g); set_error("general_sparse: list totals disagree (internal error)"); return TRACS_E_HIP; }
+    if (failed(hipMemcpyAsync(&tot_s, off + nsc, 8, hipMemcpyDeviceToHost, stream))) return fail_soft();
+    if (failed(hipMemcpyAsync(&tot_p, g->p_off.get() + L, 8, hipMemcpyDeviceToHost, stream))) return fail_soft();
+    if (failed(hipMemcpyAsync(&tot_n, g->n_off.get() + L, 8, hipMemcpyDeviceToHost, stream))) return fail_soft();
+    if (failed(hipMemcpyAsync(&est, d_est, 8, hipMemcpyDeviceToHost, stream))) return fail_soft();
+    if (failed(hipStreamSynchronize(stream))) return fail_soft();
+    if (tot_s != tot_p + tot_n) { set_error("general_sparse: list totals disagree (internal error)"); return TRACS_E_HIP; }
     // TRACS_LIST_CAP=<entries>: a smaller cap (diagnostics: exercises the paths taken when the lists are refused)
     static const double env_cap = [] { const char *e = std::getenv("TRACS_LIST_CAP"); return e ? std::atof(e) : -1.0; }();
     if ((double)tot_s > (env_cap >= 0.0 ? std::min(env_cap, max_entries) : max_entries)) return fail_soft();
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&g->s_ent), std::max<size_t>(tot_s, 1) * 4));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&g->p_ent), std::max<size_t>(tot_p, 1) * 4));
-    GS_TRY(hipMalloc(reinterpret_cast<void **>(&g->n_ent), std::max<size_t>(tot_n, 1) * 4));
-    hipLaunchKernelGGL((gs_sample_kernel<true, SRC>), sgrid, dim3(256), 0, stream, src, n, groups, gpc, nullptr, nullptr, nullptr, off, g->s_ent);
+    if (!g->s_ent.try_alloc(std::max<size_t>(tot_s, 1)) || !g->p_ent.try_alloc(std::max<size_t>(tot_p, 1)) ||
+        !g->n_ent.try_alloc(std::max<size_t>(tot_n, 1))) return fail_soft();
+    hipLaunchKernelGGL((gs_sample_kernel<true, SRC>), sgrid, dim3(256), 0, stream, src, n, groups, gpc, nullptr, nullptr, nullptr, off, g->s_ent.get());
     hipLaunchKernelGGL((gs_site_kernel<true, SRC>), dim3((unsigned)groups), dim3(256), 0, stream, src, n, L, nullptr, nullptr,
-                       g->p_off, g->n_off, g->p_ent, g->n_ent, nullptr);
-    GS_TRY(hipGetLastError());
-    GS_TRY(hipStreamSynchronize(stream));
-#undef GS_TRY
-    tmp_free();
+                       g->p_off.get(), g->n_off.get(), g->p_ent.get(), g->n_ent.get(), nullptr);
+    if (failed(hipGetLastError())) return fail_soft();
+    if (failed(hipStreamSynchronize(stream))) return fail_soft();
     g->est_updates = est;
-    *out = g;
+    *out = g.release();
     return TRACS_OK;
 }
 
@@ -439,8 +422,8 @@ static int fixup_launch(const GeneralSparse *g, unsigned L, size_t n, size_t row
         attr_set[dev] = true;
     }
     const dim3 grid((unsigned)(row_end - row_begin), (unsigned)((n + chunk - 1) / chunk));
-    hipLaunchKernelGGL(general_fixup_kernel, grid, dim3(1024), chunk * 4, stream, g->s_off, g->s_ent, g->p_off, g->p_ent, g->n_off,
-                       g->n_ent, g->c_n, L, (unsigned)n, (unsigned)row_begin, (unsigned)col_begin, chunk, dist, ncomp, ld);
+    hipLaunchKernelGGL(general_fixup_kernel, grid, dim3(1024), chunk * 4, stream, g->s_off.get(), g->s_ent.get(), g->p_off.get(), g->p_ent.get(), g->n_off.get(),
+                       g->n_ent.get(), g->c_n.get(), L, (unsigned)n, (unsigned)row_begin, (unsigned)col_begin, chunk, dist, ncomp, ld);
     TRACS_HIP_CHECK(hipGetLastError());
     return TRACS_OK;
 }

@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -320,45 +321,37 @@ int pair_sites_write(const tracs_alignment *a, const char *const *names, const u
         }
     }
     DeviceCall guard(nullptr);
-    unsigned *d_rows = nullptr, *d_cols = nullptr, *d_d = nullptr, *d_ent = nullptr, *h_ent = nullptr;
-    long long *d_off = nullptr;
-    FILE *fp = nullptr;
-    auto done = [&](int r) {
-        for (void *p : {(void *)d_rows, (void *)d_cols, (void *)d_d, (void *)d_ent, (void *)d_off}) if (p) (void)hipFree(p);
-        if (h_ent) (void)hipHostFree(h_ent);
-        if (fp) std::fclose(fp);
-        return r;
-    };
-#define PS_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { (void)hipGetLastError(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return done(TRACS_E_HIP); } } while (0)
+    DeviceArray<unsigned> rows_buf, cols_buf, d_buf, ent_buf;
+    PinnedArray<unsigned> host_buf;
+    DeviceArray<long long> off_buf;
     const size_t np1 = std::max<size_t>(n_pairs, 1);
-    PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_rows), np1 * 4));
-    PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_cols), np1 * 4));
-    PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_d), np1 * 4));
-    PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_off), (n_pairs + 1) * 8));
+    if ((rc = rows_buf.alloc(np1, "pair rows")) || (rc = cols_buf.alloc(np1, "pair columns")) || (rc = d_buf.alloc(np1, "pair distances")) ||
+        (rc = off_buf.alloc(n_pairs + 1, "pair offsets"))) return rc;
+    unsigned *const d_rows = rows_buf.get(), *const d_cols = cols_buf.get(), *const d_d = d_buf.get();
+    long long *const d_off = off_buf.get();
     if (n_pairs) {
-        PS_CHECK(hipMemcpy(d_rows, rows, n_pairs * 4, hipMemcpyHostToDevice));
-        PS_CHECK(hipMemcpy(d_cols, cols, n_pairs * 4, hipMemcpyHostToDevice));
+        TRACS_HIP_CHECK(hipMemcpy(d_rows, rows, n_pairs * 4, hipMemcpyHostToDevice));
+        TRACS_HIP_CHECK(hipMemcpy(d_cols, cols, n_pairs * 4, hipMemcpyHostToDevice));
     }
     uint64_t total = 0;
-    if ((rc = pair_sites_count(a, d_rows, d_cols, n_pairs, d_d, d_off, &total, nullptr))) return done(rc);
+    if ((rc = pair_sites_count(a, d_rows, d_cols, n_pairs, d_d, d_off, &total, nullptr))) return rc;
     if (total > max_entries) {
         set_error("the listed pairs differ at " + std::to_string(total) + " sites in all, more than --max-entries " + std::to_string(max_entries) +
                   "; nothing was written");
-        return done(TRACS_E_ARG);
+        return TRACS_E_ARG;
     }
     std::vector<long long> off(n_pairs + 1, 0);
-    PS_CHECK(hipMemcpy(off.data(), d_off, (n_pairs + 1) * 8, hipMemcpyDeviceToHost));
+    TRACS_HIP_CHECK(hipMemcpy(off.data(), d_off, (n_pairs + 1) * 8, hipMemcpyDeviceToHost));
     size_t cap = (256ull << 20) / 8;                                       // entries per batch: 8 bytes each
     if (const char *e = std::getenv("TRACS_PAIR_SITES_BATCH")) cap = std::max<size_t>(1, (size_t)std::strtoull(e, nullptr, 10));
     long long max_d = 0;
     for (size_t t = 0; t < n_pairs; t++) max_d = std::max(max_d, off[t + 1] - off[t]);
     const size_t room = std::max<size_t>(std::max<size_t>(std::min<size_t>(cap, total), (size_t)max_d), 1);
-    if (total) {
-        PS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_ent), room * 8));
-        PS_CHECK(hipHostMalloc(reinterpret_cast<void **>(&h_ent), room * 8, hipHostMallocDefault));
-    }
-    fp = std::fopen(path, "w");
-    if (!fp) { set_error(std::string("cannot write ") + path); return done(TRACS_E_OPEN); }
+    if (total && ((rc = ent_buf.alloc(room * 2, "pair-site entries")) || (rc = host_buf.alloc(room * 2, "pair-site entries")))) return rc;
+    unsigned *const d_ent = ent_buf.get(), *const h_ent = host_buf.get();
+    std::unique_ptr<FILE, int (*)(FILE *)> file(std::fopen(path, "w"), std::fclose);
+    FILE *const fp = file.get();
+    if (!fp) { set_error(std::string("cannot write ") + path); return TRACS_E_OPEN; }
     std::fputs("sampleA,sampleB,contig,position,alleleA,alleleB,dropped\n", fp);
     const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     const size_t n_thr = n_threads > 0 ? std::min<size_t>((size_t)n_threads, 64) : hw;
@@ -371,9 +364,9 @@ int pair_sites_write(const tracs_alignment *a, const char *const *names, const u
         const long long base = off[t0];
         const size_t entries = (size_t)(off[t1] - base);
         if (entries) {
-            if ((rc = pair_sites_fill(a, d_rows + t0, d_cols + t0, t1 - t0, d_off + t0, base, d_ent, d_ent + room, room, filter, nullptr))) return done(rc);
-            PS_CHECK(hipMemcpy(h_ent, d_ent, entries * 4, hipMemcpyDeviceToHost));
-            PS_CHECK(hipMemcpy(h_ent + room, d_ent + room, entries * 4, hipMemcpyDeviceToHost));
+            if ((rc = pair_sites_fill(a, d_rows + t0, d_cols + t0, t1 - t0, d_off + t0, base, d_ent, d_ent + room, room, filter, nullptr))) return rc;
+            TRACS_HIP_CHECK(hipMemcpy(h_ent, d_ent, entries * 4, hipMemcpyDeviceToHost));
+            TRACS_HIP_CHECK(hipMemcpy(h_ent + room, d_ent + room, entries * 4, hipMemcpyDeviceToHost));
             const unsigned *h_site = h_ent, *h_info = h_ent + room;
             auto format = [&](size_t k, size_t e0, size_t e1) {
                 std::string &s = text[k];
@@ -417,18 +410,15 @@ int pair_sites_write(const tracs_alignment *a, const char *const *names, const u
                 for (size_t k = 0; k < used; k++)
                     if (!text[k].empty() && std::fwrite(text[k].data(), 1, text[k].size(), fp) != text[k].size()) {
                         set_error(std::string("write error on ") + path);
-                        return done(TRACS_E_OPEN);
+                        return TRACS_E_OPEN;
                     }
             }
         }
         t0 = t1;
     }
-#undef PS_CHECK
-    FILE *f = fp;
-    fp = nullptr;
-    if (std::fclose(f) != 0) { set_error(std::string("write error on ") + path); return done(TRACS_E_OPEN); }
+    if (std::fclose(file.release()) != 0) { set_error(std::string("write error on ") + path); return TRACS_E_OPEN; }
     if (rows_written) *rows_written = total;
-    return done(TRACS_OK);
+    return TRACS_OK;
 }
 
 }  // namespace tracs

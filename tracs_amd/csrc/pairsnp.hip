@@ -625,13 +625,13 @@ static size_t plane_bytes(const tracs_alignment *a, int planes)
 }
 
 namespace tracs {
-hipError_t pack_alloc(tracs_alignment *a, size_t bytes, void **out)
+bool pack_alloc(tracs_alignment *a, size_t bytes, void **out)
 {
     const size_t need = (bytes + 255) / 256 * 256;
     if (a->arena && a->arena_used + need <= a->arena_bytes) {
         *out = a->arena + a->arena_used;
         a->arena_used += need;
-        return hipSuccess;
+        return true;
     }
     // a block the previous pack released, if one is large enough (the smallest such; not one more than twice the size)
     size_t best = a->pack_spare.size();
@@ -642,27 +642,26 @@ hipError_t pack_alloc(tracs_alignment *a, size_t bytes, void **out)
         *out = a->pack_spare[best].p;
         a->pack_extra.push_back(a->pack_spare[best]);
         a->pack_spare.erase(a->pack_spare.begin() + (long)best);
-        return hipSuccess;
+        return true;
     }
-    hipError_t e = hipMalloc(out, need);
-    if (e != hipSuccess && !a->pack_spare.empty()) {
+    bool got = device_try_alloc(need, out);
+    if (!got && !a->pack_spare.empty()) {
         // out of memory with blocks parked from the previous pack: give those back and try once more
-        (void)hipGetLastError();
-        for (auto &b : a->pack_spare) (void)hipFree(b.p);
+        for (auto &b : a->pack_spare) device_free(b.p);
         a->pack_spare.clear();
-        e = hipMalloc(out, need);
+        got = device_try_alloc(need, out);
     }
-    if (e == hipSuccess) a->pack_extra.push_back({*out, need});
-    else { *out = nullptr; a->pack_oom = true; }
-    return e;
+    if (got) a->pack_extra.push_back({*out, need});
+    else a->pack_oom = true;
+    return got;
 }
 void pack_release(tracs_alignment *a)
 {
     // (the spare blocks nobody took this time are freed: a handle keeps what its last pack needed beside the arena, not more --
     // and nothing at all after an allocation failed: what follows an out-of-memory soft fail needs the memory itself)
-    for (auto &b : a->pack_spare) (void)hipFree(b.p);
+    for (auto &b : a->pack_spare) device_free(b.p);
     a->pack_spare.clear();
-    if (a->pack_oom) { for (auto &b : a->pack_extra) (void)hipFree(b.p); a->pack_oom = false; }
+    if (a->pack_oom) { for (auto &b : a->pack_extra) device_free(b.p); a->pack_oom = false; }
     else a->pack_spare = std::move(a->pack_extra);
     a->pack_extra.clear();
     a->arena_used = 0;
@@ -682,18 +681,16 @@ int tracs_alignment_create(size_t n, size_t L, tracs_alignment **out)
     a->n = n; a->L = L; a->n_pad = pad_samples(n); a->groups = groups_for(L);
     const size_t bytes = tracs_alignment_bytes(a);
     if (bytes) {
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&a->planes), bytes);
-        if (e != hipSuccess) { set_error(std::string("hipMalloc(planes): ") + hipGetErrorString(e)); delete a; return TRACS_E_NOMEM; }
-        e = hipMemset(a->planes, 0, bytes);
-        if (e != hipSuccess) { set_error(std::string("hipMemset(planes): ") + hipGetErrorString(e)); (void)hipFree(a->planes); delete a; return TRACS_E_HIP; }
+        if (const int rc = device_alloc(bytes, "planes", reinterpret_cast<void **>(&a->planes))) { delete a; return rc; }
+        const hipError_t e = hipMemset(a->planes, 0, bytes);
+        if (e != hipSuccess) { set_error(std::string("hipMemset(planes): ") + hipGetErrorString(e)); device_free(a->planes); delete a; return TRACS_E_HIP; }
         // the arena of the once-per-pack structures: 30 % of the planes + up to 128 MiB covers the lists of alignments with N lists of
         // up to ~190 samples at every site of 10 000 samples -- as far as the cost model takes lists (TRACS_PACK_ARENA=<fraction>
         // overrides; 0: none).  Not getting it is not an error; what does not fit is allocated on its own.
         static const double frac = [] { const char *v = std::getenv("TRACS_PACK_ARENA"); return v ? std::atof(v) : 0.30; }();
         if (frac > 0.0 && n >= 2) {
             const size_t want = (size_t)((double)bytes * frac) + std::min<size_t>(128u << 20, 2 * bytes + (1u << 20));
-            if (hipMalloc(reinterpret_cast<void **>(&a->arena), want) == hipSuccess) a->arena_bytes = want;
-            else { a->arena = nullptr; (void)hipGetLastError(); }
+            if (device_try_alloc(want, reinterpret_cast<void **>(&a->arena))) a->arena_bytes = want;
         }
     }
     *out = a;
@@ -706,14 +703,13 @@ void tracs_alignment_free(tracs_alignment *a)
     general_sparse_free(a);
     site_classes_free(a);
     filter_index_free(a);
-    for (auto &b : a->pack_spare) (void)hipFree(b.p);
+    for (auto &b : a->pack_spare) device_free(b.p);
     a->pack_spare.clear();
-    if (a->arena) (void)hipFree(a->arena);
-    if (a->planes) (void)hipFree(a->planes);
-    if (a->cplanes) (void)hipFree(a->cplanes);
-    if (a->d_flag) (void)hipFree(a->d_flag);
-    for (auto &c : a->tile_cache)
-        if (c.d) (void)hipFree(c.d);
+    device_free(a->arena);
+    device_free(a->planes);
+    device_free(a->cplanes);
+    device_free(a->d_flag);
+    for (auto &c : a->tile_cache) device_free(c.d);
     delete a;
 }
 
@@ -763,12 +759,11 @@ int tracs_alignment_pack(tracs_alignment *a, const uint8_t *ascii, size_t first,
     a->dirty = true;                   // the consensus form / sparse lists (if any) must be re-derived
     a->flt_stale = true;
     const uint8_t *d_ascii = ascii;
-    uint8_t *tmp = nullptr;
+    DeviceArray<uint8_t> tmp;
     if (!ascii_on_device) {
-        TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&tmp), count * a->L));
-        hipError_t e = hipMemcpyAsync(tmp, ascii, count * a->L, hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) { (void)hipFree(tmp); set_error(std::string("H2D ascii: ") + hipGetErrorString(e)); return TRACS_E_HIP; }
-        d_ascii = tmp;
+        if (const int rc = tmp.alloc(count * a->L, "ascii staging")) return rc;
+        TRACS_HIP_CHECK(hipMemcpyAsync(tmp.get(), ascii, count * a->L, hipMemcpyHostToDevice, stream));
+        d_ascii = tmp.get();
     }
     // samples go over grid.y in slices of 65535 x 64; `ascii`/`first` are advanced per slice
     const size_t slice = 65535ull * 64ull;
@@ -779,10 +774,7 @@ int tracs_alignment_pack(tracs_alignment *a, const uint8_t *ascii, size_t first,
                            a->groups);
     }
     TRACS_HIP_CHECK(hipGetLastError());
-    if (tmp) {
-        TRACS_HIP_CHECK(hipStreamSynchronize(stream));
-        TRACS_HIP_CHECK(hipFree(tmp));
-    }
+    if (tmp.get()) TRACS_HIP_CHECK(hipStreamSynchronize(stream));        // the staging buffer is read until here
     return TRACS_OK;
 }
 
@@ -931,16 +923,15 @@ static int decide_pack(tracs_alignment *a, hipStream_t stream, bool mfma_off)
     const bool force_general = dense_switch::force_general();
     if (a->classes_state == 1) {
         a->enc = a->classes_cons ? 1 : 0;
-        if (a->cplanes) { TRACS_HIP_CHECK(hipFree(a->cplanes)); a->cplanes = nullptr; }
+        device_free(a->cplanes); a->cplanes = nullptr;
     } else if (!force_general && partial != 1) {
         const size_t cbytes = plane_bytes(a, 3);
         if (!a->cplanes) {
             // no room for the second copy (very large alignments): stay on the general encoding
-            if (hipMalloc(reinterpret_cast<void **>(&a->cplanes), cbytes) == hipSuccess) TRACS_HIP_CHECK(hipMemsetAsync(a->cplanes, 0, cbytes, stream));
-            else { a->cplanes = nullptr; (void)hipGetLastError(); }
+            if (device_try_alloc(cbytes, reinterpret_cast<void **>(&a->cplanes))) TRACS_HIP_CHECK(hipMemsetAsync(a->cplanes, 0, cbytes, stream));
         }
         if (a->cplanes) {
-            if (!a->d_flag) TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&a->d_flag), 64));
+            if (const int rc = a->d_flag ? TRACS_OK : device_alloc(64, "partial-code flag", reinterpret_cast<void **>(&a->d_flag))) return rc;
             TRACS_HIP_CHECK(hipMemsetAsync(a->d_flag, 0, 4, stream));
             hipLaunchKernelGGL(derive_consensus_kernel, dim3(256 * 16), dim3(256), 0, stream, a->planes, a->cplanes, a->n_pad,
                                a->groups, a->d_flag);
@@ -948,10 +939,10 @@ static int decide_pack(tracs_alignment *a, hipStream_t stream, bool mfma_off)
             TRACS_HIP_CHECK(hipMemcpyAsync(&flag, a->d_flag, 4, hipMemcpyDeviceToHost, stream));
             TRACS_HIP_CHECK(hipStreamSynchronize(stream));
             if (flag == 0) a->enc = 1;
-            else { TRACS_HIP_CHECK(hipFree(a->cplanes)); a->cplanes = nullptr; }
+            else { device_free(a->cplanes); a->cplanes = nullptr; }
         }
         pack_stage_mark("consensus planes", stream);
-    } else if (a->cplanes) { TRACS_HIP_CHECK(hipFree(a->cplanes)); a->cplanes = nullptr; }
+    } else { device_free(a->cplanes); a->cplanes = nullptr; }
     a->dirty = false;                                                      // only on success: a failed decision is made again
     return TRACS_OK;
 }
@@ -1075,9 +1066,10 @@ struct DenseCall {
         std::vector<int2> tl;
         build_tiles(a->n, row_begin, row_end, col_begin, ti, tj, tl);
         if (tl.size() > c.cap) {
-            if (c.d) TRACS_HIP_CHECK(hipFree(c.d));
-            c.d = nullptr; c.cap = tl.size() * 2 + 64;
-            TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&c.d), c.cap * sizeof(int2)));
+            device_free(c.d);
+            c.d = nullptr; c.cap = 0;
+            if (const int rc = device_alloc((tl.size() * 2 + 64) * sizeof(int2), "tile schedule", reinterpret_cast<void **>(&c.d))) return rc;
+            c.cap = tl.size() * 2 + 64;
         }
         if (!tl.empty()) {
             TRACS_HIP_CHECK(hipMemcpyAsync(c.d, tl.data(), tl.size() * sizeof(int2), hipMemcpyHostToDevice, stream));

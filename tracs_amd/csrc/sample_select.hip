@@ -113,14 +113,11 @@ static void launch_select_samples(const tracs_alignment *src, const unsigned *id
 }
 
 // the file rules' bitmap as the kernels read it: four 32-site words per group, zero behind the last column
-static int upload_keep_words(const tracs_alignment *a, const uint64_t *keep, uint4 **out, hipStream_t stream)
+static int upload_keep_words(const tracs_alignment *a, const uint64_t *keep, DeviceArray<uint4> &out, hipStream_t stream)
 {
-    *out = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(out), a->groups * 16);
-    if (e != hipSuccess) { (void)hipGetLastError(); *out = nullptr; set_error(std::string("hipMalloc(sample rule bitmap): ") + hipGetErrorString(e)); return TRACS_E_NOMEM; }
-    e = hipMemsetAsync(*out, 0, a->groups * 16, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(*out, keep, (a->L + 63) / 64 * 8, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) { (void)hipFree(*out); *out = nullptr; set_error(std::string("sample rule bitmap upload: ") + hipGetErrorString(e)); return TRACS_E_HIP; }
+    if (const int rc = out.alloc(a->groups, "sample rule bitmap")) return rc;
+    TRACS_HIP_CHECK(hipMemsetAsync(out.get(), 0, a->groups * 16, stream));
+    TRACS_HIP_CHECK(hipMemcpyAsync(out.get(), keep, (a->L + 63) / 64 * 8, hipMemcpyHostToDevice, stream));
     return TRACS_OK;
 }
 
@@ -136,18 +133,14 @@ int sample_n_counts(const tracs_alignment *a, const uint64_t *keep, size_t keep_
     DeviceCall guard(stream);
     TRACS_HIP_CHECK(hipMemsetAsync(counts, 0, a->n * 4, stream));
     if (!a->L) return TRACS_OK;
-    uint4 *keepw = nullptr;
+    DeviceArray<uint4> keepw;
     if (keep) {
-        const int rc = upload_keep_words(a, keep, &keepw, stream);
+        const int rc = upload_keep_words(a, keep, keepw, stream);
         if (rc) return rc;
     }
-    launch_sample_counts(a, keepw, counts, stream);
-    hipError_t e = hipGetLastError();
-    if (keepw) {                                                         // (the bitmap is this call's own: it goes once the kernel has read it)
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(keepw);
-    }
-    if (e != hipSuccess) { set_error(std::string("sample_n_count_kernel: ") + hipGetErrorString(e)); return TRACS_E_HIP; }
+    launch_sample_counts(a, keepw.get(), counts, stream);
+    TRACS_HIP_CHECK(hipGetLastError());
+    if (keep) TRACS_HIP_CHECK(hipStreamSynchronize(stream));           // (the bitmap is this call's own: it goes once the kernel has read it)
     return TRACS_OK;
 }
 
@@ -163,28 +156,25 @@ int select_samples(tracs_alignment *src, const uint8_t *keep_sample, tracs_align
         if (keep_sample[s]) idx.push_back((unsigned)s);
     if (idx.empty()) { set_error("no sample left after the sample rule"); return TRACS_E_ARG; }
     DeviceCall guard(stream);
-    unsigned *d_idx = nullptr;
-    tracs_alignment *dst = nullptr;
-    auto fail = [&](int r) { (void)hipStreamSynchronize(stream); if (d_idx) (void)hipFree(d_idx); if (dst) tracs_alignment_free(dst); return r; };
-#define SS_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { set_error(std::string(#x ": ") + hipGetErrorString(e__)); return fail(TRACS_E_HIP); } } while (0)
     if (release_src_arena && src->arena && src->arena_used == 0 && src->pack_extra.empty()) {
-        SS_CHECK(hipFree(src->arena));
+        device_free(src->arena);
         src->arena = nullptr;
         src->arena_bytes = 0;
     }
-    int rc = tracs_alignment_create(idx.size(), src->L, &dst);
-    if (rc) return fail(rc);
+    tracs_alignment *made = nullptr;
+    int rc = tracs_alignment_create(idx.size(), src->L, &made);
+    if (rc) return rc;
+    AlignmentOwner dst(made);
     if (src->L) {
-        SS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_idx), idx.size() * 4));
-        SS_CHECK(hipMemcpyAsync(d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, stream));
-        SS_CHECK(hipStreamSynchronize(nullptr));           // the new planes are cleared on the null stream
-        launch_select_samples(src, d_idx, dst, stream);
-        SS_CHECK(hipGetLastError());
-        SS_CHECK(hipStreamSynchronize(stream));
-        (void)hipFree(d_idx);
+        DeviceArray<unsigned> d_idx;
+        if ((rc = d_idx.alloc(idx.size(), "kept samples"))) return rc;
+        TRACS_HIP_CHECK(hipMemcpyAsync(d_idx.get(), idx.data(), idx.size() * 4, hipMemcpyHostToDevice, stream));
+        TRACS_HIP_CHECK(hipStreamSynchronize(nullptr));           // the new planes are cleared on the null stream
+        launch_select_samples(src, d_idx.get(), dst.get(), stream);
+        TRACS_HIP_CHECK(hipGetLastError());
+        TRACS_HIP_CHECK(hipStreamSynchronize(stream));
     }
-#undef SS_CHECK
-    *out = dst;
+    *out = dst.release();
     return TRACS_OK;
 }
 
@@ -242,42 +232,31 @@ int tracs_debug_sample_select_timing(const tracs_alignment *src, const uint64_t 
     if (idx.empty()) { set_error("no sample left after the sample rule"); return TRACS_E_ARG; }
     hipStream_t stream = nullptr;
     DeviceCall guard(stream);
-    unsigned *d_idx = nullptr, *d_counts = nullptr;
-    uint4 *keepw = nullptr;
-    tracs_alignment *dst = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    auto done = [&](int r) {
-        (void)hipDeviceSynchronize();
-        void *q[] = {d_idx, d_counts, keepw};
-        for (void *x : q) if (x) (void)hipFree(x);
-        if (dst) tracs_alignment_free(dst);
-        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-        return r;
-    };
-#define SS_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { set_error(std::string(#x ": ") + hipGetErrorString(e__)); return done(TRACS_E_HIP); } } while (0)
-    for (auto &e : ev) SS_CHECK(hipEventCreate(&e));
-    int rc = TRACS_OK;
-    if (keep && (rc = upload_keep_words(src, keep, &keepw, stream))) return done(rc);
-    SS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_counts), src->n * 4));
-    SS_CHECK(hipMalloc(reinterpret_cast<void **>(&d_idx), idx.size() * 4));
-    SS_CHECK(hipMemcpy(d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
-    if ((rc = tracs_alignment_create(idx.size(), src->L, &dst))) return done(rc);
-    SS_CHECK(hipDeviceSynchronize());
+    OwnedEvents<3> ev;
+    DeviceArray<unsigned> d_idx, d_counts;
+    DeviceArray<uint4> keepw;
+    int rc = ev.create();
+    if (rc || (keep && (rc = upload_keep_words(src, keep, keepw, stream)))) return rc;
+    if ((rc = d_counts.alloc(src->n, "sample counts")) || (rc = d_idx.alloc(idx.size(), "kept samples"))) return rc;
+    TRACS_HIP_CHECK(hipMemcpy(d_idx.get(), idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+    tracs_alignment *made = nullptr;
+    if ((rc = tracs_alignment_create(idx.size(), src->L, &made))) return rc;
+    AlignmentOwner dst(made);
+    TRACS_HIP_CHECK(hipDeviceSynchronize());
     for (int r = -1; r < repeats; r++) {                    // r = -1: warm-up
-        SS_CHECK(hipMemsetAsync(d_counts, 0, src->n * 4, stream));
-        SS_CHECK(hipEventRecord(ev[0], stream));
-        launch_sample_counts(src, keepw, d_counts, stream);
-        SS_CHECK(hipEventRecord(ev[1], stream));
-        launch_select_samples(src, d_idx, dst, stream);
-        SS_CHECK(hipEventRecord(ev[2], stream));
-        SS_CHECK(hipGetLastError());
-        SS_CHECK(hipEventSynchronize(ev[2]));
+        TRACS_HIP_CHECK(hipMemsetAsync(d_counts.get(), 0, src->n * 4, stream));
+        TRACS_HIP_CHECK(hipEventRecord(ev[0], stream));
+        launch_sample_counts(src, keepw.get(), d_counts.get(), stream);
+        TRACS_HIP_CHECK(hipEventRecord(ev[1], stream));
+        launch_select_samples(src, d_idx.get(), dst.get(), stream);
+        TRACS_HIP_CHECK(hipEventRecord(ev[2], stream));
+        TRACS_HIP_CHECK(hipGetLastError());
+        TRACS_HIP_CHECK(hipEventSynchronize(ev[2]));
         if (r >= 0)
-            for (int k = 0; k < 2; k++) SS_CHECK(hipEventElapsedTime(&ms[r * 2 + k], ev[k], ev[k + 1]));
+            for (int k = 0; k < 2; k++) TRACS_HIP_CHECK(hipEventElapsedTime(&ms[r * 2 + k], ev[k], ev[k + 1]));
     }
-#undef SS_CHECK
     if (n_kept) *n_kept = idx.size();
-    return done(TRACS_OK);
+    return TRACS_OK;
 }
 
 }  // extern "C"

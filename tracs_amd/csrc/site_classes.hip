@@ -808,9 +808,9 @@ static int decide(tracs_alignment *a, bool allow_minor, bool allow_nnl, hipStrea
     const size_t vbytes = class_plane_bytes(a, gv, npv, PAD_GROUPS), ibytes = class_plane_bytes(a, gi, 1, PAD_GROUPS);
     unsigned *lists = nullptr;
     if ((rc = workspace_get(WS_SC_LISTS, L_dense + L_count + 1, &lists))) return rc;
-    if (pack_alloc(a, vbytes, reinterpret_cast<void **>(&a->vplanes)) != hipSuccess) return soft_fail();
-    if (gi && pack_alloc(a, ibytes, reinterpret_cast<void **>(&a->iplanes)) != hipSuccess) return soft_fail();
-    if (pack_alloc(a, a->n_pad * sizeof(unsigned), reinterpret_cast<void **>(&a->c_counted)) != hipSuccess) return soft_fail();
+    if (!pack_alloc(a, vbytes, reinterpret_cast<void **>(&a->vplanes))) return soft_fail();
+    if (gi && !pack_alloc(a, ibytes, reinterpret_cast<void **>(&a->iplanes))) return soft_fail();
+    if (!pack_alloc(a, a->n_pad * sizeof(unsigned), reinterpret_cast<void **>(&a->c_counted))) return soft_fail();
     unsigned *list_dense = lists, *list_count = lists + L_dense;
     bool ok = hipMemsetAsync(a->vplanes, 0, vbytes, stream) == hipSuccess &&
               (!gi || hipMemsetAsync(a->iplanes, 0, ibytes, stream) == hipSuccess) &&
@@ -877,7 +877,7 @@ static int decide(tracs_alignment *a, bool allow_minor, bool allow_nnl, hipStrea
     const bool gram_on = gram && L_minor > 0 && a->lists != nullptr;
     if (gram_on && !gram_rows) {
         const size_t ubytes = class_plane_bytes(a, groups, 1, PAD_GROUPS);
-        if (pack_alloc(a, ubytes, reinterpret_cast<void **>(&a->uplane)) != hipSuccess) { soft_fail(); return refuse_gram(); }
+        if (!pack_alloc(a, ubytes, reinterpret_cast<void **>(&a->uplane))) { soft_fail(); return refuse_gram(); }
         // (the pad groups and the slack behind them: zero)
         ok = ok && hipMemsetAsync(a->uplane + groups * a->n_pad, 0, ubytes - groups * a->n_pad * sizeof(uint4), stream) == hipSuccess;
         if (a->n_pad > a->n) ok = ok && hipMemsetAsync(a->uplane, 0, groups * a->n_pad * sizeof(uint4), stream) == hipSuccess;

@@ -1397,32 +1397,32 @@ int minority_lists_build(tracs_alignment *a, const MinorBuild &mb_, hipStream_t 
     if (L == 0 || L >= (1ull << 26) || n >= (1ull << 27)) return TRACS_OK;           // entries hold rank << 5 (+ a flag bit) / sample << 5
     auto *g = new SiteLists();
     auto fail_soft = [&]() { (void)hipGetLastError(); pack_stage_count_gone(&g->slot_lines); delete g; return TRACS_OK; };
-#define SL_TRY(x) do { if ((x) != hipSuccess) return fail_soft(); } while (0)
+    const auto failed = [](hipError_t e) { return e != hipSuccess; };
     g->sites = L; g->groups = groups; g->tot_p = mb.tot_p; g->tot_nnl = mb.tot_nnl;
     g->n_rows = mb.n_rows;
     for (int k = 0; k < 4; k++) g->rows[k] = mb.rows[k];
     g->n_lines = mb.gram ? 0ull : (unsigned long long)L + mb.tot_o;      // (gram: no site carries an N list)
     g->tgroups = (groups + 15) / 16 * 16;
-    SL_TRY(pack_alloc(a, (g->n_lines + 1) * 128, reinterpret_cast<void **>(&g->lines)));
-    SL_TRY(pack_alloc(a, (L + 1) * 8, reinterpret_cast<void **>(&g->p_off)));
-    SL_TRY(pack_alloc(a, std::max<size_t>(mb.tot_p, 1) * 4, reinterpret_cast<void **>(&g->p_ent)));
+    if (!pack_alloc(a, (g->n_lines + 1) * 128, reinterpret_cast<void **>(&g->lines))) return fail_soft();
+    if (!pack_alloc(a, (L + 1) * 8, reinterpret_cast<void **>(&g->p_off))) return fail_soft();
+    if (!pack_alloc(a, std::max<size_t>(mb.tot_p, 1) * 4, reinterpret_cast<void **>(&g->p_ent))) return fail_soft();
     g->n_qlines = mb.long_p ? (unsigned long long)L + mb.tot_q : 0ull;
     g->qw = mb.qw;
-    SL_TRY(pack_alloc(a, (g->n_qlines + 1) * (size_t)g->qw * 4, reinterpret_cast<void **>(&g->qlines)));
-    SL_TRY(pack_alloc(a, (n + 1) * 8, reinterpret_cast<void **>(&g->s_off)));
-    SL_TRY(pack_alloc(a, std::max<size_t>(mb.tot_p, 1) * 4, reinterpret_cast<void **>(&g->s_ent)));
-    SL_TRY(pack_alloc(a, std::max<size_t>(n, 1) * 4, reinterpret_cast<void **>(&g->c_p)));
-    SL_TRY(pack_alloc(a, groups * sizeof(uint4), reinterpret_cast<void **>(&g->lst_mask)));
-    SL_TRY(pack_alloc(a, groups * sizeof(unsigned), reinterpret_cast<void **>(&g->off_lst)));
+    if (!pack_alloc(a, (g->n_qlines + 1) * (size_t)g->qw * 4, reinterpret_cast<void **>(&g->qlines))) return fail_soft();
+    if (!pack_alloc(a, (n + 1) * 8, reinterpret_cast<void **>(&g->s_off))) return fail_soft();
+    if (!pack_alloc(a, std::max<size_t>(mb.tot_p, 1) * 4, reinterpret_cast<void **>(&g->s_ent))) return fail_soft();
+    if (!pack_alloc(a, std::max<size_t>(n, 1) * 4, reinterpret_cast<void **>(&g->c_p))) return fail_soft();
+    if (!pack_alloc(a, groups * sizeof(uint4), reinterpret_cast<void **>(&g->lst_mask))) return fail_soft();
+    if (!pack_alloc(a, groups * sizeof(unsigned), reinterpret_cast<void **>(&g->off_lst))) return fail_soft();
     const bool bitmaps = mb.tot_nnl > 0;
     // the rows' N sites: slots where a slot holds few entries on average, else bitmaps (TRACS_ROW_LISTS=0|1 forces the choice: A/B runs, tests)
     static const int env_slots = [] { const char *e = getenv("TRACS_ROW_LISTS"); return e ? atoi(e) : -1; }();
     g->batches = (g->tgroups + SLOT_GROUPS - 1) / SLOT_GROUPS;
     const bool row_slots = bitmaps && (env_slots >= 0 ? env_slots != 0 : (double)mb.tot_nnl <= SLOT_MEAN_MAX * (double)n * (double)g->batches);
     if (row_slots) {
-        SL_TRY(pack_alloc(a, n * g->batches * SLOT_BYTES, reinterpret_cast<void **>(&g->slots)));
-        SL_TRY(pack_alloc(a, groups * sizeof(uint4), reinterpret_cast<void **>(&g->nnl_mask)));
-    } else if (bitmaps) SL_TRY(pack_alloc(a, n * g->tgroups * sizeof(uint4), reinterpret_cast<void **>(&g->T)));
+        if (!pack_alloc(a, n * g->batches * SLOT_BYTES, reinterpret_cast<void **>(&g->slots))) return fail_soft();
+        if (!pack_alloc(a, groups * sizeof(uint4), reinterpret_cast<void **>(&g->nnl_mask))) return fail_soft();
+    } else if (bitmaps) if (!pack_alloc(a, n * g->tgroups * sizeof(uint4), reinterpret_cast<void **>(&g->T))) return fail_soft();
     unsigned *cnt = nullptr, *e_cnt = nullptr;
     uint2 *E = nullptr, *tmp = nullptr;
     int rc;
@@ -1437,11 +1437,11 @@ int minority_lists_build(tracs_alignment *a, const MinorBuild &mb_, hipStream_t 
     while (n && ((n - 1) >> shift) >= 256u) shift++;                                  // at most 256 buckets of 2^shift samples
     const bool two_pass = mb.tot_p >= ENT_TILE && mb.tot_p < (1ull << 32) && shift <= 10 &&      // (32-bit run cursors; at most 1 024 samples per bucket)
                           workspace_try(WS_SL_ENTRIES_TMP, (size_t)mb.tot_p, &tmp);       // (optional: without it the fill is the one-pass one)
-    SL_TRY(hipMemsetAsync(cnt, 0, (2 * std::max<size_t>(n, 1) + 8 + 256) * 4, stream));
-    SL_TRY(hipMemsetAsync(g->c_p, 0, std::max<size_t>(n, 1) * 4, stream));
-    SL_TRY(hipMemcpyAsync(g->lst_mask, mb.lst_mask, groups * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
-    SL_TRY(hipMemcpyAsync(g->off_lst, mb.off_lst, groups * sizeof(unsigned), hipMemcpyDeviceToDevice, stream));
-    if (row_slots) SL_TRY(hipMemcpyAsync(g->nnl_mask, mb.nnl_mask, groups * sizeof(uint4), hipMemcpyDeviceToDevice, stream));
+    if (failed(hipMemsetAsync(cnt, 0, (2 * std::max<size_t>(n, 1) + 8 + 256) * 4, stream))) return fail_soft();
+    if (failed(hipMemsetAsync(g->c_p, 0, std::max<size_t>(n, 1) * 4, stream))) return fail_soft();
+    if (failed(hipMemcpyAsync(g->lst_mask, mb.lst_mask, groups * sizeof(uint4), hipMemcpyDeviceToDevice, stream))) return fail_soft();
+    if (failed(hipMemcpyAsync(g->off_lst, mb.off_lst, groups * sizeof(unsigned), hipMemcpyDeviceToDevice, stream))) return fail_soft();
+    if (row_slots) if (failed(hipMemcpyAsync(g->nnl_mask, mb.nnl_mask, groups * sizeof(uint4), hipMemcpyDeviceToDevice, stream))) return fail_soft();
     const double plane_b = (double)groups * (double)a->n_pad * sizeof(uint4);      // the N plane
 #ifndef TRACS_SITE_PIECE
 #define TRACS_SITE_PIECE 512
@@ -1483,7 +1483,7 @@ int minority_lists_build(tracs_alignment *a, const MinorBuild &mb_, hipStream_t 
         pack_stage_mark("N slots of the rows", stream, plane_b, 0.0);
         pack_stage_written_later(&g->slot_lines, 128.0);
         static_assert(offsetof(SiteLists, slot_lines) == offsetof(SiteLists, max_row) + 8, "max_row and slot_lines come back in one copy");
-        SL_TRY(hipMemcpyAsync(&g->max_row, d_max, 16, hipMemcpyDeviceToHost, stream));       // (read after the caller's synchronisation)
+        if (failed(hipMemcpyAsync(&g->max_row, d_max, 16, hipMemcpyDeviceToHost, stream))) return fail_soft();       // (read after the caller's synchronisation)
     } else if (bitmaps) {
         // (a->c_counted was zeroed by the caller: this kernel is what fills it when the rows' bitmaps are built)
         const size_t octs = g->tgroups / NB_GW;
@@ -1495,19 +1495,18 @@ int minority_lists_build(tracs_alignment *a, const MinorBuild &mb_, hipStream_t 
         double rows = (double)n;
         if (mb.n_rows) { rows = 0.0; for (int k = 0; k < mb.n_rows; k++) rows += (double)(std::min<size_t>(mb.rows[2 * k + 1], n) - std::min<size_t>(mb.rows[2 * k], n)); }
         pack_stage_mark("N bitmaps of the rows", stream, plane_b, rows * (double)g->tgroups * sizeof(uint4));
-        SL_TRY(hipMemcpyAsync(&g->max_row, d_max, 4, hipMemcpyDeviceToHost, stream));       // (read after the caller's synchronisation)
+        if (failed(hipMemcpyAsync(&g->max_row, d_max, 4, hipMemcpyDeviceToHost, stream))) return fail_soft();       // (read after the caller's synchronisation)
     }
     if (mb.gram == 2) {
         // nw_rows: the N plane site-major, and the site of every rank (class_list_kernel's job, here over the mask of the sites with lists)
         g->ns_words = ns_words_for(a->n_pad);
-        SL_TRY(pack_alloc(a, groups * 128 * g->ns_words * 4, reinterpret_cast<void **>(&g->ns)));
-        SL_TRY(pack_alloc(a, std::max<size_t>(L, 1) * 4, reinterpret_cast<void **>(&g->site_of)));
+        if (!pack_alloc(a, groups * 128 * g->ns_words * 4, reinterpret_cast<void **>(&g->ns))) return fail_soft();
+        if (!pack_alloc(a, std::max<size_t>(L, 1) * 4, reinterpret_cast<void **>(&g->site_of))) return fail_soft();
         launch_ns_build(a->planes, a->n_pad, (unsigned)groups, g->ns, g->ns_words, stream);
         hipLaunchKernelGGL(site_of_rank_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, stream, g->lst_mask, g->off_lst, groups, g->site_of);
         pack_stage_mark("N plane site-major (NS)", stream, plane_b, (double)groups * 128.0 * (double)g->ns_words * 4.0);
     }
-    SL_TRY(hipGetLastError());
-#undef SL_TRY
+    if (failed(hipGetLastError())) return fail_soft();
     a->lists = g;
     *ok = 1;
     return TRACS_OK;
@@ -1653,8 +1652,9 @@ size_t tracs_debug_lists(const tracs_alignment *a, int what, void *out, size_t c
         // rows in slots: expanded to the bitmap they stand for (rows outside the handle's ranges: zero)
         bytes = a->n * g->tgroups * 16;
         if (bytes == 0 || bytes > cap) return 0;
-        uint4 *tmp = nullptr;
-        if (hipDeviceSynchronize() != hipSuccess || hipMalloc(reinterpret_cast<void **>(&tmp), bytes) != hipSuccess) { (void)hipGetLastError(); return 0; }
+        DeviceArray<uint4> tmp_buf;
+        if (hipDeviceSynchronize() != hipSuccess || !tmp_buf.try_alloc(bytes / 16)) { (void)hipGetLastError(); return 0; }
+        uint4 *const tmp = tmp_buf.get();
         bool ok = true;
         for (size_t s0 = 0; s0 < a->n && ok; ) {
             // (runs of rows that are all wanted or all not: at most five)
@@ -1668,7 +1668,6 @@ size_t tracs_debug_lists(const tracs_alignment *a, int what, void *out, size_t c
             s0 = s1;
         }
         ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, tmp, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-        (void)hipFree(tmp);
         return ok ? bytes : 0;
     }
     case 9: src = g->c_p; bytes = a->n * 4; break;

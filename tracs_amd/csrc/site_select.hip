@@ -300,7 +300,7 @@ void launch_compact_general(const uint4 *src, const unsigned *list, unsigned cou
 
 // the temporaries of one selection, one device block: [N counts] [caller's bitmap] final bitmap, word offsets, the total, the list
 struct Selection {
-    uint8_t *tmp = nullptr;
+    DeviceArray<uint8_t> tmp;
     unsigned *counts = nullptr, *keep_in = nullptr, *keepw = nullptr, *woff = nullptr, *list = nullptr;
     unsigned long long *total_d = nullptr;
     size_t words = 0, words64 = 0;
@@ -316,9 +316,8 @@ static int selection_alloc(const tracs_alignment *src, bool has_keep, uint32_t m
     const bool n_rule = max_n != UINT32_MAX;
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t b_counts = n_rule ? up(L * 4) : 0, b_in = has_keep ? up(sel.words * 4) : 0, b_words = up(sel.words * 4), b_list = up(L * 4);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&sel.tmp), b_counts + b_in + 2 * b_words + 256 + b_list);
-    if (e != hipSuccess) { (void)hipGetLastError(); sel.tmp = nullptr; set_error(std::string("hipMalloc(site selection): ") + hipGetErrorString(e)); return TRACS_E_NOMEM; }
-    uint8_t *p = sel.tmp;
+    if (const int rc = sel.tmp.alloc(b_counts + b_in + 2 * b_words + 256 + b_list, "site selection")) return rc;
+    uint8_t *p = sel.tmp.get();
     if (n_rule) sel.counts = reinterpret_cast<unsigned *>(p);
     p += b_counts;
     if (has_keep) sel.keep_in = reinterpret_cast<unsigned *>(p);
@@ -385,33 +384,30 @@ int select_sites(tracs_alignment *src, const uint64_t *keep, size_t keep_len, ui
     DeviceCall guard(stream);
     Selection sel;
     if ((rc = selection_alloc(src, keep != nullptr, max_n_samples, sel))) return rc;
-    tracs_alignment *dst = nullptr;
-    auto fail = [&](int r) { (void)hipStreamSynchronize(stream); (void)hipFree(sel.tmp); if (dst) tracs_alignment_free(dst); return r; };
-#define SEL_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { set_error(std::string(#x ": ") + hipGetErrorString(e__)); return fail(TRACS_E_HIP); } } while (0)
-    SEL_CHECK(selection_upload(sel, keep, stream));
+    TRACS_HIP_CHECK(selection_upload(sel, keep, stream));
     if (sel.counts) launch_n_counts(src, sel.counts, stream);
     selection_bitmap(src, sel, stream);
-    SEL_CHECK(hipGetLastError());
+    TRACS_HIP_CHECK(hipGetLastError());
     unsigned long long total = 0;
-    SEL_CHECK(hipMemcpyAsync(&total, sel.total_d, 8, hipMemcpyDeviceToHost, stream));
-    SEL_CHECK(hipStreamSynchronize(stream));
-    if (total == 0) { set_error("no site left after the site rules"); return fail(TRACS_E_ARG); }
+    TRACS_HIP_CHECK(hipMemcpyAsync(&total, sel.total_d, 8, hipMemcpyDeviceToHost, stream));
+    TRACS_HIP_CHECK(hipStreamSynchronize(stream));
+    if (total == 0) { set_error("no site left after the site rules"); return TRACS_E_ARG; }
     selection_list(sel, stream);
     if (release_src_arena && src->arena && src->arena_used == 0 && src->pack_extra.empty()) {
-        SEL_CHECK(hipFree(src->arena));
+        device_free(src->arena);
         src->arena = nullptr;
         src->arena_bytes = 0;
     }
-    if ((rc = tracs_alignment_create(src->n, (size_t)total, &dst))) return fail(rc);
-    SEL_CHECK(hipStreamSynchronize(nullptr));              // the new planes are cleared on the null stream
-    selection_pack(src, sel, (unsigned)total, dst, stream);
-    SEL_CHECK(hipGetLastError());
-    if (kept) SEL_CHECK(hipMemcpyAsync(kept, sel.keepw, sel.words64 * 8, hipMemcpyDeviceToHost, stream));
-    SEL_CHECK(hipStreamSynchronize(stream));
-#undef SEL_CHECK
-    (void)hipFree(sel.tmp);
+    tracs_alignment *made = nullptr;
+    if ((rc = tracs_alignment_create(src->n, (size_t)total, &made))) return rc;
+    AlignmentOwner dst(made);
+    TRACS_HIP_CHECK(hipStreamSynchronize(nullptr));              // the new planes are cleared on the null stream
+    selection_pack(src, sel, (unsigned)total, dst.get(), stream);
+    TRACS_HIP_CHECK(hipGetLastError());
+    if (kept) TRACS_HIP_CHECK(hipMemcpyAsync(kept, sel.keepw, sel.words64 * 8, hipMemcpyDeviceToHost, stream));
+    TRACS_HIP_CHECK(hipStreamSynchronize(stream));
     if (n_kept) *n_kept = (size_t)total;
-    *out = dst;
+    *out = dst.release();
     return TRACS_OK;
 }
 
@@ -452,61 +448,53 @@ int tracs_debug_site_select_timing(const tracs_alignment *src, const uint64_t *k
     if (src->n_pad / 64 > 65535) { set_error("tracs_debug_site_select_timing: too many samples for the re-pack kernel"); return TRACS_E_ARG; }
     hipStream_t stream = nullptr;
     DeviceCall guard(stream);
+    OwnedEvents<5> ev;
     Selection sel;
-    if ((rc = selection_alloc(src, keep != nullptr, max_n_samples, sel))) return rc;
-    tracs_alignment *dst = nullptr, *dst_old = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    auto done = [&](int r) {
-        (void)hipDeviceSynchronize();
-        (void)hipFree(sel.tmp);
-        if (dst) tracs_alignment_free(dst);
-        if (dst_old) tracs_alignment_free(dst_old);
-        for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-        return r;
-    };
-#define SEL_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { set_error(std::string(#x ": ") + hipGetErrorString(e__)); return done(TRACS_E_HIP); } } while (0)
-    for (auto &e : ev) SEL_CHECK(hipEventCreate(&e));
-    SEL_CHECK(selection_upload(sel, keep, stream));
+    if ((rc = selection_alloc(src, keep != nullptr, max_n_samples, sel)) || (rc = ev.create())) return rc;
+    AlignmentOwner dst, dst_old;
+    TRACS_HIP_CHECK(selection_upload(sel, keep, stream));
     unsigned long long total = 0;
     for (int r = -1; r < repeats; r++) {                    // r = -1: warm-up, and the round that sizes the two output handles
-        SEL_CHECK(hipEventRecord(ev[0], stream));
+        TRACS_HIP_CHECK(hipEventRecord(ev[0], stream));
         if (sel.counts) launch_n_counts(src, sel.counts, stream);
-        SEL_CHECK(hipEventRecord(ev[1], stream));
+        TRACS_HIP_CHECK(hipEventRecord(ev[1], stream));
         selection_bitmap(src, sel, stream);
         selection_list(sel, stream);
-        SEL_CHECK(hipEventRecord(ev[2], stream));
+        TRACS_HIP_CHECK(hipEventRecord(ev[2], stream));
         if (r < 0) {
-            SEL_CHECK(hipMemcpy(&total, sel.total_d, 8, hipMemcpyDeviceToHost));
-            if (total == 0) { set_error("no site left after the site rules"); return done(TRACS_E_ARG); }
-            if ((rc = tracs_alignment_create(src->n, (size_t)total, &dst))) return done(rc);
-            if ((rc = tracs_alignment_create(src->n, (size_t)total, &dst_old))) return done(rc);
-            SEL_CHECK(hipDeviceSynchronize());
-            SEL_CHECK(hipEventRecord(ev[2], stream));
+            TRACS_HIP_CHECK(hipMemcpy(&total, sel.total_d, 8, hipMemcpyDeviceToHost));
+            if (total == 0) { set_error("no site left after the site rules"); return TRACS_E_ARG; }
+            for (AlignmentOwner *o : {&dst, &dst_old}) {
+                tracs_alignment *made = nullptr;
+                if ((rc = tracs_alignment_create(src->n, (size_t)total, &made))) return rc;
+                o->reset(made);
+            }
+            TRACS_HIP_CHECK(hipDeviceSynchronize());
+            TRACS_HIP_CHECK(hipEventRecord(ev[2], stream));
         }
-        selection_pack(src, sel, (unsigned)total, dst, stream);
-        SEL_CHECK(hipEventRecord(ev[3], stream));
+        selection_pack(src, sel, (unsigned)total, dst.get(), stream);
+        TRACS_HIP_CHECK(hipEventRecord(ev[3], stream));
         launch_compact_general(src->planes, sel.list, (unsigned)total, dst_old->planes, src->n_pad, (unsigned)src->n, (unsigned)dst_old->groups, stream);
-        SEL_CHECK(hipEventRecord(ev[4], stream));
-        SEL_CHECK(hipGetLastError());
-        SEL_CHECK(hipEventSynchronize(ev[4]));
+        TRACS_HIP_CHECK(hipEventRecord(ev[4], stream));
+        TRACS_HIP_CHECK(hipGetLastError());
+        TRACS_HIP_CHECK(hipEventSynchronize(ev[4]));
         if (r >= 0)
-            for (int k = 0; k < 4; k++) SEL_CHECK(hipEventElapsedTime(&ms[r * 4 + k], ev[k], ev[k + 1]));
+            for (int k = 0; k < 4; k++) TRACS_HIP_CHECK(hipEventElapsedTime(&ms[r * 4 + k], ev[k], ev[k + 1]));
     }
     if (same) {
         // both handles were cleared when they were created, so every byte either kernel left alone is zero in both
-        const size_t bytes = tracs_alignment_bytes(dst);
+        const size_t bytes = tracs_alignment_bytes(dst.get());
         std::vector<uint8_t> a(std::min<size_t>(bytes, 64u << 20)), b(a.size());
         *same = 1;
         for (size_t o = 0; o < bytes && *same; o += a.size()) {
             const size_t k = std::min(a.size(), bytes - o);
-            SEL_CHECK(hipMemcpy(a.data(), reinterpret_cast<const uint8_t *>(dst->planes) + o, k, hipMemcpyDeviceToHost));
-            SEL_CHECK(hipMemcpy(b.data(), reinterpret_cast<const uint8_t *>(dst_old->planes) + o, k, hipMemcpyDeviceToHost));
+            TRACS_HIP_CHECK(hipMemcpy(a.data(), reinterpret_cast<const uint8_t *>(dst->planes) + o, k, hipMemcpyDeviceToHost));
+            TRACS_HIP_CHECK(hipMemcpy(b.data(), reinterpret_cast<const uint8_t *>(dst_old->planes) + o, k, hipMemcpyDeviceToHost));
             if (std::memcmp(a.data(), b.data(), k) != 0) *same = 0;
         }
     }
-#undef SEL_CHECK
     if (n_kept) *n_kept = (size_t)total;
-    return done(TRACS_OK);
+    return TRACS_OK;
 }
 
 }  // extern "C"

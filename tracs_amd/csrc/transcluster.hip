@@ -1204,12 +1204,12 @@ static int get_lgamma_table(hipStream_t stream, const double **out)
     TRACS_HIP_CHECK(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) { set_error("device index out of range"); return TRACS_E_HIP; }
     if (!g_lg[dev]) {
-        double *p = nullptr;
-        TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&p), (LG_TABLE + 2 * LK_TABLE) * sizeof(double)));
-        hipLaunchKernelGGL(lgamma_table_kernel, dim3((LG_TABLE + 2 * LK_TABLE + 255) / 256), dim3(256), 0, stream, p, LG_TABLE);
+        DeviceArray<double> p;
+        if (const int rc = p.alloc(LG_TABLE + 2 * LK_TABLE, "lgamma table")) return rc;
+        hipLaunchKernelGGL(lgamma_table_kernel, dim3((LG_TABLE + 2 * LK_TABLE + 255) / 256), dim3(256), 0, stream, p.get(), LG_TABLE);
         TRACS_HIP_CHECK(hipGetLastError());
         TRACS_HIP_CHECK(hipStreamSynchronize(stream));
-        g_lg[dev] = p;
+        g_lg[dev] = p.detach();            // kept for the life of the process
     }
     *out = g_lg[dev];
     return TRACS_OK;
@@ -1790,21 +1790,15 @@ int tracs_trans_dist(const int32_t *snpdiff, const double *datediff, size_t n, d
 {
     if (n == 0) return TRACS_OK;
     if (!snpdiff || !datediff || !p0_log || !eK) { set_error("tracs_trans_dist: NULL argument"); return TRACS_E_ARG; }
-    int *dN = nullptr; double *dD = nullptr, *dP = nullptr, *dE = nullptr;
-    auto cleanup = [&]() { if (dN) (void)hipFree(dN); if (dD) (void)hipFree(dD); if (dP) (void)hipFree(dP); if (dE) (void)hipFree(dE); };
-#define TD_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
-    TD_CHECK(hipMalloc(reinterpret_cast<void **>(&dN), n * 4));
-    TD_CHECK(hipMalloc(reinterpret_cast<void **>(&dD), n * 8));
-    TD_CHECK(hipMalloc(reinterpret_cast<void **>(&dP), n * 8));
-    TD_CHECK(hipMalloc(reinterpret_cast<void **>(&dE), n * 8));
-    TD_CHECK(hipMemcpy(dN, snpdiff, n * 4, hipMemcpyHostToDevice));
-    TD_CHECK(hipMemcpy(dD, datediff, n * 8, hipMemcpyHostToDevice));
-    int rc = tracs_trans_dist_device(dN, dD, n, lamb, beta, threshold_Ek, 0, dP, dE, nullptr);
-    if (rc) { cleanup(); return rc; }
-    TD_CHECK(hipMemcpy(p0_log, dP, n * 8, hipMemcpyDeviceToHost));
-    TD_CHECK(hipMemcpy(eK, dE, n * 8, hipMemcpyDeviceToHost));
-#undef TD_CHECK
-    cleanup();
+    DeviceArray<int> dN;
+    DeviceArray<double> dD, dP, dE;
+    int rc;
+    if ((rc = dN.alloc(n, "snpdiff")) || (rc = dD.alloc(n, "datediff")) || (rc = dP.alloc(n, "p0_log")) || (rc = dE.alloc(n, "eK"))) return rc;
+    TRACS_HIP_CHECK(hipMemcpy(dN.get(), snpdiff, n * 4, hipMemcpyHostToDevice));
+    TRACS_HIP_CHECK(hipMemcpy(dD.get(), datediff, n * 8, hipMemcpyHostToDevice));
+    if ((rc = tracs_trans_dist_device(dN.get(), dD.get(), n, lamb, beta, threshold_Ek, 0, dP.get(), dE.get(), nullptr))) return rc;
+    TRACS_HIP_CHECK(hipMemcpy(p0_log, dP.get(), n * 8, hipMemcpyDeviceToHost));
+    TRACS_HIP_CHECK(hipMemcpy(eK, dE.get(), n * 8, hipMemcpyDeviceToHost));
     return TRACS_OK;
 }
 
@@ -1815,25 +1809,20 @@ int tracs_lprob_k_given_N(const uint64_t *N, const uint64_t *k, const double *de
     if (!N || !k || !delta || !lgamma_tab || !lprob || !lhs) { set_error("tracs_lprob_k_given_N: NULL argument"); return TRACS_E_ARG; }
     for (size_t i = 0; i < n; i++)
         if (N[i] + k[i] + 1 >= lgamma_len) { set_error("tracs_lprob_k_given_N: lgamma table shorter than N+k+2"); return TRACS_E_ARG; }
-    unsigned long long *dN = nullptr, *dK = nullptr; double *dD = nullptr, *dL = nullptr, *dO = nullptr, *dH = nullptr;
-    auto cleanup = [&]() { void *p[] = {dN, dK, dD, dL, dO, dH}; for (void *q : p) if (q) (void)hipFree(q); };
-#define LP_CHECK(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { cleanup(); set_error(std::string(#x ": ") + hipGetErrorString(e__)); return TRACS_E_HIP; } } while (0)
-    LP_CHECK(hipMalloc(reinterpret_cast<void **>(&dN), n * 8));
-    LP_CHECK(hipMalloc(reinterpret_cast<void **>(&dK), n * 8));
-    LP_CHECK(hipMalloc(reinterpret_cast<void **>(&dD), n * 8));
-    LP_CHECK(hipMalloc(reinterpret_cast<void **>(&dL), lgamma_len * 8));
-    LP_CHECK(hipMalloc(reinterpret_cast<void **>(&dO), n * 8));
-    LP_CHECK(hipMalloc(reinterpret_cast<void **>(&dH), n * 8));
-    LP_CHECK(hipMemcpy(dN, N, n * 8, hipMemcpyHostToDevice));
-    LP_CHECK(hipMemcpy(dK, k, n * 8, hipMemcpyHostToDevice));
-    LP_CHECK(hipMemcpy(dD, delta, n * 8, hipMemcpyHostToDevice));
-    LP_CHECK(hipMemcpy(dL, lgamma_tab, lgamma_len * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(lprob_k_given_N_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, dN, dK, dD, n, lamb, beta, dL, dO, dH);
-    LP_CHECK(hipGetLastError());
-    LP_CHECK(hipMemcpy(lprob, dO, n * 8, hipMemcpyDeviceToHost));
-    LP_CHECK(hipMemcpy(lhs, dH, n * 8, hipMemcpyDeviceToHost));
-#undef LP_CHECK
-    cleanup();
+    DeviceArray<unsigned long long> dN, dK;
+    DeviceArray<double> dD, dL, dO, dH;
+    int rc;
+    if ((rc = dN.alloc(n, "N")) || (rc = dK.alloc(n, "k")) || (rc = dD.alloc(n, "delta")) || (rc = dL.alloc(lgamma_len, "lgamma_tab")) ||
+        (rc = dO.alloc(n, "lprob")) || (rc = dH.alloc(n, "lhs"))) return rc;
+    TRACS_HIP_CHECK(hipMemcpy(dN.get(), N, n * 8, hipMemcpyHostToDevice));
+    TRACS_HIP_CHECK(hipMemcpy(dK.get(), k, n * 8, hipMemcpyHostToDevice));
+    TRACS_HIP_CHECK(hipMemcpy(dD.get(), delta, n * 8, hipMemcpyHostToDevice));
+    TRACS_HIP_CHECK(hipMemcpy(dL.get(), lgamma_tab, lgamma_len * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(lprob_k_given_N_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, nullptr, dN.get(), dK.get(), dD.get(), n, lamb, beta,
+                       dL.get(), dO.get(), dH.get());
+    TRACS_HIP_CHECK(hipGetLastError());
+    TRACS_HIP_CHECK(hipMemcpy(lprob, dO.get(), n * 8, hipMemcpyDeviceToHost));
+    TRACS_HIP_CHECK(hipMemcpy(lhs, dH.get(), n * 8, hipMemcpyDeviceToHost));
     return TRACS_OK;
 }
 

@@ -306,20 +306,17 @@ int tracs_tree_transfer(size_t n, const uint32_t *parent, const uint32_t *child,
     const size_t bytes = tracs_transfer_state_bytes(n);
     if (!bytes) { set_error("tracs_tree_transfer: more than 2^24 leaves"); return TRACS_E_ARG; }
     if (n_edges != 2 * n - 3) { set_error("tracs_tree_transfer: a tree over n leaves has 2n - 3 edges"); return TRACS_E_ARG; }
-    char *d = nullptr;
-    TRACS_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), bytes + n_edges * 4));
+    DeviceArray<char> buf;
+    int rc = buf.alloc(bytes + n_edges * 4, "transfer state and phi");
+    if (rc) return rc;
+    char *const d = buf.get();
     uint32_t *d_phi = reinterpret_cast<uint32_t *>(d + bytes);
     std::vector<uint32_t> got(n_edges);
-    auto done = [&](int r) { (void)hipDeviceSynchronize(); (void)hipFree(d); return r; };
-    int rc;
-    if ((rc = tracs_transfer_init(d, n, parent, child, n_edges, nullptr))) return done(rc);
-    if ((rc = tracs_transfer_add(d, n, rep_parent, rep_child, rep_n_edges, d_phi, nullptr))) return done(rc);
-    if (hipMemcpy(got.data(), d_phi, n_edges * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-        set_error("tracs_tree_transfer: the kernel or the copy of its result failed");
-        return done(TRACS_E_HIP);
-    }
+    if ((rc = tracs_transfer_init(d, n, parent, child, n_edges, nullptr)) ||
+        (rc = tracs_transfer_add(d, n, rep_parent, rep_child, rep_n_edges, d_phi, nullptr))) return rc;
+    TRACS_HIP_CHECK(hipMemcpy(got.data(), d_phi, n_edges * 4, hipMemcpyDeviceToHost));
     for (size_t e = 0; e < n_edges; e++) if (child[e] >= n) phi[e] = got[e];
-    return done(TRACS_OK);
+    return TRACS_OK;
 }
 
 // Measurement (scripts/bench_transfer.py): tracs_transfer_init with the host's share and the uploads timed apart -> seconds[2]

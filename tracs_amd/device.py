@@ -330,6 +330,20 @@ def scratch_hits():
     return [int(x) for x in hits[:n]]
 
 
+def alloc_stats():
+    """(live device blocks, live device bytes, live pinned blocks, allocations since the previous call) of the library's
+    allocation path; the fourth is reset (tracs_debug_alloc_stats)."""
+    out = (C.c_uint64 * 4)()
+    _lib.load().tracs_debug_alloc_stats(out)
+    return tuple(int(x) for x in out)
+
+
+def fail_alloc(nth):
+    """Tests: the nth allocation from now (1-based, device or pinned) fails as out of memory, once; 0 switches it off
+    (tracs_debug_fail_alloc)."""
+    _lib.load().tracs_debug_fail_alloc(int(nth))
+
+
 def pack_stages():
     """[(stage, ms), ..] of the last once-per-pack build (encoding decision, site classes, lists), from HIP events on the launch
     stream; recorded when tracs_debug_pack_timing(1) was set before the dense call (diagnostics: bench.py's single_pass)."""
