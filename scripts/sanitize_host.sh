@@ -15,3 +15,6 @@ TSAN_OPTIONS=halt_on_error=1 $OUT/tsan_driver $OUT
 ${HIPCC:-/opt/rocm/bin/hipcc} -std=c++17 -O1 -g -x hip --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer \
     scripts/san_alloc.cpp -o $OUT/san_alloc
 ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $OUT/san_alloc
+# fourth pass: the run-time switches' accessors (csrc/switches.h): host only, nothing from HIP
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer scripts/san_switches.cpp -lpthread -o $OUT/san_switches
+ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $OUT/san_switches

@@ -3,13 +3,15 @@ import os
 import subprocess
 import sys
 
+from . import switches
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libtracs_hip.so")
 SOURCES = ["capi.hip", "pairsnp.hip", "pairsnp_mfma.hip", "general_sparse.hip", "site_lists.hip", "site_classes.hip", "site_select.hip", "sample_select.hip", "msa_out.hip", "transcluster.hip", "dmultinomial.hip", "cluster.hip", "filter.hip", "filter_lists.hip", "pair_sites.hip", "nearest.hip", "forest.hip", "ancestors.hip", "nj.hip", "bootstrap.hip", "transfer.hip", "fitch.hip", "tree_mask.hip", "histogram.hip", "dirichlet.hip", "exchange.hip", "fasta.cpp", "alignio.cpp", "comm.cpp"]
-HEADERS = ["common.h", "alloc_path.h", "pairsnp_kernels.h", "filter_math.h", "scan_kernels.h", "pair_select.h", "fasta.h", "rowwriter.h", "debug_api.h", os.path.join("..", "..", "include", "tracs_hip.h")]
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+HEADERS = ["common.h", "alloc_path.h", "switches.h", "pairsnp_kernels.h", "filter_math.h", "scan_kernels.h", "pair_select.h", "fasta.h", "rowwriter.h", "debug_api.h", os.path.join("..", "..", "include", "tracs_hip.h")]
+HIPCC = switches.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fgpu-rdc" if False else "-fno-gpu-rdc",
          "-Wall", "-Wno-unused-function", "-ffp-contract=off"]
 
@@ -25,7 +27,7 @@ def build(force=False, verbose=False, extra_flags=(), libdir=None):
     """Compile every HIP source for gfx950 and link the shared library.  Cross-compiles without a GPU.
     TRACS_EXTRA_HIPCC_FLAGS adds flags (e.g. -DTRACS_MFMA_SWEEP: every matrix-core tile shape, for shape sweeps).
     libdir: build into another directory (tests/test_build.py compiles from scratch without touching the loaded library)."""
-    extra_flags = list(extra_flags) + os.environ.get("TRACS_EXTRA_HIPCC_FLAGS", "").split()
+    extra_flags = list(extra_flags) + switches.get("TRACS_EXTRA_HIPCC_FLAGS", "").split()
     out_dir = LIBDIR if libdir is None else libdir
     lib = os.path.join(out_dir, "libtracs_hip.so")
     if libdir is None and not force and not _stale():

@@ -131,7 +131,7 @@ void tracs_debug_fail_alloc(long nth) { fail_alloc(nth); }
 struct StageClock {
     bool on;
     std::chrono::steady_clock::time_point t;
-    StageClock() : on(std::getenv("TRACS_STAGE_TRACE") != nullptr), t(std::chrono::steady_clock::now()) {}
+    StageClock() : on(sw::is_set(sw::TRACS_STAGE_TRACE)), t(std::chrono::steady_clock::now()) {}
     void mark(const char *name, double bytes = 0.0)
     {
         if (!on) return;
@@ -255,14 +255,6 @@ using ResultOwner = std::unique_ptr<tracs_pairsnp_result, ResultFree>;
 
 static int interrupted() { set_error("Interrupted by user!"); return TRACS_E_INTERRUPTED; }
 
-// a diagnostics switch that counts rows, read on every call (0: not set, or below `least`)
-static size_t env_rows(const char *name, long long least)
-{
-    const char *e = std::getenv(name);
-    const long long v = e ? std::atoll(e) : 0;
-    return v >= least ? (size_t)v : (size_t)0;
-}
-
 // where a stage-trace lap goes: the entry point that owns the timers says which of its sums takes it
 enum Lap { LAP_DENSE, LAP_TC, LAP_COO, LAP_FILTER };
 using LapFn = std::function<void(Lap)>;
@@ -293,7 +285,7 @@ struct PanelWalk {
     // with_off: row offsets for a PairStage; with_f64: the P(direct) and E(K) panels of the dense transcluster route
     int begin(bool with_off, bool with_f64)
     {
-        const size_t rows = env_rows("TRACS_FOREST_PANEL_ROWS", 1);
+        const size_t rows = (size_t)std::max(0LL, sw::integer(sw::TRACS_FOREST_PANEL_ROWS, 0LL));     // (0: not set, or below 1)
         height = rows ? std::min(rows, i_end) : std::max<size_t>(64, std::min<size_t>(i_end, (1ull << 28) / std::max<size_t>(n, 1)));
         int rc;
         if ((rc = d_dist.alloc(height * n * 4, "dist")) || (rc = d_nn.alloc(height * n * 4, "nn"))) return rc;
@@ -990,7 +982,8 @@ int tracs_distance_run(tracs_distance *h, int dist, const int32_t *days, double 
     SigintScope sigint;
     const bool with_dates = days != nullptr;
     // rows per device-to-host batch (TRACS_DISTANCE_BATCH_ROWS: diagnostics -- small batches in tests)
-    const size_t batch_rows = env_rows("TRACS_DISTANCE_BATCH_ROWS", 16);
+    const long long env_rows = sw::integer(sw::TRACS_DISTANCE_BATCH_ROWS, 0LL);
+    const size_t batch_rows = env_rows >= 16 ? (size_t)env_rows : 0;            // (below 16: as if not set)
     // (never more than the pairs there can be: ten isolates do not pin a quarter of a gigabyte of host memory)
     const size_t CH = std::max<size_t>(64, std::min<size_t>(batch_rows ? batch_rows : (size_t)1 << 22, (h->n_fasta == 1 ? h->a->n : h->n0) * h->a->n));
     tracs::DistanceRowWriter writer;

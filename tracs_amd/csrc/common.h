@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/tracs_hip.h"
+#include "switches.h"
 
 namespace tracs {
 

@@ -12,6 +12,7 @@
 // Own implementation: a streaming state machine over 4 MiB gzread blocks (zlib reads plain and gzip files alike, as
 // gzopen does for the reference), plus a multi-threaded mmap fast path for large well-formed plain FASTA files.
 #include "fasta.h"
+#include "switches.h"
 
 #include <zlib.h>
 
@@ -277,8 +278,8 @@ static bool read_fasta_members(const std::string &path, FastaData &out)
 
 int read_fasta(const std::string &path, FastaData &out, std::string &err)
 {
-    if (out.n == 0 && out.seq.empty() && !getenv("TRACS_SERIAL_FASTA") && read_fasta_members(path, out)) return TRACS_OK;
-    if (out.n == 0 && out.seq.empty() && !getenv("TRACS_SERIAL_FASTA") && read_fasta_parallel(path, out)) return TRACS_OK;
+    if (out.n == 0 && out.seq.empty() && !sw::is_set(sw::TRACS_SERIAL_FASTA) && read_fasta_members(path, out)) return TRACS_OK;
+    if (out.n == 0 && out.seq.empty() && !sw::is_set(sw::TRACS_SERIAL_FASTA) && read_fasta_parallel(path, out)) return TRACS_OK;
     gzFile f = gzopen(path.c_str(), "rb");
     if (!f) { err = "cannot open '" + path + "'"; return TRACS_E_OPEN; }
     gzbuffer(f, 1u << 20);

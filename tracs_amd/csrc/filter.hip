@@ -176,8 +176,7 @@ static int filter_scan_launch(const tracs_alignment *a, const unsigned *rows, co
 {
     const unsigned blocks = (unsigned)std::min<size_t>(n_pairs, 256 * 64);
     // a pair per lane needs enough pairs to fill the chip (every lane walks all groups); below that, a wave per pair
-    size_t lanes_min = 16384;
-    if (const char *e = std::getenv("TRACS_FILTER_LANES_MIN")) lanes_min = (size_t)std::strtoull(e, nullptr, 10);
+    const size_t lanes_min = (size_t)sw::size(sw::TRACS_FILTER_LANES_MIN, 16384);
     if (n_pairs >= lanes_min)
         hipLaunchKernelGGL(filter_extract_lanes_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, a->planes,
                            a->n_pad, (unsigned)a->L, (unsigned)a->groups, rows, cols, n_pairs, pos_off, positions, found);
@@ -206,8 +205,7 @@ int filter_scan_route(const tracs_alignment *a, const unsigned *rows, const unsi
                       hipStream_t stream)
 {
     if (!n_pairs) return TRACS_OK;
-    size_t kMaxPos = 1ull << 28;
-    if (const char *e = std::getenv("TRACS_FILTER_SCAN_MAXPOS")) kMaxPos = std::max<size_t>(1, (size_t)std::strtoull(e, nullptr, 10));   // (tests: several batches)
+    const size_t kMaxPos = std::max<size_t>(1, (size_t)sw::size(sw::TRACS_FILTER_SCAN_MAXPOS, 1ull << 28));   // (tests: several batches)
     const size_t per = std::max<size_t>(1, std::min<size_t>(n_pairs, kMaxPos / std::max<size_t>(max_d, 1)));
     unsigned *pos, *found;
     long long *off;

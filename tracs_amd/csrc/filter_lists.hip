@@ -1054,12 +1054,6 @@ __global__ __launch_bounds__(256) void flt_max_kernel(const unsigned *__restrict
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 
-static bool flt_env_off(const char *name)
-{
-    const char *e = std::getenv(name);
-    return e && e[0] == '0';
-}
-
 // a part that is kept from one build of the handle to the next: allocated once
 template <class T>
 static bool flt_alloc(DeviceArray<T> &p, size_t count) { return p.get() || p.try_alloc(count); }
@@ -1087,7 +1081,7 @@ static int filter_index_get(tracs_alignment *a, hipStream_t stream)
     f->usable = false;
     f->n = a->n; f->L = a->L;
     a->flt_stale = false;
-    if (flt_env_off("TRACS_FILTER_LISTS") || a->L >= (1ull << FLT_POS_BITS) || a->n < 2 || a->L == 0) return TRACS_OK;
+    if (sw::is_zero(sw::TRACS_FILTER_LISTS) || a->L >= (1ull << FLT_POS_BITS) || a->n < 2 || a->L == 0) return TRACS_OK;
     const unsigned n = (unsigned)a->n, groups = (unsigned)a->groups;
     const unsigned chunks = (groups + FLT_GCHUNK - 1) / FLT_GCHUNK;
     FltEvents E;
@@ -1151,7 +1145,7 @@ static int filter_index_get(tracs_alignment *a, hipStream_t stream)
         f->build_ms[k] = ms;
     }
     f->usable = true;
-    if (std::getenv("TRACS_CLASSES_TRACE"))
+    if (sw::is_set(sw::TRACS_CLASSES_TRACE))
         std::fprintf(stderr, "[filter index] %llu entries (longest list %u), alloc %.2f ms, ref %.3f count %.3f offsets %.3f fill %.3f NT %.3f NS %.3f ms\n",
                      total, max_len, f->alloc_ms, f->build_ms[0], f->build_ms[1], f->build_ms[2], f->build_ms[3], f->build_ms[4], f->build_ms[5]);
     return done(TRACS_OK);
@@ -1195,7 +1189,7 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
     if (!f->counters.get() && (rc = f->counters.alloc(16, "filter counters"))) return rc;
     TRACS_HIP_CHECK(hipMemsetAsync(f->counters.get(), 0, 64, stream));
     // thresholds of the binomial test for the d of this call
-    const bool use_tbl = !flt_env_off("TRACS_FILTER_TABLE");
+    const bool use_tbl = !sw::is_zero(sw::TRACS_FILTER_TABLE);
     if (use_tbl) {
         if ((rc = flt_table_rows(f, a, stream))) return rc;
         const unsigned blocks = (unsigned)std::min<size_t>((n_pairs + 255) / 256, 256 * 16);
@@ -1209,7 +1203,7 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
     bool all_left = true;
     if (f->usable) {
         unsigned cap = std::min(FLT_CAP_MAX, (std::max(f->max_len, 1u) + 63u) / 64u * 64u);
-        if (const char *e = std::getenv("TRACS_FILTER_CAP")) cap = std::max(64u, std::min(FLT_CAP_MAX, (unsigned)std::atoi(e) / 64u * 64u));
+        if (sw::is_set(sw::TRACS_FILTER_CAP)) cap = std::max(64u, std::min(FLT_CAP_MAX, (unsigned)sw::integer(sw::TRACS_FILTER_CAP, 0) / 64u * 64u));
         FltPairArgs A;
         A.rows = rows; A.cols = cols; A.d = d; A.n_pairs = n_pairs;
         A.dep = f->dep.get(); A.dep_off = f->dep_off.get();
@@ -1218,8 +1212,7 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
         A.L = (unsigned)a->L; A.cap = cap;
         A.tbl = tbl; A.tbl_state = f->tbl_state.get(); A.lg = lg;
         A.filt = filt; A.counters = f->counters.get();
-        const char *form_env = std::getenv("TRACS_FILTER_KERNEL");
-        const int form = form_env ? std::atoi(form_env) : 2;
+        const int form = sw::integer(sw::TRACS_FILTER_KERNEL, 2);
         if (form == 2 && cap <= 1024) {
             const unsigned r = cap / 64;
             if (r <= 1) flt_launch2<1>(A, stream);
@@ -1271,7 +1264,7 @@ int tracs_filter_recomb_pairs(tracs_alignment *a, const uint32_t *rows, const ui
         A.tbl = tbl; A.tbl_state = f->tbl_state.get(); A.lg = lg;
         A.filt = filt; A.counters = f->counters.get();
         // (TRACS_FILTER_LONG=seq: the per-lane sequential merge over global memory instead of the tiled one: tests, A/B)
-        const char *lf = std::getenv("TRACS_FILTER_LONG");
+        const char *lf = sw::text(sw::TRACS_FILTER_LONG);
         if (lf && lf[0] == 's')
             hipLaunchKernelGGL(flt_pairs_long_kernel, dim3((unsigned)waves), dim3(64), 0, stream, A, idx, n_left, scratch, slot);
         else
@@ -1320,7 +1313,7 @@ int tracs_filter_recomb_lists(tracs_alignment *a, const int64_t *off, const uint
     if (rc) return rc;
     if (!a->flt) { a->flt = new FilterIndex(); a->flt_stale = true; }     // (the rows only: a pair call builds the lists when it comes)
     FilterIndex *f = a->flt;
-    const bool use_tbl = !flt_env_off("TRACS_FILTER_TABLE");
+    const bool use_tbl = !sw::is_zero(sw::TRACS_FILTER_TABLE);
     if (use_tbl) {
         if ((rc = flt_table_rows(f, a, stream))) return rc;
         const unsigned blocks = (unsigned)std::min<size_t>((n_lists + 255) / 256, 256 * 16);

@@ -353,7 +353,7 @@ int fitch_slabs(const tracs_alignment *a, const uint32_t *child, size_t n_edges,
     const size_t n = a->n, nodes = n >= 3 ? 2 * n - 2 : n;
     size_t slab = std::max<size_t>(1, FITCH_SLAB_BYTES / (nodes * 64));
     if (slab >= 16) slab &= ~(size_t)15;                                   // (whole waves of words)
-    if (const char *e = std::getenv("TRACS_FITCH_SLAB_GROUPS")) slab = std::max<size_t>(1, (size_t)std::strtoull(e, nullptr, 10));
+    slab = std::max<size_t>(1, (size_t)sw::size(sw::TRACS_FITCH_SLAB_GROUPS, slab));
     slab = std::min(slab, g_end - g_begin);
     if (max_slab) slab = std::min(slab, max_slab);
     int rc;
@@ -507,8 +507,7 @@ int fitch_edge_sites(const tracs_alignment *a, const uint32_t *parent, const uin
         (rc = offsets_scan_launch(edge_changes, n_edges, sums, edge_off, stream))) return rc;
     if (!room || !a->L) return TRACS_OK;
     const size_t g_end = groups_for(a->L);
-    size_t range_chunks = std::max<size_t>(1, FITCH_MATRIX_BYTES / (n_edges * 4));
-    if (const char *e = std::getenv("TRACS_FITCH_MATRIX_CHUNKS")) range_chunks = std::max<size_t>(1, (size_t)std::strtoull(e, nullptr, 10));
+    const size_t range_chunks = std::max<size_t>(1, (size_t)sw::size(sw::TRACS_FITCH_MATRIX_CHUNKS, FITCH_MATRIX_BYTES / (n_edges * 4)));
     FitchSlabs S;
     // (a slab of g groups walks ceil(g / 16) chunks: one that outgrows the range is cut to whole chunks)
     if ((rc = fitch_slabs(a, child, n_edges, 0, g_end, range_chunks * FITCH_CHUNK_GROUPS, S, stream))) return rc;
@@ -649,8 +648,7 @@ int fitch_write(const tracs_alignment *a, const char *const *names, const uint64
     PinnedArray<unsigned> host_buf;
     const std::vector<long long> &off = t.off;
     const uint64_t total = t.total;
-    size_t cap = (256ull << 20) / 12;                                      // entries per batch: 12 bytes each
-    if (const char *e = std::getenv("TRACS_FITCH_BATCH")) cap = std::max<size_t>(1, (size_t)std::strtoull(e, nullptr, 10));
+    const size_t cap = std::max<size_t>(1, (size_t)sw::size(sw::TRACS_FITCH_BATCH, (256ull << 20) / 12));         // entries per batch: 12 bytes each
     long long max_c = 0;
     for (size_t s = 0; s < L; s++) max_c = std::max(max_c, off[s + 1] - off[s]);
     const size_t room = std::max<size_t>(std::max<size_t>(std::min<size_t>(cap, total), (size_t)max_c), 1);

@@ -381,7 +381,7 @@ static int gs_build(const SRC src, size_t n, size_t L, size_t groups, double max
     if (failed(hipStreamSynchronize(stream))) return fail_soft();
     if (tot_s != tot_p + tot_n) { set_error("general_sparse: list totals disagree (internal error)"); return TRACS_E_HIP; }
     // TRACS_LIST_CAP=<entries>: a smaller cap (diagnostics: exercises the paths taken when the lists are refused)
-    static const double env_cap = [] { const char *e = std::getenv("TRACS_LIST_CAP"); return e ? std::atof(e) : -1.0; }();
+    const double env_cap = sw::real(sw::TRACS_LIST_CAP, -1.0);
     if ((double)tot_s > (env_cap >= 0.0 ? std::min(env_cap, max_entries) : max_entries)) return fail_soft();
     if (!g->s_ent.try_alloc(std::max<size_t>(tot_s, 1)) || !g->p_ent.try_alloc(std::max<size_t>(tot_p, 1)) ||
         !g->n_ent.try_alloc(std::max<size_t>(tot_n, 1))) return fail_soft();

@@ -288,8 +288,8 @@ __global__ __launch_bounds__(256) void hist_fill_kernel(const u64 *__restrict__ 
 // sweep is in DESIGN.md 3.11 and profiles/histogram/variant_*.json
 unsigned hist_grid()
 {
-    static const unsigned v = [] { const char *e = std::getenv("TRACS_HIST_GRID"); const long c = e ? std::atol(e) : 0; return (c >= 1 && c <= 65535) ? (unsigned)c : 2048u; }();
-    return v;
+    const long c = tracs::sw::integer(tracs::sw::TRACS_HIST_GRID, 0L);
+    return (c >= 1 && c <= 65535) ? (unsigned)c : 2048u;
 }
 
 }  // namespace

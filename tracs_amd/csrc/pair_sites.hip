@@ -204,9 +204,7 @@ int get_lgamma_table_for_filter(hipStream_t stream, const double **out);   // tr
 static size_t pair_sites_lanes_min()
 {
     // a pair per lane needs enough pairs to fill the chip (every lane walks all groups); below that, a wave per pair
-    size_t lanes_min = 16384;
-    if (const char *e = std::getenv("TRACS_PAIR_SITES_LANES_MIN")) lanes_min = (size_t)std::strtoull(e, nullptr, 10);
-    return lanes_min;
+    return (size_t)sw::size(sw::TRACS_PAIR_SITES_LANES_MIN, 16384);
 }
 
 static int pair_sites_check(const tracs_alignment *a, const char *who)
@@ -342,8 +340,7 @@ int pair_sites_write(const tracs_alignment *a, const char *const *names, const u
     }
     std::vector<long long> off(n_pairs + 1, 0);
     TRACS_HIP_CHECK(hipMemcpy(off.data(), d_off, (n_pairs + 1) * 8, hipMemcpyDeviceToHost));
-    size_t cap = (256ull << 20) / 8;                                       // entries per batch: 8 bytes each
-    if (const char *e = std::getenv("TRACS_PAIR_SITES_BATCH")) cap = std::max<size_t>(1, (size_t)std::strtoull(e, nullptr, 10));
+    const size_t cap = std::max<size_t>(1, (size_t)sw::size(sw::TRACS_PAIR_SITES_BATCH, (256ull << 20) / 8));     // entries per batch: 8 bytes each
     long long max_d = 0;
     for (size_t t = 0; t < n_pairs; t++) max_d = std::max(max_d, off[t + 1] - off[t]);
     const size_t room = std::max<size_t>(std::max<size_t>(std::min<size_t>(cap, total), (size_t)max_d), 1);

@@ -552,7 +552,7 @@ static void build_tiles(size_t n, size_t row_begin, size_t row_end, size_t col_b
     // tiles per supertile ~ one XCD's resident set; TRACS_SUPERTILE=<rows>x<cols> overrides (diagnostics)
     static const std::pair<size_t, size_t> shape = [] {
         std::pair<size_t, size_t> v{4, 8};
-        if (const char *e = std::getenv("TRACS_SUPERTILE")) {
+        if (const char *e = sw::text(sw::TRACS_SUPERTILE)) {
             unsigned a = 0, b = 0;
             if (std::sscanf(e, "%ux%u", &a, &b) == 2 && a >= 1 && b >= 1 && a <= 64 && b <= 64) v = {a, b};
         }
@@ -612,11 +612,8 @@ static constexpr int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0
 
 static const TileVariant &current_variant(bool consensus)
 {
-    static const int forced = [] {
-        if (const char *e = std::getenv("TRACS_TILE_VARIANT")) { const int v = std::atoi(e); if (v >= 0 && v < kNumVariants) return v; }
-        return -1;
-    }();
-    return kVariants[forced >= 0 ? forced : (consensus ? 1 : 0)];
+    const int forced = sw::integer(sw::TRACS_TILE_VARIANT, -1);
+    return kVariants[forced >= 0 && forced < kNumVariants ? forced : (consensus ? 1 : 0)];
 }
 
 static size_t plane_bytes(const tracs_alignment *a, int planes)
@@ -687,7 +684,7 @@ int tracs_alignment_create(size_t n, size_t L, tracs_alignment **out)
         // the arena of the once-per-pack structures: 30 % of the planes + up to 128 MiB covers the lists of alignments with N lists of
         // up to ~190 samples at every site of 10 000 samples -- as far as the cost model takes lists (TRACS_PACK_ARENA=<fraction>
         // overrides; 0: none).  Not getting it is not an error; what does not fit is allocated on its own.
-        static const double frac = [] { const char *v = std::getenv("TRACS_PACK_ARENA"); return v ? std::atof(v) : 0.30; }();
+        const double frac = sw::real(sw::TRACS_PACK_ARENA, 0.30);
         if (frac > 0.0 && n >= 2) {
             const size_t want = (size_t)((double)bytes * frac) + std::min<size_t>(128u << 20, 2 * bytes + (1u << 20));
             if (device_try_alloc(want, reinterpret_cast<void **>(&a->arena))) a->arena_bytes = want;
@@ -895,17 +892,15 @@ static inline void pair_mark(int k, hipStream_t stream)
     if (k == 4) g_pair_calls++;
 }
 
-static int env_flag(const char *name) { const char *e = std::getenv(name); return e ? std::atoi(e) : -1; }
-
 // ---- host driver of the dense call --------------------------------------------------------------------------
-// Its switches.  mfma_off .. thr_one_pass are read once per process, when a call first gets there; ksplit and thr_prefix by every call
+// Its switches, by the names the driver uses (kinds and lifetimes: switches.h)
 namespace dense_switch {
-static bool mfma_off()      { static const bool v = env_flag("TRACS_MFMA") == 0 || std::getenv("TRACS_TILE_VARIANT") != nullptr; return v; }
-static bool force_general() { static const bool v = std::getenv("TRACS_FORCE_GENERAL") != nullptr; return v; }
-static int general_mfma()   { static const int v = env_flag("TRACS_GENERAL_MFMA"); return v; }   // 1: always, 0: never the matrix cores for general alignments
-static bool thr_one_pass()  { static const bool v = std::getenv("TRACS_THR_ONE_PASS") != nullptr; return v; }
-static int ksplit()         { const char *e = std::getenv("TRACS_KSPLIT"); return e ? std::atoi(e) : 0; }
-static int thr_prefix()     { const char *e = std::getenv("TRACS_THR_PREFIX"); return e ? std::atoi(e) : 0; }
+static bool mfma_off()      { return sw::integer(sw::TRACS_MFMA, -1) == 0 || sw::is_set(sw::TRACS_TILE_VARIANT); }
+static bool force_general() { return sw::is_set(sw::TRACS_FORCE_GENERAL); }
+static int general_mfma()   { return sw::integer(sw::TRACS_GENERAL_MFMA, -1); }   // 1: always, 0: never the matrix cores for general alignments
+static bool thr_one_pass()  { return sw::is_set(sw::TRACS_THR_ONE_PASS); }
+static int ksplit()         { return sw::integer(sw::TRACS_KSPLIT, 0); }
+static int thr_prefix()     { return sw::integer(sw::TRACS_THR_PREFIX, 0); }
 }
 
 // ---- once per pack: encoding and site classes, decided together from the general planes (site_classes.hip) --------------------

@@ -465,7 +465,7 @@ const MfmaShape &mfma_shape(int idx) { return kShapes[idx].s; }
 int mfma_shape_current(bool general)
 {
     static const int forced = [] {
-        if (const char *e = std::getenv("TRACS_MFMA_TILE"))
+        if (const char *e = sw::text(sw::TRACS_MFMA_TILE))
             for (int i = 0; i < mfma_shape_count(); i++)
                 if (!std::strcmp(e, kShapes[i].s.name)) return i;
         return -1;
@@ -504,7 +504,7 @@ static const CountShape kCountShapes[] = {
 CountShape count_shape_current()
 {
     static const int forced = [] {
-        if (const char *e = std::getenv("TRACS_COUNT_TILE"))
+        if (const char *e = sw::text(sw::TRACS_COUNT_TILE))
             for (size_t i = 0; i < sizeof(kCountShapes) / sizeof(kCountShapes[0]); i++)
                 if (!std::strcmp(e, kCountShapes[i].name)) return (int)i;
         return 0;

@@ -598,8 +598,7 @@ static bool g_stage_on = false, g_stage_valid = false;
 
 static void stage_begin(hipStream_t stream)
 {
-    static const bool trace = std::getenv("TRACS_CLASSES_TRACE") != nullptr;
-    if (trace) g_stage_on = true;
+    if (sw::is_set(sw::TRACS_CLASSES_TRACE)) g_stage_on = true;
     g_stage_n = 0; g_stage_valid = false;
     if (!g_stage_on) return;
     if (!g_stage_ev[0]) for (auto &e : g_stage_ev) (void)hipEventCreate(&e);
@@ -627,8 +626,7 @@ void pack_stage_count_gone(const unsigned long long *count)
 }
 void pack_stage_end()
 {
-    static const bool trace = std::getenv("TRACS_CLASSES_TRACE") != nullptr;
-    if (!trace || !g_stage_valid) return;
+    if (!sw::is_set(sw::TRACS_CLASSES_TRACE) || !g_stage_valid) return;
     (void)hipEventSynchronize(g_stage_ev[g_stage_n]);
     for (int k = 0; k < g_stage_n; k++) {
         float ms = 0.0f;
@@ -654,13 +652,13 @@ static int decide(tracs_alignment *a, bool allow_minor, bool allow_nnl, hipStrea
                   bool no_gram = false)
 {
     a->classes_state = -1;
-    const int env_gram = [] { const char *e = std::getenv("TRACS_NW_GRAM"); return e ? std::atoi(e) : -1; }();    // (read per pack: tests switch it)
+    const int env_gram = sw::integer(sw::TRACS_NW_GRAM, -1);
     if (env_gram == 1 && allow_minor) gram = true;
     const bool gram_next = !gram && !no_gram && env_gram != 0 && allow_minor && allow_nnl;
-    static const int env_force = [] { const char *e = std::getenv("TRACS_SITE_CLASSES"); return e ? std::atoi(e) : -1; }();
+    const int env_force = sw::integer(sw::TRACS_SITE_CLASSES, -1);
     const int force = g_force_classes >= -1 ? g_force_classes : env_force;
-    static const bool no_minor = [] { const char *e = std::getenv("TRACS_MINORITY"); return e && std::atoi(e) == 0; }();
-    static const bool force_general = std::getenv("TRACS_FORCE_GENERAL") != nullptr;
+    const bool no_minor = sw::integer(sw::TRACS_MINORITY, -1) == 0;
+    const bool force_general = sw::is_set(sw::TRACS_FORCE_GENERAL);
     const size_t groups = a->groups;
     // sample blocks in grid.y of the re-pack kernels (<= 65535 x 64 samples per launch; beyond that the classes are not used)
     const unsigned sblocks = (unsigned)(a->n_pad / 64);
@@ -694,20 +692,20 @@ static int decide(tracs_alignment *a, bool allow_minor, bool allow_nnl, hipStrea
     // for 3.8e10 with 0.5 % partial codes) -- k (cN + k) <= n^2 / 2000: 50 000 entries at 10 000 samples.  (n^2 / 8000 until round 5
     // sent the 16 896 sites of the partial-code alignment with k >= 73 through the pair kernel: 4.5 ms of a 51.5 ms call;
     // TRACS_MINOR_BUDGET_DIV overrides the divisor for that measurement)
-    static const double budget_div = [] { const char *e = std::getenv("TRACS_MINOR_BUDGET_DIV"); return e && std::atof(e) > 0 ? std::atof(e) : 2000.0; }();
+    const double env_div = sw::real(sw::TRACS_MINOR_BUDGET_DIV, 0.0), budget_div = env_div > 0 ? env_div : 2000.0;
     const double bsites = (double)a->n * (double)a->n / budget_div;
     const unsigned budget = (no_minor || !allow_minor) ? 0u : (unsigned)std::min(1.0e9, std::max(16.0, bsites));
     // The N co-occurrences of a site with cN N samples cost cN list walks of one cache line per ~115 samples of the list (n8 lines,
     // pairsnp_kernels.h; nn_rows_kernel is bound by the lines it pulls through the fabric) against n^2 / 2 pairs on the matrix
     // cores, whatever cN: lists while cN x lines <= TRACS_NN_LIST_K x n^2 (default 6e-6: DESIGN.md 3.1); TRACS_NN_LISTS=0: never
-    static const bool no_nnl = [] { const char *e = std::getenv("TRACS_NN_LISTS"); return e && std::atoi(e) == 0; }();
-    static const double nnl_k = [] { const char *e = std::getenv("TRACS_NN_LIST_K"); return e ? std::atof(e) : 6e-6; }();
+    const bool no_nnl = sw::integer(sw::TRACS_NN_LISTS, -1) == 0;
+    const double nnl_k = sw::real(sw::TRACS_NN_LIST_K, 6e-6);
     const unsigned nn_list_max = (no_nnl || !allow_nnl) ? 0u : (unsigned)std::min(4.0e9, nnl_k * (double)a->n * (double)a->n);
     TRACS_HIP_CHECK(hipMemsetAsync(totals, 0, 256, stream));
 #define TRACS_CLASSIFY_ARGS a->planes, a->n_pad, (unsigned)a->n, budget, nn_list_max, gram ? 1u : 0u, masks, groups, cntP, cntN, gcnt, gcnt + groups, \
                             gcnt + 2 * groups, gcnt + 3 * groups, gcnt + 4 * groups, gcnt + 5 * groups, gcnt + 6 * groups, flags, flag_words, d_flag,          \
                             gram_next ? masks2 : (uint4 *)nullptr, gram_next ? gcnt2 : (unsigned *)nullptr
-    const int env_threads = [] { const char *e = std::getenv("TRACS_CLASSIFY_THREADS"); return e ? std::atoi(e) : 0; }();      // (read per pack: tests switch it)
+    const int env_threads = sw::integer(sw::TRACS_CLASSIFY_THREADS, 0);
     if (env_threads == 64 || (env_threads == 0 && a->n <= 2048))
         hipLaunchKernelGGL(classify_sites_kernel<64>, dim3((unsigned)groups), dim3(64), 0, stream, TRACS_CLASSIFY_ARGS);
     else if (env_threads != 256)
@@ -730,7 +728,7 @@ static int decide(tracs_alignment *a, bool allow_minor, bool allow_nnl, hipStrea
     size_t L_count = (size_t)tot[M_COUNT], L_nnl = (size_t)tot[M_NNL], L_lst = (size_t)tot[M_LST], L_un = (size_t)tot[M_UN];
     unsigned long long tot_p = tot[7], tot_q = long_p ? tot[13] : 0ull;
     // (256-byte q lines when the minority sites list more than Q_WIDE_MEAN samples on average: site_lists.hip; TRACS_QLINE_DWORDS=32|64 forces)
-    static const int force_qw = [] { const char *e = std::getenv("TRACS_QLINE_DWORDS"); return e ? std::atoi(e) : 0; }();
+    const int force_qw = sw::integer(sw::TRACS_QLINE_DWORDS, 0);
     unsigned qw = force_qw == 32 || force_qw == 64 ? (unsigned)force_qw : ((long_p && L_minor && (double)tot_p > Q_WIDE_MEAN * (double)L_minor) ? 64u : 32u);
     unsigned long long tot_o = tot[8], tot_nnl = tot[10];
     int lst_slot = M_LST, ovf_slot = 1;                      // which mask / per-group overflow bound the lists are built from
@@ -742,7 +740,7 @@ static int decide(tracs_alignment *a, bool allow_minor, bool allow_nnl, hipStrea
     // every site is counted (10 % N); and for SMALL alignments (config 2: 1 000 samples -- 87 % of the sites counted, the re-pack 0.75 of
     // the call's 2.4 ms), whose NNL sites then go to the matrix cores as well: the lists are built for the minority sites alone
     // (TRACS_COUNT_IN_PLACE=0|1 forces the choice: diagnostics).
-    static const int force_in_place = [] { const char *e = std::getenv("TRACS_COUNT_IN_PLACE"); return e ? std::atoi(e) : -1; }();
+    const int force_in_place = sw::integer(sw::TRACS_COUNT_IN_PLACE, -1);
     const double t_extra = 1.5e-13 * (double)(a->L - L_count) * (double)a->n * (double)a->n;
     const double t_repack = 4.0e-10 * (double)L_count * (double)a->n_pad;
     // (gram: n n^T over every site is part of the distances: always the stored N plane in place)
@@ -790,7 +788,7 @@ static int decide(tracs_alignment *a, bool allow_minor, bool allow_nnl, hipStrea
     // (the minority sites stay dense)
     if (L_lst) {
         // (TRACS_LIST_CAP=<entries of four bytes>: diagnostics)
-        static const double env_cap = [] { const char *e = std::getenv("TRACS_LIST_CAP"); return e ? 4.0 * std::atof(e) : -1.0; }();
+        const double env_cap = 4.0 * sw::real(sw::TRACS_LIST_CAP, -1.0);                  // (bytes; negative: none)
         const double cap = 0.8 * (double)NPLANES * (double)groups * (double)a->n_pad * sizeof(uint4);
         // N-list lines (primary + the overflow lines they can need at most), p lists and their per-sample form, the rows' N bitmaps
         const double bytes = ((double)L_lst + (double)tot_o) * 128.0 + 16.0 * (double)tot_p + (long_p ? ((double)L_lst + (double)tot_q) * 4.0 * (double)qw : 0.0) +
@@ -859,7 +857,7 @@ static int decide(tracs_alignment *a, bool allow_minor, bool allow_nnl, hipStrea
         // second form: the N x listed terms from the rows of the site-major N matrix, summed per listed sample (|W| x ns_words x 4 bytes from
         // HBM at ~4.5 TB/s, + the matrix itself: one read and one write of a plane), when that is less than a one-plane pass over every site
         // (1.5e-13 ms per site and pair of samples) + the U plane (four plane reads); tot_p bounds |W| from above.  TRACS_NW_ROWS=0|1 forces.
-        const int env_rows = [] { const char *e = std::getenv("TRACS_NW_ROWS"); return e ? std::atoi(e) : -1; }();
+        const int env_rows = sw::integer(sw::TRACS_NW_ROWS, -1);
         const double t_rows = (double)tot_p * (double)ns_words_for(a->n_pad) * 4.0 / 4.5e9 + 2.0 * plane_b / 5.0e9;
         const double t_upass = 1.5e-13 * (double)a->L * (double)a->n * (double)a->n + 4.0 * plane_b / 5.0e9;
         gram_rows = gram && (env_rows >= 0 ? env_rows == 1 : t_rows < t_upass);

@@ -1416,7 +1416,7 @@ int minority_lists_build(tracs_alignment *a, const MinorBuild &mb_, hipStream_t 
     if (!pack_alloc(a, groups * sizeof(unsigned), reinterpret_cast<void **>(&g->off_lst))) return fail_soft();
     const bool bitmaps = mb.tot_nnl > 0;
     // the rows' N sites: slots where a slot holds few entries on average, else bitmaps (TRACS_ROW_LISTS=0|1 forces the choice: A/B runs, tests)
-    static const int env_slots = [] { const char *e = getenv("TRACS_ROW_LISTS"); return e ? atoi(e) : -1; }();
+    const int env_slots = sw::integer(sw::TRACS_ROW_LISTS, -1);
     g->batches = (g->tgroups + SLOT_GROUPS - 1) / SLOT_GROUPS;
     const bool row_slots = bitmaps && (env_slots >= 0 ? env_slots != 0 : (double)mb.tot_nnl <= SLOT_MEAN_MAX * (double)n * (double)g->batches);
     if (row_slots) {
@@ -1543,8 +1543,7 @@ int nn_rows_add(tracs_alignment *a, size_t row_begin, size_t row_end, size_t col
     // are loaded non-temporally).  The price is one flush of the row per segment (atomic adds): 10 000 x 5 Mbp, 1.2 GB of lines:
     // 10.9 ms in one segment, 10.2 in 3 to 5 (512 / 256 MiB), 10.6 in 10, 12.9 in 32 (profiles/r04/nn_rows_n8.txt).
     // TRACS_NN_SEGMENT_MB overrides the segment size (0: one segment) for that measurement.
-    const char *seg_env = getenv("TRACS_NN_SEGMENT_MB");
-    const unsigned long long seg_bytes = (seg_env ? strtoull(seg_env, nullptr, 10) : 256ull) << 20;
+    const unsigned long long seg_bytes = sw::size(sw::TRACS_NN_SEGMENT_MB, 256) << 20;
     const unsigned segments = seg_bytes ? (unsigned)std::min<unsigned long long>(NN_MAX_SPLITS, std::max<unsigned long long>(1, (g->n_lines * 128ull + seg_bytes - 1) / seg_bytes)) : 1u;
     const unsigned splits = (unsigned)std::min<unsigned long long>(NN_MAX_SPLITS, std::max<unsigned long long>(segments, ((unsigned long long)g->max_row + target - 1) / target));
     const dim3 grid((unsigned)(row_end - row_begin), (unsigned)((n + chunk - 1) / chunk), splits);

@@ -1346,7 +1346,7 @@ static int run_trans_dist_grid(const DenseSource &src, size_t total, double lamb
 {
     *done = 0;
     if (total == 0) { *done = 1; return TRACS_OK; }
-    static const bool off = [] { const char *e = std::getenv("TRACS_TC_GRID"); return e && std::atoi(e) == 0; }();
+    const bool off = sw::integer(sw::TRACS_TC_GRID, -1) == 0;
     if (off) return TRACS_OK;
     DeviceCall guard(stream);
     const double *lg = nullptr;

@@ -34,8 +34,7 @@ constexpr unsigned long long MASK_RANGE = 1ull << 30;      // cells per launch: 
 // TRACS_MASK_RANGE (diagnostic; tests): cells per launch instead, at most MASK_RANGE, so that small inputs cross ranges.  Read per call.
 unsigned long long mask_range()
 {
-    const char *e = std::getenv("TRACS_MASK_RANGE");
-    const unsigned long long v = e ? std::strtoull(e, nullptr, 10) : 0ull;
+    const unsigned long long v = sw::size(sw::TRACS_MASK_RANGE, 0);
     return v >= 1 && v <= MASK_RANGE ? v : MASK_RANGE;
 }
 

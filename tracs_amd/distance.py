@@ -14,7 +14,7 @@ import sys
 import time
 from datetime import date
 
-from . import _lib
+from . import _lib, switches
 from .handle import OPEN_STAGE, DistanceHandle, require_files
 from .utils import check_nearest_k, check_positive_float, check_positive_int
 
@@ -932,7 +932,7 @@ def _pairs_multi_gpu(msas, args, ctx):
     from . import device as dev
     from . import multigpu, partition
     dist, rank, world, device = ctx
-    if not args.recomb_filter and os.environ.get("TRACS_DIST_PARTITION", "sites") == "sites":
+    if not args.recomb_filter and switches.get("TRACS_DIST_PARTITION", "sites") == "sites":
         # SITE shards (the default): every rank holds 1 / P of the sites and counts all pairs over them -- every stage of the call,
         # what is built once per alignment included, works on 1 / P of the data; the sums arrive as row panels (reduce-scatter)
         aln = multigpu.site_sharded_alignment(msas, dist, rank, world, device)
@@ -947,7 +947,7 @@ def _pairs_multi_gpu(msas, args, ctx):
         return host[0], host[1], host[2], names, np.zeros(len(host[0]), np.uint64), host[3]      # filter off: `len` zeros (:452)
     # PAIR partition (with --filter: the recombination filter wants every site of a pair in one place): every rank holds the whole
     # alignment and computes its row panels
-    if os.environ.get("TRACS_DIST_PARSE_ALL"):
+    if switches.get("TRACS_DIST_PARSE_ALL"):
         aln = dev.Alignment.from_fasta(msas)              # every rank parses and packs
     else:
         aln = multigpu.shared_alignment(msas, dist, rank, world, device)      # rank 0 parses, the packed planes are broadcast
@@ -969,7 +969,7 @@ class _Stages:
     the one before it, or since the alignment's start()"""
 
     def __init__(self, lead):
-        self.on = lead and os.environ.get("TRACS_STAGE_TRACE") is not None
+        self.on = lead and switches.get("TRACS_STAGE_TRACE") is not None
         self.start()
         if self.on:
             try:
@@ -1059,7 +1059,7 @@ def distance(args):
             globals()[route[0]](msas, args, groups if args.histogram else dates, ref, stage, **ruled)      # (--histogram takes no --meta)
             logging.info(route[1], msa)
             continue
-        if ctx is None and nearest is None and os.environ.get("TRACS_DISTANCE_ARRAYS") is None:
+        if ctx is None and nearest is None and switches.get("TRACS_DISTANCE_ARRAYS") is None:
             # one GPU: the results stay on the device until the CSV rows (with --filter: the filtered distances and the transmission
             # model they drive too)
             require_files(msas)                              # (api.pairsnp_arrays's diagnosis; the reference passes a NULL gzFile on)

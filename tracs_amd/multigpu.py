@@ -15,13 +15,13 @@ import socket
 import subprocess
 import sys
 
-from . import partition
+from . import partition, switches
 
 
 def in_worker():
     """True in a process spawn() started.  The ambient WORLD_SIZE / RANK of somebody else's torchrun or SLURM job do not
     count: a plain `tracs distance` run inside such a job stays a single-GPU run."""
-    return os.environ.get("TRACS_MULTIGPU_WORKER") == "1" and int(os.environ.get("WORLD_SIZE", "1")) > 1 and "RANK" in os.environ
+    return switches.get("TRACS_MULTIGPU_WORKER") == "1" and int(os.environ.get("WORLD_SIZE", "1")) > 1 and "RANK" in os.environ
 
 
 def spawn(module, argv, gpus):

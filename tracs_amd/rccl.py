@@ -9,10 +9,9 @@ against the caller's stream with events, so an exchange enqueued with async_op=T
 The CPU tests (gloo, several ranks on one host) keep using torch.distributed itself: RCCL wants one GPU per rank.
 """
 import ctypes as C
-import os
 import pickle
 
-from . import _lib
+from . import _lib, switches
 
 
 class _Work:
@@ -235,7 +234,7 @@ class RcclDist:
 def backend_choice(world, ndev, env_name):
     """'rccl' (the library's own RCCL entry points), 'nccl' (torch.distributed over RCCL) or 'gloo': the environment variable
     `env_name` when set, else rccl when every rank has a GPU of its own, else gloo (several ranks on one GPU: tests)."""
-    v = os.environ.get(env_name)
+    v = switches.get(env_name)
     if v:
         return v
     return "rccl" if ndev >= world else "gloo"
